@@ -2,6 +2,7 @@
 """bench.py -- throughput of the barcode-correct -> UMI-dedup -> count hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--workload cfg3|cfg2|cfg4|cfg5] [--reads-per-gpu R] [--whitelist W] [--dupinfo]
+                    [--dump-outputs DIR] [--full]
 
 One process per GPU.  Under torchrun (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment) this process is one
 rank; WITHOUT them `--gpus N` (N > 1) makes this process a launcher that starts N fresh rank processes itself (before
@@ -24,6 +25,12 @@ generated on the device by the seeded integer generator of libcrgpu):
 
 C1/C2/C3 are libcrgpu's own collectives (RCCL over xGMI, csrc/comm.hip).  Weak scaling: every rank holds the same number
 of reads of ONE GEM well.  Prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (the per-family figures come from the library's
+ledger of those same steps).  `--full` adds what needs work of its own: the short loop with the library's default options
+(`default_options_ms_per_step`), and for cfg3 on one GPU the untimed full-size property checks (`verify`) and the rate
+with the host hand-over (`end_to_end`), and the CPU baseline of the oracle (`cpu_baseline`).  `--dump-outputs DIR` writes
+what rank 0's last timed step returned as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -82,7 +89,40 @@ def parse_args():
     ap.add_argument("--no-verify", action="store_true", help="skip the untimed full-size property checks (cfg3, N=1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-end-to-end", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the default-options loop, verify, end_to_end and "
+                         "the CPU baseline (each of them still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float64, seeded samples of long arrays)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_SAMPLE = 1 << 19   # elements written of a longer output array
+DUMP_SEED = 20240917
+
+
+def dump_outputs(dirname, outs):
+    """outs: name -> (1-D torch tensor, numpy dtype of its elements or None for the tensor's own).  Each array goes to
+    DIR/<name>.npy as float64 (every value is an integer below 2^53, so the conversion is exact).  An array of more than
+    DUMP_SAMPLE elements is written as its values at DUMP_SAMPLE positions drawn by a fixed seed from its length (so two
+    runs with equal lengths sample the same entries); at most 8 arrays of at most 4 MiB each keep a run's files far below
+    64 MB."""
+    import numpy as np
+    import torch
+
+    assert len(outs) <= 8
+    os.makedirs(dirname, exist_ok=True)
+    for name, (t, dtype) in outs.items():
+        n = t.numel()
+        if n > DUMP_SAMPLE:
+            pos = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLE))
+            t = t[torch.from_numpy(pos).to(t.device)]
+        a = t.cpu().numpy()
+        a = (a if dtype is None else a.view(dtype)).astype(np.float64)
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def launch_ranks(n):
@@ -539,6 +579,36 @@ def main():
         step()
     dt, ledger, result, step_marks = timed(args.steps)
 
+    if args.dump_outputs and rank == 0:
+        from cellranger_amd.pipeline import _DevView
+
+        def dev(p, count, typestr):
+            if count == 0:
+                return torch.empty(0, dtype={"<i4": torch.int32, "<i8": torch.int64}[typestr], device="cuda")
+            return torch.as_tensor(_DevView(p, (count,), typestr), device="cuda")
+
+        outs = {}
+        if workload == "cfg2":
+            outs["barcode_index"] = (dev(shard["idx"].ptr, n, "<i4"), np.uint32)
+        elif result is not None:
+            if workload == "cfg5":
+                cols = {k: result[k] for k in ("barcode_rank", "gem_group", "indptr", "indices", "data")}
+            else:
+                v = result._mv.contents
+                cols = dict(barcode_rank=dev(v.d_barcode_rank, result.n_barcodes, "<i4"),
+                            indptr=dev(v.d_indptr, result.n_barcodes + 1, "<i8"),
+                            indices=dev(v.d_indices, result.nnz, "<i4"), data=dev(v.d_data, result.nnz, "<i4"))
+            for k, t in cols.items():
+                outs[k] = (t, np.uint32 if k == "barcode_rank" else None)
+            # every matrix entry counts in one of these sums, also where indices / data are sampled
+            csum = torch.cat([torch.zeros(1, dtype=torch.int64, device=cols["data"].device), torch.cumsum(cols["data"].long(), 0)])
+            outs["column_totals"] = (csum[cols["indptr"][1:]] - csum[cols["indptr"][:-1]], np.int64)
+        if dup_out is not None:
+            for name, a, typestr in zip(("dupinfo_umi", "dupinfo_reads", "dupinfo_flags"), dup_out, ("<i4", "<i4", "|u1")):
+                outs[name] = (dev(a.ptr, n, typestr), a.dtype)
+        torch.cuda.synchronize()
+        dump_outputs(args.dump_outputs, outs)
+
     out_info = {}
     if workload in ("cfg3", "cfg4") and rank == 0 and result is not None:
         out_info = {"matrix_columns": result.n_barcodes, "matrix_nnz": result.nnz}
@@ -556,7 +626,7 @@ def main():
     # the same loop without the promise about the buffers (the default of the library): K2 scans for its misses, the sort
     # counts its digits itself.  What a default-configured host gets; `value` is the line above.
     default_ms = None
-    if not args.no_default_options:
+    if args.full and not args.no_default_options:
         ctx.trust_unchanged_buffers(False)
         if dense_keys and key_layout_args:
             ctx.set_option(1, 0)
@@ -650,13 +720,13 @@ def main():
         }
         if world > 1 and ledger.get("comm", (0, 0, 0))[1]:
             cm = ledger["comm"]
-            total_steps = args.warmup + args.steps + (0 if args.no_default_options else 1 + max(1, min(2, args.steps)))
+            total_steps = args.warmup + args.steps + (0 if default_ms is None else 1 + max(1, min(2, args.steps)))
             line["comm"] = {"ms_per_step": cm[0] / args.steps, "collectives_per_step": cm[1] / args.steps,
                             "bytes_per_step_rank0": {"C1_table_allreduce": ctx.stat(5) / total_steps, "C2_key_exchange": ctx.stat(6) / total_steps,
                                                      "C3_triplet_gather": ctx.stat(7) / total_steps},
                             "note": "rank 0's C1 / C2 / C3 spans incl. waiting for the other ranks (HIP events around each collective); "
                                     "bytes = what rank 0 put into each collective per step (C2: its keys, own share included)"}
-        if world == 1 and workload == "cfg3" and not args.no_verify and dup_out is None:
+        if args.full and world == 1 and workload == "cfg3" and not args.no_verify and dup_out is None:
             # not timed: the laws of cellranger_amd/selfcheck.py on this very workload at its full size
             from cellranger_amd import selfcheck
             try:
@@ -664,17 +734,17 @@ def main():
             except AssertionError as e:  # report, never hide: the line still carries the timing
                 import traceback
                 line["verify"] = {"ok": False, "failed": traceback.format_exc(limit=2).strip().splitlines()[-3:], "msg": str(e)}
-        if world == 1 and workload == "cfg3" and not args.no_end_to_end:
+        if args.full and world == 1 and workload == "cfg3" and not args.no_end_to_end:
             be.reset()
             try:
                 k1_ms = ledger.get("match", (0.0, 0, 0))[0] / args.steps
                 line["end_to_end"] = end_to_end(ctx, w, n, ms_per_step * 1e-3, k1_ms * 1e-3, 32_000_000)
             except Exception as e:  # noqa: BLE001 - an extra figure must never cost the line
                 line["end_to_end"] = {"error": repr(e)}
-        if world == 1 and not args.no_cpu_baseline and workload != "cfg4":
+        if args.full and world == 1 and not args.no_cpu_baseline and workload != "cfg4":
             line["cpu_baseline"] = cpu_baseline(w, "cfg2" if workload == "cfg2" else "cfg3", min(args.cpu_sample, n),
                                                 min(args.cpu_1thread_sample, n))
-        elif world == 1 and not args.no_cpu_baseline:
+        elif args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline_cfg4(cfg4, min(args.cpu_sample // 4, cfg4.n_fb))
         print(json.dumps(line))
         sys.stdout.flush()

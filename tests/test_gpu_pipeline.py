@@ -374,3 +374,41 @@ def test_a_rank_that_fails_in_front_of_the_key_exchange_fails_everywhere(dupinfo
     _check_against_oracle(c0, w, r_all, m0)
     for c, _ in results:
         c.close()
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """bench.py without --full prints the headline line only; --dump-outputs writes the last timed step's outputs as
+    float64 .npy files that two runs with the same arguments reproduce, and the DupInfo path's matrix equals the
+    keys-only path's on the same reads."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+
+    def run(tag, *extra):
+        out = tmp_path / tag
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                            "--reads-per-gpu", "4000000", "--dump-outputs", str(out)] + list(extra),
+                           env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        files = {p.stem: np.load(p) for p in sorted(out.glob("*.npy"))}
+        assert sum(p.stat().st_size for p in out.glob("*.npy")) <= 64_000_000
+        return line, files
+
+    line, a = run("a")
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["output"]["matrix_nnz"] > 1000
+    assert not {"cpu_baseline", "verify", "end_to_end"} & set(line) and line["default_options_ms_per_step"] is None
+    assert set(a) == {"barcode_rank", "indptr", "indices", "data", "column_totals"}
+    assert all(x.dtype == np.float64 for x in a.values())
+    assert len(a["barcode_rank"]) == line["output"]["matrix_columns"] and a["indptr"][-1] == line["output"]["matrix_nnz"]
+    assert len(a["data"]) == min(line["output"]["matrix_nnz"], 1 << 19) and len(a["indices"]) == len(a["data"])
+    assert (a["data"] >= 1).all() and (a["column_totals"] >= np.diff(a["indptr"])).all()
+    _, b = run("b")
+    assert set(b) == set(a) and all(np.array_equal(a[k], b[k]) for k in a)
+    _, d = run("d", "--dupinfo")
+    assert set(d) == set(a) | {"dupinfo_umi", "dupinfo_reads", "dupinfo_flags"}
+    assert all(np.array_equal(a[k], d[k]) for k in a)
+    assert d["dupinfo_reads"].max() >= 1
