@@ -564,6 +564,21 @@ __device__ __forceinline__ uint32_t hot_probe_slot(const unsigned long long *s_h
     slot = s;
     return r;
 }
+// the same for a table whose rank words carry a hit counter above bit `shift` (LH_HOTCNT): the ranks are compared masked.
+// An empty slot's word masks to rank_mask, which is never a rank (rank_mask >= n_canon), so a real entry still wins.
+__device__ __forceinline__ uint32_t hot_probe_cnt(const unsigned long long *s_hot, uint32_t key, uint32_t rank_mask,
+                                                  uint32_t &slot) {
+    const uint32_t b0 = hot_hash(key), b1 = (b0 + 1u) & (HOT_BUCKETS - 1u);
+    const uint4 x = *reinterpret_cast<const uint4 *>(s_hot + 2u * b0);
+    const uint4 y = *reinterpret_cast<const uint4 *>(s_hot + 2u * b1);
+    uint32_t r = rank_mask, s = 0xFFFFu;
+    if (x.x == key && (x.y & rank_mask) < r) { r = x.y & rank_mask; s = 2u * b0; }
+    if (x.z == key && (x.w & rank_mask) < r) { r = x.w & rank_mask; s = 2u * b0 + 1u; }
+    if (y.x == key && (y.y & rank_mask) < r) { r = y.y & rank_mask; s = 2u * b1; }
+    if (y.z == key && (y.w & rank_mask) < r) { r = y.w & rank_mask; s = 2u * b1 + 1u; }
+    slot = s;
+    return r < rank_mask ? r : CRGPU_MISS;
+}
 // monotone bucketing of a count >= 1 into 256 classes (8 per octave)
 __device__ __forceinline__ uint32_t hot_class(uint32_t c) {
     const uint32_t e = 31u - (uint32_t)__clz((int)c);
@@ -652,9 +667,27 @@ __global__ __launch_bounds__(256) void k_hot_build(const uint32_t *__restrict__ 
 //   Opt-in (CRGPU_K1_MODE=count), measured SLOWER at 1 B reads: pass A 8.05 -> 9.05 ms on the 737 K list, 12.0 -> 12.65 on the
 //   6.8 M one, cfg2 0.93 -> 1.13 -- the rank gather (64 different lines of the image per wave instruction) costs the lookup
 //   more than the staging it saves; profiles/r03_count_stage_and_sort_ab.txt.
+// MODE 3 (LH_HOTCNT, the default of the table rounds): the table keeps its 8-byte entries and counts the hits it answers in
+//   the free high bits of each entry's rank word (ranks need `cnt_shift` bits; the field above them starts at zero, the
+//   image's high rank bits being zero).  A hit adds 1 << cnt_shift to its word with an LDS atomic and still reads its rank
+//   from LDS; nothing per read goes out but idx.  The lane whose returned old value shows a full field (all ones) lets it
+//   wrap to zero -- the carry leaves bit 31, the rank bits below never change -- and adds the 2^(32 - cnt_shift) hits the
+//   wrap dropped to VALID with one device atomic: every hit is in exactly one of the wraps or the final field.  When the
+//   workgroup ends, the fields go to VALID (flush below).  Cold hits go to the per-wave regions as in MODE 1; a full region
+//   counts its surplus hits with device atomics, so no round needs a fallback.  The regions are not cleared: k_stage_idx
+//   reads the ranks each one holds (cold_count), and for k_match_binned every wave closes its region with CRGPU_MISS.
 #define LH_FULL 0
 #define LH_SPLIT 1
 #define LH_COUNT 2
+#define LH_HOTCNT 3
+// Flush of the LH_HOTCNT fields at the end of a workgroup: each workgroup writes its 16384 fields as one coalesced row of
+// a slot image and k_hot_flush adds the column sums to VALID (one atomic per non-empty slot and row slice).  One device
+// atomic into VALID per non-zero field and workgroup instead (up to 256 x 8192 per round on the same 8192 addresses) was
+// measured 0.05 ms per 1 B reads slower (profiles/r04_k1_hotcnt_ab.txt).
+#define HC_MAX_RANK_BITS 24u  // LH_HOTCNT needs at least 8 bits of counter field
+#ifndef HC_GROUP
+#define HC_GROUP 4            // LH_HOTCNT: reads probed together before their atomics
+#endif
 // 4-byte-key table: slot of `key` or 0xFFFF.  An empty slot holds 0xFFFFFFFF, so the all-T barcode is never cached (cold path).
 __device__ __forceinline__ uint32_t hot_probe_keys(const uint32_t *s_key, uint32_t key) {
     const uint32_t b0 = hot_hash(key), b1 = (b0 + 1u) & (HOT_BUCKETS - 1u);
@@ -677,15 +710,22 @@ __global__ __launch_bounds__(LH_THREADS) void k_lookup_hot(const WlViewSet vs,
                                                            uint32_t rec_cap, uint32_t rec_regions, uint32_t i_offset,
                                                            uint16_t *__restrict__ hot_slot_out, uint32_t *__restrict__ cold_rank,
                                                            uint32_t *__restrict__ cold_count, uint32_t cold_cap,
-                                                           uint32_t cold_regions) {
+                                                           uint32_t cold_regions, uint32_t cnt_shift = 0u,
+                                                           uint32_t *__restrict__ cnt_image = nullptr, bool cold_fill = false) {
     // hot_slot_out / cold_rank (both or neither): the histogram's inputs.  A hit answered by the LDS table is recorded as
     // the table slot that answered (2 bytes per read, 0xFFFF otherwise) and counted later in LDS by k_hist_hot_slots; a hit
     // found in the global tables is appended to this wave's region of cold_rank (no atomics, cursor in a register) and goes
     // through the staged histogram -- 15 % of the reads instead of all of them.
+    // cnt_shift / cnt_image (LH_HOTCNT): rank bits of the table's rank words / the slot image of the flush (rows of
+    // HOT_SLOTS fields, one per workgroup).  cold_fill (LH_HOTCNT): close every region with CRGPU_MISS behind its ranks,
+    // for a staging kernel that reads whole regions; without it only cold_count tells how many ranks a region holds.
     extern __shared__ __attribute__((aligned(16))) unsigned long long s_hot[];  // HOT_SLOTS, then the cold queues
     uint32_t *s_queue = reinterpret_cast<uint32_t *>(s_hot + HOT_SLOTS);          // LH_THREADS / 64 queues of LH_QUEUE
-    constexpr bool SPLIT = MODE == LH_SPLIT, COUNT = MODE == LH_COUNT, COLD = MODE != LH_FULL;
+    constexpr bool SPLIT = MODE == LH_SPLIT, COUNT = MODE == LH_COUNT, HOTCNT = MODE == LH_HOTCNT, COLD = MODE != LH_FULL;
     uint32_t *s_key = reinterpret_cast<uint32_t *>(s_hot), *s_cnt = s_key + HOT_SLOTS;  // COUNT: keys, then one counter per slot
+    // HOTCNT: the rank word of slot s is s_key[2 s + 1]; its field counts up to cnt_max and then wraps
+    const uint32_t rank_mask = HOTCNT ? (1u << cnt_shift) - 1u : CRGPU_MISS;
+    const uint32_t cnt_max = HOTCNT ? 0xFFFFFFFFu >> cnt_shift : 0u;
     const uint32_t *__restrict__ hot_words = reinterpret_cast<const uint32_t *>(hot_image);  // [2 s] key, [2 s + 1] rank of slot s
     const uint32_t tid = threadIdx.x;
     const WlView &w = vs.v[0];
@@ -745,6 +785,29 @@ __global__ __launch_bounds__(LH_THREADS) void k_lookup_hot(const WlViewSet vs,
                     todo[j] = false;
                     atomicAdd(&s_cnt[hslot[j]], 1u);
                 }
+        } else if (HOTCNT) {
+            // HC_GROUP reads at a time: their probes issued together, then their (independent) LDS atomics -- all eight
+            // probes in flight at once would hold 64 VGPRs of entries beside the atomics' return values and spill
+#pragma unroll
+            for (int h = 0; h < LH_ITEMS; h += HC_GROUP) {
+#pragma unroll
+                for (int j = h; j < h + HC_GROUP; j++) {
+                    uint32_t sl = 0xFFFFu;
+                    const uint32_t r = hot_probe_cnt(s_hot, key[j], rank_mask, sl);
+                    hslot[j] = 0xFFFFu;
+                    if (todo[j] && r != CRGPU_MISS) {
+                        rank[j] = r;
+                        todo[j] = false;
+                        hslot[j] = sl;
+                    }
+                }
+#pragma unroll
+                for (int j = h; j < h + HC_GROUP; j++)
+                    if (hslot[j] != 0xFFFFu) {
+                        const uint32_t old = atomicAdd(&s_key[2u * hslot[j] + 1u], 1u << cnt_shift);
+                        if ((old >> cnt_shift) == cnt_max) atomicAdd(&w.valid[rank[j]], cnt_max + 1u);  // the field wrapped
+                    }
+            }
         } else {
 #pragma unroll
         for (int j = 0; j < LH_ITEMS; j++) {
@@ -817,7 +880,7 @@ __global__ __launch_bounds__(LH_THREADS) void k_lookup_hot(const WlViewSet vs,
                     const unsigned long long cm = __ballot(found != CRGPU_MISS);
                     const uint32_t pos = cold_cur + __builtin_amdgcn_mbcnt_hi((uint32_t)(cm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cm, 0u));
                     if (found != CRGPU_MISS && pos < cold_cap) cold_rank[(uint64_t)region * cold_cap + pos] = found;
-                    if (COUNT && found != CRGPU_MISS && pos >= cold_cap) atomicAdd(&w.valid[found], 1u);  // region full: counted here
+                    if ((COUNT || HOTCNT) && found != CRGPU_MISS && pos >= cold_cap) atomicAdd(&w.valid[found], 1u);  // region full: counted here
                     cold_cur += (uint32_t)__popcll(cm);
                 }
             }
@@ -861,6 +924,33 @@ __global__ __launch_bounds__(LH_THREADS) void k_lookup_hot(const WlViewSet vs,
             if (c) atomicAdd(&w.valid[hot_words[2u * s + 1u]], c);
         }
     }
+    if (HOTCNT) {
+        if (cold_fill) {  // the rest of this wave's region reads as CRGPU_MISS (the regions are not cleared beforehand)
+            const uint64_t rbase = (uint64_t)region * cold_cap;
+            for (uint32_t p = (cold_cur < cold_cap ? cold_cur : cold_cap) + (tid & 63u); p < cold_cap; p += 64u)
+                cold_rank[rbase + p] = CRGPU_MISS;
+        }
+        if ((tid & 63u) == 0u) cold_count[region] = cold_cur < cold_cap ? cold_cur : cold_cap;
+        __syncthreads();  // every hit of the workgroup is in its field
+        for (uint32_t s = tid; s < HOT_SLOTS; s += LH_THREADS) {
+            // an empty slot's word is all ones: its "field" is not a count (its masked rank, rank_mask, is never a rank)
+            const uint32_t word = s_key[2u * s + 1u], c = (word & rank_mask) != rank_mask ? word >> cnt_shift : 0u;
+            cnt_image[(uint64_t)blockIdx.x * HOT_SLOTS + s] = c;
+        }
+    }
+}
+
+// LH_HOTCNT flush: column sums of the slot image (rows = the lookup's workgroups) into VALID.  blockIdx.y takes every
+// gridDim.y-th row, so that the 16384 columns are summed by enough workgroups to keep the loads in flight.
+__global__ __launch_bounds__(256) void k_hot_flush(const uint32_t *__restrict__ cnt_image, uint32_t rows,
+                                                   const unsigned long long *__restrict__ hot_image, uint32_t *__restrict__ valid) {
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    if (s >= HOT_SLOTS) return;
+    uint32_t c = 0;
+#pragma unroll 4
+    for (uint32_t g = blockIdx.y; g < rows; g += gridDim.y) c += cnt_image[(uint64_t)g * HOT_SLOTS + s];
+    const uint32_t rank = (uint32_t)(hot_image[s] >> 32);
+    if (c && rank != CRGPU_MISS) atomicAdd(&valid[rank], c);  // (only a slot that holds an entry has hits)
 }
 
 // Histogram of the hits the LDS table answered: 16384 counters (one per table slot) in LDS, the slot stream read with
@@ -913,9 +1003,13 @@ __global__ __launch_bounds__(256) void k_hist_ranks_atomic(const uint32_t *__res
 #endif
 #define SI_TILE (256 * SI_ITEMS)
 #define SI_MISS_BUCKET 31u
+// region_fill (nullable): idx is a row of n / region_cap regions of region_cap entries, of which region q holds
+// region_fill[q] ranks at its start and nothing worth reading behind them (LH_HOTCNT's cold regions: the rest is never
+// written).  Tiles are then cut per region, and a tile beyond its region's ranks is skipped whole.
 __global__ __launch_bounds__(256) void k_stage_idx(const BinPlan plan, const uint32_t *__restrict__ idx, uint64_t n,
                                                    uint16_t *__restrict__ stage, uint32_t *__restrict__ cursor,
-                                                   const uint32_t *__restrict__ skip_if = nullptr) {
+                                                   const uint32_t *__restrict__ skip_if = nullptr,
+                                                   const uint32_t *__restrict__ region_fill = nullptr, uint32_t region_cap = 0u) {
     __shared__ uint32_t wcount[4][32];  // per-wave bucket counts -> tile-local start of (wave, bucket)
     __shared__ uint32_t gbase[32];      // global base of the tile's run of each bucket
     __shared__ uint32_t tstart[32];     // tile-local start of each bucket
@@ -924,18 +1018,27 @@ __global__ __launch_bounds__(256) void k_stage_idx(const BinPlan plan, const uin
     __shared__ uint32_t tile_hits;
     if (skip_if && *skip_if) return;
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint64_t n_tiles = (n + SI_TILE - 1) / SI_TILE;
+    const uint64_t tiles_per_region = region_fill ? (region_cap + SI_TILE - 1) / SI_TILE : 0;
+    const uint64_t n_tiles = region_fill ? n / region_cap * tiles_per_region : (n + SI_TILE - 1) / SI_TILE;
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        uint64_t first = tile * SI_TILE, end = n;  // the tile's entries: [first, min(first + SI_TILE, end))
+        if (region_fill) {
+            const uint64_t q = tile / tiles_per_region, t = tile - q * tiles_per_region;
+            const uint32_t fill = region_fill[q];
+            if (t * SI_TILE >= fill) continue;  // the same for the whole workgroup (the last iteration ended in a barrier)
+            first = q * region_cap + t * SI_TILE;
+            end = q * region_cap + fill;
+        }
         if (tid < 128) wcount[tid >> 5][tid & 31u] = 0;
         __syncthreads();
         uint32_t dr[SI_ITEMS];  // (bucket << 16) | rank inside (wave, bucket)
         uint16_t v[SI_ITEMS];
-        const uint64_t wave_base = tile * SI_TILE + (uint64_t)wave * (64 * SI_ITEMS) + lane;  // wave-major order
+        const uint64_t wave_base = first + (uint64_t)wave * (64 * SI_ITEMS) + lane;  // wave-major order
         uint32_t r[SI_ITEMS];
 #pragma unroll
         for (int j = 0; j < SI_ITEMS; j++) {
             const uint64_t i = wave_base + (uint64_t)j * 64;
-            r[j] = i < n ? idx[i] : CRGPU_MISS;
+            r[j] = i < end ? idx[i] : CRGPU_MISS;
         }
 #pragma unroll
         for (int j = 0; j < SI_ITEMS; j++) {
@@ -1195,31 +1298,38 @@ extern "C" int crgpu_match_and_count_dev(crgpu_ctx *ctx, const uint32_t *d_cb, c
         cr_allow_lds(ctx, (const void *)k_lookup_hot<LH_FULL>, lookup_lds);
         cr_allow_lds(ctx, (const void *)k_lookup_hot<LH_SPLIT>, lookup_lds);
         cr_allow_lds(ctx, (const void *)k_lookup_hot<LH_COUNT>, lookup_lds);
+        cr_allow_lds(ctx, (const void *)k_lookup_hot<LH_HOTCNT>, lookup_lds);
     }
     hipError_t e = hipSuccess;
     bool hot_ready = false;
     // Split histogram of the table rounds (k_lookup_hot's comment): hits the table answers are counted per table slot in
     // LDS, the others are appended to per-wave regions and staged -- a sixth of the entries the staging used to see, so the
     // rounds can be that much longer.  Sized after the sampling batch from the share of the reads the table's barcodes
-    // carry; a region that overflows makes its round fall back to device atomics (cold_count[regions] != 0).
+    // carry.  A region that overflows: LH_SPLIT makes its round fall back to device atomics (cold_count[regions] != 0),
+    // LH_HOTCNT and LH_COUNT count the surplus hits with device atomics in the lookup.
     const uint32_t cold_regions = 256u * (LH_THREADS / 64);
     uint16_t *d_hot_slot = nullptr;
-    uint32_t *d_cold = nullptr, *d_cold_count = nullptr;
+    uint32_t *d_cold = nullptr, *d_cold_count = nullptr, *d_cnt_image = nullptr;
     uint64_t hot_round = 0;   // reads per table round (0: the split histogram is off)
     uint32_t cold_cap = 0;
+    int table_mode = LH_FULL;  // k_lookup_hot's MODE in the table rounds
+    // LH_HOTCNT: the rank bits of the table's rank words, so that rank_mask = 2^bits - 1 >= n_canon is never a rank
+    uint32_t cnt_shift = 1;
+    while (cnt_shift < 32u && (1ull << cnt_shift) <= ctx->n_canon) cnt_shift++;
     // CRGPU_K1_MODE=count: table hits counted inside the lookup kernel (LH_COUNT); =split / =full: the other two
     const char *k1_mode = getenv("CRGPU_K1_MODE");
     const bool count_mode = k1_mode && strcmp(k1_mode, "count") == 0;
     struct ColdRelease {
         crgpu_ctx *c;
         uint16_t *&a;
-        uint32_t *&b, *&d;
+        uint32_t *&b, *&d, *&f;
         ~ColdRelease() {
             cr_pool_free(c, a);
             cr_pool_free(c, b);
             cr_pool_free(c, d);
+            cr_pool_free(c, f);
         }
-    } cold_release{ctx, d_hot_slot, d_cold, d_cold_count};
+    } cold_release{ctx, d_hot_slot, d_cold, d_cold_count, d_cnt_image};
     for (uint64_t off = 0; off < n && e == hipSuccess;) {
         uint64_t m = n - off < sb ? n - off : sb;
         if (use_hot && off == 0 && m > first) m = first;
@@ -1229,33 +1339,51 @@ extern "C" int crgpu_match_and_count_dev(crgpu_ctx *ctx, const uint32_t *d_cb, c
             e = hipMemsetAsync(d_cursor, 0, plan.n_buckets * MB_CURSOR_STRIDE * sizeof(uint32_t), ctx->stream);
             if (hot_ready && hot_round) {
                 ctx->k1_split_rounds++;
-                const uint64_t C = (uint64_t)cold_regions * cold_cap;
+                const uint32_t lh_grid = cr_grid((m + MB_TILE - 1) / MB_TILE, 1, 256u);
+                uint64_t C = (uint64_t)cold_regions * cold_cap;
                 const uint32_t *d_over = d_cold_count + cold_regions;  // != 0 after the lookup: a cold region overflowed
                 if (e == hipSuccess) e = hipMemsetAsync(d_cold_count, 0, (cold_regions + 1) * sizeof(uint32_t), ctx->stream);
-                if (e == hipSuccess) e = hipMemsetAsync(d_cold, 0xFF, C * sizeof(uint32_t), ctx->stream);
-                if (count_mode) {
-                    d_over = nullptr;  // nothing to fall back to: a full region counts its surplus hits itself
-                    hipLaunchKernelGGL(k_lookup_hot<LH_COUNT>, dim3(cr_grid((m + MB_TILE - 1) / MB_TILE, 1, 256u)), dim3(LH_THREADS),
-                                       lookup_lds, ctx->stream, vs, ctx->d_hot_image, d_cb + off, d_flags ? d_flags + off : nullptr, m,
-                                       d_idx_out + off, rec.valid ? rec.d_i : nullptr, rec.d_key, rec.d_fl, rec.d_count, rec.cap,
-                                       rec.regions, (uint32_t)off, (uint16_t *)nullptr, d_cold, d_cold_count, cold_cap, cold_regions);
+                if (table_mode == LH_HOTCNT) {
+                    // the regions of the launched waves; k_stage_idx reads the ranks each holds (cold_count), k_match_binned
+                    // whole regions, which their waves close with CRGPU_MISS; no fallback round
+                    C = (uint64_t)lh_grid * (LH_THREADS / 64) * cold_cap;
+                    d_over = nullptr;
+                    hipLaunchKernelGGL(k_lookup_hot<LH_HOTCNT>, dim3(lh_grid), dim3(LH_THREADS), lookup_lds, ctx->stream, vs,
+                                       ctx->d_hot_image, d_cb + off, d_flags ? d_flags + off : nullptr, m, d_idx_out + off,
+                                       rec.valid ? rec.d_i : nullptr, rec.d_key, rec.d_fl, rec.d_count, rec.cap, rec.regions,
+                                       (uint32_t)off, (uint16_t *)nullptr, d_cold, d_cold_count, cold_cap, cold_regions, cnt_shift,
+                                       d_cnt_image, plan.n_buckets > SI_MISS_BUCKET);
+                    hipLaunchKernelGGL(k_hot_flush, dim3(HOT_SLOTS / 256u, 8), dim3(256), 0, ctx->stream, d_cnt_image, lh_grid,
+                                       ctx->d_hot_image, uw.d_valid);
                 } else {
-                hipLaunchKernelGGL(k_lookup_hot<LH_SPLIT>, dim3(cr_grid((m + MB_TILE - 1) / MB_TILE, 1, 256u)), dim3(LH_THREADS), lookup_lds,
-                                   ctx->stream, vs, ctx->d_hot_image, d_cb + off, d_flags ? d_flags + off : nullptr, m,
-                                   d_idx_out + off, rec.valid ? rec.d_i : nullptr, rec.d_key, rec.d_fl, rec.d_count, rec.cap,
-                                   rec.regions, (uint32_t)off, d_hot_slot, d_cold, d_cold_count, cold_cap, cold_regions);
-                const uint64_t lh_chunk = (uint64_t)LH_THREADS * LH_ITEMS;
-                hipLaunchKernelGGL(k_hist_hot_slots, dim3(128), dim3(HH_THREADS), HOT_SLOTS * sizeof(uint32_t), ctx->stream, d_hot_slot,
-                                   (m + lh_chunk - 1) / lh_chunk * LH_THREADS, ctx->d_hot_image, uw.d_valid, d_over);
+                    if (e == hipSuccess) e = hipMemsetAsync(d_cold, 0xFF, C * sizeof(uint32_t), ctx->stream);
+                    if (table_mode == LH_COUNT) {
+                        d_over = nullptr;  // nothing to fall back to: a full region counts its surplus hits itself
+                        hipLaunchKernelGGL(k_lookup_hot<LH_COUNT>, dim3(lh_grid), dim3(LH_THREADS), lookup_lds, ctx->stream, vs,
+                                           ctx->d_hot_image, d_cb + off, d_flags ? d_flags + off : nullptr, m, d_idx_out + off,
+                                           rec.valid ? rec.d_i : nullptr, rec.d_key, rec.d_fl, rec.d_count, rec.cap, rec.regions,
+                                           (uint32_t)off, (uint16_t *)nullptr, d_cold, d_cold_count, cold_cap, cold_regions, 0u,
+                                           (uint32_t *)nullptr);
+                    } else {
+                        hipLaunchKernelGGL(k_lookup_hot<LH_SPLIT>, dim3(lh_grid), dim3(LH_THREADS), lookup_lds, ctx->stream, vs,
+                                           ctx->d_hot_image, d_cb + off, d_flags ? d_flags + off : nullptr, m, d_idx_out + off,
+                                           rec.valid ? rec.d_i : nullptr, rec.d_key, rec.d_fl, rec.d_count, rec.cap, rec.regions,
+                                           (uint32_t)off, d_hot_slot, d_cold, d_cold_count, cold_cap, cold_regions, 0u,
+                                           (uint32_t *)nullptr);
+                        const uint64_t lh_chunk = (uint64_t)LH_THREADS * LH_ITEMS;
+                        hipLaunchKernelGGL(k_hist_hot_slots, dim3(128), dim3(HH_THREADS), HOT_SLOTS * sizeof(uint32_t), ctx->stream,
+                                           d_hot_slot, (m + lh_chunk - 1) / lh_chunk * LH_THREADS, ctx->d_hot_image, uw.d_valid, d_over);
+                    }
                 }
                 if (plan.n_buckets <= SI_MISS_BUCKET)
                     hipLaunchKernelGGL(k_stage_idx, dim3(cr_grid((C + SI_TILE - 1) / SI_TILE, 1, 256u * 6u)), dim3(256), 0, ctx->stream,
-                                       plan, d_cold, C, d_stage, d_cursor, d_over);
+                                       plan, d_cold, C, d_stage, d_cursor, d_over,
+                                       table_mode == LH_HOTCNT ? (const uint32_t *)d_cold_count : nullptr, cold_cap);
                 else
                     hipLaunchKernelGGL((k_match_binned<true, true>), dim3(cr_grid((C + MB_ITEMS - 1) / MB_ITEMS, 256, 256u * 6u)),
                                        dim3(256), 0, ctx->stream, vs, plan, (const uint32_t *)nullptr, (const uint8_t *)nullptr, C, d_cold,
                                        d_stage, d_cursor, d_over);
-                if (!count_mode)
+                if (table_mode == LH_SPLIT)
                     hipLaunchKernelGGL(k_hist_ranks_atomic, dim3(cr_grid(m, 256)), dim3(256), 0, ctx->stream, d_idx_out + off, m, uw.d_valid,
                                        d_over);
                 if (getenv("CRGPU_K1_DEBUG")) {
@@ -1307,12 +1435,19 @@ extern "C" int crgpu_match_and_count_dev(crgpu_ctx *ctx, const uint32_t *d_cb, c
                 hot_ready = true;
                 // share of the hits that the table will not answer (one read-back per call) -> size of the cold regions
                 unsigned long long sums[2] = {0, 0};
-                // Where it pays (measured, profiles/r02_k1_split_ab.txt): whitelists beyond the 31 buckets of k_stage_idx (the
-                // 6.8 M-entry list: 208 buckets, 49 staging rounds) -4 ms per 1 B reads; on the 737 K list the 2 bytes per read
-                // of the slot stream cost the lookup what the shorter staging saves (8.05 against 8.07 ms) and 100 M-read calls
-                // lose 5 %.  CRGPU_K1_SPLIT=1 / 0 forces it on / off.
+                // The default is LH_HOTCNT (hit counters in the table entries) on every list whose ranks leave it 8 bits of
+                // field.  LH_SPLIT (slot stream) pays only beyond the 31 buckets of k_stage_idx (profiles/r02_k1_split_ab.txt:
+                // -4 ms per 1 B reads on the 6.8 M-entry list, a wash on the 737 K one); it is the default where LH_HOTCNT
+                // cannot run.  CRGPU_K1_SPLIT=1 forces LH_SPLIT, =0 the full staging of every round.
                 const char *split_env = getenv("CRGPU_K1_SPLIT");
-                const bool want_split = count_mode || (split_env ? split_env[0] != '0' : plan.n_buckets > SI_MISS_BUCKET);
+                int mode = LH_FULL;
+                if (count_mode)
+                    mode = LH_COUNT;
+                else if (split_env)
+                    mode = split_env[0] != '0' ? LH_SPLIT : LH_FULL;
+                else
+                    mode = cnt_shift <= HC_MAX_RANK_BITS ? LH_HOTCNT : plan.n_buckets > SI_MISS_BUCKET ? LH_SPLIT : LH_FULL;
+                const bool want_split = mode != LH_FULL;
                 if (e == hipSuccess && want_split && !getenv("CRGPU_K1_FULL_STAGING") &&
                     hipMemcpyAsync(sums, d_sums, sizeof(sums), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
                     hipStreamSynchronize(ctx->stream) == hipSuccess && sums[0] > 0) {
@@ -1333,13 +1468,16 @@ extern "C" int crgpu_match_and_count_dev(crgpu_ctx *ctx, const uint32_t *d_cb, c
                         if (const char *env = getenv("CRGPU_COLD_CAP")) cap = strtoull(env, nullptr, 10);  // tests: force the overflow fallback
                         if ((round >= sb || round >= (n - first) / MB_TILE * MB_TILE) && round > 0 && cap * cold_regions <= plan.cap) {
                             const uint64_t lh_chunk = (uint64_t)LH_THREADS * LH_ITEMS;
-                            int rr = count_mode ? CRGPU_OK
+                            int rr = mode != LH_SPLIT ? CRGPU_OK
                                                 : cr_pool_alloc(ctx, (void **)&d_hot_slot, (round + lh_chunk) / lh_chunk * lh_chunk * sizeof(uint16_t));
+                            if (rr == CRGPU_OK && mode == LH_HOTCNT)  // the flush image: one row of fields per workgroup
+                                rr = cr_pool_alloc(ctx, (void **)&d_cnt_image, 256u * HOT_SLOTS * sizeof(uint32_t));
                             if (rr == CRGPU_OK) rr = cr_pool_alloc(ctx, (void **)&d_cold, cap * cold_regions * sizeof(uint32_t));
                             if (rr == CRGPU_OK) rr = cr_pool_alloc(ctx, (void **)&d_cold_count, (cold_regions + 1) * sizeof(uint32_t));
                             if (rr == CRGPU_OK) {
                                 hot_round = round;
                                 cold_cap = (uint32_t)cap;
+                                table_mode = mode;
                                 cr_allow_lds(ctx, (const void *)k_hist_hot_slots, HOT_SLOTS * sizeof(uint32_t));
                             }  // else: not fatal, the rounds are staged in full as before
                         }
