@@ -143,6 +143,10 @@ SYMBOLS = {
     "crgpu_abi_layout": (_i, [C.c_char_p, _vp, _u32]),
     "crgpu_count_host": (_i, [_vp, C.POINTER(Records), _u32, C.POINTER(C.POINTER(MatrixView)), _vp, C.POINTER(_vp)]),
     "crgpu_counts_probe_idx": (_i, [_vp, _vp, _vp]),
+    "crgpu_counts_probe_triplets_dev": (_i, [_vp, _vp, _u32, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_u64)]),
+    "crgpu_counts_probe_triplets": (_i, [_vp, _vp, _u32, _vp, _vp, _vp, C.POINTER(_u64)]),
+    "crgpu_assemble_probe_matrix_dev": (_i, [_vp, _vp, _u32, _vp, _u64, C.POINTER(C.POINTER(MatrixDevView))]),
+    "crgpu_probe_metrics_dev": (_i, [_vp, _vp, _u32, _vp, _u64, _vp, _vp]),
     "crgpu_get_unique_id": (_i, [_vp]),
     "crgpu_local_group_id": (_i, [_u32, _vp]),
     "crgpu_create": (_i, [C.POINTER(_vp), _i, _i, _i, _vp]),

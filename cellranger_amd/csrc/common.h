@@ -211,6 +211,8 @@ struct crgpu_ctx {
     uint64_t feature_reads_requeued = 0;   // reads k_extract_features handed to the wide-map launch
     uint64_t comm_bytes[3] = {0, 0, 0};    // bytes this rank put into C1 (table all-reduce), C2 (key exchange), C3 (triplet gather)
     uint64_t sort_fallbacks = 0;           // sorts whose look-back watchdog fired and that were finished by the classic passes
+    uint64_t probe_segments[3] = {0, 0, 0};  // barcode segments the last probe-triplet computation ordered per wave / per workgroup / by the global sort
+    uint32_t probe_seg_cap = 0xFFFFFFFFu;  // CRGPU_PROBE_SEG_CAP (tests, read at create): largest segment the LDS classes take
 
     double max_expected_errors = 1.7976931348623157e308;  // corrector.rs:104 (f64::MAX)
     double confidence_threshold = 0.975;                   // corrector.rs:83

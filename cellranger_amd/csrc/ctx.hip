@@ -156,6 +156,7 @@ extern "C" int crgpu_create(crgpu_ctx **out, int device_id, int n_ranks, int ran
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && total_b) ctx->pool_budget = (uint64_t)total_b / 2;
     }
+    if (const char *cap = getenv("CRGPU_PROBE_SEG_CAP")) ctx->probe_seg_cap = (uint32_t)strtoul(cap, nullptr, 10);  // tests: force the global route
     // probability(q) = 10^(-(q-33)/10) computed on the HOST with libm pow, exactly as the
     // reference does per call (corrector.rs:167-171), for every 7-bit quality character.
     double ptab[128];
@@ -243,6 +244,11 @@ extern "C" int crgpu_get_stat(crgpu_ctx *ctx, int which, uint64_t *value_out) {
             return CRGPU_OK;
         case CRGPU_STAT_FEATURE_READS_REQUEUED:
             *value_out = ctx->feature_reads_requeued;
+            return CRGPU_OK;
+        case CRGPU_STAT_PROBE_SEGMENTS_WAVE:
+        case CRGPU_STAT_PROBE_SEGMENTS_WORKGROUP:
+        case CRGPU_STAT_PROBE_SEGMENTS_GLOBAL:
+            *value_out = ctx->probe_segments[which - CRGPU_STAT_PROBE_SEGMENTS_WAVE];
             return CRGPU_OK;
         default:
             return cr_fail(ctx, CRGPU_EINVAL, "crgpu_get_stat: unknown counter %d", which);

@@ -39,6 +39,11 @@ struct crgpu_counts {
     uint32_t n_back = 0;
     uint32_t n_canon = 0;
     KeyLayout layout;
+    // (barcode rank, probe_idx, umi_count) triplets, made on the first request (probe_counts.h) for pt_n_probes probes
+    bool pt_valid = false;
+    uint32_t pt_n_probes = 0;
+    uint64_t n_pt = 0;
+    uint32_t *d_pt_bc = nullptr, *d_pt_probe = nullptr, *d_pt_count = nullptr;
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -3197,6 +3202,9 @@ extern "C" void crgpu_counts_free(crgpu_ctx *ctx, crgpu_counts *c) {
     cr_pool_free(ctx, c->d_filt_reads);
     cr_pool_free(ctx, c->d_mprobe);
     cr_pool_free(ctx, c->d_back);
+    cr_pool_free(ctx, c->d_pt_bc);
+    cr_pool_free(ctx, c->d_pt_probe);
+    cr_pool_free(ctx, c->d_pt_count);
     delete c;
 }
 
@@ -3305,3 +3313,5 @@ extern "C" int crgpu_trim_molecule_barcodes_dev(crgpu_ctx *ctx, uint64_t *d_barc
     *n_retained_out = kept;
     return CRGPU_OK;
 }
+
+#include "probe_counts.h"

@@ -270,6 +270,46 @@ class Counts:
             self.ctx._check(self.ctx.L.crgpu_counts_probe_idx(self.ctx.h, self.h, ptr(out)))
         return out
 
+    def probe_triplets_dev(self, n_probes):
+        """BcUmiInfo::probe_counts of every barcode (types.rs:190-204) as device views: (d_bc, d_probe, d_count, n), ordered by
+        (barcode rank, probe_idx); valid until free().  Computed on the first request."""
+        a, b, c, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint64()
+        self.ctx._check(self.ctx.L.crgpu_counts_probe_triplets_dev(self.ctx.h, self.h, n_probes, C.byref(a), C.byref(b), C.byref(c),
+                                                                   C.byref(n)))
+        return a.value, b.value, c.value, n.value
+
+    def probe_triplets(self, n_probes):
+        """the ProbeBarcodeCount stream (types.rs:141-146) on the host: (barcode rank, probe_idx, umi_count) arrays"""
+        L, h, n = self.ctx.L, self.ctx.h, C.c_uint64()
+        self.ctx._check(L.crgpu_counts_probe_triplets(h, self.h, n_probes, None, None, None, C.byref(n)))
+        bc, pr, ct = (np.zeros(n.value, np.uint32) for _ in range(3))
+        if n.value:
+            self.ctx._check(L.crgpu_counts_probe_triplets(h, self.h, n_probes, ptr(bc), ptr(pr), ptr(ct), C.byref(n)))
+        return bc, pr, ct
+
+    def probe_matrix(self, n_probes, sample_ranks=None):
+        """raw probe x barcode matrix (probe_barcode_matrix.rs:176-262) as a MatrixDev: columns = sample_ranks (strictly
+        ascending canonical ranks; a numpy array is uploaded, a DeviceArray is used as it is) or, when None, the context's
+        BarcodeIndex"""
+        d_ranks, n = None, 0
+        if sample_ranks is not None:
+            d_ranks = sample_ranks if isinstance(sample_ranks, DeviceArray) else self.ctx.upload(
+                np.ascontiguousarray(sample_ranks, dtype=np.uint32))
+            n = d_ranks.size
+        out = C.POINTER(_lib.MatrixDevView)()
+        self.ctx._check(self.ctx.L.crgpu_assemble_probe_matrix_dev(self.ctx.h, self.h, n_probes, _p(d_ranks), n, C.byref(out)))
+        return MatrixDev(self.ctx, out)
+
+    def probe_metrics(self, n_probes, cell_ranks):
+        """collate_probe_metrics' sums per probe (gdna_utils.rs:217-237): (umis_in_all_barcodes, umis_in_filtered_barcodes),
+        the second over the barcodes of cell_ranks (strictly ascending canonical ranks, numpy or DeviceArray)"""
+        d_cells = cell_ranks if isinstance(cell_ranks, DeviceArray) else self.ctx.upload(
+            np.ascontiguousarray(cell_ranks, dtype=np.uint32))
+        all_, filt = np.zeros(n_probes, np.uint64), np.zeros(n_probes, np.uint64)
+        self.ctx._check(self.ctx.L.crgpu_probe_metrics_dev(self.ctx.h, self.h, n_probes, _p(d_cells), d_cells.size, ptr(all_),
+                                                           ptr(filt)))
+        return all_, filt
+
     def barcode_summary(self, rank_lo=0, rank_hi=0xFFFFFFFF):
         """BarcodeSummary rows (cr_lib/src/aligner.rs:33-68) of the barcode ranks in [rank_lo, rank_hi), ordered by
         (library, rank): a numpy record array of _lib.BARCODE_SUMMARY_DTYPE"""

@@ -128,6 +128,9 @@ int crgpu_invalidate(crgpu_ctx *ctx);
 #define CRGPU_STAT_LOW_SUPPORT_CANDIDATES 10 /* of those, the keys the low-support filter had to group by (barcode, UMI) */
 #define CRGPU_STAT_MISS_RECORD_SETS 11       /* pass-A calls whose miss records are still kept for their pass B (at most 4) */
 #define CRGPU_STAT_SORT_REFINISHED 1 /* sorts redone on all key bits because a run of equal top bits was too long for the finishing pass */
+#define CRGPU_STAT_PROBE_SEGMENTS_WAVE 12      /* barcode segments the last probe-triplet computation ordered in registers (<= 64 molecules) */
+#define CRGPU_STAT_PROBE_SEGMENTS_WORKGROUP 13 /* ... in LDS, one workgroup each (<= 32768 molecules) */
+#define CRGPU_STAT_PROBE_SEGMENTS_GLOBAL 14    /* ... through the device radix sort (larger ones; all above CRGPU_PROBE_SEG_CAP) */
 int crgpu_get_stat(crgpu_ctx *ctx, int which, uint64_t *value_out);
 /* ctx may be NULL: returns the message of the last failed crgpu_create on this thread. */
 const char *crgpu_last_error(const crgpu_ctx *ctx);
@@ -488,6 +491,29 @@ int crgpu_counts_molecule_info(crgpu_ctx *ctx, const crgpu_counts *c, uint16_t g
  * has none.  CRGPU_ESTATE when the counts were made without crgpu_records.d_probe_idx (or by crgpu_count_keys_dev: keys
  * carry no read identity). */
 int crgpu_counts_probe_idx(crgpu_ctx *ctx, const crgpu_counts *c, int32_t *probe_idx_out);
+/* BcUmiInfo::probe_counts (cr_types/src/types.rs:190-204), the second histogram ALIGN_AND_COUNT sends downstream for every
+ * valid barcode (cr_lib/src/stages/align_and_count.rs:311-333): over ALL molecules of the counts (every library pooled; the
+ * entries crgpu_counts_molecules lists) whose probe is not CRGPU_NO_PROBE, one ProbeBarcodeCount (types.rs:141-146)
+ * (barcode rank, probe_idx, umi_count = number of such molecules) per distinct (barcode, probe), ordered by (barcode rank,
+ * probe_idx) -- the derived Ord of ProbeBarcodeCount, the shard sort key.  Computed on the device on the first request,
+ * kept in the counts and freed with them; counts that are never asked launch and allocate nothing for it.
+ * n_probes = number of probes of the probe set: a molecule probe >= n_probes or < -1 fails with CRGPU_ERANGE (the
+ * reference panics there).  CRGPU_ESTATE when the counts were made without crgpu_records.d_probe_idx (or by
+ * crgpu_count_keys_dev).  No molecules / no probed molecules: zero triplets.
+ *   crgpu_counts_probe_triplets_dev  device views u32[*n_out], valid until crgpu_counts_free or a request with another n_probes
+ *   crgpu_counts_probe_triplets      host copies; NULL arrays: size query
+ * Segments (the molecules of one barcode) of up to 32768 molecules are ordered in registers / LDS, larger ones by the device
+ * radix sort; CRGPU_PROBE_SEG_CAP=<n> in the environment when the context is created (tests) lowers that bound, 0 sends every
+ * segment through the sort.  crgpu_get_stat(CRGPU_STAT_PROBE_SEGMENTS_*) tells how many segments took which route. */
+int crgpu_counts_probe_triplets_dev(crgpu_ctx *ctx, crgpu_counts *c, uint32_t n_probes, uint32_t **d_bc, uint32_t **d_probe,
+                                    uint32_t **d_count, uint64_t *n_out);
+int crgpu_counts_probe_triplets(crgpu_ctx *ctx, crgpu_counts *c, uint32_t n_probes, uint32_t *bc_out, uint32_t *probe_out,
+                                uint32_t *count_out, uint64_t *n_out);
+/* The two sums of collate_probe_metrics (cr_lib/src/gdna_utils.rs:217-237) per probe: UMIs over all barcodes and over the
+ * barcodes of d_cell_ranks (device, n_cells canonical ranks, strictly ascending, else CRGPU_EINVAL; the filtered barcodes).
+ * Host output arrays of n_probes u64, either may be NULL. */
+int crgpu_probe_metrics_dev(crgpu_ctx *ctx, crgpu_counts *c, uint32_t n_probes, const uint32_t *d_cell_ranks, uint64_t n_cells,
+                            uint64_t *umis_in_all_barcodes_out, uint64_t *umis_in_filtered_barcodes_out);
 /* molecule table: bc rank, library, feature, 2-bit umi, read_count, utype (0 Txomic,1 NonTxomic) */
 int crgpu_counts_molecules(crgpu_ctx *ctx, const crgpu_counts *c, uint32_t *bc_out, uint8_t *lib_out,
                            uint32_t *feature_out, uint32_t *umi_out, uint32_t *read_count_out,
@@ -585,6 +611,14 @@ typedef struct {
 int crgpu_assemble_matrix_dev(crgpu_ctx *ctx, const uint32_t *d_bc, const uint32_t *d_feature, const uint32_t *d_count,
                               uint64_t n_triplets, crgpu_matrix_dev **out);
 void crgpu_matrix_dev_free(crgpu_ctx *ctx, crgpu_matrix_dev *m);
+/* The raw probe x barcode matrix of write_probe_matrix_h5_helper (cr_lib/src/probe_barcode_matrix.rs:176-262; DEMUX_PROBE_BC_MATRIX,
+ * stages/demux_probe_bc_matrix.rs:76-131) from the probe triplets of `c` (crgpu_counts_probe_triplets_dev): the columns are
+ * exactly the barcodes of d_sample_ranks (device, n_sample canonical ranks, strictly ascending, else CRGPU_EINVAL --
+ * BarcodeIndex::from_iter(sample_bcs)); a listed barcode without probe counts is an empty column, the counts of barcodes that
+ * are not listed are skipped; inside a column the rows (probe indices) ascend.  d_sample_ranks == NULL: the BarcodeIndex of
+ * this context, as crgpu_assemble_matrix_dev.  The H5 container and the probe annotation columns stay with the host. */
+int crgpu_assemble_probe_matrix_dev(crgpu_ctx *ctx, crgpu_counts *c, uint32_t n_probes, const uint32_t *d_sample_ranks,
+                                    uint64_t n_sample, crgpu_matrix_dev **out);
 /* aggr-style post-processing of DEVICE matrices (the host versions are crgpu_sum_matrices / crgpu_select_barcodes):
  * crgpu_sum_matrices_dev     element-wise sum of two CSCs over the same columns (same barcode ranks in the same order;
  *                            CountMatrix.merge, lib/python/cellranger/matrix.py:479-482,1319-1329): per column a merge of the

@@ -167,7 +167,7 @@ class BarcodeCorrector {
     std::map<std::string, uint32_t> seq_rank_;
 };
 
-/// UmiCount (cr_types/src/types.rs:152-160) without probe_idx.
+/// UmiCount (cr_types/src/types.rs:152-160) without probe_idx (BarcodeDupMarker::probe_counts carries the histogram of it).
 struct UmiCount {
     uint32_t barcode_rank;
     uint16_t library_idx;
@@ -177,6 +177,11 @@ struct UmiCount {
 /// FeatureBarcodeCount (types.rs:121-137), BarcodeThenFeatureOrder.
 struct FeatureBarcodeCount {
     uint32_t barcode_rank, feature_idx, umi_count;
+};
+
+/// ProbeBarcodeCount (types.rs:141-146), ordered by (barcode, probe_idx) as its derived Ord.
+struct ProbeBarcodeCount {
+    uint32_t barcode, probe_idx, umi_count;  // barcode = canonical rank
 };
 
 /// Result of DupBuilder::build: what BarcodeDupMarker::process + BcUmiInfo::feature_counts yield for all
@@ -199,6 +204,8 @@ struct BarcodeDupMarker {
     std::vector<BarcodeSummary> barcode_summaries;    // ordered by (library, barcode), one per barcode with a read
     std::vector<UmiCount> umi_counts;                 // sorted per barcode as align_and_count.rs:314
     std::vector<FeatureBarcodeCount> feature_counts;  // sorted by (barcode, feature)
+    /// BcUmiInfo::probe_counts (types.rs:190-204) of every barcode: filled when a read was observed with a probe
+    std::vector<ProbeBarcodeCount> probe_counts;      // sorted by (barcode, probe_idx)
     /// process(read): one entry per observe() call, in call order (the order stands in for the qname
     /// rank: observe reads in read-header order).  nullopt = process() returned None.
     std::vector<std::optional<DupInfo>> dup_infos;
@@ -212,8 +219,9 @@ class DupBuilder {
         : ctx_(ctx), n_features_(n_features), umi_len_(umi_len) {
         ctx_.check(crgpu_set_key_layout(ctx_.get(), n_features, umi_len, n_libs, multiplexing_lib_mask));
     }
+    /// probe_idx: the read's confidently mapped LHS probe (RTL / Flex reads, mark_dups.rs:332-342) or CRGPU_NO_PROBE
     void observe(uint32_t barcode_rank, int lib, const std::string &umi, const std::vector<uint8_t> &umi_qual, uint32_t feature,
-                 bool is_txomic = true) {
+                 bool is_txomic = true, int32_t probe_idx = CRGPU_NO_PROBE) {
         if (umi.size() != umi_len_ || umi_qual.size() != umi_len_) throw Error(CRGPU_EINVAL, "UMI length differs from the layout's");
         uint32_t packed = 0;
         for (uint32_t j = 0; j < umi_len_; j++) {
@@ -226,6 +234,9 @@ class DupBuilder {
         umi_.push_back(packed);
         feature_.push_back(feature);
         flags_.push_back((uint8_t)((lib & 0x0F) | (is_txomic ? 0 : CRGPU_FLAG_NONTXOMIC)));
+        if (probe_idx < CRGPU_NO_PROBE) throw Error(CRGPU_ERANGE, "probe_idx below CRGPU_NO_PROBE");
+        probe_.push_back(probe_idx);
+        if (probe_idx >= 0 && (uint32_t)probe_idx + 1u > n_probes_) n_probes_ = (uint32_t)probe_idx + 1u;
     }
     BarcodeDupMarker build() {
         const uint64_t n = bc_.size();
@@ -245,8 +256,10 @@ class DupBuilder {
         std::vector<uint32_t> pu(n), rc32(n);
         std::vector<uint8_t> df(n);
         Dev d_pu(ctx_, pu.data(), n * 4), d_rc(ctx_, rc32.data(), n * 4), d_df(ctx_, df.data(), n);
+        Dev d_pr(ctx_, probe_.data(), n * 4);
         crgpu_records recs{n, umi_len_, (const uint32_t *)d_bc.p, (const uint32_t *)d_umi.p, (const uint8_t *)d_q.p,
                            (const uint32_t *)d_f.p, (const uint8_t *)d_fl.p};
+        if (n_probes_) recs.d_probe_idx = (const int32_t *)d_pr.p;
         crgpu_counts *c = nullptr;
         ctx_.check(crgpu_count_records_dev(ctx_.get(), &recs, &c, (uint32_t *)d_pu.p, (uint32_t *)d_rc.p, (uint8_t *)d_df.p));
         uint64_t nt = 0, nm = 0;
@@ -263,6 +276,13 @@ class DupBuilder {
             if (rc == CRGPU_OK && n_rows)
                 rc = crgpu_counts_barcode_summary(ctx_.get(), c, 0, 0xFFFFFFFFu, rows.data(), n_rows, &n_rows);
         }
+        std::vector<uint32_t> pb, pp, pc;
+        if (rc == CRGPU_OK && n_probes_) {
+            uint64_t np = 0;
+            rc = crgpu_counts_probe_triplets(ctx_.get(), c, n_probes_, nullptr, nullptr, nullptr, &np);
+            pb.resize(np), pp.resize(np), pc.resize(np);
+            if (rc == CRGPU_OK && np) rc = crgpu_counts_probe_triplets(ctx_.get(), c, n_probes_, pb.data(), pp.data(), pc.data(), &np);
+        }
         crgpu_counts_free(ctx_.get(), c);
         ctx_.check(rc);
         ctx_.check(crgpu_memcpy_d2h(ctx_.get(), pu.data(), d_pu.p, n * 4));
@@ -276,6 +296,7 @@ class DupBuilder {
         for (const auto &r : rows)
             out.barcode_summaries.push_back({r.barcode_rank, r.library, r.reads, r.umis, r.candidate_dup_reads, r.umi_corrected_reads});
         for (uint64_t i = 0; i < nt; i++) out.feature_counts.push_back({tb[i], tf[i], tc[i]});
+        for (size_t i = 0; i < pb.size(); i++) out.probe_counts.push_back({pb[i], pp[i], pc[i]});
         for (uint64_t i = 0; i < nm; i++) out.umi_counts.push_back({mb[i], ml[i], mf[i], mu[i], mr[i], mt[i]});
         return out;
     }
@@ -285,6 +306,8 @@ class DupBuilder {
     uint32_t n_features_, umi_len_;
     std::vector<uint32_t> bc_, umi_, feature_;
     std::vector<uint8_t> qualn_, flags_;
+    std::vector<int32_t> probe_;
+    uint32_t n_probes_ = 0;  // largest probe_idx observed + 1 (0: no read carried a probe)
 };
 
 /// FeatureDef (cr_types/src/reference/feature_reference.rs): the columns FeatureExtractor reads.
