@@ -23,6 +23,8 @@ COUNTS_VALID, COUNTS_CORRECTED, COUNTS_PRIOR = 0, 1, 2
 T_NAMES = ["pack", "match", "correct", "keys", "sort_scatter", "dedup", "matrix", "synth", "sort_hist", "scan", "comm", "feature"]
 UNIQUE_ID_BYTES = 128
 OPT_BUFFERS_UNCHANGED_BETWEEN_CALLS = 0
+STAT_SORT_REFINISHED = 1
+STAT_RL_COUNTS_FROM_FINISH = 15
 
 
 class CrgpuError(RuntimeError):

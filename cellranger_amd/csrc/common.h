@@ -204,6 +204,7 @@ struct crgpu_ctx {
     std::map<const void *, size_t> lds_attr_done;  // kernels whose dynamic-LDS limit was raised on this context's device (to how much)
     uint32_t n_xcc = 0;                    // XCDs that receive workgroups (probed by the first onesweep sort); 0 = unknown
     uint64_t last_distinct_keys = 0, last_low_support_candidates = 0;  // of the last count call
+    uint64_t rl_counts_from_finish = 0;    // count calls whose run-length pass skipped its count launch (tile counts from the finishing step)
     uint64_t sort_refinished = 0;          // sorts whose finishing pass met a run too long for it and that were redone on all bits
     uint64_t k1_split_rounds = 0;          // table rounds of K1 whose histogram was split (table slots in LDS + staged cold hits)
     uint64_t feature_resumed_reads = 0;    // captures a pass with a distribution took from the records of the pass without one
@@ -325,7 +326,17 @@ bool cr_sweep_plan(uint32_t lo_bit, uint32_t hi_bit, SweepPlan *plan, uint32_t *
 // low bits of a molecule key of total_bits that the radix passes leave to the finishing pass (0: none)
 uint32_t cr_sort_low_bits(uint32_t total_bits, uint32_t umi_bits);
 bool cr_sort_finish_experiment();  // CRGPU_SORT_FINISH=1: the 16-bit finishing pass of round 2 instead of k_order_runs
-int cr_order_runs(crgpu_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, uint64_t n, uint32_t low_bits, bool *fell_back);
+// Run heads as a by-product of the finishing step: the number of keys i with i == 0 or (key[i] >> shift) != (key[i - 1] >> shift)
+// in every tile of `tile` keys of the ORDERED buffer, for the run-length pass that follows (dedup.hip, run_lengths).
+// k_find_descents counts them on the keys as they are before the repair, every repair adds what it changes.
+struct CrRunHeads {
+    uint32_t shift;      // in: at most low_bits (so that a run of equal top bits begins and ends with a head whatever its order)
+    uint64_t tile;       // in: keys per tile, a multiple of the 512 keys a wave of k_find_descents takes at a time
+    uint32_t *d_counts;  // in: ceil(n / tile) device words
+    bool valid;          // out: d_counts holds the counts (never when *fell_back, or when another finishing step ran)
+};
+int cr_order_runs(crgpu_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, uint64_t n, uint32_t low_bits, bool *fell_back,
+                  CrRunHeads *heads = nullptr);
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (context, kernel): the attribute is per device
 static inline void cr_allow_lds(crgpu_ctx *ctx, const void *kernel, size_t bytes) {
     size_t &have = ctx->lds_attr_done[kernel];

@@ -216,6 +216,9 @@ extern "C" int crgpu_get_stat(crgpu_ctx *ctx, int which, uint64_t *value_out) {
         case CRGPU_STAT_SORT_REFINISHED:
             *value_out = ctx->sort_refinished;
             return CRGPU_OK;
+        case CRGPU_STAT_RL_COUNTS_FROM_FINISH:
+            *value_out = ctx->rl_counts_from_finish;
+            return CRGPU_OK;
         case CRGPU_STAT_K1_SPLIT_ROUNDS:
             *value_out = ctx->k1_split_rounds;
             return CRGPU_OK;

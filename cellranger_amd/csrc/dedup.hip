@@ -1059,12 +1059,18 @@ __global__ __launch_bounds__(CP_BLOCK) void k_rl_write(const uint64_t *__restric
     }
 }
 
+// counts_ready: d_block already holds the run heads of every tile of cp_blocks(n) -- the finishing step of the sort counted
+// them while it held the keys (cr_order_runs with a CrRunHeads) -- and the count pass over all keys is skipped.  k_rl_write
+// is the check on them: with wrong tile counts its output has gaps or overlaps.
 static int run_lengths(crgpu_ctx *ctx, const uint64_t *keys, uint32_t shift, uint64_t n, uint64_t *ukey, uint32_t *upos,
-                       uint32_t *d_block, uint32_t *d_total_out, uint16_t *z_st = nullptr, uint32_t *z_inc = nullptr,
-                       uint32_t *z_min = nullptr) {
+                       uint32_t *d_block, uint32_t *d_total_out, bool counts_ready = false, uint16_t *z_st = nullptr,
+                       uint32_t *z_inc = nullptr, uint32_t *z_min = nullptr) {
     uint64_t tile;
     const uint32_t nb = cp_blocks(n, &tile);
-    hipLaunchKernelGGL(k_rl_count, dim3(nb), dim3(CP_BLOCK), 0, ctx->stream, keys, shift, n, tile, d_block);
+    if (!counts_ready)
+        hipLaunchKernelGGL(k_rl_count, dim3(nb), dim3(CP_BLOCK), 0, ctx->stream, keys, shift, n, tile, d_block);
+    else
+        ctx->rl_counts_from_finish++;
     CR_TRY(cr_scan_small(ctx, d_block, nb, d_total_out));
     hipLaunchKernelGGL(k_rl_write, dim3(nb), dim3(CP_BLOCK), 0, ctx->stream, keys, shift, n, tile, d_block, ukey, upos, z_st, z_inc,
                        z_min);
@@ -2047,13 +2053,19 @@ static int count_keys_impl(crgpu_ctx *ctx, uint64_t *d_keys_inout, uint64_t n_ke
     uint32_t *upos = upos_b.as<uint32_t>();
     uint64_t nd = 0;
     bool emitted = false;
+    CrRunHeads rl_heads{1u, 0, nullptr, false};
     if (low_left) {
         bool fell_back = false;
         if (cr_sort_finish_experiment()) {
             CR_TRY(cr_finish_emit(ctx, keys_rw, vals_rw, n_keys, low_left, ukey, upos, &nd, &fell_back));
             emitted = !fell_back;
         } else {
-            CR_TRY(cr_order_runs(ctx, keys_rw, vals_rw, n_keys, low_left, &fell_back));  // then the run lengths as usual
+            // then the run lengths -- whose count pass the finishing step can spare: it holds every key and its left neighbour
+            // anyway and counts the run heads of the tiles of run_lengths() into d_block on the way
+            rl_heads.shift = 1u;
+            (void)cp_blocks(n_keys, &rl_heads.tile);
+            rl_heads.d_counts = getenv("CRGPU_RL_GENERIC") ? nullptr : d_block;
+            CR_TRY(cr_order_runs(ctx, keys_rw, vals_rw, n_keys, low_left, &fell_back, &rl_heads));
         }
         if (fell_back) {
             // a run of equal top bits too long for the fused pass: sort the buffer (the same multiset) on all bits
@@ -2066,6 +2078,7 @@ static int count_keys_impl(crgpu_ctx *ctx, uint64_t *d_keys_inout, uint64_t n_ke
                 keys_rw = other;
                 vals_rw = vother;
             }
+            rl_heads.valid = false;  // (cr_order_runs says so already: the counts were of another order of the buffer)
         }
     }
     const uint64_t *keys = keys_rw;
@@ -2077,7 +2090,7 @@ static int count_keys_impl(crgpu_ctx *ctx, uint64_t *d_keys_inout, uint64_t n_ke
             if (getenv("CRGPU_RL_GENERIC"))  // A/B: the generic compaction with its three loads per key
                 CR_TRY(compact(ctx, HeadFlag{keys, 1u}, EmitRun{keys, ukey, upos}, n_keys, d_block, d_total));
             else
-                CR_TRY(run_lengths(ctx, keys, 1u, n_keys, ukey, upos, d_block, d_total, fused_zero ? st_b.as<uint16_t>() : nullptr,
+                CR_TRY(run_lengths(ctx, keys, 1u, n_keys, ukey, upos, d_block, d_total, rl_heads.valid, fused_zero ? st_b.as<uint16_t>() : nullptr,
                                    fused_zero ? incall_b.as<uint32_t>() : nullptr, fused_zero ? minidx_b.as<uint32_t>() : nullptr));
         }
         CR_TRY(read_u32(ctx, d_total, &nd32));

@@ -964,9 +964,34 @@ __device__ void or_flag_permute(uint64_t *__restrict__ keys, uint32_t *__restric
     }
 }
 
+// Device side of CrRunHeads (common.h): counts == nullptr -- nobody asked.
+struct RhDev {
+    uint32_t *counts = nullptr;
+    uint64_t tile = 1;
+    uint32_t shift = 0;
+};
+// the interior head flags of the run [i, e) as it lies in memory, added to (or taken from) the tiles its positions lie in
+__device__ void or_add_heads(const uint64_t *keys, uint64_t i, uint64_t e, const RhDev rh, bool add) {
+    uint64_t t = i / rh.tile, bnd = (t + 1) * rh.tile;
+    uint32_t c = 0;
+    uint64_t prev = keys[i];
+    for (uint64_t a = i + 1; a < e; a++) {
+        if (a == bnd) {
+            if (c) atomicAdd(&rh.counts[t], add ? c : 0u - c);
+            c = 0;
+            t++;
+            bnd += rh.tile;
+        }
+        const uint64_t k = keys[a];
+        c += (k >> rh.shift) != (prev >> rh.shift) ? 1u : 0u;
+        prev = k;
+    }
+    if (c) atomicAdd(&rh.counts[t], add ? c : 0u - c);
+}
+
 template <bool HAS_VALS>
 __device__ void or_run_through_memory(uint64_t *__restrict__ keys, uint32_t *__restrict__ vals, uint64_t n, uint32_t low, uint64_t i,
-                                      uint32_t *__restrict__ bad) {
+                                      uint32_t *__restrict__ bad, const RhDev rh = RhDev()) {
     const uint64_t first = keys[i], top = first >> low;
     uint64_t e = i + 1, prev = first;
     bool disorder = false;
@@ -982,6 +1007,7 @@ __device__ void or_run_through_memory(uint64_t *__restrict__ keys, uint32_t *__r
         return;
     }
     if (!disorder) return;
+    if (rh.counts) or_add_heads(keys, i, e, rh, false);  // the run's head flags: out as they are, back in once it is ordered
     const uint64_t len = e - i;
     if (len <= OR_CAP) {  // insertion sort in place (only this lane touches the run)
         for (uint64_t a = i + 1; a < e; a++) {
@@ -998,30 +1024,31 @@ __device__ void or_run_through_memory(uint64_t *__restrict__ keys, uint32_t *__r
                 if (HAS_VALS) vals[b] = v;
             }
         }
-        return;
+    } else {
+        // a long run that mixes low bits (many reads of one UMI with both UmiTypes, ...): in-place bucket permutation on the
+        // low bits (American flag sort).  Up to 8 low bits: one level of at most 256 buckets; 9 .. OR_MAX_LOW_BITS: first on the
+        // bits above the low eight (at most 8 buckets), then every such bucket on its low eight.  (The bucket arrays live in
+        // scratch, per lane: 256 entries each is what a kernel with 256-thread workgroups can afford.)
+        uint32_t cnt[256], nxt[256];
+        if (low > OR_MAX_LOW_BITS) {  // cannot happen (cr_sort_low_bits): never overrun the arrays, let the caller sort on all bits
+            atomicOr(bad, 1u);        // (the head counts are void with it)
+            return;
+        }
+        if (low <= 8u) {
+            or_flag_permute<HAS_VALS>(keys, vals, i, e, 0u, low, cnt, nxt);
+        } else {
+            uint32_t ends[1u << (OR_MAX_LOW_BITS - 8u)];
+            const uint32_t hi_bits = low - 8u;
+            or_flag_permute<HAS_VALS>(keys, vals, i, e, 8u, hi_bits, cnt, nxt);
+            for (uint32_t d = 0; d < (1u << hi_bits); d++) ends[d] = cnt[d];
+            uint32_t from = 0;
+            for (uint32_t d = 0; d < (1u << hi_bits); d++) {
+                if (ends[d] - from > 1u) or_flag_permute<HAS_VALS>(keys, vals, i + from, i + ends[d], 0u, 8u, cnt, nxt);
+                from = ends[d];
+            }
+        }
     }
-    // a long run that mixes low bits (many reads of one UMI with both UmiTypes, ...): in-place bucket permutation on the
-    // low bits (American flag sort).  Up to 8 low bits: one level of at most 256 buckets; 9 .. OR_MAX_LOW_BITS: first on the
-    // bits above the low eight (at most 8 buckets), then every such bucket on its low eight.  (The bucket arrays live in
-    // scratch, per lane: 256 entries each is what a kernel with 256-thread workgroups can afford.)
-    uint32_t cnt[256], nxt[256];
-    if (low > OR_MAX_LOW_BITS) {  // cannot happen (cr_sort_low_bits): never overrun the arrays, let the caller sort on all bits
-        atomicOr(bad, 1u);
-        return;
-    }
-    if (low <= 8u) {
-        or_flag_permute<HAS_VALS>(keys, vals, i, e, 0u, low, cnt, nxt);
-        return;
-    }
-    uint32_t ends[1u << (OR_MAX_LOW_BITS - 8u)];
-    const uint32_t hi_bits = low - 8u;
-    or_flag_permute<HAS_VALS>(keys, vals, i, e, 8u, hi_bits, cnt, nxt);
-    for (uint32_t d = 0; d < (1u << hi_bits); d++) ends[d] = cnt[d];
-    uint32_t from = 0;
-    for (uint32_t d = 0; d < (1u << hi_bits); d++) {
-        if (ends[d] - from > 1u) or_flag_permute<HAS_VALS>(keys, vals, i + from, i + ends[d], 0u, 8u, cnt, nxt);
-        from = ends[d];
-    }
+    if (rh.counts) or_add_heads(keys, i, e, rh, true);
 }
 
 template <bool HAS_VALS>
@@ -1129,8 +1156,13 @@ static int cr_order_runs_r02(crgpu_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals,
 //                     caller sorts on all bits).  The lists spread the runs of a few hot barcodes over the whole device.
 // Runs are disjoint, so the repairing lanes never touch each other's keys.
 #define FD_ITEMS 8
+// span_heads (nullable, CrRunHeads): entry gw receives the number of keys of span gw that open a run of equal (key >> rl_shift)
+// -- the key and its left neighbour are in registers anyway.  One plain store per 512 keys; k_tile_heads adds the spans of a
+// tile up.  (One device atomic per span on the tile's counter would put the neighbouring spans, which are in flight at the
+// same time, on one address.)
 __global__ __launch_bounds__(256) void k_find_descents(const uint64_t *__restrict__ keys, uint64_t n, uint32_t low,
-                                                       unsigned long long *__restrict__ desc, uint32_t *__restrict__ n_words_set) {
+                                                       unsigned long long *__restrict__ desc, uint32_t *__restrict__ n_words_set,
+                                                       const uint32_t rl_shift, uint32_t *__restrict__ span_heads) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t span = 64ull * FD_ITEMS;
     const uint64_t n_spans = (n + span - 1) / span;
@@ -1141,6 +1173,7 @@ __global__ __launch_bounds__(256) void k_find_descents(const uint64_t *__restric
         uint64_t key[FD_ITEMS];
         uint64_t carry = keys[w0 > 0 ? w0 - 1 : 0];
         bool carry_valid = w0 > 0;
+        uint32_t heads = 0;  // wave-uniform
 #pragma unroll
         for (int j = 0; j < FD_ITEMS; j++) {
             const uint64_t i = w0 + (uint64_t)j * 64 + lane;
@@ -1158,11 +1191,39 @@ __global__ __launch_bounds__(256) void k_find_descents(const uint64_t *__restric
                 desc[(w0 >> 6) + j] = m;
                 set += m != 0ull;
             }
+            if (span_heads) {
+                const bool hd = i < n && (!has_left || (key[j] >> rl_shift) != (left >> rl_shift));
+                heads += (uint32_t)__popcll(__ballot(hd));
+            }
             carry = __shfl(key[j], 63);
             carry_valid = true;
         }
+        if (span_heads && lane == 0) span_heads[gw] = heads;
     }
     if (lane == 0 && set) atomicAdd(n_words_set, set);
+}
+// the run heads of every tile (spans_per_tile spans of k_find_descents each) as they are BEFORE the repair: plain stores, in
+// front of the repair kernels, which add what they change
+__global__ __launch_bounds__(256) void k_tile_heads(const uint32_t *__restrict__ span_heads, uint64_t n_spans, uint64_t spans_per_tile,
+                                                    uint32_t *__restrict__ tile_heads) {
+    __shared__ uint32_t ws[4];
+    const uint64_t s0 = (uint64_t)blockIdx.x * spans_per_tile;
+    const uint64_t s1 = s0 + spans_per_tile < n_spans ? s0 + spans_per_tile : n_spans;
+    uint32_t c = 0;
+    for (uint64_t i = s0 + threadIdx.x; i < s1; i += 256) c += span_heads[i];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
+    if ((threadIdx.x & 63u) == 0) ws[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) tile_heads[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
+}
+// a repair's change of the head count of tile t: into the workgroup's LDS counters when t is one of theirs, else to memory
+#define RH_LDS 68u  // tiles a workgroup of k_repair_runs can meet: RR_WORDS * 64 keys / the smallest tile (2048 keys) + the edges
+__device__ __forceinline__ void rh_add(const RhDev rh, uint64_t t, int d, int *s_delta, uint64_t s_t0) {
+    if (!d) return;
+    const uint64_t idx = t - s_t0;  // (wraps to a large number for a tile in front of the workgroup's)
+    if (s_delta && idx < RH_LDS) atomicAdd(&s_delta[idx], d);
+    else atomicAdd(&rh.counts[t], (uint32_t)d);
 }
 
 #define RR_SHORT 12u  // runs up to this many keys are ordered in registers
@@ -1173,7 +1234,8 @@ template <bool HAS_VALS>
 __device__ __forceinline__ void repair_at(uint64_t *__restrict__ keys, uint32_t *__restrict__ vals, uint64_t n, uint32_t low,
                                           const unsigned long long *__restrict__ desc, uint64_t p, uint32_t *__restrict__ bad,
                                           unsigned long long *__restrict__ later_list = nullptr,
-                                          uint32_t *__restrict__ later_n = nullptr, uint32_t later_cap = 0u) {
+                                          uint32_t *__restrict__ later_n = nullptr, uint32_t later_cap = 0u,
+                                          const RhDev rh = RhDev(), int *s_delta = nullptr, uint64_t s_t0 = 0) {
     // keys[p] < keys[p - 1], same top bits.  Walk back to the head of the run.  An earlier descent on the way means another
     // lane owns the run.  Only things that no repair changes are looked at: the descent bits (read-only here) and the TOP
     // bits of the keys (a repair permutes keys inside one run, whose top bits are all equal) -- the owner may already be
@@ -1214,7 +1276,7 @@ __device__ __forceinline__ void repair_at(uint64_t *__restrict__ keys, uint32_t 
                     return;
                 }
             }
-            or_run_through_memory<HAS_VALS>(keys, vals, n, low, h, bad);
+            or_run_through_memory<HAS_VALS>(keys, vals, n, low, h, bad, rh);
             return;
         }
         len = RR_SHORT;
@@ -1240,12 +1302,29 @@ __device__ __forceinline__ void repair_at(uint64_t *__restrict__ keys, uint32_t 
             v[j + 1] = sw ? va : vb;
         }
     }
+    // head flags of the interior positions (the run's first key and the key behind the run are heads either way), before and
+    // after, as bit masks: the keys are dead by the time the tiles are worked out
+    uint32_t heads_before = 0, heads_after = 0;
+    if (rh.counts) {
+#pragma unroll
+        for (uint32_t j = 1; j < RR_SHORT; j++)
+            if (j < len) {
+                heads_before |= (uint32_t)((k0[j] >> rh.shift) != (k0[j - 1] >> rh.shift)) << j;
+                heads_after |= (uint32_t)((k[j] >> rh.shift) != (k[j - 1] >> rh.shift)) << j;
+            }
+    }
 #pragma unroll
     for (uint32_t j = 0; j < RR_SHORT; j++)
         if (j < len && (k[j] != k0[j] || (HAS_VALS && v[j] != v0[j]))) {
             keys[h + j] = k[j];
             if (HAS_VALS) vals[h + j] = v[j];
         }
+    if (heads_before != heads_after) {  // RR_SHORT keys lie in at most two tiles
+        const uint64_t t0 = h / rh.tile, to_next = (t0 + 1) * rh.tile - h;  // positions h + to_next .. belong to tile t0 + 1
+        const uint32_t in_t0 = to_next < 32u ? (1u << (uint32_t)to_next) - 1u : 0xFFFFFFFFu;
+        rh_add(rh, t0, __popc(heads_after & in_t0) - __popc(heads_before & in_t0), s_delta, s_t0);
+        rh_add(rh, t0 + 1, __popc(heads_after & ~in_t0) - __popc(heads_before & ~in_t0), s_delta, s_t0);
+    }
 }
 
 // The descents are few (a few per mille of the keys) and scattered: a lane that took them straight from its mask word
@@ -1257,13 +1336,16 @@ template <bool HAS_VALS>
 __global__ __launch_bounds__(256) void k_repair_runs(uint64_t *__restrict__ keys, uint32_t *__restrict__ vals, uint64_t n, uint32_t low,
                                                      const unsigned long long *__restrict__ desc, uint64_t n_words,
                                                      uint32_t *__restrict__ bad, unsigned long long *__restrict__ med_list,
-                                                     uint32_t *__restrict__ n_med, uint32_t med_cap) {
+                                                     uint32_t *__restrict__ n_med, uint32_t med_cap, const RhDev rh) {
     __shared__ uint32_t s_n;
     __shared__ uint32_t s_pos[RR_CAP];  // position inside the tile (RR_WORDS * 64 keys: 17 bits)
+    __shared__ int s_delta[RH_LDS];     // changes of the head counts of the run-length tiles this tile's keys lie in (rh_add)
     const uint64_t n_tiles = (n_words + RR_WORDS - 1) / RR_WORDS;
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const uint64_t w0 = tile * RR_WORDS;
+        const uint64_t s_t0 = w0 * 64 / rh.tile;
         if (threadIdx.x == 0) s_n = 0;
+        if (threadIdx.x < RH_LDS) s_delta[threadIdx.x] = 0;
         __syncthreads();
         for (uint32_t j = threadIdx.x; j < RR_WORDS; j += 256) {
             unsigned long long m = w0 + j < n_words ? desc[w0 + j] : 0ull;
@@ -1272,14 +1354,16 @@ __global__ __launch_bounds__(256) void k_repair_runs(uint64_t *__restrict__ keys
                 m &= m - 1ull;
                 const uint32_t slot = atomicAdd(&s_n, 1u);
                 if (slot < RR_CAP) s_pos[slot] = j * 64u + b;
-                else repair_at<HAS_VALS>(keys, vals, n, low, desc, (w0 + j) * 64 + b, bad, med_list, n_med, med_cap);  // a tile full of descents: at once
+                else  // a tile full of descents: at once
+                    repair_at<HAS_VALS>(keys, vals, n, low, desc, (w0 + j) * 64 + b, bad, med_list, n_med, med_cap, rh, s_delta, s_t0);
             }
         }
         __syncthreads();
         const uint32_t cnt = s_n < RR_CAP ? s_n : RR_CAP;
         for (uint32_t t = threadIdx.x; t < cnt; t += 256)
-            repair_at<HAS_VALS>(keys, vals, n, low, desc, w0 * 64 + s_pos[t], bad, med_list, n_med, med_cap);
+            repair_at<HAS_VALS>(keys, vals, n, low, desc, w0 * 64 + s_pos[t], bad, med_list, n_med, med_cap, rh, s_delta, s_t0);
         __syncthreads();
+        if (rh.counts && threadIdx.x < RH_LDS && s_delta[threadIdx.x]) atomicAdd(&rh.counts[s_t0 + threadIdx.x], (uint32_t)s_delta[threadIdx.x]);
         __syncthreads();
     }
 }
@@ -1295,7 +1379,7 @@ __global__ __launch_bounds__(256) void k_repair_medium_runs(uint64_t *__restrict
                                                             uint32_t low, const unsigned long long *__restrict__ med_list,
                                                             const uint32_t *__restrict__ n_med, uint32_t med_cap,
                                                             unsigned long long *__restrict__ long_list, uint32_t *__restrict__ n_long,
-                                                            uint32_t long_cap, uint32_t *__restrict__ bad) {
+                                                            uint32_t long_cap, uint32_t *__restrict__ bad, const RhDev rh) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t cnt = *n_med < med_cap ? *n_med : med_cap;
     const uint32_t n_waves = gridDim.x * (blockDim.x >> 6);
@@ -1312,18 +1396,34 @@ __global__ __launch_bounds__(256) void k_repair_medium_runs(uint64_t *__restrict
             if (lane == 0) {
                 const uint32_t slot = long_cap ? atomicAdd(n_long, 1u) : 0xFFFFFFFFu;
                 if (slot < long_cap) long_list[slot] = h;
-                else or_run_through_memory<HAS_VALS>(keys, vals, n, low, h, bad);
+                else or_run_through_memory<HAS_VALS>(keys, vals, n, low, h, bad, rh);
             }
             continue;
         }
-        uint32_t rank = 0;
+        // same_before: the run's keys with my (key >> rh.shift) that the order puts in front of me -- none: I open a run of it
+        uint32_t rank = 0, same_before = 0;
         for (uint32_t i = 0; i < len; i++) {  // uniform
             const uint64_t ki = __shfl(key, (int)i);
-            rank += (ki < key || (ki == key && i < lane)) ? 1u : 0u;
+            const bool before_me = ki < key || (ki == key && i < lane);
+            rank += before_me ? 1u : 0u;
+            same_before += (before_me && (ki >> rh.shift) == (key >> rh.shift)) ? 1u : 0u;
         }
         if (lane < len && rank != lane) {  // (every key of the run is in a register by now: the stores cannot hit a key not yet read)
             keys[h + rank] = key;
             if (HAS_VALS) vals[h + rank] = val;
+        }
+        if (rh.counts) {  // uniform
+            // interior head flags: before at my position (lane), after at the position my key goes to (rank); at most two tiles
+            const uint64_t left = __shfl_up(key, 1);
+            const bool before = lane >= 1u && lane < len && (key >> rh.shift) != (left >> rh.shift);
+            const bool after = lane < len && rank >= 1u && same_before == 0u;
+            const uint64_t t0 = h / rh.tile, bnd = (t0 + 1) * rh.tile - h;  // first position (relative to h) of tile t0 + 1
+            const int d0 = __popcll(__ballot(after && rank < bnd)) - __popcll(__ballot(before && lane < bnd));
+            const int d1 = __popcll(__ballot(after && rank >= bnd)) - __popcll(__ballot(before && lane >= bnd));
+            if (lane == 0) {
+                rh_add(rh, t0, d0, nullptr, 0);
+                rh_add(rh, t0 + 1, d1, nullptr, 0);
+            }
         }
     }
 }
@@ -1338,10 +1438,11 @@ template <bool HAS_VALS>
 __global__ __launch_bounds__(256) void k_repair_long_runs(uint64_t *__restrict__ keys, uint32_t *__restrict__ vals, uint64_t n, uint32_t low,
                                                           const unsigned long long *__restrict__ long_list,
                                                           const uint32_t *__restrict__ n_long, uint32_t long_cap,
-                                                          uint32_t *__restrict__ bad) {
+                                                          uint32_t *__restrict__ bad, const RhDev rh) {
     __shared__ uint32_t s_c[RL_CAP];
     __shared__ uint32_t s_v[HAS_VALS ? RL_CAP : 1];
     __shared__ uint32_t s_len;
+    __shared__ int s_delta[RH_LDS];  // changes of the head counts of the tiles the run lies in (rh_add): RL_CAP keys, a handful of tiles
     const uint32_t tid = threadIdx.x;
     const uint32_t cnt = *n_long < long_cap ? *n_long : long_cap;
     const uint64_t lowmask = (1ull << low) - 1ull;
@@ -1349,6 +1450,7 @@ __global__ __launch_bounds__(256) void k_repair_long_runs(uint64_t *__restrict__
         const uint64_t h = long_list[it];
         const uint64_t top = keys[h] >> low;
         if (tid == 0) s_len = RL_CAP + 1u;
+        if (tid < RH_LDS) s_delta[tid] = 0;
         __syncthreads();
         // the run's length: the first position behind h whose top bits differ (RL_CAP + 1: the run goes on behind the window)
         for (uint32_t j = tid; j <= RL_CAP; j += 256) {
@@ -1358,10 +1460,12 @@ __global__ __launch_bounds__(256) void k_repair_long_runs(uint64_t *__restrict__
         __syncthreads();
         const uint32_t len = s_len;
         if (len > RL_CAP) {  // uniform
-            if (tid == 0) or_run_through_memory<HAS_VALS>(keys, vals, n, low, h, bad);
+            if (tid == 0) or_run_through_memory<HAS_VALS>(keys, vals, n, low, h, bad, rh);
             __syncthreads();
             continue;
         }
+        const uint64_t t0 = h / rh.tile;
+        const uint32_t in_t0 = (uint32_t)(h - t0 * rh.tile);  // the head's position inside its tile
         uint32_t P = 128;
         while (P < len) P <<= 1;
         for (uint32_t j = tid; j < P; j += 256) {
@@ -1369,6 +1473,11 @@ __global__ __launch_bounds__(256) void k_repair_long_runs(uint64_t *__restrict__
             if (HAS_VALS && j < len) s_v[j] = vals[h + j];
         }
         __syncthreads();
+        if (rh.counts) {  // the interior head flags of the run as it lies in memory: out
+            for (uint32_t j = 1 + tid; j < len; j += 256)
+                if ((s_c[j] >> (12u + rh.shift)) != (s_c[j - 1] >> (12u + rh.shift))) rh_add(rh, t0 + (in_t0 + j) / rh.tile, -1, s_delta, t0);
+            __syncthreads();
+        }
         for (uint32_t k = 2; k <= P; k <<= 1)
             for (uint32_t j = k >> 1; j > 0; j >>= 1) {
                 for (uint32_t x = tid; x < P / 2; x += 256) {
@@ -1390,22 +1499,42 @@ __global__ __launch_bounds__(256) void k_repair_long_runs(uint64_t *__restrict__
                 if (HAS_VALS) vals[h + j] = s_v[c & 4095u];
             }
         }
+        if (rh.counts) {  // ... and those of the ordered run: in
+            for (uint32_t j = 1 + tid; j < len; j += 256)
+                if ((s_c[j] >> (12u + rh.shift)) != (s_c[j - 1] >> (12u + rh.shift))) rh_add(rh, t0 + (in_t0 + j) / rh.tile, 1, s_delta, t0);
+            __syncthreads();
+            if (tid < RH_LDS && s_delta[tid]) atomicAdd(&rh.counts[t0 + tid], (uint32_t)s_delta[tid]);
+        }
         __syncthreads();
     }
 }
 
-int cr_repair_runs(crgpu_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, uint64_t n, uint32_t low_bits, bool *fell_back) {
+int cr_repair_runs(crgpu_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, uint64_t n, uint32_t low_bits, bool *fell_back, CrRunHeads *heads) {
     *fell_back = false;
+    if (heads) heads->valid = false;
     if (n < 2 || low_bits == 0) return CRGPU_OK;
     uint32_t *d_flag = ctx->d_scalars + 52, *d_set = ctx->d_scalars + 53, *d_nlong = ctx->d_scalars + 54, *d_nmed = ctx->d_scalars + 55;
     const uint64_t n_words = (n + 63) / 64;
-    void *d_desc = nullptr, *d_long = nullptr, *d_med = nullptr;
+    void *d_desc = nullptr, *d_long = nullptr, *d_med = nullptr, *d_span = nullptr;
     CR_TRY(cr_pool_alloc(ctx, &d_desc, n_words * sizeof(unsigned long long)));
     struct Rel {
         crgpu_ctx *c;
         void *&p;
         ~Rel() { cr_pool_free(c, p); }
-    } rel{ctx, d_desc}, rel_long{ctx, d_long}, rel_med{ctx, d_med};
+    } rel{ctx, d_desc}, rel_long{ctx, d_long}, rel_med{ctx, d_med}, rel_span{ctx, d_span};
+    // run heads per tile for the caller's run-length pass (CrRunHeads): one count per span of k_find_descents, added up per tile
+    const uint64_t span = 64ull * FD_ITEMS, n_spans = (n + span - 1) / span;
+    bool count_heads = heads && heads->d_counts && heads->shift <= low_bits && heads->tile >= span && heads->tile % span == 0;
+    if (count_heads && cr_pool_alloc(ctx, &d_span, n_spans * sizeof(uint32_t)) != CRGPU_OK) {
+        d_span = nullptr;  // not fatal: the caller counts the heads itself
+        count_heads = false;
+    }
+    RhDev rh;
+    if (count_heads) {
+        rh.counts = heads->d_counts;
+        rh.tile = heads->tile;
+        rh.shift = heads->shift;
+    }
     // heads of the runs of more than 64 keys that need work (a run has at least 65 keys: at most n / 65 of them; capped)
     uint32_t long_cap = (uint32_t)std::min<uint64_t>(n / 65 + 1, 1u << 20);
     if (cr_pool_alloc(ctx, &d_long, (uint64_t)long_cap * sizeof(unsigned long long)) != CRGPU_OK) {
@@ -1421,19 +1550,22 @@ int cr_repair_runs(crgpu_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, uint64_t 
     {
         CrTimer t(ctx, CRGPU_T_SORT_HIST, n);  // booked beside the histogram slot: "sort, not a scatter pass"
         CR_HIP(ctx, hipMemsetAsync(d_flag, 0, 4 * sizeof(uint32_t), ctx->stream));
-        const uint64_t n_spans = (n + 64ull * FD_ITEMS - 1) / (64ull * FD_ITEMS);
         hipLaunchKernelGGL(k_find_descents, dim3(cr_grid(n_spans * 64u, 256, 256u * 8u)), dim3(256), 0, ctx->stream, d_keys, n, low_bits,
-                           (unsigned long long *)d_desc, d_set);
+                           (unsigned long long *)d_desc, d_set, rh.shift, (uint32_t *)d_span);
+        if (count_heads)
+            hipLaunchKernelGGL(k_tile_heads, dim3((uint32_t)((n + rh.tile - 1) / rh.tile)), dim3(256), 0, ctx->stream,
+                               (const uint32_t *)d_span, n_spans, rh.tile / span, rh.counts);
         const dim3 grid(cr_grid((n_words + RR_WORDS - 1) / RR_WORDS, 1, 256u * 8u));
 #define CR_REPAIR_LAUNCH(HV)                                                                                                          \
     hipLaunchKernelGGL(k_repair_runs<HV>, grid, dim3(256), 0, ctx->stream, d_keys, d_vals, n, low_bits,                                   \
-                       (const unsigned long long *)d_desc, n_words, d_flag, (unsigned long long *)d_med, d_nmed, med_cap);                \
+                       (const unsigned long long *)d_desc, n_words, d_flag, (unsigned long long *)d_med, d_nmed, med_cap, rh);            \
     if (med_cap)                                                                                                                          \
         hipLaunchKernelGGL(k_repair_medium_runs<HV>, dim3(256u * 8u), dim3(256), 0, ctx->stream, d_keys, d_vals, n, low_bits,             \
-                           (const unsigned long long *)d_med, d_nmed, med_cap, (unsigned long long *)d_long, d_nlong, long_cap, d_flag); \
+                           (const unsigned long long *)d_med, d_nmed, med_cap, (unsigned long long *)d_long, d_nlong, long_cap, d_flag,  \
+                           rh);                                                                                                           \
     if (long_cap)                                                                                                                         \
         hipLaunchKernelGGL(k_repair_long_runs<HV>, dim3(256u * 4u), dim3(256), 0, ctx->stream, d_keys, d_vals, n, low_bits,               \
-                           (const unsigned long long *)d_long, d_nlong, long_cap, d_flag)
+                           (const unsigned long long *)d_long, d_nlong, long_cap, d_flag, rh)
         if (d_vals) {
             CR_REPAIR_LAUNCH(true);
         } else {
@@ -1445,16 +1577,19 @@ int cr_repair_runs(crgpu_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, uint64_t 
     uint32_t flag = 0;
     CR_TRY(crgpu_memcpy_d2h(ctx, &flag, d_flag, sizeof(flag)));
     *fell_back = flag != 0;
+    if (heads) heads->valid = count_heads && !*fell_back;  // (a run too long for the repair: nobody adjusted the counts for it)
     return CRGPU_OK;
 }
-// the finishing step behind the passes on the top bits: CRGPU_SORT_FINISH=3 keeps round 2's k_order_runs (A/B)
-static int order_low_bits(crgpu_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, uint64_t n, uint32_t low_bits, bool *fell_back) {
+// the finishing step behind the passes on the top bits: CRGPU_SORT_FINISH=3 keeps round 2's k_order_runs (A/B; no run heads)
+static int order_low_bits(crgpu_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, uint64_t n, uint32_t low_bits, bool *fell_back,
+                          CrRunHeads *heads = nullptr) {
+    if (heads) heads->valid = false;
     const char *e = getenv("CRGPU_SORT_FINISH");
     if (e && atoi(e) == 3) return cr_order_runs_r02(ctx, d_keys, d_vals, n, low_bits, fell_back);
-    return cr_repair_runs(ctx, d_keys, d_vals, n, low_bits, fell_back);
+    return cr_repair_runs(ctx, d_keys, d_vals, n, low_bits, fell_back, heads);
 }
-int cr_order_runs(crgpu_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, uint64_t n, uint32_t low_bits, bool *fell_back) {
-    return order_low_bits(ctx, d_keys, d_vals, n, low_bits, fell_back);
+int cr_order_runs(crgpu_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, uint64_t n, uint32_t low_bits, bool *fell_back, CrRunHeads *heads) {
+    return order_low_bits(ctx, d_keys, d_vals, n, low_bits, fell_back, heads);
 }
 
 static int finish_runs(crgpu_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, uint64_t n, uint32_t low_bits, bool *fell_back) {

@@ -131,6 +131,7 @@ int crgpu_invalidate(crgpu_ctx *ctx);
 #define CRGPU_STAT_PROBE_SEGMENTS_WAVE 12      /* barcode segments the last probe-triplet computation ordered in registers (<= 64 molecules) */
 #define CRGPU_STAT_PROBE_SEGMENTS_WORKGROUP 13 /* ... in LDS, one workgroup each (<= 32768 molecules) */
 #define CRGPU_STAT_PROBE_SEGMENTS_GLOBAL 14    /* ... through the device radix sort (larger ones; all above CRGPU_PROBE_SEG_CAP) */
+#define CRGPU_STAT_RL_COUNTS_FROM_FINISH 15 /* count calls whose run-length pass took its tile counts from the finishing step of the sort */
 int crgpu_get_stat(crgpu_ctx *ctx, int which, uint64_t *value_out);
 /* ctx may be NULL: returns the message of the last failed crgpu_create on this thread. */
 const char *crgpu_last_error(const crgpu_ctx *ctx);
