@@ -138,6 +138,30 @@ class BcCorrectionMetrics(C.Structure):
                 ("effective_barcode_diversity", C.c_double)]
 
 
+ORDMAG_SAMPLES = 100
+
+
+class OrdmagResult(C.Structure):
+    """crgpu_ordmag_result"""
+    _fields_ = [
+        ("n_nonzero", C.c_uint64),
+        ("recovered_cells", C.c_int64),
+        ("recovered_boot", C.c_int64 * ORDMAG_SAMPLES),
+        ("loss_boot", C.c_double * ORDMAG_SAMPLES),
+        ("baseline_bc_idx", C.c_int64),
+        ("top_n_boot", C.c_int64 * ORDMAG_SAMPLES),
+        ("filtered_bcs_mean", C.c_double),
+        ("filtered_bcs_var", C.c_double),
+        ("filtered_bcs_cv", C.c_double),
+        ("filtered_bcs_lb", C.c_double),
+        ("filtered_bcs_ub", C.c_double),
+        ("filtered_bcs", C.c_int64),
+        ("filtered_bcs_cutoff", C.c_int64),
+        ("filtered_bcs_cutoff_set", C.c_int32),
+        ("estimated", C.c_int32),
+    ]
+
+
 # every symbol include/crgpu.h declares: (restype, argtypes)
 _vp, _u8p, _u32, _u64, _i, _dbl = C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_double
 SYMBOLS = {
@@ -227,6 +251,13 @@ SYMBOLS = {
     "crgpu_sum_matrices_dev": (_i, [_vp, C.POINTER(MatrixDevView), C.POINTER(MatrixDevView), C.POINTER(C.POINTER(MatrixDevView))]),
     "crgpu_select_barcodes_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u64, C.POINTER(C.POINTER(MatrixDevView))]),
     "crgpu_matrix_dev_free": (None, [_vp, C.POINTER(MatrixDevView)]),
+    "crgpu_matrix_dev_column_sums": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, _vp]),
+    "crgpu_ordmag_candidates": (_i, [C.c_int64, _vp, _u32, C.POINTER(_u32)]),
+    "crgpu_call_cells_ordmag_dev": (_i, [_vp, _vp, _u64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(OrdmagResult), C.POINTER(_vp),
+                                         C.POINTER(_u64)]),
+    "crgpu_cell_ranks_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u64, _vp]),
+    "crgpu_select_barcodes_cols_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u64, C.POINTER(C.POINTER(MatrixDevView))]),
+    "crgpu_mt19937_stream_dev": (_i, [_vp, _u32, _u64, _vp, C.POINTER(_u64), C.POINTER(_dbl)]),
     "crgpu_matrix_dev_download": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _vp, _vp, _vp]),
     "crgpu_count": (_i, [_vp, C.POINTER(Records), _u32, C.POINTER(C.POINTER(MatrixView))]),
     "crgpu_set_feature_pattern": (_i, [_vp, _i, C.c_char_p, _u32, _u32, _vp, _vp]),

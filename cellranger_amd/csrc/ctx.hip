@@ -80,6 +80,14 @@ const std::vector<AbiStruct> &abi_table() {
               ABI_F(crgpu_synth_params, n_total), ABI_F(crgpu_synth_params, n_libs)),
         ABI_S(crgpu_synth_out, ABI_F(crgpu_synth_out, cb), ABI_F(crgpu_synth_out, cb_qualn), ABI_F(crgpu_synth_out, umi),
               ABI_F(crgpu_synth_out, umi_qualn), ABI_F(crgpu_synth_out, feature), ABI_F(crgpu_synth_out, flags)),
+        ABI_S(crgpu_ordmag_result, ABI_F(crgpu_ordmag_result, n_nonzero), ABI_F(crgpu_ordmag_result, recovered_cells),
+              ABI_F(crgpu_ordmag_result, recovered_boot), ABI_F(crgpu_ordmag_result, loss_boot),
+              ABI_F(crgpu_ordmag_result, baseline_bc_idx), ABI_F(crgpu_ordmag_result, top_n_boot),
+              ABI_F(crgpu_ordmag_result, filtered_bcs_mean), ABI_F(crgpu_ordmag_result, filtered_bcs_var),
+              ABI_F(crgpu_ordmag_result, filtered_bcs_cv), ABI_F(crgpu_ordmag_result, filtered_bcs_lb),
+              ABI_F(crgpu_ordmag_result, filtered_bcs_ub), ABI_F(crgpu_ordmag_result, filtered_bcs),
+              ABI_F(crgpu_ordmag_result, filtered_bcs_cutoff), ABI_F(crgpu_ordmag_result, filtered_bcs_cutoff_set),
+              ABI_F(crgpu_ordmag_result, estimated)),
     };
     return t;
 }
@@ -157,6 +165,7 @@ extern "C" int crgpu_create(crgpu_ctx **out, int device_id, int n_ranks, int ran
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && total_b) ctx->pool_budget = (uint64_t)total_b / 2;
     }
     if (const char *cap = getenv("CRGPU_PROBE_SEG_CAP")) ctx->probe_seg_cap = (uint32_t)strtoul(cap, nullptr, 10);  // tests: force the global route
+    if (const char *b = getenv("CRGPU_ORDMAG_BATCH")) ctx->ordmag_batch = (uint32_t)strtoul(b, nullptr, 10);  // tests: small batches of the cell call
     // probability(q) = 10^(-(q-33)/10) computed on the HOST with libm pow, exactly as the
     // reference does per call (corrector.rs:167-171), for every 7-bit quality character.
     double ptab[128];

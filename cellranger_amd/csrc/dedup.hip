@@ -2863,12 +2863,20 @@ __global__ __launch_bounds__(256) void k_offsets_to_indptr(const uint32_t *__res
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n; i += stride)
         indptr[i] = i < n ? (long long)off[i] : (long long)total;
 }
+// a column position outside [0, V) (a device list is not checked on the host) is reported through *bad and reads nothing
 __global__ __launch_bounds__(256) void k_selected_lengths(const long long *__restrict__ indptr, const uint64_t *__restrict__ cols,
-                                                          uint64_t n_sel, const uint32_t *__restrict__ rank_in,
-                                                          uint32_t *__restrict__ len, uint32_t *__restrict__ rank_out) {
+                                                          uint64_t n_sel, uint64_t V, const uint32_t *__restrict__ rank_in,
+                                                          uint32_t *__restrict__ len, uint32_t *__restrict__ rank_out,
+                                                          uint32_t *__restrict__ bad) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n_sel; k += stride) {
         const uint64_t c = cols[k];
+        if (c >= V) {
+            *bad = 1u;
+            len[k] = 0u;
+            rank_out[k] = 0u;
+            continue;
+        }
         len[k] = (uint32_t)(indptr[c + 1] - indptr[c]);
         rank_out[k] = rank_in[c];
     }
@@ -2962,7 +2970,47 @@ extern "C" int crgpu_sum_matrices_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *a,
     return CRGPU_OK;
 }
 
-// CountMatrix.select_barcodes (matrix.py:860-875): the columns `cols` (host array of column positions) in the given order.
+// CountMatrix.select_barcodes (matrix.py:860-875): the columns at the positions d_cols (device) in the given order.
+static int select_columns_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *a, const uint64_t *d_cols, uint64_t n_cols, const char *who,
+                              crgpu_matrix_dev **out) {
+    DevBuf len_b, rank_b;
+    CR_TRY(dmalloc(ctx, len_b, (n_cols + 1) * sizeof(uint32_t)));
+    CR_TRY(dmalloc(ctx, rank_b, (n_cols ? n_cols : 1) * sizeof(uint32_t)));
+    uint32_t *d_total = ctx->d_scalars + 16, *d_bad = ctx->d_scalars + 48, total = 0, bad = 0;
+    const long long *pa = (const long long *)a->d_indptr;
+    {
+        CrTimer t(ctx, CRGPU_T_MATRIX, n_cols);
+        CR_HIP(ctx, hipMemsetAsync(d_bad, 0, sizeof(uint32_t), ctx->stream));
+        if (n_cols)
+            hipLaunchKernelGGL(k_selected_lengths, dim3(cr_grid(n_cols, 256)), dim3(256), 0, ctx->stream, pa, d_cols, n_cols, a->n_barcodes,
+                               a->d_barcode_rank, len_b.as<uint32_t>(), rank_b.as<uint32_t>(), d_bad);
+        CR_HIP(ctx, hipGetLastError());
+        CR_TRY(cr_scan_small(ctx, len_b.as<uint32_t>(), n_cols, d_total));
+    }
+    CR_TRY(read_u32(ctx, d_bad, &bad));
+    CR_REQUIRE(ctx, !bad, CRGPU_EINVAL, "%s: a column is out of range", who);
+    CR_TRY(read_u32(ctx, d_total, &total));
+    MatrixDevImpl *m = nullptr;
+    CR_TRY(new_matrix_dev(ctx, n_cols, total, &m));
+    {
+        CrTimer t(ctx, CRGPU_T_MATRIX);
+        if (n_cols) {
+            CR_HIP(ctx, hipMemcpyAsync(m->d_rank, rank_b.p, n_cols * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+            hipLaunchKernelGGL(k_copy_columns, dim3(cr_grid(n_cols * 64, 256)), dim3(256), 0, ctx->stream, pa, d_cols, n_cols,
+                               len_b.as<uint32_t>(), a->d_indices, a->d_data, m->d_indices, m->d_data);
+        }
+        hipLaunchKernelGGL(k_offsets_to_indptr, dim3(cr_grid(n_cols + 1, 256)), dim3(256), 0, ctx->stream, len_b.as<uint32_t>(), n_cols,
+                           total, m->d_indptr);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
+            crgpu_matrix_dev_free(ctx, &m->view);
+            return cr_fail(ctx, CRGPU_EHIP, "%s: kernel failed", who);
+        }
+    }
+    *out = &m->view;
+    return CRGPU_OK;
+}
+
+// ... with `cols` a host array of column positions
 extern "C" int crgpu_select_barcodes_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *a, const uint64_t *cols, uint64_t n_cols,
                                          crgpu_matrix_dev **out) {
     if (!ctx || !out) return CRGPU_EINVAL;
@@ -2972,41 +3020,20 @@ extern "C" int crgpu_select_barcodes_dev(crgpu_ctx *ctx, const crgpu_matrix_dev 
     for (uint64_t k = 0; k < n_cols; k++)
         CR_REQUIRE(ctx, cols[k] < a->n_barcodes, CRGPU_EINVAL, "crgpu_select_barcodes_dev: column %llu out of range",
                    (unsigned long long)cols[k]);
-    DevBuf cols_b, len_b, rank_b;
+    DevBuf cols_b;
     CR_TRY(dmalloc(ctx, cols_b, (n_cols ? n_cols : 1) * sizeof(uint64_t)));
-    CR_TRY(dmalloc(ctx, len_b, (n_cols + 1) * sizeof(uint32_t)));
-    CR_TRY(dmalloc(ctx, rank_b, (n_cols ? n_cols : 1) * sizeof(uint32_t)));
-    uint32_t *d_total = ctx->d_scalars + 16, total = 0;
-    const long long *pa = (const long long *)a->d_indptr;
-    {
-        CrTimer t(ctx, CRGPU_T_MATRIX, n_cols);
-        if (n_cols) {
-            CR_HIP(ctx, hipMemcpyAsync(cols_b.p, cols, n_cols * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-            hipLaunchKernelGGL(k_selected_lengths, dim3(cr_grid(n_cols, 256)), dim3(256), 0, ctx->stream, pa, cols_b.as<uint64_t>(), n_cols,
-                               a->d_barcode_rank, len_b.as<uint32_t>(), rank_b.as<uint32_t>());
-        }
-        CR_HIP(ctx, hipGetLastError());
-        CR_TRY(cr_scan_small(ctx, len_b.as<uint32_t>(), n_cols, d_total));
-    }
-    CR_TRY(read_u32(ctx, d_total, &total));
-    MatrixDevImpl *m = nullptr;
-    CR_TRY(new_matrix_dev(ctx, n_cols, total, &m));
-    {
-        CrTimer t(ctx, CRGPU_T_MATRIX);
-        if (n_cols) {
-            CR_HIP(ctx, hipMemcpyAsync(m->d_rank, rank_b.p, n_cols * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
-            hipLaunchKernelGGL(k_copy_columns, dim3(cr_grid(n_cols * 64, 256)), dim3(256), 0, ctx->stream, pa, cols_b.as<uint64_t>(), n_cols,
-                               len_b.as<uint32_t>(), a->d_indices, a->d_data, m->d_indices, m->d_data);
-        }
-        hipLaunchKernelGGL(k_offsets_to_indptr, dim3(cr_grid(n_cols + 1, 256)), dim3(256), 0, ctx->stream, len_b.as<uint32_t>(), n_cols,
-                           total, m->d_indptr);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
-            crgpu_matrix_dev_free(ctx, &m->view);
-            return cr_fail(ctx, CRGPU_EHIP, "crgpu_select_barcodes_dev: kernel failed");
-        }
-    }
-    *out = &m->view;
-    return CRGPU_OK;
+    if (n_cols) CR_HIP(ctx, hipMemcpyAsync(cols_b.p, cols, n_cols * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    return select_columns_dev(ctx, a, cols_b.as<uint64_t>(), n_cols, "crgpu_select_barcodes_dev", out);
+}
+
+// ... with a device list (the called cells of crgpu_call_cells_ordmag_dev: the filtered matrix)
+extern "C" int crgpu_select_barcodes_cols_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *a, const uint64_t *d_cols, uint64_t n_cols,
+                                              crgpu_matrix_dev **out) {
+    if (!ctx || !out) return CRGPU_EINVAL;
+    CR_ENTER(ctx);
+    *out = nullptr;
+    CR_REQUIRE(ctx, a && (d_cols || n_cols == 0), CRGPU_EINVAL, "crgpu_select_barcodes_cols_dev: NULL argument");
+    return select_columns_dev(ctx, a, d_cols, n_cols, "crgpu_select_barcodes_cols_dev", out);
 }
 
 extern "C" void crgpu_matrix_dev_free(crgpu_ctx *ctx, crgpu_matrix_dev *mv) {
@@ -3328,3 +3355,4 @@ extern "C" int crgpu_trim_molecule_barcodes_dev(crgpu_ctx *ctx, uint64_t *d_barc
 }
 
 #include "probe_counts.h"
+#include "cell_calling.h"

@@ -220,6 +220,57 @@ class MatrixDev:
             pass
 
 
+class CellCall:
+    """Result of Context.call_cells_ordmag: `cols` = the called columns (DeviceArray of u64, ascending positions in the count
+    vector / the matrix the counts came from), `n_cells`, `metrics` = crgpu_ordmag_result as a dict (BarcodeFilterResults of
+    cell_calling_helpers.py:832-955 plus the bootstrap's per-sample values)."""
+
+    def __init__(self, ctx, cols, n_cells, res, matrix=None):
+        self.ctx, self.cols, self.n_cells, self._matrix = ctx, cols, n_cells, matrix
+        m = {}
+        for name, _ in _lib.OrdmagResult._fields_:
+            v = getattr(res, name)
+            m[name] = np.array(v[:]) if hasattr(v, "__len__") else v
+        m["filtered_bcs_cutoff"] = m["filtered_bcs_cutoff"] if m.pop("filtered_bcs_cutoff_set") else None
+        m["estimated"] = bool(m["estimated"])
+        self.metrics = m
+
+    def cols_host(self):
+        return self.cols.to_host(self.n_cells)
+
+    def ranks_dev(self, m=None):
+        """canonical ranks of the called cells (DeviceArray of u32, strictly ascending): what Counts.probe_metrics and
+        Counts.probe_matrix take; `m` = the MatrixDev whose columns were counted (default: the one the call was made on)"""
+        m = m or self._matrix
+        if m is None:
+            raise ValueError("the call was made on a bare count vector: pass the MatrixDev its columns belong to")
+        out = self.ctx.empty(self.n_cells, np.uint32)
+        self.ctx._check(self.ctx.L.crgpu_cell_ranks_dev(self.ctx.h, m._mv, _p(self.cols), self.n_cells, _p(out)))
+        return out
+
+    @property
+    def ranks(self):
+        return self.ranks_dev().to_host(self.n_cells)
+
+    def filtered_matrix(self, m=None):
+        """the filtered feature-barcode matrix: the called columns of `m` (MatrixDev), selected on the device"""
+        m = m or self._matrix
+        if m is None:
+            raise ValueError("the call was made on a bare count vector: pass the MatrixDev to filter")
+        mv = C.POINTER(_lib.MatrixDevView)()
+        self.ctx._check(self.ctx.L.crgpu_select_barcodes_cols_dev(self.ctx.h, m._mv, _p(self.cols), self.n_cells, C.byref(mv)))
+        return MatrixDev(self.ctx, mv)
+
+
+def ordmag_candidates(max_expected_cells=1 << 18):
+    """the recovered-cells grid of estimate_recovered_cells_ordmag (cell_calling_helpers.py:879-880); host only"""
+    out, n = np.zeros(2000, np.int64), C.c_uint32()
+    rc = _lib.load().crgpu_ordmag_candidates(max_expected_cells, ptr(out), len(out), C.byref(n))
+    if rc != 0:
+        raise _lib.CrgpuError(rc, "crgpu_ordmag_candidates")
+    return out[: n.value].copy()
+
+
 class Counts:
     """crgpu_counts: sorted (barcode, feature, count) triplets + the molecule table."""
 
@@ -727,6 +778,42 @@ class Context:
         mv = C.POINTER(_lib.MatrixDevView)()
         self._check(self.L.crgpu_select_barcodes_dev(self.h, m._mv, ptr(cols), len(cols), C.byref(mv)))
         return MatrixDev(self, mv)
+
+    # ---- cell calling ----------------------------------------------------------------------------------
+    def column_sums(self, m, feature_mask=None):
+        """get_counts_per_bc of a feature sub-matrix: per column of the MatrixDev `m` the sum over the features whose
+        feature_mask entry is non-zero (None: all) -> DeviceArray of u32"""
+        out = self.empty(m.n_barcodes, np.uint32)
+        mask = None if feature_mask is None else np.ascontiguousarray(np.asarray(feature_mask) != 0, dtype=np.uint8)
+        self._check(self.L.crgpu_matrix_dev_column_sums(self.h, m._mv, ptr(mask), 0 if mask is None else len(mask), _p(out)))
+        return out
+
+    def call_cells_ordmag(self, counts, recovered_cells=None, max_expected_cells=1 << 18, force_cells=None):
+        """filter_cellular_barcodes_ordmag (force_cells: filter_cellular_barcodes_fixed_cutoff) of one GEM group on the device.
+        counts: a MatrixDev (its column sums over all features are taken), a DeviceArray of u32 or a numpy array of UMI totals
+        per column -> CellCall"""
+        matrix = counts if isinstance(counts, MatrixDev) else None
+        if matrix is not None:
+            d = self.column_sums(matrix)
+        elif isinstance(counts, DeviceArray):
+            d = counts
+        else:
+            d = self.upload(np.ascontiguousarray(counts, dtype=np.uint32))
+        res, cols, n = _lib.OrdmagResult(), C.c_void_p(), C.c_uint64()
+        self._check(self.L.crgpu_call_cells_ordmag_dev(self.h, _p(d), d.size, recovered_cells or 0, max_expected_cells,
+                                                       force_cells or 0, C.byref(res), C.byref(cols), C.byref(n)))
+        # no barcode called: an empty list of our own, so that .ranks / .filtered_matrix work on an all-zero well, too
+        d_cols = DeviceArray(self, n.value, np.uint64, adopt=cols.value) if cols.value else self.empty(0, np.uint64)
+        return CellCall(self, d_cols, n.value, res, matrix)
+
+    def mt19937_stream(self, seed, n_words):
+        """the generator kernel of the cell call on its own: (DeviceArray of the first n_words outputs of
+        np.random.RandomState(seed)'s raw stream, rounded down to whole chunks; kernel milliseconds)"""
+        out = self.empty(max(n_words, 1), np.uint32)
+        n, ms = C.c_uint64(), C.c_double()
+        self._check(self.L.crgpu_mt19937_stream_dev(self.h, seed, n_words, _p(out), C.byref(n), C.byref(ms)))
+        out.shape = (n.value,)
+        return out, ms.value
 
     def trim_molecule_barcodes(self, d_barcode_idx, n_molecules, n_barcodes, pass_filter_idx=None, pass_only=False, offset=0):
         """MERGE_MOLECULES on barcode_idx (crgpu.h): rewrites the device column in place; returns (retained old indices,

@@ -632,6 +632,69 @@ int crgpu_select_barcodes_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *a, const u
 int crgpu_matrix_dev_download(crgpu_ctx *ctx, const crgpu_matrix_dev *m, uint32_t *rank_out, int64_t *indptr_out,
                               int32_t *indices_out, int32_t *data_out);
 
+/* ---- cell calling: the order-of-magnitude ("OrdMag") barcode filter and the filtered matrix ----------------------------------
+ * Replaces the initial cell call of FILTER_BARCODES: filter_cellular_barcodes_ordmag with estimate_recovered_cells_ordmag,
+ * find_within_ordmag and summarize_bootstrapped_top_n (lib/python/cellranger/cell_calling_helpers.py:832-955, reached from
+ * call_initial_cells / _call_cells_by_gem_group, :435-572) and filter_cellular_barcodes_fixed_cutoff (:958-964), for ONE
+ * GEM group.  The bootstrap's random stream is np.random.RandomState(0).choice -- MT19937 seeded with init_genrand(0), each
+ * 32-bit output masked and rejected -- generated on the device, so every number below equals the reference's.
+ *   crgpu_matrix_dev_column_sums  get_counts_per_bc of a feature sub-matrix: d_sums_out[c] (device, u32[n_barcodes]) = the sum
+ *                                 of column c over the features f with feature_mask[f] != 0 (host, n_features bytes; NULL: all
+ *                                 rows, n_features is then ignored).  CRGPU_ERANGE when a sum does not fit 32 bits,
+ *                                 CRGPU_EINVAL when a masked matrix holds a row >= n_features.
+ *   crgpu_ordmag_candidates       the recovered-cells grid of the estimate (:879-880): unique(round(2 ^ linspace(1,
+ *                                 log2(max_expected_cells), 2000))), ascending.  Host only, no context.  out may be NULL
+ *                                 (size query); CRGPU_ERANGE (with *n_out set) when cap is too small; max_expected_cells >= 2.
+ *   crgpu_call_cells_ordmag_dev   d_bc_counts: device u32[V], the UMI total of every column (V < 2^31).
+ *       recovered_cells <= 0      estimated: 100 bootstrap samples, each scored against the whole grid up to
+ *                                 max_expected_cells (the caller passes min(get_empty_drops_range(...)[0], 1 << 18));
+ *                                 2 .. 2^30, else CRGPU_EINVAL;
+ *       recovered_cells  > 0      max(given, 50) is used, no sample is drawn for the estimate;
+ *       force_cells      > 0      the fixed cutoff: the top min(force_cells, N) barcodes, no bootstrap at all.
+ *                                 then 100 more samples from the same stream give top_n_boot and its summary.
+ *     *d_cell_cols (library-owned: release it with crgpu_free) = the called columns, ascending positions in d_bc_counts --
+ *     with the counts of a crgpu_matrix_dev, positions in its d_barcode_rank; *n_cells their number.  Among equal counts the
+ *     larger column wins (a stable ascending argsort, reversed).  No non-zero count: no cells, a zeroed result, no error.
+ *     Samples are processed in batches whose temporaries stay bounded; CRGPU_ORDMAG_BATCH=<n> in the environment when the
+ *     context is created (tests) fixes the samples per batch.  The result does not depend on it.
+ *   crgpu_cell_ranks_dev          d_ranks_out[k] (device, u32[n_cells]) = m->d_barcode_rank[d_cell_cols[k]]: the canonical ranks
+ *                                 crgpu_probe_metrics_dev and crgpu_assemble_probe_matrix_dev take (strictly ascending).
+ *   crgpu_select_barcodes_cols_dev  crgpu_select_barcodes_dev with a DEVICE column list: the filtered matrix without a round
+ *                                 trip of the columns.  CRGPU_EINVAL when a column is out of range.
+ * EmptyDrops, the gradient / targeted / manual methods and the filters that follow the initial call are not covered. */
+#define CRGPU_ORDMAG_SAMPLES 100 /* ORDMAG_NUM_BOOTSTRAP_SAMPLES */
+struct crgpu_ordmag_result {
+    uint64_t n_nonzero;            /* N: barcodes with a non-zero count */
+    int64_t recovered_cells;       /* the value used (estimated or given, at least 50); 0 with force_cells or N == 0 */
+    int64_t recovered_boot[100];   /* estimate: the grid value of least loss per sample (zeros when not estimated) */
+    double loss_boot[100];         /* ... and that loss */
+    int64_t baseline_bc_idx;       /* min(round(recovered_cells * (1 - 0.99)), N - 1) */
+    int64_t top_n_boot[100];       /* find_within_ordmag of every sample of the call */
+    double filtered_bcs_mean, filtered_bcs_var, filtered_bcs_cv;
+    double filtered_bcs_lb, filtered_bcs_ub; /* NaN when the variance is 0, as scipy's norm.ppf with scale 0 */
+    int64_t filtered_bcs;          /* barcodes called (== *n_cells) */
+    int64_t filtered_bcs_cutoff;   /* valid when filtered_bcs_cutoff_set != 0 */
+    int32_t filtered_bcs_cutoff_set;
+    int32_t estimated;             /* 1: recovered_cells was estimated here */
+};
+typedef struct crgpu_ordmag_result crgpu_ordmag_result; /* (declared by tag: crgpu_abi_layout knows it as "crgpu_ordmag_result") */
+int crgpu_matrix_dev_column_sums(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const uint8_t *feature_mask, uint32_t n_features,
+                                 uint32_t *d_sums_out);
+int crgpu_ordmag_candidates(int64_t max_expected_cells, int64_t *out, uint32_t cap, uint32_t *n_out);
+int crgpu_call_cells_ordmag_dev(crgpu_ctx *ctx, const uint32_t *d_bc_counts, uint64_t V, int64_t recovered_cells,
+                                int64_t max_expected_cells, int64_t force_cells, crgpu_ordmag_result *res, uint64_t **d_cell_cols,
+                                uint64_t *n_cells);
+int crgpu_cell_ranks_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const uint64_t *d_cell_cols, uint64_t n_cells,
+                         uint32_t *d_ranks_out);
+int crgpu_select_barcodes_cols_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *a, const uint64_t *d_cols, uint64_t n_cols,
+                                   crgpu_matrix_dev **out);
+/* Test and measurement hook, NOT a stable interface (it may change or go without a version bump; a host has no use for it):
+ * the 32-bit output stream of MT19937 after init_genrand(seed) -- np.random.RandomState(seed)'s
+ * raw stream -- written to d_out (device) by the generator kernel of the cell call; *ms_out (nullable) = the kernel's time.
+ * n_words is rounded down to a multiple of the kernel's chunk of 3632 words; *n_written_out tells how many came. */
+int crgpu_mt19937_stream_dev(crgpu_ctx *ctx, uint32_t seed, uint64_t n_words, uint32_t *d_out, uint64_t *n_written_out,
+                             double *ms_out);
+
 /* one-call convenience (single GPU): build keys -> dedup -> matrix */
 int crgpu_count(crgpu_ctx *ctx, const crgpu_records *recs, uint32_t n_features, crgpu_matrix **out);
 /* The count entry of SURVEY.md 8(b) for a host that holds its records in HOST memory (the Rust stage code after STAR

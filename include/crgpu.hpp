@@ -10,6 +10,7 @@
 //                           compile_pattern
 //   crgpu::BarcodeIndex     cr_types/src/barcode_index.rs:14-53
 //   crgpu::CountMatrix      cr_h5/src/count_matrix.rs:382-448, cr_lib/src/stages/write_matrix_market.rs:80-122
+//   crgpu::filter_cellular_barcodes_ordmag / _fixed_cutoff  lib/python/cellranger/cell_calling_helpers.py:864-964 (Python there)
 //
 // Errors are C++ exceptions carrying crgpu_last_error (the Rust returns anyhow::Result); nothing here
 // computes on the CPU: every result comes from libcrgpu, and construction fails without a gfx950 device.
@@ -456,5 +457,49 @@ class CountMatrix {
     Context &ctx_;
     crgpu_matrix *m_ = nullptr;
 };
+
+/// filter_cellular_barcodes_ordmag (lib/python/cellranger/cell_calling_helpers.py:864-955) of one GEM group: bc_counts = the
+/// UMI total of every matrix column, recovered_cells = std::nullopt to estimate it (the grid then ends at max_expected_cells).
+/// Returns (top_bc_idx: the called columns, ascending; metrics: BarcodeFilterResults plus the bootstrap's per-sample values,
+/// the C struct itself).  The third element of the reference's tuple, the warning for all-zero counts, is
+/// `metrics.n_nonzero == 0`.
+static_assert(sizeof(crgpu_ordmag_result) == 2488, "crgpu_ordmag_result changed: bump CRGPU_ABI_VERSION and every binding");
+struct CellCall {
+    std::vector<uint64_t> top_bc_idx;
+    crgpu_ordmag_result metrics;
+};
+namespace detail {
+inline CellCall call_cells(Context &ctx, const std::vector<uint32_t> &bc_counts, int64_t recovered_cells, int64_t max_expected_cells,
+                           int64_t force_cells) {
+    CellCall out{};
+    void *d_counts = nullptr;
+    uint64_t *d_cols = nullptr, n = 0;
+    const size_t bytes = bc_counts.size() * sizeof(uint32_t);
+    if (bytes) {
+        ctx.check(crgpu_malloc(ctx.get(), &d_counts, bytes));
+        int rc = crgpu_memcpy_h2d(ctx.get(), d_counts, bc_counts.data(), bytes);
+        if (rc == CRGPU_OK)
+            rc = crgpu_call_cells_ordmag_dev(ctx.get(), (const uint32_t *)d_counts, bc_counts.size(), recovered_cells, max_expected_cells,
+                                             force_cells, &out.metrics, &d_cols, &n);
+        if (rc == CRGPU_OK && n) {
+            out.top_bc_idx.resize(n);
+            rc = crgpu_memcpy_d2h(ctx.get(), out.top_bc_idx.data(), d_cols, n * sizeof(uint64_t));
+        }
+        crgpu_free(ctx.get(), d_counts);
+        if (d_cols) crgpu_free(ctx.get(), d_cols);
+        ctx.check(rc);
+    }
+    return out;
+}
+}  // namespace detail
+inline CellCall filter_cellular_barcodes_ordmag(Context &ctx, const std::vector<uint32_t> &bc_counts, std::optional<int64_t> recovered_cells,
+                                                int64_t max_expected_cells = 1 << 18) {
+    return detail::call_cells(ctx, bc_counts, recovered_cells ? std::max<int64_t>(*recovered_cells, 1) : 0, max_expected_cells, 0);
+}
+/// filter_cellular_barcodes_fixed_cutoff (:958-964): the top min(cutoff, non-zero barcodes) columns
+inline CellCall filter_cellular_barcodes_fixed_cutoff(Context &ctx, const std::vector<uint32_t> &bc_counts, int64_t cutoff) {
+    if (cutoff <= 0) throw Error(CRGPU_EINVAL, "filter_cellular_barcodes_fixed_cutoff: cutoff must be positive");
+    return detail::call_cells(ctx, bc_counts, 0, 1 << 18, cutoff);
+}
 
 }  // namespace crgpu
