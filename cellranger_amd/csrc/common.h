@@ -169,7 +169,7 @@ struct crgpu_ctx {
     // second in-order stream + fork / join events: the count stage runs the search for low-support candidates beside the
     // UMI correction (dedup.hip, CrFork); created with the context, idle otherwise
     hipStream_t stream2 = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_aux = nullptr;
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     std::string err;
     std::recursive_mutex mu;  // every entry point holds it (CR_ENTER): calls of several host threads are serialised
     int n_ranks = 1, rank = 0;
@@ -292,8 +292,6 @@ int cr_comm_exchange_counts(crgpu_ctx *ctx, int local_rc, const uint64_t *send_c
 int cr_comm_test_failure(crgpu_ctx *ctx);
 int cr_comm_alltoallv(crgpu_ctx *ctx, const void *d_send, const uint64_t *send_off, const uint64_t *send_bytes, void *d_recv,
                       const uint64_t *recv_off, const uint64_t *recv_bytes);
-int cr_partition_by_payload(crgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, const uint32_t *d_vin, uint32_t *d_vout,
-                            uint64_t n, uint32_t shift);
 int cr_partition_by_owner_kv(crgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, const uint32_t *d_vin, uint32_t *d_vout,
                              uint64_t n, uint32_t sh_bc, uint32_t n_ranks, const uint32_t *bounds, uint64_t *counts_out);
 void cr_set_thread_error(const char *msg);
@@ -326,7 +324,6 @@ void cr_drop_miss_records(crgpu_ctx *ctx, MissRecords &r);  // one set
 bool cr_sweep_plan(uint32_t lo_bit, uint32_t hi_bit, SweepPlan *plan, uint32_t *widths);
 // low bits of a molecule key of total_bits that the radix passes leave to the finishing pass (0: none)
 uint32_t cr_sort_low_bits(uint32_t total_bits, uint32_t umi_bits);
-bool cr_sort_finish_experiment();  // CRGPU_SORT_FINISH=1: the 16-bit finishing pass of round 2 instead of k_order_runs
 // Run heads as a by-product of the finishing step: the number of keys i with i == 0 or (key[i] >> shift) != (key[i - 1] >> shift)
 // in every tile of `tile` keys of the ORDERED buffer, for the run-length pass that follows (dedup.hip, run_lengths).
 // k_find_descents counts them on the keys as they are before the repair, every repair adds what it changes.
@@ -334,7 +331,7 @@ struct CrRunHeads {
     uint32_t shift;      // in: at most low_bits (so that a run of equal top bits begins and ends with a head whatever its order)
     uint64_t tile;       // in: keys per tile, a multiple of the 512 keys a wave of k_find_descents takes at a time
     uint32_t *d_counts;  // in: ceil(n / tile) device words
-    bool valid;          // out: d_counts holds the counts (never when *fell_back, or when another finishing step ran)
+    bool valid;          // out: d_counts holds the counts (never when *fell_back)
 };
 int cr_order_runs(crgpu_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, uint64_t n, uint32_t low_bits, bool *fell_back,
                   CrRunHeads *heads = nullptr);
@@ -381,12 +378,10 @@ static inline uint32_t cr_grid(uint64_t n, uint32_t block, uint32_t max_blocks =
 // internal entry points shared between translation units
 int cr_radix_sort_u64(crgpu_ctx *ctx, uint64_t *d_keys, uint64_t *d_tmp, uint32_t *d_vals, uint32_t *d_vals_tmp,
                       uint64_t n, uint32_t lo_bit, uint32_t hi_bit, bool *result_in_tmp);
-// sort on the top key bits only when that saves passes: *low_left low bits are left to cr_finish_emit (0: fully sorted)
+// sort on the top key bits only when that saves passes: *low_left low bits are left to cr_order_runs (0: fully sorted)
 int cr_radix_sort_u64_top(crgpu_ctx *ctx, uint64_t *d_keys, uint64_t *d_tmp, uint32_t *d_vals, uint32_t *d_vals_tmp,
                           uint64_t n, uint32_t hi_bit, bool *result_in_tmp, uint32_t *low_left);
 int cr_radix_sort_u64_full(crgpu_ctx *ctx, uint64_t *d_keys, uint64_t *d_tmp, uint32_t *d_vals, uint32_t *d_vals_tmp, uint64_t n,
                            uint32_t hi_bit, bool *result_in_tmp);
-int cr_finish_emit(crgpu_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, uint64_t n, uint32_t low_bits, uint64_t *d_ukey,
-                   uint32_t *d_upos, uint64_t *nd_out, bool *fell_back);
 int cr_radix_sort_u32(crgpu_ctx *ctx, uint32_t *d_keys, uint32_t *d_tmp, uint32_t *d_vals, uint32_t *d_vals_tmp,
                       uint64_t n, uint32_t lo_bit, uint32_t hi_bit, bool *result_in_tmp);

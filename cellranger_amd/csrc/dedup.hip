@@ -833,25 +833,6 @@ __device__ __forceinline__ uint32_t rep_source(uint32_t min_raw, uint32_t K, uin
 }
 
 // ---- functors --------------------------------------------------------------------------------------
-struct HeadFlag {  // first element of a run of equal (key >> shift)
-    const uint64_t *keys;
-    uint32_t shift;
-    __device__ __forceinline__ bool operator()(uint64_t i) const {
-        const uint64_t prev = keys[i ? i - 1 : 0];  // no load behind a branch
-        return (i == 0) | ((keys[i] >> shift) != (prev >> shift));
-    }
-};
-struct EmitRun {  // distinct key + start position of its run
-    const uint64_t *keys;
-    uint64_t *ukey;
-    uint32_t *upos;
-    typedef uint64_t Pre;
-    __device__ __forceinline__ Pre pre(uint64_t i) const { return keys[i]; }
-    __device__ __forceinline__ void operator()(uint64_t i, uint32_t o, Pre key) const {
-        ukey[o] = key;
-        upos[o] = (uint32_t)i;
-    }
-};
 // targeted-panel filter (mark_dups.rs:311-320): a corrected key of an on-target feature whose read count stays below
 // the threshold yields no UmiCount (and its reads carry is_filtered_target_umi); min_reads == 0: None
 struct TargetFilter {
@@ -937,17 +918,10 @@ struct EmitMol {
         if (mprobe) mprobe[o] = probe[rep_read[mi != NONE32 ? mi : (uint32_t)k]];
     }
 };
-struct EmitTriplet {
-    const uint64_t *mkeys;
-    uint32_t *tpos;
-    struct Pre {};
-    __device__ __forceinline__ Pre pre(uint64_t) const { return Pre(); }
-    __device__ __forceinline__ void operator()(uint64_t i, uint32_t o, Pre) const { tpos[o] = (uint32_t)i; }
-};
 
 // ---- run lengths of the sorted keys (DupBuilder::observe): distinct keys + the start of every run -------------------------
-// The generic compaction evaluates HeadFlag with two loads per key (keys[i], keys[i - 1]) and EmitRun with a third; these
-// passes are bound by load instructions in flight, not by bytes.  With the wave-blocked layout (a wave owns 64 * CP_ITEMS
+// These passes are bound by load instructions in flight, not by bytes (the generic compaction took three loads per key:
+// profiles/r02_mol_trip_ab.txt).  With the wave-blocked layout (a wave owns 64 * CP_ITEMS
 // consecutive keys of a round) the left neighbour comes from the lane below or from the previous item slot's lane 63, and
 // only a wave's first key of a round looks at memory: one load per key.
 __device__ __forceinline__ bool rl_is_head(uint64_t key, uint64_t &carry_key, bool &carry_valid, uint32_t shift, uint32_t lane) {
@@ -995,13 +969,9 @@ __global__ __launch_bounds__(CP_BLOCK) void k_rl_count(const uint64_t *__restric
     }
 }
 
-// z_st / z_inc / z_min (nullable, together): the per-key state of the UMI correction starts out here -- 0, 0 and all ones for
-// every distinct key written -- instead of in three memsets on the critical path behind this kernel
 __global__ __launch_bounds__(CP_BLOCK) void k_rl_write(const uint64_t *__restrict__ keys, const uint32_t shift, const uint64_t n,
                                                        const uint64_t tile, const uint32_t *__restrict__ block_offs,
-                                                       uint64_t *__restrict__ ukey, uint32_t *__restrict__ upos,
-                                                       uint16_t *__restrict__ z_st, uint32_t *__restrict__ z_inc,
-                                                       uint32_t *__restrict__ z_min) {
+                                                       uint64_t *__restrict__ ukey, uint32_t *__restrict__ upos) {
     __shared__ uint32_t ws[CP_ITEMS * CP_WAVES];  // heads of (wave, item slot), then their exclusive prefix
     __shared__ uint32_t round_total;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -1048,11 +1018,6 @@ __global__ __launch_bounds__(CP_BLOCK) void k_rl_write(const uint64_t *__restric
                 const uint32_t o = run + ws[wave * CP_ITEMS + j] + below[j];
                 ukey[o] = key[j];
                 upos[o] = (uint32_t)(w0 + (uint64_t)j * 64 + lane);
-                if (z_st) {
-                    z_st[o] = 0;
-                    z_inc[o] = 0u;
-                    z_min[o] = 0xFFFFFFFFu;
-                }
             }
         run += round_total;
         __syncthreads();
@@ -1063,8 +1028,7 @@ __global__ __launch_bounds__(CP_BLOCK) void k_rl_write(const uint64_t *__restric
 // them while it held the keys (cr_order_runs with a CrRunHeads) -- and the count pass over all keys is skipped.  k_rl_write
 // is the check on them: with wrong tile counts its output has gaps or overlaps.
 static int run_lengths(crgpu_ctx *ctx, const uint64_t *keys, uint32_t shift, uint64_t n, uint64_t *ukey, uint32_t *upos,
-                       uint32_t *d_block, uint32_t *d_total_out, bool counts_ready = false, uint16_t *z_st = nullptr,
-                       uint32_t *z_inc = nullptr, uint32_t *z_min = nullptr) {
+                       uint32_t *d_block, uint32_t *d_total_out, bool counts_ready = false) {
     uint64_t tile;
     const uint32_t nb = cp_blocks(n, &tile);
     if (!counts_ready)
@@ -1072,18 +1036,17 @@ static int run_lengths(crgpu_ctx *ctx, const uint64_t *keys, uint32_t shift, uin
     else
         ctx->rl_counts_from_finish++;
     CR_TRY(cr_scan_small(ctx, d_block, nb, d_total_out));
-    hipLaunchKernelGGL(k_rl_write, dim3(nb), dim3(CP_BLOCK), 0, ctx->stream, keys, shift, n, tile, d_block, ukey, upos, z_st, z_inc,
-                       z_min);
+    hipLaunchKernelGGL(k_rl_write, dim3(nb), dim3(CP_BLOCK), 0, ctx->stream, keys, shift, n, tile, d_block, ukey, upos);
     CR_HIP(ctx, hipGetLastError());
     return CRGPU_OK;
 }
 
 // ---- molecules and (barcode, feature) triplets from the same two launches over the distinct keys ---------------------
-// The molecule compaction (count + write over st / ukey / upos) was followed by a second compaction over the molecule keys
-// just to find the first molecule of every (barcode, feature) and by k_triplets: two more reads of the 3.2 GB molecule table
-// per 1 B records.  Here the count launch counts molecules AND the molecules that open a triplet, and the write launch
-// emits both (block offsets from two small scans), so both outputs keep the key order.  A molecule opens a triplet when no
-// earlier molecule shares its (barcode, feature): inside a wave that is ballot arithmetic on the lanes' own keys, from one
+// A molecule compaction followed by a second compaction over the molecule keys, just to find the first molecule of every
+// (barcode, feature), and a triplet kernel cost two more reads of the 3.2 GB molecule table per 1 B records
+// (profiles/r02_mol_trip_ab.txt).  Here the count launch counts molecules AND the molecules that open a triplet, and the
+// write launch emits both (block offsets from two small scans), so both outputs keep the key order.  A molecule opens a
+// triplet when no earlier molecule shares its (barcode, feature): inside a wave that is ballot arithmetic on the lanes' own keys, from one
 // item slot to the next a wave-uniform carry in registers, and for a wave's first slot of a round one walk back over the
 // distinct keys that yield no molecule (corrected away / low support), rarely more than one step.
 // (A single launch with tickets and a decoupled look-back carrying both counts in one status word was measured first: with
@@ -1367,47 +1330,26 @@ __device__ __forceinline__ uint64_t mix64(uint64_t g) {
 }
 #define LF_THREADS 1024u  // a workgroup may own one giant barcode: many threads + batched loads keep that pole short
 #define LF_BATCH 4
-// EMIT (CRGPU_CAND_EMIT=1; measured slower, see the driver): instead of a flag per key -- which a count + write compaction then turned into the list of
-// (hash, index) pairs with two more reads of the flags and one of the keys -- the second pass writes the pairs of its
-// candidates itself: a workgroup counts them, reserves its stretch of the list with ONE atomic per tile and appends.  The
-// list is sorted by hash afterwards, so the order of the tiles in it does not matter.
 #define LS_HASH_BITS 32u
-struct CandEmit {
-    uint32_t *hash, *val;       // the list (room for every key)
-    unsigned long long *n_out;  // its length (device counter, zeroed by the host)
-    uint32_t vbits;
-};
 // entry e of the table: bit 0 "seen", bit 1 "seen again"
 __device__ __forceinline__ void lf_note(uint32_t *bm, uint32_t e) {
     const uint32_t sh = (e & 15u) * 2u;
     const uint32_t old = atomicOr(&bm[e >> 4], 1u << sh);
     if ((old >> sh) & 1u) atomicOr(&bm[e >> 4], 2u << sh);
 }
-// two: TWO entries per group (bits 0.. and 24.. of the mix; opt-in, see the driver): a group with two members has hit both of
-// its entries twice, a single key is marked only if other keys hit BOTH of its entries
-__device__ __forceinline__ bool lf_again(const uint32_t *bm, uint64_t mx, uint32_t emask, bool two) {
-    const uint32_t e1 = (uint32_t)mx & emask, e2 = (uint32_t)(mx >> 24) & emask;
-    const bool a1 = (bm[e1 >> 4] >> ((e1 & 15u) * 2u + 1u)) & 1u;
-    return two ? a1 && ((bm[e2 >> 4] >> ((e2 & 15u) * 2u + 1u)) & 1u) : a1;
-}
-template <bool EMIT>
+__device__ __forceinline__ bool lf_again(const uint32_t *bm, uint32_t e) { return (bm[e >> 4] >> ((e & 15u) * 2u + 1u)) & 1u; }
 __global__ __launch_bounds__(LF_THREADS) void k_group_candidates(const KL kl, const uint64_t *__restrict__ ukey, uint64_t nd,
-                                                                 uint8_t *__restrict__ cand, const CandEmit em, const bool two) {
+                                                                 uint8_t *__restrict__ cand) {
     __shared__ uint32_t bm[LF_WORDS];
     __shared__ uint32_t s_first;
     __shared__ unsigned long long s_end;
-    __shared__ uint32_t s_cnt;                 // EMIT: candidates of the tile so far
-    __shared__ unsigned long long s_base;      // EMIT: the tile's stretch of the list
     const uint32_t tid = threadIdx.x;
     const uint64_t n_tiles = (nd + LF_TILE - 1) / LF_TILE;
     const uint32_t emask = (1u << LF_ENTRY_BITS) - 1u;
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const uint64_t t0 = tile * LF_TILE;
         const uint64_t t1 = t0 + LF_TILE < nd ? t0 + LF_TILE : nd;
-        if (tid == 0) {
-            s_first = 0xFFFFFFFFu;
-            s_cnt = 0u;
-        }
+        if (tid == 0) s_first = 0xFFFFFFFFu;
         for (uint32_t w = tid; w < LF_WORDS; w += LF_THREADS) bm[w] = 0u;
         __syncthreads();
         // first barcode head of the tile
@@ -1455,80 +1397,22 @@ __global__ __launch_bounds__(LF_THREADS) void k_group_candidates(const KL kl, co
 #pragma unroll
             for (int j = 0; j < LF_BATCH; j++) {
                 if (k0 + (uint64_t)j * LF_THREADS >= b) break;
-                const uint64_t mx = mix64(group_id(kl, key[j]));
-                lf_note(bm, (uint32_t)mx & emask);
-                if (two) lf_note(bm, (uint32_t)(mx >> 24) & emask);
+                lf_note(bm, (uint32_t)mix64(group_id(kl, key[j])) & emask);
             }
         }
         __syncthreads();
-        if (!EMIT) {
-            for (uint64_t k0 = a + tid; k0 < b; k0 += (uint64_t)LF_THREADS * LF_BATCH) {
-                uint64_t key[LF_BATCH];
+        for (uint64_t k0 = a + tid; k0 < b; k0 += (uint64_t)LF_THREADS * LF_BATCH) {
+            uint64_t key[LF_BATCH];
 #pragma unroll
-                for (int j = 0; j < LF_BATCH; j++) {
-                    const uint64_t k = k0 + (uint64_t)j * LF_THREADS;
-                    key[j] = k < b ? ukey[k] : 0ull;
-                }
-#pragma unroll
-                for (int j = 0; j < LF_BATCH; j++) {
-                    const uint64_t k = k0 + (uint64_t)j * LF_THREADS;
-                    if (k >= b) break;
-                    cand[k] = (uint8_t)lf_again(bm, mix64(group_id(kl, key[j])), emask, two);
-                }
-            }
-        } else {
-            // count the range's candidates (a second read of its keys, out of L2), reserve the range's stretch of the list
-            // with ONE global atomic, then read the keys once more and append: slots inside the stretch come from an LDS
-            // counter that every wave bumps once per item slot (no barrier inside the passes)
-            const uint32_t lane = tid & 63u;
-            uint32_t mine = 0;
-            for (uint64_t k0 = a + tid; k0 < b; k0 += (uint64_t)LF_THREADS * LF_BATCH) {
-                uint64_t key[LF_BATCH];
-#pragma unroll
-                for (int j = 0; j < LF_BATCH; j++) {
-                    const uint64_t k = k0 + (uint64_t)j * LF_THREADS;
-                    key[j] = k < b ? ukey[k] : 0ull;
-                }
-#pragma unroll
-                for (int j = 0; j < LF_BATCH; j++) {
-                    const uint64_t k = k0 + (uint64_t)j * LF_THREADS;
-                    mine += (k < b && lf_again(bm, mix64(group_id(kl, key[j])), emask, two)) ? 1u : 0u;
-                }
+            for (int j = 0; j < LF_BATCH; j++) {
+                const uint64_t k = k0 + (uint64_t)j * LF_THREADS;
+                key[j] = k < b ? ukey[k] : 0ull;
             }
 #pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) mine += __shfl_xor(mine, d);
-            if (lane == 0 && mine) atomicAdd(&s_cnt, mine);
-            __syncthreads();
-            if (tid == 0) {
-                s_base = s_cnt ? atomicAdd(em.n_out, (unsigned long long)s_cnt) : 0ull;
-                s_cnt = 0u;
-            }
-            __syncthreads();
-            const unsigned long long base = s_base;
-            for (uint64_t k0 = a + tid; k0 < b; k0 += (uint64_t)LF_THREADS * LF_BATCH) {
-                uint64_t key[LF_BATCH];
-#pragma unroll
-                for (int j = 0; j < LF_BATCH; j++) {
-                    const uint64_t k = k0 + (uint64_t)j * LF_THREADS;
-                    key[j] = k < b ? ukey[k] : 0ull;
-                }
-#pragma unroll
-                for (int j = 0; j < LF_BATCH; j++) {
-                    const uint64_t k = k0 + (uint64_t)j * LF_THREADS;
-                    const bool is_c = k < b && lf_again(bm, mix64(group_id(kl, key[j])), emask, two);
-                    const unsigned long long m = __ballot(is_c);
-                    if (!m) continue;  // wave-uniform
-                    uint32_t wbase = 0;
-                    if (lane == (uint32_t)(__ffsll((long long)m) - 1)) wbase = atomicAdd(&s_cnt, (uint32_t)__popcll(m));
-                    wbase = __shfl(wbase, __ffsll((long long)m) - 1);
-                    if (is_c) {
-                        const unsigned long long o = base + wbase + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-                        // the high half of the mix: independent of the low bits the filter consumed (as EmitHash)
-                        const uint64_t g = mix64(group_id(kl, key[j]) ^ 0x9E3779B97F4A7C15ull);
-                        em.hash[o] = LS_HASH_BITS >= 32u ? (uint32_t)g : ((uint32_t)g & ((1u << (LS_HASH_BITS & 31u)) - 1u));
-                        em.val[o] = (em.vbits >= 32u ? 0u : ((uint32_t)(g >> 32) << em.vbits)) | (uint32_t)k;
-                    }
-                }
+            for (int j = 0; j < LF_BATCH; j++) {
+                const uint64_t k = k0 + (uint64_t)j * LF_THREADS;
+                if (k >= b) break;
+                cand[k] = (uint8_t)lf_again(bm, (uint32_t)mix64(group_id(kl, key[j])) & emask);
             }
         }
         __syncthreads();
@@ -1605,22 +1489,6 @@ __global__ __launch_bounds__(256) void k_low_support(const KL kl, const uint32_t
         if (n_members < 2) continue;
         // low iff below the group's maximum, or the maximum is shared (mark_dups.rs:96-106)
         if (my_c1 < mx || n_max >= 2) st_or(st, me, ST_LOW);
-    }
-}
-
-__global__ __launch_bounds__(256) void k_triplets(const KL kl, const uint64_t *__restrict__ mkeys,
-                                                  const uint32_t *__restrict__ tpos, uint64_t nt, uint64_t nm,
-                                                  uint32_t *__restrict__ bc, uint32_t *__restrict__ feat,
-                                                  uint32_t *__restrict__ cnt, const uint32_t *__restrict__ back) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < nt; t += stride) {
-        const uint32_t p = tpos[t];
-        const uint32_t end = t + 1 < nt ? tpos[t + 1] : (uint32_t)nm;
-        const uint64_t key = mkeys[p];
-        const uint32_t bcf = (uint32_t)(key >> kl.sh_bc);
-        bc[t] = back ? back[bcf] : bcf;
-        feat[t] = (uint32_t)((key >> kl.sh_feat) & lowmask(kl.bits_feat));
-        cnt[t] = end - p;  // number of surviving molecules of (barcode, feature): types.rs:180-188
     }
 }
 
@@ -1709,63 +1577,6 @@ __global__ __launch_bounds__(256) void k_unpack_dupinfo(const void *__restrict__
             cnt = d.read_count;
             fl = d.flags;
         }
-        if (out_umi) out_umi[r] = umi;
-        if (out_cnt) out_cnt[r] = cnt;
-        if (out_flags) out_flags[r] = (uint8_t)fl;
-    }
-}
-
-// ---- the same through windows of read ordinals ---------------------------------------------------------------------------
-// (experiment, off by default -- see the driver) A read's position in sorted-key order has nothing to do with its ordinal:
-// k_per_read's 12-byte stores go all over the output (35 ms per 1 B records, 23 G stores/s).  Instead: one 8-byte record per SORTED position (coalesced), a stable
-// counting pass that groups (record, ordinal) by the top 9 bits of the ordinal (cr_partition_by_payload), and a scatter
-// whose stores then stay inside one window of n / 512 reads at a time -- small enough for the memory-side cache to merge
-// them into whole lines.  Packed record: [processed UMI 32][read_count 27][flags 5]; a read count that does not fit
-// raises *overflow and the host takes the direct path above.
-#define PR_COUNT_BITS 27u
-__device__ __forceinline__ uint64_t pack_duprec(uint32_t umi, uint32_t read_count, uint32_t flags) {
-    return ((uint64_t)umi << 32) | ((uint64_t)read_count << 5) | (flags & 0x1Fu);
-}
-__global__ __launch_bounds__(256) void k_per_read_sorted(const KL kl, const uint64_t *__restrict__ ukey,
-                                                         const uint32_t *__restrict__ vals, const uint32_t *__restrict__ upos,
-                                                         uint64_t nd, uint64_t n_keys, const uint32_t *__restrict__ corr,
-                                                         const uint32_t *__restrict__ inc_all, const uint16_t *__restrict__ st,
-                                                         const uint32_t *__restrict__ minidx, const uint32_t *__restrict__ rep_read,
-                                                         uint64_t *__restrict__ prec, uint32_t *__restrict__ overflow,
-                                                         const TargetFilter tf) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < nd; k += stride) {
-        const uint32_t b = upos[k], e = k + 1 < nd ? upos[k + 1] : (uint32_t)n_keys;
-        const bool corrected = (st[k] & ST_CORRECTED) != 0u;
-        const uint32_t K = corrected ? corr[k] : (uint32_t)k;
-        const uint32_t sK = st[K];
-        const uint32_t endK = (uint64_t)K + 1 < nd ? upos[K + 1] : (uint32_t)n_keys;
-        const uint32_t cntK = endK - upos[K];
-        const bool is_target = st_inc1(sK) != 0u;
-        const uint32_t read_count = ((sK & ST_CORRECTED) ? 0u : cntK) + (is_target ? inc_all[K] : 0u);
-        if (read_count >> PR_COUNT_BITS) *overflow = 1u;
-        const uint32_t umi = (uint32_t)((ukey[K] >> kl.sh_umi) & lowmask(kl.bits_umi));
-        const uint32_t mi = is_target ? rep_source(minidx[K], K, sK) : NONE32;
-        const uint32_t rep = rep_read[mi != NONE32 ? mi : K];
-        const bool lowK = (sK & ST_LOW) != 0u;
-        const bool filt = tf.filtered(ukey[K], read_count, lowK);
-        const uint32_t base = CRGPU_DUP_HAS | (corrected ? CRGPU_DUP_CORRECTED : 0u) | (lowK ? CRGPU_DUP_LOW_SUPPORT : 0u) |
-                              (filt ? CRGPU_DUP_FILTERED_TARGET : 0u);
-        for (uint32_t i = b; i < e; i++)
-            prec[i] = pack_duprec(umi, read_count, base | ((!lowK && !filt && vals[i] == rep) ? CRGPU_DUP_UMI_COUNT : 0u));
-    }
-}
-// (record, ordinal) pairs grouped by ordinal window -> the output arrays (any may be NULL) or the packed 12-byte records
-__global__ __launch_bounds__(256) void k_scatter_records(const uint64_t *__restrict__ prec, const uint32_t *__restrict__ ordinal,
-                                                         uint64_t n_keys, uint32_t *__restrict__ out_umi,
-                                                         uint32_t *__restrict__ out_cnt, uint8_t *__restrict__ out_flags,
-                                                         DupRec *__restrict__ packed_out) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n_keys; j += stride) {
-        const uint64_t d = prec[j];
-        const uint32_t r = ordinal[j];
-        const uint32_t umi = (uint32_t)(d >> 32), cnt = (uint32_t)((d >> 5) & ((1u << PR_COUNT_BITS) - 1u)), fl = (uint32_t)(d & 0x1Fu);
-        if (packed_out) packed_out[r] = DupRec{umi, cnt, fl};
         if (out_umi) out_umi[r] = umi;
         if (out_cnt) out_cnt[r] = cnt;
         if (out_flags) out_flags[r] = (uint8_t)fl;
@@ -1910,6 +1721,16 @@ struct CrFork {
         if (!c->stream2 || (e && e[0] == '0')) return false;
         return (e && e[0] == '2') ? nd > 0 : nd >= (1u << 20);
     }
+    // call before the main branch is enqueued: the point the side branch starts behind, and the start of the region's one span
+    int mark() {
+        CR_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
+        if (ctx->timing) {
+            t0 = cr_take_event(ctx);
+            t1 = cr_take_event(ctx);
+            CR_HIP(ctx, hipEventRecord(t0, ctx->stream));
+        }
+        return CRGPU_OK;
+    }
     // call after the main branch has been enqueued; start_of_region = the event recorded before it
     int side(hipEvent_t start_of_region) {
         main = ctx->stream;
@@ -1993,48 +1814,7 @@ static int count_keys_impl(crgpu_ctx *ctx, uint64_t *d_keys_inout, uint64_t n_ke
                                    ctx->stream));
     }
 
-    // 0. the per-key state of the UMI correction (section "per-key state") has to start out zeroed: 10 bytes per distinct key.
-    //    The number of distinct keys is not known yet, but it is at most n_keys: the arrays are sized by that and zeroed NOW on
-    //    the second stream, in the shadow of the sort (which is bound by the latency of its chunks, not by bandwidth) instead
-    //    of 0.8 ms on the critical path behind the run lengths.  CRGPU_NO_PREZERO=1: as before.
-    DevBuf corr_b, incall_b, st_b, minidx_b;
-    // (measured at 1 B records: the 8 GB of zeroing cost the sort passes more than the 0.8 ms they save -- sized by n_keys they
-    // are twice what the distinct keys need: OFF unless CRGPU_PREZERO=1, kept for the A/B record)
-    const bool prezero = ctx->stream2 && n_keys >= (1u << 20) && getenv("CRGPU_PREZERO") != nullptr;
-    // experiment: the run-length write pass zeroes the state of every distinct key it emits (arrays sized by n_keys, the bound on
-    // the number of distinct keys known before that pass) instead of three memsets behind it
-    // (measured at 1 B records: k_rl_write 2.2 -> 3.3 ms with the three extra stores per distinct key, against 0.8 ms of memsets:
-    // OFF unless CRGPU_STATE_FUSED_ZERO=1, kept for the A/B record)
-    const bool fused_zero = !prezero && getenv("CRGPU_STATE_FUSED_ZERO") && !getenv("CRGPU_RL_GENERIC") && !cr_sort_finish_experiment();
-    const uint64_t st_cap = (prezero || fused_zero) ? n_keys : 0;
-    if (fused_zero) {
-        CR_TRY(dmalloc(ctx, minidx_b, st_cap * sizeof(uint32_t)));
-        CR_TRY(dmalloc(ctx, corr_b, st_cap * sizeof(uint32_t)));
-        CR_TRY(dmalloc(ctx, incall_b, st_cap * sizeof(uint32_t)));
-        CR_TRY(dmalloc(ctx, st_b, ((st_cap + 1) & ~1ull) * sizeof(uint16_t) + 4));
-    }
-    if (prezero) {
-        CR_TRY(dmalloc(ctx, minidx_b, st_cap * sizeof(uint32_t)));
-        CR_TRY(dmalloc(ctx, corr_b, st_cap * sizeof(uint32_t)));
-        CR_TRY(dmalloc(ctx, incall_b, st_cap * sizeof(uint32_t)));
-        CR_TRY(dmalloc(ctx, st_b, ((st_cap + 1) & ~1ull) * sizeof(uint16_t) + 4));
-        // the blocks may have been in use by work queued on the main stream: the second stream starts behind it
-        CR_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-        CR_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-        CR_HIP(ctx, hipMemsetAsync(incall_b.p, 0, st_cap * sizeof(uint32_t), ctx->stream2));
-        CR_HIP(ctx, hipMemsetAsync(st_b.p, 0, ((st_cap + 1) & ~1ull) * sizeof(uint16_t) + 4, ctx->stream2));
-        CR_HIP(ctx, hipMemsetAsync(minidx_b.p, 0xFF, st_cap * sizeof(uint32_t), ctx->stream2));
-        CR_HIP(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
-    }
-    struct PrezeroGuard {  // an error return in between must not leave the second stream writing into blocks the pool hands out again
-        crgpu_ctx *c;
-        bool armed;
-        ~PrezeroGuard() {
-            if (armed) (void)hipStreamSynchronize(c->stream2);
-        }
-    } prezero_guard{ctx, prezero};
-
-    // 1. sort the keys: fully, or on their top bits with the finishing left to the run-length pass (CRGPU_SORT_FINISH)
+    // 1. sort the keys: fully, or on their top bits with the few low bits left to the finishing step below (CRGPU_SORT_FINISH)
     DevBuf tmp, vtmp;
     CR_TRY(dmalloc(ctx, tmp, n_keys * sizeof(uint64_t)));
     if (pr.d_vals) CR_TRY(dmalloc(ctx, vtmp, n_keys * sizeof(uint32_t)));
@@ -2051,24 +1831,15 @@ static int count_keys_impl(crgpu_ctx *ctx, uint64_t *d_keys_inout, uint64_t n_ke
     CR_TRY(dmalloc(ctx, upos_b, (n_keys + 1) * sizeof(uint32_t)));
     uint64_t *ukey = ukey_b.as<uint64_t>();
     uint32_t *upos = upos_b.as<uint32_t>();
-    uint64_t nd = 0;
-    bool emitted = false;
-    CrRunHeads rl_heads{1u, 0, nullptr, false};
+    CrRunHeads rl_heads{1u, 0, d_block, false};
     if (low_left) {
+        // the finishing step, which can spare the run lengths their count pass: it holds every key and its left neighbour
+        // anyway and counts the run heads of the tiles of run_lengths() into d_block on the way
         bool fell_back = false;
-        if (cr_sort_finish_experiment()) {
-            CR_TRY(cr_finish_emit(ctx, keys_rw, vals_rw, n_keys, low_left, ukey, upos, &nd, &fell_back));
-            emitted = !fell_back;
-        } else {
-            // then the run lengths -- whose count pass the finishing step can spare: it holds every key and its left neighbour
-            // anyway and counts the run heads of the tiles of run_lengths() into d_block on the way
-            rl_heads.shift = 1u;
-            (void)cp_blocks(n_keys, &rl_heads.tile);
-            rl_heads.d_counts = getenv("CRGPU_RL_GENERIC") ? nullptr : d_block;
-            CR_TRY(cr_order_runs(ctx, keys_rw, vals_rw, n_keys, low_left, &fell_back, &rl_heads));
-        }
+        (void)cp_blocks(n_keys, &rl_heads.tile);
+        CR_TRY(cr_order_runs(ctx, keys_rw, vals_rw, n_keys, low_left, &fell_back, &rl_heads));
         if (fell_back) {
-            // a run of equal top bits too long for the fused pass: sort the buffer (the same multiset) on all bits
+            // a run of equal top bits too long for the finishing step: sort the buffer (the same multiset) on all bits
             ctx->sort_refinished++;
             uint64_t *other = in_tmp ? d_keys_inout : tmp.as<uint64_t>();
             uint32_t *vother = pr.d_vals ? (in_tmp ? pr.d_vals : vtmp.as<uint32_t>()) : nullptr;
@@ -2083,50 +1854,30 @@ static int count_keys_impl(crgpu_ctx *ctx, uint64_t *d_keys_inout, uint64_t n_ke
     }
     const uint64_t *keys = keys_rw;
     const uint32_t *vals = vals_rw;
-    if (!emitted) {
-        uint32_t nd32 = 0;
-        {
-            CrTimer t(ctx, CRGPU_T_DEDUP, n_keys);  // the family's unit: one sorted key (counted here, once per call)
-            if (getenv("CRGPU_RL_GENERIC"))  // A/B: the generic compaction with its three loads per key
-                CR_TRY(compact(ctx, HeadFlag{keys, 1u}, EmitRun{keys, ukey, upos}, n_keys, d_block, d_total));
-            else
-                CR_TRY(run_lengths(ctx, keys, 1u, n_keys, ukey, upos, d_block, d_total, rl_heads.valid, fused_zero ? st_b.as<uint16_t>() : nullptr,
-                                   fused_zero ? incall_b.as<uint32_t>() : nullptr, fused_zero ? minidx_b.as<uint32_t>() : nullptr));
-        }
-        CR_TRY(read_u32(ctx, d_total, &nd32));
-        nd = nd32;
+    uint32_t nd32 = 0;
+    {
+        CrTimer t(ctx, CRGPU_T_DEDUP, n_keys);  // the family's unit: one sorted key (counted here, once per call)
+        CR_TRY(run_lengths(ctx, keys, 1u, n_keys, ukey, upos, d_block, d_total, rl_heads.valid));
     }
+    CR_TRY(read_u32(ctx, d_total, &nd32));
+    const uint64_t nd = nd32;
 
     // 3. UMI correction + the read moves (state layout: umi_correct.h)
+    // The 10 bytes of state per distinct key are filled by three memsets below.  (Zeroing them beside the sort, or from the
+    // run-length write pass, was measured slower: profiles/r03_count_stage_and_sort_ab.txt, profiles/r05_state_init_ab.txt.)
     const uint64_t st_bytes = ((nd + 1) & ~1ull) * sizeof(uint16_t) + 4;
-    const bool zeroed = prezero || (fused_zero && !emitted);
-    if (!prezero && !fused_zero) {
-        CR_TRY(dmalloc(ctx, minidx_b, nd * sizeof(uint32_t)));
-        CR_TRY(dmalloc(ctx, corr_b, nd * sizeof(uint32_t)));   // written (and valid) only where st says "corrected"
-        CR_TRY(dmalloc(ctx, incall_b, nd * sizeof(uint32_t)));
-        CR_TRY(dmalloc(ctx, st_b, st_bytes));
-    } else if (prezero) {
-        CR_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));  // the zeroing of step 0
-        prezero_guard.armed = false;
-    }
+    DevBuf corr_b, incall_b, st_b, minidx_b;
+    CR_TRY(dmalloc(ctx, minidx_b, nd * sizeof(uint32_t)));
+    CR_TRY(dmalloc(ctx, corr_b, nd * sizeof(uint32_t)));   // written (and valid) only where st says "corrected"
+    CR_TRY(dmalloc(ctx, incall_b, nd * sizeof(uint32_t)));
+    CR_TRY(dmalloc(ctx, st_b, st_bytes));
     uint32_t *corr = corr_b.as<uint32_t>(), *inc_all = incall_b.as<uint32_t>(), *minidx = minidx_b.as<uint32_t>();
     uint16_t *st = st_b.as<uint16_t>();
     // the candidate search of step 4 needs nothing of step 3: it runs beside it on the second stream (CrFork)
     const bool overlap = CrFork::enabled(ctx, nd);
     CrFork fork(ctx);
     DevBuf heads_b, giant_b, best_b;  // step 3's temporaries, alive until the branches have joined
-    bool edges_small_on_side = false;
-    uint64_t es_tiles = 0;
-    uint32_t *es_first = nullptr, *es_last = nullptr, *es_ngiant = nullptr;
-    GiantItem *es_items = nullptr;
-    if (overlap) {
-        CR_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-        if (ctx->timing) {
-            fork.t0 = cr_take_event(ctx);
-            fork.t1 = cr_take_event(ctx);
-            CR_HIP(ctx, hipEventRecord(fork.t0, ctx->stream));
-        }
-    }
+    if (overlap) CR_TRY(fork.mark());
     {
         const bool timing_was = ctx->timing;
         if (overlap) ctx->timing = false;  // one span for the whole region (CrFork::join)
@@ -2136,11 +1887,9 @@ static int count_keys_impl(crgpu_ctx *ctx, uint64_t *d_keys_inout, uint64_t n_ke
             ~TimingBack() { c->timing = v; }
         } timing_back{ctx, timing_was};
         CrTimer t(ctx, CRGPU_T_DEDUP);
-        if (!zeroed) {
-            CR_HIP(ctx, hipMemsetAsync(inc_all, 0, nd * sizeof(uint32_t), ctx->stream));
-            CR_HIP(ctx, hipMemsetAsync(st, 0, st_bytes, ctx->stream));
-            CR_HIP(ctx, hipMemsetAsync(minidx, 0xFF, nd * sizeof(uint32_t), ctx->stream));
-        }
+        CR_HIP(ctx, hipMemsetAsync(inc_all, 0, nd * sizeof(uint32_t), ctx->stream));
+        CR_HIP(ctx, hipMemsetAsync(st, 0, st_bytes, ctx->stream));
+        CR_HIP(ctx, hipMemsetAsync(minidx, 0xFF, nd * sizeof(uint32_t), ctx->stream));
         const uint64_t n_tiles = (nd + UC_TILE - 1) / UC_TILE;
         CR_TRY(dmalloc(ctx, heads_b, 2 * n_tiles * sizeof(uint32_t)));  // per tile: first / last segment head
         uint32_t *tile_first = heads_b.as<uint32_t>(), *tile_last = tile_first + n_tiles;
@@ -2162,22 +1911,9 @@ static int count_keys_impl(crgpu_ctx *ctx, uint64_t *d_keys_inout, uint64_t n_ke
             GiantItem *items = reinterpret_cast<GiantItem *>(giant_b.as<unsigned char>() + 16);
             unsigned long long *best = best_b.as<unsigned long long>();
             CR_HIP(ctx, hipMemsetAsync(n_giant, 0, sizeof(uint32_t), ctx->stream));
-            // the small edge segments only need the tile heads: with two streams they go to the second one, behind the candidate
-            // search (which ends before this branch does), and leave this branch the large segments and the giant chain
-            // (measured at 1 B records: 61.66 against 61.45 ms per step with everything on the main stream -- no gain, the candidate
-            // branch is not idle for long enough: OFF unless CRGPU_EDGES_SIDE=1)
-            edges_small_on_side = overlap && ctx->ev_aux && getenv("CRGPU_EDGES_SIDE") != nullptr;
-            if (edges_small_on_side) {
-                CR_HIP(ctx, hipEventRecord(ctx->ev_aux, ctx->stream));  // the tile heads are written
-                es_tiles = n_tiles;
-                es_first = tile_first;
-                es_last = tile_last;
-                es_items = items;
-                es_ngiant = n_giant;
-            } else
-                hipLaunchKernelGGL(k_correct_umis_edges<true>, dim3(cr_grid(n_tiles - 1, 1, 256u * 6u)), dim3(UES_THREADS),
-                                   lds_small, ctx->stream, kl, ukey, upos, nd, n_keys, tile_first, tile_last, corr, st, inc_all,
-                                   minidx, items, n_giant);
+            // (the small edge segments on the second stream behind the candidate search: no gain, profiles/r03_count_stage_and_sort_ab.txt)
+            hipLaunchKernelGGL(k_correct_umis_edges<true>, dim3(cr_grid(n_tiles - 1, 1, 256u * 6u)), dim3(UES_THREADS), lds_small,
+                               ctx->stream, kl, ukey, upos, nd, n_keys, tile_first, tile_last, corr, st, inc_all, minidx, items, n_giant);
             hipLaunchKernelGGL(k_correct_umis_edges<false>, dim3(cr_grid(n_tiles - 1, 1, 256u * 2u)), dim3(UE_THREADS),
                                lds_large, ctx->stream, kl, ukey, upos, nd, n_keys, tile_first, tile_last, corr, st, inc_all,
                                minidx, items, n_giant);
@@ -2196,53 +1932,23 @@ static int count_keys_impl(crgpu_ctx *ctx, uint64_t *d_keys_inout, uint64_t n_ke
     //    (barcode, library, UMI) through a 32-bit hash sort -> exact comparison of the phase-1 counts
     {
         DevBuf cand_b, h_b, v_b;
-        bool side_edges_done = false;
-        auto side_edges = [&]() -> int {  // the small edge segments of step 3, on the stream the candidate search ran on
-            if (!edges_small_on_side || side_edges_done || !fork.on_side) return CRGPU_OK;
-            side_edges_done = true;
-            CR_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_aux, 0));
-            const size_t lds_small = (2 * UES_CAP + UES_BUCKETS * 8) * sizeof(uint32_t);
-            hipLaunchKernelGGL(k_correct_umis_edges<true>, dim3(cr_grid(es_tiles - 1, 1, 256u * 6u)), dim3(UES_THREADS), lds_small,
-                               ctx->stream, kl, ukey, upos, nd, n_keys, es_first, es_last, corr, st, inc_all, minidx, es_items, es_ngiant);
-            CR_HIP(ctx, hipGetLastError());
-            return CRGPU_OK;
-        };
-        if (!getenv("CRGPU_CAND_EMIT")) CR_TRY(dmalloc(ctx, cand_b, nd));
+        CR_TRY(dmalloc(ctx, cand_b, nd));                    // a flag per distinct key
         CR_TRY(dmalloc(ctx, h_b, nd * sizeof(uint32_t)));   // room for every key; the candidates are ~1/5 of them
         CR_TRY(dmalloc(ctx, v_b, nd * sizeof(uint32_t)));
         const uint32_t vbits = cr_ceil_log2(nd ? nd : 1);  // bits the distinct-key index needs inside the payload
         uint32_t n_cand32 = 0;
         if (overlap) CR_TRY(fork.side(fork.t0));  // from here to join(): ctx->stream is the second stream
-        // default: a flag per key + the count / write compaction.  CRGPU_CAND_EMIT=1: the filter kernel appends the (hash, index)
-        // pairs itself -- measured SLOWER at 1 B records (k_group_candidates 2.6 -> 7.4 ms for the 2.6 ms of compaction it saves:
-        // a third pass over every barcode range, whose longest ones are one workgroup's job), kept for the A/B record
-        const bool cand_flags = getenv("CRGPU_CAND_EMIT") == nullptr;
-        // CRGPU_CAND_FILTER=2: two table entries per group.  Measured at 1 B records: the filter kernel 2.6 -> 3.8 ms, the hash sort
-        // only 20 % shorter (the large cells saturate the table either way), k_cp_count 1.6 -> 0.5: no change of the stage
-        const char *cf2 = getenv("CRGPU_CAND_FILTER");
-        const bool two_entries = cf2 && atoi(cf2) == 2;
-        unsigned long long *d_ncand = (unsigned long long *)(ctx->d_scalars + 64);
+        // a flag per key + the count / write compaction.  (The filter kernel appending the (hash, index) pairs itself, and two table
+        // entries per group, were measured slower or equal: profiles/r03_count_stage_and_sort_ab.txt.)
         {
             CrTimer t(ctx, CRGPU_T_DEDUP);
             const uint64_t n_ftiles = (nd + LF_TILE - 1) / LF_TILE;
-            if (cand_flags) {
-                hipLaunchKernelGGL(k_group_candidates<false>, dim3(cr_grid(n_ftiles, 1, 256u * 2u)), dim3(LF_THREADS), 0, ctx->stream, kl,
-                                   ukey, nd, cand_b.as<uint8_t>(), CandEmit{}, two_entries);
-                CR_HIP(ctx, hipGetLastError());
-                CR_TRY(compact(ctx, CandFlag{cand_b.as<uint8_t>()}, EmitHash{kl, ukey, vbits, h_b.as<uint32_t>(), v_b.as<uint32_t>()}, nd,
-                               d_block, d_total));
-            } else {
-                CR_HIP(ctx, hipMemsetAsync(d_ncand, 0, sizeof(unsigned long long), ctx->stream));
-                hipLaunchKernelGGL(k_group_candidates<true>, dim3(cr_grid(n_ftiles, 1, 256u * 2u)), dim3(LF_THREADS), 0, ctx->stream, kl,
-                                   ukey, nd, (uint8_t *)nullptr, CandEmit{h_b.as<uint32_t>(), v_b.as<uint32_t>(), d_ncand, vbits}, two_entries);
-                CR_HIP(ctx, hipGetLastError());
-            }
+            hipLaunchKernelGGL(k_group_candidates, dim3(cr_grid(n_ftiles, 1, 256u * 2u)), dim3(LF_THREADS), 0, ctx->stream, kl, ukey, nd,
+                               cand_b.as<uint8_t>());
+            CR_HIP(ctx, hipGetLastError());
+            CR_TRY(compact(ctx, CandFlag{cand_b.as<uint8_t>()}, EmitHash{kl, ukey, vbits, h_b.as<uint32_t>(), v_b.as<uint32_t>()}, nd, d_block,
+                           d_total));
         }
-        if (!cand_flags) {
-            unsigned long long nc64 = 0;
-            CR_TRY(crgpu_memcpy_d2h(ctx, &nc64, d_ncand, sizeof(nc64)));
-            n_cand32 = (uint32_t)nc64;
-        } else
         CR_TRY(read_u32(ctx, d_total, &n_cand32));
         const uint64_t n_cand = n_cand32;
         ctx->last_distinct_keys = nd;
@@ -2254,7 +1960,6 @@ static int count_keys_impl(crgpu_ctx *ctx, uint64_t *d_keys_inout, uint64_t n_ke
             bool s_in_tmp = false;
             CR_TRY(cr_radix_sort_u32(ctx, h_b.as<uint32_t>(), ht_b.as<uint32_t>(), v_b.as<uint32_t>(), vt_b.as<uint32_t>(), n_cand,
                                      0, LS_HASH_BITS, &s_in_tmp));
-            CR_TRY(side_edges());
             CR_TRY(fork.join());  // k_low_support compares the phase-1 counts: it needs both branches
             {
                 CrTimer t(ctx, CRGPU_T_DEDUP);
@@ -2264,17 +1969,15 @@ static int count_keys_impl(crgpu_ctx *ctx, uint64_t *d_keys_inout, uint64_t n_ke
                 CR_HIP(ctx, hipGetLastError());
             }
         }
-        CR_TRY(side_edges());
         CR_TRY(fork.join());  // (no candidates: nothing was joined above)
     }
 
     const TargetFilter tf{ctx->d_on_target, ctx->n_target_features, L.sh_feat(), L.bits_feat, ctx->d_on_target ? ctx->target_min_reads : 0};
     // 5b. optional per-read DupInfo.  Its scattered stores and the molecule / triplet passes of step 5 and 6 only share
-    //     inputs: with the direct scatter the whole of 5b goes to the second stream and is joined at the end of the call
+    //     inputs: the whole of 5b goes to the second stream and is joined at the end of the call
     //     (the ledger then books 5b + 5 + 5c + 6 as one span)
     CrFork fork2(ctx);
     DevBuf rep_b, packed_b;
-    const bool windowed = getenv("CRGPU_DUPINFO_WINDOWED") != nullptr;
     const bool want_probe = vals && pr.d_probe;
     if (vals) CR_TRY(dmalloc(ctx, rep_b, nd * sizeof(uint32_t)));
     if (want_probe) {  // the molecule pass of step 5 needs the representative reads, too: before the streams part
@@ -2283,153 +1986,63 @@ static int count_keys_impl(crgpu_ctx *ctx, uint64_t *d_keys_inout, uint64_t n_ke
                            rep_b.as<uint32_t>());
         CR_HIP(ctx, hipGetLastError());
     }
-    if (vals && !windowed && CrFork::enabled(ctx, nd)) {
-        CR_HIP(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-        if (ctx->timing) {
-            fork2.t0 = cr_take_event(ctx);
-            fork2.t1 = cr_take_event(ctx);
-            CR_HIP(ctx, hipEventRecord(fork2.t0, ctx->stream));
-        }
+    if (vals && CrFork::enabled(ctx, nd)) {
+        CR_TRY(fork2.mark());
         CR_TRY(fork2.side(fork2.t0));
     }
     // Beside the main stream these grid-stride kernels take 6 of the 8 workgroups a CU holds: with all 8 every wave slot was
     // theirs for their whole run time, and the main stream's next (often tiny) kernel waited milliseconds for one to end
-    uint32_t side_wgs = fork2.on_side ? 256u * 6u : 256u * 8u;
-    if (const char *g = getenv("CRGPU_SIDE_WGS")) side_wgs = 256u * (uint32_t)atoi(g);  // (A/B switch)
-    if (side_wgs < 256u) side_wgs = 256u * 8u;
+    const uint32_t side_wgs = fork2.on_side ? 256u * 6u : 256u * 8u;
     if (vals) {
         CrTimer t(ctx, CRGPU_T_DEDUP);
         if (!want_probe)
             hipLaunchKernelGGL(k_rep_read, dim3(cr_grid(nd, 256, side_wgs)), dim3(256), 0, ctx->stream, keys, vals, upos, nd, n_keys,
                                rep_b.as<uint32_t>());
-        // reads that never reach DupBuilder::observe get no DupInfo (mark_dups.rs:289-291): zeros.  The direct scatter into our
-        // own packed temporary is followed by k_unpack_dupinfo, which writes all three arrays for EVERY read (zeros where the
+        // reads that never reach DupBuilder::observe get no DupInfo (mark_dups.rs:289-291): zeros.  The scatter into our own
+        // packed temporary is followed by k_unpack_dupinfo, which writes all three arrays for EVERY read (zeros where the
         // temporary holds none): zeroing them first was 9 GB of fills per 1 B reads in front of the scatter.
-        const bool unpack_covers_all = !windowed && !pr.packed_out;
-        if (pr.packed_out) {
-            CR_HIP(ctx, hipMemsetAsync(pr.packed_out, 0, pr.n_reads * sizeof(DupRec), ctx->stream));
-        } else if (!unpack_covers_all) {
-            if (pr.out_umi) CR_HIP(ctx, hipMemsetAsync(pr.out_umi, 0, pr.n_reads * sizeof(uint32_t), ctx->stream));
-            if (pr.out_cnt) CR_HIP(ctx, hipMemsetAsync(pr.out_cnt, 0, pr.n_reads * sizeof(uint32_t), ctx->stream));
-            if (pr.out_flags) CR_HIP(ctx, hipMemsetAsync(pr.out_flags, 0, pr.n_reads, ctx->stream));
+        // (Grouping the records by windows of read ordinals before the scatter was measured slower: profiles/r02_dupinfo_windowed_ab.txt.)
+        if (pr.packed_out) CR_HIP(ctx, hipMemsetAsync(pr.packed_out, 0, pr.n_reads * sizeof(DupRec), ctx->stream));
+        // our own temporary may use the 8-byte layout; UMIs of more than 12 bases and the caller's records take 12 bytes
+        const bool pack8 = !pr.packed_out && kl.bits_umi <= 24u;
+        if (!pr.packed_out) {
+            const uint64_t bytes = pr.n_reads * (pack8 ? sizeof(DupRec8) : sizeof(DupRec));
+            CR_TRY(dmalloc(ctx, packed_b, bytes));
+            CR_HIP(ctx, hipMemsetAsync(packed_b.p, 0, bytes, ctx->stream));
         }
-        // The direct scatter is the default.  CRGPU_DUPINFO_WINDOWED=1 takes the windowed one (k_per_read_sorted): measured at
-        // 1 B records it is SLOWER (dedup family 119-138 ms against 77 ms, profiles/r02_dupinfo_windowed_ab.txt): 512 windows of
-        // 2 M reads are 24 MB of output each, far beyond the 4 MB L2 of an XCD, and the three output arrays take three
-        // scattered stores per read instead of one.  Kept as a tested experiment for windows that fit the L2 (two levels).
-        bool direct = !windowed;
-        if (!direct) {
-            // CRGPU_DUPINFO_WINDOWED=2: two stable partition passes (18 bits of the ordinal, low digit first) leave windows of
-            // 2^(bits - 18) reads -- 32 KB of output per array at 1 B reads, which the L2 merges into whole lines
-            const char *wenv = getenv("CRGPU_DUPINFO_WINDOWED");
-            const bool two_level = wenv && wenv[0] == '2';
-            DevBuf prec_b, prec2_b, ord2_b, ord3_b;
-            CR_TRY(dmalloc(ctx, prec_b, n_keys * sizeof(uint64_t)));
-            CR_TRY(dmalloc(ctx, prec2_b, n_keys * sizeof(uint64_t)));
-            CR_TRY(dmalloc(ctx, ord2_b, n_keys * sizeof(uint32_t)));
-            if (two_level) CR_TRY(dmalloc(ctx, ord3_b, n_keys * sizeof(uint32_t)));
-            uint32_t *d_over = ctx->d_scalars + 56, over = 0;
-            CR_HIP(ctx, hipMemsetAsync(d_over, 0, sizeof(uint32_t), ctx->stream));
-            hipLaunchKernelGGL(k_per_read_sorted, dim3(cr_grid(nd, 256)), dim3(256), 0, ctx->stream, kl, ukey, vals, upos, nd, n_keys,
-                               corr, inc_all, st, minidx, rep_b.as<uint32_t>(), prec_b.as<uint64_t>(), d_over, tf);
-            CR_HIP(ctx, hipGetLastError());
-            CR_TRY(read_u32(ctx, d_over, &over));
-            if (over) {
-                direct = true;
-            } else {
-                const uint32_t bits = cr_ceil_log2(pr.n_reads ? pr.n_reads : 1);
-                if (two_level && bits > 18) {
-                    CR_TRY(cr_partition_by_payload(ctx, prec_b.as<uint64_t>(), prec2_b.as<uint64_t>(), vals, ord2_b.as<uint32_t>(), n_keys,
-                                                   bits - 18));
-                    CR_TRY(cr_partition_by_payload(ctx, prec2_b.as<uint64_t>(), prec_b.as<uint64_t>(), ord2_b.as<uint32_t>(),
-                                                   ord3_b.as<uint32_t>(), n_keys, bits - 9));
-                    hipLaunchKernelGGL(k_scatter_records, dim3(cr_grid(n_keys, 256)), dim3(256), 0, ctx->stream, prec_b.as<uint64_t>(),
-                                       ord3_b.as<uint32_t>(), n_keys, pr.out_umi, pr.out_cnt, pr.out_flags, pr.packed_out);
-                } else {
-                    CR_TRY(cr_partition_by_payload(ctx, prec_b.as<uint64_t>(), prec2_b.as<uint64_t>(), vals, ord2_b.as<uint32_t>(), n_keys,
-                                                   bits > 9 ? bits - 9 : 0));
-                    hipLaunchKernelGGL(k_scatter_records, dim3(cr_grid(n_keys, 256)), dim3(256), 0, ctx->stream, prec2_b.as<uint64_t>(),
-                                       ord2_b.as<uint32_t>(), n_keys, pr.out_umi, pr.out_cnt, pr.out_flags, pr.packed_out);
-                }
-                CR_HIP(ctx, hipGetLastError());
-            }
-        }
-        if (direct) {
-            // our own temporary may use the 8-byte layout
-            const bool pack8 = !pr.packed_out && kl.bits_umi <= 24u && !getenv("CRGPU_DUPINFO_PACK12");
-            if (!pr.packed_out) {
-                const uint64_t bytes = pr.n_reads * (pack8 ? sizeof(DupRec8) : sizeof(DupRec));
-                CR_TRY(dmalloc(ctx, packed_b, bytes));
-                CR_HIP(ctx, hipMemsetAsync(packed_b.p, 0, bytes, ctx->stream));
-            }
-            DupRec *packed = pr.packed_out ? pr.packed_out : packed_b.as<DupRec>();
+        DupRec *packed = pr.packed_out ? pr.packed_out : packed_b.as<DupRec>();
+        if (pack8)
+            hipLaunchKernelGGL(k_per_read<true>, dim3(cr_grid(nd, 256, side_wgs)), dim3(256), 0, ctx->stream, kl, ukey, vals, upos, nd, n_keys,
+                               corr, inc_all, st, minidx, rep_b.as<uint32_t>(), (void *)packed, tf);
+        else
+            hipLaunchKernelGGL(k_per_read<false>, dim3(cr_grid(nd, 256, side_wgs)), dim3(256), 0, ctx->stream, kl, ukey, vals, upos, nd, n_keys,
+                               corr, inc_all, st, minidx, rep_b.as<uint32_t>(), (void *)packed, tf);
+        if (!pr.packed_out) {
             if (pack8)
-                hipLaunchKernelGGL(k_per_read<true>, dim3(cr_grid(nd, 256, side_wgs)), dim3(256), 0, ctx->stream, kl, ukey, vals, upos, nd, n_keys,
-                                   corr, inc_all, st, minidx, rep_b.as<uint32_t>(), (void *)packed, tf);
+                hipLaunchKernelGGL(k_unpack_dupinfo<true>, dim3(cr_grid(pr.n_reads, 256, side_wgs)), dim3(256), 0, ctx->stream,
+                                   (const void *)packed, pr.n_reads, pr.out_umi, pr.out_cnt, pr.out_flags);
             else
-                hipLaunchKernelGGL(k_per_read<false>, dim3(cr_grid(nd, 256, side_wgs)), dim3(256), 0, ctx->stream, kl, ukey, vals, upos, nd, n_keys,
-                                   corr, inc_all, st, minidx, rep_b.as<uint32_t>(), (void *)packed, tf);
-            if (!pr.packed_out) {
-                if (pack8)
-                    hipLaunchKernelGGL(k_unpack_dupinfo<true>, dim3(cr_grid(pr.n_reads, 256, side_wgs)), dim3(256), 0, ctx->stream,
-                                       (const void *)packed, pr.n_reads, pr.out_umi, pr.out_cnt, pr.out_flags);
-                else
-                    hipLaunchKernelGGL(k_unpack_dupinfo<false>, dim3(cr_grid(pr.n_reads, 256, side_wgs)), dim3(256), 0, ctx->stream,
-                                       (const void *)packed, pr.n_reads, pr.out_umi, pr.out_cnt, pr.out_flags);
-            }
-            CR_HIP(ctx, hipGetLastError());
+                hipLaunchKernelGGL(k_unpack_dupinfo<false>, dim3(cr_grid(pr.n_reads, 256, side_wgs)), dim3(256), 0, ctx->stream,
+                                   (const void *)packed, pr.n_reads, pr.out_umi, pr.out_cnt, pr.out_flags);
         }
+        CR_HIP(ctx, hipGetLastError());
     }
     fork2.pause();  // the rest of the call is enqueued on the main stream again; joined before the return
 
     // 5. molecules = distinct keys some read lands on and that are not low support; with them, in the same two launches,
-    //    the (barcode, feature) triplets (6.): CRGPU_MOL_FUSED=0 keeps the separate passes (the A/B path)
+    //    the (barcode, feature) triplets (6.).  (Separate compactions for the two: profiles/r02_mol_trip_ab.txt.)
     DevBuf mkeys_b, mreads_b, tpos_b;
     CR_TRY(dmalloc(ctx, mkeys_b, nd * sizeof(uint64_t)));
     CR_TRY(dmalloc(ctx, mreads_b, nd * sizeof(uint32_t)));
     uint32_t nm32 = 0, nt32 = 0;
     if (want_probe) CR_TRY(cr_pool_alloc(ctx, (void **)&res->d_mprobe, nd * sizeof(int32_t)));
-    const char *fused_env = getenv("CRGPU_MOL_FUSED");
-    const bool fused = nd > 0 && !(fused_env && fused_env[0] == '0');
-    if (fused) {
-        CR_TRY(dmalloc(ctx, tpos_b, (nd + 1) * sizeof(uint32_t)));
-        // the triplet arrays are sized before the number of triplets is known: one entry per distinct key is the bound
-        CR_TRY(cr_pool_alloc(ctx, (void **)&res->d_bc, nd * sizeof(uint32_t)));
-        CR_TRY(cr_pool_alloc(ctx, (void **)&res->d_feature, nd * sizeof(uint32_t)));
-        uint32_t *d_heads = d_block + 4096;      // the second set of block counters
-        uint32_t *d_total_h = ctx->d_scalars + 17;
-        {
-            CrTimer t(ctx, CRGPU_T_DEDUP);
-            EmitMol emit{ukey, upos, inc_all, minidx, st, n_keys, nd, mkeys_b.as<uint64_t>(), mreads_b.as<uint32_t>()};
-            if (want_probe) {
-                emit.rep_read = rep_b.as<uint32_t>();
-                emit.probe = pr.d_probe;
-                emit.mprobe = res->d_mprobe;
-            }
-            uint64_t tile;
-            const uint32_t nb = cp_blocks(nd, &tile);
-            const MolFlagTargeted flag_t{st, ukey, upos, inc_all, n_keys, nd, tf};
-            const MolFlag flag_p{st};
-            if (tf.min_reads)
-                hipLaunchKernelGGL(k_mt_count<MolFlagTargeted>, dim3(nb), dim3(CP_BLOCK), 0, ctx->stream, flag_t, ukey, L.sh_feat(), nd,
-                                   tile, d_block, d_heads);
-            else
-                hipLaunchKernelGGL(k_mt_count<MolFlag>, dim3(nb), dim3(CP_BLOCK), 0, ctx->stream, flag_p, ukey, L.sh_feat(), nd, tile,
-                                   d_block, d_heads);
-            CR_TRY(cr_scan_small(ctx, d_block, nb, d_total));
-            CR_TRY(cr_scan_small(ctx, d_heads, nb, d_total_h));
-            if (tf.min_reads)
-                hipLaunchKernelGGL(k_mt_write<MolFlagTargeted>, dim3(nb), dim3(CP_BLOCK), 0, ctx->stream, flag_t, emit, L.sh_bc(),
-                                   L.sh_feat(), L.bits_feat, nd, tile, d_block, d_heads, res->d_bc, res->d_feature, tpos_b.as<uint32_t>(),
-                                   res->d_back);
-            else
-                hipLaunchKernelGGL(k_mt_write<MolFlag>, dim3(nb), dim3(CP_BLOCK), 0, ctx->stream, flag_p, emit, L.sh_bc(), L.sh_feat(),
-                                   L.bits_feat, nd, tile, d_block, d_heads, res->d_bc, res->d_feature, tpos_b.as<uint32_t>(), res->d_back);
-            CR_HIP(ctx, hipGetLastError());
-        }
-        CR_TRY(read_u32(ctx, d_total, &nm32));
-        CR_TRY(read_u32(ctx, d_total_h, &nt32));
-    } else {
+    CR_TRY(dmalloc(ctx, tpos_b, (nd + 1) * sizeof(uint32_t)));
+    // the triplet arrays are sized before the number of triplets is known: one entry per distinct key is the bound
+    CR_TRY(cr_pool_alloc(ctx, (void **)&res->d_bc, nd * sizeof(uint32_t)));
+    CR_TRY(cr_pool_alloc(ctx, (void **)&res->d_feature, nd * sizeof(uint32_t)));
+    uint32_t *d_heads = d_block + 4096;      // the second set of block counters
+    uint32_t *d_total_h = ctx->d_scalars + 17;
+    {
         CrTimer t(ctx, CRGPU_T_DEDUP);
         EmitMol emit{ukey, upos, inc_all, minidx, st, n_keys, nd, mkeys_b.as<uint64_t>(), mreads_b.as<uint32_t>()};
         if (want_probe) {
@@ -2437,12 +2050,29 @@ static int count_keys_impl(crgpu_ctx *ctx, uint64_t *d_keys_inout, uint64_t n_ke
             emit.probe = pr.d_probe;
             emit.mprobe = res->d_mprobe;
         }
+        uint64_t tile;
+        const uint32_t nb = cp_blocks(nd, &tile);
+        const MolFlagTargeted flag_t{st, ukey, upos, inc_all, n_keys, nd, tf};
+        const MolFlag flag_p{st};
         if (tf.min_reads)
-            CR_TRY(compact(ctx, MolFlagTargeted{st, ukey, upos, inc_all, n_keys, nd, tf}, emit, nd, d_block, d_total));
+            hipLaunchKernelGGL(k_mt_count<MolFlagTargeted>, dim3(nb), dim3(CP_BLOCK), 0, ctx->stream, flag_t, ukey, L.sh_feat(), nd,
+                               tile, d_block, d_heads);
         else
-            CR_TRY(compact(ctx, MolFlag{st}, emit, nd, d_block, d_total));
+            hipLaunchKernelGGL(k_mt_count<MolFlag>, dim3(nb), dim3(CP_BLOCK), 0, ctx->stream, flag_p, ukey, L.sh_feat(), nd, tile,
+                               d_block, d_heads);
+        CR_TRY(cr_scan_small(ctx, d_block, nb, d_total));
+        CR_TRY(cr_scan_small(ctx, d_heads, nb, d_total_h));
+        if (tf.min_reads)
+            hipLaunchKernelGGL(k_mt_write<MolFlagTargeted>, dim3(nb), dim3(CP_BLOCK), 0, ctx->stream, flag_t, emit, L.sh_bc(),
+                               L.sh_feat(), L.bits_feat, nd, tile, d_block, d_heads, res->d_bc, res->d_feature, tpos_b.as<uint32_t>(),
+                               res->d_back);
+        else
+            hipLaunchKernelGGL(k_mt_write<MolFlag>, dim3(nb), dim3(CP_BLOCK), 0, ctx->stream, flag_p, emit, L.sh_bc(), L.sh_feat(),
+                               L.bits_feat, nd, tile, d_block, d_heads, res->d_bc, res->d_feature, tpos_b.as<uint32_t>(), res->d_back);
+        CR_HIP(ctx, hipGetLastError());
     }
-    if (!fused) CR_TRY(read_u32(ctx, d_total, &nm32));
+    CR_TRY(read_u32(ctx, d_total, &nm32));
+    CR_TRY(read_u32(ctx, d_total_h, &nt32));
     const uint64_t nm = nm32;
 
     // 5c. optional: reads with a corrected UMI per (library, barcode) -- the one BarcodeSummary column that cannot be
@@ -2463,32 +2093,12 @@ static int count_keys_impl(crgpu_ctx *ctx, uint64_t *d_keys_inout, uint64_t n_ke
         CR_HIP(ctx, hipGetLastError());
     }
 
-    // 6. (barcode, feature) triplets = run lengths of the molecule keys at the feature boundary
-    if (!fused) {
-        CR_TRY(dmalloc(ctx, tpos_b, (nm + 1) * sizeof(uint32_t)));
-        if (nm) {
-            {
-                CrTimer t(ctx, CRGPU_T_DEDUP);
-                CR_TRY(compact(ctx, HeadFlag{mkeys_b.as<uint64_t>(), L.sh_feat()}, EmitTriplet{mkeys_b.as<uint64_t>(), tpos_b.as<uint32_t>()},
-                               nm, d_block, d_total));
-            }
-            CR_TRY(read_u32(ctx, d_total, &nt32));
-        }
-    }
+    // 6. (barcode, feature) triplets: their barcodes and features were written by step 5, their counts are the distances of tpos
     const uint64_t nt = nt32;
-    if (!fused) {
-        CR_TRY(cr_pool_alloc(ctx, (void **)&res->d_bc, nt * sizeof(uint32_t)));
-        CR_TRY(cr_pool_alloc(ctx, (void **)&res->d_feature, nt * sizeof(uint32_t)));
-    }
     CR_TRY(cr_pool_alloc(ctx, (void **)&res->d_count, nt * sizeof(uint32_t)));
     if (nt) {
         CrTimer t(ctx, CRGPU_T_DEDUP);
-        if (fused)
-            hipLaunchKernelGGL(k_trip_counts, dim3(cr_grid(nt, 256)), dim3(256), 0, ctx->stream, tpos_b.as<uint32_t>(), nt, nm,
-                               res->d_count);
-        else
-            hipLaunchKernelGGL(k_triplets, dim3(cr_grid(nt, 256)), dim3(256), 0, ctx->stream, kl, mkeys_b.as<uint64_t>(),
-                               tpos_b.as<uint32_t>(), nt, nm, res->d_bc, res->d_feature, res->d_count, res->d_back);
+        hipLaunchKernelGGL(k_trip_counts, dim3(cr_grid(nt, 256)), dim3(256), 0, ctx->stream, tpos_b.as<uint32_t>(), nt, nm, res->d_count);
         CR_HIP(ctx, hipGetLastError());
     }
     CR_TRY(fork2.join());

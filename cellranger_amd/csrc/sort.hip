@@ -57,8 +57,8 @@
 #endif
 #ifndef SORT_MAX_BLOCKS
 #define SORT_MAX_BLOCKS 1024
-#define OR_MAX_LOW_BITS 16u  // low key bits the finishing step may be left with (two levels of bucket arrays in or_run_through_memory)
 #endif
+#define OR_MAX_LOW_BITS 16u  // low key bits the finishing step may be left with (two levels of bucket arrays in or_run_through_memory)
 
 // ---- exclusive scan of a small u32 array (block counts of the compactions), single workgroup -----
 __global__ __launch_bounds__(1024) void k_scan_small(uint32_t *__restrict__ data, uint64_t n,
@@ -108,20 +108,12 @@ int cr_scan_small(crgpu_ctx *ctx, uint32_t *d_data, uint64_t n, uint32_t *d_tota
 //                                                  contiguous barcode-rank ranges, like shardio's make_chunks)
 // OwnerBounds  index of the range [bounds[r], bounds[r+1]) that holds (key >> shift); `bounds` has
 //              width+1 ascending entries in device memory (histogram-balanced ranges)
-// PayloadDigit (payload >> shift) & mask         (partition by the top bits of the read ordinal that travels as payload)
-// Every functor is called as dig(key, payload); only PayloadDigit looks at the payload.
+// Every functor is called as dig(key, payload); none of them looks at the payload.
 struct RadixDigit {
     uint32_t shift, mask;
     template <typename K>
     __device__ __forceinline__ uint32_t operator()(K key, uint32_t = 0u) const {
         return (uint32_t)(key >> shift) & mask;
-    }
-};
-struct PayloadDigit {
-    uint32_t shift, mask;
-    template <typename K>
-    __device__ __forceinline__ uint32_t operator()(K, uint32_t val) const {
-        return (val >> shift) & mask;
     }
 };
 struct OwnerDiv {
@@ -730,52 +722,28 @@ static int onesweep_sort_u64(crgpu_ctx *ctx, uint64_t *d_keys, uint64_t *d_tmp, 
     return CRGPU_OK;
 }
 
-// Bits of the molecule keys that the radix passes leave to k_finish_runs: with L low bits left out, the passes sort on
-// the top bits only (all 9 bits wide) and the finishing pass orders the short runs of equal top bits in LDS.  L is the
-// largest value <= 16 that makes ceil((total - L) / 9) passes cover the rest: 61 bits -> 5 passes + 16 bits (instead
-// of 7 passes), 64 -> 6 + 10, 50 -> 4 + 14.  0: keys too short to gain a pass, or not switched on.
-// OFF by default (CRGPU_SORT_FINISH=1 turns it on; the whole GPU suite passes with it).  At 1 B records the five passes
-// take 18.7 ms instead of 25.7, but the finishing costs more than the 7 ms it saves, as a kernel of its own (20 ms) and
-// fused with the run-length pass (k_finish_emit, 23 ms against the 3.6 ms of the two compaction launches it replaces:
-// 7.5 ms without any ordering work -- 389 K tiles of 2048 keys with a ticket, ten barriers and a look-back each -- 1.2 ms
-// for the run bounds and 14.4 ms for the ranks).  The ranks are only 4.8 G compare steps, but 13 % of the keys sit in
-// runs of 8 to 64 (the top genes of every cell: Zipf x log-normal cell sizes), their tiles take ten times as long as the
-// others, and under ticket order every later tile waits in its look-back for the slow tile's count with all workgroup
-// slots taken.  profiles/r02_finish_pass_ab.txt.
-// How many low key bits the radix passes leave alone (0: none; the default).
-//   CRGPU_SORT_FINISH=2     the fewest low bits (at most 8) whose omission saves a whole pass, provided at least 16 UMI bits
-//                           stay above the cut: keys that agree on everything above it are then rare and few (the reads of one
-//                           UMI whose UmiType bits differ; UMIs of one (barcode, feature) that share their leading bases), and
-//                           k_order_runs puts those short runs in order -- 61 bits: 6 passes + 7 bits, 64 bits: 7 passes + 1 bit.
-//                           Measured at 1 B records: the passes 25.9 -> 22.8 ms, k_order_runs 3.7 ms (8.1 with one lane walking
-//                           every run through memory, 5.5 with in-register odd-even sorting of the runs inside a wave, 3.7 with
-//                           waves 48 keys apart so that short runs never leave their wave): +0.6 ms, so it is not the default;
-//                           fused into the run-length count (which reads the keys anyway) it would be -1.5 ms
-//   CRGPU_SORT_FINISH=1     the earlier experiment: up to 16 low bits, finished by k_finish_runs / k_finish_emit (slower still)
+// How many low key bits of the molecule keys the radix passes leave alone (0: none).  The default is the fewest low bits, at
+// most OR_MAX_LOW_BITS, whose omission saves a whole pass, provided at least 14 UMI bits stay above the cut: keys that agree on
+// everything above it are then rare and few (the reads of one UMI whose UmiType bits differ; UMIs of one (barcode, feature)
+// that share their leading bases), and cr_repair_runs puts those runs in order -- 61 bits: 6 passes + 7 bits, 64 bits:
+// 6 passes + 10 bits.  CRGPU_SORT_FINISH=0: radix passes on every bit.
+// Measured and removed: up to 16 low bits finished in LDS by a kernel of its own or fused with the run-length pass
+// (profiles/r02_finish_pass_ab.txt); one streaming pass that orders every run inside its wave (3.7 ms against the 1.9 ms of
+// the repair step, profiles/r03_count_stage_and_sort_ab.txt).
 uint32_t cr_sort_low_bits(uint32_t total_bits, uint32_t umi_bits) {
     const char *e = getenv("CRGPU_SORT_FINISH");
     if (!onesweep_enabled() || total_bits <= 27) return 0;
-    if (e && atoi(e) == 0) return 0;   // round 3: leaving the few low bits that save a pass is the default (cr_repair_runs)
+    if (e && atoi(e) == 0) return 0;
     const uint32_t p8 = (total_bits + 7) / 8, p9 = (total_bits + 8) / 9;
     const uint32_t full = p9 < p8 ? p9 : p8;
-    if (e && atoi(e) == 1) {
-        if (const char *lo = getenv("CRGPU_SORT_FINISH_LOW")) {  // experiment: exactly this many low bits
-            const uint32_t low = (uint32_t)atoi(lo);
-            return low >= 1 && low <= 16 && low < total_bits ? low : 0;
-        }
-        const uint32_t p = (total_bits - 16 + 8) / 9;      // passes of 9 bits for the top part
-        if (9 * p >= total_bits) return 0;
-        const uint32_t low = total_bits - 9 * p;          // <= 16 by construction
-        return p < full ? low : 0;
-    }
     // at most OR_MAX_LOW_BITS low bits, and at least 14 UMI bits above the cut (sixteen low bits for the 61-bit layout -- five passes --
-    // make the runs whole groups of UMIs and the finishing step 24 ms: measured): runs of up to 12 keys are ordered in registers
-    // (k_repair_runs), up to 64 by a wave (k_repair_medium_runs), longer ones by a workgroup in LDS (k_repair_long_runs); what does
-    // not fit the lists or LDS is walked through memory by one lane (two levels of at most 256 buckets beyond eight bits)
+    // make the runs whole groups of UMIs and the finishing step 24 ms: profiles/r03_count_stage_and_sort_ab.txt): runs of up to 12
+    // keys are ordered in registers (k_repair_runs), up to 64 by a wave (k_repair_medium_runs), longer ones by a workgroup in LDS
+    // (k_repair_long_runs); what does not fit the lists or LDS is walked through memory by one lane (two levels of at most 256
+    // buckets beyond eight bits)
     static_assert(OR_MAX_LOW_BITS >= 8 && OR_MAX_LOW_BITS <= 16, "or_run_through_memory: two levels of at most 256 buckets");
     uint32_t best_low = 0, best_passes = full;
-    uint32_t umi_above = 14u;  // UMI bits that stay above the cut (CRGPU_SORT_UMI_ABOVE: A/B)
-    if (const char *ua = getenv("CRGPU_SORT_UMI_ABOVE")) umi_above = (uint32_t)atoi(ua);
+    const uint32_t umi_above = 14u;  // UMI bits that stay above the cut
     for (uint32_t low = 1; low <= OR_MAX_LOW_BITS && low < total_bits; low++) {
         const uint32_t top = total_bits - low;
         const uint32_t q8 = (top + 7) / 8, q9 = (top + 8) / 9;
@@ -787,10 +755,6 @@ uint32_t cr_sort_low_bits(uint32_t total_bits, uint32_t umi_bits) {
         }
     }
     return best_low;
-}
-bool cr_sort_finish_experiment() {
-    const char *e = getenv("CRGPU_SORT_FINISH");
-    return e && atoi(e) == 1;
 }
 
 bool cr_sweep_plan(uint32_t lo_bit, uint32_t hi_bit, SweepPlan *plan, uint32_t *widths) {
@@ -815,119 +779,16 @@ bool cr_sweep_plan(uint32_t lo_bit, uint32_t hi_bit, SweepPlan *plan, uint32_t *
     return true;
 }
 
-// ---- finishing pass: order the runs of equal top bits by their low bits ---------------------------------------------
-// After the radix passes on bits [low, total) the keys are sorted by their top bits and stable otherwise.  Runs of equal
-// top bits are short (keys of one (barcode, feature, library) whose UMIs share their leading bases, mostly copies of one
-// key), so every key finds its place by counting the keys of its run that precede it (by low bits, ties by position:
-// exactly the order the full stable sort produces).  A workgroup takes the whole runs whose head lies in its tile of
-// FIN_TILE keys, stages tile + halo in LDS with one coalesced load (no dependent global loads) and writes back only the
-// keys that move.  A run longer than FIN_HALO raises *fallback and its tile writes nothing: the host then sorts the
-// buffer, still a permutation of the keys, again on all bits.
-#define FIN_TILE 4096u
-#define FIN_HALO 1024u     // keys staged behind the tile: the runs that begin in the tile end in there, or the sort is redone
-#define FIN_CAP (1u + FIN_TILE + FIN_HALO)
-template <bool HAS_VALS>
-__global__ __launch_bounds__(256) void k_finish_runs(uint64_t *__restrict__ keys, uint32_t *__restrict__ vals, uint64_t n,
-                                                     uint32_t low_bits, uint32_t *__restrict__ fallback) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    uint64_t *sk = reinterpret_cast<uint64_t *>(smem);                                       // FIN_CAP keys
-    uint16_t *spos = reinterpret_cast<uint16_t *>(smem + (size_t)FIN_CAP * 8);              // where each key belongs
-    uint32_t *sv = reinterpret_cast<uint32_t *>(smem + (size_t)FIN_CAP * 8 + ((FIN_CAP * 2 + 15) & ~15u));  // payloads
-    __shared__ uint32_t s_a, s_b, s_bad;
-    const uint32_t tid = threadIdx.x;
-    const uint64_t n_tiles = (n + FIN_TILE - 1) / FIN_TILE;
-    const uint64_t lowmask = (1ull << low_bits) - 1ull;
-    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const uint64_t t0 = tile * FIN_TILE, t1 = t0 + FIN_TILE < n ? t0 + FIN_TILE : n;
-        // one coalesced load of the window: the key before the tile, the tile, the halo
-        const uint64_t w0 = t0 ? t0 - 1 : 0, w1 = t1 + FIN_HALO < n ? t1 + FIN_HALO : n;
-        const uint32_t cnt = (uint32_t)(w1 - w0), off0 = (uint32_t)(t0 - w0), off1 = (uint32_t)(t1 - w0);
-        if (tid == 0) {
-            s_a = t0 == 0 ? 0u : 0xFFFFFFFFu;
-            s_b = 0xFFFFFFFFu;
-            s_bad = 0u;
-        }
-        for (uint32_t i = tid; i < cnt; i += 256) {
-            sk[i] = keys[w0 + i];
-            if (HAS_VALS) sv[i] = vals[w0 + i];
-        }
-        __syncthreads();
-        // [a, b): the whole runs whose head lies in the tile = first run head at or after t0 .. first one at or after t1
-        // (every thread keeps its first hit, a wave reduces, four LDS atomics per tile: one atomic per head cost 25 ms)
-        {
-            uint32_t fa = 0xFFFFFFFFu, fb = 0xFFFFFFFFu;
-            for (uint32_t i = tid + 1; i < cnt && fb == 0xFFFFFFFFu; i += 256) {
-                if ((sk[i] >> low_bits) == (sk[i - 1] >> low_bits)) continue;
-                if (i >= off0 && fa == 0xFFFFFFFFu) fa = i;
-                if (i >= off1) fb = i;
-            }
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {
-                const uint32_t xa = __shfl_xor(fa, d), xb = __shfl_xor(fb, d);
-                fa = xa < fa ? xa : fa;
-                fb = xb < fb ? xb : fb;
-            }
-            if ((tid & 63u) == 0u) {
-                if (fa != 0xFFFFFFFFu) atomicMin(&s_a, fa);
-                if (fb != 0xFFFFFFFFu) atomicMin(&s_b, fb);
-            }
-        }
-        __syncthreads();
-        const uint32_t ra = s_a;
-        uint32_t rb = s_b;
-        if (rb == 0xFFFFFFFFu && w1 == n) rb = cnt;  // the last run ends with the array
-        __syncthreads();
-        if (ra == 0xFFFFFFFFu || ra >= off1) {
-            // no run begins in this tile: it lies inside a run whose owner deals with it (or raises the fallback)
-            continue;
-        }
-        if (rb == 0xFFFFFFFFu) {  // the last run of the tile goes on beyond the halo
-            if (tid == 0) atomicOr(fallback, 1u);
-            continue;
-        }
-        for (uint32_t i = ra + tid; i < rb; i += 256) {
-            const uint64_t k = sk[i];
-            const uint64_t top = k >> low_bits, low = k & lowmask;
-            uint32_t s = i, e = i + 1, rank = 0;
-            while (s > ra && (sk[s - 1] >> low_bits) == top) s--;
-            while (e < rb && (sk[e] >> low_bits) == top) e++;
-            if (e - s > FIN_HALO) s_bad = 1u;  // quadratic work beyond this: leave it to the full sort
-            else {
-                for (uint32_t j = s; j < i; j++) rank += (sk[j] & lowmask) <= low;   // earlier position: ties stay in front
-                for (uint32_t j = i + 1; j < e; j++) rank += (sk[j] & lowmask) < low;
-            }
-            spos[i] = (uint16_t)(s + rank);
-        }
-        __syncthreads();
-        const bool bad = s_bad != 0u;
-        if (bad) {
-            if (tid == 0) atomicOr(fallback, 1u);  // nothing of this tile is written: the buffer stays a permutation
-        } else {
-            for (uint32_t i = ra + tid; i < rb; i += 256) {
-                const uint32_t p = spos[i];
-                if (p != i) {
-                    keys[w0 + p] = sk[i];
-                    if (HAS_VALS) vals[w0 + p] = sv[i];
-                }
-            }
-        }
-        __syncthreads();
-    }
-}
-
 // ---- ordering the short runs that a sort on the top bits leaves ------------------------------------------------------------
 // After passes on the bits above `low`, keys that agree on those bits sit next to each other in arrival order.  With the
 // cut of cr_sort_low_bits such runs are mostly single keys or copies of ONE key (the reads of a molecule); what needs work
 // are the reads of one UMI whose UmiType bits differ and the rare UMIs of a (barcode, feature) that share their leading bases.
-// One streaming pass: the lane that holds the first key of a run (neighbours from the lanes next to it, memory only at the
-// wave's edges) owns the run: two keys are compared and swapped in registers, longer runs (rare) are insertion-sorted in
-// place through memory, long disordered ones by an in-place bucket permutation on the low bits; a run of more than OR_MAX
-// keys raises *bad and the caller sorts on all bits instead.  Rewriting a run never changes the bits above the cut, which is
-// all a neighbouring lane looks at.
-#define OR_STEP 48u     // keys between the waves of k_order_runs (64 keys each)
+// Rewriting a run never changes the bits above the cut, which is all that the owner of a neighbouring run looks at.
+// First the part of the repair that one lane does through memory (or_run_through_memory): short runs are insertion-sorted
+// in place, long disordered ones by an in-place bucket permutation on the low bits; a run of more than OR_MAX keys raises
+// *bad and the caller sorts on all bits instead.
 #define OR_CAP 32u      // runs up to this length: insertion sort
 #define OR_MAX 65536u   // longer runs than this are not scanned by one lane: the caller sorts on all bits
-// one lane puts the run [i, e) in order through memory: e found by scanning, nothing to do when it is already ordered
 // in-place bucket permutation (American flag sort) of keys[a, e) on the `bits` (<= 8) bits above `shift`; cnt / nxt hold 2^bits
 // entries; on return cnt[d] = end of bucket d (relative to a)
 template <bool HAS_VALS>
@@ -989,6 +850,7 @@ __device__ void or_add_heads(const uint64_t *keys, uint64_t i, uint64_t e, const
     if (c) atomicAdd(&rh.counts[t], add ? c : 0u - c);
 }
 
+// one lane puts the run that starts at i in order through memory: its end found by scanning, nothing to do when it is ordered
 template <bool HAS_VALS>
 __device__ void or_run_through_memory(uint64_t *__restrict__ keys, uint32_t *__restrict__ vals, uint64_t n, uint32_t low, uint64_t i,
                                       uint32_t *__restrict__ bad, const RhDev rh = RhDev()) {
@@ -1027,7 +889,7 @@ __device__ void or_run_through_memory(uint64_t *__restrict__ keys, uint32_t *__r
     } else {
         // a long run that mixes low bits (many reads of one UMI with both UmiTypes, ...): in-place bucket permutation on the
         // low bits (American flag sort).  Up to 8 low bits: one level of at most 256 buckets; 9 .. OR_MAX_LOW_BITS: first on the
-        // bits above the low eight (at most 8 buckets), then every such bucket on its low eight.  (The bucket arrays live in
+        // bits above the low eight (up to 256 buckets), then every such bucket on its low eight.  (The bucket arrays live in
         // scratch, per lane: 256 entries each is what a kernel with 256-thread workgroups can afford.)
         uint32_t cnt[256], nxt[256];
         if (low > OR_MAX_LOW_BITS) {  // cannot happen (cr_sort_low_bits): never overrun the arrays, let the caller sort on all bits
@@ -1051,99 +913,8 @@ __device__ void or_run_through_memory(uint64_t *__restrict__ keys, uint32_t *__r
     if (rh.counts) or_add_heads(keys, i, e, rh, true);
 }
 
-template <bool HAS_VALS>
-__global__ __launch_bounds__(256) void k_order_runs(uint64_t *__restrict__ keys, uint32_t *__restrict__ vals, uint64_t n, uint32_t low,
-                                                    uint32_t *__restrict__ bad) {
-    // A wave looks at 64 consecutive keys but the waves are only OR_STEP keys apart: a wave owns the runs that START in its
-    // first OR_STEP lanes, so a run of up to 64 - OR_STEP + 1 keys always ends inside the wave that owns it (a run that
-    // leaves its wave costs one lane a serial walk through memory while the other 63 wait: with waves 64 apart that was
-    // half of all waves and 4 of the pass's 5.5 ms).
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t n_waves = (n + OR_STEP - 1) / OR_STEP;
-    const uint64_t wave_stride = (uint64_t)gridDim.x * (blockDim.x >> 6);
-    for (uint64_t gw = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); gw < n_waves; gw += wave_stride) {
-        const uint64_t i = gw * OR_STEP + lane;
-        const bool in = i < n;
-        const uint64_t ic = in ? i : n - 1;
-        uint64_t key = keys[ic];
-        uint32_t val = HAS_VALS ? vals[ic] : 0u;
-        const uint64_t key0 = key;
-        const uint32_t val0 = val;
-        uint64_t left = __shfl_up(key, 1);
-        if (lane == 0) left = ic > 0 ? keys[ic - 1] : ~key;
-        uint64_t behind = ~key;  // the key behind the wave (lane 63 only)
-        if (lane == 63 && ic + 1 < n) behind = keys[ic + 1];
-        const uint64_t top = key >> low;
-        const bool start = in && (i == 0 || (left >> low) != top);
-        const unsigned long long starts = __ballot(start);
-        const unsigned long long upto = ~0ull >> (63u - lane);  // lanes 0 .. lane
-        const bool has_head = (starts & upto) != 0ull;          // else: part of a run that began before the wave
-        const uint32_t rs = has_head ? 63u - (uint32_t)__clzll((long long)(starts & upto)) : 0u;
-        const unsigned long long above = lane < 63u ? starts >> (lane + 1u) : 0ull;
-        const uint32_t n_in = (uint32_t)__popcll(__ballot(in));  // lanes behind the last key hold a copy of it: not part of any run
-        uint32_t re = above ? lane + 1u + (uint32_t)__ffsll((long long)above) - 1u : 64u;  // exclusive
-        const bool to_wave_end = re == 64u;
-        re = re < n_in ? re : n_in;
-        // the wave's last run goes on behind the wave?  (also: keys behind n do not exist)
-        const bool last_goes_on = __shfl((behind >> low) == top && in, 63);
-        const bool owned = in && has_head && rs < OR_STEP;  // runs that start in the last lanes belong to the next wave
-        const bool closed = owned && !(to_wave_end && last_goes_on);
-        // a run that starts here and leaves the wave: its first lane does it through memory
-        if (start && owned && to_wave_end && last_goes_on) or_run_through_memory<HAS_VALS>(keys, vals, n, low, i, bad);
-        // closed runs with a descent somewhere: odd-even transposition across the lanes, in registers
-        const unsigned long long desc = __ballot(closed && lane > rs && key < left);
-        const unsigned long long mine = (re >= 64u ? ~0ull : ((1ull << re) - 1ull)) & ~((1ull << rs) - 1ull);  // lanes rs .. re - 1
-        const bool need = closed && (desc & mine) != 0ull;
-        uint32_t len = need ? re - rs : 0u;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const uint32_t o = __shfl_xor(len, d);
-            len = o > len ? o : len;
-        }
-        for (uint32_t t = 0; t < len; t++) {  // uniform: the longest run of the wave that needs work
-            const bool low_side = ((lane - rs) & 1u) == (t & 1u);
-            const uint32_t partner = low_side ? lane + 1u : lane - 1u;
-            const bool ok = need && (low_side ? partner < re : lane > rs);
-            const uint64_t pk = __shfl(key, (int)(partner & 63u));
-            const uint32_t pv = HAS_VALS ? __shfl(val, (int)(partner & 63u)) : 0u;
-            if (ok) {
-                const bool take = low_side ? pk < key : pk > key;  // the lower lane keeps the smaller key
-                if (take) {
-                    key = pk;
-                    val = pv;
-                }
-            }
-        }
-        if (need && (key != key0 || (HAS_VALS && val != val0))) {  // an equal key may have arrived with another read's ordinal
-            keys[i] = key;
-            if (HAS_VALS) vals[i] = val;
-        }
-    }
-}
-
-static int cr_order_runs_r02(crgpu_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, uint64_t n, uint32_t low_bits, bool *fell_back) {
-    *fell_back = false;
-    if (n < 2 || low_bits == 0) return CRGPU_OK;
-    uint32_t *d_flag = ctx->d_scalars + 52;
-    {
-        CrTimer t(ctx, CRGPU_T_SORT_HIST, n);  // booked beside the histogram slot: "sort, not a scatter pass"
-        CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
-        const dim3 grid(cr_grid((n + OR_STEP - 1) / OR_STEP * 64u, 256, 256u * 16u));
-        if (d_vals)
-            hipLaunchKernelGGL(k_order_runs<true>, grid, dim3(256), 0, ctx->stream, d_keys, d_vals, n, low_bits, d_flag);
-        else
-            hipLaunchKernelGGL(k_order_runs<false>, grid, dim3(256), 0, ctx->stream, d_keys, d_vals, n, low_bits, d_flag);
-        CR_HIP(ctx, hipGetLastError());
-    }
-    uint32_t flag = 0;
-    CR_TRY(crgpu_memcpy_d2h(ctx, &flag, d_flag, sizeof(flag)));
-    *fell_back = flag != 0;
-    return CRGPU_OK;
-}
-
-// ---- the same in two steps: find the descents, repair only the runs that hold one (the default since round 3) -------------
-// k_order_runs touches every key of the buffer one load per lane at a time (3.7 ms per 796 M keys, more than the radix pass
-// it saves).  But almost every run of equal top bits is a single key or copies of ONE key: nothing to do.  So:
+// ---- the finishing step: find the descents, repair only the runs that hold one -------------------------------------------
+// Almost every run of equal top bits is a single key or copies of ONE key: nothing to do.  So:
 //   k_find_descents   a streaming read with the wave-blocked layout of the run-length passes (several loads per lane in
 //                     flight, the left neighbour from the lane below): bit i of desc[] = key i continues the run of its left
 //                     neighbour (same bits above `low`) and is SMALLER than it -- the run is out of order there.  One 64-bit
@@ -1580,43 +1351,13 @@ int cr_repair_runs(crgpu_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, uint64_t 
     if (heads) heads->valid = count_heads && !*fell_back;  // (a run too long for the repair: nobody adjusted the counts for it)
     return CRGPU_OK;
 }
-// the finishing step behind the passes on the top bits: CRGPU_SORT_FINISH=3 keeps round 2's k_order_runs (A/B; no run heads)
-static int order_low_bits(crgpu_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, uint64_t n, uint32_t low_bits, bool *fell_back,
-                          CrRunHeads *heads = nullptr) {
-    if (heads) heads->valid = false;
-    const char *e = getenv("CRGPU_SORT_FINISH");
-    if (e && atoi(e) == 3) return cr_order_runs_r02(ctx, d_keys, d_vals, n, low_bits, fell_back);
+// the finishing step behind the passes on the top bits
+int cr_order_runs(crgpu_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, uint64_t n, uint32_t low_bits, bool *fell_back, CrRunHeads *heads) {
     return cr_repair_runs(ctx, d_keys, d_vals, n, low_bits, fell_back, heads);
 }
-int cr_order_runs(crgpu_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, uint64_t n, uint32_t low_bits, bool *fell_back, CrRunHeads *heads) {
-    return order_low_bits(ctx, d_keys, d_vals, n, low_bits, fell_back, heads);
-}
 
-static int finish_runs(crgpu_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, uint64_t n, uint32_t low_bits, bool *fell_back) {
-    *fell_back = false;
-    uint32_t *d_flag = ctx->d_scalars + 52;
-    const size_t lds = (size_t)FIN_CAP * 8 + ((FIN_CAP * 2 + 15) & ~15u) + (d_vals ? (size_t)FIN_CAP * 4 : 0);
-    {
-        CrTimer t(ctx, CRGPU_T_SORT_HIST, n);  // booked beside the histogram slot: "sort, not a scatter pass"
-        CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
-        const dim3 grid(cr_grid((n + FIN_TILE - 1) / FIN_TILE, 1, 256u * 8u));
-        if (d_vals) {
-            cr_allow_lds(ctx, (const void *)k_finish_runs<true>, lds);
-            hipLaunchKernelGGL(k_finish_runs<true>, grid, dim3(256), lds, ctx->stream, d_keys, d_vals, n, low_bits, d_flag);
-        } else {
-            cr_allow_lds(ctx, (const void *)k_finish_runs<false>, lds);
-            hipLaunchKernelGGL(k_finish_runs<false>, grid, dim3(256), lds, ctx->stream, d_keys, d_vals, n, low_bits, d_flag);
-        }
-        CR_HIP(ctx, hipGetLastError());
-    }
-    uint32_t flag = 0;
-    CR_TRY(crgpu_memcpy_d2h(ctx, &flag, d_flag, sizeof(flag)));
-    *fell_back = flag != 0;
-    return CRGPU_OK;
-}
-
-// low_left (nullable): the caller finishes the sort itself (cr_finish_emit: finishing pass fused with the run-length
-// pass); *low_left = number of low bits the passes did not sort on (0: fully sorted)
+// low_left (nullable): the caller finishes the sort itself (cr_order_runs, which can count the run heads on the way);
+// *low_left = number of low bits the passes did not sort on (0: fully sorted)
 template <typename K>
 static int radix_sort(crgpu_ctx *ctx, K *d_keys, K *d_tmp, uint32_t *d_vals, uint32_t *d_vals_tmp, uint64_t n,
                       uint32_t lo_bit, uint32_t hi_bit, bool *result_in_tmp, uint32_t *low_left = nullptr) {
@@ -1637,7 +1378,7 @@ static int radix_sort(crgpu_ctx *ctx, K *d_keys, K *d_tmp, uint32_t *d_vals, uin
     if (sizeof(K) == 8) {
         SweepPlan plan;
         uint32_t widths[OS_MAX_PASSES];
-        // the passes sort on the top bits only when that saves one; k_finish_runs orders the `low` bits afterwards
+        // the passes sort on the top bits only when that saves one; cr_order_runs orders the `low` bits afterwards
         const uint32_t low = (lo_bit == 0 && ctx->layout.set && hi_bit == ctx->layout.total_bits())
                                  ? cr_sort_low_bits(hi_bit, ctx->layout.bits_umi) : 0u;
         const bool sweep = cr_sweep_plan(lo_bit + low, hi_bit, &plan, widths);
@@ -1659,12 +1400,8 @@ static int radix_sort(crgpu_ctx *ctx, K *d_keys, K *d_tmp, uint32_t *d_vals, uin
                 return CRGPU_OK;
             }
             bool fell_back = false;
-            if (cr_sort_finish_experiment())
-                CR_TRY(finish_runs(ctx, *result_in_tmp ? k1 : k0, d_vals ? (*result_in_tmp ? d_vals_tmp : d_vals) : nullptr, n, low,
-                                   &fell_back));
-            else
-                CR_TRY(order_low_bits(ctx, *result_in_tmp ? k1 : k0, d_vals ? (*result_in_tmp ? d_vals_tmp : d_vals) : nullptr, n, low,
-                                      &fell_back));
+            CR_TRY(cr_order_runs(ctx, *result_in_tmp ? k1 : k0, d_vals ? (*result_in_tmp ? d_vals_tmp : d_vals) : nullptr, n, low,
+                                 &fell_back, nullptr));
             if (!fell_back) return CRGPU_OK;
             // a run of equal top bits too long for the finishing pass (it may have moved keys inside other runs: the
             // buffer still holds every key): sort it again on all bits
@@ -1711,7 +1448,8 @@ int cr_radix_sort_u64(crgpu_ctx *ctx, uint64_t *d_keys, uint64_t *d_tmp, uint32_
                       uint64_t n, uint32_t lo_bit, uint32_t hi_bit, bool *result_in_tmp) {
     return radix_sort<uint64_t>(ctx, d_keys, d_tmp, d_vals, d_vals_tmp, n, lo_bit, hi_bit, result_in_tmp);
 }
-// all key bits by radix passes, whatever CRGPU_SORT_FINISH says (the fallback of the fused finishing pass)
+// all key bits by radix passes, whatever CRGPU_SORT_FINISH says (the count stage's fallback when the finishing step meets a
+// run too long for it)
 int cr_radix_sort_u64_full(crgpu_ctx *ctx, uint64_t *d_keys, uint64_t *d_tmp, uint32_t *d_vals, uint32_t *d_vals_tmp, uint64_t n,
                            uint32_t hi_bit, bool *result_in_tmp) {
     *result_in_tmp = false;
@@ -1727,243 +1465,6 @@ int cr_radix_sort_u64_full(crgpu_ctx *ctx, uint64_t *d_keys, uint64_t *d_tmp, ui
 int cr_radix_sort_u64_top(crgpu_ctx *ctx, uint64_t *d_keys, uint64_t *d_tmp, uint32_t *d_vals, uint32_t *d_vals_tmp,
                           uint64_t n, uint32_t hi_bit, bool *result_in_tmp, uint32_t *low_left) {
     return radix_sort<uint64_t>(ctx, d_keys, d_tmp, d_vals, d_vals_tmp, n, 0, hi_bit, result_in_tmp, low_left);
-}
-
-// ---- finishing pass fused with the run-length pass -----------------------------------------------------------------------
-// The keys are sorted by their top bits (stable otherwise).  One pass over them orders every run of equal top bits by its
-// low bits in LDS (as k_finish_runs does) AND emits the distinct keys (ignoring the utype bit 0) with the position of their
-// first read -- what the two HeadFlag compaction launches did on fully sorted keys -- so the finishing costs no pass of
-// its own.  Tiles are handed out by tickets and get the number of distinct keys before them from a decoupled look-back
-// (one status word per tile), which keeps the output in key order.  WRITE_BACK (the per-read DupInfo path): the ordered
-// keys and payloads also go back to the buffer.  A run that outgrows the staged window raises *fallback (nothing of that
-// tile is emitted or written; the chain still moves on) and the host redoes everything the slow way.
-#define FE_TILE 2048u
-#define FE_HALO 512u
-#define FE_CAP (1u + FE_TILE + FE_HALO)
-#define FE_ROUNDS ((FE_CAP + 255u) / 256u)   // 11
-#define FE_WORDS ((FE_CAP + 63u) / 64u)      // 41
-template <bool WRITE_BACK>
-__global__ __launch_bounds__(256) void k_finish_emit(uint64_t *__restrict__ keys, uint32_t *__restrict__ vals, uint64_t n,
-                                                     uint32_t low_bits, uint64_t *__restrict__ ukey, uint32_t *__restrict__ upos,
-                                                     unsigned long long *__restrict__ status, uint32_t *__restrict__ ticket,
-                                                     unsigned long long *__restrict__ n_out, uint32_t *__restrict__ fallback) {
-    __shared__ __attribute__((aligned(16))) uint64_t sk[FE_CAP];
-    __shared__ uint16_t slo[FE_CAP], spos[FE_CAP];
-    __shared__ uint32_t sv[WRITE_BACK ? FE_CAP : 1];
-    __shared__ unsigned long long s_head[FE_WORDS + 1];
-    __shared__ uint32_t s_cnt[FE_ROUNDS * 4 + 4];
-    __shared__ unsigned long long s_base;
-    __shared__ uint32_t s_tile, s_a, s_b, s_bad;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint64_t n_tiles = (n + FE_TILE - 1) / FE_TILE;
-    const uint32_t lowmask = (1u << low_bits) - 1u;
-    for (;;) {
-        if (tid == 0) s_tile = atomicAdd(ticket, 1u);
-        __syncthreads();
-        const uint64_t tile = s_tile;
-        if (tile >= n_tiles) break;  // uniform
-        const uint64_t t0 = tile * FE_TILE, t1 = t0 + FE_TILE < n ? t0 + FE_TILE : n;
-        const uint64_t w0 = t0 ? t0 - 1 : 0, w1 = t1 + FE_HALO < n ? t1 + FE_HALO : n;
-        const uint32_t cnt = (uint32_t)(w1 - w0), off0 = (uint32_t)(t0 - w0), off1 = (uint32_t)(t1 - w0);
-        if (tid == 0) s_bad = 0u;
-        for (uint32_t i = tid; i < cnt; i += 256) {
-            const uint64_t k = keys[w0 + i];
-            sk[i] = k;
-            slo[i] = (uint16_t)((uint32_t)k & lowmask);
-            if (WRITE_BACK) sv[i] = vals[w0 + i];
-        }
-        __syncthreads();
-        // run heads (equal top bits) as a bit mask: one ballot per 64 positions
-#pragma unroll 1
-        for (uint32_t j = 0; j < FE_ROUNDS; j++) {
-            const uint32_t i = j * 256u + tid;
-            bool h = false;
-            if (i < cnt) h = i == 0 ? (w0 == 0) : (sk[i] >> low_bits) != (sk[i - 1] >> low_bits);
-            const unsigned long long m = __ballot(h);
-            if (lane == 0 && j * 4u + wave < FE_WORDS + 1) s_head[j * 4u + wave] = m;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            // [ra, rb): the whole runs whose head lies in the tile
-            uint32_t ra = 0xFFFFFFFFu, rb = 0xFFFFFFFFu;
-            for (uint32_t w = off0 >> 6; w < FE_WORDS && ra == 0xFFFFFFFFu; w++) {
-                unsigned long long m = s_head[w];
-                if (w == (off0 >> 6)) m &= ~0ull << (off0 & 63u);
-                if (m) ra = w * 64u + (uint32_t)(__ffsll((long long)m) - 1);
-            }
-            for (uint32_t w = off1 >> 6; w < FE_WORDS && rb == 0xFFFFFFFFu; w++) {
-                unsigned long long m = s_head[w];
-                if (w == (off1 >> 6)) m &= ~0ull << (off1 & 63u);
-                if (m) rb = w * 64u + (uint32_t)(__ffsll((long long)m) - 1);
-            }
-            if (rb == 0xFFFFFFFFu && w1 == n) rb = cnt;  // the last run ends with the array
-            if (ra != 0xFFFFFFFFu && ra >= off1) ra = 0xFFFFFFFFu;  // no run begins in this tile
-            if (ra != 0xFFFFFFFFu && rb == 0xFFFFFFFFu) s_bad = 1u;  // the tile's last run goes on beyond the halo
-            s_a = ra;
-            s_b = rb;
-        }
-        __syncthreads();
-        const uint32_t ra = s_a, rb = s_b;
-        const bool active = ra != 0xFFFFFFFFu && !s_bad;
-        // place of every key inside its run: bounds from the bit mask, rank by the 16-bit low parts
-        uint64_t mykey[FE_ROUNDS];
-        uint32_t myval[FE_ROUNDS];
-        if (active) {
-#pragma unroll 1
-            for (uint32_t j = 0; j < FE_ROUNDS; j++) {
-                const uint32_t i = j * 256u + tid;
-                if (i < ra || i >= rb) continue;
-                // s = last head at or before i
-                uint32_t w = i >> 6;
-                unsigned long long m = s_head[w] & (~0ull >> (63u - (i & 63u)));
-                while (!m) m = s_head[--w];  // position ra is a head: the walk ends there at the latest
-                const uint32_t s0 = w * 64u + 63u - (uint32_t)__clzll((long long)m);
-                // e = first head after i, or rb
-                uint32_t e0 = rb;
-                w = i >> 6;
-                m = (i & 63u) == 63u ? 0ull : (s_head[w] & (~0ull << ((i & 63u) + 1u)));
-                for (;;) {
-                    if (m) {
-                        const uint32_t c = w * 64u + (uint32_t)(__ffsll((long long)m) - 1);
-                        e0 = c < rb ? c : rb;
-                        break;
-                    }
-                    if (++w >= FE_WORDS || w * 64u >= rb) break;
-                    m = s_head[w];
-                }
-                uint32_t rank = i - s0;
-                if (e0 - s0 > 1u) {
-                    if (e0 - s0 > FE_HALO) {
-                        s_bad = 1u;  // quadratic work beyond this: the slow way
-                    } else {
-                        const uint32_t low = slo[i];
-                        rank = 0;
-                        for (uint32_t q = s0; q < i; q++) rank += slo[q] <= low;   // earlier position: ties stay in front
-                        for (uint32_t q = i + 1; q < e0; q++) rank += slo[q] < low;
-                    }
-                }
-                spos[i] = (uint16_t)(s0 + rank);
-            }
-        }
-        __syncthreads();
-        const bool ok = active && !s_bad;
-        if (ok) {
-            // permute in place through registers
-#pragma unroll
-            for (uint32_t j = 0; j < FE_ROUNDS; j++) {
-                const uint32_t i = j * 256u + tid;
-                if (i >= ra && i < rb) {
-                    mykey[j] = sk[i];
-                    if (WRITE_BACK) myval[j] = sv[i];
-                }
-            }
-        }
-        __syncthreads();
-        if (ok) {
-#pragma unroll
-            for (uint32_t j = 0; j < FE_ROUNDS; j++) {
-                const uint32_t i = j * 256u + tid;
-                if (i >= ra && i < rb) {
-                    const uint32_t p = spos[i];
-                    sk[p] = mykey[j];
-                    if (WRITE_BACK) sv[p] = myval[j];
-                }
-            }
-        }
-        __syncthreads();
-        // distinct keys (ignoring the utype bit) among [ra, rb): ra starts a run of equal top bits, so it is one
-        uint32_t below[FE_ROUNDS];
-#pragma unroll
-        for (uint32_t j = 0; j < FE_ROUNDS; j++) {
-            const uint32_t i = j * 256u + tid;
-            const bool d = ok && i >= ra && i < rb && (i == ra || (sk[i] >> 1) != (sk[i - 1] >> 1));
-            const unsigned long long m = __ballot(d);
-            below[j] = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-            if (lane == 0) s_cnt[j * 4u + wave] = (uint32_t)__popcll(m);
-        }
-        __syncthreads();
-        if (tid < 64) {  // exclusive scan of the FE_ROUNDS * 4 = 44 (round, wave) counts + the look-back, by wave 0
-            const uint32_t v = tid < FE_ROUNDS * 4u ? s_cnt[tid] : 0u;
-            uint32_t x = v;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t y = __shfl_up(x, d);
-                if (tid >= (uint32_t)d) x += y;
-            }
-            if (tid < FE_ROUNDS * 4u) s_cnt[tid] = x - v;
-            const uint32_t total = __shfl(x, 63);
-            if (tid == 0 && tile > 0)
-                __hip_atomic_store(&status[tile], OS_AGG | total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned long long excl = wave_lookback(status, tile);  // every lower ticket is running or done
-            if (tid == 0) {
-                __hip_atomic_store(&status[tile], OS_INC | (excl + total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (tile + 1 == n_tiles) *n_out = excl + total;
-                s_base = excl;
-            }
-        }
-        __syncthreads();
-        if (ok) {
-            const unsigned long long base = s_base;
-#pragma unroll
-            for (uint32_t j = 0; j < FE_ROUNDS; j++) {
-                const uint32_t i = j * 256u + tid;
-                if (i < ra || i >= rb) continue;
-                const uint64_t k = sk[i];
-                if (i == ra || (k >> 1) != (sk[i - 1] >> 1)) {
-                    const unsigned long long o = base + s_cnt[j * 4u + wave] + below[j];
-                    ukey[o] = k;
-                    upos[o] = (uint32_t)(w0 + i);
-                }
-                if (WRITE_BACK) {
-                    keys[w0 + i] = k;
-                    vals[w0 + i] = sv[i];
-                }
-            }
-        } else if (s_bad && tid == 0) {
-            atomicOr(fallback, 1u);
-        }
-        __syncthreads();
-    }
-}
-
-// Finishes a sort that cr_radix_sort_u64_top left with `low_bits` unsorted low bits and emits the distinct keys:
-// ukey / upos (room for n entries), *nd_out = their number.  *fell_back: a run was too long; ukey / upos are garbage, the
-// keys (and payloads) are untouched or partly ordered inside their runs -- still the same multiset.
-int cr_finish_emit(crgpu_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, uint64_t n, uint32_t low_bits, uint64_t *d_ukey,
-                   uint32_t *d_upos, uint64_t *nd_out, bool *fell_back) {
-    *fell_back = false;
-    *nd_out = 0;
-    if (n == 0) return CRGPU_OK;
-    const uint64_t n_tiles = (n + FE_TILE - 1) / FE_TILE;
-    void *d_status = nullptr;
-    CR_TRY(cr_pool_alloc(ctx, &d_status, n_tiles * sizeof(unsigned long long) + 64));
-    uint32_t *d_ticket = ctx->d_scalars + 44, *d_flag = ctx->d_scalars + 52;
-    unsigned long long *d_n = (unsigned long long *)(ctx->d_scalars + 8);
-    hipError_t e;
-    {
-        CrTimer t(ctx, CRGPU_T_DEDUP, n);  // it is the run-length pass of the dedup family (which counts its keys here)
-        e = hipMemsetAsync(d_status, 0, n_tiles * sizeof(unsigned long long), ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_ticket, 0, sizeof(uint32_t), ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(d_n, 0, sizeof(unsigned long long), ctx->stream);
-        const dim3 grid((unsigned)(n_tiles < 2048 ? n_tiles : 2048));
-        if (d_vals)
-            hipLaunchKernelGGL(k_finish_emit<true>, grid, dim3(256), 0, ctx->stream, d_keys, d_vals, n, low_bits, d_ukey, d_upos,
-                               (unsigned long long *)d_status, d_ticket, d_n, d_flag);
-        else
-            hipLaunchKernelGGL(k_finish_emit<false>, grid, dim3(256), 0, ctx->stream, d_keys, d_vals, n, low_bits, d_ukey, d_upos,
-                               (unsigned long long *)d_status, d_ticket, d_n, d_flag);
-        if (e == hipSuccess) e = hipGetLastError();
-    }
-    cr_pool_free(ctx, d_status);
-    if (e != hipSuccess) return cr_fail(ctx, CRGPU_EHIP, "finish + emit: %s", hipGetErrorString(e));
-    uint32_t flag = 0;
-    unsigned long long nd = 0;
-    CR_TRY(crgpu_memcpy_d2h(ctx, &flag, d_flag, sizeof(flag)));
-    CR_TRY(crgpu_memcpy_d2h(ctx, &nd, d_n, sizeof(nd)));
-    *fell_back = flag != 0;
-    *nd_out = nd;
-    return CRGPU_OK;
 }
 
 int cr_radix_sort_u32(crgpu_ctx *ctx, uint32_t *d_keys, uint32_t *d_tmp, uint32_t *d_vals, uint32_t *d_vals_tmp,
@@ -2026,12 +1527,4 @@ int cr_partition_by_owner_kv(crgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_o
 int cr_partition_by_owner(crgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, uint64_t n, uint32_t sh_bc,
                           uint32_t n_ranks, const uint32_t *bounds, uint64_t *counts_out) {
     return cr_partition_by_owner_kv(ctx, d_in, d_out, nullptr, nullptr, n, sh_bc, n_ranks, bounds, counts_out);
-}
-
-// One stable counting pass of (64-bit value, 32-bit payload) pairs keyed by the top bits of the PAYLOAD: groups the
-// per-read records of the DupInfo path by windows of read ordinals before they are scattered to the reads.
-int cr_partition_by_payload(crgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, const uint32_t *d_vin, uint32_t *d_vout,
-                            uint64_t n, uint32_t shift) {
-    if (n == 0) return CRGPU_OK;
-    return radix_pass<uint64_t, PayloadDigit, 9>(ctx, d_in, d_out, d_vin, d_vout, n, PayloadDigit{shift, 511u}, CRGPU_T_DEDUP);
 }

@@ -28,8 +28,8 @@ def family(k):
                             "k_flag_corrected")): return "correct"
     if any(x in k for x in ("k_csc", "SeenFlag")): return "matrix"
     if any(x in k for x in ("k_extract_", "k_feature_counts", "k_match_features")): return "feature"
-    if any(x in k for x in ("k_find_descents", "k_tile_heads", "k_repair_runs", "k_order_runs", "k_global_hist")): return "sort_hist"
-    if any(x in k for x in ("k_cp_", "k_correct_umis", "k_giant", "k_rep_", "k_group_", "k_low_support", "k_triplets", "k_radix_scatter<unsigned int",
+    if any(x in k for x in ("k_find_descents", "k_tile_heads", "k_repair_runs", "k_global_hist")): return "sort_hist"
+    if any(x in k for x in ("k_cp_", "k_correct_umis", "k_giant", "k_rep_", "k_group_", "k_low_support", "k_radix_scatter<unsigned int",
                             "k_radix_hist<unsigned int", "k_per_read", "k_unpack", "k_corrected_reads", "k_mt_", "k_rl_", "k_trip_counts")): return "dedup"
     return None
 kern, fam = [], collections.defaultdict(float)

@@ -337,12 +337,11 @@ def test_clustered_umis_and_long_runs_of_near_identical_keys(big_run, finish, wi
     """UMIs that differ only in their last bases (three 8-base prefixes), UmiTypes mixed inside every UMI, and keys that
     agree in everything but the last 2.5 bases of the UMI in runs of 2..30, of 100 and of 50 000 reads: Hamming-1
     neighbourhoods are dense, counts tie, and one (barcode, feature) segment holds most of the reads.
-    finish (CRGPU_SORT_FINISH): "0" = radix passes on every key bit; "2" (the default since round 3) = the sort leaves the
+    finish (CRGPU_SORT_FINISH): "0" = radix passes on every key bit; "2" (the default) = the sort leaves the
     lowest key bits that save a pass to k_find_descents + k_repair_runs (only the runs of equal top bits that are out of order
     are touched: up to 12 keys in registers, up to 64 by a wave, longer ones by a workgroup in LDS, beyond 4096 keys an in-place
-    bucket permutation through memory up to 65 536); "3" = round 2's k_order_runs (runs inside
-    a wave by an odd-even transposition in registers).  A run of 90 000 keys makes either hand the job back to a sort on all
-    bits (CRGPU_STAT_SORT_REFINISHED).  wide: a 6.8 M-entry whitelist and 36 601 features make the key 64 bits wide; the
+    bucket permutation through memory up to 65 536); "3" = any value other than "0" means the default as well.  A run of
+    90 000 keys makes it hand the job back to a sort on all bits (CRGPU_STAT_SORT_REFINISHED).  wide: a 6.8 M-entry whitelist and 36 601 features make the key 64 bits wide; the
     passes then leave TEN low bits (six passes instead of seven): runs of 13 .. 64 keys are put in order by a wave (a lane per
     key, place = number of keys that go before it), the long run by the two-level bucket permutation."""
     top_bits_sort = finish != "0"
@@ -486,25 +485,30 @@ def test_3m_whitelist_64_bit_keys_bit_exact():
     c.close()
 
 
-def test_finishing_pass_hands_long_runs_back_to_the_full_sort(monkeypatch):
-    """(experimental path, CRGPU_SORT_FINISH=1) The radix passes sort the molecule keys on their top bits and k_finish_runs orders the runs of equal top bits.
-    One (barcode, feature) whose UMIs all share their leading bases makes a run far longer than the finishing pass
-    stages (FIN_RUN_MAX): the sort must notice, redo the buffer on all key bits, and give the same molecules as the
-    plain seven / eight-pass sort (CRGPU_SORT_FINISH=0) -- checked through the oracle."""
+def test_finishing_pass_hands_long_runs_back_to_the_full_sort():
+    """The radix passes sort the molecule keys on their top bits and the repair step (k_find_descents + k_repair_runs)
+    orders the runs of equal top bits.  With the 43-bit layout the passes leave 7 low bits (five passes for 43 bits, four for
+    36; 24 UMI bits >= 14 + 6): a run is the reads of one (barcode, feature) whose UMIs share their first nine bases.
+    90 000 reads with such UMIs make one run longer than the repair step walks (OR_MAX = 65 536): it must notice, the count
+    stage redoes the buffer on all key bits, and the molecules are those of a sort on every bit -- checked through the
+    oracle.  The other 60 000 reads (four fixed leading bases, runs of about 60 keys) keep the short-run repairs busy in
+    the same buffer."""
     _needs_onesweep()
     import gpu_helpers as G
     import oracle_lib as O
     from cellranger_amd import engine as E
 
-    monkeypatch.setenv("CRGPU_SORT_FINISH", "1")
     rng = np.random.default_rng(5)
-    n = 60_000
+    n_short, n_long = 60_000, 90_000
+    n = n_short + n_long
     wl = ["ACGTACGTACGTACGT", "TTTTACGTACGTACGA", "GGGGACGTACGTACCC"]
     c = G.fresh_ctx(dense=False)   # records without a barcode stage: no tables to take a BarcodeIndex from
     c.set_whitelist_ascii(0, wl)
-    c.set_key_layout(40_000, 12, 1, 0)   # 2 + 16 + 24 + 1 = 43 bits: three passes + 16 low bits
-    # every UMI = 4 fixed leading bases + 8 random ones: 65 536 possible keys share the top bits of one run
-    umi = (np.uint32(0b00011011) << np.uint32(16)) | rng.integers(0, 1 << 16, n, dtype=np.uint32)
+    c.set_key_layout(40_000, 12, 1, 0)   # 2 + 16 + 24 + 1 = 43 bits: four passes + 7 low bits
+    # 60 000 UMIs = 4 fixed leading bases + 8 random ones; 90 000 UMIs = 9 other fixed leading bases + 3 random ones: the
+    # top 18 UMI bits, all that lies above the cut, are equal -- one run
+    umi = np.concatenate([(np.uint32(0b00011011) << np.uint32(16)) | rng.integers(0, 1 << 16, n_short, dtype=np.uint32),
+                          (np.uint32(0b111001001101100011) << np.uint32(6)) | rng.integers(0, 1 << 6, n_long, dtype=np.uint32)])
     idx = np.zeros(n, np.uint32)
     feature = np.full(n, 7, np.uint32)
     uq = np.full((n, 12), 70, np.uint8)
@@ -526,16 +530,14 @@ def test_finishing_pass_hands_long_runs_back_to_the_full_sort(monkeypatch):
     c.close()
 
 
-@pytest.mark.parametrize("levels", ["1", "2"])
 @pytest.mark.parametrize("n", [300_000, 2_000_000])
-def test_windowed_dupinfo_scatter_matches_the_oracle(n, levels, monkeypatch):
-    """The experimental windowed scatter of the per-read records (CRGPU_DUPINFO_WINDOWED=1: k_per_read_sorted ->
-    cr_partition_by_payload -> k_scatter_records; =2: two partition passes, windows of 2^(bits - 18) reads): every read's
-    DupInfo equals the oracle's, as the direct path's does in the other tests."""
+def test_dupinfo_scatter_matches_the_oracle(n):
+    """The scatter of the per-read records (k_per_read -> k_unpack_dupinfo): every read's DupInfo equals the oracle's.  At
+    2 M reads the distinct keys pass 2^20: the scatter then runs on the second stream beside the molecule / triplet passes,
+    at the threshold a context has by default."""
     import gpu_helpers as G
     from cellranger_amd import synth as S
 
-    monkeypatch.setenv("CRGPU_DUPINFO_WINDOWED", levels)
     w = S.Workload(n_total=n, seed=S.SEED0 + 9, n_wl=100_000, n_cells=300, n_ambient=20000, n_genes=2000)
     c = G.fresh_ctx()
     c.set_whitelist(0, w.wl_packed, length=16)
