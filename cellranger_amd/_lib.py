@@ -162,6 +162,35 @@ class OrdmagResult(C.Structure):
     ]
 
 
+class EmptydropsResult(C.Structure):
+    """crgpu_emptydrops_result"""
+    _fields_ = [
+        ("status", C.c_int32),
+        ("sim_in_lds", C.c_int32),
+        ("n_ambient_used", C.c_uint64),
+        ("max_background_umis", C.c_uint64),
+        ("emptydrops_minimum_umis", C.c_uint64),
+        ("n_eval_features", C.c_uint64),
+        ("n_candidates", C.c_uint64),
+        ("n_distinct_n", C.c_uint64),
+        ("n_nonambient", C.c_uint64),
+        ("sgt_slope", C.c_double),
+        ("sgt_p0", C.c_double),
+        ("sim_ms", C.c_double),
+    ]
+
+
+class EmptydropsArrays(C.Structure):
+    """crgpu_emptydrops_arrays"""
+    _fields_ = [(n, C.c_uint64) for n in ("n_candidates", "n_called", "n_eval_features", "n_distinct_n", "num_sims")] + [
+        (n, C.c_void_p) for n in ("d_eval_cols", "d_umis", "d_obs_loglk", "d_n_lower", "d_pvalues", "d_pvalues_adj", "d_is_nonambient",
+                                  "d_called_cols", "d_eval_features", "d_profile_p", "d_sim_n", "d_sim_loglk")]
+
+
+ED_STATUS = {0: "ok", 1: "no usable ambient barcode", 2: "SGT not applicable", 3: "no initial cell", 4: "no candidate"}
+ED_KEEP_PROFILE, ED_KEEP_SIM_TABLE = 1, 2
+SGT_TOO_FEW, SGT_SLOPE = 1, 2
+
 # every symbol include/crgpu.h declares: (restype, argtypes)
 _vp, _u8p, _u32, _u64, _i, _dbl = C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_double
 SYMBOLS = {
@@ -258,6 +287,12 @@ SYMBOLS = {
     "crgpu_cell_ranks_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u64, _vp]),
     "crgpu_select_barcodes_cols_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u64, C.POINTER(C.POINTER(MatrixDevView))]),
     "crgpu_mt19937_stream_dev": (_i, [_vp, _u32, _u64, _vp, C.POINTER(_u64), C.POINTER(_dbl)]),
+    "crgpu_sgt_proportions": (_i, [_vp, _u64, _vp, C.POINTER(_dbl), C.POINTER(_dbl)]),
+    "crgpu_emptydrops_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, _vp, _vp, _u64, _u64, _u64, _u64, _u32, _dbl, _u64, _vp, _u32,
+                                  _vp, _u32, C.POINTER(EmptydropsResult), C.POINTER(EmptydropsArrays)]),
+    "crgpu_ambient_pvalues_dev": (_i, [_vp, _vp, _vp, _u64, _vp, _u32, _vp, _u32, _dbl, _vp, _vp, _vp, _vp, C.POINTER(_u64)]),
+    "crgpu_emptydrops_arrays_free": (None, [_vp, C.POINTER(EmptydropsArrays)]),
+    "crgpu_emptydrops_simulate_dev": (_i, [_vp, _vp, _u32, _vp, _vp, _u64, _u32, _u64, _vp, C.POINTER(_u32), _vp, _vp, C.POINTER(_dbl)]),
     "crgpu_matrix_dev_download": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _vp, _vp, _vp]),
     "crgpu_count": (_i, [_vp, C.POINTER(Records), _u32, C.POINTER(C.POINTER(MatrixView))]),
     "crgpu_set_feature_pattern": (_i, [_vp, _i, C.c_char_p, _u32, _u32, _vp, _vp]),

@@ -215,6 +215,7 @@ struct crgpu_ctx {
     uint64_t probe_segments[3] = {0, 0, 0};  // barcode segments the last probe-triplet computation ordered per wave / per workgroup / by the global sort
     uint32_t probe_seg_cap = 0xFFFFFFFFu;  // CRGPU_PROBE_SEG_CAP (tests, read at create): largest segment the LDS classes take
     uint32_t ordmag_batch = 0;             // CRGPU_ORDMAG_BATCH (tests, read at create): bootstrap samples per batch of the cell call, 0 = by memory
+    uint32_t ed_lds_features = 0xFFFFFFFFu;  // CRGPU_ED_LDS_FEATURES (tests, read at create): largest n_eval_features the EmptyDrops simulation counts in LDS
 
     double max_expected_errors = 1.7976931348623157e308;  // corrector.rs:104 (f64::MAX)
     double confidence_threshold = 0.975;                   // corrector.rs:83

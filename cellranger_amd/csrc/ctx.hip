@@ -88,6 +88,21 @@ const std::vector<AbiStruct> &abi_table() {
               ABI_F(crgpu_ordmag_result, filtered_bcs_ub), ABI_F(crgpu_ordmag_result, filtered_bcs),
               ABI_F(crgpu_ordmag_result, filtered_bcs_cutoff), ABI_F(crgpu_ordmag_result, filtered_bcs_cutoff_set),
               ABI_F(crgpu_ordmag_result, estimated)),
+        ABI_S(crgpu_emptydrops_result, ABI_F(crgpu_emptydrops_result, status), ABI_F(crgpu_emptydrops_result, sim_in_lds),
+              ABI_F(crgpu_emptydrops_result, n_ambient_used), ABI_F(crgpu_emptydrops_result, max_background_umis),
+              ABI_F(crgpu_emptydrops_result, emptydrops_minimum_umis), ABI_F(crgpu_emptydrops_result, n_eval_features),
+              ABI_F(crgpu_emptydrops_result, n_candidates), ABI_F(crgpu_emptydrops_result, n_distinct_n),
+              ABI_F(crgpu_emptydrops_result, n_nonambient), ABI_F(crgpu_emptydrops_result, sgt_slope),
+              ABI_F(crgpu_emptydrops_result, sgt_p0), ABI_F(crgpu_emptydrops_result, sim_ms)),
+        ABI_S(crgpu_emptydrops_arrays, ABI_F(crgpu_emptydrops_arrays, n_candidates), ABI_F(crgpu_emptydrops_arrays, n_called),
+              ABI_F(crgpu_emptydrops_arrays, n_eval_features), ABI_F(crgpu_emptydrops_arrays, n_distinct_n),
+              ABI_F(crgpu_emptydrops_arrays, num_sims), ABI_F(crgpu_emptydrops_arrays, d_eval_cols),
+              ABI_F(crgpu_emptydrops_arrays, d_umis), ABI_F(crgpu_emptydrops_arrays, d_obs_loglk),
+              ABI_F(crgpu_emptydrops_arrays, d_n_lower), ABI_F(crgpu_emptydrops_arrays, d_pvalues),
+              ABI_F(crgpu_emptydrops_arrays, d_pvalues_adj), ABI_F(crgpu_emptydrops_arrays, d_is_nonambient),
+              ABI_F(crgpu_emptydrops_arrays, d_called_cols), ABI_F(crgpu_emptydrops_arrays, d_eval_features),
+              ABI_F(crgpu_emptydrops_arrays, d_profile_p), ABI_F(crgpu_emptydrops_arrays, d_sim_n),
+              ABI_F(crgpu_emptydrops_arrays, d_sim_loglk)),
     };
     return t;
 }
@@ -165,6 +180,7 @@ extern "C" int crgpu_create(crgpu_ctx **out, int device_id, int n_ranks, int ran
     }
     if (const char *cap = getenv("CRGPU_PROBE_SEG_CAP")) ctx->probe_seg_cap = (uint32_t)strtoul(cap, nullptr, 10);  // tests: force the global route
     if (const char *b = getenv("CRGPU_ORDMAG_BATCH")) ctx->ordmag_batch = (uint32_t)strtoul(b, nullptr, 10);  // tests: small batches of the cell call
+    if (const char *f = getenv("CRGPU_ED_LDS_FEATURES")) ctx->ed_lds_features = (uint32_t)strtoul(f, nullptr, 10);  // tests: 0 = counters in global memory
     // probability(q) = 10^(-(q-33)/10) computed on the HOST with libm pow, exactly as the
     // reference does per call (corrector.rs:167-171), for every 7-bit quality character.
     double ptab[128];

@@ -2966,3 +2966,4 @@ extern "C" int crgpu_trim_molecule_barcodes_dev(crgpu_ctx *ctx, uint64_t *d_barc
 
 #include "probe_counts.h"
 #include "cell_calling.h"
+#include "emptydrops.h"

@@ -227,6 +227,9 @@ class CellCall:
 
     def __init__(self, ctx, cols, n_cells, res, matrix=None):
         self.ctx, self.cols, self.n_cells, self._matrix = ctx, cols, n_cells, matrix
+        if isinstance(res, dict):  # a merged call (Context.call_additional_cells) keeps the metrics of the initial one
+            self.metrics = dict(res)
+            return
         m = {}
         for name, _ in _lib.OrdmagResult._fields_:
             v = getattr(res, name)
@@ -260,6 +263,57 @@ class CellCall:
         mv = C.POINTER(_lib.MatrixDevView)()
         self.ctx._check(self.ctx.L.crgpu_select_barcodes_cols_dev(self.ctx.h, m._mv, _p(self.cols), self.n_cells, C.byref(mv)))
         return MatrixDev(self.ctx, mv)
+
+
+class AdditionalCells:
+    """Result of Context.call_additional_cells (find_nonambient_barcodes, cell_calling.py:144-263).  Per candidate, in
+    ascending column order (the rows of nonambient_summary): eval_cols, umis, obs_loglk, n_lower, pvalues, pvalues_adj,
+    is_nonambient (numpy).  `status` = 0 or which `return None` of the reference was taken (status_text), `metrics` =
+    crgpu_emptydrops_result as a dict, `call` = the merged CellCall (initial cells + non-ambient candidates), whose
+    .filtered_matrix() and .ranks work as after the initial call.  profile_p / eval_features and sim_n / sim_loglk are set
+    when they were asked for."""
+
+    def __init__(self, ctx, res, arr, initial, matrix):
+        self.metrics = {name: getattr(res, name) for name, _ in _lib.EmptydropsResult._fields_}
+        self.status = int(res.status)
+        self.status_text = _lib.ED_STATUS[self.status]
+        n = int(arr.n_candidates)
+
+        def take(name, dtype, count):
+            p = getattr(arr, name)
+            if not (p and count):
+                return np.zeros(0, dtype)  # (an unused allocation goes with crgpu_emptydrops_arrays_free below)
+            setattr(arr, name, None)  # adopted: released with the DeviceArray
+            return DeviceArray(ctx, count, dtype, adopt=p).to_host(count)
+
+        self.eval_cols = take("d_eval_cols", np.uint64, n)
+        self.umis = take("d_umis", np.uint32, n)
+        self.obs_loglk = take("d_obs_loglk", np.float64, n)
+        self.n_lower = take("d_n_lower", np.uint32, n)
+        self.pvalues = take("d_pvalues", np.float64, n)
+        self.pvalues_adj = take("d_pvalues_adj", np.float64, n)
+        self.is_nonambient = take("d_is_nonambient", np.uint8, n).astype(bool)
+        nf, nd, ns = int(arr.n_eval_features), int(arr.n_distinct_n), int(arr.num_sims)
+        self.eval_features = take("d_eval_features", np.uint32, nf) if arr.d_eval_features else None
+        self.profile_p = take("d_profile_p", np.float64, nf) if arr.d_profile_p else None
+        self.sim_n = take("d_sim_n", np.int64, nd) if arr.d_sim_n else None
+        self.sim_loglk = take("d_sim_loglk", np.float64, nd * ns).reshape(nd, ns) if arr.d_sim_loglk else None
+        cols, n_called = arr.d_called_cols, int(arr.n_called)
+        arr.d_called_cols = None
+        d_cols = DeviceArray(ctx, n_called, np.uint64, adopt=cols) if cols else ctx.empty(0, np.uint64)
+        self.call = CellCall(ctx, d_cols, n_called, initial.metrics, matrix)
+        ctx.L.crgpu_emptydrops_arrays_free(ctx.h, C.byref(arr))  # whatever was not taken
+
+
+def sgt_proportions(freq):
+    """sgt_proportions (sgt.py:97-132) on the host through the C ABI: non-zero item frequencies -> (pstar, p0, slope, status);
+    status 0, or _lib.SGT_TOO_FEW / _lib.SGT_SLOPE for the reference's two SimpleGoodTuringError cases (pstar is then None)"""
+    f = np.ascontiguousarray(freq, dtype=np.uint64)
+    pstar, p0, slope = np.zeros(len(f), np.float64), C.c_double(np.nan), C.c_double(np.nan)
+    rc = _lib.load().crgpu_sgt_proportions(ptr(f), len(f), ptr(pstar), C.byref(p0), C.byref(slope))
+    if rc < 0:
+        raise _lib.CrgpuError(rc, "crgpu_sgt_proportions")
+    return (pstar if rc == 0 else None), p0.value, slope.value, rc
 
 
 def ordmag_candidates(max_expected_cells=1 << 18):
@@ -805,6 +859,58 @@ class Context:
         # no barcode called: an empty list of our own, so that .ranks / .filtered_matrix work on an all-zero well, too
         d_cols = DeviceArray(self, n.value, np.uint64, adopt=cols.value) if cols.value else self.empty(0, np.uint64)
         return CellCall(self, d_cols, n.value, res, matrix)
+
+    def call_additional_cells(self, m, call, low, high, emptydrops_minimum_umis=500, num_sims=10000, max_adj_pvalue=0.01, seed=0,
+                              feature_mask=None, sim_table=None, keep_sim_table=False, keep_profile=True):
+        """find_nonambient_barcodes (cell_calling.py:144-263) behind the initial call `call` (CellCall) on the MatrixDev `m`:
+        the ambient profile from places [low, high) of the descending totals (get_empty_drops_range), the candidates above
+        max(emptydrops_minimum_umis, 1 + max_background_umis), their p-values from num_sims simulations on the device (seed:
+        the Philox key) or from sim_table = (sim_n, sim_loglk) of the reference's simulate_multinomial_loglikelihoods, BH and
+        the merged call -> AdditionalCells.  feature_mask: the rows of one genome / library type (crgpu.h)."""
+        mask = None if feature_mask is None else np.ascontiguousarray(np.asarray(feature_mask) != 0, dtype=np.uint8)
+        d_counts = self.column_sums(m, mask)
+        sim_n = sim_ll = None
+        if sim_table is not None:
+            sim_n = np.ascontiguousarray(sim_table[0], dtype=np.int64)
+            sim_ll = np.ascontiguousarray(sim_table[1], dtype=np.float64)
+            if sim_ll.shape != (len(sim_n), num_sims):
+                raise ValueError("sim_table: sim_loglk must be len(sim_n) x num_sims")
+        flags = (_lib.ED_KEEP_PROFILE if keep_profile else 0) | (_lib.ED_KEEP_SIM_TABLE if keep_sim_table and sim_table is None else 0)
+        res, arr = _lib.EmptydropsResult(), _lib.EmptydropsArrays()
+        self._check(self.L.crgpu_emptydrops_dev(self.h, m._mv, ptr(mask), 0 if mask is None else len(mask), _p(d_counts), _p(call.cols),
+                                                call.n_cells, low, high, emptydrops_minimum_umis, num_sims, max_adj_pvalue, seed,
+                                                ptr(sim_n), 0 if sim_n is None else len(sim_n), ptr(sim_ll), flags, C.byref(res),
+                                                C.byref(arr)))
+        return AdditionalCells(self, res, arr, call, m)
+
+    def ambient_pvalues(self, umis, obs_loglk, sim_n, sim_loglk, max_adj_pvalue=0.01):
+        """compute_ambient_pvalues (stats.py:205-231) + adjust_pvalue_bh + the calls against a simulated table ->
+        (n_lower, pvalues, pvalues_adj, is_nonambient) as numpy arrays"""
+        umis, obs = np.ascontiguousarray(umis, dtype=np.uint32), np.ascontiguousarray(obs_loglk, dtype=np.float64)
+        sim_n, tab = np.ascontiguousarray(sim_n, dtype=np.int64), np.ascontiguousarray(sim_loglk, dtype=np.float64)
+        assert tab.ndim == 2 and tab.shape[0] == len(sim_n) and len(umis) == len(obs)
+        n = len(umis)
+        d_nl, d_p, d_q, d_c = self.empty(n, np.uint32), self.empty(n, np.float64), self.empty(n, np.float64), self.empty(n, np.uint8)
+        d_umis, d_obs, d_tab = self.upload(umis), self.upload(obs), self.upload(tab.ravel())    # named: alive until the call is over
+        called = C.c_uint64()
+        self._check(self.L.crgpu_ambient_pvalues_dev(self.h, _p(d_umis), _p(d_obs), n, ptr(sim_n), len(sim_n), _p(d_tab), tab.shape[1],
+                                                     max_adj_pvalue, _p(d_nl), _p(d_p), _p(d_q), _p(d_c), C.byref(called)))
+        return d_nl.to_host(n), d_p.to_host(n), d_q.to_host(n), d_c.to_host(n).astype(bool)
+
+    def emptydrops_simulate(self, profile_p, umis, num_sims, seed=0, obs_loglk=None, keep_table=True):
+        """the simulation kernel of call_additional_cells on its own (test and measurement hook): -> (sim_n, sim_loglk or
+        None, n_lower or None, kernel milliseconds)"""
+        p = np.ascontiguousarray(profile_p, dtype=np.float64)
+        u = np.ascontiguousarray(umis, dtype=np.uint32)
+        obs = None if obs_loglk is None else np.ascontiguousarray(obs_loglk, dtype=np.float64)
+        d = len(np.unique(u))
+        sim_n, tab = np.zeros(len(u), np.int64), (np.zeros((d, num_sims), np.float64) if keep_table else None)
+        nl = None if obs is None else np.zeros(len(u), np.uint32)
+        nd, ms = C.c_uint32(), C.c_double()
+        self._check(self.L.crgpu_emptydrops_simulate_dev(self.h, ptr(p), len(p), ptr(u), ptr(obs), len(u), num_sims, seed, ptr(sim_n),
+                                                         C.byref(nd), ptr(tab), ptr(nl), C.byref(ms)))
+        assert nd.value == d
+        return sim_n[:d].copy(), tab, nl, ms.value
 
     def mt19937_stream(self, seed, n_words):
         """the generator kernel of the cell call on its own: (DeviceArray of the first n_words outputs of

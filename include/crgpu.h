@@ -661,7 +661,7 @@ int crgpu_matrix_dev_download(crgpu_ctx *ctx, const crgpu_matrix_dev *m, uint32_
  *                                 crgpu_probe_metrics_dev and crgpu_assemble_probe_matrix_dev take (strictly ascending).
  *   crgpu_select_barcodes_cols_dev  crgpu_select_barcodes_dev with a DEVICE column list: the filtered matrix without a round
  *                                 trip of the columns.  CRGPU_EINVAL when a column is out of range.
- * EmptyDrops, the gradient / targeted / manual methods and the filters that follow the initial call are not covered. */
+ * EmptyDrops follows below; the gradient / targeted / manual methods and the other filters behind the initial call are not covered. */
 #define CRGPU_ORDMAG_SAMPLES 100 /* ORDMAG_NUM_BOOTSTRAP_SAMPLES */
 struct crgpu_ordmag_result {
     uint64_t n_nonzero;            /* N: barcodes with a non-zero count */
@@ -694,6 +694,114 @@ int crgpu_select_barcodes_cols_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *a, co
  * n_words is rounded down to a multiple of the kernel's chunk of 3632 words; *n_written_out tells how many came. */
 int crgpu_mt19937_stream_dev(crgpu_ctx *ctx, uint32_t seed, uint64_t n_words, uint32_t *d_out, uint64_t *n_written_out,
                              double *ms_out);
+
+/* ---- cell calling: the non-ambient ("EmptyDrops") barcodes behind the initial call ---------------------------------------------
+ * Replaces find_nonambient_barcodes (lib/python/cellranger/cell_calling.py:144-263) as call_additional_cells runs it
+ * (cell_calling_helpers.py:575-668) for ONE genome / GEM group; the caller loops and passes a feature mask.
+ *   crgpu_sgt_proportions      sgt_proportions / simple_good_turing (sgt.py:24-132) on the host, f64, no context: freq = n
+ *                              non-zero item frequencies; pstar (n, nullable) = the adjusted proportions, *p0 = the mass of the
+ *                              unobserved items, *slope = the log-log slope (linregress as mean((x-mx)(y-my)) / mean((x-mx)^2)).
+ *                              Returns CRGPU_OK, or one of the reference's two refusals as a POSITIVE status (pstar untouched):
+ *                              CRGPU_SGT_TOO_FEW (fewer than 10 distinct frequencies) or CRGPU_SGT_SLOPE (slope > -1, *slope set);
+ *                              CRGPU_EINVAL for an empty vector or a zero frequency.
+ *   crgpu_emptydrops_dev       m: the raw matrix; feature_mask / n_features as crgpu_matrix_dev_column_sums (NULL mask: all rows;
+ *                              n_features may then be 0 = the rows the matrix uses); d_bc_counts: device u32[n_barcodes], the
+ *                              column sums under the same mask (a candidate whose count is not its column's sum: CRGPU_EINVAL); d_cell_cols / n_cells: the initial call (ascending columns,
+ *                              crgpu_call_cells_ordmag_dev).
+ *       ambient set            places [low, high) of the columns in descending order of their total -- among equal totals the
+ *                              LARGER column first (np.argsort(kind="stable")[::-1]; the reference leaves the order of ties to
+ *                              numpy's introsort) -- without the zero totals (cell_calling.py:164-179).  low / high:
+ *                              get_empty_drops_range (:122-141): (N / 2, N) with N = 9 000 partitions on the LT chip, 160 000
+ *                              (80 000 x probe barcodes when multiplexed) on the chips with doubled GEM count, 90 000
+ *                              (45 000 x probe barcodes) otherwise.
+ *       profile                row sums over the ambient columns restricted to the rows that are non-zero anywhere
+ *                              (eval_features), smoothed by Simple Good-Turing (est_background_profile_sgt, :47-102).
+ *       candidates             columns outside the initial call with a total >= max(emptydrops_minimum_umis, 1 +
+ *                              max_background_umis), ascending (:191-220); their multinomial log-likelihood under the profile
+ *                              (eval_multinomial_loglikelihoods, stats.py:24-46).
+ *       simulation             replaces simulate_multinomial_loglikelihoods (stats.py:81-202), whose serial np.random stream is
+ *                              NOT reproduced: draw t of simulation s is word (t & 3) of Philox4x64-10(counter = (1 + (t >> 2),
+ *                              s, 0, 0), key = (seed, 0)) -- element t of np.random.Philox(counter=[0, s, 0, 0], key=[seed,
+ *                              0]).random_raw() --, u = (word >> 11) * 2^-53, feature = searchsorted(cdf, u, side="right") with
+ *                              cdf = the sequential running sum of profile_p over its last element; the counts at N are the
+ *                              first N draws; loglk = lgamma(N + 1) + sum_j (c_j log p_j - lgamma(c_j + 1)), accumulated in
+ *                              64-bit fixed point (within N * 2^-40 of the f64 sum), bit-identical between runs and between
+ *                              the LDS and the global-memory counters (CRGPU_ED_LDS_FEATURES=<n> in the environment when the
+ *                              context is created (tests): the largest n_eval_features that keeps its counters in LDS).
+ *       sim_n / sim_loglk      (host, nullable) a simulated table to use INSTEAD: n_sim_n ascending N and n_sim_n x num_sims
+ *                              values, what simulate_multinomial_loglikelihoods returns; every candidate total must have a
+ *                              row, else CRGPU_EINVAL.  p-values, BH and calls are then the reference's bit for bit.
+ *       p-values               (1 + #{simulated < observed}) / (1 + num_sims) (compute_ambient_pvalues, stats.py:205-231),
+ *                              adjust_pvalue_bh (analysis/diffexp.py:88-97), is_nonambient = pvalues_adj <= max_adj_pvalue
+ *                              (get_empty_drops_fdr, cell_calling.py:114-119: 0.001 on the chips with doubled GEM count, else 0.01).
+ *       flags                  CRGPU_ED_KEEP_PROFILE: out->d_eval_features / d_profile_p; CRGPU_ED_KEEP_SIM_TABLE: out->d_sim_n /
+ *                              d_sim_loglk (n_distinct_n x num_sims, at most 2^27 values; small shapes and tests -- the table
+ *                              is otherwise never materialised: every simulation is compared with the candidates of each N as
+ *                              it passes that N).
+ *     res->status != 0 is the reference's `return None`: no additional cell, out->d_called_cols = the initial cells, CRGPU_OK.
+ *     out: library-owned device arrays, released by crgpu_emptydrops_arrays_free (also after a status != 0).  d_called_cols is what
+ *     crgpu_select_barcodes_cols_dev and crgpu_cell_ranks_dev take.
+ *   crgpu_ambient_pvalues_dev  compute_ambient_pvalues + adjust_pvalue_bh + the calls for n candidates (device d_umis, d_obs_loglk)
+ *                              against a table (sim_n: host, ascending; d_sim_loglk: device, n_sim_n x num_sims); the outputs
+ *                              are caller-allocated device arrays of n entries, any may be NULL.
+ * The gradient / targeted filters and the filters after EmptyDrops are not covered. */
+#define CRGPU_SGT_TOO_FEW 1
+#define CRGPU_SGT_SLOPE 2
+#define CRGPU_ED_OK 0
+#define CRGPU_ED_NO_AMBIENT 1          /* no barcode with a non-zero total in [low, high) */
+#define CRGPU_ED_SGT_NOT_APPLICABLE 2  /* SimpleGoodTuringError */
+#define CRGPU_ED_NO_CELLS 3            /* no initial cell */
+#define CRGPU_ED_NO_CANDIDATES 4
+#define CRGPU_ED_KEEP_PROFILE 1u
+#define CRGPU_ED_KEEP_SIM_TABLE 2u
+struct crgpu_emptydrops_result {
+    int32_t status;                    /* CRGPU_ED_* */
+    int32_t sim_in_lds;                /* diagnostic: 1 = the simulation kept its counters in LDS */
+    uint64_t n_ambient_used;           /* len(use_bcs) */
+    uint64_t max_background_umis;
+    uint64_t emptydrops_minimum_umis;  /* the threshold used: max(given, 1 + max_background_umis) */
+    uint64_t n_eval_features;
+    uint64_t n_candidates;
+    uint64_t n_distinct_n;
+    uint64_t n_nonambient;
+    double sgt_slope, sgt_p0;
+    double sim_ms;                     /* diagnostic: the simulation kernel's milliseconds */
+};
+typedef struct crgpu_emptydrops_result crgpu_emptydrops_result; /* (by tag, as crgpu_ordmag_result) */
+struct crgpu_emptydrops_arrays {
+    uint64_t n_candidates, n_called, n_eval_features, n_distinct_n, num_sims;
+    uint64_t *d_eval_cols;             /* n_candidates: the candidates' columns, ascending (the rows of nonambient_summary) */
+    uint32_t *d_umis;
+    double *d_obs_loglk;
+    uint32_t *d_n_lower;               /* simulated values strictly below the observed one */
+    double *d_pvalues, *d_pvalues_adj;
+    uint8_t *d_is_nonambient;
+    uint64_t *d_called_cols;           /* n_called: the sorted union of the initial cells and the non-ambient candidates */
+    uint32_t *d_eval_features;         /* n_eval_features rows, CRGPU_ED_KEEP_PROFILE */
+    double *d_profile_p;
+    int64_t *d_sim_n;                  /* n_distinct_n, CRGPU_ED_KEEP_SIM_TABLE */
+    double *d_sim_loglk;               /* n_distinct_n x num_sims */
+};
+typedef struct crgpu_emptydrops_arrays crgpu_emptydrops_arrays;
+int crgpu_sgt_proportions(const uint64_t *freq, uint64_t n, double *pstar, double *p0, double *slope);
+int crgpu_emptydrops_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const uint8_t *feature_mask, uint32_t n_features,
+                         const uint32_t *d_bc_counts, const uint64_t *d_cell_cols, uint64_t n_cells, uint64_t low, uint64_t high,
+                         uint64_t emptydrops_minimum_umis, uint32_t num_sims, double max_adj_pvalue, uint64_t seed,
+                         const int64_t *sim_n, uint32_t n_sim_n, const double *sim_loglk, uint32_t flags,
+                         crgpu_emptydrops_result *res, crgpu_emptydrops_arrays *out);
+int crgpu_ambient_pvalues_dev(crgpu_ctx *ctx, const uint32_t *d_umis, const double *d_obs_loglk, uint64_t n, const int64_t *sim_n,
+                              uint32_t n_sim_n, const double *d_sim_loglk, uint32_t num_sims, double max_adj_pvalue,
+                              uint32_t *d_n_lower_out, double *d_pvalues_out, double *d_pvalues_adj_out,
+                              uint8_t *d_is_nonambient_out, uint64_t *n_nonambient_out);
+void crgpu_emptydrops_arrays_free(crgpu_ctx *ctx, crgpu_emptydrops_arrays *a);
+/* Test and measurement hook, NOT a stable interface (as crgpu_mt19937_stream_dev): the simulation kernel of crgpu_emptydrops_dev
+ * on a given profile (host, n_features probabilities in (0, 1]) for n candidate totals (host, all > 0).  sim_n_out (host, room
+ * for n, nullable) / *n_distinct_out = the distinct totals, ascending; sim_loglk_out (host, nullable, n_distinct x num_sims, at
+ * most 2^27 values) = the simulated table; with obs_loglk (host, n, nullable) n_lower_out (host, n) = the simulated values
+ * strictly below each observed one; *ms_out (nullable) = the kernel's time. */
+int crgpu_emptydrops_simulate_dev(crgpu_ctx *ctx, const double *profile_p, uint32_t n_features, const uint32_t *umis,
+                                  const double *obs_loglk, uint64_t n, uint32_t num_sims, uint64_t seed, int64_t *sim_n_out,
+                                  uint32_t *n_distinct_out, double *sim_loglk_out, uint32_t *n_lower_out, double *ms_out);
 
 /* one-call convenience (single GPU): build keys -> dedup -> matrix */
 int crgpu_count(crgpu_ctx *ctx, const crgpu_records *recs, uint32_t n_features, crgpu_matrix **out);

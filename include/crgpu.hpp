@@ -11,6 +11,8 @@
 //   crgpu::BarcodeIndex     cr_types/src/barcode_index.rs:14-53
 //   crgpu::CountMatrix      cr_h5/src/count_matrix.rs:382-448, cr_lib/src/stages/write_matrix_market.rs:80-122
 //   crgpu::filter_cellular_barcodes_ordmag / _fixed_cutoff  lib/python/cellranger/cell_calling_helpers.py:864-964 (Python there)
+//   crgpu::find_nonambient_barcodes / compute_ambient_pvalues / sgt_proportions
+//                           lib/python/cellranger/cell_calling.py:144-263, stats.py:205-231, sgt.py:97-132 (Python there)
 //
 // Errors are C++ exceptions carrying crgpu_last_error (the Rust returns anyhow::Result); nothing here
 // computes on the CPU: every result comes from libcrgpu, and construction fails without a gfx950 device.
@@ -500,6 +502,105 @@ inline CellCall filter_cellular_barcodes_ordmag(Context &ctx, const std::vector<
 inline CellCall filter_cellular_barcodes_fixed_cutoff(Context &ctx, const std::vector<uint32_t> &bc_counts, int64_t cutoff) {
     if (cutoff <= 0) throw Error(CRGPU_EINVAL, "filter_cellular_barcodes_fixed_cutoff: cutoff must be positive");
     return detail::call_cells(ctx, bc_counts, 0, 1 << 18, cutoff);
+}
+
+/// sgt_proportions (lib/python/cellranger/sgt.py:97-132), host code: nullopt for the reference's SimpleGoodTuringError
+/// (*status_out, nullable: CRGPU_SGT_TOO_FEW or CRGPU_SGT_SLOPE), else (pstar, p0).
+inline std::optional<std::pair<std::vector<double>, double>> sgt_proportions(const std::vector<uint64_t> &frequencies, int *status_out = nullptr) {
+    std::vector<double> pstar(frequencies.size());
+    double p0 = 0.0, slope = 0.0;
+    const int rc = crgpu_sgt_proportions(frequencies.data(), frequencies.size(), pstar.data(), &p0, &slope);
+    if (rc < 0) throw Error(rc, crgpu_last_error(nullptr));
+    if (status_out) *status_out = rc;
+    if (rc != CRGPU_OK) return std::nullopt;
+    return std::make_pair(std::move(pstar), p0);
+}
+
+/// find_nonambient_barcodes (lib/python/cellranger/cell_calling.py:144-263) of one genome / GEM group behind the initial call:
+/// NonAmbientBarcodeResult's arrays per candidate (ascending columns), `metrics` = the C struct itself (metrics.status != 0 is
+/// the reference's `return None`: no candidate rows, called == the initial cells) and `called` = the sorted union of the
+/// initial cells and the non-ambient candidates.
+static_assert(sizeof(crgpu_emptydrops_result) == 88, "crgpu_emptydrops_result changed: bump CRGPU_ABI_VERSION and every binding");
+static_assert(sizeof(crgpu_emptydrops_arrays) == 136, "crgpu_emptydrops_arrays changed: bump CRGPU_ABI_VERSION and every binding");
+struct NonAmbientBarcodeResult {
+    std::vector<uint64_t> eval_bcs;
+    std::vector<uint32_t> umis;
+    std::vector<double> log_likelihood, pvalues, pvalues_adj;
+    std::vector<uint8_t> is_nonambient;
+    std::vector<uint64_t> called;
+    crgpu_emptydrops_result metrics;
+};
+namespace detail {
+template <typename T>
+inline int fetch(Context &ctx, std::vector<T> &out, const T *d, uint64_t n) {
+    out.resize(n);
+    return n ? crgpu_memcpy_d2h(ctx.get(), out.data(), d, n * sizeof(T)) : CRGPU_OK;
+}
+}  // namespace detail
+/// raw: the device matrix; d_bc_counts: its column sums under feature_mask (crgpu_matrix_dev_column_sums); orig_cells: the
+/// initially-called columns, ascending; low / high: get_empty_drops_range (cell_calling.py:122-141); feature_mask empty = all rows.
+inline NonAmbientBarcodeResult find_nonambient_barcodes(Context &ctx, const crgpu_matrix_dev *raw, const uint32_t *d_bc_counts,
+                                                        const std::vector<uint64_t> &orig_cells, uint64_t low, uint64_t high,
+                                                        uint64_t emptydrops_minimum_umis = 500, uint32_t num_sims = 10000,
+                                                        double max_adj_pvalue = 0.01, uint64_t seed = 0,
+                                                        const std::vector<uint8_t> &feature_mask = {}) {
+    NonAmbientBarcodeResult out{};
+    crgpu_emptydrops_arrays a{};
+    void *d_cells = nullptr;
+    if (!orig_cells.empty()) {
+        ctx.check(crgpu_malloc(ctx.get(), &d_cells, orig_cells.size() * sizeof(uint64_t)));
+        const int rc = crgpu_memcpy_h2d(ctx.get(), d_cells, orig_cells.data(), orig_cells.size() * sizeof(uint64_t));
+        if (rc != CRGPU_OK) {
+            crgpu_free(ctx.get(), d_cells);
+            ctx.check(rc);
+        }
+    }
+    int rc = crgpu_emptydrops_dev(ctx.get(), raw, feature_mask.empty() ? nullptr : feature_mask.data(), (uint32_t)feature_mask.size(),
+                                  d_bc_counts, (const uint64_t *)d_cells, orig_cells.size(), low, high, emptydrops_minimum_umis, num_sims,
+                                  max_adj_pvalue, seed, nullptr, 0, nullptr, 0, &out.metrics, &a);
+    if (d_cells) crgpu_free(ctx.get(), d_cells);
+    ctx.check(rc);
+    const uint64_t n = a.n_candidates;
+    rc = detail::fetch(ctx, out.eval_bcs, a.d_eval_cols, n);
+    if (rc == CRGPU_OK) rc = detail::fetch(ctx, out.umis, a.d_umis, n);
+    if (rc == CRGPU_OK) rc = detail::fetch(ctx, out.log_likelihood, a.d_obs_loglk, n);
+    if (rc == CRGPU_OK) rc = detail::fetch(ctx, out.pvalues, a.d_pvalues, n);
+    if (rc == CRGPU_OK) rc = detail::fetch(ctx, out.pvalues_adj, a.d_pvalues_adj, n);
+    if (rc == CRGPU_OK) rc = detail::fetch(ctx, out.is_nonambient, a.d_is_nonambient, n);
+    if (rc == CRGPU_OK) rc = detail::fetch(ctx, out.called, a.d_called_cols, a.n_called);
+    crgpu_emptydrops_arrays_free(ctx.get(), &a);
+    ctx.check(rc);
+    return out;
+}
+
+/// compute_ambient_pvalues (lib/python/cellranger/stats.py:205-231) + adjust_pvalue_bh (analysis/diffexp.py:88-97) against a
+/// simulated table (sim_n ascending, sim_loglk = sim_n.size() rows of num_sims values): (pvalues, pvalues_adj).
+inline std::pair<std::vector<double>, std::vector<double>> compute_ambient_pvalues(Context &ctx, const std::vector<uint32_t> &umis_per_bc,
+                                                                                  const std::vector<double> &obs_loglk,
+                                                                                  const std::vector<int64_t> &sim_n,
+                                                                                  const std::vector<double> &sim_loglk) {
+    const size_t n = umis_per_bc.size();
+    if (obs_loglk.size() != n || sim_n.empty() || sim_loglk.size() % sim_n.size()) throw Error(CRGPU_EINVAL, "compute_ambient_pvalues: shapes");
+    std::vector<double> p(n), q(n);
+    if (!n) return {p, q};
+    const size_t b_umis = n * sizeof(uint32_t), b_obs = n * sizeof(double), b_tab = sim_loglk.size() * sizeof(double);
+    void *d[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    const size_t bytes[5] = {b_umis, b_obs, b_tab, b_obs, b_obs};
+    int rc = CRGPU_OK;
+    for (int i = 0; i < 5 && rc == CRGPU_OK; i++) rc = crgpu_malloc(ctx.get(), &d[i], bytes[i]);
+    if (rc == CRGPU_OK) rc = crgpu_memcpy_h2d(ctx.get(), d[0], umis_per_bc.data(), b_umis);
+    if (rc == CRGPU_OK) rc = crgpu_memcpy_h2d(ctx.get(), d[1], obs_loglk.data(), b_obs);
+    if (rc == CRGPU_OK) rc = crgpu_memcpy_h2d(ctx.get(), d[2], sim_loglk.data(), b_tab);
+    if (rc == CRGPU_OK)
+        rc = crgpu_ambient_pvalues_dev(ctx.get(), (const uint32_t *)d[0], (const double *)d[1], n, sim_n.data(), (uint32_t)sim_n.size(),
+                                       (const double *)d[2], (uint32_t)(sim_loglk.size() / sim_n.size()), 1.0, nullptr, (double *)d[3],
+                                       (double *)d[4], nullptr, nullptr);
+    if (rc == CRGPU_OK) rc = crgpu_memcpy_d2h(ctx.get(), p.data(), d[3], b_obs);
+    if (rc == CRGPU_OK) rc = crgpu_memcpy_d2h(ctx.get(), q.data(), d[4], b_obs);
+    for (void *x : d)
+        if (x) crgpu_free(ctx.get(), x);
+    ctx.check(rc);
+    return {p, q};
 }
 
 }  // namespace crgpu
