@@ -187,6 +187,27 @@ class EmptydropsArrays(C.Structure):
                                   "d_called_cols", "d_eval_features", "d_profile_p", "d_sim_n", "d_sim_loglk")]
 
 
+class SubsampleArgs(C.Structure):
+    """crgpu_subsample_args"""
+    _fields_ = [(n, C.c_uint32) for n in ("n_tasks", "n_genomes", "n_libs", "n_features")] + [("n_cells", C.c_uint64), ("seed", C.c_uint64)] + [
+        (n, C.c_void_p) for n in ("rates", "task_type", "d_cell_ranks", "cell_genome_mask", "feature_genome", "feature_mask", "umis_per_bc",
+                                  "read_pairs_per_bc", "features_det_per_bc", "read_pairs", "umis", "total_features_det", "any_reads")]
+
+
+class SubsampleResult(C.Structure):
+    """crgpu_subsample_result"""
+    _fields_ = [(n, C.c_uint64) for n in ("n_molecules", "n_groups", "n_lane", "n_wave", "n_workgroup")] + [
+        ("n_active_tasks", C.c_uint32), ("n_batches", C.c_uint32), ("draw_ms", C.c_double)]
+
+
+SS_PER_CELL, SS_CELLS_ONLY, SS_BULK = 0, 1, 2
+SS_PLAN_RAW, SS_PLAN_MAPPED, SS_PLAN_RAW_CELLS, SS_PLAN_BULK = 0, 1, 2, 3
+SS_NUM_ADDITIONAL_DEPTHS = 10
+SS_FIXED_DEPTHS = (3000, 5000, 10000, 20000, 30000, 50000)
+SS_TARGETED_FIXED_DEPTHS = (100, 250, 500, 1000, 2500, 3000, 5000, 10000, 15000, 20000, 30000, 40000, 50000)
+SS_BULK_FIXED_DEPTHS = (10000, 50000, 100000, 250000, 500000, 1000000, 2500000, 5000000, 7500000, 10000000, 50000000, 100000000, 1000000000)
+SS_SUMMARY_COLS = ("mean_read_pairs", "median_read_pairs", "mean_umis", "median_umis", "mean_features", "median_features", "duplication_frac")
+
 ED_STATUS = {0: "ok", 1: "no usable ambient barcode", 2: "SGT not applicable", 3: "no initial cell", 4: "no candidate"}
 ED_KEEP_PROFILE, ED_KEEP_SIM_TABLE = 1, 2
 SGT_TOO_FEW, SGT_SLOPE = 1, 2
@@ -293,6 +314,9 @@ SYMBOLS = {
     "crgpu_ambient_pvalues_dev": (_i, [_vp, _vp, _vp, _u64, _vp, _u32, _vp, _u32, _dbl, _vp, _vp, _vp, _vp, C.POINTER(_u64)]),
     "crgpu_emptydrops_arrays_free": (None, [_vp, C.POINTER(EmptydropsArrays)]),
     "crgpu_emptydrops_simulate_dev": (_i, [_vp, _vp, _u32, _vp, _vp, _u64, _u32, _u64, _vp, C.POINTER(_u32), _vp, _vp, C.POINTER(_dbl)]),
+    "crgpu_subsample_dev": (_i, [_vp, _vp, C.POINTER(SubsampleArgs), C.POINTER(SubsampleResult)]),
+    "crgpu_subsample_plan": (_i, [_i, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _u32, C.POINTER(_u32)]),
+    "crgpu_subsample_summary": (_i, [_u32, _u32, _u64, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "crgpu_matrix_dev_download": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _vp, _vp, _vp]),
     "crgpu_count": (_i, [_vp, C.POINTER(Records), _u32, C.POINTER(C.POINTER(MatrixView))]),
     "crgpu_set_feature_pattern": (_i, [_vp, _i, C.c_char_p, _u32, _u32, _vp, _vp]),

@@ -216,6 +216,9 @@ struct crgpu_ctx {
     uint32_t probe_seg_cap = 0xFFFFFFFFu;  // CRGPU_PROBE_SEG_CAP (tests, read at create): largest segment the LDS classes take
     uint32_t ordmag_batch = 0;             // CRGPU_ORDMAG_BATCH (tests, read at create): bootstrap samples per batch of the cell call, 0 = by memory
     uint32_t ed_lds_features = 0xFFFFFFFFu;  // CRGPU_ED_LDS_FEATURES (tests, read at create): largest n_eval_features the EmptyDrops simulation counts in LDS
+    // read subsampling (subsample.h; tests, read at create): molecules of fewer reads than ss_wave_min are drawn one per lane, up to
+    // ss_wg_min one per wave, larger ones one per workgroup; ss_task_batch = tasks per batch, 0 = by memory
+    uint32_t ss_wave_min = 64, ss_wg_min = 4096, ss_task_batch = 0;  // CRGPU_SS_WAVE_MIN, CRGPU_SS_WG_MIN, CRGPU_SS_TASK_BATCH
 
     double max_expected_errors = 1.7976931348623157e308;  // corrector.rs:104 (f64::MAX)
     double confidence_threshold = 0.975;                   // corrector.rs:83

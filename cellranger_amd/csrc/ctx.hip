@@ -103,6 +103,19 @@ const std::vector<AbiStruct> &abi_table() {
               ABI_F(crgpu_emptydrops_arrays, d_called_cols), ABI_F(crgpu_emptydrops_arrays, d_eval_features),
               ABI_F(crgpu_emptydrops_arrays, d_profile_p), ABI_F(crgpu_emptydrops_arrays, d_sim_n),
               ABI_F(crgpu_emptydrops_arrays, d_sim_loglk)),
+        ABI_S(crgpu_subsample_args, ABI_F(crgpu_subsample_args, n_tasks), ABI_F(crgpu_subsample_args, n_genomes),
+              ABI_F(crgpu_subsample_args, n_libs), ABI_F(crgpu_subsample_args, n_features),
+              ABI_F(crgpu_subsample_args, n_cells), ABI_F(crgpu_subsample_args, seed), ABI_F(crgpu_subsample_args, rates),
+              ABI_F(crgpu_subsample_args, task_type), ABI_F(crgpu_subsample_args, d_cell_ranks),
+              ABI_F(crgpu_subsample_args, cell_genome_mask), ABI_F(crgpu_subsample_args, feature_genome),
+              ABI_F(crgpu_subsample_args, feature_mask), ABI_F(crgpu_subsample_args, umis_per_bc),
+              ABI_F(crgpu_subsample_args, read_pairs_per_bc), ABI_F(crgpu_subsample_args, features_det_per_bc),
+              ABI_F(crgpu_subsample_args, read_pairs), ABI_F(crgpu_subsample_args, umis),
+              ABI_F(crgpu_subsample_args, total_features_det), ABI_F(crgpu_subsample_args, any_reads)),
+        ABI_S(crgpu_subsample_result, ABI_F(crgpu_subsample_result, n_molecules), ABI_F(crgpu_subsample_result, n_groups),
+              ABI_F(crgpu_subsample_result, n_lane), ABI_F(crgpu_subsample_result, n_wave),
+              ABI_F(crgpu_subsample_result, n_workgroup), ABI_F(crgpu_subsample_result, n_active_tasks),
+              ABI_F(crgpu_subsample_result, n_batches), ABI_F(crgpu_subsample_result, draw_ms)),
     };
     return t;
 }
@@ -181,6 +194,9 @@ extern "C" int crgpu_create(crgpu_ctx **out, int device_id, int n_ranks, int ran
     if (const char *cap = getenv("CRGPU_PROBE_SEG_CAP")) ctx->probe_seg_cap = (uint32_t)strtoul(cap, nullptr, 10);  // tests: force the global route
     if (const char *b = getenv("CRGPU_ORDMAG_BATCH")) ctx->ordmag_batch = (uint32_t)strtoul(b, nullptr, 10);  // tests: small batches of the cell call
     if (const char *f = getenv("CRGPU_ED_LDS_FEATURES")) ctx->ed_lds_features = (uint32_t)strtoul(f, nullptr, 10);  // tests: 0 = counters in global memory
+    if (const char *v = getenv("CRGPU_SS_WAVE_MIN")) ctx->ss_wave_min = (uint32_t)strtoul(v, nullptr, 10);  // tests: reach the wave path of the subsampling draw
+    if (const char *v = getenv("CRGPU_SS_WG_MIN")) ctx->ss_wg_min = (uint32_t)strtoul(v, nullptr, 10);      // ... and its workgroup path
+    if (const char *v = getenv("CRGPU_SS_TASK_BATCH")) ctx->ss_task_batch = (uint32_t)strtoul(v, nullptr, 10);  // tests: small task batches
     // probability(q) = 10^(-(q-33)/10) computed on the HOST with libm pow, exactly as the
     // reference does per call (corrector.rs:167-171), for every 7-bit quality character.
     double ptab[128];

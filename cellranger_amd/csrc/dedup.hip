@@ -44,6 +44,9 @@ struct crgpu_counts {
     uint32_t pt_n_probes = 0;
     uint64_t n_pt = 0;
     uint32_t *d_pt_bc = nullptr, *d_pt_probe = nullptr, *d_pt_count = nullptr;
+    // device position -> position in the table crgpu_counts_molecules lists, made on the first subsampling of counts with
+    // several libraries or UMI lengths (subsample.h), else NULL
+    uint32_t *d_ss_pos = nullptr;
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -2855,6 +2858,7 @@ extern "C" void crgpu_counts_free(crgpu_ctx *ctx, crgpu_counts *c) {
     cr_pool_free(ctx, c->d_pt_bc);
     cr_pool_free(ctx, c->d_pt_probe);
     cr_pool_free(ctx, c->d_pt_count);
+    cr_pool_free(ctx, c->d_ss_pos);
     delete c;
 }
 
@@ -2967,3 +2971,4 @@ extern "C" int crgpu_trim_molecule_barcodes_dev(crgpu_ctx *ctx, uint64_t *d_barc
 #include "probe_counts.h"
 #include "cell_calling.h"
 #include "emptydrops.h"
+#include "subsample.h"

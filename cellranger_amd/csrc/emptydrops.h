@@ -23,6 +23,8 @@
 #include <algorithm>
 #include <cmath>
 
+#include "philox.h"
+
 #define ED_SIM_THREADS 1024
 #define ED_LDS_BYTES (160u * 1024u - 64u)  // dynamic LDS a workgroup of k_ed_simulate may take (its static part is 24 bytes)
 #define ED_FIXED_BITS 40                   // fraction bits of the fixed-point log terms (fewer when the sum would not fit 2^62)
@@ -217,28 +219,9 @@ __global__ __launch_bounds__(256) void k_ed_observed(const uint64_t *__restrict_
 }
 
 // ---- the simulation -------------------------------------------------------------------------------------------------------------
-// Draw t of simulation s is word t & 3 of Philox4x64-10(counter = (1 + (t >> 2), s, 0, 0), key = (seed, 0)): element t of
+// Draw t of simulation s is word t & 3 (philox.h) of Philox4x64-10(counter = (1 + (t >> 2), s, 0, 0), key = (seed, 0)): element t of
 // np.random.Philox(counter=[0, s, 0, 0], key=[seed, 0]).random_raw().  u = (word >> 11) * 2^-53, feature = searchsorted(cdf, u,
 // side="right").  The counts after N draws are the first N draws (nested, as stats.py:143-197 extends one sample).
-__device__ __forceinline__ void ed_philox4x64_10(unsigned long long c0, unsigned long long c1, unsigned long long k0, unsigned long long w[4]) {
-    unsigned long long c2 = 0, c3 = 0, k1 = 0;
-#pragma unroll
-    for (int r = 0; r < 10; r++) {
-        const unsigned long long hi0 = __umul64hi(0xD2E7470EE14C6C93ull, c0), lo0 = 0xD2E7470EE14C6C93ull * c0;
-        const unsigned long long hi1 = __umul64hi(0xCA5A826395121157ull, c2), lo1 = 0xCA5A826395121157ull * c2;
-        c0 = hi1 ^ c1 ^ k0;
-        c1 = lo1;
-        c2 = hi0 ^ c3 ^ k1;
-        c3 = lo0;
-        k0 += 0x9E3779B97F4A7C15ull;
-        k1 += 0xBB67AE8584CAA73Bull;
-    }
-    w[0] = c0;
-    w[1] = c1;
-    w[2] = c2;
-    w[3] = c3;
-}
-
 struct EdSimArgs {
     const double *cdf;        // n_feat, last == 1.0
     const uint32_t *guide;    // (1 << guide_bits) + 1: guide[b] = #{cdf <= b * 2^-guide_bits}
@@ -282,7 +265,7 @@ __global__ __launch_bounds__(ED_SIM_THREADS) void k_ed_simulate(EdSimArgs a) {
             long long acc = 0;
             for (uint32_t b = (lo >> 2) + tid; b <= ((hi - 1u) >> 2); b += ED_SIM_THREADS) {
                 unsigned long long w[4];
-                ed_philox4x64_10((unsigned long long)b + 1ull, s, a.seed, w);
+                cr_philox4x64_10((unsigned long long)b + 1ull, s, a.seed, w);
 #pragma unroll
                 for (uint32_t k = 0; k < 4; k++) {
                     const unsigned long long t = 4ull * b + k;

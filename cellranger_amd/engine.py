@@ -325,6 +325,43 @@ def ordmag_candidates(max_expected_cells=1 << 18):
     return out[: n.value].copy()
 
 
+def subsample_plan(subsample_type, lib_indices, num_cells_per_lib, raw_reads_per_lib, usable_reads_per_lib, fixed_depths=None,
+                   num_additional_depths=_lib.SS_NUM_ADDITIONAL_DEPTHS):
+    """make_subsamplings (subsample.py:140-309) through the C ABI, host only: (depths int64[n], rates float64[n][n_libs]) for
+    the libraries `lib_indices` of one library type.  subsample_type: _lib.SS_PLAN_*; for SS_PLAN_BULK usable_reads_per_lib are
+    the transcriptomic reads.  fixed_depths None: the reference's list for the type (bulk / all others)."""
+    if fixed_depths is None:
+        fixed_depths = _lib.SS_BULK_FIXED_DEPTHS if subsample_type == _lib.SS_PLAN_BULK else _lib.SS_FIXED_DEPTHS
+    idx = np.ascontiguousarray(lib_indices, dtype=np.uint32)
+    cells, raw, usable = (np.ascontiguousarray(x, dtype=np.float64) for x in (num_cells_per_lib, raw_reads_per_lib, usable_reads_per_lib))
+    assert len(cells) == len(raw) == len(usable)
+    fixed = np.ascontiguousarray(fixed_depths, dtype=np.int64)
+    cap = len(fixed) + int(num_additional_depths) + 1
+    depths, rates, n = np.zeros(cap, np.int64), np.zeros((cap, len(cells)), np.float64), C.c_uint32()
+    rc = _lib.load().crgpu_subsample_plan(int(subsample_type), ptr(idx), len(idx), len(cells), ptr(cells), ptr(raw), ptr(usable), ptr(fixed),
+                                          len(fixed), int(num_additional_depths), ptr(depths), ptr(rates), cap, C.byref(n))
+    if rc != 0:
+        raise _lib.CrgpuError(rc, "crgpu_subsample_plan")
+    return depths[: n.value].copy(), rates[: n.value].copy()
+
+
+def subsample_summary(data, task_types, cell_genome_mask=None):
+    """the per-task, per-genome numbers of calculate_subsampling_metrics (subsample.py:719-845) from the dict Counts.subsample
+    returns: (table float64[task][genome][len(_lib.SS_SUMMARY_COLS)], whole-dataset duplication fraction float64[task])"""
+    upb, rpb, fpb = (np.ascontiguousarray(data[k], dtype=np.int64) for k in ("umis_per_bc", "read_pairs_per_bc", "features_det_per_bc"))
+    rp, um, tfd = (np.ascontiguousarray(data[k], dtype=np.int64) for k in ("read_pairs", "umis", "total_features_det"))
+    T, G, NC = upb.shape
+    types = np.ascontiguousarray(task_types, dtype=np.uint8)
+    assert len(types) == T
+    cgm = None if cell_genome_mask is None else np.ascontiguousarray(cell_genome_mask, dtype=np.uint32)
+    out, allf = np.zeros((T, G, len(_lib.SS_SUMMARY_COLS)), np.float64), np.zeros(T, np.float64)
+    rc = _lib.load().crgpu_subsample_summary(T, G, NC, tfd.shape[2], ptr(types), ptr(cgm), ptr(upb), ptr(rpb), ptr(fpb), ptr(rp), ptr(um),
+                                             ptr(tfd), ptr(out), ptr(allf))
+    if rc != 0:
+        raise _lib.CrgpuError(rc, "crgpu_subsample_summary")
+    return out, allf
+
+
 class Counts:
     """crgpu_counts: sorted (barcode, feature, count) triplets + the molecule table."""
 
@@ -414,6 +451,41 @@ class Counts:
         self.ctx._check(self.ctx.L.crgpu_probe_metrics_dev(self.ctx.h, self.h, n_probes, _p(d_cells), d_cells.size, ptr(all_),
                                                            ptr(filt)))
         return all_, filt
+
+    def subsample(self, rates, task_types, cell_ranks, n_genomes=1, feature_genome=None, cell_genome_mask=None, feature_mask=None,
+                  seed=1, n_features=None):
+        """run_subsampling (subsample.py:430-654) on the molecule table, the binomial replaced by a Philox stream (crgpu.h).
+        rates: [n_tasks][n_libs]; task_types: _lib.SS_PER_CELL / SS_CELLS_ONLY / SS_BULK per task; cell_ranks: strictly ascending
+        canonical ranks, a numpy array or a DeviceArray (CellCall.ranks_dev()); n_features: of the key layout (default: the
+        length of feature_genome / feature_mask).  Returns the SubsampleDataDict arrays plus `any_reads` [library][genome] and
+        `info` (crgpu_subsample_result as a dict)."""
+        rates = np.ascontiguousarray(rates, dtype=np.float64)
+        rates = rates.reshape(len(rates), -1) if rates.ndim != 2 else rates
+        T, NL = rates.shape
+        types = np.ascontiguousarray(task_types, dtype=np.uint8)
+        assert len(types) == T
+        d_cells = cell_ranks if isinstance(cell_ranks, DeviceArray) else self.ctx.upload(np.ascontiguousarray(cell_ranks, dtype=np.uint32))
+        NC, G = d_cells.size, int(n_genomes)
+        fg = None if feature_genome is None else np.ascontiguousarray(feature_genome, dtype=np.uint8)
+        fm = None if feature_mask is None else np.ascontiguousarray(feature_mask, dtype=np.uint8)
+        cgm = None if cell_genome_mask is None else np.ascontiguousarray(cell_genome_mask, dtype=np.uint32)
+        if n_features is None:
+            if fg is None and fm is None:
+                raise ValueError("n_features (of the key layout) is needed without feature_genome / feature_mask")
+            n_features = len(fg) if fg is not None else len(fm)
+        F = int(n_features)
+        assert (fg is None or len(fg) == F) and (fm is None or len(fm) == F) and (cgm is None or len(cgm) == NC)
+        out = dict(umis_per_bc=np.zeros((T, G, NC), np.int64), features_det_per_bc=np.zeros((T, G, NC), np.int64),
+                   read_pairs_per_bc=np.zeros((T, G, NC), np.int64), read_pairs=np.zeros((T, G), np.int64), umis=np.zeros((T, G), np.int64),
+                   total_features_det=np.zeros((T, G, F), np.int64), any_reads=np.zeros((NL, G), np.uint8))
+        a = _lib.SubsampleArgs(n_tasks=T, n_genomes=G, n_libs=NL, n_features=F, n_cells=NC, seed=int(seed), rates=ptr(rates), task_type=ptr(types),
+                               d_cell_ranks=_p(d_cells), cell_genome_mask=ptr(cgm), feature_genome=ptr(fg), feature_mask=ptr(fm),
+                               **{k: ptr(v) for k, v in out.items()})
+        res = _lib.SubsampleResult()
+        self.ctx._check(self.ctx.L.crgpu_subsample_dev(self.ctx.h, self.h, C.byref(a), C.byref(res)))
+        out["any_reads"] = out["any_reads"].astype(bool)
+        out["info"] = {name: getattr(res, name) for name, _ in _lib.SubsampleResult._fields_}
+        return out
 
     def barcode_summary(self, rank_lo=0, rank_hi=0xFFFFFFFF):
         """BarcodeSummary rows (cr_lib/src/aligner.rs:33-68) of the barcode ranks in [rank_lo, rank_hi), ordered by

@@ -803,6 +803,120 @@ int crgpu_emptydrops_simulate_dev(crgpu_ctx *ctx, const double *profile_p, uint3
                                   const double *obs_loglk, uint64_t n, uint32_t num_sims, uint64_t seed, int64_t *sim_n_out,
                                   uint32_t *n_distinct_out, double *sim_loglk_out, uint32_t *n_lower_out, double *ms_out);
 
+/* ---- read subsampling: the tallies behind the saturation curves ------------------------------------------------------------------
+ * Replaces run_subsampling / _run_subsample_task of SUBSAMPLE_READS (lib/python/cellranger/subsample.py:430-654) on the molecule
+ * table of `c` for ONE chunk holding the whole table (the reference adds chunk results, so a barcode that straddles a chunk
+ * boundary gets its features counted twice; that is not restated), with compute_target_depths / make_subsamplings /
+ * _subsampling_for_depth (:140-309) and the per-task numbers of calculate_subsampling_metrics (:719-845) as host functions.
+ *   the draw        np.random.seed(1); np.random.binomial(count, rate) -- the serial MT19937 stream -- is NOT reproduced.  Read j
+ *                   (0-based, j < count) of molecule m (its position in the table crgpu_counts_molecules lists, before any
+ *                   feature mask) owns word (j & 3) of Philox4x64-10(counter = (1 + (j >> 2), m, 0, 0), key = (seed, 0)) --
+ *                   element j of np.random.Philox(counter=[0, m, 0, 0], key=[seed, 0]).random_raw() --; u = word >> 11; the read
+ *                   is kept in task t iff u < floor(rates[t][library] * 2^53).  kept ~ Binomial(count, floor(rate * 2^53) / 2^53)
+ *                   exactly, rate 1 keeps every read, rate 0 none, and the whole rule is integer arithmetic.  The words do not
+ *                   depend on the task: the subsamples are nested in the rate, and a task's result depends neither on the
+ *                   other tasks of the call nor on how the call batches them (CRGPU_SS_TASK_BATCH=<n> in the environment when the
+ *                   context is created (tests) fixes the tasks per batch, at most 64).
+ *   crgpu_subsample_dev   args->rates: host f64 [n_tasks][n_libs]; a rate outside [0, 1]: CRGPU_EINVAL.  A task whose rates are
+ *                   all 0, or in which a library that has a (feature-masked) molecule has a NaN rate, yields zeros (:598-605).
+ *                   task_type[n_tasks] (host): CRGPU_SS_PER_CELL (raw_rpc, conf_mapped_barcoded_filtered_bc_rpc),
+ *                   CRGPU_SS_CELLS_ONLY (raw_barcoded_filtered_bc_rpc), CRGPU_SS_BULK (raw_reads).
+ *                   d_cell_ranks / n_cells: device, strictly ascending canonical ranks (crgpu_cell_ranks_dev), else CRGPU_EINVAL.
+ *                   cell_genome_mask (host u32[n_cells], bit g = a cell of genome g; NULL: of every genome), feature_genome
+ *                   (host u8[n_features]; NULL: genome 0), n_genomes 1..8, feature_mask (host u8[n_features], the targeted
+ *                   panel; NULL: all; a masked-out molecule takes part in nothing).  n_libs / n_features must be those of the key
+ *                   layout the counts were made with.  Outputs (host, caller-allocated, any may be NULL):
+ *                     umis_per_bc, read_pairs_per_bc, features_det_per_bc   i64 [task][genome][cell]
+ *                     read_pairs, umis                                      i64 [task][genome]
+ *                     total_features_det                                    i64 [task][genome][feature]
+ *                     any_reads   u8 [library][genome]: a molecule with count > 0 exists (lib_type_genome_any_reads before the
+ *                                 host folds libraries into library types)
+ *                   per barcode and genome g: umis = molecules of g with kept > 0, read_pairs = the sum of kept, features_det =
+ *                   distinct features among them (one feature in two libraries of a barcode is ONE feature).
+ *                     PER_CELL    cell entries for the barcodes that are cells of g; total_features_det = per-feature survivors of
+ *                                 those cells; read_pairs / umis add EVERY barcode;
+ *                     CELLS_ONLY  a barcode that is not a cell of g contributes nothing anywhere;
+ *                     BULK        the table is one group: every cell entry of umis_per_bc / read_pairs_per_bc = the table's total,
+ *                                 features_det_per_bc = 0, total_features_det = per-feature survivors over all barcodes.
+ *                   Molecules of fewer than CRGPU_SS_WAVE_MIN reads (default 64, at most 256) are drawn one per lane, up to
+ *                   CRGPU_SS_WG_MIN (default 4096, at most 16128) one per wave, larger ones one per workgroup; both are read from
+ *                   the environment when the context is created (tests) and the results do not depend on them.
+ *                   res (nullable): what ran and the milliseconds of the draw kernels.
+ *   crgpu_subsample_plan  host, f64, no context.  subsample_type CRGPU_SS_PLAN_*; lib_indices: the libraries of the library type;
+ *                   num_cells / raw_reads / usable_reads: per library (n_libs each; for BULK usable_reads = the transcriptomic
+ *                   reads); fixed_depths: CRGPU_SS_FIXED_DEPTHS / _TARGETED_ / _BULK_ or the caller's own.  depths_out (i64) = the
+ *                   sorted distinct target depths, rates_out [depth][n_libs] with the renormalisation at the largest computed
+ *                   depth and rates > 1 set to 0.  np.linspace(0, max, num + 1, dtype=int) is trunc(i * (max / num)) with the
+ *                   last element = max.  Outputs may be NULL (size query); CRGPU_ERANGE (with *n_out set) when cap is too small;
+ *                   CRGPU_EINVAL when the largest feasible depth is not finite (the reference's integer cast is undefined there).
+ *   crgpu_subsample_summary  host: out[task][genome][CRGPU_SS_SUMMARY_COLS] = mean and median read pairs, mean and median UMIs,
+ *                   mean and median detected features over the cells of the genome (numpy's median: the mean of the two middle
+ *                   values; NaN without cells; BULK: both feature columns = the non-zero entries of total_features_det), and
+ *                   subsampled_duplication_frac = (read_pairs - umis) / read_pairs (0 without reads); dup_frac_all_out[task]
+ *                   (nullable) = the whole-dataset duplication fraction.  Metric names and JSON stay with the host. */
+#define CRGPU_SS_PER_CELL 0
+#define CRGPU_SS_CELLS_ONLY 1
+#define CRGPU_SS_BULK 2
+#define CRGPU_SS_PLAN_RAW 0        /* raw_rpc */
+#define CRGPU_SS_PLAN_MAPPED 1     /* conf_mapped_barcoded_filtered_bc_rpc */
+#define CRGPU_SS_PLAN_RAW_CELLS 2  /* raw_barcoded_filtered_bc_rpc */
+#define CRGPU_SS_PLAN_BULK 3       /* raw_reads */
+#define CRGPU_SS_NUM_ADDITIONAL_DEPTHS 10
+#define CRGPU_SS_FIXED_DEPTHS {3000, 5000, 10000, 20000, 30000, 50000}
+#define CRGPU_SS_TARGETED_FIXED_DEPTHS {100, 250, 500, 1000, 2500, 3000, 5000, 10000, 15000, 20000, 30000, 40000, 50000}
+#define CRGPU_SS_BULK_FIXED_DEPTHS \
+    {10000, 50000, 100000, 250000, 500000, 1000000, 2500000, 5000000, 7500000, 10000000, 50000000, 100000000, 1000000000}
+#define CRGPU_SS_SUMMARY_COLS 7
+#define CRGPU_SS_MEAN_READ_PAIRS 0
+#define CRGPU_SS_MEDIAN_READ_PAIRS 1
+#define CRGPU_SS_MEAN_UMIS 2
+#define CRGPU_SS_MEDIAN_UMIS 3
+#define CRGPU_SS_MEAN_FEATURES 4
+#define CRGPU_SS_MEDIAN_FEATURES 5
+#define CRGPU_SS_DUP_FRAC 6
+struct crgpu_subsample_args {
+    uint32_t n_tasks;
+    uint32_t n_genomes;
+    uint32_t n_libs;
+    uint32_t n_features;
+    uint64_t n_cells;
+    uint64_t seed;
+    const double *rates;
+    const uint8_t *task_type;
+    const uint32_t *d_cell_ranks;
+    const uint32_t *cell_genome_mask;
+    const uint8_t *feature_genome;
+    const uint8_t *feature_mask;
+    int64_t *umis_per_bc;
+    int64_t *read_pairs_per_bc;
+    int64_t *features_det_per_bc;
+    int64_t *read_pairs;
+    int64_t *umis;
+    int64_t *total_features_det;
+    uint8_t *any_reads;
+};
+typedef struct crgpu_subsample_args crgpu_subsample_args; /* (by tag, as crgpu_ordmag_result) */
+struct crgpu_subsample_result {
+    uint64_t n_molecules;      /* molecules that took part (inside the feature mask) */
+    uint64_t n_groups;         /* barcode groups of the table */
+    uint64_t n_lane;           /* molecules drawn one per lane ... */
+    uint64_t n_wave;           /* ... one per wave ... */
+    uint64_t n_workgroup;      /* ... one per workgroup */
+    uint32_t n_active_tasks;   /* tasks that were drawn (the others are zeros by the early returns) */
+    uint32_t n_batches;
+    double draw_ms;            /* diagnostic: the draw kernels' milliseconds, all batches */
+};
+typedef struct crgpu_subsample_result crgpu_subsample_result;
+int crgpu_subsample_dev(crgpu_ctx *ctx, crgpu_counts *c, const crgpu_subsample_args *args, crgpu_subsample_result *res);
+int crgpu_subsample_plan(int subsample_type, const uint32_t *lib_indices, uint32_t n_lib_indices, uint32_t n_libs,
+                         const double *num_cells_per_lib, const double *raw_reads_per_lib, const double *usable_reads_per_lib,
+                         const int64_t *fixed_depths, uint32_t n_fixed_depths, uint32_t num_additional_depths, int64_t *depths_out,
+                         double *rates_out, uint32_t cap, uint32_t *n_out);
+int crgpu_subsample_summary(uint32_t n_tasks, uint32_t n_genomes, uint64_t n_cells, uint32_t n_features, const uint8_t *task_type,
+                            const uint32_t *cell_genome_mask, const int64_t *umis_per_bc, const int64_t *read_pairs_per_bc,
+                            const int64_t *features_det_per_bc, const int64_t *read_pairs, const int64_t *umis,
+                            const int64_t *total_features_det, double *out, double *dup_frac_all_out);
+
 /* one-call convenience (single GPU): build keys -> dedup -> matrix */
 int crgpu_count(crgpu_ctx *ctx, const crgpu_records *recs, uint32_t n_features, crgpu_matrix **out);
 /* The count entry of SURVEY.md 8(b) for a host that holds its records in HOST memory (the Rust stage code after STAR

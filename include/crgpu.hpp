@@ -241,7 +241,10 @@ class DupBuilder {
         probe_.push_back(probe_idx);
         if (probe_idx >= 0 && (uint32_t)probe_idx + 1u > n_probes_) n_probes_ = (uint32_t)probe_idx + 1u;
     }
-    BarcodeDupMarker build() {
+    /// keep (nullable): receives the crgpu_counts of the batch (what crgpu::run_subsampling takes) instead of their being freed;
+    /// release them with crgpu_counts_free.  *keep stays NULL for an empty batch.
+    BarcodeDupMarker build(crgpu_counts **keep = nullptr) {
+        if (keep) *keep = nullptr;
         const uint64_t n = bc_.size();
         struct Dev {
             const Context &c;
@@ -286,7 +289,10 @@ class DupBuilder {
             pb.resize(np), pp.resize(np), pc.resize(np);
             if (rc == CRGPU_OK && np) rc = crgpu_counts_probe_triplets(ctx_.get(), c, n_probes_, pb.data(), pp.data(), pc.data(), &np);
         }
-        crgpu_counts_free(ctx_.get(), c);
+        if (keep && rc == CRGPU_OK)
+            *keep = c;
+        else
+            crgpu_counts_free(ctx_.get(), c);
         ctx_.check(rc);
         ctx_.check(crgpu_memcpy_d2h(ctx_.get(), pu.data(), d_pu.p, n * 4));
         ctx_.check(crgpu_memcpy_d2h(ctx_.get(), rc32.data(), d_rc.p, n * 4));
@@ -601,6 +607,104 @@ inline std::pair<std::vector<double>, std::vector<double>> compute_ambient_pvalu
         if (x) crgpu_free(ctx.get(), x);
     ctx.check(rc);
     return {p, q};
+}
+
+/// SUBSAMPLE_READS (lib/python/cellranger/subsample.py).  SubsamplingDef (:161-168) of one depth: the rates per library and the
+/// task type (CRGPU_SS_PER_CELL / CRGPU_SS_CELLS_ONLY / CRGPU_SS_BULK).
+static_assert(sizeof(crgpu_subsample_args) == 136, "crgpu_subsample_args changed: bump CRGPU_ABI_VERSION and every binding");
+static_assert(sizeof(crgpu_subsample_result) == 56, "crgpu_subsample_result changed: bump CRGPU_ABI_VERSION and every binding");
+struct SubsamplingDef {
+    int64_t target_read_pairs_per_cell;
+    uint8_t task_type;
+    std::vector<double> library_subsample_rates;
+};
+/// make_subsamplings (:222-309) for the libraries `lib_indices` of one library type; subsample_type: CRGPU_SS_PLAN_*.
+inline std::vector<SubsamplingDef> make_subsamplings(int subsample_type, const std::vector<uint32_t> &lib_indices,
+                                                     const std::vector<double> &num_cells_per_lib, const std::vector<double> &raw_reads_per_lib,
+                                                     const std::vector<double> &usable_reads_per_lib, const std::vector<int64_t> &fixed_depths,
+                                                     uint32_t num_additional_depths = CRGPU_SS_NUM_ADDITIONAL_DEPTHS) {
+    const uint32_t n_libs = (uint32_t)num_cells_per_lib.size();
+    if (raw_reads_per_lib.size() != n_libs || usable_reads_per_lib.size() != n_libs) throw Error(CRGPU_EINVAL, "make_subsamplings: shapes");
+    const uint32_t cap = (uint32_t)fixed_depths.size() + num_additional_depths + 1;
+    std::vector<int64_t> depths(cap);
+    std::vector<double> rates((size_t)cap * n_libs);
+    uint32_t n = 0;
+    const int rc = crgpu_subsample_plan(subsample_type, lib_indices.data(), (uint32_t)lib_indices.size(), n_libs, num_cells_per_lib.data(),
+                                        raw_reads_per_lib.data(), usable_reads_per_lib.data(), fixed_depths.data(), (uint32_t)fixed_depths.size(),
+                                        num_additional_depths, depths.data(), rates.data(), cap, &n);
+    if (rc != CRGPU_OK) throw Error(rc, crgpu_last_error(nullptr));
+    const uint8_t type = subsample_type == CRGPU_SS_PLAN_BULK ? CRGPU_SS_BULK : subsample_type == CRGPU_SS_PLAN_RAW_CELLS ? CRGPU_SS_CELLS_ONLY : CRGPU_SS_PER_CELL;
+    std::vector<SubsamplingDef> out;
+    for (uint32_t d = 0; d < n; d++) out.push_back({depths[d], type, {rates.begin() + (size_t)d * n_libs, rates.begin() + (size_t)(d + 1) * n_libs}});
+    return out;
+}
+/// SubsampleDataDict (:406-415): [task][genome][cell], [task][genome], [task][genome][feature]; any_reads [library][genome]
+struct SubsampleData {
+    uint32_t n_tasks = 0, n_genomes = 0, n_libs = 0, n_features = 0;
+    uint64_t n_cells = 0;
+    std::vector<int64_t> umis_per_bc, read_pairs_per_bc, features_det_per_bc, read_pairs, umis, total_features_det;
+    std::vector<uint8_t> any_reads;
+    crgpu_subsample_result info{};
+};
+/// run_subsampling (:430-569) on the molecule table of `counts` (DupBuilder::build(&counts)); cell_ranks: strictly ascending
+/// canonical ranks; feature_genome / cell_genome_mask / feature_mask: empty = genome 0 / cells of every genome / all features.
+inline SubsampleData run_subsampling(Context &ctx, crgpu_counts *counts, const std::vector<SubsamplingDef> &tasks, uint32_t n_libs,
+                                     uint32_t n_features, const std::vector<uint32_t> &cell_ranks, uint32_t n_genomes = 1,
+                                     const std::vector<uint8_t> &feature_genome = {}, const std::vector<uint32_t> &cell_genome_mask = {},
+                                     const std::vector<uint8_t> &feature_mask = {}, uint64_t seed = 1) {
+    SubsampleData out;
+    out.n_tasks = (uint32_t)tasks.size(), out.n_genomes = n_genomes, out.n_libs = n_libs, out.n_features = n_features, out.n_cells = cell_ranks.size();
+    if ((!feature_genome.empty() && feature_genome.size() != n_features) || (!feature_mask.empty() && feature_mask.size() != n_features) ||
+        (!cell_genome_mask.empty() && cell_genome_mask.size() != cell_ranks.size()))
+        throw Error(CRGPU_EINVAL, "run_subsampling: shapes");
+    std::vector<double> rates;
+    std::vector<uint8_t> types;
+    for (const auto &t : tasks) {
+        if (t.library_subsample_rates.size() != n_libs) throw Error(CRGPU_EINVAL, "run_subsampling: a task with another number of libraries");
+        rates.insert(rates.end(), t.library_subsample_rates.begin(), t.library_subsample_rates.end());
+        types.push_back(t.task_type);
+    }
+    const size_t T = tasks.size(), G = n_genomes, NC = cell_ranks.size();
+    out.umis_per_bc.assign(T * G * NC, 0), out.read_pairs_per_bc.assign(T * G * NC, 0), out.features_det_per_bc.assign(T * G * NC, 0);
+    out.read_pairs.assign(T * G, 0), out.umis.assign(T * G, 0), out.total_features_det.assign(T * G * n_features, 0);
+    out.any_reads.assign((size_t)n_libs * G, 0);
+    void *d_cells = nullptr;
+    if (NC) {
+        ctx.check(crgpu_malloc(ctx.get(), &d_cells, NC * sizeof(uint32_t)));
+        const int rc = crgpu_memcpy_h2d(ctx.get(), d_cells, cell_ranks.data(), NC * sizeof(uint32_t));
+        if (rc != CRGPU_OK) {
+            crgpu_free(ctx.get(), d_cells);
+            ctx.check(rc);
+        }
+    }
+    crgpu_subsample_args a{};
+    a.n_tasks = out.n_tasks, a.n_genomes = n_genomes, a.n_libs = n_libs, a.n_features = n_features, a.n_cells = NC, a.seed = seed;
+    a.rates = rates.data(), a.task_type = types.data(), a.d_cell_ranks = (const uint32_t *)d_cells;
+    a.cell_genome_mask = cell_genome_mask.empty() ? nullptr : cell_genome_mask.data();
+    a.feature_genome = feature_genome.empty() ? nullptr : feature_genome.data();
+    a.feature_mask = feature_mask.empty() ? nullptr : feature_mask.data();
+    a.umis_per_bc = out.umis_per_bc.data(), a.read_pairs_per_bc = out.read_pairs_per_bc.data(), a.features_det_per_bc = out.features_det_per_bc.data();
+    a.read_pairs = out.read_pairs.data(), a.umis = out.umis.data(), a.total_features_det = out.total_features_det.data();
+    a.any_reads = out.any_reads.data();
+    const int rc = crgpu_subsample_dev(ctx.get(), counts, &a, &out.info);
+    if (d_cells) crgpu_free(ctx.get(), d_cells);
+    ctx.check(rc);
+    return out;
+}
+/// the per-task, per-genome numbers of calculate_subsampling_metrics (:719-845): [task][genome][CRGPU_SS_SUMMARY_COLS] and the
+/// whole-dataset duplication fraction per task
+inline std::pair<std::vector<double>, std::vector<double>> subsampling_summary(const SubsampleData &d, const std::vector<SubsamplingDef> &tasks,
+                                                                              const std::vector<uint32_t> &cell_genome_mask = {}) {
+    std::vector<uint8_t> types;
+    for (const auto &t : tasks) types.push_back(t.task_type);
+    if (types.size() != d.n_tasks) throw Error(CRGPU_EINVAL, "subsampling_summary: shapes");
+    std::vector<double> out((size_t)d.n_tasks * d.n_genomes * CRGPU_SS_SUMMARY_COLS), all(d.n_tasks);
+    const int rc = crgpu_subsample_summary(d.n_tasks, d.n_genomes, d.n_cells, d.n_features, types.data(),
+                                           cell_genome_mask.empty() ? nullptr : cell_genome_mask.data(), d.umis_per_bc.data(),
+                                           d.read_pairs_per_bc.data(), d.features_det_per_bc.data(), d.read_pairs.data(), d.umis.data(),
+                                           d.total_features_det.data(), out.data(), all.data());
+    if (rc != CRGPU_OK) throw Error(rc, crgpu_last_error(nullptr));
+    return {out, all};
 }
 
 }  // namespace crgpu
