@@ -200,6 +200,19 @@ class SubsampleResult(C.Structure):
         ("n_active_tasks", C.c_uint32), ("n_batches", C.c_uint32), ("draw_ms", C.c_double)]
 
 
+class NormalizeDepthArgs(C.Structure):
+    """crgpu_normalize_depth_args"""
+    _fields_ = [(n, C.c_uint32) for n in ("n_libs", "n_features", "n_classes", "reserved")] + [("n_cells", C.c_uint64), ("seed", C.c_uint64)] + [
+        (n, C.c_void_p) for n in ("frac_reads_kept", "feature_class", "d_cell_ranks", "cell_class_mask", "matrix", "raw_mapped_reads",
+                                  "flt_mapped_reads", "reads_per_lib", "kept_reads_per_lib", "kept_molecules_per_lib", "kept_out")]
+
+
+class NormalizeDepthResult(C.Structure):
+    """crgpu_normalize_depth_result"""
+    _fields_ = [(n, C.c_uint64) for n in ("n_molecules", "n_lane", "n_wave", "n_workgroup", "n_kept_molecules", "n_triplets")] + [
+        ("draw_ms", C.c_double), ("tally_ms", C.c_double)]
+
+
 SS_PER_CELL, SS_CELLS_ONLY, SS_BULK = 0, 1, 2
 SS_PLAN_RAW, SS_PLAN_MAPPED, SS_PLAN_RAW_CELLS, SS_PLAN_BULK = 0, 1, 2, 3
 SS_NUM_ADDITIONAL_DEPTHS = 10
@@ -317,6 +330,9 @@ SYMBOLS = {
     "crgpu_subsample_dev": (_i, [_vp, _vp, C.POINTER(SubsampleArgs), C.POINTER(SubsampleResult)]),
     "crgpu_subsample_plan": (_i, [_i, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _u32, C.POINTER(_u32)]),
     "crgpu_subsample_summary": (_i, [_u32, _u32, _u64, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "crgpu_normalize_depth_dev": (_i, [_vp, _vp, C.POINTER(NormalizeDepthArgs), C.POINTER(NormalizeDepthResult)]),
+    "crgpu_select_features_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, C.POINTER(C.POINTER(MatrixDevView))]),
+    "crgpu_normalize_depth_plan": (_i, [_u32, _vp, _vp, _vp, _i, _i, _vp, _dbl, _vp]),
     "crgpu_matrix_dev_download": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _vp, _vp, _vp]),
     "crgpu_count": (_i, [_vp, C.POINTER(Records), _u32, C.POINTER(C.POINTER(MatrixView))]),
     "crgpu_set_feature_pattern": (_i, [_vp, _i, C.c_char_p, _u32, _u32, _vp, _vp]),

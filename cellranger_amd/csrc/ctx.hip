@@ -116,6 +116,20 @@ const std::vector<AbiStruct> &abi_table() {
               ABI_F(crgpu_subsample_result, n_lane), ABI_F(crgpu_subsample_result, n_wave),
               ABI_F(crgpu_subsample_result, n_workgroup), ABI_F(crgpu_subsample_result, n_active_tasks),
               ABI_F(crgpu_subsample_result, n_batches), ABI_F(crgpu_subsample_result, draw_ms)),
+        ABI_S(crgpu_normalize_depth_args, ABI_F(crgpu_normalize_depth_args, n_libs),
+              ABI_F(crgpu_normalize_depth_args, n_features), ABI_F(crgpu_normalize_depth_args, n_classes),
+              ABI_F(crgpu_normalize_depth_args, reserved), ABI_F(crgpu_normalize_depth_args, n_cells),
+              ABI_F(crgpu_normalize_depth_args, seed), ABI_F(crgpu_normalize_depth_args, frac_reads_kept),
+              ABI_F(crgpu_normalize_depth_args, feature_class), ABI_F(crgpu_normalize_depth_args, d_cell_ranks),
+              ABI_F(crgpu_normalize_depth_args, cell_class_mask), ABI_F(crgpu_normalize_depth_args, matrix),
+              ABI_F(crgpu_normalize_depth_args, raw_mapped_reads), ABI_F(crgpu_normalize_depth_args, flt_mapped_reads),
+              ABI_F(crgpu_normalize_depth_args, reads_per_lib), ABI_F(crgpu_normalize_depth_args, kept_reads_per_lib),
+              ABI_F(crgpu_normalize_depth_args, kept_molecules_per_lib), ABI_F(crgpu_normalize_depth_args, kept_out)),
+        ABI_S(crgpu_normalize_depth_result, ABI_F(crgpu_normalize_depth_result, n_molecules),
+              ABI_F(crgpu_normalize_depth_result, n_lane), ABI_F(crgpu_normalize_depth_result, n_wave),
+              ABI_F(crgpu_normalize_depth_result, n_workgroup), ABI_F(crgpu_normalize_depth_result, n_kept_molecules),
+              ABI_F(crgpu_normalize_depth_result, n_triplets), ABI_F(crgpu_normalize_depth_result, draw_ms),
+              ABI_F(crgpu_normalize_depth_result, tally_ms)),
     };
     return t;
 }

@@ -47,6 +47,7 @@ struct crgpu_counts {
     // device position -> position in the table crgpu_counts_molecules lists, made on the first subsampling of counts with
     // several libraries or UMI lengths (subsample.h), else NULL
     uint32_t *d_ss_pos = nullptr;
+    bool sharded = false;  // one rank's share of a well counted over several ranks (crgpu_count_records_sharded_dev)
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -2272,6 +2273,7 @@ extern "C" int crgpu_count_records_sharded_dev(crgpu_ctx *ctx, const crgpu_recor
                            pvals_b.as<uint32_t>(), n_keys, d_processed_umi_out, d_read_count_out, d_dupflags_out);
     CR_HIP(ctx, hipGetLastError());
     CR_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the temporaries above go back to the pool
+    if (*out) (*out)->sharded = W > 1;
     return CRGPU_OK;
 }
 
@@ -2972,3 +2974,4 @@ extern "C" int crgpu_trim_molecule_barcodes_dev(crgpu_ctx *ctx, uint64_t *d_barc
 #include "cell_calling.h"
 #include "emptydrops.h"
 #include "subsample.h"
+#include "normalize_depth.h"

@@ -362,6 +362,34 @@ def subsample_summary(data, task_types, cell_genome_mask=None):
     return out, allf
 
 
+def normalize_depth_plan(library_type, usable_reads, num_cells, downsample=True, targeted_aggr=False, is_targeted_lib=None,
+                         targeted_depth_factor=1.0):
+    """frac_reads_kept float64[n_libs] of NORMALIZE_DEPTH's split() (normalize_depth/__init__.py:139-176) through the C ABI, host
+    only.  library_type: a small integer id per library; usable_reads, num_cells: per library; downsample False: all ones;
+    targeted_aggr: _adjust_frac_kept with the libraries marked in is_targeted_lib and targeted_depth_factor."""
+    types = np.ascontiguousarray(library_type, dtype=np.uint32)
+    usable, cells = (np.ascontiguousarray(x, dtype=np.float64) for x in (usable_reads, num_cells))
+    tg = None if is_targeted_lib is None else np.ascontiguousarray(np.asarray(is_targeted_lib) != 0, dtype=np.uint8)
+    assert len(types) == len(usable) == len(cells) and (tg is None or len(tg) == len(types))
+    frac = np.zeros(len(types), np.float64)
+    rc = _lib.load().crgpu_normalize_depth_plan(len(types), ptr(types), ptr(usable), ptr(cells), int(bool(downsample)), int(bool(targeted_aggr)),
+                                                ptr(tg), float(targeted_depth_factor), ptr(frac))
+    if rc != 0:
+        raise _lib.CrgpuError(rc, "crgpu_normalize_depth_plan")
+    return frac
+
+
+class NormalizedDepth:
+    """Result of Counts.normalize_depth: `matrix` (MatrixDev: the raw UMI matrix after the draw, over the context's BarcodeIndex),
+    `raw_mapped_reads` / `flt_mapped_reads` int64[n_classes], `reads_per_lib` / `kept_reads_per_lib` / `kept_molecules_per_lib`
+    int64[n_libs], `kept` (uint32 per molecule in table order, or None) and `result` (crgpu_normalize_depth_result as a dict)."""
+
+    def __init__(self, matrix, sums, kept, result):
+        self.matrix, self.kept, self.result = matrix, kept, result
+        for k, v in sums.items():
+            setattr(self, k, v)
+
+
 class Counts:
     """crgpu_counts: sorted (barcode, feature, count) triplets + the molecule table."""
 
@@ -486,6 +514,36 @@ class Counts:
         out["any_reads"] = out["any_reads"].astype(bool)
         out["info"] = {name: getattr(res, name) for name, _ in _lib.SubsampleResult._fields_}
         return out
+
+    def normalize_depth(self, frac_reads_kept, cell_ranks=None, feature_class=None, n_classes=1, cell_class_mask=None, seed=0,
+                        want_kept=False, n_features=None):
+        """NORMALIZE_DEPTH's main (normalize_depth/__init__.py:387-517) for the whole table of one GEM well, the binomial replaced
+        by the Philox stream of Counts.subsample (crgpu.h).  frac_reads_kept: per library (normalize_depth_plan); cell_ranks:
+        strictly ascending canonical ranks, a numpy array or a DeviceArray, None: no cells; feature_class: per feature the
+        (feature type, genome) pair of summarize_read_matrix, None: one class; cell_class_mask: per cell, bit k = a cell of class
+        k, None: of every class; n_features: of the key layout (default: the length of feature_class).  -> NormalizedDepth"""
+        frac = np.ascontiguousarray(frac_reads_kept, dtype=np.float64).reshape(-1)
+        if cell_ranks is None:
+            cell_ranks = np.zeros(0, np.uint32)
+        d_cells = cell_ranks if isinstance(cell_ranks, DeviceArray) else self.ctx.upload(np.ascontiguousarray(cell_ranks, dtype=np.uint32))
+        NC, NK, NL = d_cells.size, int(n_classes), len(frac)
+        fc = None if feature_class is None else np.ascontiguousarray(feature_class, dtype=np.uint8)
+        ccm = None if cell_class_mask is None else np.ascontiguousarray(cell_class_mask, dtype=np.uint32)
+        if n_features is None:
+            if fc is None:
+                raise ValueError("n_features (of the key layout) is needed without feature_class")
+            n_features = len(fc)
+        assert (fc is None or len(fc) == int(n_features)) and (ccm is None or len(ccm) == NC)
+        sums = dict(raw_mapped_reads=np.zeros(max(NK, 0), np.int64), flt_mapped_reads=np.zeros(max(NK, 0), np.int64),
+                    reads_per_lib=np.zeros(NL, np.int64), kept_reads_per_lib=np.zeros(NL, np.int64), kept_molecules_per_lib=np.zeros(NL, np.int64))
+        kept = np.zeros(self.n_molecules, np.uint32) if want_kept else None
+        mv = C.POINTER(_lib.MatrixDevView)()
+        a = _lib.NormalizeDepthArgs(n_libs=NL, n_features=int(n_features), n_classes=NK, n_cells=NC, seed=int(seed), frac_reads_kept=ptr(frac),
+                                    feature_class=ptr(fc), d_cell_ranks=_p(d_cells) if NC else None, cell_class_mask=ptr(ccm),
+                                    matrix=C.cast(C.pointer(mv), C.c_void_p), kept_out=ptr(kept), **{k: ptr(v) for k, v in sums.items()})
+        res = _lib.NormalizeDepthResult()
+        self.ctx._check(self.ctx.L.crgpu_normalize_depth_dev(self.ctx.h, self.h, C.byref(a), C.byref(res)))
+        return NormalizedDepth(MatrixDev(self.ctx, mv), sums, kept, {name: getattr(res, name) for name, _ in _lib.NormalizeDepthResult._fields_})
 
     def barcode_summary(self, rank_lo=0, rank_hi=0xFFFFFFFF):
         """BarcodeSummary rows (cr_lib/src/aligner.rs:33-68) of the barcode ranks in [rank_lo, rank_hi), ordered by
@@ -903,6 +961,14 @@ class Context:
         cols = np.ascontiguousarray(cols, dtype=np.uint64)
         mv = C.POINTER(_lib.MatrixDevView)()
         self._check(self.L.crgpu_select_barcodes_dev(self.h, m._mv, ptr(cols), len(cols), C.byref(mv)))
+        return MatrixDev(self, mv)
+
+    def select_features_dev(self, m, feature_mask):
+        """CountMatrix.select_features for an ascending index list: the rows of the MatrixDev `m` whose feature_mask entry is
+        non-zero, renumbered to their position among the kept rows; every column stays"""
+        mask = np.ascontiguousarray(np.asarray(feature_mask) != 0, dtype=np.uint8)
+        mv = C.POINTER(_lib.MatrixDevView)()
+        self._check(self.L.crgpu_select_features_dev(self.h, m._mv, ptr(mask), len(mask), C.byref(mv)))
         return MatrixDev(self, mv)
 
     # ---- cell calling ----------------------------------------------------------------------------------

@@ -917,6 +917,91 @@ int crgpu_subsample_summary(uint32_t n_tasks, uint32_t n_genomes, uint64_t n_cel
                             const int64_t *features_det_per_bc, const int64_t *read_pairs, const int64_t *umis,
                             const int64_t *total_features_det, double *out, double *dup_frac_all_out);
 
+/* ---- depth normalisation: aggr's downsampled matrix of one GEM well ----------------------------------------------------------------
+ * Replaces main / _update_metrics / _get_new_read_pairs / _get_matrix / summarize_read_matrix of NORMALIZE_DEPTH
+ * (mro/rna/stages/aggregator/normalize_depth/__init__.py:229-263,316-517) on the molecule table of `c` for ONE chunk holding the
+ * whole table of one GEM well, with the rates of split() (:139-176) as a host function and CountMatrix.select_features
+ * (lib/python/cellranger/matrix.py:886-894) on a device CSC.  Every library of an aggr belongs to one GEM well: the caller makes
+ * one call per well with that well's rates and concatenates the columns (crgpu_concat_matrices).
+ *   the draw        np.random.seed(0); np.random.binomial(count, frac_reads_kept[library_idx]) -- the serial MT19937 stream -- is
+ *                   NOT reproduced.  Read j (0-based, j < count) of molecule m (its position in the table crgpu_counts_molecules
+ *                   lists) owns word (j & 3) of Philox4x64-10(counter = (1 + (j >> 2), m, 0, 0), key = (seed, 0)) -- element j of
+ *                   np.random.Philox(counter=[0, m, 0, 0], key=[seed, 0]).random_raw() --; u = word >> 11; the read is kept iff
+ *                   u < floor(frac_reads_kept[library] * 2^53).  kept ~ Binomial(count, floor(frac * 2^53) / 2^53) exactly, rate 1
+ *                   keeps every read, rate 0 none, and the whole rule is integer arithmetic: the stream and the rule of
+ *                   crgpu_subsample_dev, so one task of it at the same rates and seed keeps the same reads, and the matrices are
+ *                   nested in the rate.
+ *   crgpu_normalize_depth_dev   args (host arrays except d_cell_ranks): n_libs / n_features must be those of the key layout the
+ *                   counts were made with; frac_reads_kept f64 [n_libs], a value outside [0, 1] or a NaN: CRGPU_EINVAL (numpy's
+ *                   binomial raises there); seed (the stage seeds with 0).  A class is one (feature type, genome) pair of
+ *                   summarize_read_matrix: n_classes 1..32, feature_class u8 [n_features] (NULL: class 0; an entry >= n_classes:
+ *                   CRGPU_EINVAL), d_cell_ranks / n_cells: DEVICE, strictly ascending canonical ranks (else CRGPU_EINVAL; NULL with
+ *                   n_cells 0), cell_class_mask u32 [n_cells], bit k = a cell of class k, i.e. in get_filtered_barcodes(genome_idx,
+ *                   library_type) of that pair (NULL: of every class).  Outputs (caller-allocated, any may be NULL):
+ *                     matrix      crgpu_matrix_dev ** (release with crgpu_matrix_dev_free): the raw UMI matrix after the draw.  The
+ *                                 entry of (feature, barcode) = the molecules of the pair with kept > 0, all libraries pooled (the
+ *                                 coo_matrix of ones sums duplicates); zero entries are dropped, rows ascend inside a column.  The
+ *                                 columns are the context's BarcodeIndex exactly as crgpu_assemble_matrix_dev gives it: a barcode
+ *                                 that loses every molecule keeps an empty column, so the column positions of a cell call on the
+ *                                 undrawn matrix stay valid;
+ *                     raw_mapped_reads, flt_mapped_reads   i64 [n_classes]: the sum of kept over the molecules whose feature is of
+ *                                 class k / over those whose barcode also is a cell of class k;
+ *                     reads_per_lib, kept_reads_per_lib, kept_molecules_per_lib   i64 [n_libs];
+ *                     kept_out    u32 [n_molecules]: the new read count of every molecule in table order (for a host that
+ *                                 rewrites the count column).
+ *                   No molecules: a matrix of empty columns and zero sums.  Counts that hold one rank's share of a sharded well
+ *                   (crgpu_count_records_sharded_dev with more than one rank) are refused with CRGPU_ESTATE.  The draw takes the
+ *                   lane / wave / workgroup paths of crgpu_subsample_dev under CRGPU_SS_WAVE_MIN / CRGPU_SS_WG_MIN; the results do
+ *                   not depend on them.  res (nullable): what ran, the milliseconds of the draw kernels and of the tally (the sums,
+ *                   both compactions and the triplet counts: everything between the draw and the assembly).
+ *   crgpu_select_features_dev   the rows of `m` whose feature_mask byte (host, n_features of them) is non-zero, renumbered to their
+ *                   position among the kept rows; every column stays, empty ones included.  A row >= n_features in the matrix:
+ *                   CRGPU_EINVAL.  With crgpu_select_barcodes[_cols]_dev this is the filtered matrix of main() (:498-517), the
+ *                   targeted case included.
+ *   crgpu_normalize_depth_plan  host, f64, no context: frac_out[n_libs] of split().  library_type: small integer ids;
+ *                   usable_rpc = usable_reads / num_cells where num_cells > 0, else 0; frac = (the minimum usable_rpc of the
+ *                   library's type) / usable_rpc when that minimum is not 0, else 0; downsample == 0: all ones.  targeted_aggr != 0:
+ *                   the libraries with a non-zero is_targeted_lib byte (NULL: none) are multiplied by targeted_depth_factor, and
+ *                   if any product exceeds 1 the unadjusted list is returned whole (_adjust_frac_kept).  An input that is not
+ *                   finite or is negative: CRGPU_EINVAL.  The metrics dictionary, its names and the JSON stay with the host. */
+struct crgpu_normalize_depth_args {
+    uint32_t n_libs;
+    uint32_t n_features;
+    uint32_t n_classes;
+    uint32_t reserved;                 /* 0 */
+    uint64_t n_cells;
+    uint64_t seed;
+    const double *frac_reads_kept;
+    const uint8_t *feature_class;
+    const uint32_t *d_cell_ranks;
+    const uint32_t *cell_class_mask;
+    crgpu_matrix_dev **matrix;
+    int64_t *raw_mapped_reads;
+    int64_t *flt_mapped_reads;
+    int64_t *reads_per_lib;
+    int64_t *kept_reads_per_lib;
+    int64_t *kept_molecules_per_lib;
+    uint32_t *kept_out;
+};
+typedef struct crgpu_normalize_depth_args crgpu_normalize_depth_args; /* (by tag, as crgpu_subsample_args) */
+struct crgpu_normalize_depth_result {
+    uint64_t n_molecules;
+    uint64_t n_lane;           /* molecules drawn one per lane ... */
+    uint64_t n_wave;           /* ... one per wave ... */
+    uint64_t n_workgroup;      /* ... one per workgroup */
+    uint64_t n_kept_molecules; /* molecules that keep at least one read */
+    uint64_t n_triplets;       /* entries of the matrix (0 when no matrix was asked for) */
+    double draw_ms;            /* diagnostic: the draw kernels' milliseconds */
+    double tally_ms;           /* diagnostic: from the end of the draw to the triplets */
+};
+typedef struct crgpu_normalize_depth_result crgpu_normalize_depth_result;
+int crgpu_normalize_depth_dev(crgpu_ctx *ctx, crgpu_counts *c, const crgpu_normalize_depth_args *args, crgpu_normalize_depth_result *res);
+int crgpu_select_features_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const uint8_t *feature_mask, uint32_t n_features,
+                              crgpu_matrix_dev **out);
+int crgpu_normalize_depth_plan(uint32_t n_libs, const uint32_t *library_type, const double *usable_reads, const double *num_cells,
+                               int downsample, int targeted_aggr, const uint8_t *is_targeted_lib, double targeted_depth_factor,
+                               double *frac_out);
+
 /* one-call convenience (single GPU): build keys -> dedup -> matrix */
 int crgpu_count(crgpu_ctx *ctx, const crgpu_records *recs, uint32_t n_features, crgpu_matrix **out);
 /* The count entry of SURVEY.md 8(b) for a host that holds its records in HOST memory (the Rust stage code after STAR

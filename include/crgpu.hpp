@@ -707,4 +707,106 @@ inline std::pair<std::vector<double>, std::vector<double>> subsampling_summary(c
     return {out, all};
 }
 
+/// NORMALIZE_DEPTH of aggr (mro/rna/stages/aggregator/normalize_depth/__init__.py) for one GEM well; the draw is the Philox
+/// stream of run_subsampling (crgpu.h), not the reference's serial np.random.binomial.
+static_assert(sizeof(crgpu_normalize_depth_args) == 120, "crgpu_normalize_depth_args changed: bump CRGPU_ABI_VERSION and every binding");
+static_assert(sizeof(crgpu_normalize_depth_result) == 64, "crgpu_normalize_depth_result changed: bump CRGPU_ABI_VERSION and every binding");
+/// frac_reads_kept of split() (:139-176): library_type = a small integer id per library; is_targeted_lib empty = none.
+inline std::vector<double> normalize_depth_plan(const std::vector<uint32_t> &library_type, const std::vector<double> &usable_reads,
+                                                const std::vector<double> &num_cells, bool downsample = true, bool targeted_aggr = false,
+                                                const std::vector<uint8_t> &is_targeted_lib = {}, double targeted_depth_factor = 1.0) {
+    const size_t n = library_type.size();
+    if (usable_reads.size() != n || num_cells.size() != n || (!is_targeted_lib.empty() && is_targeted_lib.size() != n))
+        throw Error(CRGPU_EINVAL, "normalize_depth_plan: shapes");
+    std::vector<double> frac(n);
+    const int rc = crgpu_normalize_depth_plan((uint32_t)n, library_type.data(), usable_reads.data(), num_cells.data(), downsample, targeted_aggr,
+                                              is_targeted_lib.empty() ? nullptr : is_targeted_lib.data(), targeted_depth_factor, frac.data());
+    if (rc != CRGPU_OK) throw Error(rc, crgpu_last_error(nullptr));
+    return frac;
+}
+/// a device-resident CSC (crgpu_matrix_dev), released with its owner
+class MatrixDev {
+   public:
+    MatrixDev(Context &ctx, crgpu_matrix_dev *m) : ctx_(&ctx), m_(m) {}
+    ~MatrixDev() {
+        if (m_) crgpu_matrix_dev_free(ctx_->get(), m_);
+    }
+    MatrixDev(MatrixDev &&o) noexcept : ctx_(o.ctx_), m_(o.m_) { o.m_ = nullptr; }
+    MatrixDev(const MatrixDev &) = delete;
+    MatrixDev &operator=(const MatrixDev &) = delete;
+    const crgpu_matrix_dev *get() const { return m_; }
+    uint64_t n_barcodes() const { return m_->n_barcodes; }
+    uint64_t nnz() const { return m_->nnz; }
+    struct Host {
+        std::vector<uint32_t> barcode_rank;
+        std::vector<int64_t> indptr;
+        std::vector<int32_t> indices, data;
+    };
+    Host download() const {
+        Host h;
+        h.barcode_rank.resize(m_->n_barcodes), h.indptr.resize(m_->n_barcodes + 1), h.indices.resize(m_->nnz), h.data.resize(m_->nnz);
+        ctx_->check(crgpu_matrix_dev_download(ctx_->get(), m_, h.barcode_rank.data(), h.indptr.data(), h.indices.data(), h.data.data()));
+        return h;
+    }
+
+   private:
+    Context *ctx_;
+    crgpu_matrix_dev *m_;
+};
+/// what main() (:481-532) computes: the raw UMI matrix after the draw, summarize_read_matrix's sums per class, the per-library sums
+struct NormalizedDepth {
+    MatrixDev matrix;
+    std::vector<int64_t> raw_mapped_reads, flt_mapped_reads;                          // [class]
+    std::vector<int64_t> reads_per_lib, kept_reads_per_lib, kept_molecules_per_lib;   // [library]
+    std::vector<uint32_t> kept;                                                       // per molecule in table order (want_kept)
+    crgpu_normalize_depth_result info{};
+};
+/// `counts` = DupBuilder::build(&counts) of the well; cell_ranks: strictly ascending canonical ranks; feature_class empty = one
+/// class; cell_class_mask empty = every cell is a cell of every class.
+inline NormalizedDepth normalize_depth(Context &ctx, crgpu_counts *counts, const std::vector<double> &frac_reads_kept, uint32_t n_features,
+                                       const std::vector<uint32_t> &cell_ranks = {}, const std::vector<uint8_t> &feature_class = {},
+                                       uint32_t n_classes = 1, const std::vector<uint32_t> &cell_class_mask = {}, uint64_t seed = 0,
+                                       bool want_kept = false) {
+    if ((!feature_class.empty() && feature_class.size() != n_features) || (!cell_class_mask.empty() && cell_class_mask.size() != cell_ranks.size()))
+        throw Error(CRGPU_EINVAL, "normalize_depth: shapes");
+    const size_t NL = frac_reads_kept.size(), NC = cell_ranks.size();
+    crgpu_matrix_dev *mv = nullptr;
+    std::vector<int64_t> raw(n_classes, 0), flt(n_classes, 0), reads(NL, 0), kept_reads(NL, 0), kept_mols(NL, 0);
+    std::vector<uint32_t> kept;
+    if (want_kept && counts) {
+        uint64_t nm = 0;
+        ctx.check(crgpu_counts_info(ctx.get(), counts, nullptr, &nm));
+        kept.assign(nm, 0);
+    }
+    void *d_cells = nullptr;
+    if (NC) {
+        ctx.check(crgpu_malloc(ctx.get(), &d_cells, NC * sizeof(uint32_t)));
+        const int rc = crgpu_memcpy_h2d(ctx.get(), d_cells, cell_ranks.data(), NC * sizeof(uint32_t));
+        if (rc != CRGPU_OK) {
+            crgpu_free(ctx.get(), d_cells);
+            ctx.check(rc);
+        }
+    }
+    crgpu_normalize_depth_args a{};
+    a.n_libs = (uint32_t)NL, a.n_features = n_features, a.n_classes = n_classes, a.n_cells = NC, a.seed = seed;
+    a.frac_reads_kept = frac_reads_kept.data(), a.d_cell_ranks = (const uint32_t *)d_cells;
+    a.feature_class = feature_class.empty() ? nullptr : feature_class.data();
+    a.cell_class_mask = cell_class_mask.empty() ? nullptr : cell_class_mask.data();
+    a.matrix = &mv;
+    a.raw_mapped_reads = raw.data(), a.flt_mapped_reads = flt.data(), a.reads_per_lib = reads.data();
+    a.kept_reads_per_lib = kept_reads.data(), a.kept_molecules_per_lib = kept_mols.data();
+    a.kept_out = kept.empty() ? nullptr : kept.data();
+    crgpu_normalize_depth_result info{};
+    const int rc = crgpu_normalize_depth_dev(ctx.get(), counts, &a, &info);
+    if (d_cells) crgpu_free(ctx.get(), d_cells);
+    ctx.check(rc);
+    return NormalizedDepth{MatrixDev(ctx, mv), raw, flt, reads, kept_reads, kept_mols, kept, info};
+}
+/// CountMatrix.select_features (lib/python/cellranger/matrix.py:886-894) for the ascending indices whose mask byte is non-zero
+inline MatrixDev select_features(Context &ctx, const MatrixDev &m, const std::vector<uint8_t> &feature_mask) {
+    crgpu_matrix_dev *out = nullptr;
+    ctx.check(crgpu_select_features_dev(ctx.get(), m.get(), feature_mask.data(), (uint32_t)feature_mask.size(), &out));
+    return MatrixDev(ctx, out);
+}
+
 }  // namespace crgpu
