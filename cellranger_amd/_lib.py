@@ -213,6 +213,19 @@ class NormalizeDepthResult(C.Structure):
         ("draw_ms", C.c_double), ("tally_ms", C.c_double)]
 
 
+class MultigenomeResult(C.Structure):
+    """crgpu_multigenome_result"""
+    _fields_ = [("n", C.c_uint64), ("obs_thresh0", C.c_double), ("obs_thresh1", C.c_double)] + [
+        (n, C.c_int64) for n in ("observed_multiplets", "observed_genome0", "observed_genome1")] + [
+        (n, C.c_uint64) for n in ("sum_c0_genome0", "sum_all_genome0", "sum_c1_genome1", "sum_all_genome1", "sum_max_single", "sum_all_single")] + [
+        (n, C.c_double) for n in ("purity0", "purity1", "purity_overall", "boot_mean")] + [("inferred_multiplets", C.c_int64)] + [
+        (n, C.c_double) for n in ("multiplet_rate", "normalized_multiplet_rate", "multiplet_rate_lb", "multiplet_rate_ub")] + [
+        ("generator_words", C.c_uint64), ("obs_branch", C.c_int32), ("rate_bounds_set", C.c_int32)]
+
+
+MG_MAX_BOOTSTRAPS = 65536
+MG_BRANCH_DEFAULT, MG_BRANCH_PERCENTILES, MG_BRANCH_DEFAULT_SUM, MG_BRANCH_PERCENTILES_SUM = 0, 1, 2, 3
+MG_GENOME0, MG_GENOME1, MG_MULTIPLET = 0, 1, 2
 SS_PER_CELL, SS_CELLS_ONLY, SS_BULK = 0, 1, 2
 SS_PLAN_RAW, SS_PLAN_MAPPED, SS_PLAN_RAW_CELLS, SS_PLAN_BULK = 0, 1, 2, 3
 SS_NUM_ADDITIONAL_DEPTHS = 10
@@ -333,6 +346,9 @@ SYMBOLS = {
     "crgpu_normalize_depth_dev": (_i, [_vp, _vp, C.POINTER(NormalizeDepthArgs), C.POINTER(NormalizeDepthResult)]),
     "crgpu_select_features_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, C.POINTER(C.POINTER(MatrixDevView))]),
     "crgpu_normalize_depth_plan": (_i, [_u32, _vp, _vp, _vp, _i, _i, _vp, _dbl, _vp]),
+    "crgpu_matrix_dev_genome_totals": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, _u32, _vp]),
+    "crgpu_multigenome_dev": (_i, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, C.POINTER(MultigenomeResult)]),
+    "crgpu_multigenome_summary": (_i, [_vp, _u32, _u64, _vp, C.POINTER(MultigenomeResult)]),
     "crgpu_matrix_dev_download": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _vp, _vp, _vp]),
     "crgpu_count": (_i, [_vp, C.POINTER(Records), _u32, C.POINTER(C.POINTER(MatrixView))]),
     "crgpu_set_feature_pattern": (_i, [_vp, _i, C.c_char_p, _u32, _u32, _vp, _vp]),

@@ -18,6 +18,7 @@
 // Integer work except rint(0.1 * baseline) and the loss divide (f64, -ffp-contract=off like the rest of the library).
 #include <algorithm>
 #include <cmath>
+#include <optional>
 
 // ---- MT19937 (the raw stream of np.random.RandomState) -----------------------------------------------------------------------
 // x[n] = x[n - 227] ^ twist(x[n - 624], x[n - 623]): 227 consecutive words depend on older ones only.  ONE workgroup keeps a
@@ -382,6 +383,13 @@ struct OmBootstrap {
     DevBuf state, raw, hist;
     uint64_t raw_words = 0, total = 0;                          // room of d_raw; accepted draws the whole call needs
     uint64_t acc_before = 0, acc_round = 0, round_words = 0;  // accepted draws before / in the round in hand, its raw words
+    // samples per batch: at most batch_cap; batch_forced >= 0 replaces CRGPU_ORDMAG_BATCH (the multi-genome bootstrap, multigenome.h)
+    uint32_t batch_cap = CRGPU_ORDMAG_SAMPLES;
+    long long batch_forced = -1;
+    uint64_t words_made = 0;  // raw words the generator produced for this call
+    // ledger spans of the generator, the compaction and the scan: off for the cell call, whose ledger slots stay as they were
+    bool timed = false;
+    const char *who = "cell call";  // the caller, for the error text
 
     uint64_t words_wanted(uint64_t draws) const {
         const double w = (double)draws * ((double)mask + 1.0) / (double)N * 1.001 + (double)MT_CHUNK;
@@ -393,13 +401,15 @@ struct OmBootstrap {
         d_sorted = sorted;
         total = (uint64_t)n_samples * N;
         for (mask = 0; mask < N - 1u; mask = (mask << 1) | 1u) {}
-        if (ctx->ordmag_batch) {
-            B = ctx->ordmag_batch;
+        const uint32_t forced = batch_forced >= 0 ? (uint32_t)batch_forced : ctx->ordmag_batch;
+        if (forced) {
+            B = forced;
         } else {  // histograms of one batch: at most 256 MB
             const uint64_t fit = (64ull << 20) / N;
-            B = (uint32_t)(fit < 1 ? 1 : fit > CRGPU_ORDMAG_SAMPLES ? CRGPU_ORDMAG_SAMPLES : fit);
+            B = (uint32_t)(fit < 1 ? 1 : fit > batch_cap ? batch_cap : fit);
         }
-        if (B > CRGPU_ORDMAG_SAMPLES) B = CRGPU_ORDMAG_SAMPLES;
+        if (B > batch_cap) B = batch_cap;
+        if (B > n_samples) B = n_samples;  // no rows beyond the call's samples (n_samples >= 1)
         if ((uint64_t)B * N > 0xFFFFFFFFull) B = (uint32_t)(0xFFFFFFFFull / N);  // OmDrawEmit counts inside a batch in 32 bits
         CR_TRY(dmalloc(ctx, hist, (uint64_t)B * N * sizeof(uint32_t)));
         if (N == 1) return CRGPU_OK;  // choice() of one element consumes no generator output
@@ -419,7 +429,11 @@ struct OmBootstrap {
         uint32_t *d_total = ctx->d_scalars + 16, t = 0;
         OmDrawFlag flag{raw.as<uint32_t>(), mask, N - 1u};
         OmDrawEmit emit{raw.as<uint32_t>(), d_pos, hist.as<uint32_t>(), mask, N, (long long)acc_before - (long long)w0, w1 - w0};
-        CR_TRY(compact(ctx, flag, emit, round_words, ctx->d_sort_hist, d_total));
+        {
+            std::optional<CrTimer> tm;
+            if (timed) tm.emplace(ctx, CRGPU_T_KEYS, round_words);
+            CR_TRY(compact(ctx, flag, emit, round_words, ctx->d_sort_hist, d_total));
+        }
         CR_TRY(read_u32(ctx, d_total, &t));
         acc_round = t;
         return CRGPU_OK;
@@ -438,13 +452,20 @@ struct OmBootstrap {
             acc_before += acc_round;
             acc_round = 0;
             round_words = std::min(words_wanted(total - acc_before), raw_words);
-            hipLaunchKernelGGL(k_mt19937<false>, dim3(1), dim3(256), 0, ctx->stream, state.as<uint32_t>(), raw.as<uint32_t>(),
-                               round_words / MT_CHUNK);
-            CR_HIP(ctx, hipGetLastError());
+            {
+                std::optional<CrTimer> tm;
+                if (timed) tm.emplace(ctx, CRGPU_T_SYNTH, round_words);
+                hipLaunchKernelGGL(k_mt19937<false>, dim3(1), dim3(256), 0, ctx->stream, state.as<uint32_t>(), raw.as<uint32_t>(),
+                                   round_words / MT_CHUNK);
+                CR_HIP(ctx, hipGetLastError());
+            }
+            words_made += round_words;
             CR_TRY(consume(w0, w1));
-            CR_REQUIRE(ctx, acc_round > 0, CRGPU_EHIP, "cell call: a generator round of %llu words held no draw",
+            CR_REQUIRE(ctx, acc_round > 0, CRGPU_EHIP, "%s: a generator round of %llu words held no draw", who,
                        (unsigned long long)round_words);
         }
+        std::optional<CrTimer> tm;
+        if (timed) tm.emplace(ctx, CRGPU_T_SCAN, w1 - w0);
         hipLaunchKernelGGL(k_om_row_scan, dim3(s1 - s0), dim3(256), 0, ctx->stream, hist.as<uint32_t>(), N);
         CR_HIP(ctx, hipGetLastError());
         return CRGPU_OK;

@@ -215,6 +215,9 @@ struct crgpu_ctx {
     uint64_t probe_segments[3] = {0, 0, 0};  // barcode segments the last probe-triplet computation ordered per wave / per workgroup / by the global sort
     uint32_t probe_seg_cap = 0xFFFFFFFFu;  // CRGPU_PROBE_SEG_CAP (tests, read at create): largest segment the LDS classes take
     uint32_t ordmag_batch = 0;             // CRGPU_ORDMAG_BATCH (tests, read at create): bootstrap samples per batch of the cell call, 0 = by memory
+    // multi-genome bootstrap (multigenome.h; tests, read at create): samples per batch, 0 = by memory; largest n whose row of
+    // multiplicities a sample's workgroup holds in LDS (128 KiB of the CU's 160; 0 = always device memory)
+    uint32_t mg_batch = 0, mg_lds_cells = 32768;  // CRGPU_MG_BATCH, CRGPU_MG_LDS_CELLS
     uint32_t ed_lds_features = 0xFFFFFFFFu;  // CRGPU_ED_LDS_FEATURES (tests, read at create): largest n_eval_features the EmptyDrops simulation counts in LDS
     // read subsampling (subsample.h; tests, read at create): molecules of fewer reads than ss_wave_min are drawn one per lane, up to
     // ss_wg_min one per wave, larger ones one per workgroup; ss_task_batch = tasks per batch, 0 = by memory

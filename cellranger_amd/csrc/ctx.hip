@@ -130,6 +130,30 @@ const std::vector<AbiStruct> &abi_table() {
               ABI_F(crgpu_normalize_depth_result, n_workgroup), ABI_F(crgpu_normalize_depth_result, n_kept_molecules),
               ABI_F(crgpu_normalize_depth_result, n_triplets), ABI_F(crgpu_normalize_depth_result, draw_ms),
               ABI_F(crgpu_normalize_depth_result, tally_ms)),
+        ABI_S(crgpu_multigenome_result, ABI_F(crgpu_multigenome_result, n),
+              ABI_F(crgpu_multigenome_result, obs_thresh0),
+              ABI_F(crgpu_multigenome_result, obs_thresh1),
+              ABI_F(crgpu_multigenome_result, observed_multiplets),
+              ABI_F(crgpu_multigenome_result, observed_genome0),
+              ABI_F(crgpu_multigenome_result, observed_genome1),
+              ABI_F(crgpu_multigenome_result, sum_c0_genome0),
+              ABI_F(crgpu_multigenome_result, sum_all_genome0),
+              ABI_F(crgpu_multigenome_result, sum_c1_genome1),
+              ABI_F(crgpu_multigenome_result, sum_all_genome1),
+              ABI_F(crgpu_multigenome_result, sum_max_single),
+              ABI_F(crgpu_multigenome_result, sum_all_single),
+              ABI_F(crgpu_multigenome_result, purity0),
+              ABI_F(crgpu_multigenome_result, purity1),
+              ABI_F(crgpu_multigenome_result, purity_overall),
+              ABI_F(crgpu_multigenome_result, boot_mean),
+              ABI_F(crgpu_multigenome_result, inferred_multiplets),
+              ABI_F(crgpu_multigenome_result, multiplet_rate),
+              ABI_F(crgpu_multigenome_result, normalized_multiplet_rate),
+              ABI_F(crgpu_multigenome_result, multiplet_rate_lb),
+              ABI_F(crgpu_multigenome_result, multiplet_rate_ub),
+              ABI_F(crgpu_multigenome_result, generator_words),
+              ABI_F(crgpu_multigenome_result, obs_branch),
+              ABI_F(crgpu_multigenome_result, rate_bounds_set)),
     };
     return t;
 }
@@ -206,6 +230,11 @@ extern "C" int crgpu_create(crgpu_ctx **out, int device_id, int n_ranks, int ran
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && total_b) ctx->pool_budget = (uint64_t)total_b / 2;
     }
     if (const char *cap = getenv("CRGPU_PROBE_SEG_CAP")) ctx->probe_seg_cap = (uint32_t)strtoul(cap, nullptr, 10);  // tests: force the global route
+    if (const char *b = getenv("CRGPU_MG_BATCH")) ctx->mg_batch = (uint32_t)strtoul(b, nullptr, 10);  // tests: small batches of the multi-genome bootstrap
+    if (const char *b = getenv("CRGPU_MG_LDS_CELLS")) {  // tests: the LDS / device-memory seam
+        const unsigned long v = strtoul(b, nullptr, 10);
+        ctx->mg_lds_cells = v < 32768ul ? (uint32_t)v : 32768u;
+    }
     if (const char *b = getenv("CRGPU_ORDMAG_BATCH")) ctx->ordmag_batch = (uint32_t)strtoul(b, nullptr, 10);  // tests: small batches of the cell call
     if (const char *f = getenv("CRGPU_ED_LDS_FEATURES")) ctx->ed_lds_features = (uint32_t)strtoul(f, nullptr, 10);  // tests: 0 = counters in global memory
     if (const char *v = getenv("CRGPU_SS_WAVE_MIN")) ctx->ss_wave_min = (uint32_t)strtoul(v, nullptr, 10);  // tests: reach the wave path of the subsampling draw

@@ -2975,3 +2975,4 @@ extern "C" int crgpu_trim_molecule_barcodes_dev(crgpu_ctx *ctx, uint64_t *d_barc
 #include "emptydrops.h"
 #include "subsample.h"
 #include "normalize_depth.h"
+#include "multigenome.h"

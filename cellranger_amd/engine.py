@@ -3,7 +3,9 @@
 The product path: every method ends in a libcrgpu call; there is no CPU implementation behind
 any of them (a missing library / GPU raises CrgpuError).
 """
+import csv
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -314,6 +316,85 @@ def sgt_proportions(freq):
     if rc < 0:
         raise _lib.CrgpuError(rc, "crgpu_sgt_proportions")
     return (pstar if rc == 0 else None), p0.value, slope.value, rc
+
+
+class Multigenome:
+    """Result of Context.multigenome (MultiGenomeAnalysis.run_all, analysis/multigenome.py:251-335).  `call_dev` = DeviceArray of
+    u8 per barcode (_lib.MG_GENOME0 / MG_GENOME1 / MG_MULTIPLET), `call` = its host copy; `boot_counts` int64[B, 3] =
+    (Multiplets, genome0, genome1) per bootstrap sample, `boot_thresholds` float64[B, 2], `boot_branch` int32[B]
+    (_lib.MG_BRANCH_*), `boot` float64[B] = the inferred multiplets per sample; `obs_thresholds`, `obs_branch`, `observed` =
+    (Multiplets, genome0, genome1) of the unresampled input; `purity_sums` (six integers) and `purity` = (genome0, genome1,
+    overall); `summary` = the numbers of :287-301 (rate_lb / rate_ub None with one sample); `res` = crgpu_multigenome_result
+    as a dict.  From Context.multigenome_from_matrix also `totals`, `top_two`, `count0` / `count1` (DeviceArrays)."""
+
+    def __init__(self, ctx, res, call_dev, boot_counts, boot_thresholds, boot_branch, boot):
+        self.ctx, self.call_dev = ctx, call_dev
+        self.boot_counts, self.boot_thresholds, self.boot_branch, self.boot = boot_counts, boot_thresholds, boot_branch, boot
+        r = self.res = {name: getattr(res, name) for name, _ in _lib.MultigenomeResult._fields_}
+        self.n = int(r["n"])
+        self.call = call_dev.to_host(self.n) if self.n else np.zeros(0, np.uint8)
+        self.obs_thresholds, self.obs_branch = (r["obs_thresh0"], r["obs_thresh1"]), int(r["obs_branch"])
+        self.observed = (int(r["observed_multiplets"]), int(r["observed_genome0"]), int(r["observed_genome1"]))
+        self.purity_sums = tuple(int(r[k]) for k in ("sum_c0_genome0", "sum_all_genome0", "sum_c1_genome1", "sum_all_genome1",
+                                                      "sum_max_single", "sum_all_single"))
+        self.purity = (r["purity0"], r["purity1"], r["purity_overall"])
+        bounds = bool(r["rate_bounds_set"])
+        self.summary = dict(observed_all=self.n, observed_multiplets=self.observed[0], mean=r["boot_mean"],
+                            inferred_multiplets=int(r["inferred_multiplets"]), rate=r["multiplet_rate"],
+                            normalized_rate=r["normalized_multiplet_rate"], rate_lb=r["multiplet_rate_lb"] if bounds else None,
+                            rate_ub=r["multiplet_rate_ub"] if bounds else None)
+        self.totals = self.top_two = self.count0 = self.count1 = None
+
+
+def multigenome_summary(boot_counts, n):
+    """the host summary of the multiplet bootstrap through the C ABI (crgpu_multigenome_summary, no context): boot_counts
+    int64[B, 3] = (Multiplets, genome0, genome1) per sample -> (boot float64[B], dict as Multigenome.summary without the
+    observed entries)"""
+    bc = np.ascontiguousarray(boot_counts, dtype=np.int64).reshape(-1, 3)
+    boot, res = np.zeros(len(bc), np.float64), _lib.MultigenomeResult()
+    rc = _lib.load().crgpu_multigenome_summary(ptr(bc), len(bc), int(n), ptr(boot), C.byref(res))
+    if rc != 0:
+        raise _lib.CrgpuError(rc, "crgpu_multigenome_summary")
+    bounds = bool(res.rate_bounds_set)
+    return boot, dict(mean=res.boot_mean, inferred_multiplets=int(res.inferred_multiplets), rate=res.multiplet_rate,
+                      normalized_rate=res.normalized_multiplet_rate, rate_lb=res.multiplet_rate_lb if bounds else None,
+                      rate_ub=res.multiplet_rate_ub if bounds else None)
+
+
+def multigenome_top_two(totals):
+    """the two genomes of the analysis (multigenome.py:256-262): sorted(argsort(totals)[::-1][:2]); among equal totals the
+    larger index comes first (a stable ascending argsort, reversed)"""
+    return sorted(int(i) for i in np.argsort(np.asarray(totals), kind="stable")[::-1][:2])
+
+
+def write_gem_classification_csv(path, barcodes, count0, count1, call, genome0, genome1):
+    """gem_classification.csv of save_gem_class_csv (multigenome.py:356-384): header barcode,<genome0>,<genome1>,call; the call
+    written as the genome's name or Multiplet; line terminator os.linesep"""
+    names = {_lib.MG_GENOME0: genome0, _lib.MG_GENOME1: genome1, _lib.MG_MULTIPLET: "Multiplet"}
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f, lineterminator=os.linesep)
+        w.writerow(["barcode", genome0, genome1, "call"])
+        for bc, a, b, c in zip(barcodes, np.asarray(count0).tolist(), np.asarray(count1).tolist(), np.asarray(call).tolist()):
+            w.writerow([bc.decode() if isinstance(bc, bytes) else bc, a, b, names[c]])
+
+
+def multigenome_metrics(result, genome0, genome1):
+    """the summary dictionary of run_all (multigenome.py:287-325) from a Multigenome, without the purity-outlier entries"""
+    s, d = result.summary, {}
+    if result.n == 0:
+        return d  # "Don't compute multiplet / purity metrics if no cells detected"
+    d["filtered_bcs_observed_all"] = s["observed_all"]
+    d["filtered_bcs_observed_multiplets"] = s["observed_multiplets"]
+    d["filtered_bcs_inferred_multiplets"] = s["inferred_multiplets"]
+    d["filtered_bcs_inferred_multiplet_rate"] = s["rate"]
+    d["filtered_bcs_inferred_normalized_multiplet_rate"] = s["normalized_rate"]
+    if s["rate_lb"] is not None:
+        d["filtered_bcs_inferred_multiplet_rate_lb"] = s["rate_lb"]
+        d["filtered_bcs_inferred_multiplet_rate_ub"] = s["rate_ub"]
+    d["%s_filtered_bcs_mean_count_purity" % genome0] = result.purity[0]
+    d["%s_filtered_bcs_mean_count_purity" % genome1] = result.purity[1]
+    d["multi_filtered_bcs_mean_count_purity"] = result.purity[2]
+    return d
 
 
 def ordmag_candidates(max_expected_cells=1 << 18):
@@ -997,6 +1078,46 @@ class Context:
         # no barcode called: an empty list of our own, so that .ranks / .filtered_matrix work on an all-zero well, too
         d_cols = DeviceArray(self, n.value, np.uint64, adopt=cols.value) if cols.value else self.empty(0, np.uint64)
         return CellCall(self, d_cols, n.value, res, matrix)
+
+    # ---- multi-genome wells ---------------------------------------------------------------------------
+    def genome_totals(self, m, feature_genome, n_genomes):
+        """per-genome sums of the MatrixDev `m` (txome_counts of multigenome.py:259): feature_genome[f] = the genome of row f,
+        a value >= n_genomes = not counted -> numpy u64[n_genomes]"""
+        fg = np.ascontiguousarray(feature_genome, dtype=np.uint8)
+        out = np.zeros(n_genomes, np.uint64)
+        self._check(self.L.crgpu_matrix_dev_genome_totals(self.h, m._mv, ptr(fg), len(fg), n_genomes, ptr(out)))
+        return out
+
+    def multigenome(self, counts0, counts1, bootstraps=1000):
+        """classify_gems, the multiplet bootstrap and the mean purities (multigenome.py:80-301) of the filtered barcodes whose
+        UMI totals over the two genomes are counts0 / counts1 (DeviceArrays of u32 or numpy arrays) -> Multigenome"""
+        d0, d1 = (x if isinstance(x, DeviceArray) else self.upload(np.ascontiguousarray(x, dtype=np.uint32)) for x in (counts0, counts1))
+        n = d0.size
+        if d1.size != n:
+            raise ValueError("multigenome: counts0 and counts1 differ in length")
+        if d0.dtype != np.uint32 or d1.dtype != np.uint32:
+            raise TypeError("multigenome: device counts must be u32 (as Context.column_sums gives them)")
+        call = self.empty(n, np.uint8)
+        bc, thr, br = np.zeros((bootstraps, 3), np.int64), np.zeros((bootstraps, 2), np.float64), np.zeros(bootstraps, np.int32)
+        res = _lib.MultigenomeResult()
+        self._check(self.L.crgpu_multigenome_dev(self.h, _p(d0), _p(d1), n, bootstraps, _p(call), ptr(bc), ptr(thr), ptr(br), C.byref(res)))
+        boot = multigenome_summary(bc, n)[0] if n else np.zeros(bootstraps, np.float64)
+        out = Multigenome(self, res, call, bc, thr, br, boot)
+        out.count0, out.count1 = d0, d1
+        return out
+
+    def multigenome_from_matrix(self, filtered_matrix, feature_genome, n_genomes, bootstraps=1000):
+        """run_all (multigenome.py:251-335) on the filtered MatrixDev: per-genome totals, the top two genomes, their column sums,
+        then Context.multigenome; the result also carries totals, top_two (ascending genome indices) and count0 / count1"""
+        fg = np.ascontiguousarray(feature_genome, dtype=np.uint8)
+        totals = self.genome_totals(filtered_matrix, fg, n_genomes)
+        top = multigenome_top_two(totals)
+        if len(top) != 2:
+            raise ValueError("multigenome_from_matrix: the analysis needs at least two genomes")
+        d0, d1 = (self.column_sums(filtered_matrix, fg == g) for g in top)
+        out = self.multigenome(d0, d1, bootstraps)
+        out.totals, out.top_two = totals, top
+        return out
 
     def call_additional_cells(self, m, call, low, high, emptydrops_minimum_umis=500, num_sims=10000, max_adj_pvalue=0.01, seed=0,
                               feature_mask=None, sim_table=None, keep_sim_table=False, keep_profile=True):

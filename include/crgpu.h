@@ -695,6 +695,77 @@ int crgpu_select_barcodes_cols_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *a, co
 int crgpu_mt19937_stream_dev(crgpu_ctx *ctx, uint32_t seed, uint64_t n_words, uint32_t *d_out, uint64_t *n_written_out,
                              double *ms_out);
 
+/* ---- multi-genome wells: GEM classes, the multiplet bootstrap and the count purities ------------------------------------------
+ * Replaces MultiGenomeAnalysis.run_all of RUN_MULTIGENOME_ANALYSIS (lib/python/cellranger/analysis/multigenome.py:251-335) with
+ * classify_gems (:138-177), _infer_multiplets (:209-249), infer_multiplets_from_observed (:113-135) and the mean purities of
+ * compute_count_purity (:80-98), for ONE well after the filtered matrix.  The bootstrap's stream is np.random.seed(0) followed
+ * by np.random.choice(n, n) per sample -- the generator, mask-and-reject and draw numbering of the cell call above -- so every
+ * number below equals the reference's: there is no tolerance anywhere in this block.
+ *   crgpu_matrix_dev_genome_totals  totals_out[g] (host, u64[n_genomes]) = the sum of the device matrix over the features f with
+ *                                 feature_genome[f] == g (host, n_features bytes; a value >= n_genomes: the feature is not
+ *                                 counted, as for the subsampling's feature_genome): txome_counts of :259.  CRGPU_EINVAL when the
+ *                                 matrix holds a row >= n_features.  The top two genomes (:260) are chosen by the host:
+ *                                 sorted(argsort(totals)[::-1][:2]), among equal totals the LARGER index first (a stable ascending
+ *                                 argsort, reversed, the rule of the cell call).
+ *   crgpu_multigenome_dev         d_counts0 / d_counts1: device u32[n], the UMI totals of the n filtered barcodes over the
+ *                                 features of the two genomes (crgpu_matrix_dev_column_sums of the filtered matrix under each
+ *                                 genome's mask); n < 2^31.  CRGPU_ERANGE when a barcode's c0 + c1 does not fit 32 bits (the
+ *                                 order by c0 + c1 is kept in 32-bit keys).  bootstraps: 1 .. CRGPU_MULTIGENOME_MAX_BOOTSTRAPS
+ *                                 (the reference passes 1000).
+ *       classes                   t0 = t1 = 10; with A = {c0 > c1} and B = {c1 > c0} both non-empty t0 = P10(c0[A]), t1 =
+ *                                 P10(c1[B]); when min(t0, t1) < 50 and max / min > 25 both become P10(c0 + c1 over all).  A
+ *                                 barcode is a Multiplet iff c0 >= t0 and c1 >= t1, else genome1 iff c1 > c0, else genome0.
+ *                                 P10 = np.percentile(x, 10.0), linear, in numpy's own arithmetic (f64, unfused).
+ *       d_call_out                device u8[n], nullable: 0 genome0, 1 genome1, 2 Multiplet, of the unresampled input.
+ *       boot_counts_out           host int64[3 * bootstraps]: (Multiplets, genome0, genome1) of sample s at [3 s .. 3 s + 2].  The
+ *                                 thresholds and the branch are decided anew in every sample.
+ *       boot_thresholds_out       host double[2 * bootstraps], nullable: (t0, t1) of sample s at [2 s], [2 s + 1].
+ *       boot_branch_out           host int32[bootstraps], nullable: CRGPU_MG_BRANCH_* of sample s.
+ *     n == 0: a zeroed result and no error (the reference returns before it computes anything).  n == 1 consumes no generator
+ *     output.  Samples are processed in batches whose histograms stay bounded; CRGPU_MG_BATCH=<n> in the environment when the
+ *     context is created (tests) fixes the samples per batch.  A sample's row of multiplicities is held in LDS up to 32 768
+ *     barcodes (128 KiB of the CU's 160) and read from device memory beyond; CRGPU_MG_LDS_CELLS=<n> (tests, read at create; 0 =
+ *     always device memory) moves that limit.  No result depends on either.
+ *     The counts of ONE rank of a sharded well cannot be told from a whole well's: a sharded well gathers its matrix first.
+ *   crgpu_multigenome_summary     host only, no context: from boot_counts (as above) the per-sample inferred multiplets
+ *                                 (boot_out, nullable, double[bootstraps]: 0 when genome0 or genome1 is empty, else min(m / p,
+ *                                 m + g0 + g1) with p = 2 (g0 / (g0 + g1)) (g1 / (g0 + g1))), their np.mean (numpy's pairwise
+ *                                 sum), int(round(mean)) half to even, the rates and np.percentile(boot, 2.5 / 97.5) / n of
+ *                                 :287-301 into res->n and the fields from boot_mean to rate_bounds_set; the other fields are left
+ *                                 alone.  crgpu_multigenome_dev calls it: the arithmetic exists once.  A rate whose n is 0: NaN.
+ * NOT covered: the purity-outlier diagnostics of compute_count_purity (:46-78: scipy.stats.beta.fit / ppf, an iterative optimiser;
+ * "not used for any important metrics" there) -- a host computes them from c0, c1 and the call. */
+#define CRGPU_MULTIGENOME_MAX_BOOTSTRAPS 65536
+#define CRGPU_MG_BRANCH_DEFAULT 0         /* t0 = t1 = 10 */
+#define CRGPU_MG_BRANCH_PERCENTILES 1     /* the two per-genome percentiles */
+#define CRGPU_MG_BRANCH_DEFAULT_SUM 2     /* 10 / 10 never passes the fold-change test: unreachable, named for completeness */
+#define CRGPU_MG_BRANCH_PERCENTILES_SUM 3 /* the percentiles failed the fold-change test: P10(c0 + c1) for both */
+struct crgpu_multigenome_result {
+    uint64_t n;                           /* filtered_bcs_observed_all */
+    double obs_thresh0, obs_thresh1;      /* of the unresampled input */
+    int64_t observed_multiplets, observed_genome0, observed_genome1;
+    uint64_t sum_c0_genome0, sum_all_genome0; /* purity sums over the barcodes called genome0: c0, c0 + c1 */
+    uint64_t sum_c1_genome1, sum_all_genome1; /* ... genome1: c1, c0 + c1 */
+    uint64_t sum_max_single, sum_all_single;  /* ... genome0 or genome1: max(c0, c1), c0 + c1 */
+    double purity0, purity1, purity_overall;  /* the quotients; NaN when the denominator is 0 (robust_divide) */
+    double boot_mean;                     /* np.mean of the per-sample inferred multiplets */
+    int64_t inferred_multiplets;          /* int(round(boot_mean)) */
+    double multiplet_rate;                /* boot_mean / n */
+    double normalized_multiplet_rate;     /* 1000 * multiplet_rate / n */
+    double multiplet_rate_lb, multiplet_rate_ub; /* percentiles 2.5 / 97.5 of the samples / n; valid when rate_bounds_set != 0 */
+    uint64_t generator_words;             /* raw 32-bit words the generator produced for this call */
+    int32_t obs_branch;                   /* CRGPU_MG_BRANCH_* of the unresampled input */
+    int32_t rate_bounds_set;              /* bootstraps > 1 */
+};
+typedef struct crgpu_multigenome_result crgpu_multigenome_result; /* (by tag, as crgpu_ordmag_result) */
+int crgpu_matrix_dev_genome_totals(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const uint8_t *feature_genome, uint32_t n_features,
+                                   uint32_t n_genomes, uint64_t *totals_out);
+int crgpu_multigenome_dev(crgpu_ctx *ctx, const uint32_t *d_counts0, const uint32_t *d_counts1, uint64_t n, uint32_t bootstraps,
+                          uint8_t *d_call_out, int64_t *boot_counts_out, double *boot_thresholds_out, int32_t *boot_branch_out,
+                          crgpu_multigenome_result *res);
+int crgpu_multigenome_summary(const int64_t *boot_counts, uint32_t bootstraps, uint64_t n, double *boot_out,
+                              crgpu_multigenome_result *res);
+
 /* ---- cell calling: the non-ambient ("EmptyDrops") barcodes behind the initial call ---------------------------------------------
  * Replaces find_nonambient_barcodes (lib/python/cellranger/cell_calling.py:144-263) as call_additional_cells runs it
  * (cell_calling_helpers.py:575-668) for ONE genome / GEM group; the caller loops and passes a feature mask.

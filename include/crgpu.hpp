@@ -13,6 +13,7 @@
 //   crgpu::filter_cellular_barcodes_ordmag / _fixed_cutoff  lib/python/cellranger/cell_calling_helpers.py:864-964 (Python there)
 //   crgpu::find_nonambient_barcodes / compute_ambient_pvalues / sgt_proportions
 //                           lib/python/cellranger/cell_calling.py:144-263, stats.py:205-231, sgt.py:97-132 (Python there)
+//   crgpu::multigenome_analysis / multigenome_top_two  lib/python/cellranger/analysis/multigenome.py:80-335 (Python there)
 //
 // Errors are C++ exceptions carrying crgpu_last_error (the Rust returns anyhow::Result); nothing here
 // computes on the CPU: every result comes from libcrgpu, and construction fails without a gfx950 device.
@@ -807,6 +808,59 @@ inline MatrixDev select_features(Context &ctx, const MatrixDev &m, const std::ve
     crgpu_matrix_dev *out = nullptr;
     ctx.check(crgpu_select_features_dev(ctx.get(), m.get(), feature_mask.data(), (uint32_t)feature_mask.size(), &out));
     return MatrixDev(ctx, out);
+}
+
+/// MultiGenomeAnalysis.run_all (lib/python/cellranger/analysis/multigenome.py:251-335) behind the filtered matrix: classify_gems,
+/// the multiplet bootstrap (np.random.seed(0) / np.random.choice, reproduced on the device) and the mean count purities.  The
+/// purity-outlier diagnostics (scipy's beta.fit) are not covered (crgpu.h).
+static_assert(sizeof(crgpu_multigenome_result) == 184, "crgpu_multigenome_result changed: bump CRGPU_ABI_VERSION and every binding");
+struct MultigenomeAnalysis {
+    std::vector<uint8_t> call;                 // per barcode: 0 genome0, 1 genome1, 2 Multiplet
+    std::vector<int64_t> boot_counts;          // [3 * bootstraps]: (Multiplets, genome0, genome1) per sample
+    std::vector<double> boot_thresholds;       // [2 * bootstraps]
+    std::vector<int32_t> boot_branch;          // [bootstraps]: CRGPU_MG_BRANCH_*
+    std::vector<double> boot;                  // [bootstraps]: inferred multiplets per sample
+    crgpu_multigenome_result result{};         // the C struct itself
+};
+/// counts0 / counts1: the UMI totals of the filtered barcodes over the features of the two top genomes
+inline MultigenomeAnalysis multigenome_analysis(Context &ctx, const std::vector<uint32_t> &counts0, const std::vector<uint32_t> &counts1,
+                                                uint32_t bootstraps = 1000) {
+    if (counts0.size() != counts1.size()) throw Error(CRGPU_EINVAL, "multigenome_analysis: shapes");
+    const size_t n = counts0.size(), bytes = n * sizeof(uint32_t);
+    MultigenomeAnalysis out;
+    out.call.assign(n, 0), out.boot_counts.assign((size_t)3 * bootstraps, 0), out.boot_thresholds.assign((size_t)2 * bootstraps, 0.0);
+    out.boot_branch.assign(bootstraps, 0), out.boot.assign(bootstraps, 0.0);
+    void *d0 = nullptr, *d1 = nullptr, *dc = nullptr;
+    int rc = CRGPU_OK;
+    if (n) {
+        rc = crgpu_malloc(ctx.get(), &d0, bytes);
+        if (rc == CRGPU_OK) rc = crgpu_malloc(ctx.get(), &d1, bytes);
+        if (rc == CRGPU_OK) rc = crgpu_malloc(ctx.get(), &dc, n);
+        if (rc == CRGPU_OK) rc = crgpu_memcpy_h2d(ctx.get(), d0, counts0.data(), bytes);
+        if (rc == CRGPU_OK) rc = crgpu_memcpy_h2d(ctx.get(), d1, counts1.data(), bytes);
+    }
+    if (rc == CRGPU_OK)
+        rc = crgpu_multigenome_dev(ctx.get(), (const uint32_t *)d0, (const uint32_t *)d1, n, bootstraps, (uint8_t *)dc, out.boot_counts.data(),
+                                   out.boot_thresholds.data(), out.boot_branch.data(), &out.result);
+    if (rc == CRGPU_OK && n) rc = crgpu_memcpy_d2h(ctx.get(), out.call.data(), dc, n);
+    for (void *p : {d0, d1, dc})
+        if (p) crgpu_free(ctx.get(), p);
+    ctx.check(rc);
+    if (n) {
+        crgpu_multigenome_result again = out.result;  // the per-sample values come from the summary (host code, no context)
+        if (crgpu_multigenome_summary(out.boot_counts.data(), bootstraps, n, out.boot.data(), &again) != CRGPU_OK)
+            throw Error(CRGPU_EINVAL, crgpu_last_error(nullptr));
+    }
+    return out;
+}
+/// sorted(np.argsort(totals)[::-1][:2]) of :260: among equal totals the larger index first
+inline std::vector<uint32_t> multigenome_top_two(const std::vector<uint64_t> &totals) {
+    std::vector<uint32_t> idx(totals.size());
+    for (uint32_t i = 0; i < idx.size(); i++) idx[i] = i;
+    std::stable_sort(idx.begin(), idx.end(), [&](uint32_t a, uint32_t b) { return totals[a] < totals[b]; });
+    std::vector<uint32_t> top(idx.rbegin(), idx.rbegin() + std::min<size_t>(2, idx.size()));
+    std::sort(top.begin(), top.end());
+    return top;
 }
 
 }  // namespace crgpu
