@@ -223,6 +223,30 @@ class MultigenomeResult(C.Structure):
         ("generator_words", C.c_uint64), ("obs_branch", C.c_int32), ("rate_bounds_set", C.c_int32)]
 
 
+class RtlGemRuns(C.Structure):
+    """crgpu_rtl_gem_runs"""
+    _fields_ = [("gems_per_tag", C.c_uint64 * 64), ("common", C.c_uint64 * 4096), ("cells_per_tag", C.c_uint64 * 64),
+                ("cells_per_gem_hist", C.c_uint64 * 257), ("cells_per_probe", C.c_uint64 * 256),
+                ("first_cell_col_per_probe", C.c_uint64 * 256), ("gems_with_cells", C.c_uint64), ("n_gems", C.c_uint64),
+                ("n_cells", C.c_uint64), ("n_probe", C.c_uint32), ("n_tags", C.c_uint32), ("present", C.c_uint8 * 64)]
+
+
+class RtlOverlapRow(C.Structure):
+    """crgpu_rtl_overlap_row"""
+    _fields_ = [("tag1", C.c_uint32), ("tag2", C.c_uint32), ("gems1", C.c_int64), ("gems2", C.c_int64), ("common_gems", C.c_int64),
+                ("overlap", C.c_double)]
+
+
+class RtlHighOccupancy(C.Structure):
+    """crgpu_rtl_high_occupancy"""
+    _fields_ = [(n, C.c_uint64) for n in ("n_cells", "n_kept", "gems_with_cells", "high_occupancy_gems", "cells_in_high_occupancy_gems")] + [
+        ("fraction_cell_gems_high_occupancy", C.c_double), ("fraction_cells_in_high_occupancy_gems", C.c_double),
+        ("threshold", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+RTL_MAX_TAGS, RTL_MAX_PROBES, RTL_MAX_TYPES = 64, 256, 8
+RTL_KIND_RTL, RTL_KIND_ANTIBODY, RTL_KIND_OTHER = 0, 1, 2
+RTL_NONE = 0xFF
 MG_MAX_BOOTSTRAPS = 65536
 MG_BRANCH_DEFAULT, MG_BRANCH_PERCENTILES, MG_BRANCH_DEFAULT_SUM, MG_BRANCH_PERCENTILES_SUM = 0, 1, 2, 3
 MG_GENOME0, MG_GENOME1, MG_MULTIPLET = 0, 1, 2
@@ -349,6 +373,15 @@ SYMBOLS = {
     "crgpu_matrix_dev_genome_totals": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, _u32, _vp]),
     "crgpu_multigenome_dev": (_i, [_vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _vp, C.POINTER(MultigenomeResult)]),
     "crgpu_multigenome_summary": (_i, [_vp, _u32, _u64, _vp, C.POINTER(MultigenomeResult)]),
+    "crgpu_rtl_tags_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp]),
+    "crgpu_rtl_sample_columns_dev": (_i, [_vp, _vp, _u64, _vp, _u32, _u32, _i, _vp, _u64, _vp, _vp]),
+    "crgpu_rtl_gem_runs_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, _vp, _u64, _vp, _vp, _vp, C.POINTER(RtlGemRuns)]),
+    "crgpu_rtl_medians_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _vp, _u64, _vp, _vp]),
+    "crgpu_rtl_overlap_rows": (_i, [_vp, _vp, _vp, _u32, C.POINTER(RtlOverlapRow), _u32, _vp]),
+    "crgpu_rtl_ab_thresholds": (_i, [_vp, _vp, _vp, _u32, _vp, _u32, _vp]),
+    "crgpu_rtl_suspicious_pairings": (_i, [C.POINTER(RtlOverlapRow), _u32, _vp, _vp, _u32, C.POINTER(RtlOverlapRow), _vp]),
+    "crgpu_rtl_occupancy_summary": (_i, [_vp, _u32, _u64, _vp, C.c_int64, _dbl, _vp, _vp, _vp]),
+    "crgpu_rtl_remove_high_occupancy_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u64, _u32, _vp, C.POINTER(RtlHighOccupancy)]),
     "crgpu_matrix_dev_download": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _vp, _vp, _vp]),
     "crgpu_count": (_i, [_vp, C.POINTER(Records), _u32, C.POINTER(C.POINTER(MatrixView))]),
     "crgpu_set_feature_pattern": (_i, [_vp, _i, C.c_char_p, _u32, _u32, _vp, _vp]),

@@ -154,6 +154,33 @@ const std::vector<AbiStruct> &abi_table() {
               ABI_F(crgpu_multigenome_result, generator_words),
               ABI_F(crgpu_multigenome_result, obs_branch),
               ABI_F(crgpu_multigenome_result, rate_bounds_set)),
+        ABI_S(crgpu_rtl_gem_runs, ABI_F(crgpu_rtl_gem_runs, gems_per_tag),
+              ABI_F(crgpu_rtl_gem_runs, common),
+              ABI_F(crgpu_rtl_gem_runs, cells_per_tag),
+              ABI_F(crgpu_rtl_gem_runs, cells_per_gem_hist),
+              ABI_F(crgpu_rtl_gem_runs, cells_per_probe),
+              ABI_F(crgpu_rtl_gem_runs, first_cell_col_per_probe),
+              ABI_F(crgpu_rtl_gem_runs, gems_with_cells),
+              ABI_F(crgpu_rtl_gem_runs, n_gems),
+              ABI_F(crgpu_rtl_gem_runs, n_cells),
+              ABI_F(crgpu_rtl_gem_runs, n_probe),
+              ABI_F(crgpu_rtl_gem_runs, n_tags),
+              ABI_F(crgpu_rtl_gem_runs, present)),
+        ABI_S(crgpu_rtl_overlap_row, ABI_F(crgpu_rtl_overlap_row, tag1),
+              ABI_F(crgpu_rtl_overlap_row, tag2),
+              ABI_F(crgpu_rtl_overlap_row, gems1),
+              ABI_F(crgpu_rtl_overlap_row, gems2),
+              ABI_F(crgpu_rtl_overlap_row, common_gems),
+              ABI_F(crgpu_rtl_overlap_row, overlap)),
+        ABI_S(crgpu_rtl_high_occupancy, ABI_F(crgpu_rtl_high_occupancy, n_cells),
+              ABI_F(crgpu_rtl_high_occupancy, n_kept),
+              ABI_F(crgpu_rtl_high_occupancy, gems_with_cells),
+              ABI_F(crgpu_rtl_high_occupancy, high_occupancy_gems),
+              ABI_F(crgpu_rtl_high_occupancy, cells_in_high_occupancy_gems),
+              ABI_F(crgpu_rtl_high_occupancy, fraction_cell_gems_high_occupancy),
+              ABI_F(crgpu_rtl_high_occupancy, fraction_cells_in_high_occupancy_gems),
+              ABI_F(crgpu_rtl_high_occupancy, threshold),
+              ABI_F(crgpu_rtl_high_occupancy, reserved)),
     };
     return t;
 }

@@ -2976,3 +2976,4 @@ extern "C" int crgpu_trim_molecule_barcodes_dev(crgpu_ctx *ctx, uint64_t *d_barc
 #include "subsample.h"
 #include "normalize_depth.h"
 #include "multigenome.h"
+#include "rtl_tags.h"

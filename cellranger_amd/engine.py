@@ -397,6 +397,202 @@ def multigenome_metrics(result, genome0, genome1):
     return d
 
 
+class RtlTags:
+    """Result of Context.rtl_tags: `tags_dev` = DeviceArray of u8, the tag of every column of `matrix` (kept for the later calls),
+    `barcodes_per_tag` u64[n_tags] (all columns, empty ones included), `umi_per_tag` u64[n_types, n_tags] or None."""
+
+    def __init__(self, ctx, matrix, tags_dev, n_tags, barcodes_per_tag, umi_per_tag):
+        self.ctx, self.matrix, self.tags_dev, self.n_tags = ctx, matrix, tags_dev, n_tags
+        self.barcodes_per_tag, self.umi_per_tag = barcodes_per_tag, umi_per_tag
+
+    @property
+    def tags(self):
+        return self.tags_dev.to_host(self.matrix.n_barcodes)
+
+    def sample_columns(self, sample_of_tag, n_samples, cols=None):
+        """the columns of every sample (sample_barcodes; with a cell call: sample_cell_barcodes): sample_of_tag u8[n_tags], 0xFF =
+        no sample; cols = None (all columns), a CellCall, or ascending columns (DeviceArray of u64 / numpy) ->
+        (DeviceArray of u64: sample 0's columns, then sample 1's, ..., ascending inside each; offsets u64[n_samples + 1])"""
+        ctx = self.ctx
+        sot = np.ascontiguousarray(sample_of_tag, dtype=np.uint8)
+        if len(sot) != self.n_tags:
+            raise ValueError("sample_columns: sample_of_tag must have one entry per tag")
+        d_cols, n = None, 0
+        if cols is not None:
+            if isinstance(cols, CellCall):
+                d_cols, n = cols.cols, cols.n_cells
+            elif isinstance(cols, DeviceArray):
+                d_cols, n = cols, cols.size
+            else:
+                h = np.ascontiguousarray(cols, dtype=np.uint64)
+                d_cols, n = ctx.upload(h) if len(h) else ctx.empty(0, np.uint64), len(h)
+        out, off = C.c_void_p(), np.zeros(n_samples + 1, np.uint64)
+        ctx._check(ctx.L.crgpu_rtl_sample_columns_dev(ctx.h, _p(self.tags_dev), self.matrix.n_barcodes, ptr(sot), self.n_tags, n_samples,
+                                                      int(cols is not None), _p(d_cols) if d_cols is not None else None, n, C.byref(out),
+                                                      ptr(off)))
+        kept = int(off[-1])
+        d_out = DeviceArray(ctx, kept, np.uint64, adopt=out.value) if out.value else ctx.empty(0, np.uint64)
+        return d_out, off
+
+
+class RtlGemRuns:
+    """Result of Context.rtl_gem_runs (crgpu_rtl_gem_runs): gems_per_tag, cells_per_tag u64[T]; common u64[T, T] (i < j); present
+    bool[T]; cells_per_gem_hist u64[n_probe + 1] ([k] = GEMs holding k cells, [0] unused); cells_per_probe and
+    first_cell_col_per_probe u64[n_probe] (all ones: the probe rank has no cell); gems_with_cells, n_gems, n_cells."""
+
+    def __init__(self, res):
+        T, P = int(res.n_tags), int(res.n_probe)
+        self.n_tags, self.n_probe = T, P
+        self.gems_per_tag = np.array(res.gems_per_tag[:T], np.uint64)
+        self.common = np.array(res.common[:], np.uint64).reshape(64, 64)[:T, :T].copy()
+        self.cells_per_tag = np.array(res.cells_per_tag[:T], np.uint64)
+        self.present = np.array(res.present[:T], np.uint8) != 0
+        self.cells_per_gem_hist = np.array(res.cells_per_gem_hist[:P + 1], np.uint64)
+        self.cells_per_probe = np.array(res.cells_per_probe[:P], np.uint64)
+        self.first_cell_col_per_probe = np.array(res.first_cell_col_per_probe[:P], np.uint64)
+        self.gems_with_cells, self.n_gems, self.n_cells = int(res.gems_with_cells), int(res.n_gems), int(res.n_cells)
+
+
+def rtl_tag_kind(identifier):
+    """categorize_multiplexing_barcode_id (barcode/src/whitelist.rs:181-192) reduced to what CALL_TAGS_RTL asks: RTL_KIND_RTL for
+    BC001 .. BC024 and BC...A-D, RTL_KIND_ANTIBODY for BC025 and above and ABnnn, RTL_KIND_OTHER otherwise"""
+    head, tail = identifier[:2], identifier[2:]
+    num = int(tail) if tail.isdigit() else None
+    if head == "BC" and ((num is not None and num <= 24) or (num is None and identifier[-1:] in "ABCD" and identifier[-1:] != "")):
+        return _lib.RTL_KIND_RTL
+    if (head == "BC" and num is not None) or (head == "AB" and num is not None):
+        return _lib.RTL_KIND_ANTIBODY
+    return _lib.RTL_KIND_OTHER
+
+
+def _rtl_rows(arr, n):
+    return [dict(tag1=int(r.tag1), tag2=int(r.tag2), gems1=int(r.gems1), gems2=int(r.gems2), common_gems=int(r.common_gems),
+                 overlap=float(r.overlap)) for r in arr[:n]]
+
+
+def rtl_overlap_rows(gems_per_tag, common, present):
+    """calculate_frp_gem_barcode_overlap through the C ABI (crgpu_rtl_overlap_rows, no context): one dict per pair i < j of present
+    tags in (i, j) order: tag1, tag2, gems1, gems2, common_gems, overlap (NaN for 0 / 0)"""
+    g = np.ascontiguousarray(gems_per_tag, dtype=np.uint64)
+    T = len(g)
+    full = np.zeros((64, 64), np.uint64)
+    full[:T, :T] = np.asarray(common, np.uint64).reshape(T, T)
+    pr = np.ascontiguousarray(np.asarray(present) != 0, dtype=np.uint8)
+    rows, n = (_lib.RtlOverlapRow * max(1, T * (T - 1) // 2))(), C.c_uint32()
+    rc = _lib.load().crgpu_rtl_overlap_rows(ptr(g), ptr(full), ptr(pr), T, rows, len(rows), C.byref(n))
+    if rc != 0:
+        raise _lib.CrgpuError(rc, "crgpu_rtl_overlap_rows")
+    return _rtl_rows(rows, n.value)
+
+
+def rtl_ab_thresholds(median, n_nonzero, ab_tag_of_probe, tag_kind):
+    """the Antibody thresholds of detect_suspicious_rtl_ab_pairings (crgpu_rtl_ab_thresholds, no context): u64[n_tags],
+    round(0.1 * median) half away from zero, UINT64_MAX = the tag is removed"""
+    med, nz = np.ascontiguousarray(median, dtype=np.uint64), np.ascontiguousarray(n_nonzero, dtype=np.uint64)
+    abt, kind = np.ascontiguousarray(ab_tag_of_probe, dtype=np.uint8), np.ascontiguousarray(tag_kind, dtype=np.uint8)
+    out = np.zeros(len(kind), np.uint64)
+    rc = _lib.load().crgpu_rtl_ab_thresholds(ptr(med), ptr(nz), ptr(abt), len(abt), ptr(kind), len(kind), ptr(out))
+    if rc != 0:
+        raise _lib.CrgpuError(rc, "crgpu_rtl_ab_thresholds")
+    return out
+
+
+def rtl_suspicious_pairings(rows, tag_kind, paired_with):
+    """the filter at the end of detect_suspicious_rtl_ab_pairings (crgpu_rtl_suspicious_pairings, no context): the RTL + Antibody
+    rows that are no configured pairing (paired_with[rtl tag] = antibody tag or -1), RTL first, sorted by (tag1, tag2)"""
+    kind, pw = np.ascontiguousarray(tag_kind, dtype=np.uint8), np.ascontiguousarray(paired_with, dtype=np.int32)
+    arr, out, n = (_lib.RtlOverlapRow * max(1, len(rows)))(), (_lib.RtlOverlapRow * max(1, len(rows)))(), C.c_uint32()
+    for k, r in enumerate(rows):
+        arr[k] = _lib.RtlOverlapRow(r["tag1"], r["tag2"], r["gems1"], r["gems2"], r["common_gems"], r["overlap"])
+    rc = _lib.load().crgpu_rtl_suspicious_pairings(arr, len(rows), ptr(kind), ptr(pw), len(kind), out, C.byref(n))
+    if rc != 0:
+        raise _lib.CrgpuError(rc, "crgpu_rtl_suspicious_pairings")
+    return _rtl_rows(out, n.value)
+
+
+def rtl_occupancy_summary(cells_per_gem_hist, gems_with_cells, cells_per_probe, total_instrument_partitions=115000,
+                          recovery_factor=1 / 1.65):
+    """the head of remove_bcs_from_high_occupancy_gems (crgpu_rtl_occupancy_summary, no context) from RtlGemRuns' occupancy
+    outputs -> dict(histogram={cells: GEMs} with the zero bin, estimated_lambda, total_probe_barcodes)"""
+    hist = np.ascontiguousarray(cells_per_gem_hist, dtype=np.uint64)
+    cpp = np.ascontiguousarray(cells_per_probe, dtype=np.uint64)
+    zero, lam, probes = C.c_uint64(), C.c_double(), C.c_uint32()
+    rc = _lib.load().crgpu_rtl_occupancy_summary(ptr(hist), len(cpp), int(gems_with_cells), ptr(cpp), int(total_instrument_partitions),
+                                                 float(recovery_factor), C.byref(zero), C.byref(lam), C.byref(probes))
+    if rc != 0:
+        raise _lib.CrgpuError(rc, "crgpu_rtl_occupancy_summary")
+    histogram = {k: int(hist[k]) for k in range(1, len(hist)) if hist[k]}
+    histogram[0] = int(zero.value)
+    return dict(histogram=histogram, estimated_lambda=lam.value, total_probe_barcodes=int(probes.value))
+
+
+def high_occupancy_gem_threshold(estimated_lambda, cells_per_probe, first_cell_col_per_probe, total_simulated_gems=1000000):
+    """_get_high_occupancy_gem_threshold (cell_calling_helpers.py:273-312) with real numpy: the one number of the stage that comes
+    from the host, because np.random.poisson consumes a data-dependent number of uniforms per draw and is serial.  The probe
+    barcodes' probabilities are ordered by first appearance among the cells (Counter(probe_bcs)): that order decides which
+    simulated barcode a uniform selects, so RtlGemRuns reports it."""
+    if estimated_lambda == 0:
+        return 0
+    cpp = np.asarray(cells_per_probe, np.uint64)
+    seen = np.flatnonzero(cpp)
+    order = seen[np.argsort(np.asarray(first_cell_col_per_probe, np.uint64)[seen], kind="stable")]
+    prob = cpp[order].astype(np.int64) / int(cpp.sum())
+    np.random.seed(0)
+    gems = np.random.poisson(estimated_lambda, total_simulated_gems)
+    gems = gems[gems > 0]
+    width = int(gems.max())
+    sim = np.random.choice(np.arange(len(prob)), size=(len(gems), width), p=prob)
+    # distinct barcodes among the first gems[i] of row i: mask the tail, sort the row, count the steps
+    sim = np.where(np.arange(width)[None, :] < gems[:, None], sim, -1)
+    sim.sort(axis=1)
+    distinct = (np.diff(sim, axis=1) != 0).sum(axis=1) + 1 - (sim[:, 0] == -1)
+    return int(np.ceil(np.quantile(distinct, 0.999)))
+
+
+def call_tags_rtl(ctx, m, call, probe_ids, feature_types=None, type_prefixes=None, pairings=None, antibody_type="Antibody Capture"):
+    """CALL_TAGS_RTL (call_tags_rtl.rs:143-301) for the raw MatrixDev `m` and the cell call `call` (CellCall).  probe_ids: the
+    (translated) identifier of every probe rank, None = not on the whitelist; feature_types: the type name of every feature;
+    type_prefixes: {type name: metric prefix or None}; pairings: {RTL identifier: its antibody identifier} of the multi graph.
+    -> dict(tag_ids, tags=RtlTags, runs=RtlGemRuns, barcodes_per_tag={id: count}, rows=[dict with barcode1_id ...], metrics)"""
+    ids = sorted(set(i for i in probe_ids if i is not None) | set((pairings or {}).values()))
+    tag = {i: t for t, i in enumerate(ids)}
+    top = np.array([tag[i] if i is not None else _lib.RTL_NONE for i in probe_ids], np.uint8)
+    types, ft = [], None
+    if feature_types is not None:
+        for ty in feature_types:
+            if ty not in types:
+                types.append(ty)
+        ft = np.array([types.index(ty) for ty in feature_types], np.uint8)
+    tags = ctx.rtl_tags(m, top, len(ids), ft, len(types))
+    runs = ctx.rtl_gem_runs(m, tags, call)
+    rows = rtl_overlap_rows(runs.gems_per_tag, runs.common, runs.present)
+    if pairings:
+        if feature_types is None:
+            raise ValueError("call_tags_rtl: pairings need feature_types")
+        kind = np.array([rtl_tag_kind(i) for i in ids], np.uint8)
+        abt = np.array([tag[pairings.get(i, i)] if i is not None else _lib.RTL_NONE for i in probe_ids], np.uint8)
+        sums = ctx.column_sums(m, np.array([ty == antibody_type for ty in feature_types]))
+        nz, med = ctx.rtl_medians(sums, call, m)
+        low = rtl_ab_thresholds(med, nz, abt, kind)
+        both = ctx.rtl_gem_runs(m, tags, call, ab=(abt, sums, low))
+        pw = np.full(len(ids), -1, np.int32)
+        for a, b in pairings.items():
+            if a in tag:
+                pw[tag[a]] = tag[b]
+        rows = rows + rtl_suspicious_pairings(rtl_overlap_rows(both.gems_per_tag, both.common, both.present), kind, pw)
+    out_rows = [dict(barcode1_id=ids[r["tag1"]], barcode2_id=ids[r["tag2"]], barcode1_gems=r["gems1"], barcode2_gems=r["gems2"],
+                     common_gems=r["common_gems"], overlap=r["overlap"]) for r in rows]
+    metrics = dict(filtered_gel_bead_barcodes_count=runs.gems_with_cells,
+                   filtered_barcodes_per_probe_barcode={ids[t]: int(runs.gems_per_tag[t]) for t in range(len(ids)) if runs.present[t]},
+                   probe_barcode_overlap_coefficients={"%s_%s" % (r["barcode1_id"], r["barcode2_id"]): r["overlap"] for r in out_rows})
+    for k, ty in enumerate(types):
+        prefix = (type_prefixes or {}).get(ty)
+        name = "%s_umi_per_probe_barcode" % prefix if prefix else "umi_per_probe_barcode"
+        metrics[name] = {ids[t]: int(tags.umi_per_tag[k, t]) for t in range(len(ids)) if tags.umi_per_tag[k, t]}
+    return dict(tag_ids=ids, tags=tags, runs=runs, rows=out_rows, metrics=metrics,
+                barcodes_per_tag={ids[t]: int(n) for t, n in enumerate(tags.barcodes_per_tag) if n})
+
+
 def ordmag_candidates(max_expected_cells=1 << 18):
     """the recovered-cells grid of estimate_recovered_cells_ordmag (cell_calling_helpers.py:879-880); host only"""
     out, n = np.zeros(2000, np.int64), C.c_uint32()
@@ -1119,6 +1315,70 @@ class Context:
         out.totals, out.top_two = totals, top
         return out
 
+    # ---- multiplexed Flex (RTL) wells ------------------------------------------------------------------
+    def _rtl_probes(self, who):
+        """the size of the construct's probe segment as Context.set_barcode_segments recorded it; the host tables per probe rank
+        are sized by it, so a construct this object does not know is refused instead of guessed"""
+        n = getattr(self, "rtl_n_probe", 0)
+        if not n:
+            raise ValueError("%s: no GelBeadAndProbe construct was set through Context.set_barcode_segments" % who)
+        return n
+
+    def rtl_tags(self, m, tag_of_probe, n_tags, feature_type=None, n_types=0):
+        """the tag of every column of the raw MatrixDev `m`, the barcodes per tag and (with feature_type u8[n_features], values
+        < n_types or 0xFF) the UMIs per feature type and tag (read_level_multiplexing.rs:22-68) -> RtlTags"""
+        if not isinstance(m, MatrixDev):
+            raise TypeError("rtl_tags: a MatrixDev (a sharded well gathers its matrix first)")
+        top = np.ascontiguousarray(tag_of_probe, dtype=np.uint8)
+        if len(top) != self._rtl_probes("rtl_tags"):
+            raise ValueError("rtl_tags: tag_of_probe must have one entry per probe barcode (%d)" % self.rtl_n_probe)
+        ft = None if feature_type is None else np.ascontiguousarray(feature_type, dtype=np.uint8)
+        d_tags = self.empty(m.n_barcodes, np.uint8)
+        per_tag = np.zeros(n_tags, np.uint64)
+        umi = np.zeros((n_types, n_tags), np.uint64) if n_types else None
+        self._check(self.L.crgpu_rtl_tags_dev(self.h, m._mv, ptr(top), n_tags, ptr(ft), 0 if ft is None else len(ft), n_types, _p(d_tags),
+                                              ptr(per_tag), ptr(umi)))
+        return RtlTags(self, m, d_tags, n_tags, per_tag, umi)
+
+    def rtl_gem_runs(self, m, tags, call, ab=None):
+        """one pass over the GEMs of the raw MatrixDev `m`: gel-bead overlaps of the tags and the GEM occupancy of the cell call
+        `call` (CellCall).  ab = (ab_tag_of_probe u8[n_probe], Antibody column sums as DeviceArray of u32, ab_min_count u64[n_tags])
+        turns the antibody part on (detect_suspicious_rtl_ab_pairings) -> RtlGemRuns"""
+        res = _lib.RtlGemRuns()
+        abt = d_sums = low = None
+        if ab is not None:
+            abt, d_sums, low = np.ascontiguousarray(ab[0], dtype=np.uint8), ab[1], np.ascontiguousarray(ab[2], dtype=np.uint64)
+            if not isinstance(d_sums, DeviceArray):
+                d_sums = self.upload(np.ascontiguousarray(d_sums, dtype=np.uint32))
+            if d_sums.dtype != np.uint32 or d_sums.size != m.n_barcodes or len(low) != tags.n_tags:
+                raise ValueError("rtl_gem_runs: the Antibody sums are u32 per column, ab_min_count has one entry per tag")
+            if len(abt) != self._rtl_probes("rtl_gem_runs"):
+                raise ValueError("rtl_gem_runs: ab_tag_of_probe must have one entry per probe barcode (%d)" % self.rtl_n_probe)
+        self._check(self.L.crgpu_rtl_gem_runs_dev(self.h, m._mv, _p(tags.tags_dev), tags.n_tags, _p(call.cols), call.n_cells, ptr(abt),
+                                                  _p(d_sums), ptr(low), C.byref(res)))
+        return RtlGemRuns(res)
+
+    def rtl_medians(self, counts, call, m=None):
+        """get_median_umi_per_cell for one feature type: counts = the column sums of the raw matrix under that type's mask
+        (DeviceArray of u32) -> (n_nonzero u64[n_probe], median u64[n_probe]) per probe rank"""
+        m = m or call._matrix
+        if m is None:
+            raise ValueError("rtl_medians: pass the MatrixDev the counts belong to")
+        P = self._rtl_probes("rtl_medians")
+        nz, med = np.zeros(256, np.uint64), np.zeros(256, np.uint64)
+        self._check(self.L.crgpu_rtl_medians_dev(self.h, m._mv, _p(counts), _p(call.cols), call.n_cells, ptr(nz), ptr(med)))
+        return nz[:P], med[:P]
+
+    def remove_high_occupancy_gems(self, m, call, threshold):
+        """remove_bcs_from_high_occupancy_gems (cell_calling_helpers.py:315-424) behind its threshold: the cells of GEMs with more
+        than `threshold` cells are dropped -> (CellCall of the kept columns, dict of crgpu_rtl_high_occupancy)"""
+        res, out = _lib.RtlHighOccupancy(), C.c_void_p()
+        self._check(self.L.crgpu_rtl_remove_high_occupancy_dev(self.h, m._mv, _p(call.cols), call.n_cells, int(threshold), C.byref(out),
+                                                               C.byref(res)))
+        kept = DeviceArray(self, int(res.n_kept), np.uint64, adopt=out.value)
+        d = {name: getattr(res, name) for name, _ in _lib.RtlHighOccupancy._fields_ if name != "reserved"}
+        return CellCall(self, kept, int(res.n_kept), dict(call.metrics), m), d
+
     def call_additional_cells(self, m, call, low, high, emptydrops_minimum_umis=500, num_sims=10000, max_adj_pvalue=0.01, seed=0,
                               feature_mask=None, sim_table=None, keep_sim_table=False, keep_profile=True):
         """find_nonambient_barcodes (cell_calling.py:144-263) behind the initial call `call` (CellCall) on the MatrixDev `m`:
@@ -1236,6 +1496,7 @@ class Context:
         pp = (C.c_void_p * k)(*[a.ctypes.data for a in keep])
         self._check(self.L.crgpu_set_barcode_segments(self.h, lib, k, n, ln, pp))
         self.cb_len, self.n_canon = int(sum(seg_lens)), int(np.prod([len(a) for a in keep], dtype=np.int64))
+        self.rtl_n_probe = len(keep[-1]) if k >= 2 else 0  # the probe segment of a GelBeadAndProbe construct
 
     def combine_segments(self, lib, d_seg_idx, n, d_idx_inout, after_correction=False):
         pp = (C.c_void_p * len(d_seg_idx))(*[_p(a) for a in d_seg_idx])

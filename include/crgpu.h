@@ -661,7 +661,8 @@ int crgpu_matrix_dev_download(crgpu_ctx *ctx, const crgpu_matrix_dev *m, uint32_
  *                                 crgpu_probe_metrics_dev and crgpu_assemble_probe_matrix_dev take (strictly ascending).
  *   crgpu_select_barcodes_cols_dev  crgpu_select_barcodes_dev with a DEVICE column list: the filtered matrix without a round
  *                                 trip of the columns.  CRGPU_EINVAL when a column is out of range.
- * EmptyDrops follows below; the gradient / targeted / manual methods and the other filters behind the initial call are not covered. */
+ * EmptyDrops and the high-occupancy-GEM removal of multiplexed Flex wells follow below; the gradient / targeted / manual methods and
+ * the other filters behind the initial call are not covered. */
 #define CRGPU_ORDMAG_SAMPLES 100 /* ORDMAG_NUM_BOOTSTRAP_SAMPLES */
 struct crgpu_ordmag_result {
     uint64_t n_nonzero;            /* N: barcodes with a non-zero count */
@@ -766,6 +767,110 @@ int crgpu_multigenome_dev(crgpu_ctx *ctx, const uint32_t *d_counts0, const uint3
 int crgpu_multigenome_summary(const int64_t *boot_counts, uint32_t bootstraps, uint64_t n, double *boot_out,
                               crgpu_multigenome_result *res);
 
+/* ---- multiplexed Flex (RTL) wells: tags, sample columns, probe-barcode overlaps, high-occupancy GEMs -----------------------------
+ * Replaces CALL_TAGS_RTL (lib/rust/cr_lib/src/stages/call_tags_rtl.rs:143-498, barcode_overlap.rs, read_level_multiplexing.rs:22-68)
+ * and remove_bcs_from_high_occupancy_gems of FILTER_BARCODES (lib/python/cellranger/cell_calling_helpers.py:315-424) for ONE well.
+ * Every number is an integer, or an f64 quotient of two integers: all of them equal the reference's, there is no tolerance.
+ * The context's barcode construct (crgpu_set_barcode_segments) must have at least 2 segments, else CRGPU_ESTATE; its last segment
+ * is the probe barcode: n_probe = its size (<= CRGPU_RTL_MAX_PROBES, else CRGPU_ERANGE).  A column of canonical rank r has probe
+ * rank p = r % n_probe and GEM g = r / n_probe; the columns of one GEM are adjacent (a run).  A TAG is an index 0 .. n_tags - 1
+ * (n_tags <= CRGPU_RTL_MAX_TAGS, else CRGPU_ERANGE) into the caller's probe-barcode identifiers in ascending identifier order.
+ * All calls need V < 2^32 - 1 columns.
+ *   crgpu_rtl_tags_dev            tag_of_probe: host u8[n_probe], 0xFF = not on the map.  d_tags_out: device u8[V], the tag of every
+ *                                 column; CRGPU_EINVAL when a column uses a probe rank that is not on the map (the reference
+ *                                 panics).  barcodes_per_tag_out: host u64[n_tags], all columns (the list lengths of
+ *                                 get_barcodes_per_multiplexing_identifier).  n_types > 0 (<= CRGPU_RTL_MAX_TYPES): feature_type is
+ *                                 host u8[n_features] with values < n_types or 0xFF = not counted, umi_per_tag_out host
+ *                                 u64[n_types * n_tags] = get_umi_per_multiplexing_identifier (a pair is in the reference's map
+ *                                 iff its sum is non-zero); CRGPU_EINVAL when the matrix holds a row >= n_features.
+ *   crgpu_rtl_sample_columns_dev  sample_of_tag: host u8[n_tags], 0xFF = no sample; n_samples 1 .. 255.  restricted != 0: only
+ *                                 the ascending device columns d_cols / n_cols (a cell call; an empty call, NULL or not, gives
+ *                                 an empty result); restricted == 0: all V columns, d_cols / n_cols are ignored.  *d_cols_out
+ *                                 (library-owned: crgpu_free) = the columns of sample 0, then sample 1, ..., ascending inside each;
+ *                                 offsets_out: host u64[n_samples + 1].  Slices are what crgpu_select_barcodes_cols_dev and
+ *                                 crgpu_cell_ranks_dev take.  NULL (nothing to free) when no column is kept.
+ *   crgpu_rtl_gem_runs_dev        one pass over the runs.  d_cell_cols / n_cells: the cell call (ascending columns).  The antibody
+ *                                 part is on when the three arguments are given: ab_tag_of_probe host u8[n_probe] (the
+ *                                 reverse-translated tag), d_ab_sums device u32[V] (crgpu_matrix_dev_column_sums under the Antibody
+ *                                 mask), ab_min_count host u64[n_tags] (UINT64_MAX = the tag was removed).  A run's mask has bit t
+ *                                 when a cell column of the run has tag t, or (antibody part) when the non-zero Antibody sums of
+ *                                 the run's columns with ab_tag t add up to at least ab_min_count[t] and t is not removed.
+ *                                 Antibody part off: ProbeBarcodeGelBeadGrouper::group_all + calculate_barcode_overlap_counts of
+ *                                 the filtered matrix; on: the combined map of detect_suspicious_rtl_ab_pairings.
+ *   crgpu_rtl_medians_dev         get_median_umi_per_cell for one feature type: d_sums = the column sums under that type's mask;
+ *                                 per probe rank the number of cells with a non-zero sum and their median (even count:
+ *                                 (a + b) / 2 in integers); host u64[n_probe] each.
+ *   crgpu_rtl_overlap_rows        host: one row per pair i < j of present tags in (i, j) order (calculate_frp_gem_barcode_overlap);
+ *                                 overlap = common / min(gems) in f64, 0 / 0 = NaN.  rows_out NULL: the count only.
+ *   crgpu_rtl_ab_thresholds       host: ab_min_count[t] = round(0.1 * median) half away from zero from the Antibody medians per
+ *                                 probe rank; UINT64_MAX for a tag none of whose probes has a cell with Antibody counts.
+ *                                 CRGPU_EINVAL: a tag with a median whose kind is not Antibody (the reference's assert_eq), two
+ *                                 probe ranks with medians on one tag (the reference's map would keep one of them).
+ *   crgpu_rtl_suspicious_pairings host: of the combined rows the RTL + Antibody ones that are no configured pairing
+ *                                 (paired_with[rtl tag] = its antibody tag or -1), RTL first, sorted by (tag1, tag2).
+ *   crgpu_rtl_occupancy_summary   host: the zero bin max(0, int(partitions * recovery_factor - gems_with_cells)) (the reference
+ *                                 passes 115000 and 1 / 1.65), estimated_lambda = sum(k w) / sum(w), the distinct probe barcodes.
+ *   crgpu_rtl_remove_high_occupancy_dev  the cells whose GEM holds more than `threshold` cells are dropped: *d_kept_cols_out
+ *                                 (library-owned: crgpu_free) ascending, for crgpu_select_barcodes_cols_dev.  The threshold comes
+ *                                 from the host (_get_high_occupancy_gem_threshold needs numpy's serial poisson stream).
+ * NOT covered: the read fractions of remove_bcs_from_high_occupancy_gems (per-barcode read counts, not in the matrix).
+ * A sharded well gathers its matrix first. */
+#define CRGPU_RTL_MAX_TAGS 64
+#define CRGPU_RTL_MAX_PROBES 256
+#define CRGPU_RTL_MAX_TYPES 8
+#define CRGPU_RTL_KIND_RTL 0
+#define CRGPU_RTL_KIND_ANTIBODY 1
+#define CRGPU_RTL_KIND_OTHER 2
+struct crgpu_rtl_gem_runs {
+    uint64_t gems_per_tag[64];              /* runs whose mask has the tag */
+    uint64_t common[4096];                  /* [i * 64 + j], i < j: runs with both bits */
+    uint64_t cells_per_tag[64];
+    uint64_t cells_per_gem_hist[257];       /* [k], k = 1 .. n_probe: runs holding k cells */
+    uint64_t cells_per_probe[256];
+    uint64_t first_cell_col_per_probe[256]; /* the smallest cell column of the probe rank; UINT64_MAX: none */
+    uint64_t gems_with_cells, n_gems, n_cells;
+    uint32_t n_probe, n_tags;
+    uint8_t present[64];                    /* the tag is a key of the reference's map */
+};
+typedef struct crgpu_rtl_gem_runs crgpu_rtl_gem_runs;
+struct crgpu_rtl_overlap_row { /* FRPGemBarcodeOverlapRow with tags for identifiers */
+    uint32_t tag1, tag2;
+    int64_t gems1, gems2, common_gems;
+    double overlap;
+};
+typedef struct crgpu_rtl_overlap_row crgpu_rtl_overlap_row;
+struct crgpu_rtl_high_occupancy {
+    uint64_t n_cells, n_kept, gems_with_cells;
+    uint64_t high_occupancy_gems;          /* GEMs with more cells than the threshold */
+    uint64_t cells_in_high_occupancy_gems;
+    double fraction_cell_gems_high_occupancy;     /* NaN when the denominator is 0 (robust_divide) */
+    double fraction_cells_in_high_occupancy_gems;
+    uint32_t threshold, reserved;
+};
+typedef struct crgpu_rtl_high_occupancy crgpu_rtl_high_occupancy;
+int crgpu_rtl_tags_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const uint8_t *tag_of_probe, uint32_t n_tags,
+                       const uint8_t *feature_type, uint32_t n_features, uint32_t n_types, uint8_t *d_tags_out,
+                       uint64_t *barcodes_per_tag_out, uint64_t *umi_per_tag_out);
+int crgpu_rtl_sample_columns_dev(crgpu_ctx *ctx, const uint8_t *d_tags, uint64_t n_barcodes, const uint8_t *sample_of_tag, uint32_t n_tags,
+                                 uint32_t n_samples, int restricted, const uint64_t *d_cols, uint64_t n_cols,
+                                 uint64_t **d_cols_out, uint64_t *offsets_out);
+int crgpu_rtl_gem_runs_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const uint8_t *d_tags, uint32_t n_tags, const uint64_t *d_cell_cols,
+                           uint64_t n_cells, const uint8_t *ab_tag_of_probe, const uint32_t *d_ab_sums, const uint64_t *ab_min_count,
+                           crgpu_rtl_gem_runs *res);
+int crgpu_rtl_medians_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const uint32_t *d_sums, const uint64_t *d_cell_cols, uint64_t n_cells,
+                          uint64_t *n_nonzero_out, uint64_t *median_out);
+int crgpu_rtl_overlap_rows(const uint64_t *gems_per_tag, const uint64_t *common, const uint8_t *present, uint32_t n_tags,
+                           crgpu_rtl_overlap_row *rows_out, uint32_t cap, uint32_t *n_rows_out);
+int crgpu_rtl_ab_thresholds(const uint64_t *median, const uint64_t *n_nonzero, const uint8_t *ab_tag_of_probe, uint32_t n_probe,
+                            const uint8_t *tag_kind, uint32_t n_tags, uint64_t *ab_min_count_out);
+int crgpu_rtl_suspicious_pairings(const crgpu_rtl_overlap_row *rows, uint32_t n_rows, const uint8_t *tag_kind, const int32_t *paired_with,
+                                  uint32_t n_tags, crgpu_rtl_overlap_row *rows_out, uint32_t *n_rows_out);
+int crgpu_rtl_occupancy_summary(const uint64_t *cells_per_gem_hist, uint32_t n_probe, uint64_t gems_with_cells, const uint64_t *cells_per_probe,
+                                int64_t total_instrument_partitions, double recovery_factor, uint64_t *zero_bin_out,
+                                double *estimated_lambda_out, uint32_t *total_probe_barcodes_out);
+int crgpu_rtl_remove_high_occupancy_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const uint64_t *d_cell_cols, uint64_t n_cells,
+                                        uint32_t threshold, uint64_t **d_kept_cols_out, crgpu_rtl_high_occupancy *res);
+
 /* ---- cell calling: the non-ambient ("EmptyDrops") barcodes behind the initial call ---------------------------------------------
  * Replaces find_nonambient_barcodes (lib/python/cellranger/cell_calling.py:144-263) as call_additional_cells runs it
  * (cell_calling_helpers.py:575-668) for ONE genome / GEM group; the caller loops and passes a feature mask.
@@ -815,7 +920,8 @@ int crgpu_multigenome_summary(const int64_t *boot_counts, uint32_t bootstraps, u
  *   crgpu_ambient_pvalues_dev  compute_ambient_pvalues + adjust_pvalue_bh + the calls for n candidates (device d_umis, d_obs_loglk)
  *                              against a table (sim_n: host, ascending; d_sim_loglk: device, n_sim_n x num_sims); the outputs
  *                              are caller-allocated device arrays of n entries, any may be NULL.
- * The gradient / targeted filters and the filters after EmptyDrops are not covered. */
+ * The gradient / targeted filters and the filters after EmptyDrops are not covered, except the high-occupancy-GEM removal of
+ * multiplexed Flex wells (crgpu_rtl_remove_high_occupancy_dev). */
 #define CRGPU_SGT_TOO_FEW 1
 #define CRGPU_SGT_SLOPE 2
 #define CRGPU_ED_OK 0

@@ -14,6 +14,9 @@
 //   crgpu::find_nonambient_barcodes / compute_ambient_pvalues / sgt_proportions
 //                           lib/python/cellranger/cell_calling.py:144-263, stats.py:205-231, sgt.py:97-132 (Python there)
 //   crgpu::multigenome_analysis / multigenome_top_two  lib/python/cellranger/analysis/multigenome.py:80-335 (Python there)
+//   crgpu::rtl_tags / rtl_sample_columns / rtl_gem_runs / rtl_medians / rtl_ab_thresholds / rtl_overlap_rows /
+//   rtl_suspicious_pairings / rtl_occupancy_summary / remove_high_occupancy_gems
+//                           lib/rust/cr_lib/src/stages/call_tags_rtl.rs:143-498, barcode_overlap.rs; cell_calling_helpers.py:315-424
 //
 // Errors are C++ exceptions carrying crgpu_last_error (the Rust returns anyhow::Result); nothing here
 // computes on the CPU: every result comes from libcrgpu, and construction fails without a gfx950 device.
@@ -861,6 +864,197 @@ inline std::vector<uint32_t> multigenome_top_two(const std::vector<uint64_t> &to
     std::vector<uint32_t> top(idx.rbegin(), idx.rbegin() + std::min<size_t>(2, idx.size()));
     std::sort(top.begin(), top.end());
     return top;
+}
+
+/// CALL_TAGS_RTL (lib/rust/cr_lib/src/stages/call_tags_rtl.rs:143-498, barcode_overlap.rs, read_level_multiplexing.rs:22-68) and
+/// remove_bcs_from_high_occupancy_gems (lib/python/cellranger/cell_calling_helpers.py:315-424) on the raw device matrix of a
+/// multiplexed Flex well.  Tags index the caller's probe-barcode identifiers in ascending order.
+static_assert(sizeof(crgpu_rtl_gem_runs) == 40040, "crgpu_rtl_gem_runs changed: bump CRGPU_ABI_VERSION and every binding");
+static_assert(sizeof(crgpu_rtl_overlap_row) == 40, "crgpu_rtl_overlap_row changed: bump CRGPU_ABI_VERSION and every binding");
+static_assert(sizeof(crgpu_rtl_high_occupancy) == 64, "crgpu_rtl_high_occupancy changed: bump CRGPU_ABI_VERSION and every binding");
+namespace detail {
+struct DeviceCols {  // an ascending column list on the device for the length of a call
+    Context &ctx;
+    void *d = nullptr;
+    DeviceCols(Context &c, const std::vector<uint64_t> &cols) : ctx(c) {
+        if (cols.empty()) return;
+        ctx.check(crgpu_malloc(ctx.get(), &d, cols.size() * sizeof(uint64_t)));
+        const int rc = crgpu_memcpy_h2d(ctx.get(), d, cols.data(), cols.size() * sizeof(uint64_t));
+        if (rc != CRGPU_OK) {
+            crgpu_free(ctx.get(), d);
+            d = nullptr;
+            ctx.check(rc);
+        }
+    }
+    ~DeviceCols() {
+        if (d) crgpu_free(ctx.get(), d);
+    }
+    DeviceCols(const DeviceCols &) = delete;
+    const uint64_t *get() const { return (const uint64_t *)d; }
+};
+}  // namespace detail
+struct RtlTags {
+    std::vector<uint8_t> tags;                 // per column of the raw matrix
+    std::vector<uint64_t> barcodes_per_tag;    // [n_tags]
+    std::vector<uint64_t> umi_per_tag;         // [n_types * n_tags]
+};
+/// get_barcodes_per_multiplexing_identifier / get_umi_per_multiplexing_identifier; tag_of_probe[p] = 0xFF: not on the map
+inline RtlTags rtl_tags(Context &ctx, const crgpu_matrix_dev *raw, const std::vector<uint8_t> &tag_of_probe, uint32_t n_tags,
+                        const std::vector<uint8_t> &feature_type = {}, uint32_t n_types = 0) {
+    RtlTags out;
+    out.tags.assign(raw->n_barcodes, 0), out.barcodes_per_tag.assign(n_tags, 0), out.umi_per_tag.assign((size_t)n_types * n_tags, 0);
+    void *d_tags = nullptr;
+    ctx.check(crgpu_malloc(ctx.get(), &d_tags, raw->n_barcodes ? raw->n_barcodes : 1));
+    int rc = crgpu_rtl_tags_dev(ctx.get(), raw, tag_of_probe.data(), n_tags, feature_type.empty() ? nullptr : feature_type.data(),
+                                (uint32_t)feature_type.size(), n_types, (uint8_t *)d_tags, out.barcodes_per_tag.data(),
+                                n_types ? out.umi_per_tag.data() : nullptr);
+    if (rc == CRGPU_OK && raw->n_barcodes) rc = crgpu_memcpy_d2h(ctx.get(), out.tags.data(), d_tags, raw->n_barcodes);
+    crgpu_free(ctx.get(), d_tags);
+    ctx.check(rc);
+    return out;
+}
+namespace detail {
+template <typename T>
+struct DeviceCopy {  // a host vector on the device for the length of a call (one byte when the vector is empty)
+    Context &ctx;
+    void *d = nullptr;
+    DeviceCopy(Context &c, const std::vector<T> &h) : ctx(c) {
+        ctx.check(crgpu_malloc(ctx.get(), &d, h.empty() ? 1 : h.size() * sizeof(T)));
+        const int rc = h.empty() ? CRGPU_OK : crgpu_memcpy_h2d(ctx.get(), d, h.data(), h.size() * sizeof(T));
+        if (rc != CRGPU_OK) {
+            crgpu_free(ctx.get(), d);
+            d = nullptr;
+            ctx.check(rc);
+        }
+    }
+    ~DeviceCopy() {
+        if (d) crgpu_free(ctx.get(), d);
+    }
+    DeviceCopy(const DeviceCopy &) = delete;
+    const T *get() const { return (const T *)d; }
+};
+}  // namespace detail
+/// the antibody part of detect_suspicious_rtl_ab_pairings: the reverse-translated tag of every probe rank, the Antibody sum of
+/// every raw column (crgpu_matrix_dev_column_sums under the Antibody mask) and the thresholds of rtl_ab_thresholds
+struct RtlAntibody {
+    std::vector<uint8_t> ab_tag_of_probe;
+    std::vector<uint32_t> ab_sums;
+    std::vector<uint64_t> ab_min_count;   // UINT64_MAX: the tag is removed
+};
+/// ProbeBarcodeGelBeadGrouper::group_all + calculate_barcode_overlap_counts of the filtered barcodes `cells` (ascending columns of
+/// the raw matrix), and the GEM occupancy of the same pass; with `ab` the combined map of detect_suspicious_rtl_ab_pairings
+inline crgpu_rtl_gem_runs rtl_gem_runs(Context &ctx, const crgpu_matrix_dev *raw, const std::vector<uint8_t> &tags, uint32_t n_tags,
+                                       const std::vector<uint64_t> &cells, const RtlAntibody *ab = nullptr) {
+    crgpu_rtl_gem_runs res{};
+    if (tags.size() != raw->n_barcodes || (ab && (ab->ab_sums.size() != raw->n_barcodes || ab->ab_min_count.size() != n_tags)))
+        throw Error(CRGPU_EINVAL, "rtl_gem_runs: shapes");
+    detail::DeviceCols d_cells(ctx, cells);
+    detail::DeviceCopy<uint8_t> d_tags(ctx, tags);
+    if (ab) {
+        detail::DeviceCopy<uint32_t> d_sums(ctx, ab->ab_sums);
+        ctx.check(crgpu_rtl_gem_runs_dev(ctx.get(), raw, d_tags.get(), n_tags, d_cells.get(), cells.size(), ab->ab_tag_of_probe.data(),
+                                         d_sums.get(), ab->ab_min_count.data(), &res));
+    } else {
+        ctx.check(crgpu_rtl_gem_runs_dev(ctx.get(), raw, d_tags.get(), n_tags, d_cells.get(), cells.size(), nullptr, nullptr, nullptr, &res));
+    }
+    return res;
+}
+/// sample_barcodes (cells == nullptr: all columns) / sample_cell_barcodes (the called columns, ascending): per sample its columns,
+/// ascending -- with crgpu_cell_ranks_dev what crgpu_assemble_probe_matrix_dev takes as d_sample_ranks.  sample_of_tag[t] = 0xFF:
+/// the tag belongs to no sample
+inline std::vector<std::vector<uint64_t>> rtl_sample_columns(Context &ctx, const crgpu_matrix_dev *raw, const std::vector<uint8_t> &tags,
+                                                             const std::vector<uint8_t> &sample_of_tag, uint32_t n_samples,
+                                                             const std::vector<uint64_t> *cells = nullptr) {
+    if (tags.size() != raw->n_barcodes) throw Error(CRGPU_EINVAL, "rtl_sample_columns: one tag per column");
+    detail::DeviceCopy<uint8_t> d_tags(ctx, tags);
+    detail::DeviceCols d_cells(ctx, cells ? *cells : std::vector<uint64_t>{});
+    std::vector<uint64_t> off(n_samples + 1, 0), all;
+    uint64_t *d_out = nullptr;
+    ctx.check(crgpu_rtl_sample_columns_dev(ctx.get(), d_tags.get(), raw->n_barcodes, sample_of_tag.data(), (uint32_t)sample_of_tag.size(),
+                                           n_samples, cells != nullptr, d_cells.get(), cells ? cells->size() : 0, &d_out, off.data()));
+    const int rc = detail::fetch(ctx, all, (const uint64_t *)d_out, off[n_samples]);
+    if (d_out) crgpu_free(ctx.get(), d_out);
+    ctx.check(rc);
+    std::vector<std::vector<uint64_t>> out(n_samples);
+    for (uint32_t s = 0; s < n_samples; s++) out[s].assign(all.begin() + off[s], all.begin() + off[s + 1]);
+    return out;
+}
+struct RtlMedians {
+    std::vector<uint64_t> n_nonzero, median;   // per probe rank
+};
+/// get_median_umi_per_cell for one feature type: sums = the column sums of the raw matrix under that type's mask
+inline RtlMedians rtl_medians(Context &ctx, const crgpu_matrix_dev *raw, const std::vector<uint32_t> &sums, const std::vector<uint64_t> &cells,
+                              uint32_t n_probe) {
+    if (sums.size() != raw->n_barcodes || n_probe > CRGPU_RTL_MAX_PROBES) throw Error(CRGPU_EINVAL, "rtl_medians: shapes");
+    detail::DeviceCopy<uint32_t> d_sums(ctx, sums);
+    detail::DeviceCols d_cells(ctx, cells);
+    RtlMedians out;
+    out.n_nonzero.assign(CRGPU_RTL_MAX_PROBES, 0), out.median.assign(CRGPU_RTL_MAX_PROBES, 0);
+    ctx.check(crgpu_rtl_medians_dev(ctx.get(), raw, d_sums.get(), d_cells.get(), cells.size(), out.n_nonzero.data(), out.median.data()));
+    out.n_nonzero.resize(n_probe), out.median.resize(n_probe);
+    return out;
+}
+/// the Antibody thresholds of detect_suspicious_rtl_ab_pairings: round(0.1 * median), UINT64_MAX = removed
+inline std::vector<uint64_t> rtl_ab_thresholds(const RtlMedians &med, const std::vector<uint8_t> &ab_tag_of_probe,
+                                               const std::vector<uint8_t> &tag_kind) {
+    if (med.median.size() != ab_tag_of_probe.size() || med.n_nonzero.size() != ab_tag_of_probe.size()) throw Error(CRGPU_EINVAL, "rtl_ab_thresholds: shapes");
+    std::vector<uint64_t> out(tag_kind.size());
+    const int rc = crgpu_rtl_ab_thresholds(med.median.data(), med.n_nonzero.data(), ab_tag_of_probe.data(), (uint32_t)ab_tag_of_probe.size(),
+                                           tag_kind.data(), (uint32_t)tag_kind.size(), out.data());
+    if (rc != CRGPU_OK) throw Error(rc, crgpu_last_error(nullptr));
+    return out;
+}
+/// the tail of detect_suspicious_rtl_ab_pairings: RTL + Antibody rows that are no configured pairing, RTL first, sorted
+inline std::vector<crgpu_rtl_overlap_row> rtl_suspicious_pairings(const std::vector<crgpu_rtl_overlap_row> &rows, const std::vector<uint8_t> &tag_kind,
+                                                                  const std::vector<int32_t> &paired_with) {
+    if (paired_with.size() != tag_kind.size()) throw Error(CRGPU_EINVAL, "rtl_suspicious_pairings: shapes");
+    std::vector<crgpu_rtl_overlap_row> out(rows.size() ? rows.size() : 1);
+    uint32_t n = 0;
+    const int rc = crgpu_rtl_suspicious_pairings(rows.data(), (uint32_t)rows.size(), tag_kind.data(), paired_with.data(), (uint32_t)tag_kind.size(),
+                                                 out.data(), &n);
+    if (rc != CRGPU_OK) throw Error(rc, crgpu_last_error(nullptr));
+    out.resize(n);
+    return out;
+}
+struct RtlOccupancy {
+    uint64_t zero_bin = 0;               // GEMs without a cell: max(0, int(partitions * recovery_factor - gems_with_cells))
+    double estimated_lambda = 0.0;
+    uint32_t total_probe_barcodes = 0;
+};
+/// the head of remove_bcs_from_high_occupancy_gems from the occupancy outputs of rtl_gem_runs
+inline RtlOccupancy rtl_occupancy_summary(const crgpu_rtl_gem_runs &r, int64_t total_instrument_partitions = 115000,
+                                          double recovery_factor = 1 / 1.65) {
+    RtlOccupancy out;
+    const int rc = crgpu_rtl_occupancy_summary(r.cells_per_gem_hist, r.n_probe, r.gems_with_cells, r.cells_per_probe, total_instrument_partitions,
+                                               recovery_factor, &out.zero_bin, &out.estimated_lambda, &out.total_probe_barcodes);
+    if (rc != CRGPU_OK) throw Error(rc, crgpu_last_error(nullptr));
+    return out;
+}
+/// calculate_frp_gem_barcode_overlap: one row per pair of present tags
+inline std::vector<crgpu_rtl_overlap_row> rtl_overlap_rows(const crgpu_rtl_gem_runs &r) {
+    uint32_t n = 0;
+    if (crgpu_rtl_overlap_rows(r.gems_per_tag, r.common, r.present, r.n_tags, nullptr, 0, &n) != CRGPU_OK)
+        throw Error(CRGPU_EINVAL, crgpu_last_error(nullptr));
+    std::vector<crgpu_rtl_overlap_row> rows(n);
+    if (n && crgpu_rtl_overlap_rows(r.gems_per_tag, r.common, r.present, r.n_tags, rows.data(), n, &n) != CRGPU_OK)
+        throw Error(CRGPU_EINVAL, crgpu_last_error(nullptr));
+    return rows;
+}
+struct HighOccupancyRemoval {
+    std::vector<uint64_t> kept;           // the kept cell columns, ascending
+    crgpu_rtl_high_occupancy summary{};
+};
+/// remove_bcs_from_high_occupancy_gems behind its threshold (the host's: _get_high_occupancy_gem_threshold needs numpy's stream)
+inline HighOccupancyRemoval remove_high_occupancy_gems(Context &ctx, const crgpu_matrix_dev *raw, const std::vector<uint64_t> &cells,
+                                                       uint32_t threshold) {
+    HighOccupancyRemoval out;
+    detail::DeviceCols d_cells(ctx, cells);
+    uint64_t *d_kept = nullptr;
+    ctx.check(crgpu_rtl_remove_high_occupancy_dev(ctx.get(), raw, d_cells.get(), cells.size(), threshold, &d_kept, &out.summary));
+    const int rc = detail::fetch(ctx, out.kept, (const uint64_t *)d_kept, out.summary.n_kept);
+    crgpu_free(ctx.get(), d_kept);
+    ctx.check(rc);
+    return out;
 }
 
 }  // namespace crgpu
