@@ -244,6 +244,23 @@ class RtlHighOccupancy(C.Structure):
         ("threshold", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class MatrixSummaryClass(C.Structure):
+    """crgpu_matrix_summary_class"""
+    _fields_ = [(n, C.c_uint64) for n in ("n_features_class", "n_cells", "raw_total_counts", "union_total_counts", "union_nnz", "cells_total_counts",
+                                          "cells_nnz", "genes_detected", "counts_sum", "counts_sumsq_hi", "counts_sumsq_lo", "genes_sum",
+                                          "genes_sumsq_hi", "genes_sumsq_lo", "reads_cells")] + [
+        ("top_counts_value", C.c_uint64 * 5), ("top_cells_value", C.c_uint64 * 5), ("counts_q", C.c_uint32 * 6), ("genes_q", C.c_uint32 * 6),
+        ("top_counts_feature", C.c_uint32 * 5), ("top_cells_feature", C.c_uint32 * 5), ("n_top", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class MatrixSummaryFloats(C.Structure):
+    """crgpu_matrix_summary_floats"""
+    _fields_ = [(n, C.c_double) for n in ("counts_mean", "counts_median", "counts_cv", "counts_iqr", "counts_std", "genes_mean", "genes_median",
+                                          "genes_cv", "genes_iqr", "genes_std", "density", "cum_frac", "dupe_frac", "reads_per_cell",
+                                          "reads_cum_frac")]
+
+
+MS_MAX_CLASSES, MS_NO_CLASS, MS_TOP_N = 32, 255, 5
 RTL_MAX_TAGS, RTL_MAX_PROBES, RTL_MAX_TYPES = 64, 256, 8
 RTL_KIND_RTL, RTL_KIND_ANTIBODY, RTL_KIND_OTHER = 0, 1, 2
 RTL_NONE = 0xFF
@@ -382,6 +399,10 @@ SYMBOLS = {
     "crgpu_rtl_suspicious_pairings": (_i, [C.POINTER(RtlOverlapRow), _u32, _vp, _vp, _u32, C.POINTER(RtlOverlapRow), _vp]),
     "crgpu_rtl_occupancy_summary": (_i, [_vp, _u32, _u64, _vp, C.c_int64, _dbl, _vp, _vp, _vp]),
     "crgpu_rtl_remove_high_occupancy_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u64, _u32, _vp, C.POINTER(RtlHighOccupancy)]),
+    "crgpu_matrix_summary_dev": (_i, [_vp, C.POINTER(MatrixDevView), _u32, _u32, _vp, _vp, _u64, _vp, _vp, _vp, _vp, C.POINTER(MatrixSummaryClass),
+                                      C.POINTER(_u64), C.POINTER(_u64), _vp, _vp]),
+    "crgpu_matrix_dev_reads_per_column": (_i, [_vp, C.POINTER(MatrixDevView), _u32, _vp]),
+    "crgpu_matrix_summary_stats": (_i, [C.POINTER(MatrixSummaryClass), _u64, _u64, C.POINTER(MatrixSummaryFloats)]),
     "crgpu_matrix_dev_download": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _vp, _vp, _vp]),
     "crgpu_count": (_i, [_vp, C.POINTER(Records), _u32, C.POINTER(C.POINTER(MatrixView))]),
     "crgpu_set_feature_pattern": (_i, [_vp, _i, C.c_char_p, _u32, _u32, _vp, _vp]),

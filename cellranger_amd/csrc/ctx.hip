@@ -181,6 +181,44 @@ const std::vector<AbiStruct> &abi_table() {
               ABI_F(crgpu_rtl_high_occupancy, fraction_cells_in_high_occupancy_gems),
               ABI_F(crgpu_rtl_high_occupancy, threshold),
               ABI_F(crgpu_rtl_high_occupancy, reserved)),
+        ABI_S(crgpu_matrix_summary_class, ABI_F(crgpu_matrix_summary_class, n_features_class),
+              ABI_F(crgpu_matrix_summary_class, n_cells),
+              ABI_F(crgpu_matrix_summary_class, raw_total_counts),
+              ABI_F(crgpu_matrix_summary_class, union_total_counts),
+              ABI_F(crgpu_matrix_summary_class, union_nnz),
+              ABI_F(crgpu_matrix_summary_class, cells_total_counts),
+              ABI_F(crgpu_matrix_summary_class, cells_nnz),
+              ABI_F(crgpu_matrix_summary_class, genes_detected),
+              ABI_F(crgpu_matrix_summary_class, counts_sum),
+              ABI_F(crgpu_matrix_summary_class, counts_sumsq_hi),
+              ABI_F(crgpu_matrix_summary_class, counts_sumsq_lo),
+              ABI_F(crgpu_matrix_summary_class, genes_sum),
+              ABI_F(crgpu_matrix_summary_class, genes_sumsq_hi),
+              ABI_F(crgpu_matrix_summary_class, genes_sumsq_lo),
+              ABI_F(crgpu_matrix_summary_class, reads_cells),
+              ABI_F(crgpu_matrix_summary_class, top_counts_value),
+              ABI_F(crgpu_matrix_summary_class, top_cells_value),
+              ABI_F(crgpu_matrix_summary_class, counts_q),
+              ABI_F(crgpu_matrix_summary_class, genes_q),
+              ABI_F(crgpu_matrix_summary_class, top_counts_feature),
+              ABI_F(crgpu_matrix_summary_class, top_cells_feature),
+              ABI_F(crgpu_matrix_summary_class, n_top),
+              ABI_F(crgpu_matrix_summary_class, reserved)),
+        ABI_S(crgpu_matrix_summary_floats, ABI_F(crgpu_matrix_summary_floats, counts_mean),
+              ABI_F(crgpu_matrix_summary_floats, counts_median),
+              ABI_F(crgpu_matrix_summary_floats, counts_cv),
+              ABI_F(crgpu_matrix_summary_floats, counts_iqr),
+              ABI_F(crgpu_matrix_summary_floats, counts_std),
+              ABI_F(crgpu_matrix_summary_floats, genes_mean),
+              ABI_F(crgpu_matrix_summary_floats, genes_median),
+              ABI_F(crgpu_matrix_summary_floats, genes_cv),
+              ABI_F(crgpu_matrix_summary_floats, genes_iqr),
+              ABI_F(crgpu_matrix_summary_floats, genes_std),
+              ABI_F(crgpu_matrix_summary_floats, density),
+              ABI_F(crgpu_matrix_summary_floats, cum_frac),
+              ABI_F(crgpu_matrix_summary_floats, dupe_frac),
+              ABI_F(crgpu_matrix_summary_floats, reads_per_cell),
+              ABI_F(crgpu_matrix_summary_floats, reads_cum_frac)),
     };
     return t;
 }
@@ -264,6 +302,7 @@ extern "C" int crgpu_create(crgpu_ctx **out, int device_id, int n_ranks, int ran
     }
     if (const char *b = getenv("CRGPU_ORDMAG_BATCH")) ctx->ordmag_batch = (uint32_t)strtoul(b, nullptr, 10);  // tests: small batches of the cell call
     if (const char *f = getenv("CRGPU_ED_LDS_FEATURES")) ctx->ed_lds_features = (uint32_t)strtoul(f, nullptr, 10);  // tests: 0 = counters in global memory
+    if (const char *f = getenv("CRGPU_MS_LDS_FEATURES")) ctx->ms_lds_features = (uint32_t)strtoul(f, nullptr, 10);  // tests: several slices on a small matrix; 0 = counters in device memory
     if (const char *v = getenv("CRGPU_SS_WAVE_MIN")) ctx->ss_wave_min = (uint32_t)strtoul(v, nullptr, 10);  // tests: reach the wave path of the subsampling draw
     if (const char *v = getenv("CRGPU_SS_WG_MIN")) ctx->ss_wg_min = (uint32_t)strtoul(v, nullptr, 10);      // ... and its workgroup path
     if (const char *v = getenv("CRGPU_SS_TASK_BATCH")) ctx->ss_task_batch = (uint32_t)strtoul(v, nullptr, 10);  // tests: small task batches

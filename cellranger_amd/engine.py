@@ -593,6 +593,116 @@ def call_tags_rtl(ctx, m, call, probe_ids, feature_types=None, type_prefixes=Non
                 barcodes_per_tag={ids[t]: int(n) for t, n in enumerate(tags.barcodes_per_tag) if n})
 
 
+class MatrixSummary:
+    """Result of Context.matrix_summary (crgpu_matrix_summary_dev): counts_per_feature / cells_ge2_per_feature (numpy u64 per feature,
+    over the cells of the feature's own class), classes = one dict per class with the fields of crgpu_matrix_summary_class (arrays as
+    lists), reads_all / reads_union (None without a read table), counts_per_cell / genes_per_cell (DeviceArrays of u32
+    [n_classes, n_cells], when asked for).  floats(k) = the floats of _report for class k (crgpu_matrix_summary_stats)."""
+
+    def __init__(self, ctx, structs, counts_per_feature, cells_ge2_per_feature, reads_all, reads_union, n_listed, counts_per_cell, genes_per_cell):
+        self.ctx, self._structs, self.n_classes, self.n_listed = ctx, structs, len(structs), n_listed
+        self.counts_per_feature, self.cells_ge2_per_feature = counts_per_feature, cells_ge2_per_feature
+        self.reads_all, self.reads_union = reads_all, reads_union
+        self.counts_per_cell, self.genes_per_cell = counts_per_cell, genes_per_cell
+        self.classes = []
+        for c in structs:
+            d = {}
+            for name, _ in _lib.MatrixSummaryClass._fields_:
+                v = getattr(c, name)
+                d[name] = [int(x) for x in v] if hasattr(v, "__len__") else int(v)
+            for name in ("top_counts_feature", "top_counts_value", "top_cells_feature", "top_cells_value"):
+                d[name] = d[name][:d["n_top"]]
+            del d["reserved"]
+            self.classes.append(d)
+
+    def floats(self, k, reads_cells=None, reads_all=None):
+        """mean / median / cv / iqr / std of the counts and the genes per cell, density, cum_frac, dupe_frac, reads_per_cell and
+        reads_cum_frac of class k; reads_cells / reads_all default to the class's own reads and the well's (0 without a read table)"""
+        return matrix_summary_stats(self._structs[k], self.classes[k]["reads_cells"] if reads_cells is None else reads_cells,
+                                    (self.reads_all or 0) if reads_all is None else reads_all)
+
+
+def matrix_summary_stats(cls, reads_cells=0, reads_all=0):
+    """crgpu_matrix_summary_stats: cls = a _lib.MatrixSummaryClass or a dict of its integer fields -> dict of f64"""
+    if isinstance(cls, dict):
+        c = _lib.MatrixSummaryClass()
+        for name, ctype in _lib.MatrixSummaryClass._fields_:
+            if name not in cls:
+                continue
+            if hasattr(ctype, "_length_"):
+                for i, v in enumerate(cls[name]):
+                    getattr(c, name)[i] = int(v)
+            else:
+                setattr(c, name, int(cls[name]))
+        cls = c
+    out = _lib.MatrixSummaryFloats()
+    rc = _lib.load().crgpu_matrix_summary_stats(C.byref(cls), int(reads_cells), int(reads_all), C.byref(out))
+    if rc != 0:
+        raise CrgpuError(rc, (_lib.load().crgpu_last_error(None) or b"").decode())
+    return {name: getattr(out, name) for name, _ in _lib.MatrixSummaryFloats._fields_}
+
+
+def _robust_divide(a, b):
+    a, b = float(a), float(b)
+    return float("nan") if b == 0 else a / b
+
+
+def matrix_summary_metrics(summary, k, genome, feature_ids, total_reads=None, conf_mapped_reads=None, recovered_cells=None, classes=None):
+    """the dict of _report (report_matrix.py:269-387) for class k of a MatrixSummary, keys prefixed with `genome` as report_genomes does
+    (:479-499; "multi" for a feature type without genomes).  feature_ids[f] = the id of row f.  With total_reads (the library type's
+    sequenced reads) also the keys of _report_genome_agnostic_metrics (:76-266) that need no per-genome split of barcode_summary.h5:
+    the union of the cells, reads per cell, the difference from recovered_cells, the density over every class, feature_reads_in_cells
+    and the usable reads, with the summary's read table standing for the conf-mapped barcoded reads of the library type.  The reference
+    computes that block on the sub-matrix of ONE feature type: `classes` lists the classes of the summary that are the genomes of that
+    feature type (default: every class, which is right only when the summary holds one feature type); the density and the total UMI
+    counts behind `<genome>_total_conf_mapped_deduped_barcoded_reads_per_filtered_bc` are taken over them."""
+    c, d = summary.classes[k], {}
+    if c["n_cells"]:
+        f = summary.floats(k)
+        have = summary.reads_all is not None
+        d["filtered_gene_bc_matrix_density"] = f["density"]
+        d["filtered_bcs_top_genes_with_reads"] = {feature_ids[i]: v for i, v in zip(c["top_counts_feature"], c["top_counts_value"])}
+        d["filtered_bcs_top_genes_with_unique_bcs"] = {feature_ids[i]: v for i, v in zip(c["top_cells_feature"], c["top_cells_value"])}
+        d["filtered_bcs_total_unique_genes_detected"] = c["genes_detected"]
+        d["filtered_bcs_total_counts"] = c["cells_total_counts"]
+        for name, pre in (("unique_genes_detected", "genes"), ("counts", "counts")):
+            for stat in ("mean", "median", "cv", "iqr"):
+                d["filtered_bcs_%s_%s" % (stat, name)] = f["%s_%s" % (pre, stat)]
+        d["filtered_bcs_cum_frac"] = f["cum_frac"]
+        d["filtered_bcs_cdna_pcr_dupe_reads_frac"] = f["dupe_frac"] if have else 1 - _robust_divide(0, 0)
+        d["filtered_bcs_conf_mapped_barcoded_reads_per_filtered_bc"] = f["reads_per_cell"]
+        d["filtered_bcs_conf_mapped_barcoded_reads_cum_frac"] = f["reads_cum_frac"]
+        d["filtered_bcs_conf_mapped_deduped_barcoded_reads_per_filtered_bc"] = _robust_divide(c["cells_total_counts"], c["n_cells"])
+        d["filtered_bcs_conf_mapped_deduped_barcoded_reads_cum_frac"] = f["cum_frac"]
+    out = {"%s_%s" % (genome, key): v for key, v in d.items()}
+    if total_reads is not None:
+        n_union = summary.n_listed
+        usable, reads_all = summary.reads_union or 0, summary.reads_all or 0
+        out["filtered_bcs_transcriptome_union"] = out["multi_filtered_bcs"] = n_union
+        out["reads_per_cell"] = out["multi_transcriptome_total_raw_reads_per_filtered_bc"] = _robust_divide(total_reads, n_union)
+        if conf_mapped_reads is not None:
+            out["multi_transcriptome_total_conf_mapped_reads_per_filtered_bc"] = _robust_divide(conf_mapped_reads, n_union)
+        if recovered_cells is None:
+            out["multi_filtered_bcs_difference_from_recovered_cells"] = out["multi_filtered_bcs_relative_difference_from_recovered_cells"] = 0
+        else:
+            out["multi_filtered_bcs_difference_from_recovered_cells"] = int(n_union) - int(recovered_cells)
+            out["multi_filtered_bcs_relative_difference_from_recovered_cells"] = _robust_divide(n_union - recovered_cells, recovered_cells)
+        of_type = [summary.classes[i] for i in (range(summary.n_classes) if classes is None else classes)]
+        out["multi_filtered_gene_bc_matrix_density"] = _robust_divide(sum(x["union_nnz"] for x in of_type),
+                                                                      sum(x["n_features_class"] for x in of_type) * n_union)
+        # duplicated per genome for backwards compatibility (:165-194); the deduped read type is the matrix's own total over the union
+        out["%s_total_raw_reads_per_filtered_bc" % genome] = _robust_divide(total_reads, n_union)
+        if conf_mapped_reads is not None:
+            out["%s_total_conf_mapped_reads_per_filtered_bc" % genome] = _robust_divide(conf_mapped_reads, n_union)
+        out["%s_total_conf_mapped_deduped_barcoded_reads_per_filtered_bc" % genome] = _robust_divide(
+            sum(x["union_total_counts"] for x in of_type), n_union)
+        out["multi_filtered_bcs_conf_mapped_barcoded_reads_cum_frac"] = out["feature_reads_in_cells"] = _robust_divide(usable, reads_all)
+        out["multi_transcriptome_usable_reads_frac"] = out["frac_feature_reads_usable"] = _robust_divide(usable, total_reads)
+        out["multi_usable_reads"] = usable
+        out["multi_usable_reads_per_filtered_bc"] = out["feature_reads_usable_per_cell"] = _robust_divide(usable, n_union)
+    return out
+
+
 def ordmag_candidates(max_expected_cells=1 << 18):
     """the recovered-cells grid of estimate_recovered_cells_ordmag (cell_calling_helpers.py:879-880); host only"""
     out, n = np.zeros(2000, np.int64), C.c_uint32()
@@ -1378,6 +1488,61 @@ class Context:
         kept = DeviceArray(self, int(res.n_kept), np.uint64, adopt=out.value)
         d = {name: getattr(res, name) for name, _ in _lib.RtlHighOccupancy._fields_ if name != "reserved"}
         return CellCall(self, kept, int(res.n_kept), dict(call.metrics), m), d
+
+    # ---- the summary metrics of the filtered matrix ---------------------------------------------------
+    def reads_per_column(self, m, libs=0):
+        """the counted reads (VALID + CORRECTED) of every column of the MatrixDev `m`, the libraries `libs` (an index or several: the
+        libraries of one library type) added up -> DeviceArray of u32"""
+        mask = 0
+        for l in ([libs] if np.isscalar(libs) else libs):
+            if not 0 <= int(l) < 32:
+                raise ValueError("reads_per_column: library %r" % (l,))
+            mask |= 1 << int(l)
+        out = self.empty(m.n_barcodes, np.uint32)
+        self._check(self.L.crgpu_matrix_dev_reads_per_column(self.h, m._mv, mask, _p(out)))
+        return out
+
+    def matrix_summary(self, m, cells, feature_class=None, n_classes=1, cell_class_mask=None, reads=None, per_cell=False, n_features=None):
+        """the integers behind report_matrix's _report / _report_genome_agnostic_metrics on the RAW MatrixDev `m`.  cells: a CellCall,
+        the AdditionalCells of an EmptyDrops merge, or a device / numpy array of ascending columns.  feature_class u8[n_features]
+        (0xFF: in no class; None: every feature in class 0, n_features then comes from the argument or the key layout),
+        cell_class_mask u32 per listed cell (bit k: a cell of class k; None: of every class), reads = Context.reads_per_column (or a
+        numpy array per column), per_cell: keep counts_per_cell / genes_per_cell on the device -> MatrixSummary"""
+        if isinstance(cells, AdditionalCells):
+            cells = cells.call
+        if isinstance(cells, CellCall):
+            d_cols, n_cells = cells.cols, cells.n_cells
+        elif isinstance(cells, DeviceArray):
+            d_cols, n_cells = cells, cells.size
+        else:
+            h = np.ascontiguousarray(cells, dtype=np.uint64)
+            d_cols, n_cells = (self.upload(h) if len(h) else None), len(h)
+        if d_cols is not None and n_cells and d_cols.dtype != np.uint64:
+            raise TypeError("matrix_summary: the cell columns are u64 (as the cell call returns them)")
+        fc = None if feature_class is None else np.ascontiguousarray(feature_class, dtype=np.uint8)
+        if fc is not None:
+            n_features = len(fc)
+        elif n_features is None:
+            n_features = getattr(self, "n_features", None)
+            if n_features is None:
+                raise ValueError("matrix_summary: pass feature_class or n_features")
+        cm = None if cell_class_mask is None else np.ascontiguousarray(cell_class_mask, dtype=np.uint32)
+        if cm is not None and len(cm) != n_cells:
+            raise ValueError("matrix_summary: cell_class_mask has one entry per listed cell (%d)" % n_cells)
+        if reads is not None and not isinstance(reads, DeviceArray):
+            reads = self.upload(np.ascontiguousarray(reads, dtype=np.uint32))
+        if reads is not None and (reads.dtype != np.uint32 or reads.size != m.n_barcodes):
+            raise ValueError("matrix_summary: reads are u32 per column of the matrix")
+        per_f, ge2 = np.zeros(n_features, np.uint64), np.zeros(n_features, np.uint64)
+        structs = (_lib.MatrixSummaryClass * n_classes)()
+        r_all, r_union = C.c_uint64(), C.c_uint64()
+        cpc = gpc = None
+        if per_cell:
+            cpc, gpc = self.zeros((n_classes, n_cells), np.uint32), self.zeros((n_classes, n_cells), np.uint32)
+        self._check(self.L.crgpu_matrix_summary_dev(self.h, m._mv, n_features, n_classes, ptr(fc), _p(d_cols) if n_cells else None, n_cells, ptr(cm),
+                                                    _p(reads), ptr(per_f), ptr(ge2), structs, C.byref(r_all), C.byref(r_union), _p(cpc), _p(gpc)))
+        have = reads is not None
+        return MatrixSummary(self, list(structs), per_f, ge2, r_all.value if have else None, r_union.value if have else None, n_cells, cpc, gpc)
 
     def call_additional_cells(self, m, call, low, high, emptydrops_minimum_umis=500, num_sims=10000, max_adj_pvalue=0.01, seed=0,
                               feature_mask=None, sim_table=None, keep_sim_table=False, keep_profile=True):

@@ -871,6 +871,84 @@ int crgpu_rtl_occupancy_summary(const uint64_t *cells_per_gem_hist, uint32_t n_p
 int crgpu_rtl_remove_high_occupancy_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const uint64_t *d_cell_cols, uint64_t n_cells,
                                         uint32_t threshold, uint64_t **d_kept_cols_out, crgpu_rtl_high_occupancy *res);
 
+/* ---- the summary metrics of the filtered matrix ---------------------------------------------------------------------------------
+ * Replaces the matrix arithmetic of report_genomes -> _report / _report_genome_agnostic_metrics
+ * (lib/python/cellranger/rna/report_matrix.py:76-387): sum_masked / count_ge_masked (cellranger/sparse.py:36-168) of the views
+ * (feature mask x barcode mask) of the RAW matrix, and top_n (matrix.py:55-67), for ONE well.  A CLASS is one (feature type,
+ * genome) pair, as in crgpu_normalize_depth_args.  Every integer equals the reference's; the floats are computed from the
+ * integers by crgpu_matrix_summary_stats.
+ *   crgpu_matrix_summary_dev   m: the raw matrix (V < 2^32 - 1 columns).  n_classes 1 .. CRGPU_MS_MAX_CLASSES.  feature_class: host
+ *                              u8[n_features], NULL = every feature in class 0, CRGPU_MS_NO_CLASS = in no class, another value
+ *                              >= n_classes: CRGPU_EINVAL.  d_cell_cols: DEVICE u64[n_cells], strictly ascending positions in m (what
+ *                              crgpu_call_cells_ordmag_dev and the EmptyDrops merge return; out of range or not ascending:
+ *                              CRGPU_EINVAL; NULL with n_cells == 0 is allowed).  cell_class_mask: host u32[n_cells], bit k = a cell
+ *                              of class k, NULL = a cell of every class.  d_reads_per_col: device u32[V], nullable
+ *                              (crgpu_matrix_dev_reads_per_column).  A row >= n_features, or rows that do not ascend inside a
+ *                              column: CRGPU_EINVAL.  Outputs (caller-allocated, each nullable):
+ *       counts_per_feature_out     host u64[n_features]: the sum of row f over the cells of f's own class (filtered_mat.sum(axis=1));
+ *                                  0 for a feature in no class
+ *       cells_ge2_per_feature_out  host u64[n_features]: its entries >= 2 there (count_ge(axis=1, threshold=2))
+ *       classes_out                host crgpu_matrix_summary_class[n_classes]
+ *       reads_all_out / reads_union_out  the sum of d_reads_per_col over every column / over every listed cell (0 without reads)
+ *       d_counts_per_cell_out / d_genes_per_cell_out  device u32[n_classes * n_cells], row k = class k: the sum / the entries >= 1
+ *                                  of the cell over the features of class k, 0 where the cell is not of the class
+ *     A per-cell sum above 2^32 - 1 is CRGPU_ERANGE; every other sum is 64 bits wide.  A class with no cells has zeros and n_cells
+ *     0; an empty matrix or n_cells == 0 is no error.  The per-feature sums are collected in slices of the workgroups' LDS and
+ *     added up from a slab of plain stores; CRGPU_MS_LDS_FEATURES=<n> in the environment when the context is created (tests) fixes
+ *     the features per slice, 0 = counters in device memory.  No result depends on it.
+ *     Top features: by value descending, then by feature index ascending, among the features of the class (numpy's argpartition
+ *     leaves the choice among equal values at the boundary open; the multiset of values is the reference's).
+ *   crgpu_matrix_dev_reads_per_column  d_out[c] (device u32[V]) = the sum over the libraries l with bit l of lib_mask of VALID +
+ *                              CORRECTED of the barcode of column c: the `reads` column of crgpu_barcode_summary_row with the
+ *                              libraries of one library type added up.  CRGPU_ERANGE when a sum does not fit 32 bits, CRGPU_EINVAL
+ *                              for an empty mask, a library without a whitelist or beyond the key layout, a column whose rank is
+ *                              not on the whitelist.
+ *   crgpu_matrix_summary_stats host only, no context: the floats of _report from one class.  reads_cells / reads_all: the reads
+ *                              behind dupe_frac, reads_per_cell and reads_cum_frac (the class's own, or a caller's).  Every
+ *                              division follows robust_divide (tenkit/stats.py:25-32): NaN for a zero divisor.  mean = (double)sum
+ *                              / n; median and iqr from the six order statistics with numpy's linear rule (a + (b - a) t for t <
+ *                              0.5, else b - (b - a) (1 - t)): np.mean / np.median / np.percentile bit for bit while sum < 2^53;
+ *                              std = sqrt((n sumsq - sum^2) / n^2) with the numerator exact in 128 bits (within 4 ulp of the
+ *                              exact value; np.std's own pairwise sum is NOT reproduced bit for bit); cv = std / mean.
+ * NOT covered: the per-genome conf_mapped_barcoded split of barcode_summary.h5, per-sample subsets (pass a column list),
+ * filtered_reads_per_filtered_bc, the H5 / JSON writers. */
+#define CRGPU_MS_MAX_CLASSES 32
+#define CRGPU_MS_NO_CLASS 255
+#define CRGPU_MS_TOP_N 5 /* TOP_N */
+struct crgpu_matrix_summary_class {
+    uint64_t n_features_class, n_cells;
+    uint64_t raw_total_counts;            /* the class's features, ALL columns (matrix.sum()) */
+    uint64_t union_total_counts, union_nnz; /* the class's features, every listed cell */
+    uint64_t cells_total_counts, cells_nnz; /* ... the class's own cells; entries >= 1 */
+    uint64_t genes_detected;              /* features with a non-zero counts_per_feature */
+    uint64_t counts_sum, counts_sumsq_hi, counts_sumsq_lo; /* of counts_per_cell over the class's own cells */
+    uint64_t genes_sum, genes_sumsq_hi, genes_sumsq_lo;    /* of genes_per_cell (entries >= 1) */
+    uint64_t reads_cells;                 /* d_reads_per_col over the class's own cells */
+    uint64_t top_counts_value[5], top_cells_value[5];
+    uint32_t counts_q[6], genes_q[6];     /* x[floor((n-1)q)], x[min(floor((n-1)q) + 1, n-1)] for q = 0.25, 0.5, 0.75 of the sorted values */
+    uint32_t top_counts_feature[5], top_cells_feature[5];
+    uint32_t n_top, reserved;             /* min(5, n_features_class) */
+};
+typedef struct crgpu_matrix_summary_class crgpu_matrix_summary_class;
+struct crgpu_matrix_summary_floats {
+    double counts_mean, counts_median, counts_cv, counts_iqr, counts_std;
+    double genes_mean, genes_median, genes_cv, genes_iqr, genes_std;
+    double density;        /* cells_nnz / (n_features_class * n_cells) */
+    double cum_frac;       /* cells_total_counts / raw_total_counts */
+    double dupe_frac;      /* 1 - cells_total_counts / reads_cells */
+    double reads_per_cell; /* reads_cells / n_cells */
+    double reads_cum_frac; /* reads_cells / reads_all */
+};
+typedef struct crgpu_matrix_summary_floats crgpu_matrix_summary_floats;
+int crgpu_matrix_summary_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, uint32_t n_features, uint32_t n_classes,
+                             const uint8_t *feature_class, const uint64_t *d_cell_cols, uint64_t n_cells,
+                             const uint32_t *cell_class_mask, const uint32_t *d_reads_per_col, uint64_t *counts_per_feature_out,
+                             uint64_t *cells_ge2_per_feature_out, crgpu_matrix_summary_class *classes_out, uint64_t *reads_all_out,
+                             uint64_t *reads_union_out, uint32_t *d_counts_per_cell_out, uint32_t *d_genes_per_cell_out);
+int crgpu_matrix_dev_reads_per_column(crgpu_ctx *ctx, const crgpu_matrix_dev *m, uint32_t lib_mask, uint32_t *d_out);
+int crgpu_matrix_summary_stats(const crgpu_matrix_summary_class *cls, uint64_t reads_cells, uint64_t reads_all,
+                               crgpu_matrix_summary_floats *out);
+
 /* ---- cell calling: the non-ambient ("EmptyDrops") barcodes behind the initial call ---------------------------------------------
  * Replaces find_nonambient_barcodes (lib/python/cellranger/cell_calling.py:144-263) as call_additional_cells runs it
  * (cell_calling_helpers.py:575-668) for ONE genome / GEM group; the caller loops and passes a feature mask.

@@ -1057,4 +1057,61 @@ inline HighOccupancyRemoval remove_high_occupancy_gems(Context &ctx, const crgpu
     return out;
 }
 
+// ---- the summary metrics of the filtered matrix (report_matrix.py: _report / _report_genome_agnostic_metrics) ------------------------
+static_assert(sizeof(crgpu_matrix_summary_class) == 296, "crgpu_matrix_summary_class changed: bump CRGPU_ABI_VERSION and every binding");
+static_assert(sizeof(crgpu_matrix_summary_floats) == 120, "crgpu_matrix_summary_floats changed: bump CRGPU_ABI_VERSION and every binding");
+struct MatrixSummary {
+    std::vector<uint64_t> counts_per_feature, cells_ge2_per_feature;  // [n_features], over the cells of the feature's own class
+    std::vector<crgpu_matrix_summary_class> classes;                  // [n_classes]
+    uint64_t reads_all = 0, reads_union = 0;                          // 0 without a read table
+    std::vector<uint32_t> counts_per_cell, genes_per_cell;            // [n_classes * n_cells] when asked for
+};
+/// the counted reads (VALID + CORRECTED) of every column, the libraries of lib_mask added up
+inline std::vector<uint32_t> reads_per_column(Context &ctx, const crgpu_matrix_dev *raw, uint32_t lib_mask = 1u) {
+    std::vector<uint32_t> out(raw->n_barcodes);
+    void *d = nullptr;
+    ctx.check(crgpu_malloc(ctx.get(), &d, out.empty() ? 1 : out.size() * sizeof(uint32_t)));
+    int rc = crgpu_matrix_dev_reads_per_column(ctx.get(), raw, lib_mask, (uint32_t *)d);
+    if (rc == CRGPU_OK && !out.empty()) rc = crgpu_memcpy_d2h(ctx.get(), out.data(), d, out.size() * sizeof(uint32_t));
+    crgpu_free(ctx.get(), d);
+    ctx.check(rc);
+    return out;
+}
+/// crgpu_matrix_summary_dev on the raw matrix: cells = the ascending called columns; feature_class empty = every feature in class 0
+/// (n_features then counts); cell_class_mask empty = a cell of every class; reads empty = no read table
+inline MatrixSummary matrix_summary(Context &ctx, const crgpu_matrix_dev *raw, const std::vector<uint64_t> &cells, uint32_t n_features,
+                                    const std::vector<uint8_t> &feature_class = {}, uint32_t n_classes = 1,
+                                    const std::vector<uint32_t> &cell_class_mask = {}, const std::vector<uint32_t> &reads = {},
+                                    bool per_cell = false) {
+    if ((!feature_class.empty() && feature_class.size() != n_features) || (!cell_class_mask.empty() && cell_class_mask.size() != cells.size()) ||
+        (!reads.empty() && reads.size() != raw->n_barcodes) || n_classes < 1 || n_classes > CRGPU_MS_MAX_CLASSES)
+        throw Error(CRGPU_EINVAL, "matrix_summary: shapes");
+    MatrixSummary out;
+    out.counts_per_feature.assign(n_features, 0), out.cells_ge2_per_feature.assign(n_features, 0);
+    out.classes.resize(n_classes);
+    detail::DeviceCols d_cells(ctx, cells);
+    detail::DeviceCopy<uint32_t> d_reads(ctx, reads);
+    const size_t n_pc = per_cell ? (size_t)n_classes * cells.size() : 0;
+    detail::DeviceCopy<uint32_t> d_cpc(ctx, std::vector<uint32_t>(n_pc, 0)), d_gpc(ctx, std::vector<uint32_t>(n_pc, 0));
+    ctx.check(crgpu_matrix_summary_dev(ctx.get(), raw, n_features, n_classes, feature_class.empty() ? nullptr : feature_class.data(), d_cells.get(),
+                                       cells.size(), cell_class_mask.empty() ? nullptr : cell_class_mask.data(), reads.empty() ? nullptr : d_reads.get(),
+                                       out.counts_per_feature.data(), out.cells_ge2_per_feature.data(), out.classes.data(), &out.reads_all,
+                                       &out.reads_union, per_cell ? (uint32_t *)d_cpc.d : nullptr, per_cell ? (uint32_t *)d_gpc.d : nullptr));
+    if (n_pc) {
+        ctx.check(detail::fetch(ctx, out.counts_per_cell, d_cpc.get(), n_pc));
+        ctx.check(detail::fetch(ctx, out.genes_per_cell, d_gpc.get(), n_pc));
+    }
+    return out;
+}
+/// the floats of _report from the integers of one class; reads_cells / reads_all: the class's own and the well's by default
+inline crgpu_matrix_summary_floats matrix_summary_stats(const crgpu_matrix_summary_class &c, uint64_t reads_cells, uint64_t reads_all) {
+    crgpu_matrix_summary_floats out;
+    const int rc = crgpu_matrix_summary_stats(&c, reads_cells, reads_all, &out);
+    if (rc != CRGPU_OK) throw Error(rc, crgpu_last_error(nullptr));
+    return out;
+}
+inline crgpu_matrix_summary_floats matrix_summary_stats(const MatrixSummary &s, uint32_t k) {
+    return matrix_summary_stats(s.classes.at(k), s.classes.at(k).reads_cells, s.reads_all);
+}
+
 }  // namespace crgpu
