@@ -260,7 +260,15 @@ class MatrixSummaryFloats(C.Structure):
                                           "reads_cum_frac")]
 
 
+class AggregatesInfo(C.Structure):
+    """crgpu_aggregates_info"""
+    _fields_ = [(n, C.c_uint32) for n in ("n_antibodies", "n_signal", "top_k", "n_candidates", "min_antibodies", "n_aggregates", "n_slices",
+                                          "rows_per_slice")] + [("in_lds", C.c_int32), ("reserved", C.c_uint32), ("rank_ms", C.c_double)]
+
+
 MS_MAX_CLASSES, MS_NO_CLASS, MS_TOP_N = 32, 255, 5
+AGG_KIND_OTHER, AGG_KIND_ANTIBODY, AGG_KIND_ANTIGEN = 0, 1, 2
+AGG_COUNTS, AGG_HIGHLY_CORRECTED, AGG_ANTIGEN = 1, 2, 4
 RTL_MAX_TAGS, RTL_MAX_PROBES, RTL_MAX_TYPES = 64, 256, 8
 RTL_KIND_RTL, RTL_KIND_ANTIBODY, RTL_KIND_OTHER = 0, 1, 2
 RTL_NONE = 0xFF
@@ -403,6 +411,18 @@ SYMBOLS = {
                                       C.POINTER(_u64), C.POINTER(_u64), _vp, _vp]),
     "crgpu_matrix_dev_reads_per_column": (_i, [_vp, C.POINTER(MatrixDevView), _u32, _vp]),
     "crgpu_matrix_summary_stats": (_i, [C.POINTER(MatrixSummaryClass), _u64, _u64, C.POINTER(MatrixSummaryFloats)]),
+    "crgpu_aggregate_min_antibodies": (_i, [_u32, C.POINTER(_u32)]),
+    "crgpu_antigen_outlier_threshold": (_i, [_vp, _u32, C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_dbl)]),
+    "crgpu_aggregates_by_counts_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, _u32, _vp, _vp, _u32, C.POINTER(_u32),
+                                            C.POINTER(AggregatesInfo)]),
+    "crgpu_aggregates_highly_corrected_dev": (_i, [_vp, _vp, _vp, _u64, _vp, C.POINTER(_u64)]),
+    "crgpu_counts_corrected_reads_per_column": (_i, [_vp, _vp, C.POINTER(MatrixDevView), _u32, _vp]),
+    "crgpu_aggregates_antigen_outliers_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, _vp, _vp, _u32, C.POINTER(_u32), C.POINTER(_dbl)]),
+    "crgpu_aggregates_partition_dev": (_i, [_vp, _vp, _u64, C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_vp), C.POINTER(_u64)]),
+    "crgpu_take_columns_dev": (_i, [_vp, _vp, _u32, _u64, _vp, _u64, _vp]),
+    "crgpu_sum_u32_dev": (_i, [_vp, _vp, _u64, C.POINTER(_u64)]),
+    "crgpu_filter_cells_min_umis_dev": (_i, [_vp, _vp, _u64, _vp, _u64, _u64, C.POINTER(_vp), C.POINTER(_u64)]),
+    "crgpu_filter_cells_mito_dev": (_i, [_vp, _vp, _vp, _u64, _vp, _u64, _dbl, C.POINTER(_vp), C.POINTER(_u64), C.POINTER(_vp), C.POINTER(_u64)]),
     "crgpu_matrix_dev_download": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _vp, _vp, _vp]),
     "crgpu_count": (_i, [_vp, C.POINTER(Records), _u32, C.POINTER(C.POINTER(MatrixView))]),
     "crgpu_set_feature_pattern": (_i, [_vp, _i, C.c_char_p, _u32, _u32, _vp, _vp]),

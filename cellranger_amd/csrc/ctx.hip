@@ -219,6 +219,17 @@ const std::vector<AbiStruct> &abi_table() {
               ABI_F(crgpu_matrix_summary_floats, dupe_frac),
               ABI_F(crgpu_matrix_summary_floats, reads_per_cell),
               ABI_F(crgpu_matrix_summary_floats, reads_cum_frac)),
+        ABI_S(crgpu_aggregates_info, ABI_F(crgpu_aggregates_info, n_antibodies),
+              ABI_F(crgpu_aggregates_info, n_signal),
+              ABI_F(crgpu_aggregates_info, top_k),
+              ABI_F(crgpu_aggregates_info, n_candidates),
+              ABI_F(crgpu_aggregates_info, min_antibodies),
+              ABI_F(crgpu_aggregates_info, n_aggregates),
+              ABI_F(crgpu_aggregates_info, n_slices),
+              ABI_F(crgpu_aggregates_info, rows_per_slice),
+              ABI_F(crgpu_aggregates_info, in_lds),
+              ABI_F(crgpu_aggregates_info, reserved),
+              ABI_F(crgpu_aggregates_info, rank_ms)),
     };
     return t;
 }
@@ -303,6 +314,7 @@ extern "C" int crgpu_create(crgpu_ctx **out, int device_id, int n_ranks, int ran
     if (const char *b = getenv("CRGPU_ORDMAG_BATCH")) ctx->ordmag_batch = (uint32_t)strtoul(b, nullptr, 10);  // tests: small batches of the cell call
     if (const char *f = getenv("CRGPU_ED_LDS_FEATURES")) ctx->ed_lds_features = (uint32_t)strtoul(f, nullptr, 10);  // tests: 0 = counters in global memory
     if (const char *f = getenv("CRGPU_MS_LDS_FEATURES")) ctx->ms_lds_features = (uint32_t)strtoul(f, nullptr, 10);  // tests: several slices on a small matrix; 0 = counters in device memory
+    if (const char *r = getenv("CRGPU_AGG_LDS_ROWS")) ctx->agg_lds_rows = (uint32_t)strtoul(r, nullptr, 10);  // tests: several slices of signal rows; 0 = the rank table in device memory
     if (const char *v = getenv("CRGPU_SS_WAVE_MIN")) ctx->ss_wave_min = (uint32_t)strtoul(v, nullptr, 10);  // tests: reach the wave path of the subsampling draw
     if (const char *v = getenv("CRGPU_SS_WG_MIN")) ctx->ss_wg_min = (uint32_t)strtoul(v, nullptr, 10);      // ... and its workgroup path
     if (const char *v = getenv("CRGPU_SS_TASK_BATCH")) ctx->ss_task_batch = (uint32_t)strtoul(v, nullptr, 10);  // tests: small task batches

@@ -2978,3 +2978,4 @@ extern "C" int crgpu_trim_molecule_barcodes_dev(crgpu_ctx *ctx, uint64_t *d_barc
 #include "multigenome.h"
 #include "rtl_tags.h"
 #include "matrix_summary.h"
+#include "aggregates.h"

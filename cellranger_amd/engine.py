@@ -703,6 +703,56 @@ def matrix_summary_metrics(summary, k, genome, feature_ids, total_reads=None, co
     return out
 
 
+class Aggregates:
+    """Result of Context.remove_aggregates: removed_cols (numpy u64, ascending) with reasons (numpy u8 of _lib.AGG_COUNTS |
+    AGG_HIGHLY_CORRECTED | AGG_ANTIGEN per removed column), kept = the other columns (DeviceArray of u64, n_kept of them: what
+    crgpu_select_barcodes_cols_dev takes), info = crgpu_aggregates_info as a dict, antigen_threshold (f64, None when no antigen
+    feature), libraries = {library type: dict(number_aggregate_GEMs, reads_removed, reads_total: Python ints, the reads None
+    when no read table was passed; cols, reads, umis, corrected_reads, frac_corrected_reads, frac_total_reads: numpy arrays over the
+    columns removed for that library type)}."""
+
+    def __init__(self, removed_cols, reasons, kept, n_kept, info, antigen_threshold, libraries, disabled):
+        self.removed_cols, self.reasons, self.kept, self.n_kept = removed_cols, reasons, kept, n_kept
+        self.info, self.antigen_threshold, self.libraries, self.disabled = info, antigen_threshold, libraries, disabled
+
+    def cols_with(self, bits):
+        return self.removed_cols[(self.reasons & bits) != 0]
+
+
+AGG_LIBRARY_PREFIX = {"Antibody Capture": "ANTIBODY_", "Antigen Capture": "ANTIGEN_"}  # get_library_type_metric_prefix
+
+
+def aggregate_min_antibodies(n_signal):
+    """crgpu_aggregate_min_antibodies: int(np.round(n_signal * _calculate_fraction_to_use(n_signal)))"""
+    out = C.c_uint32()
+    rc = _lib.load().crgpu_aggregate_min_antibodies(int(n_signal), C.byref(out))
+    if rc != 0:
+        raise CrgpuError(rc, _lib.load().crgpu_last_error(None).decode())
+    return out.value
+
+
+def antigen_outlier_threshold(top_counts):
+    """crgpu_antigen_outlier_threshold: (q1, q3, q3 + (q3 - q1) * 3) of the u32 counts, np.quantile's linear rule"""
+    x = np.ascontiguousarray(top_counts, dtype=np.uint32)
+    q1, q3, t = C.c_double(), C.c_double(), C.c_double()
+    rc = _lib.load().crgpu_antigen_outlier_threshold(ptr(x), len(x), C.byref(q1), C.byref(q3), C.byref(t))
+    if rc != 0:
+        raise CrgpuError(rc, _lib.load().crgpu_last_error(None).decode())
+    return q1.value, q3.value, t.value
+
+
+def aggregate_metrics(agg):
+    """the metrics of remove_antibody_antigen_aggregates (cell_calling_helpers.py:206-210) under the reference's names.
+    <prefix>reads_lost_to_aggregate_GEMs is reads_removed / reads_total as ONE division (the reference sums per-barcode quotients
+    in set order); None without a read table, NaN for a library type without reads"""
+    out = {}
+    for lib, d in agg.libraries.items():
+        prefix = AGG_LIBRARY_PREFIX[lib]
+        out[prefix + "number_aggregate_GEMs"] = d["number_aggregate_GEMs"]
+        out[prefix + "reads_lost_to_aggregate_GEMs"] = None if d["reads_total"] is None else _robust_divide(d["reads_removed"], d["reads_total"])
+    return out
+
+
 def ordmag_candidates(max_expected_cells=1 << 18):
     """the recovered-cells grid of estimate_recovered_cells_ordmag (cell_calling_helpers.py:879-880); host only"""
     out, n = np.zeros(2000, np.int64), C.c_uint32()
@@ -943,6 +993,13 @@ class Counts:
             self.ctx._check(L.crgpu_counts_barcode_summary(h, self.h, rank_lo, rank_hi, ptr(rows), n.value, C.byref(n)))
         return rows
 
+    def corrected_reads_per_column(self, m, libs=0):
+        """the umi_corrected_reads (barcode_summary) of every column of the MatrixDev `m`, the libraries `libs` (an index or several:
+        the libraries of one library type) added up -> DeviceArray of u32; the counterpart of Context.reads_per_column"""
+        out = self.ctx.empty(m.n_barcodes, np.uint32)
+        self.ctx._check(self.ctx.L.crgpu_counts_corrected_reads_per_column(self.ctx.h, self.h, m._mv, _lib_mask("corrected_reads_per_column", libs), _p(out)))
+        return out
+
     def free(self):
         if self.h is not None and self.ctx.h:
             self.ctx.L.crgpu_counts_free(self.ctx.h, self.h)
@@ -953,6 +1010,15 @@ class Counts:
             self.free()
         except Exception:
             pass
+
+
+def _lib_mask(who, libs):
+    mask = 0
+    for l in ([libs] if np.isscalar(libs) else libs):
+        if not 0 <= int(l) < 32:
+            raise ValueError("%s: library %r" % (who, l))
+        mask |= 1 << int(l)
+    return mask
 
 
 def get_unique_id():
@@ -1488,6 +1554,129 @@ class Context:
         kept = DeviceArray(self, int(res.n_kept), np.uint64, adopt=out.value)
         d = {name: getattr(res, name) for name, _ in _lib.RtlHighOccupancy._fields_ if name != "reserved"}
         return CellCall(self, kept, int(res.n_kept), dict(call.metrics), m), d
+
+    # ---- protein aggregates, the closing filters of a cell call ------------------------------------------
+    def _per_column(self, who, x, V):
+        """a u32 value per column as a DeviceArray (a numpy array is uploaded)"""
+        d = x if isinstance(x, DeviceArray) else self.upload(np.ascontiguousarray(x, dtype=np.uint32))
+        if d.dtype != np.uint32 or d.size != V:
+            raise ValueError("%s: a u32 value per column of the matrix (%d)" % (who, V))
+        return d
+
+    def take_columns(self, src, cols, n=None):
+        """src[cols] on the device: src a DeviceArray of u8 or u32 per column, cols a DeviceArray / numpy array of u64 -> numpy"""
+        d_cols = cols if isinstance(cols, DeviceArray) else self.upload(np.ascontiguousarray(cols, dtype=np.uint64))
+        n = d_cols.size if n is None else int(n)
+        out = self.empty(n, src.dtype)
+        self._check(self.L.crgpu_take_columns_dev(self.h, _p(src), src.dtype.itemsize, src.size, _p(d_cols), n, _p(out)))
+        return out.to_host(n)
+
+    def sum_u32(self, d):
+        out = C.c_uint64()
+        self._check(self.L.crgpu_sum_u32_dev(self.h, _p(d), d.size, C.byref(out)))
+        return out.value
+
+    def aggregates_by_counts(self, m, feature_kind, num_probe_barcodes=None, reasons=None):
+        """detect_aggregate_barcodes (analysis.py:133-185) on the raw MatrixDev `m`: feature_kind u8[n_features] of _lib.AGG_KIND_*,
+        reasons: a DeviceArray of u8 per column that gets _lib.AGG_COUNTS -> (numpy u64 of the columns, ascending; info dict)"""
+        kind = np.ascontiguousarray(feature_kind, dtype=np.uint8)
+        K = 25 * max(int(num_probe_barcodes or 0), 1)
+        cols, n, info = np.zeros(K, np.uint64), C.c_uint32(), _lib.AggregatesInfo()
+        self._check(self.L.crgpu_aggregates_by_counts_dev(self.h, m._mv, ptr(kind), len(kind), int(num_probe_barcodes or 0), _p(reasons), ptr(cols), K,
+                                                          C.byref(n), C.byref(info)))
+        return cols[:n.value], {name: getattr(info, name) for name, _ in _lib.AggregatesInfo._fields_ if name != "reserved"}
+
+    def highly_corrected(self, reads, corrected_reads, reasons):
+        """detect_highly_corrected_bcs (analysis.py:91-99) over two DeviceArrays of u32 per column (Context.reads_per_column,
+        Counts.corrected_reads_per_column): marks _lib.AGG_HIGHLY_CORRECTED in `reasons` -> the number of columns marked"""
+        n = C.c_uint64()
+        if reads.size != corrected_reads.size or reads.size != reasons.size:
+            raise ValueError("highly_corrected: one entry per column in every array")
+        self._check(self.L.crgpu_aggregates_highly_corrected_dev(self.h, _p(reads), _p(corrected_reads), reads.size, _p(reasons), C.byref(n)))
+        return n.value
+
+    def antigen_outliers(self, m, feature_kind, reasons=None):
+        """detect_outlier_umis_bcs (analysis.py:77-88) -> (numpy u64 of the columns, ascending; the threshold)"""
+        kind = np.ascontiguousarray(feature_kind, dtype=np.uint8)
+        cols, n, thr = np.zeros(100, np.uint64), C.c_uint32(), C.c_double()
+        self._check(self.L.crgpu_aggregates_antigen_outliers_dev(self.h, m._mv, ptr(kind), len(kind), _p(reasons), ptr(cols), 100, C.byref(n),
+                                                                 C.byref(thr)))
+        return cols[:n.value], thr.value
+
+    def remove_aggregates(self, m, feature_kind, num_probe_barcodes=None, reads=None, corrected_reads=None, disable=False):
+        """remove_antibody_antigen_aggregates (cell_calling_helpers.py:214-270) on the raw MatrixDev `m`.  feature_kind u8[n_features]
+        of _lib.AGG_KIND_*; a library type takes part when it has a feature.  reads / corrected_reads: {library type: u32 per column}
+        (DeviceArrays of Context.reads_per_column / Counts.corrected_reads_per_column, or numpy arrays); the highly corrected
+        barcodes need both for "Antibody Capture".  disable: detect and report, return `m` itself (disable_ab_aggregate_detection)
+        -> (MatrixDev, Aggregates)"""
+        kind = np.ascontiguousarray(feature_kind, dtype=np.uint8)
+        V = m.n_barcodes
+        reads = {k: self._per_column("remove_aggregates", v, V) for k, v in (reads or {}).items()}
+        corrected = {k: self._per_column("remove_aggregates", v, V) for k, v in (corrected_reads or {}).items()}
+        reasons = self.zeros(V, np.uint8)
+        info, thr, bits = None, None, {}
+        AB, AG = "Antibody Capture", "Antigen Capture"
+        if (kind == _lib.AGG_KIND_ANTIBODY).any():
+            bits[AB] = (_lib.AGG_COUNTS | _lib.AGG_HIGHLY_CORRECTED, _lib.AGG_KIND_ANTIBODY)
+            if AB in reads and AB in corrected:
+                self.highly_corrected(reads[AB], corrected[AB], reasons)
+            _, info = self.aggregates_by_counts(m, kind, num_probe_barcodes, reasons)
+        if (kind == _lib.AGG_KIND_ANTIGEN).any():
+            bits[AG] = (_lib.AGG_ANTIGEN, _lib.AGG_KIND_ANTIGEN)
+            _, thr = self.antigen_outliers(m, kind, reasons)
+        kept, n_kept, rem, n_rem = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
+        self._check(self.L.crgpu_aggregates_partition_dev(self.h, _p(reasons), V, C.byref(kept), C.byref(n_kept), C.byref(rem), C.byref(n_rem)))
+        d_kept = DeviceArray(self, n_kept.value, np.uint64, adopt=kept.value)
+        d_rem = DeviceArray(self, n_rem.value, np.uint64, adopt=rem.value)
+        removed = d_rem.to_host(n_rem.value)
+        why = self.take_columns(reasons, d_rem, n_rem.value)
+        libraries = {}
+        for lib, (mask, k) in bits.items():
+            cols = removed[(why & mask) != 0]
+            d = {"number_aggregate_GEMs": int(len(cols)), "cols": cols, "reads_removed": None, "reads_total": None}
+            d["umis"] = self.take_columns(self.column_sums(m, kind == k), cols)
+            if lib in reads:
+                d["reads"] = self.take_columns(reads[lib], cols)
+                d["reads_removed"], d["reads_total"] = int(d["reads"].sum(dtype=np.uint64)), self.sum_u32(reads[lib])
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    d["frac_total_reads"] = d["reads"].astype(np.float64) / np.float64(d["reads_total"])
+                    if lib in corrected:
+                        d["corrected_reads"] = self.take_columns(corrected[lib], cols)
+                        d["frac_corrected_reads"] = d["corrected_reads"].astype(np.float64) / d["reads"].astype(np.float64)
+            libraries[lib] = d
+        agg = Aggregates(removed, why, d_kept, n_kept.value, info, thr, libraries, bool(disable))
+        if disable:
+            return m, agg
+        mv = C.POINTER(_lib.MatrixDevView)()
+        self._check(self.L.crgpu_select_barcodes_cols_dev(self.h, m._mv, _p(d_kept), n_kept.value, C.byref(mv)))
+        return MatrixDev(self, mv), agg
+
+    def apply_minimum_umis(self, call, umis, minimum_umis):
+        """apply_global_minimum_umis_threshold (cell_calling_helpers.py:749-785) of one GEM group and genome: the cells of the
+        CellCall whose entry of `umis` (u32 per column of the matrix: Context.column_sums with the feature types' mask) is >=
+        minimum_umis, in their order -> CellCall"""
+        V = umis.size if isinstance(umis, DeviceArray) else len(umis)
+        d = self._per_column("apply_minimum_umis", umis, V)
+        out, n = C.c_void_p(), C.c_uint64()
+        self._check(self.L.crgpu_filter_cells_min_umis_dev(self.h, _p(d), V, _p(call.cols), call.n_cells, int(minimum_umis), C.byref(out), C.byref(n)))
+        return CellCall(self, DeviceArray(self, n.value, np.uint64, adopt=out.value), n.value, dict(call.metrics), call._matrix)
+
+    def apply_mito_threshold(self, call, mito_umis, total_umis, max_mito_percent):
+        """apply_mitochondrial_threshold (cell_calling_helpers.py:671-746) of one GEM group and genome: mito_umis / total_umis = u32
+        per column of the matrix (Context.column_sums over the mitochondrial genes / over all Gene Expression rows of the genome).
+        Cells with 100.0 * mito / total > max_mito_percent leave (0 / 0 is NaN and stays)
+        -> (CellCall, dict(cols, total_umis, mt_pct: numpy arrays over the removed cells, threshold))"""
+        V = total_umis.size if isinstance(total_umis, DeviceArray) else len(total_umis)
+        d_t, d_m = self._per_column("apply_mito_threshold", total_umis, V), self._per_column("apply_mito_threshold", mito_umis, V)
+        kept, n_kept, rem, n_rem = C.c_void_p(), C.c_uint64(), C.c_void_p(), C.c_uint64()
+        self._check(self.L.crgpu_filter_cells_mito_dev(self.h, _p(d_m), _p(d_t), V, _p(call.cols), call.n_cells, float(max_mito_percent), C.byref(kept),
+                                                       C.byref(n_kept), C.byref(rem), C.byref(n_rem)))
+        d_rem = DeviceArray(self, n_rem.value, np.uint64, adopt=rem.value)
+        tot, mt = self.take_columns(d_t, d_rem, n_rem.value), self.take_columns(d_m, d_rem, n_rem.value)
+        with np.errstate(divide="ignore", invalid="ignore"):      # (a removed cell has a percentage: total 0 only with mito > 0, inf)
+            pct = 100.0 * mt.astype(np.float64) / tot.astype(np.float64)      # the device's own expression, f64 and unfused on both sides
+        summary = {"cols": d_rem.to_host(n_rem.value), "total_umis": tot, "mt_pct": pct, "threshold": float(max_mito_percent)}
+        return CellCall(self, DeviceArray(self, n_kept.value, np.uint64, adopt=kept.value), n_kept.value, dict(call.metrics), call._matrix), summary
 
     # ---- the summary metrics of the filtered matrix ---------------------------------------------------
     def reads_per_column(self, m, libs=0):

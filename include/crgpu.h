@@ -949,6 +949,92 @@ int crgpu_matrix_dev_reads_per_column(crgpu_ctx *ctx, const crgpu_matrix_dev *m,
 int crgpu_matrix_summary_stats(const crgpu_matrix_summary_class *cls, uint64_t reads_cells, uint64_t reads_all,
                                crgpu_matrix_summary_floats *out);
 
+/* ---- protein aggregates of an antibody / antigen well, and the closing filters of a cell call -----------------------------------
+ * Replaces remove_antibody_antigen_aggregates (lib/python/cellranger/cell_calling_helpers.py:188-270) with
+ * detect_aggregate_barcodes, detect_highly_corrected_bcs, detect_outlier_umis_bcs (cellranger/feature/antibody/analysis.py:77-185),
+ * which FILTER_BARCODES runs on the RAW matrix before the cell call, and apply_mitochondrial_threshold /
+ * apply_global_minimum_umis_threshold (cell_calling_helpers.py:671-785), which close it.  The three detections OR their bit
+ * (CRGPU_AGG_*) into a caller-owned DEVICE u8[V] of reasons (zeroed by the caller); crgpu_aggregates_partition_dev turns it into
+ * the removed and the kept columns, and crgpu_select_barcodes_cols_dev of the kept ones is the cleaned matrix.
+ * ONE ORDER: wherever "the top n" is taken, the columns are ordered as pairs (value, column) ascending and the top n are the n
+ * largest pairs: np.argsort(x, kind="stable")[-n:].  The reference sorts with numpy's default (unstable) sort, which leaves the
+ * choice among equal values at the n-th place open; its np.argsort(-counts)[:100] of the antigen step is replaced by the same rule.
+ *   crgpu_aggregate_min_antibodies  host, no context: int(np.round(n_signal * frac)), frac = 0.6 for n_signal > 26, else
+ *                              -0.02 * n_signal + 1.1 (_calculate_fraction_to_use), f64, half to even; defined for every n_signal.
+ *   crgpu_antigen_outlier_threshold host, no context: q1, q3 = np.quantile(x, 0.25 / 0.75) of the n >= 1 counts (any order; numpy's
+ *                              linear rule, bit for bit) and threshold = q3 + (q3 - q1) * 3.  q1_out / q3_out nullable.
+ *   crgpu_aggregates_by_counts_dev  detect_aggregate_barcodes.  m: the raw matrix (V < 2^32 - 1 columns, rows strictly ascending
+ *                              inside a column and < n_features, else CRGPU_EINVAL).  feature_kind: host u8[n_features],
+ *                              CRGPU_AGG_KIND_* (another value: CRGPU_EINVAL); at most 4096 antibody features (CRGPU_ERANGE).
+ *                              num_probe_barcodes 0 counts as 1, at most 40 (CRGPU_ERANGE); K = 25 * num_probe_barcodes.  Signal
+ *                              antibodies: antibody rows whose sum over all columns is >= 1000; fewer than 5 of them: no column.
+ *                              Candidates: the top min(K, V) columns by their sum over the signal rows.  A candidate is an
+ *                              aggregate when, for at least crgpu_aggregate_min_antibodies(n_signal) signal rows, it is among the
+ *                              top K columns of the row (implicit zeros take part).  cols_out: host u64[cap], the columns found,
+ *                              ascending (at most K; nullable; more than cap: CRGPU_ERANGE with *n_cols_out set).  d_reason_inout
+ *                              nullable.  info nullable.  The per-row places are counted in ONE pass over the signal rows' entries,
+ *                              the candidates' sorted pairs in the workgroups' LDS when they fit it, else in device memory;
+ *                              CRGPU_AGG_LDS_ROWS=<n> in the environment when the context is created (tests, A/B) asks for LDS
+ *                              slices of at most n signal rows, 0 = the table in device memory.  No result depends on it.
+ *   crgpu_aggregates_highly_corrected_dev  detect_highly_corrected_bcs over two DEVICE u32[V]: column c is marked when d_reads[c] >
+ *                              10000 and 2 * d_corrected_reads[c] > d_reads[c] (== corrected / reads > 0.5 in f64).
+ *   crgpu_counts_corrected_reads_per_column  d_out[c] (device u32[V]) = the umi_corrected_reads of crgpu_barcode_summary_row of the
+ *                              barcode of column c of m, the libraries with a bit in lib_mask added up: the counterpart of
+ *                              crgpu_matrix_dev_reads_per_column.  CRGPU_ESTATE when the counts carry no corrected-read table (as
+ *                              crgpu_counts_barcode_summary), CRGPU_EINVAL for an empty mask or a library beyond the key layout.
+ *   crgpu_aggregates_antigen_outliers_dev  detect_outlier_umis_bcs: the top min(100, V) columns by their sum over the antigen
+ *                              rows, crgpu_antigen_outlier_threshold of their sums (*threshold_out, NaN without a column); below
+ *                              1000 no column, else those of the top with a sum >= threshold, ascending.
+ *   crgpu_aggregates_partition_dev  the columns with a zero reason (kept) and the others (removed), each an ascending DEVICE u64 list
+ *                              of the caller's (crgpu_free), never NULL on success.
+ *   crgpu_take_columns_dev     d_out[i] = d_src[d_cols[i]] for elements of 1 or 4 bytes (the reasons, reads, UMIs of the removed
+ *                              columns); a column >= V: CRGPU_EINVAL.     crgpu_sum_u32_dev: the u64 sum of a device u32 array.
+ *   crgpu_filter_cells_min_umis_dev  the cells c of the list (DEVICE u64, strictly ascending, < V, as the cell call returns it; else
+ *                              CRGPU_EINVAL) with d_umis_per_col[c] >= minimum_umis, in the order of the list.
+ *   crgpu_filter_cells_mito_dev  kept: the cells with !(100.0 * mito / total > max_mito_percent) in f64 (0 / 0 is NaN and stays);
+ *                              removed: the others.  Both lists are the caller's (crgpu_free), in the order of the list.
+ * NOT covered: aggregate_barcodes.csv (pandas' float formatting), reads_lost_to_aggregate_GEMs as the reference's sum of per-barcode
+ * quotients (reads_removed / reads_total of the integers is reported as ONE division), remove_cells_with_zero_targeted_counts. */
+#define CRGPU_AGG_KIND_OTHER 0
+#define CRGPU_AGG_KIND_ANTIBODY 1
+#define CRGPU_AGG_KIND_ANTIGEN 2
+#define CRGPU_AGG_COUNTS 1           /* reason bits */
+#define CRGPU_AGG_HIGHLY_CORRECTED 2
+#define CRGPU_AGG_ANTIGEN 4
+struct crgpu_aggregates_info {
+    uint32_t n_antibodies, n_signal;   /* antibody features; those with >= 1000 UMIs */
+    uint32_t top_k, n_candidates;      /* K; min(K, V), 0 when the detection did not run */
+    uint32_t min_antibodies;           /* crgpu_aggregate_min_antibodies(n_signal) */
+    uint32_t n_aggregates;
+    uint32_t n_slices, rows_per_slice; /* of the rank pass; rows_per_slice 0 = device memory */
+    int32_t in_lds;
+    uint32_t reserved;
+    double rank_ms;                    /* the rank pass alone */
+};
+typedef struct crgpu_aggregates_info crgpu_aggregates_info;
+int crgpu_aggregate_min_antibodies(uint32_t n_signal, uint32_t *out);
+int crgpu_antigen_outlier_threshold(const uint32_t *top_counts, uint32_t n, double *q1_out, double *q3_out, double *threshold_out);
+int crgpu_aggregates_by_counts_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const uint8_t *feature_kind, uint32_t n_features,
+                                   uint32_t num_probe_barcodes, uint8_t *d_reason_inout, uint64_t *cols_out, uint32_t cap,
+                                   uint32_t *n_cols_out, crgpu_aggregates_info *info);
+int crgpu_aggregates_highly_corrected_dev(crgpu_ctx *ctx, const uint32_t *d_reads, const uint32_t *d_corrected_reads, uint64_t V,
+                                          uint8_t *d_reason_inout, uint64_t *n_found_out);
+int crgpu_counts_corrected_reads_per_column(crgpu_ctx *ctx, const crgpu_counts *counts, const crgpu_matrix_dev *m, uint32_t lib_mask,
+                                            uint32_t *d_out);
+int crgpu_aggregates_antigen_outliers_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const uint8_t *feature_kind, uint32_t n_features,
+                                          uint8_t *d_reason_inout, uint64_t *cols_out, uint32_t cap, uint32_t *n_cols_out,
+                                          double *threshold_out);
+int crgpu_aggregates_partition_dev(crgpu_ctx *ctx, const uint8_t *d_reason, uint64_t V, uint64_t **d_kept_cols_out, uint64_t *n_kept_out,
+                                   uint64_t **d_removed_cols_out, uint64_t *n_removed_out);
+int crgpu_take_columns_dev(crgpu_ctx *ctx, const void *d_src, uint32_t elem_bytes, uint64_t V, const uint64_t *d_cols, uint64_t n,
+                           void *d_out);
+int crgpu_sum_u32_dev(crgpu_ctx *ctx, const uint32_t *d_values, uint64_t n, uint64_t *sum_out);
+int crgpu_filter_cells_min_umis_dev(crgpu_ctx *ctx, const uint32_t *d_umis_per_col, uint64_t V, const uint64_t *d_cell_cols,
+                                    uint64_t n_cells, uint64_t minimum_umis, uint64_t **d_kept_cols_out, uint64_t *n_kept_out);
+int crgpu_filter_cells_mito_dev(crgpu_ctx *ctx, const uint32_t *d_mito_umis_per_col, const uint32_t *d_total_umis_per_col, uint64_t V,
+                                const uint64_t *d_cell_cols, uint64_t n_cells, double max_mito_percent, uint64_t **d_kept_cols_out,
+                                uint64_t *n_kept_out, uint64_t **d_removed_cols_out, uint64_t *n_removed_out);
+
 /* ---- cell calling: the non-ambient ("EmptyDrops") barcodes behind the initial call ---------------------------------------------
  * Replaces find_nonambient_barcodes (lib/python/cellranger/cell_calling.py:144-263) as call_additional_cells runs it
  * (cell_calling_helpers.py:575-668) for ONE genome / GEM group; the caller loops and passes a feature mask.

@@ -1114,4 +1114,85 @@ inline crgpu_matrix_summary_floats matrix_summary_stats(const MatrixSummary &s, 
     return matrix_summary_stats(s.classes.at(k), s.classes.at(k).reads_cells, s.reads_all);
 }
 
+// ---- protein aggregates of an antibody / antigen well; the closing filters of a cell call ---------------------------------------------
+static_assert(sizeof(crgpu_aggregates_info) == 48, "crgpu_aggregates_info changed: bump CRGPU_ABI_VERSION and every binding");
+/// int(np.round(n_signal * _calculate_fraction_to_use(n_signal)))
+inline uint32_t aggregate_min_antibodies(uint32_t n_signal) {
+    uint32_t out = 0;
+    const int rc = crgpu_aggregate_min_antibodies(n_signal, &out);
+    if (rc != CRGPU_OK) throw Error(rc, crgpu_last_error(nullptr));
+    return out;
+}
+struct Aggregates {
+    std::vector<uint64_t> removed;   // ascending
+    std::vector<uint8_t> reasons;    // CRGPU_AGG_COUNTS | CRGPU_AGG_HIGHLY_CORRECTED | CRGPU_AGG_ANTIGEN per removed column
+    std::vector<uint64_t> kept;      // ascending: what select_barcodes takes
+    crgpu_aggregates_info info{};
+    double antigen_threshold = 0.0;  // NaN without a column
+};
+/// remove_antibody_antigen_aggregates on the raw matrix up to the column lists: feature_kind = CRGPU_AGG_KIND_* per feature; reads /
+/// corrected_reads = the Antibody library's per column (both empty: no highly-corrected detection)
+inline Aggregates detect_aggregates(Context &ctx, const crgpu_matrix_dev *raw, const std::vector<uint8_t> &feature_kind, uint32_t num_probe_barcodes = 0,
+                                    const std::vector<uint32_t> &reads = {}, const std::vector<uint32_t> &corrected_reads = {}) {
+    const uint64_t V = raw->n_barcodes;
+    if (reads.size() != corrected_reads.size() || (!reads.empty() && reads.size() != V)) throw Error(CRGPU_EINVAL, "detect_aggregates: shapes");
+    Aggregates out;
+    detail::DeviceCopy<uint8_t> d_reason(ctx, std::vector<uint8_t>(V, 0));
+    if (!reads.empty()) {
+        detail::DeviceCopy<uint32_t> d_reads(ctx, reads), d_corr(ctx, corrected_reads);
+        ctx.check(crgpu_aggregates_highly_corrected_dev(ctx.get(), d_reads.get(), d_corr.get(), V, (uint8_t *)d_reason.d, nullptr));
+    }
+    uint32_t n = 0;
+    ctx.check(crgpu_aggregates_by_counts_dev(ctx.get(), raw, feature_kind.data(), (uint32_t)feature_kind.size(), num_probe_barcodes,
+                                             (uint8_t *)d_reason.d, nullptr, 0, &n, &out.info));
+    ctx.check(crgpu_aggregates_antigen_outliers_dev(ctx.get(), raw, feature_kind.data(), (uint32_t)feature_kind.size(), (uint8_t *)d_reason.d, nullptr, 0,
+                                                    &n, &out.antigen_threshold));
+    uint64_t *d_kept = nullptr, *d_removed = nullptr, n_kept = 0, n_removed = 0;
+    ctx.check(crgpu_aggregates_partition_dev(ctx.get(), d_reason.get(), V, &d_kept, &n_kept, &d_removed, &n_removed));
+    int rc = detail::fetch(ctx, out.kept, (const uint64_t *)d_kept, n_kept);
+    if (rc == CRGPU_OK) rc = detail::fetch(ctx, out.removed, (const uint64_t *)d_removed, n_removed);
+    if (rc == CRGPU_OK && n_removed) {
+        detail::DeviceCopy<uint8_t> d_why(ctx, std::vector<uint8_t>(n_removed, 0));
+        rc = crgpu_take_columns_dev(ctx.get(), d_reason.get(), 1, V, d_removed, n_removed, d_why.d);
+        if (rc == CRGPU_OK) rc = detail::fetch(ctx, out.reasons, d_why.get(), n_removed);
+    }
+    crgpu_free(ctx.get(), d_kept);
+    crgpu_free(ctx.get(), d_removed);
+    ctx.check(rc);
+    return out;
+}
+/// apply_global_minimum_umis_threshold: the cells (ascending columns) whose entry of umis_per_col is >= minimum_umis
+inline std::vector<uint64_t> apply_minimum_umis(Context &ctx, const std::vector<uint32_t> &umis_per_col, const std::vector<uint64_t> &cells,
+                                                uint64_t minimum_umis) {
+    detail::DeviceCopy<uint32_t> d_umis(ctx, umis_per_col);
+    detail::DeviceCols d_cells(ctx, cells);
+    uint64_t *d_kept = nullptr, n = 0;
+    ctx.check(crgpu_filter_cells_min_umis_dev(ctx.get(), d_umis.get(), umis_per_col.size(), d_cells.get(), cells.size(), minimum_umis, &d_kept, &n));
+    std::vector<uint64_t> out;
+    const int rc = detail::fetch(ctx, out, (const uint64_t *)d_kept, n);
+    crgpu_free(ctx.get(), d_kept);
+    ctx.check(rc);
+    return out;
+}
+struct MitoFilter {
+    std::vector<uint64_t> kept, removed;  // in the order of the call
+};
+/// apply_mitochondrial_threshold: cells with 100.0 * mito / total > max_mito_percent leave (0 / 0 stays)
+inline MitoFilter apply_mito_threshold(Context &ctx, const std::vector<uint32_t> &mito_per_col, const std::vector<uint32_t> &total_per_col,
+                                       const std::vector<uint64_t> &cells, double max_mito_percent) {
+    if (mito_per_col.size() != total_per_col.size()) throw Error(CRGPU_EINVAL, "apply_mito_threshold: shapes");
+    detail::DeviceCopy<uint32_t> d_mito(ctx, mito_per_col), d_total(ctx, total_per_col);
+    detail::DeviceCols d_cells(ctx, cells);
+    uint64_t *d_kept = nullptr, *d_removed = nullptr, n_kept = 0, n_removed = 0;
+    ctx.check(crgpu_filter_cells_mito_dev(ctx.get(), d_mito.get(), d_total.get(), total_per_col.size(), d_cells.get(), cells.size(), max_mito_percent,
+                                          &d_kept, &n_kept, &d_removed, &n_removed));
+    MitoFilter out;
+    int rc = detail::fetch(ctx, out.kept, (const uint64_t *)d_kept, n_kept);
+    if (rc == CRGPU_OK) rc = detail::fetch(ctx, out.removed, (const uint64_t *)d_removed, n_removed);
+    crgpu_free(ctx.get(), d_kept);
+    crgpu_free(ctx.get(), d_removed);
+    ctx.check(rc);
+    return out;
+}
+
 }  // namespace crgpu
