@@ -1,5 +1,5 @@
-// aggregates.h -- protein aggregates of an antibody / antigen well and the two closing cell filters on the device (part of dedup.hip,
-// behind matrix_summary.h: uses its ms_lower_bound, the column sums of cell_calling.h, the radix sort, the compaction, DevBuf).
+// aggregates.h -- protein aggregates of an antibody / antigen well and the two closing cell filters on the device (part of
+// matrix_stages.hip).
 //
 // Replaces remove_antibody_antigen_aggregates (lib/python/cellranger/cell_calling_helpers.py:188-270) with detect_aggregate_barcodes,
 // detect_highly_corrected_bcs and detect_outlier_umis_bcs (cellranger/feature/antibody/analysis.py:77-185), which FILTER_BARCODES runs
@@ -29,8 +29,12 @@
 //      (otherwise nnz >= K decides); such rows bump a second set of counters by column (device memory: fewer than K entries each).
 //      A candidate passes a row with fewer than K pairs above it; votes[j] = rows passed.
 // Integer work throughout; the two thresholds are f64 on the host.
+#pragma once
+
 #include <algorithm>
 #include <cmath>
+
+#include "stage_common.h"
 
 #define AG_NONE 0xFFFFFFFFu
 #define AG_MAX_ANTIBODIES 4096u                      // rows whose sums a workgroup of pass 1 keeps in LDS (12 bytes each)
@@ -216,8 +220,8 @@ __global__ __launch_bounds__(AG_WG) void k_ag_rank(const long long *__restrict__
     for (uint64_t c = (uint64_t)w * AG_WAVES + wave; c < V; c += c_step) {  // uniform in the wave
         long long b = indptr[c], e = indptr[c + 1];
         if (e - b > 64) {
-            if (flo > 0u) b = ms_lower_bound(indices, b, e, flo, lane);
-            if (fhi < n_features) e = ms_lower_bound(indices, b, e, fhi, lane);
+            if (flo > 0u) b = wave_lower_bound(indices, b, e, flo, lane);
+            if (fhi < n_features) e = wave_lower_bound(indices, b, e, fhi, lane);
         }
         for (long long i = b + lane; i < e; i += 64) {
             const uint32_t f = (uint32_t)indices[i], d = (uint32_t)data[i];
@@ -321,7 +325,7 @@ extern "C" int crgpu_aggregates_by_counts_dev(crgpu_ctx *ctx, const crgpu_matrix
     CR_TRY(dmalloc(ctx, nnz_b, nab1 * sizeof(uint32_t)));
     CR_HIP(ctx, hipMemsetAsync(sum_b.p, 0, nab1 * sizeof(unsigned long long), ctx->stream));
     CR_HIP(ctx, hipMemsetAsync(nnz_b.p, 0, nab1 * sizeof(uint32_t), ctx->stream));
-    uint32_t *d_flag = ctx->d_scalars + 48, flag = 0;
+    uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, flag = 0;
     CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
     {
         CrTimer t(ctx, CRGPU_T_MATRIX, m->nnz);
@@ -507,7 +511,7 @@ extern "C" int crgpu_aggregates_highly_corrected_dev(crgpu_ctx *ctx, const uint3
     if (n_found_out) *n_found_out = 0;
     if (!V) return CRGPU_OK;
     CR_REQUIRE(ctx, d_reads && d_corrected_reads && d_reason_inout, CRGPU_EINVAL, "crgpu_aggregates_highly_corrected_dev: NULL argument");
-    uint32_t *d_n = ctx->d_scalars + 48, n = 0;
+    uint32_t *d_n = ctx->d_scalars + CR_SCALAR_FLAG, n = 0;
     CR_HIP(ctx, hipMemsetAsync(d_n, 0, sizeof(uint32_t), ctx->stream));
     hipLaunchKernelGGL(k_ag_highly_corrected, dim3(cr_grid(V, 256)), dim3(256), 0, ctx->stream, d_reads, d_corrected_reads, V, d_reason_inout, d_n);
     CR_HIP(ctx, hipGetLastError());
@@ -550,7 +554,7 @@ extern "C" int crgpu_counts_corrected_reads_per_column(crgpu_ctx *ctx, const crg
     const uint64_t V = m->n_barcodes;
     if (!V) return CRGPU_OK;
     CR_REQUIRE(ctx, d_out != nullptr, CRGPU_EINVAL, "%s: NULL output", who);
-    uint32_t *d_flag = ctx->d_scalars + 48, flag = 0;
+    uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, flag = 0;
     CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
     {
         CrTimer t(ctx, CRGPU_T_MATRIX, V);
@@ -617,7 +621,7 @@ struct AgColEmit {
 // a pool block with the columns c in [0, V) that flag(c) keeps, ascending (the caller's, released with crgpu_free)
 template <typename Flag>
 static int ag_list(crgpu_ctx *ctx, Flag flag, uint64_t V, uint64_t **d_out, uint64_t *n_out) {
-    uint32_t *d_total = ctx->d_scalars + 16, n = 0;
+    uint32_t *d_total = ctx->d_scalars + CR_SCALAR_TOTAL, n = 0;
     DevBuf tmp;
     CR_TRY(dmalloc(ctx, tmp, (V ? V : 1) * sizeof(uint64_t)));
     if (V) {
@@ -673,7 +677,7 @@ extern "C" int crgpu_take_columns_dev(crgpu_ctx *ctx, const void *d_src, uint32_
     CR_REQUIRE(ctx, elem_bytes == 1u || elem_bytes == 4u, CRGPU_EINVAL, "crgpu_take_columns_dev: elements of 1 or 4 bytes");
     if (!n) return CRGPU_OK;
     CR_REQUIRE(ctx, d_src && d_cols && d_out, CRGPU_EINVAL, "crgpu_take_columns_dev: NULL argument");
-    uint32_t *d_flag = ctx->d_scalars + 48, flag = 0;
+    uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, flag = 0;
     CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
     if (elem_bytes == 1u)
         hipLaunchKernelGGL(k_ag_take<uint8_t>, dim3(cr_grid(n, 256)), dim3(256), 0, ctx->stream, (const uint8_t *)d_src, V, d_cols, n, (uint8_t *)d_out, d_flag);
@@ -689,7 +693,7 @@ __global__ __launch_bounds__(256) void k_ag_sum_u32(const uint32_t *__restrict__
     unsigned long long s = 0;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) s += x[i];
-    s = rt_wave_sum(s);
+    s = wave_sum(s);
     if ((threadIdx.x & 63u) == 0u && s) atomicAdd(out, s);
 }
 
@@ -720,7 +724,7 @@ static int ag_check_cols(crgpu_ctx *ctx, const char *who, const uint64_t *d_cols
     CR_REQUIRE(ctx, n <= V && (d_cols || !n), CRGPU_EINVAL, "%s: the cell call does not fit the %llu columns", who, (unsigned long long)V);
     CR_REQUIRE(ctx, V < 0xFFFFFFFFull, CRGPU_ERANGE, "%s: fewer than 2^32 - 1 columns", who);
     if (!n) return CRGPU_OK;
-    uint32_t *d_flag = ctx->d_scalars + 48, flag = 0;
+    uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, flag = 0;
     CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
     hipLaunchKernelGGL(k_ag_check_cols, dim3(cr_grid(n, 256)), dim3(256), 0, ctx->stream, d_cols, n, V, d_flag);
     CR_HIP(ctx, hipGetLastError());
@@ -761,7 +765,7 @@ static int ag_filter_cells(crgpu_ctx *ctx, const char *who, AgCellFlag flag, uin
     if (d_removed) *d_removed = nullptr, *n_removed = 0;
     CR_REQUIRE(ctx, flag.total || !n_cells, CRGPU_EINVAL, "%s: NULL counts", who);
     CR_TRY(ag_check_cols(ctx, who, flag.cols, n_cells, V));
-    uint32_t *d_total = ctx->d_scalars + 16;
+    uint32_t *d_total = ctx->d_scalars + CR_SCALAR_TOTAL;
     for (int pass = 0; pass < (d_removed ? 2 : 1); pass++) {
         flag.keep = pass == 0;
         uint64_t *d = nullptr;

@@ -264,7 +264,7 @@ static int pick_uniform_lib(crgpu_ctx *ctx, const uint8_t *d_flags, uint64_t n, 
         if (ctx->wl[0].set) *ulib_out = 0;
         return CRGPU_OK;
     }
-    uint32_t *d_mask = ctx->d_scalars + 28, mask = 0;
+    uint32_t *d_mask = ctx->d_scalars + CR_SCALAR_LIB_MASK, mask = 0;
     CR_HIP(ctx, hipMemsetAsync(d_mask, 0, sizeof(uint32_t), ctx->stream));
     hipLaunchKernelGGL(k_lib_mask, dim3(cr_grid(n, 256 * 16)), dim3(256), 0, ctx->stream, d_flags, n, d_mask);
     CR_HIP(ctx, hipGetLastError());
@@ -2151,7 +2151,7 @@ static int correct_dev_impl(crgpu_ctx *ctx, const uint32_t *d_cb, const uint8_t 
     void *ws;
     CR_TRY(cr_scratch(ctx, n * sizeof(uint32_t), &ws));
     uint32_t *miss_list = (uint32_t *)ws;
-    unsigned long long *n_miss = (unsigned long long *)ctx->d_scalars;
+    unsigned long long *n_miss = (unsigned long long *)(ctx->d_scalars + CR_SCALAR_MISS_COUNT);
     CrTimer t(ctx, CRGPU_T_CORRECT, n);
     CR_HIP(ctx, hipMemsetAsync(n_miss, 0, sizeof(unsigned long long), ctx->stream));
     if (d_corrected_out) CR_HIP(ctx, hipMemsetAsync(d_corrected_out, 0, n, ctx->stream));

@@ -139,3 +139,34 @@ __device__ __forceinline__ unsigned long long wave_lookback(const unsigned long 
         end -= 64;
     }
 }
+
+// Sum of `v` over the 64 lanes of a wave, in every lane (all lanes must call it).  64 bits travel as two 32-bit shuffles.
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t lo = __shfl_xor((uint32_t)v, d), hi = __shfl_xor((uint32_t)(v >> 32), d);
+        v += ((unsigned long long)hi << 32) | lo;
+    }
+    return v;
+}
+// ... of 32-bit values, modulo 2^32: widen the argument where 64 values may not fit
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+
+// The first i in [lo, hi) with idx[i] >= target (hi: none), idx ascending there; one wave, 64 samples per round.  Every position
+// read lies in [lo, hi) whatever the order of idx.
+__device__ __forceinline__ long long wave_lower_bound(const int32_t *__restrict__ idx, long long lo, long long hi, uint32_t target, uint32_t lane) {
+    while (hi > lo) {
+        const long long step = (hi - lo + 63) / 64, p = lo + (long long)lane * step;
+        const bool less = p < hi && (uint32_t)idx[p] < target;
+        const long long cnt = __popcll(__ballot(less));
+        if (!cnt) return lo;
+        const long long nlo = lo + (cnt - 1) * step + 1, nhi = lo + cnt * step;
+        lo = nlo;
+        hi = nhi < hi ? nhi : hi;
+    }
+    return lo;
+}

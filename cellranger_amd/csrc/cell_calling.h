@@ -1,4 +1,4 @@
-// cell_calling.h -- the initial cell call on the device (part of dedup.hip: uses its compaction and its device matrices).
+// cell_calling.h -- the initial cell call on the device (part of matrix_stages.hip: works on crgpu_matrix_dev).
 //
 // Replaces filter_cellular_barcodes_ordmag with estimate_recovered_cells_ordmag, find_within_ordmag and
 // summarize_bootstrapped_top_n (lib/python/cellranger/cell_calling_helpers.py:832-955) and
@@ -16,9 +16,13 @@
 //      two binary searches per (sample, baseline), and the estimate scores all <= 1414 grid values against the same C;
 //   4. the summary of the 100 integers and the tie extension run on the host; the selection is a compaction of pos[i] < top_n.
 // Integer work except rint(0.1 * baseline) and the loss divide (f64, -ffp-contract=off like the rest of the library).
+#pragma once
+
 #include <algorithm>
 #include <cmath>
 #include <optional>
+
+#include "stage_common.h"
 
 // ---- MT19937 (the raw stream of np.random.RandomState) -----------------------------------------------------------------------
 // x[n] = x[n - 227] ^ twist(x[n - 624], x[n - 623]): 227 consecutive words depend on older ones only.  ONE workgroup keeps a
@@ -188,7 +192,7 @@ extern "C" int crgpu_matrix_dev_column_sums(crgpu_ctx *ctx, const crgpu_matrix_d
         CR_TRY(dmalloc(ctx, mask_b, n_features ? n_features : 1));
         if (n_features) CR_TRY(crgpu_memcpy_h2d(ctx, mask_b.p, feature_mask, n_features));
     }
-    uint32_t *d_flag = ctx->d_scalars + 48, flag = 0;
+    uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, flag = 0;
     CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
     {
         CrTimer t(ctx, CRGPU_T_MATRIX, m->nnz);
@@ -426,7 +430,7 @@ struct OmBootstrap {
     // extra pass per batch seam; with CRGPU_ORDMAG_BATCH=1 and a small N (one round holds all samples) it is one pass per
     // sample, which only the tests pay.  Measured with everything else but the generator: <= 2.7 of 127 ms at N = 2^20.
     int consume(uint64_t w0, uint64_t w1) {
-        uint32_t *d_total = ctx->d_scalars + 16, t = 0;
+        uint32_t *d_total = ctx->d_scalars + CR_SCALAR_TOTAL, t = 0;
         OmDrawFlag flag{raw.as<uint32_t>(), mask, N - 1u};
         OmDrawEmit emit{raw.as<uint32_t>(), d_pos, hist.as<uint32_t>(), mask, N, (long long)acc_before - (long long)w0, w1 - w0};
         {
@@ -544,7 +548,7 @@ extern "C" int crgpu_call_cells_ordmag_dev(crgpu_ctx *ctx, const uint32_t *d_bc_
                "crgpu_call_cells_ordmag_dev: max_expected_cells must be 2 .. 2^30 to estimate the recovered cells");
     if (!V) return CRGPU_OK;
     const int S = CRGPU_ORDMAG_SAMPLES;
-    uint32_t *d_total = ctx->d_scalars + 16;
+    uint32_t *d_total = ctx->d_scalars + CR_SCALAR_TOTAL;
 
     // 1. nonzero_bc_counts with their columns
     DevBuf nzv_b, nzc_b;
@@ -667,7 +671,7 @@ extern "C" int crgpu_cell_ranks_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, c
     CR_ENTER(ctx);
     if (!n_cells) return CRGPU_OK;
     CR_REQUIRE(ctx, d_cell_cols && d_ranks_out, CRGPU_EINVAL, "crgpu_cell_ranks_dev: NULL argument");
-    uint32_t *d_flag = ctx->d_scalars + 48, flag = 0;
+    uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, flag = 0;
     CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
     hipLaunchKernelGGL(k_cell_ranks, dim3(cr_grid(n_cells, 256)), dim3(256), 0, ctx->stream, m->d_barcode_rank, m->n_barcodes, d_cell_cols,
                        n_cells, d_ranks_out, d_flag);

@@ -16,8 +16,29 @@
 #include "../../include/crgpu.h"
 
 #define CR_WAVE 64
-// words of the context's 4 KB scalar page with a fixed meaning (the other users take theirs by offset: 0, 8, 16, 28, 128, 760)
-#define CR_SCALAR_N_WITHOUT_FLAGS 40
+// Words of the context's 4 KB scalar page (crgpu_ctx::d_scalars, 1024 u32): who may use a word and how many words follow it.
+// The entry points of a context are serialised (CR_ENTER) and each one zeroes the words it takes before it uses them, so two
+// users of one word only have to be entry points that never run inside each other.
+#define CR_SCALAR_MISS_COUNT 0         // u64 (2 words): reads left to the correction pass (barcode.hip)
+#define CR_SCALAR_KEY_COUNT 8          // u64 (2 words): keys the key builder wrote (dedup.hip)
+#define CR_SCALAR_TOTAL 16             // 1 word, anybody: the total of a compaction or of cr_scan_small, read back before the next one
+                                       // (the feature extraction keeps the length of its queue here)
+#define CR_SCALAR_TRIPLET_TOTAL 17     // 1 word: the count stage's triplet total, alive beside CR_SCALAR_TOTAL (dedup.hip)
+#define CR_SCALAR_LIB_MASK 28          // 1 word: the libraries that occur in a flag array (barcode.hip)
+#define CR_SCALAR_N_WITHOUT_FLAGS 40   // 1 word: reads that came without flags (barcode.hip)
+#define CR_SCALAR_KEY_TICKET 44        // 1 word: chunk tickets of the ordered key builder (dedup.hip)
+// The flag words of the entry point that runs: "an input was refused", or a small count.  Most entry points take the first word
+// only; the Flex tags (rtl_tags.h) take 2 words, the matrix summary (matrix_summary.h) takes 3 (48 .. 50).  EmptyDrops takes
+// word 48 as its flag and names word 49 by itself (CR_SCALAR_FLAG_AUX: the largest row, then the ambient barcodes used).  These
+// uses overlap on words 49 and 50; that is safe only because no entry point does two of them.
+#define CR_SCALAR_FLAG 48              // up to 3 words, see above
+#define CR_SCALAR_FLAG_AUX 49          // 1 word: EmptyDrops only (emptydrops.h), the word behind its flag
+#define CR_SCALAR_REPAIR 52            // 4 words: flag, set, long and medium run counts of cr_repair_runs (sort.hip)
+#define CR_SCALAR_BAD_INDEX 60         // 1 word: an index outside its table (key builder, barcode trim, metrics.hip)
+#define CR_SCALAR_LOOKBACK_ABORT 61    // 1 word: watchdog of the key builder's look-back; zeroed together with word 60
+#define CR_SCALAR_REC_COUNT 66         // u64 (2 words): captures kept for the next extraction call (feature_extract.hip)
+#define CR_SCALAR_ERROR_PROBS 128      // 34 doubles (68 words): probability of an error per quality (feature.hip, feature_extract.hip)
+#define CR_SCALAR_OWNER_BOUNDS 760     // 257 words: first barcode of every rank (sort.hip, partition by owner)
 
 // --------------------------------------------------------------------------------------------
 // whitelist tables of one library type (device + host mirrors)
@@ -237,7 +258,7 @@ struct crgpu_ctx {
     uint64_t target_min_reads = 0;
 
     // scratch
-    uint32_t *d_scalars = nullptr;  // small device counters
+    uint32_t *d_scalars = nullptr;  // small device counters: the CR_SCALAR_* words above
     uint32_t *d_sort_hist = nullptr;  // RADIX x 2048 block histograms of the radix passes
     void *d_scratch = nullptr;      // growable workspace
     uint64_t scratch_bytes = 0;

@@ -1,5 +1,6 @@
 // dedup.hip -- count stage: molecule keys, run-length grouping, UMI correction, low-support
-// filtering and (barcode, feature) counting on sorted 64-bit keys.
+// filtering and (barcode, feature) counting on sorted 64-bit keys; then the device matrix (assembly,
+// sum, column selection).  The analysis stages behind it are molecule_stages.hip and matrix_stages.hip.
 //
 // Replaces, per (barcode, library type) group of the reference:
 //   UmiInfo::new                      umi/src/info.rs:20-37        (validity of each UMI)
@@ -18,38 +19,7 @@
 //   * a (barcode, feature) segment is one matrix entry.
 // Low-support grouping needs (barcode, library, UMI) across features: the DISTINCT keys are sorted a
 // second time by a 32-bit hash of that triple (index as payload) and re-checked exactly.
-#include "block_utils.h"
-#include "common.h"
-
-int cr_scan_small(crgpu_ctx *ctx, uint32_t *d_data, uint64_t n, uint32_t *d_total_out);
-int cr_partition_by_owner(crgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, uint64_t n, uint32_t sh_bc,
-                          uint32_t n_ranks, const uint32_t *bounds, uint64_t *counts_out);
-
-#define NONE32 0xFFFFFFFFu
-
-struct crgpu_counts {
-    uint64_t n_triplets = 0, n_molecules = 0;
-    uint32_t *d_bc = nullptr, *d_feature = nullptr, *d_count = nullptr;  // triplets
-    uint64_t *d_mkeys = nullptr;    // molecule keys (primary layout), n_molecules
-    uint32_t *d_mreads = nullptr;   // read_count of each molecule
-    uint32_t *d_corr_reads = nullptr;  // [library][barcode rank] reads whose UMI was corrected (BarcodeSummary), or NULL
-    uint32_t *d_filt_reads = nullptr;  // [library][barcode rank] reads of molecules the targeted-panel filter removed, or NULL
-    int32_t *d_mprobe = nullptr;    // probe_idx of each molecule's representative read (crgpu_records.d_probe_idx given), or NULL
-    uint32_t *d_back = nullptr;     // CRGPU_OPT_DENSE_BARCODE_KEYS: column -> whitelist rank of the barcode field of d_mkeys (n_back), else NULL
-    uint32_t n_back = 0;
-    uint32_t n_canon = 0;
-    KeyLayout layout;
-    // (barcode rank, probe_idx, umi_count) triplets, made on the first request (probe_counts.h) for pt_n_probes probes
-    bool pt_valid = false;
-    uint32_t pt_n_probes = 0;
-    uint64_t n_pt = 0;
-    uint32_t *d_pt_bc = nullptr, *d_pt_probe = nullptr, *d_pt_count = nullptr;
-    // device position -> position in the table crgpu_counts_molecules lists, made on the first subsampling of counts with
-    // several libraries or UMI lengths (subsample.h), else NULL
-    uint32_t *d_ss_pos = nullptr;
-    bool sharded = false;  // one rank's share of a well counted over several ranks (crgpu_count_records_sharded_dev)
-};
-
+#include "stage_common.h"
 // ------------------------------------------------------------------------------------------------
 // key layout
 // ------------------------------------------------------------------------------------------------
@@ -131,7 +101,6 @@ static KL make_kl(const KeyLayout &L) {
     return KL{L.sh_umi(), L.sh_lib(), L.sh_feat(), L.sh_bc(), L.bits_umi, L.bits_lib, L.bits_feat, L.bits_bc,
               L.umi_len, L.n_features, L.n_libs, L.mux_mask, L.bits_ulen, L.sh_libid(), L.umi_min_len};
 }
-__device__ __forceinline__ uint64_t lowmask(uint32_t bits) { return bits >= 64 ? ~0ull : ((1ull << bits) - 1ull); }
 typedef uint32_t cr_v4u32 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ uint4 ld_stream4(const uint4 *p) {  // 16-byte load that does not stay in the caches
     const cr_v4u32 v = __builtin_nontemporal_load(reinterpret_cast<const cr_v4u32 *>(p));
@@ -144,23 +113,6 @@ __device__ __forceinline__ uint32_t dense_column(const uint4 *__restrict__ fwd, 
     const uint32_t bit = rank & 63u;
     if (!((bits >> bit) & 1ull)) return CRGPU_MISS;
     return e.z + (uint32_t)__popcll(bits & ((1ull << bit) - 1ull));
-}
-
-struct DevBuf {  // pooled temporary, returned to the context's pool at scope exit
-    crgpu_ctx *ctx = nullptr;
-    void *p = nullptr;
-    ~DevBuf() { cr_pool_free(ctx, p); }
-    template <typename T>
-    T *as() { return (T *)p; }
-};
-
-static int dmalloc(crgpu_ctx *ctx, DevBuf &b, uint64_t bytes) {
-    b.ctx = ctx;
-    return cr_pool_alloc(ctx, &b.p, bytes);
-}
-
-static int read_u32(crgpu_ctx *ctx, const uint32_t *d, uint32_t *h) {
-    return crgpu_memcpy_d2h(ctx, h, d, sizeof(uint32_t));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -503,12 +455,12 @@ static int build_keys_impl(crgpu_ctx *ctx, const crgpu_records *recs, uint64_t *
                "crgpu_build_keys: per-read UMI lengths need crgpu_set_umi_min_len");
     CR_REQUIRE(ctx, (recs->umi_len & 3u) != 0u || (uintptr_t)recs->d_umi_qualn % 4 == 0, CRGPU_EINVAL,
                "crgpu_build_keys: the UMI quality buffer must be 4-byte aligned");
-    unsigned long long *d_n = (unsigned long long *)(ctx->d_scalars + 8);
+    unsigned long long *d_n = (unsigned long long *)(ctx->d_scalars + CR_SCALAR_KEY_COUNT);
     bool append = false;
     const uint64_t n_before = ctx->ghist.n;
     CR_TRY(cr_dense_ensure(ctx));  // CRGPU_OPT_DENSE_BARCODE_KEYS: the BarcodeIndex of the tables as they stand (else nothing)
     const uint4 *d_fwd = ctx->dense.valid ? ctx->dense.d_fwd : nullptr;
-    uint32_t *d_unknown = ctx->d_scalars + 60, *d_lb_abort = ctx->d_scalars + 61;
+    uint32_t *d_unknown = ctx->d_scalars + CR_SCALAR_BAD_INDEX, *d_lb_abort = ctx->d_scalars + CR_SCALAR_LOOKBACK_ABORT;
     {
         CrTimer t(ctx, CRGPU_T_KEYS, recs->n);
         CR_HIP(ctx, hipMemsetAsync(d_n, 0, sizeof(*d_n), ctx->stream));
@@ -538,7 +490,7 @@ static int build_keys_impl(crgpu_ctx *ctx, const crgpu_records *recs, uint64_t *
         // with ordinals: order-preserving compaction (tickets + look-back status, one word per 4096-read chunk)
         DevBuf status_b;
         unsigned long long *d_status = nullptr;
-        uint32_t *d_ticket = ctx->d_scalars + 44;
+        uint32_t *d_ticket = ctx->d_scalars + CR_SCALAR_KEY_TICKET;
         if (d_vals_out) {
             const uint64_t n_chunks = (recs->n + 256ull * KEY_ITEMS - 1) / (256ull * KEY_ITEMS);
             CR_TRY(dmalloc(ctx, status_b, n_chunks * sizeof(unsigned long long)));
@@ -684,123 +636,6 @@ extern "C" int crgpu_balanced_bounds(crgpu_ctx *ctx, uint32_t n_ranks, uint32_t 
         bounds_out[k] = r;
     }
     bounds_out[n_ranks] = W;
-    return CRGPU_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// generic two-pass stream compaction driven by a flag functor: out position of every flagged item
-// ------------------------------------------------------------------------------------------------
-#define CP_BLOCK 256
-#ifndef CP_ITEMS
-#define CP_ITEMS 8  // items per thread per round: their flag loads are all issued before the first compare
-#endif
-#define CP_ROUND (CP_BLOCK * CP_ITEMS)
-#define CP_WAVES (CP_BLOCK / 64)
-
-// Flags are evaluated at clamped indices and masked afterwards, so that the loads of a round are not chained
-// behind `i < hi` branches (one load in flight per wave left these passes at ~2 TB/s).
-template <typename Flag>
-__global__ __launch_bounds__(CP_BLOCK) void k_cp_count(Flag flag, uint64_t n, uint64_t tile, uint32_t *__restrict__ block_counts) {
-    __shared__ uint32_t ws[CP_WAVES];
-    const uint64_t lo = (uint64_t)blockIdx.x * tile;
-    const uint64_t hi = lo + tile < n ? lo + tile : n;
-    uint32_t c = 0;
-    for (uint64_t base = lo; base < hi; base += CP_ROUND) {
-        bool f[CP_ITEMS];
-#pragma unroll
-        for (int j = 0; j < CP_ITEMS; j++) {
-            const uint64_t i = base + (uint64_t)j * CP_BLOCK + threadIdx.x;
-            f[j] = flag(i < hi ? i : hi - 1);
-        }
-#pragma unroll
-        for (int j = 0; j < CP_ITEMS; j++) {
-            const uint64_t i = base + (uint64_t)j * CP_BLOCK + threadIdx.x;
-            c += (f[j] && i < hi) ? 1u : 0u;
-        }
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
-    if ((threadIdx.x & 63u) == 0) ws[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t t = 0;
-        for (int w = 0; w < CP_WAVES; w++) t += ws[w];
-        block_counts[blockIdx.x] = t;
-    }
-}
-
-// Stable: inside a round the output order is (item slot, wave, lane) == ascending input index.
-template <typename Flag, typename Emit>
-__global__ __launch_bounds__(CP_BLOCK) void k_cp_write(Flag flag, Emit emit, uint64_t n, uint64_t tile,
-                                                       const uint32_t *__restrict__ block_offs) {
-    __shared__ uint32_t ws[CP_ITEMS * CP_WAVES];  // flagged items of (item slot, wave), then their exclusive prefix
-    __shared__ uint32_t round_total;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint64_t lo = (uint64_t)blockIdx.x * tile;
-    const uint64_t hi = lo + tile < n ? lo + tile : n;
-    uint32_t run = block_offs[blockIdx.x];
-    for (uint64_t base = lo; base < hi; base += CP_ROUND) {
-        bool f[CP_ITEMS];
-        typename Emit::Pre pre[CP_ITEMS];  // what the emit needs from memory, requested together with the flags
-#pragma unroll
-        for (int j = 0; j < CP_ITEMS; j++) {
-            const uint64_t i = base + (uint64_t)j * CP_BLOCK + threadIdx.x;
-            f[j] = flag(i < hi ? i : hi - 1);
-            pre[j] = emit.pre(i < hi ? i : hi - 1);
-        }
-        uint32_t below[CP_ITEMS];
-#pragma unroll
-        for (int j = 0; j < CP_ITEMS; j++) {
-            const uint64_t i = base + (uint64_t)j * CP_BLOCK + threadIdx.x;
-            f[j] = f[j] && i < hi;
-            const unsigned long long m = __ballot(f[j]);
-            below[j] = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-            if (lane == 0) ws[j * CP_WAVES + wave] = (uint32_t)__popcll(m);
-        }
-        __syncthreads();
-        if (threadIdx.x < CP_ITEMS * CP_WAVES) {  // 32 lanes of wave 0: exclusive scan in (slot, wave) order
-            const uint32_t v = ws[threadIdx.x];
-            uint32_t x = v;
-#pragma unroll
-            for (int d = 1; d < CP_ITEMS * CP_WAVES; d <<= 1) {
-                const uint32_t y = __shfl_up(x, d);
-                if (threadIdx.x >= (uint32_t)d) x += y;
-            }
-            ws[threadIdx.x] = x - v;
-            if (threadIdx.x == CP_ITEMS * CP_WAVES - 1) round_total = x;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < CP_ITEMS; j++) {
-            const uint64_t i = base + (uint64_t)j * CP_BLOCK + threadIdx.x;
-            if (f[j]) emit(i, run + ws[j * CP_WAVES + wave] + below[j], pre[j]);
-        }
-        run += round_total;
-        __syncthreads();
-    }
-}
-
-static uint32_t cp_blocks(uint64_t n, uint64_t *tile_out) {
-    uint64_t nb = (n + CP_ROUND * 4 - 1) / (CP_ROUND * 4);
-    if (nb < 1) nb = 1;
-    if (nb > 4096) nb = 4096;
-    uint64_t tile = (n + nb - 1) / nb;
-    tile = (tile + CP_ROUND - 1) / CP_ROUND * CP_ROUND;
-    nb = (n + tile - 1) / tile;
-    if (nb < 1) nb = 1;
-    *tile_out = tile;
-    return (uint32_t)nb;
-}
-
-// d_block: workspace of >= 4096 u32.  *total_out (device u32) receives the number of flagged items.
-template <typename Flag, typename Emit>
-static int compact(crgpu_ctx *ctx, Flag flag, Emit emit, uint64_t n, uint32_t *d_block, uint32_t *d_total_out) {
-    uint64_t tile;
-    const uint32_t nb = cp_blocks(n, &tile);
-    hipLaunchKernelGGL(k_cp_count<Flag>, dim3(nb), dim3(CP_BLOCK), 0, ctx->stream, flag, n, tile, d_block);
-    CR_TRY(cr_scan_small(ctx, d_block, nb, d_total_out));
-    hipLaunchKernelGGL((k_cp_write<Flag, Emit>), dim3(nb), dim3(CP_BLOCK), 0, ctx->stream, flag, emit, n, tile, d_block);
-    CR_HIP(ctx, hipGetLastError());
     return CRGPU_OK;
 }
 
@@ -1422,10 +1257,6 @@ __global__ __launch_bounds__(LF_THREADS) void k_group_candidates(const KL kl, co
         __syncthreads();
     }
 }
-struct CandFlag {
-    const uint8_t *cand;
-    __device__ __forceinline__ bool operator()(uint64_t k) const { return cand[k] != 0; }
-};
 // Candidates are sorted by a 32-bit hash of their group (four passes over 8-byte pairs); members of a group are
 // then adjacent inside a run of equal hashes (27 bits in three 9-bit passes were tried: the sort got 0.5 ms faster and
 // k_low_support 0.6 ms slower on its longer runs).  val = (extra hash bits << vbits) | index: the bits of the u32 payload the
@@ -1810,7 +1641,7 @@ static int count_keys_impl(crgpu_ctx *ctx, uint64_t *d_keys_inout, uint64_t n_ke
     } guard{ctx, res};
 
     uint32_t *d_block = ctx->d_sort_hist;      // 4096 u32 block counters of the compactions
-    uint32_t *d_total = ctx->d_scalars + 16;   // device-side totals
+    uint32_t *d_total = ctx->d_scalars + CR_SCALAR_TOTAL;   // device-side totals
     if (ctx->dense.valid) {  // the result keeps its own copy of the column -> rank map: the context's may change before it is read
         res->n_back = ctx->dense.V;
         CR_TRY(cr_pool_alloc(ctx, (void **)&res->d_back, (size_t)ctx->dense.V * sizeof(uint32_t)));
@@ -2045,7 +1876,7 @@ static int count_keys_impl(crgpu_ctx *ctx, uint64_t *d_keys_inout, uint64_t n_ke
     CR_TRY(cr_pool_alloc(ctx, (void **)&res->d_bc, nd * sizeof(uint32_t)));
     CR_TRY(cr_pool_alloc(ctx, (void **)&res->d_feature, nd * sizeof(uint32_t)));
     uint32_t *d_heads = d_block + 4096;      // the second set of block counters
-    uint32_t *d_total_h = ctx->d_scalars + 17;
+    uint32_t *d_total_h = ctx->d_scalars + CR_SCALAR_TRIPLET_TOTAL;
     {
         CrTimer t(ctx, CRGPU_T_DEDUP);
         EmitMol emit{ukey, upos, inc_all, minidx, st, n_keys, nd, mkeys_b.as<uint64_t>(), mreads_b.as<uint32_t>()};
@@ -2280,24 +2111,6 @@ extern "C" int crgpu_count_records_sharded_dev(crgpu_ctx *ctx, const crgpu_recor
 // ------------------------------------------------------------------------------------------------
 // K6 on the device: barcode index + CSC (barcode_index.rs:20-53, count_matrix.rs:382-448)
 // ------------------------------------------------------------------------------------------------
-struct CountTables {
-    const uint32_t *t[2 * CRGPU_MAX_LIB];
-    uint32_t n;
-};
-struct SeenFlag {  // barcode has a non-zero valid or corrected count in some library
-    CountTables ct;
-    __device__ __forceinline__ bool operator()(uint64_t r) const {
-        uint32_t any = 0;
-        for (uint32_t k = 0; k < ct.n; k++) any |= ct.t[k][r];
-        return any != 0u;
-    }
-};
-struct EmitCol {
-    uint32_t *rank;
-    struct Pre {};
-    __device__ __forceinline__ Pre pre(uint64_t) const { return Pre(); }
-    __device__ __forceinline__ void operator()(uint64_t r, uint32_t o, Pre) const { rank[o] = (uint32_t)r; }
-};
 
 // ---- CRGPU_OPT_DENSE_BARCODE_KEYS: the BarcodeIndex of the tables as they stand (cr_types/src/barcode_index.rs:20-53) ------
 int cr_dense_ensure(crgpu_ctx *ctx) {
@@ -2314,7 +2127,7 @@ int cr_dense_ensure(crgpu_ctx *ctx) {
         }
     if (!D.d_fwd) CR_HIP(ctx, hipMalloc((void **)&D.d_fwd, (((size_t)W + 63) / 64) * sizeof(uint4)));
     if (!D.d_back) CR_HIP(ctx, hipMalloc((void **)&D.d_back, (size_t)W * sizeof(uint32_t)));
-    uint32_t *d_total = ctx->d_scalars + 16;
+    uint32_t *d_total = ctx->d_scalars + CR_SCALAR_TOTAL;
     uint32_t V = 0;
     {
         CrTimer t(ctx, CRGPU_T_KEYS);
@@ -2376,13 +2189,6 @@ __global__ __launch_bounds__(256) void k_csc(const uint32_t *__restrict__ col_ra
     }
 }
 
-struct MatrixDevImpl {
-    crgpu_matrix_dev view;
-    uint32_t *d_rank = nullptr;
-    long long *d_indptr = nullptr;
-    int32_t *d_indices = nullptr, *d_data = nullptr;
-};
-
 extern "C" int crgpu_assemble_matrix_dev(crgpu_ctx *ctx, const uint32_t *d_bc, const uint32_t *d_feature,
                                          const uint32_t *d_count, uint64_t n_triplets, crgpu_matrix_dev **out) {
     if (!ctx || !out) return CRGPU_EINVAL;
@@ -2410,7 +2216,7 @@ extern "C" int crgpu_assemble_matrix_dev(crgpu_ctx *ctx, const uint32_t *d_bc, c
     } guard{ctx, m};
     const uint32_t W = ctx->n_canon;
     CR_TRY(cr_pool_alloc(ctx, (void **)&m->d_rank, (size_t)W * sizeof(uint32_t)));
-    uint32_t *d_total = ctx->d_scalars + 16;
+    uint32_t *d_total = ctx->d_scalars + CR_SCALAR_TOTAL;
     uint32_t V = 0;
     {
         CrTimer t(ctx, CRGPU_T_MATRIX);
@@ -2478,6 +2284,9 @@ __global__ __launch_bounds__(256) void k_offsets_to_indptr(const uint32_t *__res
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n; i += stride)
         indptr[i] = i < n ? (long long)off[i] : (long long)total;
 }
+void cr_offsets_to_indptr(crgpu_ctx *ctx, const uint32_t *d_off, uint64_t n, uint32_t total, long long *d_indptr) {
+    hipLaunchKernelGGL(k_offsets_to_indptr, dim3(cr_grid(n + 1, 256)), dim3(256), 0, ctx->stream, d_off, n, total, d_indptr);
+}
 // a column position outside [0, V) (a device list is not checked on the host) is reported through *bad and reads nothing
 __global__ __launch_bounds__(256) void k_selected_lengths(const long long *__restrict__ indptr, const uint64_t *__restrict__ cols,
                                                           uint64_t n_sel, uint64_t V, const uint32_t *__restrict__ rank_in,
@@ -2514,7 +2323,7 @@ __global__ __launch_bounds__(256) void k_copy_columns(const long long *__restric
     }
 }
 
-static int new_matrix_dev(crgpu_ctx *ctx, uint64_t V, uint64_t nnz, MatrixDevImpl **out) {
+int cr_new_matrix_dev(crgpu_ctx *ctx, uint64_t V, uint64_t nnz, MatrixDevImpl **out) {
     MatrixDevImpl *m = new (std::nothrow) MatrixDevImpl();
     if (!m) return cr_fail(ctx, CRGPU_ENOMEM, "out of host memory");
     int rc = cr_pool_alloc(ctx, (void **)&m->d_rank, (V ? V : 1) * sizeof(uint32_t));
@@ -2546,7 +2355,7 @@ extern "C" int crgpu_sum_matrices_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *a,
                (unsigned long long)a->n_barcodes, (unsigned long long)b->n_barcodes);
     CR_REQUIRE(ctx, a->nnz + b->nnz < 0xFFFFFFFFull, CRGPU_ERANGE, "crgpu_sum_matrices_dev: too many entries");
     const uint64_t V = a->n_barcodes;
-    uint32_t *d_flag = ctx->d_scalars + 48, *d_total = ctx->d_scalars + 16;
+    uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, *d_total = ctx->d_scalars + CR_SCALAR_TOTAL;
     DevBuf cnt_b;
     CR_TRY(dmalloc(ctx, cnt_b, (V + 1) * sizeof(uint32_t)));
     uint32_t *cnt = cnt_b.as<uint32_t>();
@@ -2567,7 +2376,7 @@ extern "C" int crgpu_sum_matrices_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *a,
     CR_REQUIRE(ctx, !differ, CRGPU_EINVAL, "crgpu_sum_matrices_dev: the matrices hold different barcodes");
     CR_TRY(read_u32(ctx, d_total, &total));
     MatrixDevImpl *m = nullptr;
-    CR_TRY(new_matrix_dev(ctx, V, total, &m));
+    CR_TRY(cr_new_matrix_dev(ctx, V, total, &m));
     {
         CrTimer t(ctx, CRGPU_T_MATRIX);
         if (V) {
@@ -2575,7 +2384,7 @@ extern "C" int crgpu_sum_matrices_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *a,
             hipLaunchKernelGGL(k_sum_columns<true>, dim3(cr_grid(V, 256)), dim3(256), 0, ctx->stream, V, pa, a->d_indices, a->d_data, pb,
                                b->d_indices, b->d_data, (uint32_t *)nullptr, cnt, m->d_indices, m->d_data);
         }
-        hipLaunchKernelGGL(k_offsets_to_indptr, dim3(cr_grid(V + 1, 256)), dim3(256), 0, ctx->stream, cnt, V, total, m->d_indptr);
+        cr_offsets_to_indptr(ctx, cnt, V, total, m->d_indptr);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
             crgpu_matrix_dev_free(ctx, &m->view);
             return cr_fail(ctx, CRGPU_EHIP, "crgpu_sum_matrices_dev: kernel failed");
@@ -2591,7 +2400,7 @@ static int select_columns_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *a, const u
     DevBuf len_b, rank_b;
     CR_TRY(dmalloc(ctx, len_b, (n_cols + 1) * sizeof(uint32_t)));
     CR_TRY(dmalloc(ctx, rank_b, (n_cols ? n_cols : 1) * sizeof(uint32_t)));
-    uint32_t *d_total = ctx->d_scalars + 16, *d_bad = ctx->d_scalars + 48, total = 0, bad = 0;
+    uint32_t *d_total = ctx->d_scalars + CR_SCALAR_TOTAL, *d_bad = ctx->d_scalars + CR_SCALAR_FLAG, total = 0, bad = 0;
     const long long *pa = (const long long *)a->d_indptr;
     {
         CrTimer t(ctx, CRGPU_T_MATRIX, n_cols);
@@ -2606,7 +2415,7 @@ static int select_columns_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *a, const u
     CR_REQUIRE(ctx, !bad, CRGPU_EINVAL, "%s: a column is out of range", who);
     CR_TRY(read_u32(ctx, d_total, &total));
     MatrixDevImpl *m = nullptr;
-    CR_TRY(new_matrix_dev(ctx, n_cols, total, &m));
+    CR_TRY(cr_new_matrix_dev(ctx, n_cols, total, &m));
     {
         CrTimer t(ctx, CRGPU_T_MATRIX);
         if (n_cols) {
@@ -2614,8 +2423,7 @@ static int select_columns_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *a, const u
             hipLaunchKernelGGL(k_copy_columns, dim3(cr_grid(n_cols * 64, 256)), dim3(256), 0, ctx->stream, pa, d_cols, n_cols,
                                len_b.as<uint32_t>(), a->d_indices, a->d_data, m->d_indices, m->d_data);
         }
-        hipLaunchKernelGGL(k_offsets_to_indptr, dim3(cr_grid(n_cols + 1, 256)), dim3(256), 0, ctx->stream, len_b.as<uint32_t>(), n_cols,
-                           total, m->d_indptr);
+        cr_offsets_to_indptr(ctx, len_b.as<uint32_t>(), n_cols, total, m->d_indptr);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
             crgpu_matrix_dev_free(ctx, &m->view);
             return cr_fail(ctx, CRGPU_EHIP, "%s: kernel failed", who);
@@ -2703,8 +2511,8 @@ extern "C" int crgpu_counts_triplets(crgpu_ctx *ctx, const crgpu_counts *c, uint
 }
 
 // the molecule table on the host in the order ALIGN_AND_COUNT emits it: order[o] = device position of the o-th UmiCount
-static int molecule_order(crgpu_ctx *ctx, const crgpu_counts *c, std::vector<uint64_t> &keys, std::vector<uint32_t> &reads,
-                          std::vector<uint32_t> &order) {
+int cr_molecule_order(crgpu_ctx *ctx, const crgpu_counts *c, std::vector<uint64_t> &keys, std::vector<uint32_t> &reads,
+                      std::vector<uint32_t> &order) {
     const uint64_t nm = c->n_molecules;
     keys.resize(nm);
     reads.resize(nm);
@@ -2743,7 +2551,7 @@ extern "C" int crgpu_counts_molecules(crgpu_ctx *ctx, const crgpu_counts *c, uin
     if (!nm) return CRGPU_OK;
     std::vector<uint64_t> keys;
     std::vector<uint32_t> reads, order;
-    CR_TRY(molecule_order(ctx, c, keys, reads, order));
+    CR_TRY(cr_molecule_order(ctx, c, keys, reads, order));
     const KeyLayout &L = c->layout;
     auto fld = [&](uint64_t k, uint32_t sh, uint32_t bits) { return (uint32_t)((k >> sh) & (bits >= 64 ? ~0ull : ((1ull << bits) - 1))); };
     std::vector<uint32_t> back;
@@ -2773,7 +2581,7 @@ extern "C" int crgpu_counts_probe_idx(crgpu_ctx *ctx, const crgpu_counts *c, int
     CR_REQUIRE(ctx, probe_idx_out, CRGPU_EINVAL, "crgpu_counts_probe_idx: NULL output");
     std::vector<uint64_t> keys;
     std::vector<uint32_t> reads, order;
-    CR_TRY(molecule_order(ctx, c, keys, reads, order));
+    CR_TRY(cr_molecule_order(ctx, c, keys, reads, order));
     std::vector<int32_t> probe(nm);
     CR_TRY(crgpu_memcpy_d2h(ctx, probe.data(), c->d_mprobe, nm * sizeof(int32_t)));
     for (uint64_t o = 0; o < nm; o++) probe_idx_out[o] = probe[order[o]];
@@ -2817,7 +2625,7 @@ extern "C" int crgpu_counts_barcode_summary(crgpu_ctx *ctx, const crgpu_counts *
     }
     const uint64_t span = rank_hi - rank_lo;
     CR_TRY(dmalloc(ctx, rows_b, span * sizeof(crgpu_barcode_summary_row)));
-    uint32_t *d_total = ctx->d_scalars + 16;
+    uint32_t *d_total = ctx->d_scalars + CR_SCALAR_TOTAL;
     uint64_t n_rows = 0;
     for (uint32_t lib = 0; lib < slots && lib < CRGPU_MAX_LIB; lib++) {
         if (!ctx->wl[lib].set) continue;
@@ -2872,13 +2680,19 @@ extern "C" void crgpu_counts_free(crgpu_ctx *ctx, crgpu_counts *c) {
 // trimmed list; MERGE_MOLECULES' join (cr_aggr/src/merge_molecules.rs:131-330) then concatenates the samples with
 // barcode_idx shifted by the number of barcodes retained before (bc_idx_offsets).  The H5 container, the gem-group /
 // library look-up tables (two tiny maps applied per row) and the metrics JSON stay with the host.
-__global__ __launch_bounds__(256) void k_mark_u64(const uint64_t *__restrict__ idx, uint64_t n, uint64_t limit, uint8_t *__restrict__ flag,
-                                                  uint32_t *__restrict__ bad) {
+// flag[c] = 1 for the listed columns (flag == NULL: the list is only checked); bad: a column out of range.  Also the cells of
+// EmptyDrops and of the Flex GEM passes (cr_mark_columns, stage_common.h)
+__global__ __launch_bounds__(256) void k_mark_columns(const uint64_t *__restrict__ cols, uint64_t n, uint64_t V, uint8_t *__restrict__ flag,
+                                                      uint32_t *__restrict__ bad) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const uint64_t v = idx[i];
-        if (v < limit) flag[v] = 1; else *bad = 1u;
+    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += stride) {
+        const uint64_t c = cols[k];
+        if (c >= V) *bad = 1u;
+        else if (flag) flag[c] = 1u;
     }
+}
+void cr_mark_columns(crgpu_ctx *ctx, const uint64_t *d_cols, uint64_t n, uint64_t V, uint8_t *d_flag, uint32_t *d_bad) {
+    hipLaunchKernelGGL(k_mark_columns, dim3(cr_grid(n, 256)), dim3(256), 0, ctx->stream, d_cols, n, V, d_flag, d_bad);
 }
 struct EmitRetained {
     uint32_t *retained, *newpos;
@@ -2911,7 +2725,7 @@ extern "C" int crgpu_trim_molecule_barcodes_dev(crgpu_ctx *ctx, uint64_t *d_barc
     CR_TRY(dmalloc(ctx, ret_b, (n_barcodes + 1) * sizeof(uint32_t)));
     CR_TRY(dmalloc(ctx, pos_b, (n_barcodes + 1) * sizeof(uint32_t)));
     uint8_t *flag = flag_b.as<uint8_t>();
-    uint32_t *d_bad = ctx->d_scalars + 60, *d_total = ctx->d_scalars + 16, bad = 0, kept = 0;
+    uint32_t *d_bad = ctx->d_scalars + CR_SCALAR_BAD_INDEX, *d_total = ctx->d_scalars + CR_SCALAR_TOTAL, bad = 0, kept = 0;
     {
         CrTimer t(ctx, CRGPU_T_MATRIX, n_molecules);
         CR_HIP(ctx, hipMemsetAsync(flag, 0, n_barcodes + 1, ctx->stream));
@@ -2919,11 +2733,10 @@ extern "C" int crgpu_trim_molecule_barcodes_dev(crgpu_ctx *ctx, uint64_t *d_barc
         if (n_pass) {
             CR_TRY(dmalloc(ctx, pf_b, n_pass * sizeof(uint64_t)));
             CR_HIP(ctx, hipMemcpyAsync(pf_b.p, pass_filter_idx_inout, n_pass * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-            hipLaunchKernelGGL(k_mark_u64, dim3(cr_grid(n_pass, 256)), dim3(256), 0, ctx->stream, pf_b.as<uint64_t>(), n_pass, n_barcodes, flag, d_bad);
+            cr_mark_columns(ctx, pf_b.as<uint64_t>(), n_pass, n_barcodes, flag, d_bad);
         }
         if (!pass_only && n_molecules)
-            hipLaunchKernelGGL(k_mark_u64, dim3(cr_grid(n_molecules, 256)), dim3(256), 0, ctx->stream, d_barcode_idx_inout, n_molecules,
-                               n_barcodes, flag, d_bad);
+            cr_mark_columns(ctx, d_barcode_idx_inout, n_molecules, n_barcodes, flag, d_bad);
         CR_HIP(ctx, hipGetLastError());
         if (n_barcodes)
             CR_TRY(compact(ctx, CandFlag{flag}, EmitRetained{ret_b.as<uint32_t>(), pos_b.as<uint32_t>()}, n_barcodes, ctx->d_sort_hist, d_total));
@@ -2940,8 +2753,7 @@ extern "C" int crgpu_trim_molecule_barcodes_dev(crgpu_ctx *ctx, uint64_t *d_barc
             DevBuf chk_b;
             CR_TRY(dmalloc(ctx, chk_b, n_barcodes + 1));
             CR_HIP(ctx, hipMemsetAsync(chk_b.p, 0, n_barcodes + 1, ctx->stream));
-            hipLaunchKernelGGL(k_mark_u64, dim3(cr_grid(n_molecules, 256)), dim3(256), 0, ctx->stream, d_barcode_idx_inout, n_molecules,
-                               n_barcodes, chk_b.as<uint8_t>(), d_bad);
+            cr_mark_columns(ctx, d_barcode_idx_inout, n_molecules, n_barcodes, chk_b.as<uint8_t>(), d_bad);
             std::vector<uint8_t> used(n_barcodes), keep(n_barcodes);
             CR_TRY(crgpu_memcpy_d2h(ctx, used.data(), chk_b.p, n_barcodes));
             CR_TRY(crgpu_memcpy_d2h(ctx, keep.data(), flag, n_barcodes));
@@ -2969,13 +2781,3 @@ extern "C" int crgpu_trim_molecule_barcodes_dev(crgpu_ctx *ctx, uint64_t *d_barc
     *n_retained_out = kept;
     return CRGPU_OK;
 }
-
-#include "probe_counts.h"
-#include "cell_calling.h"
-#include "emptydrops.h"
-#include "subsample.h"
-#include "normalize_depth.h"
-#include "multigenome.h"
-#include "rtl_tags.h"
-#include "matrix_summary.h"
-#include "aggregates.h"

@@ -1,5 +1,5 @@
-// emptydrops.h -- the non-ambient ("EmptyDrops") barcodes behind the initial cell call (part of dedup.hip, after cell_calling.h:
-// uses its sort keys, the compaction and the device matrices).
+// emptydrops.h -- the non-ambient ("EmptyDrops") barcodes behind the initial cell call (part of matrix_stages.hip: the sort
+// keys are those of cell_calling.h).
 //
 // Replaces find_nonambient_barcodes (lib/python/cellranger/cell_calling.py:144-263) with est_background_profile_sgt /
 // estimate_profile_sgt (:47-102), sgt_proportions / simple_good_turing (sgt.py:24-132), eval_multinomial_loglikelihoods
@@ -20,10 +20,14 @@
 //   7. p-values, BH     n_lower (integers, from the device) -> (1 + n_lower) / (1 + S); p takes at most S + 1 values, so BH is
 //                       a histogram of n_lower and a running minimum over its S + 1 levels: host, O(candidates + S);
 //   8. merge            initial cells and non-ambient candidates are both ascending and disjoint: one merge on the host.
+#pragma once
+
 #include <algorithm>
 #include <cmath>
 
+#include "cell_calling.h"
 #include "philox.h"
+#include "stage_common.h"
 
 #define ED_SIM_THREADS 1024
 #define ED_LDS_BYTES (160u * 1024u - 64u)  // dynamic LDS a workgroup of k_ed_simulate may take (its static part is 24 bytes)
@@ -152,15 +156,6 @@ __global__ __launch_bounds__(256) void k_ed_ambient_rows(const uint32_t *__restr
             const uint32_t f = (uint32_t)indices[i];
             if (f < n_features && data[i] > 0 && (!mask || mask[f])) atomicAdd(&rowsum[f], (unsigned long long)data[i]);
         }
-    }
-}
-
-__global__ __launch_bounds__(256) void k_ed_mark_cells(const uint64_t *__restrict__ cols, uint64_t n, uint64_t V, uint8_t *__restrict__ is_cell,
-                                                       uint32_t *__restrict__ flag) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += stride) {
-        const uint64_t c = cols[k];
-        if (c < V) is_cell[c] = 1; else *flag = 1u;
     }
 }
 
@@ -561,7 +556,7 @@ static int ed_run(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const uint8_t *feat
                   crgpu_emptydrops_result *res, crgpu_emptydrops_arrays *out) {
     const uint64_t V = m->n_barcodes;
     const long long *indptr = (const long long *)m->d_indptr;
-    uint32_t *d_flag = ctx->d_scalars + 48, *d_total = ctx->d_scalars + 16, *d_aux = ctx->d_scalars + 49, flag = 0;
+    uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, *d_total = ctx->d_scalars + CR_SCALAR_TOTAL, *d_aux = ctx->d_scalars + CR_SCALAR_FLAG_AUX, flag = 0;
     std::vector<uint64_t> cells(n_cells);
     if (n_cells) CR_TRY(crgpu_memcpy_d2h(ctx, cells.data(), d_cell_cols, n_cells * sizeof(uint64_t)));
     for (uint64_t i = 0; i < n_cells; i++)
@@ -665,7 +660,7 @@ static int ed_run(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const uint8_t *feat
     DevBuf cell_b;
     CR_TRY(dmalloc(ctx, cell_b, V));
     CR_HIP(ctx, hipMemsetAsync(cell_b.p, 0, V, ctx->stream));
-    hipLaunchKernelGGL(k_ed_mark_cells, dim3(cr_grid(n_cells, 256)), dim3(256), 0, ctx->stream, d_cell_cols, n_cells, V, cell_b.as<uint8_t>(), d_flag);
+    cr_mark_columns(ctx, d_cell_cols, n_cells, V, cell_b.as<uint8_t>(), d_flag);
     CR_HIP(ctx, hipGetLastError());
     if (thr <= 0xFFFFFFFFull) {
         CR_TRY(cr_pool_alloc(ctx, (void **)&out->d_eval_cols, V * sizeof(uint64_t)));

@@ -280,7 +280,7 @@ extern "C" int crgpu_match_features_dev(crgpu_ctx *ctx, int pattern, const uint3
     // p_edit[qv] = 10^(-qv/10) for qv = 0..33, host libm as in feature_extraction.rs:45
     double pe[34];
     for (int q = 0; q < 34; q++) pe[q] = std::pow(10.0, -(double)q / 10.0);
-    double *d_pe = (double *)(ctx->d_scalars + 128);  // 34 doubles inside the 4 KB scalar page
+    double *d_pe = (double *)(ctx->d_scalars + CR_SCALAR_ERROR_PROBS);  // 34 doubles inside the 4 KB scalar page
     CR_HIP(ctx, hipMemcpyAsync(d_pe, pe, sizeof(pe), hipMemcpyHostToDevice, ctx->stream));
     CR_HIP(ctx, hipStreamSynchronize(ctx->stream));  // pe is a stack buffer
     PatView v{P.d_seq, P.d_index, P.has_dist ? P.d_dist : nullptr, P.n, P.len};

@@ -1033,8 +1033,8 @@ extern "C" int crgpu_extract_features_dev(crgpu_ctx *ctx, int extractor, const u
     cr_invalidate_range(ctx, d_capture_out, n * sizeof(uint32_t));
     double pe[34];
     for (int q = 0; q < 34; q++) pe[q] = std::pow(10.0, -(double)q / 10.0);  // host libm as in :45
-    double *d_pe = (double *)(ctx->d_scalars + 128);
-    uint32_t *d_nq = ctx->d_scalars + 16;
+    double *d_pe = (double *)(ctx->d_scalars + CR_SCALAR_ERROR_PROBS);
+    uint32_t *d_nq = ctx->d_scalars + CR_SCALAR_TOTAL;
     CR_HIP(ctx, hipMemcpyAsync(d_pe, pe, sizeof(pe), hipMemcpyHostToDevice, ctx->stream));
     CR_HIP(ctx, hipMemsetAsync(d_nq, 0, sizeof(uint32_t), ctx->stream));
     CR_HIP(ctx, hipStreamSynchronize(ctx->stream));  // pe is a stack buffer
@@ -1091,7 +1091,7 @@ extern "C" int crgpu_extract_features_dev(crgpu_ctx *ctx, int extractor, const u
             const size_t half_bytes = P.halves ? (size_t)X.t_n_feat * 24 : 0;
             // first pass of the two-pass flow (no distribution, by-products allowed): keep the captures without exact feature
             FxtPending *d_recs = (FxtPending *)resume.d_recs;
-            unsigned long long *d_rec_count = (unsigned long long *)(ctx->d_scalars + 66);
+            unsigned long long *d_rec_count = (unsigned long long *)(ctx->d_scalars + CR_SCALAR_REC_COUNT);
             uint64_t rec_cap = 0, n_recs_in = resume.valid ? resume.n_recs : 0;
             void *new_recs = nullptr;
             const bool record = ctx->trust_buffers && !X.has_dist && !resume.valid && n >= 4096 && !getenv("CRGPU_FXT_NO_RESUME");

@@ -1,5 +1,4 @@
-// matrix_summary.h -- the summary metrics of the filtered matrix on the device (part of dedup.hip, behind rtl_tags.h: uses its
-// rt_wave_sum, the radix sort, DevBuf).
+// matrix_summary.h -- the summary metrics of the filtered matrix on the device (part of matrix_stages.hip).
 //
 // Replaces the matrix arithmetic of report_genomes -> _report / _report_genome_agnostic_metrics
 // (lib/python/cellranger/rna/report_matrix.py:76-387): sum_masked / count_ge_masked of the views (feature mask x barcode mask) of
@@ -21,8 +20,12 @@
 //      are gathered from it.  Top features and genes detected are host work over the per-feature arrays.
 // With ctx->ms_lds_features == 0 the per-feature counters are u64 atomics in device memory (the A/B of the slice form).
 // The floats of _report come from the integers on the host (crgpu_matrix_summary_stats): f64, unfused.
+#pragma once
+
 #include <algorithm>
 #include <cmath>
+
+#include "stage_common.h"
 
 #define MS_NONE 0xFFu
 #define MS_WG 1024u                                 // threads of a pass workgroup: 16 waves, one column each
@@ -53,27 +56,6 @@ __global__ __launch_bounds__(256) void k_ms_cell_index(const uint64_t *__restric
         if (k && cols[k - 1] >= c) atomicOr(flag, 2u);
         cellidx[c] = (uint32_t)k + 1u;
     }
-}
-
-__device__ __forceinline__ uint32_t ms_wave_sum32(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
-// the first i in [lo, hi) with idx[i] >= target (hi: none), idx ascending there; 64 samples per round.  Every position read lies in
-// [lo, hi) whatever the order of idx.
-__device__ __forceinline__ long long ms_lower_bound(const int32_t *__restrict__ idx, long long lo, long long hi, uint32_t target, uint32_t lane) {
-    while (hi > lo) {
-        const long long step = (hi - lo + 63) / 64, p = lo + (long long)lane * step;
-        const bool less = p < hi && (uint32_t)idx[p] < target;
-        const long long cnt = __popcll(__ballot(less));
-        if (!cnt) return lo;
-        const long long nlo = lo + (cnt - 1) * step + 1, nhi = lo + cnt * step;
-        lo = nlo;
-        hi = nhi < hi ? nhi : hi;
-    }
-    return lo;
 }
 
 template <int NC, bool LDS>
@@ -112,8 +94,8 @@ __global__ __launch_bounds__(MS_WG) void k_ms_pass(const long long *__restrict__
         if (b >= e) continue;
         const uint32_t mask = ci ? cellmask[ci - 1u] : 0u;
         if (LDS && e - b > 64) {
-            if (lo > 0u) b = ms_lower_bound(indices, b, e, lo, lane);
-            if (hi < n_features) e = ms_lower_bound(indices, b, e, hi, lane);
+            if (lo > 0u) b = wave_lower_bound(indices, b, e, lo, lane);
+            if (hi < n_features) e = wave_lower_bound(indices, b, e, hi, lane);
         }
         unsigned long long acc[NC];
         uint32_t nz[NC];
@@ -156,8 +138,8 @@ __global__ __launch_bounds__(MS_WG) void k_ms_pass(const long long *__restrict__
 #pragma unroll
         for (int k = 0; k < NC; k++) {
             if ((uint32_t)k >= n_classes || !__ballot(acc[k] != 0ull || nz[k] != 0u)) continue;  // uniform
-            const unsigned long long sum = rt_wave_sum(acc[k]);
-            const uint32_t n = ms_wave_sum32(nz[k]);
+            const unsigned long long sum = wave_sum(acc[k]);
+            const uint32_t n = wave_sum(nz[k]);
             const bool own = (mask >> k) & 1u;
             if (lane == (uint32_t)k) {
                 t_raw += sum;
@@ -171,7 +153,7 @@ __global__ __launch_bounds__(MS_WG) void k_ms_pass(const long long *__restrict__
         }
     }
     if (bad) atomicOr(flag, 1u);
-    seen = ms_wave_sum32(seen);
+    seen = wave_sum(seen);
     if (lane == 0u && seen) atomicAdd(&s_tot[MS_T_SEEN], (unsigned long long)seen);
     if (lane < n_classes) {
         unsigned long long *t = s_tot + lane * MS_T_WORDS;
@@ -219,7 +201,7 @@ __global__ __launch_bounds__(256) void k_ms_reads(const uint32_t *__restrict__ r
         listed += r;
         for (uint32_t mk = cellmask[ci - 1u]; mk && r; mk &= mk - 1u) atomicAdd(&s_out[2 + __builtin_ctz(mk)], (unsigned long long)r);
     }
-    all = rt_wave_sum(all), listed = rt_wave_sum(listed);
+    all = wave_sum(all), listed = wave_sum(listed);
     if ((threadIdx.x & 63u) == 0u) {
         if (all) atomicAdd(&s_out[0], all);
         if (listed) atomicAdd(&s_out[1], listed);
@@ -359,7 +341,7 @@ extern "C" int crgpu_matrix_summary_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *
         CR_HIP(ctx, hipMemsetAsync(idx_b.p, 0, V * sizeof(uint32_t), ctx->stream));
         CR_TRY(dmalloc(ctx, mask_b, h_mask.size() * sizeof(uint32_t)));
         CR_TRY(crgpu_memcpy_h2d(ctx, mask_b.p, h_mask.data(), h_mask.size() * sizeof(uint32_t)));
-        uint32_t *d_flag = ctx->d_scalars + 48, flag[3] = {0, 0, 0};  // the list, the pass, the per-cell sums
+        uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, flag[3] = {0, 0, 0};  // the list, the pass, the per-cell sums
         CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(flag), ctx->stream));
         if (n_cells) {
             hipLaunchKernelGGL(k_ms_cell_index, dim3(cr_grid(n_cells, 256)), dim3(256), 0, ctx->stream, d_cell_cols, n_cells, V, idx_b.as<uint32_t>(), d_flag);
@@ -550,7 +532,7 @@ extern "C" int crgpu_matrix_dev_reads_per_column(crgpu_ctx *ctx, const crgpu_mat
     const uint64_t V = m->n_barcodes;
     if (!V) return CRGPU_OK;
     CR_REQUIRE(ctx, d_out != nullptr, CRGPU_EINVAL, "crgpu_matrix_dev_reads_per_column: NULL output");
-    uint32_t *d_flag = ctx->d_scalars + 48, flag = 0;
+    uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, flag = 0;
     CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
     {
         CrTimer t(ctx, CRGPU_T_MATRIX, V);
@@ -564,7 +546,6 @@ extern "C" int crgpu_matrix_dev_reads_per_column(crgpu_ctx *ctx, const crgpu_mat
 }
 
 // ---- the floats of _report (host, f64, unfused; no context) -----------------------------------------------------------------------
-static inline double ms_robust_divide(double a, double b) { return b == 0.0 ? std::nan("") : a / b; }
 // np.percentile(x, 25 i) of n sorted values from x[floor((n - 1) i / 4)] = a and its right neighbour b (numpy's _lerp)
 static inline double ms_percentile(uint64_t n, uint32_t i, uint32_t a, uint32_t b) {
     const double t = (double)((n - 1) * i % 4) / 4.0, d = (double)b - (double)a;
@@ -581,7 +562,7 @@ static void ms_summarize(uint64_t n, uint64_t sum, uint64_t sq_hi, uint64_t sq_l
     const unsigned __int128 sq = ((unsigned __int128)sq_hi << 64) | sq_lo, s2 = (unsigned __int128)sum * sum;
     const unsigned __int128 num = (unsigned __int128)n * sq - s2;  // n sum(x^2) - (sum x)^2 >= 0, exact: n < 2^32, sum(x^2) < 2^96
     *stddev = std::sqrt((double)num / ((double)n * (double)n));
-    *cv = ms_robust_divide(*stddev, *mean);
+    *cv = cr_robust_divide(*stddev, *mean);
 }
 
 extern "C" int crgpu_matrix_summary_stats(const crgpu_matrix_summary_class *c, uint64_t reads_cells, uint64_t reads_all, crgpu_matrix_summary_floats *out) {
@@ -593,10 +574,10 @@ extern "C" int crgpu_matrix_summary_stats(const crgpu_matrix_summary_class *c, u
     ms_summarize(c->n_cells, c->genes_sum, c->genes_sumsq_hi, c->genes_sumsq_lo, c->genes_q, &out->genes_mean, &out->genes_median, &out->genes_cv,
                  &out->genes_iqr, &out->genes_std);
     // (the products of the reference are Python integers, rounded once by float())
-    out->density = ms_robust_divide((double)c->cells_nnz, (double)((unsigned __int128)c->n_features_class * c->n_cells));
-    out->cum_frac = ms_robust_divide((double)c->cells_total_counts, (double)c->raw_total_counts);
-    out->dupe_frac = 1.0 - ms_robust_divide((double)c->cells_total_counts, (double)reads_cells);
-    out->reads_per_cell = ms_robust_divide((double)reads_cells, (double)c->n_cells);
-    out->reads_cum_frac = ms_robust_divide((double)reads_cells, (double)reads_all);
+    out->density = cr_robust_divide((double)c->cells_nnz, (double)((unsigned __int128)c->n_features_class * c->n_cells));
+    out->cum_frac = cr_robust_divide((double)c->cells_total_counts, (double)c->raw_total_counts);
+    out->dupe_frac = 1.0 - cr_robust_divide((double)c->cells_total_counts, (double)reads_cells);
+    out->reads_per_cell = cr_robust_divide((double)reads_cells, (double)c->n_cells);
+    out->reads_cum_frac = cr_robust_divide((double)reads_cells, (double)reads_all);
     return CRGPU_OK;
 }

@@ -355,7 +355,7 @@ extern "C" int crgpu_fastq_to_rows_dev(crgpu_ctx *ctx, const uint8_t *d_text, ui
     uint64_t tile = (n_bytes + nb - 1) / nb;
     tile = (tile + 255) / 256 * 256;
     nb = (n_bytes + tile - 1) / tile;
-    uint32_t *d_block = nullptr, *d_pos = nullptr, *d_total = ctx->d_scalars + 16, *d_bad = ctx->d_scalars + 60;
+    uint32_t *d_block = nullptr, *d_pos = nullptr, *d_total = ctx->d_scalars + CR_SCALAR_TOTAL, *d_bad = ctx->d_scalars + CR_SCALAR_BAD_INDEX;
     CR_TRY(cr_pool_alloc(ctx, (void **)&d_block, (nb + 1) * sizeof(uint32_t)));
     uint32_t n_lf = 0;
     int rc = CRGPU_OK;

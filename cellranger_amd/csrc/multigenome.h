@@ -1,5 +1,5 @@
 // multigenome.h -- GEM classes, the multiplet bootstrap and the count purities of a multi-genome well on the device (part of
-// dedup.hip, behind cell_calling.h: uses its generator, its draw compaction, its batches and its row scan).
+// matrix_stages.hip: the generator, the draw compaction, the batches and the row scan are those of cell_calling.h).
 //
 // Replaces MultiGenomeAnalysis.run_all (lib/python/cellranger/analysis/multigenome.py:251-335): classify_gems (:138-177),
 // _infer_multiplets (:209-249), infer_multiplets_from_observed (:113-135) and the mean purities of compute_count_purity (:80-98).
@@ -22,8 +22,13 @@
 //   4. the unresampled input is a row of ones through the same kernel, which then also writes the call per barcode and the sums
 //      of the purities; the summary of the samples is host f64 (crgpu_multigenome_summary).
 // Multiplicities and their running sums are u32: a row sums to n < 2^31.  f64 is unfused (-ffp-contract=off, as everywhere).
+#pragma once
+
 #include <algorithm>
 #include <cmath>
+
+#include "cell_calling.h"
+#include "stage_common.h"
 
 // ---- per-genome totals of a device matrix ----------------------------------------------------------------------------------------
 // flag: a row outside feature_genome
@@ -60,7 +65,7 @@ extern "C" int crgpu_matrix_dev_genome_totals(crgpu_ctx *ctx, const crgpu_matrix
     if (n_features) CR_TRY(crgpu_memcpy_h2d(ctx, fg_b.p, feature_genome, n_features));
     CR_TRY(dmalloc(ctx, tot_b, 256 * sizeof(unsigned long long)));
     CR_HIP(ctx, hipMemsetAsync(tot_b.p, 0, 256 * sizeof(unsigned long long), ctx->stream));
-    uint32_t *d_flag = ctx->d_scalars + 48, flag = 0;
+    uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, flag = 0;
     CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
     {
         CrTimer t(ctx, CRGPU_T_MATRIX, m->nnz);
@@ -330,7 +335,6 @@ static double mg_percentile_sorted(const std::vector<double> &s, double q) {
     const size_t lo = (size_t)fl, hi = lo + 1 < M ? lo + 1 : M - 1;
     return mg_lerp(s[lo], s[hi], v - fl);
 }
-static inline double mg_robust_divide(double a, double b) { return b == 0.0 ? std::nan("") : a / b; }
 
 extern "C" int crgpu_multigenome_summary(const int64_t *boot_counts, uint32_t bootstraps, uint64_t n, double *boot_out,
                                          crgpu_multigenome_result *res) {
@@ -343,14 +347,14 @@ extern "C" int crgpu_multigenome_summary(const int64_t *boot_counts, uint32_t bo
     res->n = n;
     res->boot_mean = mean;
     res->inferred_multiplets = (int64_t)std::nearbyint(mean);  // round(): half to even
-    res->multiplet_rate = mg_robust_divide(mean, dn);
-    res->normalized_multiplet_rate = 1000.0 * mg_robust_divide(res->multiplet_rate, dn);
+    res->multiplet_rate = cr_robust_divide(mean, dn);
+    res->normalized_multiplet_rate = 1000.0 * cr_robust_divide(res->multiplet_rate, dn);
     res->multiplet_rate_lb = res->multiplet_rate_ub = 0.0;
     res->rate_bounds_set = bootstraps > 1;
     if (bootstraps > 1) {
         std::sort(boot.begin(), boot.end());
-        res->multiplet_rate_lb = mg_robust_divide(mg_percentile_sorted(boot, 2.5 / 100.0), dn);
-        res->multiplet_rate_ub = mg_robust_divide(mg_percentile_sorted(boot, 97.5 / 100.0), dn);
+        res->multiplet_rate_lb = cr_robust_divide(mg_percentile_sorted(boot, 2.5 / 100.0), dn);
+        res->multiplet_rate_ub = cr_robust_divide(mg_percentile_sorted(boot, 97.5 / 100.0), dn);
     }
     return CRGPU_OK;
 }
@@ -486,9 +490,9 @@ extern "C" int crgpu_multigenome_dev(crgpu_ctx *ctx, const uint32_t *d_counts0, 
     res->sum_all_genome1 = h_sums[2] + h_sums[3];
     res->sum_max_single = h_sums[0] + h_sums[3];  // genome0: c0 >= c1, genome1: c1 > c0
     res->sum_all_single = res->sum_all_genome0 + res->sum_all_genome1;
-    res->purity0 = mg_robust_divide((double)res->sum_c0_genome0, (double)res->sum_all_genome0);
-    res->purity1 = mg_robust_divide((double)res->sum_c1_genome1, (double)res->sum_all_genome1);
-    res->purity_overall = mg_robust_divide((double)res->sum_max_single, (double)res->sum_all_single);
+    res->purity0 = cr_robust_divide((double)res->sum_c0_genome0, (double)res->sum_all_genome0);
+    res->purity1 = cr_robust_divide((double)res->sum_c1_genome1, (double)res->sum_all_genome1);
+    res->purity_overall = cr_robust_divide((double)res->sum_max_single, (double)res->sum_all_single);
     res->generator_words = boot.words_made;
     return crgpu_multigenome_summary(boot_counts_out, B, n, nullptr, res);
 }

@@ -1,5 +1,5 @@
-// normalize_depth.h -- aggr's depth normalisation of one GEM well: the downsampled UMI matrix and the read sums (part of dedup.hip,
-// after subsample.h: works on crgpu_counts and shares the draw kernels, the position map, the compaction and the matrix assembly).
+// normalize_depth.h -- aggr's depth normalisation of one GEM well: the downsampled UMI matrix and the read sums (part of
+// molecule_stages.hip: works on crgpu_counts; the draw kernels and the position map are those of subsample.h).
 //
 // Replaces main / _update_metrics / _get_new_read_pairs / _get_matrix / summarize_read_matrix of NORMALIZE_DEPTH
 // (mro/rna/stages/aggregator/normalize_depth/__init__.py:229-263,316-368,387-517) for one chunk that holds the whole table of one
@@ -18,9 +18,15 @@
 //               pair contiguous, but a run may be one molecule or a whole barcode and crosses every tile edge, so nothing walks
 //               a run: the survivors (kept > 0) are compacted to their (barcode, feature) pairs, the heads of the compacted list
 //               (a pair that differs from its predecessor) are compacted to the triplets, and a triplet's count is the distance
-//               to the next head.  Both steps are the stable compaction of dedup.hip, whose totals are the survivor and triplet
+//               to the next head.  Both steps are the stable compaction of stage_common.h, whose totals are the survivor and triplet
 //               counts; the triplets leave in (barcode, feature) order for crgpu_assemble_matrix_dev.
 // Nothing is floating point on the device and nothing depends on timing or on the two thresholds of the draw.
+#pragma once
+
+#include "probe_counts.h"
+#include "stage_common.h"
+#include "subsample.h"
+
 #define ND_THREADS 256u
 #define ND_MAX_CLASSES 32u
 #define ND_SUM_RAW 0u                                 // [class]
@@ -60,12 +66,6 @@ struct NdTally {
     unsigned long long *sums;  // [ND_SUMS], zeroed
 };
 
-__device__ __forceinline__ unsigned long long nd_wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-
 __global__ __launch_bounds__(ND_THREADS) void k_nd_tally(NdTally a) {
     __shared__ unsigned long long s_sum[ND_SUMS];
     for (uint32_t j = threadIdx.x; j < ND_SUMS; j += ND_THREADS) s_sum[j] = 0ull;
@@ -89,7 +89,7 @@ __global__ __launch_bounds__(ND_THREADS) void k_nd_tally(NdTally a) {
         while (todo) {
             const uint32_t c = __shfl(cls, __ffsll((long long)todo) - 1);
             const bool mine = ok && cls == c;
-            const unsigned long long raw = nd_wave_sum(mine ? k : 0u), flt = nd_wave_sum((mine && cell) ? k : 0u);
+            const unsigned long long raw = wave_sum((unsigned long long)(mine ? k : 0u)), flt = wave_sum((unsigned long long)((mine && cell) ? k : 0u));
             if (lane == 0) {
                 if (raw) atomicAdd(&s_sum[ND_SUM_RAW + c], raw);
                 if (flt) atomicAdd(&s_sum[ND_SUM_FLT + c], flt);
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(ND_THREADS) void k_nd_tally(NdTally a) {
         while (todo) {
             const uint32_t l = __shfl(lib, __ffsll((long long)todo) - 1) & (CRGPU_MAX_LIB - 1u);
             const bool mine = ok && lib == l;
-            const unsigned long long r = nd_wave_sum(mine ? reads : 0u), kr = nd_wave_sum(mine ? k : 0u);
+            const unsigned long long r = wave_sum((unsigned long long)(mine ? reads : 0u)), kr = wave_sum((unsigned long long)(mine ? k : 0u));
             const unsigned long long km = (unsigned long long)__popcll(__ballot(mine && k > 0u));
             if (lane == 0) {
                 if (r) atomicAdd(&s_sum[ND_SUM_READS + l], r);
@@ -168,7 +168,7 @@ static int nd_run(crgpu_ctx *ctx, crgpu_counts *c, const crgpu_normalize_depth_a
     for (int64_t *p : {a->reads_per_lib, a->kept_reads_per_lib, a->kept_molecules_per_lib})
         if (p) memset(p, 0, (size_t)NL * sizeof(int64_t));
 
-    uint32_t *d_flag = ctx->d_scalars + 48, *d_total = ctx->d_scalars + 16, differ = 0;
+    uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, *d_total = ctx->d_scalars + CR_SCALAR_TOTAL, differ = 0;
     if (NC > 1) {
         CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
         hipLaunchKernelGGL(k_pc_not_ascending, dim3(cr_grid(NC, 256)), dim3(256), 0, ctx->stream, a->d_cell_ranks, NC, d_flag);
@@ -464,7 +464,7 @@ extern "C" int crgpu_select_features_dev(crgpu_ctx *ctx, const crgpu_matrix_dev 
     CR_TRY(dmalloc(ctx, row_b, (uint64_t)n_features * sizeof(uint32_t)));
     CR_TRY(crgpu_memcpy_h2d(ctx, row_b.p, new_row.data(), (uint64_t)n_features * sizeof(uint32_t)));
     CR_TRY(dmalloc(ctx, cnt_b, (V + 1) * sizeof(uint32_t)));
-    uint32_t *d_total = ctx->d_scalars + 16, *d_flag = ctx->d_scalars + 48, total = 0, bad = 0;
+    uint32_t *d_total = ctx->d_scalars + CR_SCALAR_TOTAL, *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, total = 0, bad = 0;
     const long long *pa = (const long long *)m->d_indptr;
     {
         CrTimer t(ctx, CRGPU_T_MATRIX, m->nnz);
@@ -479,7 +479,7 @@ extern "C" int crgpu_select_features_dev(crgpu_ctx *ctx, const crgpu_matrix_dev 
     CR_REQUIRE(ctx, !bad, CRGPU_EINVAL, "crgpu_select_features_dev: the matrix holds a row >= n_features (%u)", n_features);
     CR_TRY(read_u32(ctx, d_total, &total));
     MatrixDevImpl *o = nullptr;
-    CR_TRY(new_matrix_dev(ctx, V, total, &o));
+    CR_TRY(cr_new_matrix_dev(ctx, V, total, &o));
     {
         CrTimer t(ctx, CRGPU_T_MATRIX, m->nnz);
         if (V) {
@@ -487,7 +487,7 @@ extern "C" int crgpu_select_features_dev(crgpu_ctx *ctx, const crgpu_matrix_dev 
             hipLaunchKernelGGL(k_sf_write, dim3(cr_grid(V * 64, 256)), dim3(256), 0, ctx->stream, pa, m->d_indices, m->d_data, V, row_b.as<uint32_t>(),
                                n_features, cnt_b.as<uint32_t>(), o->d_indices, o->d_data);
         }
-        hipLaunchKernelGGL(k_offsets_to_indptr, dim3(cr_grid(V + 1, 256)), dim3(256), 0, ctx->stream, cnt_b.as<uint32_t>(), V, total, o->d_indptr);
+        cr_offsets_to_indptr(ctx, cnt_b.as<uint32_t>(), V, total, o->d_indptr);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
             crgpu_matrix_dev_free(ctx, &o->view);
             return cr_fail(ctx, CRGPU_EHIP, "crgpu_select_features_dev: kernel failed");

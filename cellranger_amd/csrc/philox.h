@@ -3,6 +3,7 @@
 // element q of np.random.Philox(counter=[0, s, 0, 0], key=[seed, 0]).random_raw() (numpy advances the counter before it
 // generates the first block).
 #pragma once
+#include <hip/hip_runtime.h>
 
 __device__ __forceinline__ void cr_philox4x64_10(unsigned long long c0, unsigned long long c1, unsigned long long k0, unsigned long long w[4]) {
     unsigned long long c2 = 0, c3 = 0, k1 = 0;

@@ -1,5 +1,5 @@
-// probe_counts.h -- probe x barcode counts of a Flex / RTL well.  The last part of dedup.hip's translation unit (included at
-// its end): it works on crgpu_counts and shares the compaction, the pooled temporaries and the device-matrix helpers.
+// probe_counts.h -- probe x barcode counts of a Flex / RTL well (part of molecule_stages.hip: it works on crgpu_counts and takes the
+// compaction, the pooled temporaries and the device-matrix helpers from stage_common.h).
 //
 // Replaces, per valid barcode of ALIGN_AND_COUNT (cr_lib/src/stages/align_and_count.rs:311-333):
 //   BcUmiInfo::probe_counts            cr_types/src/types.rs:190-204   (histogram of UmiCount::probe_idx, None dropped)
@@ -20,6 +20,10 @@
 //      umi_count = distance to the next boundary.
 // Every molecule of a segment is written by exactly one lane to a fixed place, and both compactions are stable: the output
 // does not depend on timing.  The only atomics on global memory hand out list slots and count segments per class.
+
+#pragma once
+
+#include "stage_common.h"
 
 #define PC_G8_CAP 8u
 #define PC_WAVE_CAP 64u
@@ -310,7 +314,7 @@ static int probe_triplets_ensure(crgpu_ctx *ctx, crgpu_counts *c, uint32_t n_pro
     const KeyLayout &L = c->layout;
     const uint64_t n_bc = c->d_back ? c->n_back : c->n_canon;
     const uint64_t seg_max = nm < n_bc ? nm : n_bc;
-    uint32_t *d_block = ctx->d_sort_hist, *d_total = ctx->d_scalars + 16;
+    uint32_t *d_block = ctx->d_sort_hist, *d_total = ctx->d_scalars + CR_SCALAR_TOTAL;
     DevBuf seg_b, ctl_b, sp_b;
     CR_TRY(dmalloc(ctx, seg_b, (seg_max + 1) * sizeof(uint32_t)));
     CR_TRY(dmalloc(ctx, ctl_b, PC_CTL_WORDS * sizeof(uint32_t)));
@@ -513,7 +517,7 @@ extern "C" int crgpu_assemble_probe_matrix_dev(crgpu_ctx *ctx, crgpu_counts *c, 
     CR_REQUIRE(ctx, d_sample_ranks || n_sample == 0, CRGPU_EINVAL, "crgpu_assemble_probe_matrix_dev: NULL sample ranks");
     CR_REQUIRE(ctx, n_sample < 0xFFFFFFFFull, CRGPU_ERANGE, "crgpu_assemble_probe_matrix_dev: too many barcodes");
     CR_TRY(probe_triplets_ensure(ctx, c, n_probes, "crgpu_assemble_probe_matrix_dev"));
-    uint32_t *d_total = ctx->d_scalars + 16, *d_flag = ctx->d_scalars + 48;
+    uint32_t *d_total = ctx->d_scalars + CR_SCALAR_TOTAL, *d_flag = ctx->d_scalars + CR_SCALAR_FLAG;
     // the columns: the sample's barcodes (BarcodeIndex::from_iter(sample_bcs), :190-196), or the context's BarcodeIndex
     DevBuf rank_b, first_b, len_b;
     uint64_t V = n_sample;
@@ -562,7 +566,7 @@ extern "C" int crgpu_assemble_probe_matrix_dev(crgpu_ctx *ctx, crgpu_counts *c, 
     }
     CR_TRY(read_u32(ctx, d_total, &total));
     MatrixDevImpl *m = nullptr;
-    CR_TRY(new_matrix_dev(ctx, V, total, &m));
+    CR_TRY(cr_new_matrix_dev(ctx, V, total, &m));
     {
         CrTimer t(ctx, CRGPU_T_MATRIX, total);
         if (V) {
@@ -571,7 +575,7 @@ extern "C" int crgpu_assemble_probe_matrix_dev(crgpu_ctx *ctx, crgpu_counts *c, 
                 hipLaunchKernelGGL(k_pc_fill_columns, dim3(cr_grid(V * 64, 256)), dim3(256), 0, ctx->stream, V, first_b.as<uint32_t>(),
                                    len_b.as<uint32_t>(), total, c->d_pt_probe, c->d_pt_count, m->d_indices, m->d_data);
         }
-        hipLaunchKernelGGL(k_offsets_to_indptr, dim3(cr_grid(V + 1, 256)), dim3(256), 0, ctx->stream, len_b.as<uint32_t>(), V, total, m->d_indptr);
+        cr_offsets_to_indptr(ctx, len_b.as<uint32_t>(), V, total, m->d_indptr);
         if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
             crgpu_matrix_dev_free(ctx, &m->view);
             return cr_fail(ctx, CRGPU_EHIP, "crgpu_assemble_probe_matrix_dev: kernel failed");
@@ -609,7 +613,7 @@ extern "C" int crgpu_probe_metrics_dev(crgpu_ctx *ctx, crgpu_counts *c, uint32_t
     CR_REQUIRE(ctx, d_cell_ranks || n_cells == 0, CRGPU_EINVAL, "crgpu_probe_metrics_dev: NULL cell ranks");
     CR_TRY(probe_triplets_ensure(ctx, c, n_probes, "crgpu_probe_metrics_dev"));
     if (!n_probes) return CRGPU_OK;
-    uint32_t *d_flag = ctx->d_scalars + 48, differ = 0;
+    uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, differ = 0;
     DevBuf sums_b;
     const uint64_t bytes = (uint64_t)n_probes * sizeof(unsigned long long);
     CR_TRY(dmalloc(ctx, sums_b, 2 * bytes));

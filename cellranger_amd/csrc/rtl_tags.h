@@ -1,5 +1,5 @@
 // rtl_tags.h -- multiplexed Flex (RTL) wells: the tag of every barcode, the columns of every sample, the gel-bead overlap of the probe
-// barcodes and the GEM occupancy on the device (part of dedup.hip, behind multigenome.h: uses compact, the radix sorts, DevBuf).
+// barcodes and the GEM occupancy on the device (part of matrix_stages.hip).
 //
 // Replaces CALL_TAGS_RTL (lib/rust/cr_lib/src/stages/call_tags_rtl.rs:143-498 with barcode_overlap.rs and
 // read_level_multiplexing.rs:22-68) and remove_bcs_from_high_occupancy_gems (lib/python/cellranger/cell_calling_helpers.py:315-424,
@@ -9,22 +9,17 @@
 // construct's last segment); columns ascend by rank, so the barcodes of one GEM are adjacent columns: a RUN.  Nothing here sorts
 // the matrix.  Everything reported is an integer summed with integer atomics (LDS first, one global atomic per workgroup and
 // table cell), or an f64 quotient of two such integers taken on the host: no result depends on the order of arrival.
+#pragma once
+
 #include <algorithm>
 #include <cmath>
+
+#include "stage_common.h"
 
 #define RT_MAX_TAGS CRGPU_RTL_MAX_TAGS
 #define RT_MAX_PROBES CRGPU_RTL_MAX_PROBES
 #define RT_MAX_TYPES CRGPU_RTL_MAX_TYPES
 #define RT_NONE 0xFFu
-
-__device__ __forceinline__ unsigned long long rt_wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t lo = __shfl_xor((uint32_t)v, d), hi = __shfl_xor((uint32_t)(v >> 32), d);
-        v += ((unsigned long long)hi << 32) | lo;
-    }
-    return v;
-}
 
 // the probe segment of the context's construct
 static int rt_n_probe(crgpu_ctx *ctx, const char *who, uint32_t *n_probe) {
@@ -93,7 +88,7 @@ __global__ __launch_bounds__(256) void k_rt_umi(const long long *__restrict__ in
 #pragma unroll
         for (int ty = 0; ty < RT_MAX_TYPES; ty++) {
             if ((uint32_t)ty >= n_types || !__ballot(acc[ty] != 0ull)) continue;  // uniform
-            const unsigned long long w = rt_wave_sum(acc[ty]);
+            const unsigned long long w = wave_sum(acc[ty]);
             if (lane == 0) atomicAdd(&s_umi[ty * RT_MAX_TAGS + t], w);
         }
     }
@@ -130,7 +125,7 @@ extern "C" int crgpu_rtl_tags_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, con
     const uint32_t n_out = RT_MAX_TAGS + RT_MAX_TYPES * RT_MAX_TAGS;
     CR_TRY(dmalloc(ctx, out_b, n_out * sizeof(unsigned long long)));
     CR_HIP(ctx, hipMemsetAsync(out_b.p, 0, n_out * sizeof(unsigned long long), ctx->stream));
-    uint32_t *d_flag = ctx->d_scalars + 48, flag[2] = {0, 0};
+    uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, flag[2] = {0, 0};
     CR_HIP(ctx, hipMemsetAsync(d_flag, 0, 2 * sizeof(uint32_t), ctx->stream));
     unsigned long long *d_out = out_b.as<unsigned long long>();
     {
@@ -217,7 +212,7 @@ extern "C" int crgpu_rtl_sample_columns_dev(crgpu_ctx *ctx, const uint8_t *d_tag
     for (DevBuf *b : {&key_b, &keyt_b, &val_b, &valt_b}) CR_TRY(dmalloc(ctx, *b, n * sizeof(uint32_t)));
     CR_TRY(dmalloc(ctx, cnt_b, 256 * sizeof(unsigned long long)));
     CR_HIP(ctx, hipMemsetAsync(cnt_b.p, 0, 256 * sizeof(unsigned long long), ctx->stream));
-    uint32_t *d_flag = ctx->d_scalars + 48, flag = 0;
+    uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, flag = 0;
     CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
     hipLaunchKernelGGL(k_rt_sample_keys, dim3(cr_grid(n, 256)), dim3(256), 0, ctx->stream, d_tags, V, d_cols, n, sot_b.as<uint8_t>(), n_samples,
                        key_b.as<uint32_t>(), val_b.as<uint32_t>(), cnt_b.as<unsigned long long>(), d_flag);
@@ -245,17 +240,6 @@ extern "C" int crgpu_rtl_sample_columns_dev(crgpu_ctx *ctx, const uint8_t *d_tag
 }
 
 // ---- 3. one pass over the runs: overlaps and GEM occupancy ---------------------------------------------------------------------
-// cell[c] = 1 for the listed columns (cell == NULL: the list is only checked); flag: a column out of range
-__global__ __launch_bounds__(256) void k_rt_cell_flags(const uint64_t *__restrict__ cols, uint64_t n, uint64_t V, uint8_t *__restrict__ cell,
-                                                       uint32_t *__restrict__ flag) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += stride) {
-        const uint64_t c = cols[k];
-        if (c >= V) *flag = 1u;
-        else if (cell) cell[c] = 1u;
-    }
-}
-
 // the table of k_rt_gem_runs (u64 words)
 #define RT_O_GEMS 0u                                          // [64] runs whose mask has the tag
 #define RT_O_COMMON (RT_O_GEMS + RT_MAX_TAGS)                 // [T * T], row-major, i < j
@@ -394,10 +378,10 @@ extern "C" int crgpu_rtl_gem_runs_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m,
     DevBuf cell_b, out_b, abt_b, abm_b;
     CR_TRY(dmalloc(ctx, cell_b, V));
     CR_HIP(ctx, hipMemsetAsync(cell_b.p, 0, V, ctx->stream));
-    uint32_t *d_flag = ctx->d_scalars + 48, flag = 0;
+    uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, flag = 0;
     CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
     if (n_cells) {
-        hipLaunchKernelGGL(k_rt_cell_flags, dim3(cr_grid(n_cells, 256)), dim3(256), 0, ctx->stream, d_cell_cols, n_cells, V, cell_b.as<uint8_t>(), d_flag);
+        cr_mark_columns(ctx, d_cell_cols, n_cells, V, cell_b.as<uint8_t>(), d_flag);
         CR_HIP(ctx, hipGetLastError());
     }
     CR_TRY(read_u32(ctx, d_flag, &flag));
@@ -504,9 +488,9 @@ extern "C" int crgpu_rtl_medians_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, 
     CR_REQUIRE(ctx, n_cells <= V, CRGPU_EINVAL, "crgpu_rtl_medians_dev: more cells than columns");
     if (!n_cells) return CRGPU_OK;
     CR_REQUIRE(ctx, d_sums && d_cell_cols, CRGPU_EINVAL, "crgpu_rtl_medians_dev: NULL d_sums or d_cell_cols");
-    uint32_t *d_flag = ctx->d_scalars + 48, flag = 0, *d_total = ctx->d_scalars + 16, N = 0;
+    uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, flag = 0, *d_total = ctx->d_scalars + CR_SCALAR_TOTAL, N = 0;
     CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
-    hipLaunchKernelGGL(k_rt_cell_flags, dim3(cr_grid(n_cells, 256)), dim3(256), 0, ctx->stream, d_cell_cols, n_cells, V, (uint8_t *)nullptr, d_flag);
+    cr_mark_columns(ctx, d_cell_cols, n_cells, V, nullptr, d_flag);
     CR_HIP(ctx, hipGetLastError());
     CR_TRY(read_u32(ctx, d_flag, &flag));
     CR_REQUIRE(ctx, !flag, CRGPU_EINVAL, "crgpu_rtl_medians_dev: a cell column is out of range");
@@ -656,7 +640,7 @@ __global__ __launch_bounds__(256) void k_rt_occupancy(const uint32_t *__restrict
         hi_gems += high && head;
         gems += head;
     }
-    hi_gems = rt_wave_sum(hi_gems), hi_cells = rt_wave_sum(hi_cells), gems = rt_wave_sum(gems);
+    hi_gems = wave_sum(hi_gems), hi_cells = wave_sum(hi_cells), gems = wave_sum(gems);
     if ((threadIdx.x & 63u) == 0) {
         if (hi_gems) atomicAdd(&counters[0], hi_gems);
         if (hi_cells) atomicAdd(&counters[1], hi_cells);
@@ -676,7 +660,6 @@ struct RtKeepEmit {
     __device__ __forceinline__ Pre pre(uint64_t k) const { return Pre{cols[k]}; }
     __device__ __forceinline__ void operator()(uint64_t, uint32_t o, Pre p) const { out[o] = p.c; }
 };
-static inline double rt_robust_divide(uint64_t a, uint64_t b) { return b ? (double)a / (double)b : std::nan(""); }
 
 extern "C" int crgpu_rtl_remove_high_occupancy_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const uint64_t *d_cell_cols, uint64_t n_cells,
                                                    uint32_t threshold, uint64_t **d_kept_cols_out, crgpu_rtl_high_occupancy *res) {
@@ -698,7 +681,7 @@ extern "C" int crgpu_rtl_remove_high_occupancy_dev(crgpu_ctx *ctx, const crgpu_m
         CR_TRY(dmalloc(ctx, keep_b, n_cells));
         CR_TRY(dmalloc(ctx, cnt_b, 4 * sizeof(unsigned long long)));
         CR_HIP(ctx, hipMemsetAsync(cnt_b.p, 0, 4 * sizeof(unsigned long long), ctx->stream));
-        uint32_t *d_flag = ctx->d_scalars + 48, flag = 0, *d_total = ctx->d_scalars + 16, kept = 0;
+        uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, flag = 0, *d_total = ctx->d_scalars + CR_SCALAR_TOTAL, kept = 0;
         CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
         {
             CrTimer t(ctx, CRGPU_T_MATRIX, n_cells);
@@ -724,8 +707,8 @@ extern "C" int crgpu_rtl_remove_high_occupancy_dev(crgpu_ctx *ctx, const crgpu_m
         CR_TRY(cr_pool_alloc(ctx, (void **)&d_out, sizeof(uint64_t)));
     }
     res->n_cells = n_cells;
-    res->fraction_cell_gems_high_occupancy = rt_robust_divide(res->high_occupancy_gems, res->gems_with_cells);
-    res->fraction_cells_in_high_occupancy_gems = rt_robust_divide(res->cells_in_high_occupancy_gems, res->n_cells);
+    res->fraction_cell_gems_high_occupancy = cr_robust_divide((double)res->high_occupancy_gems, (double)res->gems_with_cells);
+    res->fraction_cells_in_high_occupancy_gems = cr_robust_divide((double)res->cells_in_high_occupancy_gems, (double)res->n_cells);
     *d_kept_cols_out = d_out;
     return CRGPU_OK;
 }

@@ -1284,7 +1284,7 @@ int cr_repair_runs(crgpu_ctx *ctx, uint64_t *d_keys, uint32_t *d_vals, uint64_t 
     *fell_back = false;
     if (heads) heads->valid = false;
     if (n < 2 || low_bits == 0) return CRGPU_OK;
-    uint32_t *d_flag = ctx->d_scalars + 52, *d_set = ctx->d_scalars + 53, *d_nlong = ctx->d_scalars + 54, *d_nmed = ctx->d_scalars + 55;
+    uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_REPAIR, *d_set = d_flag + 1, *d_nlong = d_flag + 2, *d_nmed = d_flag + 3;
     const uint64_t n_words = (n + 63) / 64;
     void *d_desc = nullptr, *d_long = nullptr, *d_med = nullptr, *d_span = nullptr;
     CR_TRY(cr_pool_alloc(ctx, &d_desc, n_words * sizeof(unsigned long long)));
@@ -1499,7 +1499,7 @@ int cr_partition_by_owner_kv(crgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_o
         }
         col_bounds[0] = 0;
         col_bounds[n_ranks] = ctx->dense.V;
-        uint32_t *d_bounds = ctx->d_scalars + 760;
+        uint32_t *d_bounds = ctx->d_scalars + CR_SCALAR_OWNER_BOUNDS;
         CR_HIP(ctx, hipMemcpyAsync(d_bounds, col_bounds.data(), (n_ranks + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
         CR_HIP(ctx, hipStreamSynchronize(ctx->stream));
         CR_TRY((radix_pass<uint64_t, OwnerBounds>(ctx, d_in, d_out, d_vin, d_vout, n, OwnerBounds{sh_bc, n_ranks, d_bounds})));
@@ -1509,7 +1509,7 @@ int cr_partition_by_owner_kv(crgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_o
                    "partition: bounds must start at 0 and end at or beyond the whitelist size");
         for (uint32_t r = 0; r < n_ranks; r++)
             CR_REQUIRE(ctx, bounds[r] <= bounds[r + 1], CRGPU_EINVAL, "partition: bounds must be ascending");
-        uint32_t *d_bounds = ctx->d_scalars + 760;  // 257 u32 inside the 1024-word scalar page
+        uint32_t *d_bounds = ctx->d_scalars + CR_SCALAR_OWNER_BOUNDS;  // 257 u32 inside the 1024-word scalar page
         CR_HIP(ctx, hipMemcpyAsync(d_bounds, bounds, (n_ranks + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
         CR_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the caller's array may be a temporary
         CR_TRY((radix_pass<uint64_t, OwnerBounds>(ctx, d_in, d_out, d_vin, d_vout, n, OwnerBounds{sh_bc, n_ranks, d_bounds})));

@@ -1,0 +1,221 @@
+// stage_common.h -- what the count stage (dedup.hip) and the analysis stages behind it (molecule_stages.hip on a crgpu_counts,
+// matrix_stages.hip on a crgpu_matrix_dev) share: the two opaque result types, pooled temporaries, the stream compaction and
+// the few host functions one of these units defines for the others.
+#pragma once
+
+#include <cmath>
+
+#include "block_utils.h"
+#include "common.h"
+
+int cr_scan_small(crgpu_ctx *ctx, uint32_t *d_data, uint64_t n, uint32_t *d_total_out);  // sort.hip
+int cr_partition_by_owner(crgpu_ctx *ctx, const uint64_t *d_in, uint64_t *d_out, uint64_t n, uint32_t sh_bc,
+                          uint32_t n_ranks, const uint32_t *bounds, uint64_t *counts_out);  // sort.hip
+
+#define NONE32 0xFFFFFFFFu
+
+struct crgpu_counts {
+    uint64_t n_triplets = 0, n_molecules = 0;
+    uint32_t *d_bc = nullptr, *d_feature = nullptr, *d_count = nullptr;  // triplets
+    uint64_t *d_mkeys = nullptr;    // molecule keys (primary layout), n_molecules
+    uint32_t *d_mreads = nullptr;   // read_count of each molecule
+    uint32_t *d_corr_reads = nullptr;  // [library][barcode rank] reads whose UMI was corrected (BarcodeSummary), or NULL
+    uint32_t *d_filt_reads = nullptr;  // [library][barcode rank] reads of molecules the targeted-panel filter removed, or NULL
+    int32_t *d_mprobe = nullptr;    // probe_idx of each molecule's representative read (crgpu_records.d_probe_idx given), or NULL
+    uint32_t *d_back = nullptr;     // CRGPU_OPT_DENSE_BARCODE_KEYS: column -> whitelist rank of the barcode field of d_mkeys (n_back), else NULL
+    uint32_t n_back = 0;
+    uint32_t n_canon = 0;
+    KeyLayout layout;
+    // (barcode rank, probe_idx, umi_count) triplets, made on the first request (probe_counts.h) for pt_n_probes probes
+    bool pt_valid = false;
+    uint32_t pt_n_probes = 0;
+    uint64_t n_pt = 0;
+    uint32_t *d_pt_bc = nullptr, *d_pt_probe = nullptr, *d_pt_count = nullptr;
+    // device position -> position in the table crgpu_counts_molecules lists, made on the first subsampling of counts with
+    // several libraries or UMI lengths (subsample.h), else NULL
+    uint32_t *d_ss_pos = nullptr;
+    bool sharded = false;  // one rank's share of a well counted over several ranks (crgpu_count_records_sharded_dev)
+};
+
+struct MatrixDevImpl {
+    crgpu_matrix_dev view;
+    uint32_t *d_rank = nullptr;
+    long long *d_indptr = nullptr;
+    int32_t *d_indices = nullptr, *d_data = nullptr;
+};
+
+// Defined in dedup.hip for the stage units as well: a kernel that is not a template has one definition in one unit, and
+// another unit reaches it through a host function.
+// A matrix of V columns and nnz entries with nothing in it yet
+int cr_new_matrix_dev(crgpu_ctx *ctx, uint64_t V, uint64_t nnz, MatrixDevImpl **out);
+// launch only: indptr[i] = off[i] for i < n, indptr[n] = total
+void cr_offsets_to_indptr(crgpu_ctx *ctx, const uint32_t *d_off, uint64_t n, uint32_t total, long long *d_indptr);
+// launch only: flag[c] = 1 for every listed column c < V (flag == NULL: the list is only checked); *bad = 1 for a column >= V
+void cr_mark_columns(crgpu_ctx *ctx, const uint64_t *d_cols, uint64_t n, uint64_t V, uint8_t *d_flag, uint32_t *d_bad);
+// the molecule table on the host in the order ALIGN_AND_COUNT emits it: order[o] = device position of the o-th UmiCount
+int cr_molecule_order(crgpu_ctx *ctx, const crgpu_counts *c, std::vector<uint64_t> &keys, std::vector<uint32_t> &reads,
+                      std::vector<uint32_t> &order);
+
+// robust_divide of the reference's metrics: NaN for a zero denominator
+static inline double cr_robust_divide(double a, double b) { return b == 0.0 ? std::nan("") : a / b; }
+
+__device__ __forceinline__ uint64_t lowmask(uint32_t bits) { return bits >= 64 ? ~0ull : ((1ull << bits) - 1ull); }
+
+struct DevBuf {  // pooled temporary, returned to the context's pool at scope exit
+    crgpu_ctx *ctx = nullptr;
+    void *p = nullptr;
+    ~DevBuf() { cr_pool_free(ctx, p); }
+    template <typename T>
+    T *as() { return (T *)p; }
+};
+
+static inline int dmalloc(crgpu_ctx *ctx, DevBuf &b, uint64_t bytes) {
+    b.ctx = ctx;
+    return cr_pool_alloc(ctx, &b.p, bytes);
+}
+
+static inline int read_u32(crgpu_ctx *ctx, const uint32_t *d, uint32_t *h) {
+    return crgpu_memcpy_d2h(ctx, h, d, sizeof(uint32_t));
+}
+
+// ------------------------------------------------------------------------------------------------
+// generic two-pass stream compaction driven by a flag functor: out position of every flagged item
+// ------------------------------------------------------------------------------------------------
+#define CP_BLOCK 256
+#ifndef CP_ITEMS
+#define CP_ITEMS 8  // items per thread per round: their flag loads are all issued before the first compare
+#endif
+#define CP_ROUND (CP_BLOCK * CP_ITEMS)
+#define CP_WAVES (CP_BLOCK / 64)
+
+// Flags are evaluated at clamped indices and masked afterwards, so that the loads of a round are not chained
+// behind `i < hi` branches (one load in flight per wave left these passes at ~2 TB/s).
+template <typename Flag>
+__global__ __launch_bounds__(CP_BLOCK) void k_cp_count(Flag flag, uint64_t n, uint64_t tile, uint32_t *__restrict__ block_counts) {
+    __shared__ uint32_t ws[CP_WAVES];
+    const uint64_t lo = (uint64_t)blockIdx.x * tile;
+    const uint64_t hi = lo + tile < n ? lo + tile : n;
+    uint32_t c = 0;
+    for (uint64_t base = lo; base < hi; base += CP_ROUND) {
+        bool f[CP_ITEMS];
+#pragma unroll
+        for (int j = 0; j < CP_ITEMS; j++) {
+            const uint64_t i = base + (uint64_t)j * CP_BLOCK + threadIdx.x;
+            f[j] = flag(i < hi ? i : hi - 1);
+        }
+#pragma unroll
+        for (int j = 0; j < CP_ITEMS; j++) {
+            const uint64_t i = base + (uint64_t)j * CP_BLOCK + threadIdx.x;
+            c += (f[j] && i < hi) ? 1u : 0u;
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
+    if ((threadIdx.x & 63u) == 0) ws[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+        for (int w = 0; w < CP_WAVES; w++) t += ws[w];
+        block_counts[blockIdx.x] = t;
+    }
+}
+
+// Stable: inside a round the output order is (item slot, wave, lane) == ascending input index.
+template <typename Flag, typename Emit>
+__global__ __launch_bounds__(CP_BLOCK) void k_cp_write(Flag flag, Emit emit, uint64_t n, uint64_t tile,
+                                                       const uint32_t *__restrict__ block_offs) {
+    __shared__ uint32_t ws[CP_ITEMS * CP_WAVES];  // flagged items of (item slot, wave), then their exclusive prefix
+    __shared__ uint32_t round_total;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint64_t lo = (uint64_t)blockIdx.x * tile;
+    const uint64_t hi = lo + tile < n ? lo + tile : n;
+    uint32_t run = block_offs[blockIdx.x];
+    for (uint64_t base = lo; base < hi; base += CP_ROUND) {
+        bool f[CP_ITEMS];
+        typename Emit::Pre pre[CP_ITEMS];  // what the emit needs from memory, requested together with the flags
+#pragma unroll
+        for (int j = 0; j < CP_ITEMS; j++) {
+            const uint64_t i = base + (uint64_t)j * CP_BLOCK + threadIdx.x;
+            f[j] = flag(i < hi ? i : hi - 1);
+            pre[j] = emit.pre(i < hi ? i : hi - 1);
+        }
+        uint32_t below[CP_ITEMS];
+#pragma unroll
+        for (int j = 0; j < CP_ITEMS; j++) {
+            const uint64_t i = base + (uint64_t)j * CP_BLOCK + threadIdx.x;
+            f[j] = f[j] && i < hi;
+            const unsigned long long m = __ballot(f[j]);
+            below[j] = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+            if (lane == 0) ws[j * CP_WAVES + wave] = (uint32_t)__popcll(m);
+        }
+        __syncthreads();
+        if (threadIdx.x < CP_ITEMS * CP_WAVES) {  // 32 lanes of wave 0: exclusive scan in (slot, wave) order
+            const uint32_t v = ws[threadIdx.x];
+            uint32_t x = v;
+#pragma unroll
+            for (int d = 1; d < CP_ITEMS * CP_WAVES; d <<= 1) {
+                const uint32_t y = __shfl_up(x, d);
+                if (threadIdx.x >= (uint32_t)d) x += y;
+            }
+            ws[threadIdx.x] = x - v;
+            if (threadIdx.x == CP_ITEMS * CP_WAVES - 1) round_total = x;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < CP_ITEMS; j++) {
+            const uint64_t i = base + (uint64_t)j * CP_BLOCK + threadIdx.x;
+            if (f[j]) emit(i, run + ws[j * CP_WAVES + wave] + below[j], pre[j]);
+        }
+        run += round_total;
+        __syncthreads();
+    }
+}
+
+static inline uint32_t cp_blocks(uint64_t n, uint64_t *tile_out) {
+    uint64_t nb = (n + CP_ROUND * 4 - 1) / (CP_ROUND * 4);
+    if (nb < 1) nb = 1;
+    if (nb > 4096) nb = 4096;
+    uint64_t tile = (n + nb - 1) / nb;
+    tile = (tile + CP_ROUND - 1) / CP_ROUND * CP_ROUND;
+    nb = (n + tile - 1) / tile;
+    if (nb < 1) nb = 1;
+    *tile_out = tile;
+    return (uint32_t)nb;
+}
+
+// d_block: workspace of >= 4096 u32.  *total_out (device u32) receives the number of flagged items.
+template <typename Flag, typename Emit>
+static int compact(crgpu_ctx *ctx, Flag flag, Emit emit, uint64_t n, uint32_t *d_block, uint32_t *d_total_out) {
+    uint64_t tile;
+    const uint32_t nb = cp_blocks(n, &tile);
+    hipLaunchKernelGGL(k_cp_count<Flag>, dim3(nb), dim3(CP_BLOCK), 0, ctx->stream, flag, n, tile, d_block);
+    CR_TRY(cr_scan_small(ctx, d_block, nb, d_total_out));
+    hipLaunchKernelGGL((k_cp_write<Flag, Emit>), dim3(nb), dim3(CP_BLOCK), 0, ctx->stream, flag, emit, n, tile, d_block);
+    CR_HIP(ctx, hipGetLastError());
+    return CRGPU_OK;
+}
+
+struct CandFlag {
+    const uint8_t *cand;
+    __device__ __forceinline__ bool operator()(uint64_t k) const { return cand[k] != 0; }
+};
+
+// ---- the barcode index: the canonical barcodes with a count in some library (barcode_index.rs:20-53) ----
+struct CountTables {
+    const uint32_t *t[2 * CRGPU_MAX_LIB];
+    uint32_t n;
+};
+struct SeenFlag {  // barcode has a non-zero valid or corrected count in some library
+    CountTables ct;
+    __device__ __forceinline__ bool operator()(uint64_t r) const {
+        uint32_t any = 0;
+        for (uint32_t k = 0; k < ct.n; k++) any |= ct.t[k][r];
+        return any != 0u;
+    }
+};
+struct EmitCol {
+    uint32_t *rank;
+    struct Pre {};
+    __device__ __forceinline__ Pre pre(uint64_t) const { return Pre(); }
+    __device__ __forceinline__ void operator()(uint64_t r, uint32_t o, Pre) const { rank[o] = (uint32_t)r; }
+};

@@ -1,5 +1,5 @@
-// subsample.h -- read subsampling of the molecule table: the tallies behind the saturation curves (part of dedup.hip, after
-// emptydrops.h: works on crgpu_counts and shares the compaction, the pooled temporaries and the Philox stream).
+// subsample.h -- read subsampling of the molecule table: the tallies behind the saturation curves (part of
+// molecule_stages.hip: works on crgpu_counts; the barcode segments and the ascending check are those of probe_counts.h).
 //
 // Replaces run_subsampling / _run_subsample_task (lib/python/cellranger/subsample.py:430-654) for one chunk that holds the whole
 // table, compute_target_depths / make_subsamplings / _subsampling_for_depth (:140-309, crgpu_subsample_plan) and the per-task
@@ -22,10 +22,14 @@
 //               ballots, a run that crosses a tile edge carries one bit.  Per-cell entries have one writer; the totals and the
 //               per-feature survivor counts are 64-bit integer atomics (exact in any order).
 // Nothing depends on timing, on the two thresholds or on the batch.
+#pragma once
+
 #include <algorithm>
 #include <cmath>
 
 #include "philox.h"
+#include "probe_counts.h"
+#include "stage_common.h"
 
 #define SS_THREADS 256u
 #define SS_MAX_BATCH 64u
@@ -333,7 +337,7 @@ __global__ __launch_bounds__(256) void k_ss_tally(SsTally a) {
 
 // ---- host side ------------------------------------------------------------------------------------------------------------------
 // position of every device molecule in the table crgpu_counts_molecules lists.  One library and one UMI length: the device
-// order is that order (NULL).  Otherwise the host order of molecule_order, inverted, kept in the counts.
+// order is that order (NULL).  Otherwise the host order of cr_molecule_order, inverted, kept in the counts.
 static int ss_positions(crgpu_ctx *ctx, crgpu_counts *c, const uint32_t **d_pos) {
     *d_pos = nullptr;
     const KeyLayout &L = c->layout;
@@ -341,7 +345,7 @@ static int ss_positions(crgpu_ctx *ctx, crgpu_counts *c, const uint32_t **d_pos)
     if (!c->d_ss_pos) {
         std::vector<uint64_t> keys;
         std::vector<uint32_t> reads, order;
-        CR_TRY(molecule_order(ctx, c, keys, reads, order));
+        CR_TRY(cr_molecule_order(ctx, c, keys, reads, order));
         std::vector<uint32_t> pos(order.size());
         for (size_t o = 0; o < order.size(); o++) pos[order[o]] = (uint32_t)o;
         CR_TRY(cr_pool_alloc(ctx, (void **)&c->d_ss_pos, pos.size() * sizeof(uint32_t)));
@@ -368,7 +372,7 @@ static int ss_run(crgpu_ctx *ctx, crgpu_counts *c, const crgpu_subsample_args *a
     if (a->total_features_det && T) memset(a->total_features_det, 0, (size_t)T * G * F * sizeof(int64_t));
     if (a->any_reads) memset(a->any_reads, 0, (size_t)NL * G);
 
-    uint32_t *d_flag = ctx->d_scalars + 48, *d_total = ctx->d_scalars + 16, differ = 0;
+    uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, *d_total = ctx->d_scalars + CR_SCALAR_TOTAL, differ = 0;
     if (NC > 1) {
         CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
         hipLaunchKernelGGL(k_pc_not_ascending, dim3(cr_grid(NC, 256)), dim3(256), 0, ctx->stream, a->d_cell_ranks, NC, d_flag);

@@ -11,13 +11,13 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-CP_ROUND = 2048  # keys a workgroup of the run-length pass takes per round (dedup.hip)
+CP_ROUND = 2048  # keys a workgroup of the run-length pass takes per round (stage_common.h)
 STAT_SORT_REFINISHED = 1
 STAT_RL_COUNTS_FROM_FINISH = 15
 
 
 def _rl_tile(n_keys):
-    """keys per tile of the run-length pass: the arithmetic of cp_blocks (dedup.hip)"""
+    """keys per tile of the run-length pass: the arithmetic of cp_blocks (stage_common.h)"""
     nb = max(1, min(4096, -(-n_keys // (CP_ROUND * 4))))
     tile = -(-n_keys // nb)
     return -(-tile // CP_ROUND) * CP_ROUND
