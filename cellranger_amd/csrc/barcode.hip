@@ -660,13 +660,6 @@ __global__ __launch_bounds__(256) void k_hot_build(const uint32_t *__restrict__ 
 #define LH_QUEUE (64 * LH_QITEMS)    // entries of a wave's queue: every lane of every slot could be cold
 // MODE 0: every hit goes through the staged histogram afterwards (k_stage_idx over idx).
 // MODE 1 (LH_SPLIT): hits the table answers are written out as table slots (2 bytes per read) and counted by k_hist_hot_slots.
-// MODE 2 (LH_COUNT): the table keeps 4-byte keys only (64 KB) and the other 64 KB of its LDS hold one counter per slot: a hit
-//   the table answers bumps its slot's counter right here and takes its rank from the table image in global memory (128 KB,
-//   cache resident); the counters are added to the VALID table when the workgroup ends.  No slot stream, no second kernel,
-//   and the staged histogram sees the cold hits only.  A cold region that overflows counts its surplus hits by device atomics.
-//   Opt-in (CRGPU_K1_MODE=count), measured SLOWER at 1 B reads: pass A 8.05 -> 9.05 ms on the 737 K list, 12.0 -> 12.65 on the
-//   6.8 M one, cfg2 0.93 -> 1.13 -- the rank gather (64 different lines of the image per wave instruction) costs the lookup
-//   more than the staging it saves; profiles/r03_count_stage_and_sort_ab.txt.
 // MODE 3 (LH_HOTCNT, the default of the table rounds): the table keeps its 8-byte entries and counts the hits it answers in
 //   the free high bits of each entry's rank word (ranks need `cnt_shift` bits; the field above them starts at zero, the
 //   image's high rank bits being zero).  A hit adds 1 << cnt_shift to its word with an LDS atomic and still reads its rank
@@ -678,7 +671,6 @@ __global__ __launch_bounds__(256) void k_hot_build(const uint32_t *__restrict__ 
 //   reads the ranks each one holds (cold_count), and for k_match_binned every wave closes its region with CRGPU_MISS.
 #define LH_FULL 0
 #define LH_SPLIT 1
-#define LH_COUNT 2
 #define LH_HOTCNT 3
 // Flush of the LH_HOTCNT fields at the end of a workgroup: each workgroup writes its 16384 fields as one coalesced row of
 // a slot image and k_hot_flush adds the column sums to VALID (one atomic per non-empty slot and row slice).  One device
@@ -688,18 +680,6 @@ __global__ __launch_bounds__(256) void k_hot_build(const uint32_t *__restrict__ 
 #ifndef HC_GROUP
 #define HC_GROUP 4            // LH_HOTCNT: reads probed together before their atomics
 #endif
-// 4-byte-key table: slot of `key` or 0xFFFF.  An empty slot holds 0xFFFFFFFF, so the all-T barcode is never cached (cold path).
-__device__ __forceinline__ uint32_t hot_probe_keys(const uint32_t *s_key, uint32_t key) {
-    const uint32_t b0 = hot_hash(key), b1 = (b0 + 1u) & (HOT_BUCKETS - 1u);
-    const uint2 x = *reinterpret_cast<const uint2 *>(s_key + 2u * b0);
-    const uint2 y = *reinterpret_cast<const uint2 *>(s_key + 2u * b1);
-    uint32_t sl = 0xFFFFu;
-    sl = y.y == key ? 2u * b1 + 1u : sl;
-    sl = y.x == key ? 2u * b1 : sl;
-    sl = x.y == key ? 2u * b0 + 1u : sl;
-    sl = x.x == key ? 2u * b0 : sl;
-    return key == 0xFFFFFFFFu ? 0xFFFFu : sl;
-}
 template <int MODE>
 __global__ __launch_bounds__(LH_THREADS) void k_lookup_hot(const WlViewSet vs,
                                                            const unsigned long long *__restrict__ hot_image,
@@ -721,24 +701,16 @@ __global__ __launch_bounds__(LH_THREADS) void k_lookup_hot(const WlViewSet vs,
     // for a staging kernel that reads whole regions; without it only cold_count tells how many ranks a region holds.
     extern __shared__ __attribute__((aligned(16))) unsigned long long s_hot[];  // HOT_SLOTS, then the cold queues
     uint32_t *s_queue = reinterpret_cast<uint32_t *>(s_hot + HOT_SLOTS);          // LH_THREADS / 64 queues of LH_QUEUE
-    constexpr bool SPLIT = MODE == LH_SPLIT, COUNT = MODE == LH_COUNT, HOTCNT = MODE == LH_HOTCNT, COLD = MODE != LH_FULL;
-    uint32_t *s_key = reinterpret_cast<uint32_t *>(s_hot), *s_cnt = s_key + HOT_SLOTS;  // COUNT: keys, then one counter per slot
+    constexpr bool SPLIT = MODE == LH_SPLIT, HOTCNT = MODE == LH_HOTCNT, COLD = MODE != LH_FULL;
+    uint32_t *s_key = reinterpret_cast<uint32_t *>(s_hot);
     // HOTCNT: the rank word of slot s is s_key[2 s + 1]; its field counts up to cnt_max and then wraps
     const uint32_t rank_mask = HOTCNT ? (1u << cnt_shift) - 1u : CRGPU_MISS;
     const uint32_t cnt_max = HOTCNT ? 0xFFFFFFFFu >> cnt_shift : 0u;
-    const uint32_t *__restrict__ hot_words = reinterpret_cast<const uint32_t *>(hot_image);  // [2 s] key, [2 s + 1] rank of slot s
     const uint32_t tid = threadIdx.x;
     const WlView &w = vs.v[0];
     const uint32_t *__restrict__ tw = reinterpret_cast<const uint32_t *>(w.tailA);
     const uint32_t tail_mask = (1u << w.bitsB) - 1u;
-    if (COUNT) {
-        for (uint32_t s = tid; s < HOT_SLOTS; s += LH_THREADS) {
-            s_key[s] = hot_words[2u * s];
-            s_cnt[s] = 0u;
-        }
-    } else {
-        for (uint32_t s = tid; s < HOT_SLOTS; s += LH_THREADS) s_hot[s] = hot_image[s];
-    }
+    for (uint32_t s = tid; s < HOT_SLOTS; s += LH_THREADS) s_hot[s] = hot_image[s];
     __syncthreads();
     const uint64_t chunk = (uint64_t)LH_THREADS * LH_ITEMS;
     // miss records (for K2): every wave appends to its own region, no atomics; the cursor lives in a register
@@ -770,22 +742,7 @@ __global__ __launch_bounds__(LH_THREADS) void k_lookup_hot(const WlViewSet vs,
             nkey[j] = i < n ? CR_LOAD_STREAM(&cb[i]) : 0u;
             nfl[j] = (i < n && flags) ? CR_LOAD_STREAM(&flags[i]) : 0u;
         }
-        if (COUNT) {
-#pragma unroll
-            for (int j = 0; j < LH_ITEMS; j++) {
-                const uint32_t sl = hot_probe_keys(s_key, key[j]);
-                hslot[j] = todo[j] ? sl : 0xFFFFu;
-            }
-#pragma unroll
-            for (int j = 0; j < LH_ITEMS; j++)   // the ranks of the slots that answered: independent loads, issued together
-                if (hslot[j] != 0xFFFFu) rank[j] = hot_words[2u * hslot[j] + 1u];
-#pragma unroll
-            for (int j = 0; j < LH_ITEMS; j++)
-                if (hslot[j] != 0xFFFFu) {
-                    todo[j] = false;
-                    atomicAdd(&s_cnt[hslot[j]], 1u);
-                }
-        } else if (HOTCNT) {
+        if (HOTCNT) {
             // HC_GROUP reads at a time: their probes issued together, then their (independent) LDS atomics -- all eight
             // probes in flight at once would hold 64 VGPRs of entries beside the atomics' return values and spill
 #pragma unroll
@@ -810,16 +767,16 @@ __global__ __launch_bounds__(LH_THREADS) void k_lookup_hot(const WlViewSet vs,
             }
         } else {
 #pragma unroll
-        for (int j = 0; j < LH_ITEMS; j++) {
-            uint32_t sl = 0xFFFFu;
-            const uint32_t r = SPLIT ? hot_probe_slot(s_hot, key[j], sl) : hot_probe(s_hot, key[j]);
-            hslot[j] = 0xFFFFu;
-            if (todo[j] && r != CRGPU_MISS) {
-                rank[j] = r;
-                todo[j] = false;
-                hslot[j] = sl;
+            for (int j = 0; j < LH_ITEMS; j++) {
+                uint32_t sl = 0xFFFFu;
+                const uint32_t r = SPLIT ? hot_probe_slot(s_hot, key[j], sl) : hot_probe(s_hot, key[j]);
+                hslot[j] = 0xFFFFu;
+                if (todo[j] && r != CRGPU_MISS) {
+                    rank[j] = r;
+                    todo[j] = false;
+                    hslot[j] = sl;
+                }
             }
-        }
         }
         if (SPLIT) {
             // the table slots that answered this thread's LH_ITEMS reads, as one 16-byte store: the histogram does not care
@@ -880,7 +837,7 @@ __global__ __launch_bounds__(LH_THREADS) void k_lookup_hot(const WlViewSet vs,
                     const unsigned long long cm = __ballot(found != CRGPU_MISS);
                     const uint32_t pos = cold_cur + __builtin_amdgcn_mbcnt_hi((uint32_t)(cm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)cm, 0u));
                     if (found != CRGPU_MISS && pos < cold_cap) cold_rank[(uint64_t)region * cold_cap + pos] = found;
-                    if ((COUNT || HOTCNT) && found != CRGPU_MISS && pos >= cold_cap) atomicAdd(&w.valid[found], 1u);  // region full: counted here
+                    if (HOTCNT && found != CRGPU_MISS && pos >= cold_cap) atomicAdd(&w.valid[found], 1u);  // region full: counted here
                     cold_cur += (uint32_t)__popcll(cm);
                 }
             }
@@ -915,14 +872,6 @@ __global__ __launch_bounds__(LH_THREADS) void k_lookup_hot(const WlViewSet vs,
     if (SPLIT && (tid & 63u) == 0u) {
         cold_count[region] = cold_cur;
         if (cold_cur > cold_cap) atomicOr(&cold_count[cold_regions], 1u);  // overflow: this round is counted by k_hist_ranks_atomic
-    }
-    if (COUNT) {
-        if ((tid & 63u) == 0u) cold_count[region] = cold_cur < cold_cap ? cold_cur : cold_cap;
-        __syncthreads();
-        for (uint32_t s = tid; s < HOT_SLOTS; s += LH_THREADS) {
-            const uint32_t c = s_cnt[s];
-            if (c) atomicAdd(&w.valid[hot_words[2u * s + 1u]], c);
-        }
     }
     if (HOTCNT) {
         if (cold_fill) {  // the rest of this wave's region reads as CRGPU_MISS (the regions are not cleared beforehand)
@@ -1140,14 +1089,11 @@ static int hist_from_idx(crgpu_ctx *ctx, const WlViewSet &vs, BinPlan plan, cons
     if (sb < MB_TILE) sb = MB_TILE;
     if (sb > n) sb = (n + MB_TILE - 1) / MB_TILE * MB_TILE;
     plan.cap = sb;
-    uint16_t *d_stage = nullptr;
-    uint32_t *d_cursor = nullptr;
-    CR_TRY(cr_pool_alloc(ctx, (void **)&d_stage, (uint64_t)plan.n_buckets * plan.cap * sizeof(uint16_t)));
-    int rc = cr_pool_alloc(ctx, (void **)&d_cursor, plan.n_buckets * MB_CURSOR_STRIDE * sizeof(uint32_t));
-    if (rc != CRGPU_OK) {
-        cr_pool_free(ctx, d_stage);
-        return rc;
-    }
+    DevBuf stage, cursor;
+    CR_TRY(dmalloc(ctx, stage, (uint64_t)plan.n_buckets * plan.cap * sizeof(uint16_t)));
+    CR_TRY(dmalloc(ctx, cursor, plan.n_buckets * MB_CURSOR_STRIDE * sizeof(uint32_t)));
+    uint16_t *d_stage = stage.as<uint16_t>();
+    uint32_t *d_cursor = cursor.as<uint32_t>();
     uint32_t slices = 512 / plan.n_buckets;
     if (slices < 1) slices = 1;
     cr_allow_lds(ctx, (const void *)k_hist_buckets, BIN_SIZE * 4);
@@ -1161,8 +1107,6 @@ static int hist_from_idx(crgpu_ctx *ctx, const WlViewSet &vs, BinPlan plan, cons
                            d_stage, d_cursor);
         if (e == hipSuccess) e = hipGetLastError();
     }
-    cr_pool_free(ctx, d_stage);
-    cr_pool_free(ctx, d_cursor);
     if (e != hipSuccess) return cr_fail(ctx, CRGPU_EHIP, "histogram of ranks: %s", hipGetErrorString(e));
     return CRGPU_OK;
 }
@@ -1226,14 +1170,11 @@ extern "C" int crgpu_match_and_count_dev(crgpu_ctx *ctx, const uint32_t *d_cb, c
     if (sb < MB_TILE) sb = MB_TILE;
     if (sb > n) sb = (n + MB_TILE - 1) / MB_TILE * MB_TILE;
     plan.cap = sb;  // multiple of 4096 -> every bucket region is 16-byte aligned
-    uint16_t *d_stage = nullptr;
-    uint32_t *d_cursor = nullptr;
-    CR_TRY(cr_pool_alloc(ctx, (void **)&d_stage, (uint64_t)plan.n_buckets * plan.cap * sizeof(uint16_t)));
-    int rc = cr_pool_alloc(ctx, (void **)&d_cursor, plan.n_buckets * MB_CURSOR_STRIDE * sizeof(uint32_t));
-    if (rc != CRGPU_OK) {
-        cr_pool_free(ctx, d_stage);
-        return rc;
-    }
+    DevBuf stage, cursor;
+    CR_TRY(dmalloc(ctx, stage, (uint64_t)plan.n_buckets * plan.cap * sizeof(uint16_t)));
+    CR_TRY(dmalloc(ctx, cursor, plan.n_buckets * MB_CURSOR_STRIDE * sizeof(uint32_t)));
+    uint16_t *d_stage = stage.as<uint16_t>();
+    uint32_t *d_cursor = cursor.as<uint32_t>();
     // slices per bucket: ~2 workgroups per CU in total (128 KB of LDS each -> one resident per CU)
     uint32_t slices = 512 / plan.n_buckets;
     if (slices < 1) slices = 1;
@@ -1244,8 +1185,7 @@ extern "C" int crgpu_match_and_count_dev(crgpu_ctx *ctx, const uint32_t *d_cb, c
     if (const char *env = getenv("CRGPU_HOT_MIN_READS")) hot_min = strtoull(env, nullptr, 10);
     // (a translated or partial list brings its own rank -> key array; a rank without a key of this list never has a count)
     const uint32_t *d_hot_keys = uw.d_valA ? uw.d_key_of_rank : ctx->d_canon_keys;
-    const bool use_hot = uniform && n >= hot_min && n >= 4ull * MB_TILE && d_hot_keys != nullptr &&
-                         !(uw.d_valA && getenv("CRGPU_HOT_PLAIN_ONLY"));  // (A/B switch: round 2's rule)
+    const bool use_hot = uniform && n >= hot_min && n >= 4ull * MB_TILE && d_hot_keys != nullptr;
     uint64_t first = 0;  // reads of the sampling batch (a multiple of MB_TILE)
     if (use_hot) {
         first = n / 4 < (4ull << 20) ? n / 4 : (4ull << 20);
@@ -1254,11 +1194,8 @@ extern "C" int crgpu_match_and_count_dev(crgpu_ctx *ctx, const uint32_t *d_cb, c
     const size_t hot_lds = HOT_SLOTS * sizeof(unsigned long long);                       // table image
     const size_t lookup_lds = hot_lds + (LH_THREADS / 64) * LH_QUEUE * sizeof(uint32_t);  // + per-wave cold queues
     if (use_hot && !ctx->d_hot_image) {
-        if (hipMalloc((void **)&ctx->d_hot_image, hot_lds + 256 * sizeof(uint32_t) + 2 * sizeof(unsigned long long)) != hipSuccess) {
-            cr_pool_free(ctx, d_stage);
-            cr_pool_free(ctx, d_cursor);
+        if (hipMalloc((void **)&ctx->d_hot_image, hot_lds + 256 * sizeof(uint32_t) + 2 * sizeof(unsigned long long)) != hipSuccess)
             return cr_fail(ctx, CRGPU_ENOMEM, "hipMalloc hot table failed");
-        }
     }
     // miss records for K2: one region per wave of the lookup kernel (its grid is pinned to 256 workgroups)
     uint32_t rec_slot = CR_REC_SETS;
@@ -1297,7 +1234,6 @@ extern "C" int crgpu_match_and_count_dev(crgpu_ctx *ctx, const uint32_t *d_cb, c
     if (use_hot) {
         cr_allow_lds(ctx, (const void *)k_lookup_hot<LH_FULL>, lookup_lds);
         cr_allow_lds(ctx, (const void *)k_lookup_hot<LH_SPLIT>, lookup_lds);
-        cr_allow_lds(ctx, (const void *)k_lookup_hot<LH_COUNT>, lookup_lds);
         cr_allow_lds(ctx, (const void *)k_lookup_hot<LH_HOTCNT>, lookup_lds);
     }
     hipError_t e = hipSuccess;
@@ -1306,30 +1242,15 @@ extern "C" int crgpu_match_and_count_dev(crgpu_ctx *ctx, const uint32_t *d_cb, c
     // LDS, the others are appended to per-wave regions and staged -- a sixth of the entries the staging used to see, so the
     // rounds can be that much longer.  Sized after the sampling batch from the share of the reads the table's barcodes
     // carry.  A region that overflows: LH_SPLIT makes its round fall back to device atomics (cold_count[regions] != 0),
-    // LH_HOTCNT and LH_COUNT count the surplus hits with device atomics in the lookup.
+    // LH_HOTCNT counts the surplus hits with device atomics in the lookup.
     const uint32_t cold_regions = 256u * (LH_THREADS / 64);
-    uint16_t *d_hot_slot = nullptr;
-    uint32_t *d_cold = nullptr, *d_cold_count = nullptr, *d_cnt_image = nullptr;
+    DevBuf hot_slot, cold, cold_count, cnt_image;
     uint64_t hot_round = 0;   // reads per table round (0: the split histogram is off)
     uint32_t cold_cap = 0;
     int table_mode = LH_FULL;  // k_lookup_hot's MODE in the table rounds
     // LH_HOTCNT: the rank bits of the table's rank words, so that rank_mask = 2^bits - 1 >= n_canon is never a rank
     uint32_t cnt_shift = 1;
     while (cnt_shift < 32u && (1ull << cnt_shift) <= ctx->n_canon) cnt_shift++;
-    // CRGPU_K1_MODE=count: table hits counted inside the lookup kernel (LH_COUNT); =split / =full: the other two
-    const char *k1_mode = getenv("CRGPU_K1_MODE");
-    const bool count_mode = k1_mode && strcmp(k1_mode, "count") == 0;
-    struct ColdRelease {
-        crgpu_ctx *c;
-        uint16_t *&a;
-        uint32_t *&b, *&d, *&f;
-        ~ColdRelease() {
-            cr_pool_free(c, a);
-            cr_pool_free(c, b);
-            cr_pool_free(c, d);
-            cr_pool_free(c, f);
-        }
-    } cold_release{ctx, d_hot_slot, d_cold, d_cold_count, d_cnt_image};
     for (uint64_t off = 0; off < n && e == hipSuccess;) {
         uint64_t m = n - off < sb ? n - off : sb;
         if (use_hot && off == 0 && m > first) m = first;
@@ -1337,9 +1258,21 @@ extern "C" int crgpu_match_and_count_dev(crgpu_ctx *ctx, const uint32_t *d_cb, c
         {
             CrTimer t(ctx, CRGPU_T_MATCH, m);
             e = hipMemsetAsync(d_cursor, 0, plan.n_buckets * MB_CURSOR_STRIDE * sizeof(uint32_t), ctx->stream);
+            // k_lookup_hot<mode> over this round's reads; a call states what differs between the modes: the hot-slot stream,
+            // the cold regions, cnt_shift, the slot image and cold_fill
+            const uint32_t lh_grid = cr_grid((m + MB_TILE - 1) / MB_TILE, 1, 256u);
+            auto lookup = [&](auto mode, uint16_t *slots_out, uint32_t *cold_rank, uint32_t *cold_cnt, uint32_t cap, uint32_t regions,
+                              uint32_t shift, uint32_t *image, bool cold_fill) {
+                hipLaunchKernelGGL(k_lookup_hot<decltype(mode)::value>, dim3(lh_grid), dim3(LH_THREADS), lookup_lds, ctx->stream, vs,
+                                   ctx->d_hot_image, d_cb + off, d_flags ? d_flags + off : nullptr, m, d_idx_out + off,
+                                   rec.valid ? rec.d_i : nullptr, rec.d_key, rec.d_fl, rec.d_count, rec.cap, rec.regions,
+                                   (uint32_t)off, slots_out, cold_rank, cold_cnt, cap, regions, shift, image, cold_fill);
+            };
             if (hot_ready && hot_round) {
                 ctx->k1_split_rounds++;
-                const uint32_t lh_grid = cr_grid((m + MB_TILE - 1) / MB_TILE, 1, 256u);
+                uint16_t *const d_hot_slot = hot_slot.as<uint16_t>();
+                uint32_t *const d_cold = cold.as<uint32_t>(), *const d_cold_count = cold_count.as<uint32_t>();
+                uint32_t *const d_cnt_image = cnt_image.as<uint32_t>();
                 uint64_t C = (uint64_t)cold_regions * cold_cap;
                 const uint32_t *d_over = d_cold_count + cold_regions;  // != 0 after the lookup: a cold region overflowed
                 if (e == hipSuccess) e = hipMemsetAsync(d_cold_count, 0, (cold_regions + 1) * sizeof(uint32_t), ctx->stream);
@@ -1348,32 +1281,17 @@ extern "C" int crgpu_match_and_count_dev(crgpu_ctx *ctx, const uint32_t *d_cb, c
                     // whole regions, which their waves close with CRGPU_MISS; no fallback round
                     C = (uint64_t)lh_grid * (LH_THREADS / 64) * cold_cap;
                     d_over = nullptr;
-                    hipLaunchKernelGGL(k_lookup_hot<LH_HOTCNT>, dim3(lh_grid), dim3(LH_THREADS), lookup_lds, ctx->stream, vs,
-                                       ctx->d_hot_image, d_cb + off, d_flags ? d_flags + off : nullptr, m, d_idx_out + off,
-                                       rec.valid ? rec.d_i : nullptr, rec.d_key, rec.d_fl, rec.d_count, rec.cap, rec.regions,
-                                       (uint32_t)off, (uint16_t *)nullptr, d_cold, d_cold_count, cold_cap, cold_regions, cnt_shift,
-                                       d_cnt_image, plan.n_buckets > SI_MISS_BUCKET);
+                    lookup(std::integral_constant<int, LH_HOTCNT>{}, nullptr, d_cold, d_cold_count, cold_cap, cold_regions, cnt_shift,
+                           d_cnt_image, plan.n_buckets > SI_MISS_BUCKET);
                     hipLaunchKernelGGL(k_hot_flush, dim3(HOT_SLOTS / 256u, 8), dim3(256), 0, ctx->stream, d_cnt_image, lh_grid,
                                        ctx->d_hot_image, uw.d_valid);
                 } else {
                     if (e == hipSuccess) e = hipMemsetAsync(d_cold, 0xFF, C * sizeof(uint32_t), ctx->stream);
-                    if (table_mode == LH_COUNT) {
-                        d_over = nullptr;  // nothing to fall back to: a full region counts its surplus hits itself
-                        hipLaunchKernelGGL(k_lookup_hot<LH_COUNT>, dim3(lh_grid), dim3(LH_THREADS), lookup_lds, ctx->stream, vs,
-                                           ctx->d_hot_image, d_cb + off, d_flags ? d_flags + off : nullptr, m, d_idx_out + off,
-                                           rec.valid ? rec.d_i : nullptr, rec.d_key, rec.d_fl, rec.d_count, rec.cap, rec.regions,
-                                           (uint32_t)off, (uint16_t *)nullptr, d_cold, d_cold_count, cold_cap, cold_regions, 0u,
-                                           (uint32_t *)nullptr);
-                    } else {
-                        hipLaunchKernelGGL(k_lookup_hot<LH_SPLIT>, dim3(lh_grid), dim3(LH_THREADS), lookup_lds, ctx->stream, vs,
-                                           ctx->d_hot_image, d_cb + off, d_flags ? d_flags + off : nullptr, m, d_idx_out + off,
-                                           rec.valid ? rec.d_i : nullptr, rec.d_key, rec.d_fl, rec.d_count, rec.cap, rec.regions,
-                                           (uint32_t)off, d_hot_slot, d_cold, d_cold_count, cold_cap, cold_regions, 0u,
-                                           (uint32_t *)nullptr);
-                        const uint64_t lh_chunk = (uint64_t)LH_THREADS * LH_ITEMS;
-                        hipLaunchKernelGGL(k_hist_hot_slots, dim3(128), dim3(HH_THREADS), HOT_SLOTS * sizeof(uint32_t), ctx->stream,
-                                           d_hot_slot, (m + lh_chunk - 1) / lh_chunk * LH_THREADS, ctx->d_hot_image, uw.d_valid, d_over);
-                    }
+                    lookup(std::integral_constant<int, LH_SPLIT>{}, d_hot_slot, d_cold, d_cold_count, cold_cap, cold_regions, 0u, nullptr,
+                           false);
+                    const uint64_t lh_chunk = (uint64_t)LH_THREADS * LH_ITEMS;
+                    hipLaunchKernelGGL(k_hist_hot_slots, dim3(128), dim3(HH_THREADS), HOT_SLOTS * sizeof(uint32_t), ctx->stream,
+                                       d_hot_slot, (m + lh_chunk - 1) / lh_chunk * LH_THREADS, ctx->d_hot_image, uw.d_valid, d_over);
                 }
                 if (plan.n_buckets <= SI_MISS_BUCKET)
                     hipLaunchKernelGGL(k_stage_idx, dim3(cr_grid((C + SI_TILE - 1) / SI_TILE, 1, 256u * 6u)), dim3(256), 0, ctx->stream,
@@ -1386,24 +1304,8 @@ extern "C" int crgpu_match_and_count_dev(crgpu_ctx *ctx, const uint32_t *d_cb, c
                 if (table_mode == LH_SPLIT)
                     hipLaunchKernelGGL(k_hist_ranks_atomic, dim3(cr_grid(m, 256)), dim3(256), 0, ctx->stream, d_idx_out + off, m, uw.d_valid,
                                        d_over);
-                if (getenv("CRGPU_K1_DEBUG")) {
-                    std::vector<uint32_t> cc(cold_regions + 1);
-                    (void)hipMemcpyAsync(cc.data(), d_cold_count, cc.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
-                    (void)hipStreamSynchronize(ctx->stream);
-                    uint32_t mx = 0;
-                    uint64_t tot = 0;
-                    for (uint32_t r = 0; r < cold_regions; r++) {
-                        mx = std::max(mx, cc[r]);
-                        tot += cc[r];
-                    }
-                    fprintf(stderr, "K1 round off=%llu m=%llu cap=%u max_region=%u total_cold=%llu overflow=%u\n",
-                            (unsigned long long)off, (unsigned long long)m, cold_cap, mx, (unsigned long long)tot, cc[cold_regions]);
-                }
             } else if (hot_ready) {
-                hipLaunchKernelGGL(k_lookup_hot<LH_FULL>, dim3(cr_grid((m + MB_TILE - 1) / MB_TILE, 1, 256u)), dim3(LH_THREADS), lookup_lds,
-                                   ctx->stream, vs, ctx->d_hot_image, d_cb + off, d_flags ? d_flags + off : nullptr, m,
-                                   d_idx_out + off, rec.valid ? rec.d_i : nullptr, rec.d_key, rec.d_fl, rec.d_count, rec.cap,
-                                   rec.regions, (uint32_t)off, (uint16_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, 0u, 0u);
+                lookup(std::integral_constant<int, LH_FULL>{}, nullptr, nullptr, nullptr, 0u, 0u, 0u, nullptr, false);
                 if (plan.n_buckets <= SI_MISS_BUCKET)
                     hipLaunchKernelGGL(k_stage_idx, dim3(cr_grid((m + SI_TILE - 1) / SI_TILE, 1, 256u * 6u)), dim3(256), 0,
                                        ctx->stream, plan, d_idx_out + off, m, d_stage, d_cursor);
@@ -1440,15 +1342,11 @@ extern "C" int crgpu_match_and_count_dev(crgpu_ctx *ctx, const uint32_t *d_cb, c
                 // -4 ms per 1 B reads on the 6.8 M-entry list, a wash on the 737 K one); it is the default where LH_HOTCNT
                 // cannot run.  CRGPU_K1_SPLIT=1 forces LH_SPLIT, =0 the full staging of every round.
                 const char *split_env = getenv("CRGPU_K1_SPLIT");
-                int mode = LH_FULL;
-                if (count_mode)
-                    mode = LH_COUNT;
-                else if (split_env)
-                    mode = split_env[0] != '0' ? LH_SPLIT : LH_FULL;
-                else
-                    mode = cnt_shift <= HC_MAX_RANK_BITS ? LH_HOTCNT : plan.n_buckets > SI_MISS_BUCKET ? LH_SPLIT : LH_FULL;
-                const bool want_split = mode != LH_FULL;
-                if (e == hipSuccess && want_split && !getenv("CRGPU_K1_FULL_STAGING") &&
+                const int mode = split_env ? (split_env[0] != '0' ? LH_SPLIT : LH_FULL)
+                                 : cnt_shift <= HC_MAX_RANK_BITS   ? LH_HOTCNT
+                                 : plan.n_buckets > SI_MISS_BUCKET ? LH_SPLIT
+                                                                   : LH_FULL;
+                if (e == hipSuccess && mode != LH_FULL &&
                     hipMemcpyAsync(sums, d_sums, sizeof(sums), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
                     hipStreamSynchronize(ctx->stream) == hipSuccess && sums[0] > 0) {
                     const double cold_frac = 1.0 - (double)sums[1] / (double)sums[0];
@@ -1468,12 +1366,11 @@ extern "C" int crgpu_match_and_count_dev(crgpu_ctx *ctx, const uint32_t *d_cb, c
                         if (const char *env = getenv("CRGPU_COLD_CAP")) cap = strtoull(env, nullptr, 10);  // tests: force the overflow fallback
                         if ((round >= sb || round >= (n - first) / MB_TILE * MB_TILE) && round > 0 && cap * cold_regions <= plan.cap) {
                             const uint64_t lh_chunk = (uint64_t)LH_THREADS * LH_ITEMS;
-                            int rr = mode != LH_SPLIT ? CRGPU_OK
-                                                : cr_pool_alloc(ctx, (void **)&d_hot_slot, (round + lh_chunk) / lh_chunk * lh_chunk * sizeof(uint16_t));
+                            int rr = mode != LH_SPLIT ? CRGPU_OK : dmalloc(ctx, hot_slot, (round + lh_chunk) / lh_chunk * lh_chunk * sizeof(uint16_t));
                             if (rr == CRGPU_OK && mode == LH_HOTCNT)  // the flush image: one row of fields per workgroup
-                                rr = cr_pool_alloc(ctx, (void **)&d_cnt_image, 256u * HOT_SLOTS * sizeof(uint32_t));
-                            if (rr == CRGPU_OK) rr = cr_pool_alloc(ctx, (void **)&d_cold, cap * cold_regions * sizeof(uint32_t));
-                            if (rr == CRGPU_OK) rr = cr_pool_alloc(ctx, (void **)&d_cold_count, (cold_regions + 1) * sizeof(uint32_t));
+                                rr = dmalloc(ctx, cnt_image, 256u * HOT_SLOTS * sizeof(uint32_t));
+                            if (rr == CRGPU_OK) rr = dmalloc(ctx, cold, cap * cold_regions * sizeof(uint32_t));
+                            if (rr == CRGPU_OK) rr = dmalloc(ctx, cold_count, (cold_regions + 1) * sizeof(uint32_t));
                             if (rr == CRGPU_OK) {
                                 hot_round = round;
                                 cold_cap = (uint32_t)cap;
@@ -1488,8 +1385,6 @@ extern "C" int crgpu_match_and_count_dev(crgpu_ctx *ctx, const uint32_t *d_cb, c
         }
         off += m;
     }
-    cr_pool_free(ctx, d_stage);
-    cr_pool_free(ctx, d_cursor);
     if (e != hipSuccess) {
         cr_drop_miss_records(ctx, rec);
         return cr_fail(ctx, CRGPU_EHIP, "crgpu_match_and_count: %s", hipGetErrorString(e));
@@ -1581,11 +1476,7 @@ struct K2Qual {
 __device__ __forceinline__ bool k2_load_qual(const K2Params &P, uint64_t i, uint32_t f, K2Qual &q) {
     const uint8_t *__restrict__ qualn = P.qualn;
     const uint32_t len = P.len;
-#ifdef K2_EXP_NO_QUAL
-    if (false) {
-#else
     if (qualn) {
-#endif
         if (len == 16) {
             const cr_u32x4 qv = CR_LOAD_STREAM(reinterpret_cast<const cr_u32x4 *>(qualn + i * 16));
             const uint4 q4 = make_uint4(qv.x, qv.y, qv.z, qv.w);
@@ -1751,16 +1642,12 @@ __device__ __forceinline__ uint32_t k2_solve_own(const WlView &w, const K2Params
 __device__ __forceinline__ void k2_commit(const WlView &w, const K2Params &P, uint64_t i, uint32_t rank, uint32_t *rank_sink,
                                           bool count = true, bool flag = true) {
     if (rank == CRGPU_MISS) return;
-#ifndef K2_EXP_NO_IDX   // cost-attribution builds (scripts/ab.sh): results are wrong without these stores
     CR_STORE_STREAM(rank, &P.idx_inout[i]);
-#endif
     if (flag && P.corrected_out) P.corrected_out[i] = 1;
-#ifndef K2_EXP_NO_ATOMIC
     if (rank_sink)
         CR_STORE_STREAM(rank, rank_sink);
     else if (count)
         atomicAdd(&w.corrected[rank], 1u);
-#endif
 }
 
 // one missing read: i = index in the caller's arrays, key = packed barcode, f = flag byte
@@ -1797,12 +1684,13 @@ __global__ __launch_bounds__(256) void k_correct(const WlViewSet vs, const uint3
 // then cover everything).
 // rank_out (nullable) + rec_off: the rank every record was corrected to (CRGPU_MISS: not corrected), compact in record
 // order: slot = rec_off[region] + position (rec_off = exclusive prefix of the region counts, k_region_offsets)
+#define K2_PARTS 4u  // workgroups that share a region's records
 __global__ __launch_bounds__(256) void k_correct_records(const WlViewSet vs, const uint32_t *__restrict__ rec_i,
                                                          const uint32_t *__restrict__ rec_key, const uint8_t *__restrict__ rec_fl,
                                                          const uint32_t *__restrict__ rec_count, uint32_t rec_cap,
                                                          uint32_t rec_regions, const K2Params P,
                                                          const uint32_t *__restrict__ rec_off, uint32_t *__restrict__ rank_out,
-                                                         uint32_t parts, const bool n_aside) {
+                                                         uint32_t parts) {
     if (rec_count[rec_regions] != 0u) return;
     // A read with an N takes another path than the others (four exact lookups, its quality line, prior counts: a longer chain of
     // dependent loads), and a tenth of the misses of the cfg3 model are such reads: with them inline every wave ran both paths
@@ -1810,7 +1698,7 @@ __global__ __launch_bounds__(256) void k_correct_records(const WlViewSet vs, con
     // operations complete in order) and worked off 64 at a time, so either path runs with all its lanes busy.
     __shared__ uint32_t s_q[256 / 64][3][128];  // per wave: read index, key, slot of the record (for the rank sink)
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    const bool set_aside = n_aside && P.have_flags && P.qualn != nullptr;
+    const bool set_aside = P.have_flags && P.qualn != nullptr;
     auto drain = [&](uint32_t from, uint32_t n_take, uint32_t base) {
         if (lane < n_take) {
             const uint32_t slot = s_q[wv][2][from + lane];
@@ -1877,6 +1765,7 @@ __global__ __launch_bounds__(256) void k_correct_records(const WlViewSet vs, con
 // reads the qualities of a read and finds an unannounced N, the read is appended to k_correct's list from here.  Corrected ranks are counted per run of equal ranks: one atomic per run.
 #define KS_WAVES 4
 #define KS_HEADS 8
+#define KS_WGS_PER_CU 16u  // the grid's cap: this many workgroups for each of the 256 CUs
 __global__ __launch_bounds__(64 * KS_WAVES) void k_correct_sorted(const WlViewSet vs, const uint32_t *__restrict__ skey,
                                                                   const uint32_t *__restrict__ sidx, uint32_t n_miss,
                                                                   const K2Params P, uint32_t *__restrict__ late_list,
@@ -2026,7 +1915,6 @@ __global__ __launch_bounds__(64 * KS_WAVES) void k_correct_sorted(const WlViewSe
         }
         // (the `corrected` bytes are written afterwards in read order, k_flag_corrected: a third random access per miss here)
         k2_commit(w, P, i, rank, nullptr, false, false);
-#ifndef K2_EXP_NO_ATOMIC
         {   // one atomic per run of equal corrected ranks (a run of equal keys almost always agrees on its rank)
             const uint32_t lr = __shfl_up(rank, 1);
             const unsigned long long starts = __ballot(lane == 0u || rank != lr);
@@ -2034,7 +1922,6 @@ __global__ __launch_bounds__(64 * KS_WAVES) void k_correct_sorted(const WlViewSe
             const uint32_t rl = ab ? (uint32_t)__ffsll((long long)ab) : 64u - lane;
             if (((starts >> lane) & 1ull) && rank != CRGPU_MISS) atomicAdd(&w.corrected[rank], rl);
         }
-#endif
     }
 }
 
@@ -2158,7 +2045,7 @@ static int correct_dev_impl(crgpu_ctx *ctx, const uint32_t *d_cb, const uint8_t 
     // expected_errors < f64::MAX is always true for a finite sum: skip the sum for the default
     const bool check_expected = d_qualn && !fake_quals && ctx->max_expected_errors < 1.7976931348623157e308;
     const K2Params P{d_qualn, ctx->cb_len, ctx->d_ptab, ctx->max_expected_errors, ctx->confidence_threshold, check_expected,
-                     d_idx_inout, d_corrected_out, d_flags != nullptr && getenv("CRGPU_K2_EAGER_QUAL") == nullptr};  // (A/B switch)
+                     d_idx_inout, d_corrected_out, d_flags != nullptr};
     if (use_rec) {
         // reads before rec.first (K1's sampling batch) are not in the records; everything is scanned when they overflowed
         const uint32_t *overflow = rec.d_count + rec.regions;
@@ -2179,8 +2066,9 @@ static int correct_dev_impl(crgpu_ctx *ctx, const uint32_t *d_cb, const uint8_t 
     else sorted = sorted && ctx->n_canon > (1u << 21);
     int sorted_rc = CRGPU_OK;
     if (sorted) {
-        uint32_t *d_o = nullptr, *d_k = nullptr, *d_v = nullptr, *d_kt = nullptr, *d_vt = nullptr;
-        int rc = cr_pool_alloc(ctx, (void **)&d_o, (rec.regions + 1) * sizeof(uint32_t));
+        DevBuf o, k, v, kt, vt;
+        int rc = dmalloc(ctx, o, (rec.regions + 1) * sizeof(uint32_t));
+        uint32_t *const d_o = o.as<uint32_t>();
         uint32_t total = 0;
         if (rc == CRGPU_OK) {
             hipLaunchKernelGGL(k_region_offsets, dim3(1), dim3(1024), 0, ctx->stream, rec.d_count, rec.regions, d_o);
@@ -2188,11 +2076,12 @@ static int correct_dev_impl(crgpu_ctx *ctx, const uint32_t *d_cb, const uint8_t 
         }
         if (rc == CRGPU_OK && total) {
             const uint64_t bytes = (uint64_t)total * sizeof(uint32_t);
-            if (cr_pool_alloc(ctx, (void **)&d_k, bytes) != CRGPU_OK || cr_pool_alloc(ctx, (void **)&d_v, bytes) != CRGPU_OK ||
-                cr_pool_alloc(ctx, (void **)&d_kt, bytes) != CRGPU_OK || cr_pool_alloc(ctx, (void **)&d_vt, bytes) != CRGPU_OK)
+            if (dmalloc(ctx, k, bytes) != CRGPU_OK || dmalloc(ctx, v, bytes) != CRGPU_OK || dmalloc(ctx, kt, bytes) != CRGPU_OK ||
+                dmalloc(ctx, vt, bytes) != CRGPU_OK)
                 rc = cr_fail(ctx, CRGPU_ENOMEM, "crgpu_correct: no memory for the sorted misses");
         }
         if (rc == CRGPU_OK && total) {
+            uint32_t *const d_k = k.as<uint32_t>(), *const d_v = v.as<uint32_t>(), *const d_kt = kt.as<uint32_t>(), *const d_vt = vt.as<uint32_t>();
             hipLaunchKernelGGL(k_compact_records, dim3(rec.regions), dim3(256), 0, ctx->stream, rec.d_i, rec.d_key, rec.d_fl, rec.d_count,
                                rec.cap, rec.regions, d_o, vs.ulib, d_k, d_v, miss_list, n_miss);
             bool in_tmp = false;
@@ -2201,19 +2090,13 @@ static int correct_dev_impl(crgpu_ctx *ctx, const uint32_t *d_cb, const uint8_t 
                 const bool timing = ctx->timing;
                 ctx->timing = false;
                 const uint32_t kb = 2u * ctx->cb_len;
-                uint32_t sb = kb;
-                if (const char *g = getenv("CRGPU_K2_SORT_BITS")) sb = (uint32_t)atoi(g);  // A/B: only the top bits
-                if (sb < 8u || sb > kb) sb = kb;
-                rc = cr_radix_sort_u32(ctx, d_k, d_kt, d_v, d_vt, total, kb - sb, kb, &in_tmp);
+                rc = cr_radix_sort_u32(ctx, d_k, d_kt, d_v, d_vt, total, 0u, kb, &in_tmp);
                 ctx->timing = timing;
             }
             if (rc == CRGPU_OK) {
                 const uint32_t chunks = (total + 63u) / 64u;
                 const uint32_t wgs = (chunks + KS_WAVES - 1) / KS_WAVES;
-                uint32_t per_cu = 16u;
-                if (const char *g = getenv("CRGPU_K2_WGS")) per_cu = (uint32_t)atoi(g);  // A/B
-                if (per_cu < 1u || per_cu > 64u) per_cu = 16u;
-                hipLaunchKernelGGL(k_correct_sorted, dim3(wgs < 256u * per_cu ? wgs : 256u * per_cu), dim3(64 * KS_WAVES), 0, ctx->stream, vs,
+                hipLaunchKernelGGL(k_correct_sorted, dim3(wgs < 256u * KS_WGS_PER_CU ? wgs : 256u * KS_WGS_PER_CU), dim3(64 * KS_WAVES), 0, ctx->stream, vs,
                                    in_tmp ? d_kt : d_k, in_tmp ? d_vt : d_v, total, P, miss_list, n_miss);
                 if (d_corrected_out)
                     hipLaunchKernelGGL(k_flag_corrected, dim3(rec.regions), dim3(256), 0, ctx->stream, rec.d_i, rec.d_fl, rec.d_count,
@@ -2221,11 +2104,6 @@ static int correct_dev_impl(crgpu_ctx *ctx, const uint32_t *d_cb, const uint8_t 
                 if (hipGetLastError() != hipSuccess) rc = cr_fail(ctx, CRGPU_EHIP, "crgpu_correct: launch failed");
             }
         }
-        cr_pool_free(ctx, d_o);
-        cr_pool_free(ctx, d_k);
-        cr_pool_free(ctx, d_v);
-        cr_pool_free(ctx, d_kt);
-        cr_pool_free(ctx, d_vt);
         sorted_rc = rc;
     }
     // K2 is launched for the worst case and loops over the device-side count: no host round trip
@@ -2246,27 +2124,19 @@ static int correct_dev_impl(crgpu_ctx *ctx, const uint32_t *d_cb, const uint8_t 
         for (int l = 0; l < CRGPU_MAX_LIB; l++) plan.lib_slot[l] = l == 0 ? 0u : 0xFFFFFFFFu;
         plan.buckets_per_lib = (ctx->n_canon + BIN_SIZE - 1) / BIN_SIZE;
         plan.n_buckets = plan.buckets_per_lib;
-        uint32_t *d_off = nullptr, *d_rank = nullptr;
+        DevBuf off, rank;
         const uint64_t rec_total_cap = (uint64_t)rec.regions * rec.cap;
-        static const bool no_staged = getenv("CRGPU_K2_ATOMIC_HIST") != nullptr;  // A/B switch
-        bool staged = !no_staged && plan.n_buckets <= SI_MISS_BUCKET && rec_total_cap < 0xFFFFFFFFull;
-        if (staged && (cr_pool_alloc(ctx, (void **)&d_off, (rec.regions + 1) * sizeof(uint32_t)) != CRGPU_OK ||
-                       cr_pool_alloc(ctx, (void **)&d_rank, rec_total_cap * sizeof(uint32_t)) != CRGPU_OK)) {
-            cr_pool_free(ctx, d_off);
-            d_off = d_rank = nullptr;
+        bool staged = plan.n_buckets <= SI_MISS_BUCKET && rec_total_cap < 0xFFFFFFFFull;
+        if (staged && (dmalloc(ctx, off, (rec.regions + 1) * sizeof(uint32_t)) != CRGPU_OK ||
+                       dmalloc(ctx, rank, rec_total_cap * sizeof(uint32_t)) != CRGPU_OK))
             staged = false;  // not fatal: atomics as before
-        }
+        uint32_t *const d_off = staged ? off.as<uint32_t>() : nullptr, *const d_rank = staged ? rank.as<uint32_t>() : nullptr;
         if (staged) hipLaunchKernelGGL(k_region_offsets, dim3(1), dim3(1024), 0, ctx->stream, rec.d_count, rec.regions, d_off);
         // one workgroup per region (the regions are K1's waves: 4096): with 2048 workgroups taking two regions each, the 256
         // that do not fit beside the 1792 resident ones ran almost alone at the end (K2 3.24 -> 2.87 ms per 500 M reads)
-        uint32_t k2_parts = 4;  // four workgroups per region: 2.88 -> 2.74 ms per 500 M reads on top of the one-per-region gain
-        if (const char *g = getenv("CRGPU_K2_PARTS")) k2_parts = (uint32_t)atoi(g);  // A/B
-        if (k2_parts < 1 || k2_parts > 16) k2_parts = 1;
-        uint32_t k2_grid = rec.regions * k2_parts;
-        if (const char *g = getenv("CRGPU_K2_GRID")) k2_grid = (uint32_t)atoi(g) / k2_parts * k2_parts;  // A/B
-        if (k2_grid < k2_parts) k2_grid = k2_parts;
-        hipLaunchKernelGGL(k_correct_records, dim3(k2_grid), dim3(256), 0, ctx->stream, vs, rec.d_i, rec.d_key, rec.d_fl, rec.d_count,
-                           rec.cap, rec.regions, P, d_off, d_rank, k2_parts, getenv("CRGPU_K2_N_INLINE") == nullptr);  // (A/B switch)
+        // K2_PARTS workgroups then share a region: 2.88 -> 2.74 ms per 500 M reads on top of the one-per-region gain
+        hipLaunchKernelGGL(k_correct_records, dim3(rec.regions * K2_PARTS), dim3(256), 0, ctx->stream, vs, rec.d_i, rec.d_key, rec.d_fl,
+                           rec.d_count, rec.cap, rec.regions, P, d_off, d_rank, K2_PARTS);
         int rc = CRGPU_OK;
         if (hipGetLastError() != hipSuccess) rc = cr_fail(ctx, CRGPU_EHIP, "crgpu_correct: launch failed");
         uint32_t total = 0;
@@ -2276,8 +2146,6 @@ static int correct_dev_impl(crgpu_ctx *ctx, const uint32_t *d_cb, const uint8_t 
             vc.v[0].valid = vc.v[0].corrected;  // k_hist_buckets adds to `valid` of the call's library (v[0])
             rc = hist_from_idx(ctx, vc, plan, d_rank, total);
         }
-        cr_pool_free(ctx, d_off);
-        cr_pool_free(ctx, d_rank);
         cr_drop_miss_records(ctx, rec);  // stream-ordered: the pool reuses the blocks only for later work
         return rc;
     }

@@ -380,6 +380,17 @@ static inline void cr_allow_lds(crgpu_ctx *ctx, const void *kernel, size_t bytes
 int cr_pool_alloc(crgpu_ctx *ctx, void **out, uint64_t bytes);
 void cr_pool_free(crgpu_ctx *ctx, void *p);
 void cr_pool_release_all(crgpu_ctx *ctx);  // hipFree every cached block (destroy / memory pressure)
+struct DevBuf {  // pooled temporary, returned to the context's pool at scope exit
+    crgpu_ctx *ctx = nullptr;
+    void *p = nullptr;
+    ~DevBuf() { cr_pool_free(ctx, p); }
+    template <typename T>
+    T *as() { return (T *)p; }
+};
+static inline int dmalloc(crgpu_ctx *ctx, DevBuf &b, uint64_t bytes) {
+    b.ctx = ctx;
+    return cr_pool_alloc(ctx, &b.p, bytes);
+}
 
 hipEvent_t cr_take_event(crgpu_ctx *ctx);  // an event of the ledger's pool (ctx.hip)
 // timing scope: records a HIP event pair around the launches of one family when enabled

@@ -288,13 +288,10 @@ extern "C" int crgpu_create(crgpu_ctx **out, int device_id, int n_ranks, int ran
         return cr_fail(nullptr, CRGPU_EHIP, "hipStreamCreate: %s", hipGetErrorString(e));
     }
     // the second stream carries the branch of the count stage that is NOT the critical path (candidate filter + hash sort beside
-    // the UMI correction): lowest priority, so that its kernels fill what the main stream leaves (CRGPU_STREAM2_PRIORITY=same: A/B)
+    // the UMI correction): lowest priority, so that its kernels fill what the main stream leaves
     int prio_least = 0, prio_greatest = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-    const char *sp = getenv("CRGPU_STREAM2_PRIORITY");
-    const bool low2 = !(sp && strcmp(sp, "same") == 0);
-    if ((low2 ? hipStreamCreateWithPriority(&ctx->stream2, hipStreamNonBlocking, prio_least)
-              : hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking)) != hipSuccess ||
+    if (hipStreamCreateWithPriority(&ctx->stream2, hipStreamNonBlocking, prio_least) != hipSuccess ||
         hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming) != hipSuccess) {
         (void)hipGetLastError();  // the count stage then stays on the one stream

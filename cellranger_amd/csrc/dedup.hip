@@ -520,7 +520,7 @@ static int build_keys_impl(crgpu_ctx *ctx, const crgpu_records *recs, uint64_t *
         const bool aligned16 = ((uintptr_t)recs->d_bc_idx | (uintptr_t)recs->d_umi | (uintptr_t)recs->d_feature |
                                 (uintptr_t)recs->d_umi_qualn) % 16 == 0 && (uintptr_t)recs->d_flags % 4 == 0;
         const uint32_t lqw = (recs->umi_len & 3u) == 0u ? recs->umi_len / 4u : 0u;
-        if (!d_vals_out && !recs->d_umi_len && lqw >= 1 && lqw <= 4 && aligned16 && recs->n >= 4096 && !getenv("CRGPU_KEYS_SCALAR")) {
+        if (!d_vals_out && !recs->d_umi_len && lqw >= 1 && lqw <= 4 && aligned16 && recs->n >= 4096) {
             const uint64_t n4 = recs->n & ~3ull;
 #define CR_BUILD_KEYS_V4(LQW)                                                                                                  \
     if (d_hist)                                                                                                                \

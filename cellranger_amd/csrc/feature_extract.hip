@@ -1016,7 +1016,7 @@ extern "C" int crgpu_extract_features_dev(crgpu_ctx *ctx, int extractor, const u
         if (ctx->trust_buffers && Q.valid && X0.one_tethered && X0.has_dist && Q.sig == X0.sig && Q.n == n &&
             Q.d_seq == (r2 ? d_r2_seq : d_r1_seq) && Q.d_qual == (r2 ? d_r2_qual : d_r1_qual) && Q.d_len == (r2 ? d_r2_len : d_r1_len) &&
             Q.stride == (r2 ? r2_stride : r1_stride) && Q.d_feature_out == d_feature_out && Q.d_n_ids_out == d_n_ids_out &&
-            Q.d_capture_out == d_capture_out && !getenv("CRGPU_FXT_NO_RESUME")) {
+            Q.d_capture_out == d_capture_out) {
             resume = ctx->fxp;
             ctx->fxp = FxPendingSet();  // the block now belongs to this call
         }
@@ -1053,7 +1053,7 @@ extern "C" int crgpu_extract_features_dev(crgpu_ctx *ctx, int extractor, const u
         if (X.t_anchor5) {
             win_hi = std::min(R.stride, (need + 3u) & ~3u);
             // a prefix of wildcards only ("^N{10}(BC)") is never looked at: the window starts at the capture
-            if (X.t_pre_dots && !getenv("CRGPU_FXT_DWORD_LOADS")) win_lo = X.t_pre_len & ~3u;
+            if (X.t_pre_dots) win_lo = X.t_pre_len & ~3u;
         }
         else if (X.t_anchor3 && !R.len && need <= R.stride) win_lo = (R.stride - need) & ~3u;
         const uint32_t win_dw = (win_hi - win_lo) / 4u;
@@ -1074,11 +1074,11 @@ extern "C" int crgpu_extract_features_dev(crgpu_ctx *ctx, int extractor, const u
             while (P.lanes_per_row < win_dw) P.lanes_per_row <<= 1;
             P.pitch = win_dw | 1u;
             P.quad_lanes = 0;
-            if (R.stride >= 16 && !getenv("CRGPU_FXT_DWORD_LOADS")) {  // (A/B switch: one dword per lane and load, as before)
+            if (R.stride >= 16) {  // (shorter rows: one dword per lane and load)
                 P.quad_lanes = 1;
                 while (P.quad_lanes < (win_dw + 3u) / 4u) P.quad_lanes <<= 1;
             }
-            P.prefetch = (P.quad_lanes == 1u || P.quad_lanes == 2u) && !getenv("CRGPU_FXT_NO_PREFETCH");  // (A/B switch)
+            P.prefetch = P.quad_lanes == 1u || P.quad_lanes == 2u;
             uint32_t slots = 64;
             while (slots < 2u * X.t_n_feat) slots <<= 1;  // load factor <= 0.5
             P.slot_mask = slots - 1u;
@@ -1087,14 +1087,14 @@ extern "C" int crgpu_extract_features_dev(crgpu_ctx *ctx, int extractor, const u
                 P.needle_mask = X.t_needle_len >= 4 ? 0xFFFFFFFFu : ((1u << (8u * X.t_needle_len)) - 1u);
                 P.needle_off = X.t_needle_off;
             }
-            P.halves = X.has_dist && X.t_n_feat <= 1024u && X.t_L >= 2 && !getenv("CRGPU_FXT_PROBES");
+            P.halves = X.has_dist && X.t_n_feat <= 1024u && X.t_L >= 2;
             const size_t half_bytes = P.halves ? (size_t)X.t_n_feat * 24 : 0;
             // first pass of the two-pass flow (no distribution, by-products allowed): keep the captures without exact feature
             FxtPending *d_recs = (FxtPending *)resume.d_recs;
             unsigned long long *d_rec_count = (unsigned long long *)(ctx->d_scalars + CR_SCALAR_REC_COUNT);
             uint64_t rec_cap = 0, n_recs_in = resume.valid ? resume.n_recs : 0;
             void *new_recs = nullptr;
-            const bool record = ctx->trust_buffers && !X.has_dist && !resume.valid && n >= 4096 && !getenv("CRGPU_FXT_NO_RESUME");
+            const bool record = ctx->trust_buffers && !X.has_dist && !resume.valid && n >= 4096;
             if (record) {
                 rec_cap = n / 2 + 1024;  // a third of the captures of a real library miss at most; more: the second pass reads the rows
                 if (cr_pool_alloc(ctx, &new_recs, rec_cap * sizeof(FxtPending)) == CRGPU_OK) {

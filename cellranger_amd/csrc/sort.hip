@@ -603,8 +603,6 @@ static uint32_t probe_xccs(crgpu_ctx *ctx) {
     }
     const uint32_t n = mx + 1;
     if (n > 16 || seen != (n >= 32 ? 0xFFFFFFFFu : (1u << n) - 1u)) return 1;
-    if (const char *e = getenv("CRGPU_SORT_XCC"))  // "0": one global ticket sequence (A/B)
-        if (atoi(e) == 0) return 1;
     return n;
 }
 
@@ -763,8 +761,6 @@ bool cr_sweep_plan(uint32_t lo_bit, uint32_t hi_bit, SweepPlan *plan, uint32_t *
     const uint32_t p8 = (total + 7) / 8, p9 = (total + 8) / 9;
     uint32_t n9 = 0;
     if (p9 < p8 && total > 8 * p9) n9 = total - 8 * p9;
-    if (const char *e = getenv("CRGPU_SORT_DIGITS"))
-        if (atoi(e) == 8) n9 = 0;
     const uint32_t passes = n9 ? p9 : p8;
     if (passes > OS_MAX_PASSES) return false;
     memset(plan, 0, sizeof(*plan));
@@ -1372,8 +1368,6 @@ static int radix_sort(crgpu_ctx *ctx, K *d_keys, K *d_tmp, uint32_t *d_vals, uin
     const uint32_t p8 = (total + 7) / 8, p9 = (total + 8) / 9;
     uint32_t n9 = 0;
     if (p9 < p8 && total > 8 * p9) n9 = total - 8 * p9;  // 61 bits: 7 passes, 5 of them 9 bits wide
-    if (const char *e = getenv("CRGPU_SORT_DIGITS"))     // "8": 8-bit digits only (A/B)
-        if (atoi(e) == 8) n9 = 0;
     const uint32_t passes = n9 ? p9 : p8;
     if (sizeof(K) == 8) {
         SweepPlan plan;

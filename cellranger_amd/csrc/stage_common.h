@@ -61,19 +61,6 @@ static inline double cr_robust_divide(double a, double b) { return b == 0.0 ? st
 
 __device__ __forceinline__ uint64_t lowmask(uint32_t bits) { return bits >= 64 ? ~0ull : ((1ull << bits) - 1ull); }
 
-struct DevBuf {  // pooled temporary, returned to the context's pool at scope exit
-    crgpu_ctx *ctx = nullptr;
-    void *p = nullptr;
-    ~DevBuf() { cr_pool_free(ctx, p); }
-    template <typename T>
-    T *as() { return (T *)p; }
-};
-
-static inline int dmalloc(crgpu_ctx *ctx, DevBuf &b, uint64_t bytes) {
-    b.ctx = ctx;
-    return cr_pool_alloc(ctx, &b.p, bytes);
-}
-
 static inline int read_u32(crgpu_ctx *ctx, const uint32_t *d, uint32_t *h) {
     return crgpu_memcpy_d2h(ctx, h, d, sizeof(uint32_t));
 }

@@ -156,7 +156,7 @@ def test_hot_barcode_table_path_bit_exact(monkeypatch):
 def test_split_histogram_rounds_and_their_overflow_fallback(monkeypatch):
     """With the LDS table, pass A counts table hits per table slot in LDS and stages only the other hits (per-wave regions);
     a region that overflows makes the round fall back to device atomics.  Both ways the histograms equal the oracle's, as
-    does the full staging of round 1 (CRGPU_K1_FULL_STAGING=1)."""
+    does the full staging of round 1 (CRGPU_K1_SPLIT=0)."""
     from cellranger_amd import synth as S
 
     monkeypatch.setenv("CRGPU_HOT_MIN_READS", "1")
@@ -171,15 +171,14 @@ def test_split_histogram_rounds_and_their_overflow_fallback(monkeypatch):
 
 
 @pytest.mark.parametrize("case", ["plain", "cold_regions_overflow", "3m_list", "tiny_list_all_T"])
-def test_table_hits_counted_inside_the_lookup_kernel(case, monkeypatch):
-    """CRGPU_K1_MODE=count: the LDS table holds 4-byte keys and one counter per slot; a hit the table answers bumps its
-    counter in the lookup kernel and takes its rank from the table image, the other hits go to per-wave regions and the
+def test_default_table_mode_bit_exact(case, monkeypatch):
+    """The table rounds of pass A in their default mode.  All four lists have fewer than 2^24 ranks, so the LDS table counts
+    the hits it answers in the free high bits of its entries' rank words; the other hits go to per-wave regions and the
     staged histogram (a full region counts its surplus by device atomics).  Indices and both histograms equal the oracle's;
     the all-T barcode (the value of an empty slot) is never cached and still counted."""
     from cellranger_amd import synth as S
 
     monkeypatch.setenv("CRGPU_HOT_MIN_READS", "1")
-    monkeypatch.setenv("CRGPU_K1_MODE", "count")
     if case == "plain":
         assert _compare_barcode_stage(S.Workload(n_total=600_000, seed=S.SEED0 + 19), 600_000)["k1_split_rounds"] >= 1
     elif case == "cold_regions_overflow":
