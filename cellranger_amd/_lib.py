@@ -266,7 +266,28 @@ class AggregatesInfo(C.Structure):
                                           "rows_per_slice")] + [("in_lds", C.c_int32), ("reserved", C.c_uint32), ("rank_ms", C.c_double)]
 
 
+class RpuStats(C.Structure):
+    """crgpu_rpu_stats: index 0 on-target in cells, 1 on-target all barcodes, 2 off-target in cells, 3 off-target all barcodes;
+    the gene counts: 0 on target, 1 off target"""
+    _fields_ = [(n, C.c_double * 4) for n in ("mean", "cv", "median", "iqrnorm", "perc80")] + [("pcr_dupe_reads_frac_on_target", C.c_double)] + [
+        (n, C.c_uint64 * 2) for n in ("n_genes", "n_not_detected", "n_detected", "n_not_quantifiable", "n_quantifiable")] + [
+        ("n_quantifiable_total", C.c_uint64)]
+
+
+class RpuGmmArgs(C.Structure):
+    """crgpu_rpu_gmm_args"""
+    _fields_ = [("start_lk_out", C.c_void_p), ("start_iters_out", C.c_void_p), ("enriched_out", C.c_void_p), ("reserved", C.c_uint64)]
+
+
+class RpuGmmResult(C.Structure):
+    """crgpu_rpu_gmm_result"""
+    _fields_ = [(n, C.c_double) for n in ("log_rpu_threshold", "mu_high", "mu_low", "sd_high", "sd_low", "alpha_high", "alpha_low",
+                                          "n_targeted_enriched", "n_targeted_not_enriched", "n_offtgt_enriched", "n_offtgt_not_enriched",
+                                          "max_lk", "fit_ms")] + [(n, C.c_uint32) for n in ("winner", "n_starts", "fitted", "in_lds")]
+
+
 MS_MAX_CLASSES, MS_NO_CLASS, MS_TOP_N = 32, 255, 5
+TARGETED_MIN_UMIS, GMM_STARTS = 10, 5152
 AGG_KIND_OTHER, AGG_KIND_ANTIBODY, AGG_KIND_ANTIGEN = 0, 1, 2
 AGG_COUNTS, AGG_HIGHLY_CORRECTED, AGG_ANTIGEN = 1, 2, 4
 RTL_MAX_TAGS, RTL_MAX_PROBES, RTL_MAX_TYPES = 64, 256, 8
@@ -411,6 +432,9 @@ SYMBOLS = {
                                       C.POINTER(_u64), C.POINTER(_u64), _vp, _vp]),
     "crgpu_matrix_dev_reads_per_column": (_i, [_vp, C.POINTER(MatrixDevView), _u32, _vp]),
     "crgpu_matrix_summary_stats": (_i, [C.POINTER(MatrixSummaryClass), _u64, _u64, C.POINTER(MatrixSummaryFloats)]),
+    "crgpu_feature_metrics_dev": (_i, [_vp, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "crgpu_targeted_rpu_stats": (_i, [_u32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(RpuStats), _vp, _vp, _vp]),
+    "crgpu_rpu_gmm_dev": (_i, [_vp, _vp, _vp, _u32, C.POINTER(RpuGmmArgs), C.POINTER(RpuGmmResult)]),
     "crgpu_aggregate_min_antibodies": (_i, [_u32, C.POINTER(_u32)]),
     "crgpu_antigen_outlier_threshold": (_i, [_vp, _u32, C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_dbl)]),
     "crgpu_aggregates_by_counts_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, _u32, _vp, _vp, _u32, C.POINTER(_u32),

@@ -242,6 +242,11 @@ struct crgpu_ctx {
     uint32_t ed_lds_features = 0xFFFFFFFFu;  // CRGPU_ED_LDS_FEATURES (tests, read at create): largest n_eval_features the EmptyDrops simulation counts in LDS
     uint32_t ms_lds_features = 0xFFFFFFFFu;  // CRGPU_MS_LDS_FEATURES (tests, read at create): features per LDS slice of the matrix summary, 0 = counters in device memory
     uint32_t agg_lds_rows = 0xFFFFFFFFu;     // CRGPU_AGG_LDS_ROWS (tests, read at create): signal rows per LDS slice of the aggregate rank pass (unset: one slice or none), 0 = the table in device memory
+    uint32_t fm_lds_features = 0xFFFFFFFFu;  // CRGPU_FM_LDS_FEATURES (tests, read at create): features per LDS slice of the per-feature tallies (feature_metrics.h), 0 = counters in device memory
+    // CRGPU_GMM_LDS_VALUES (tests, read at create): largest n whose values a start of the mixture fit keeps in LDS (rpu_gmm.h), 0 = always
+    // device memory.  8192 values are 64 KB, two workgroups per CU: measured 0 - 3 % faster than L2 up to there, 17 % slower at 16 000
+    // values, where one workgroup fills the LDS (profiles/targeted_metrics_throughput.txt)
+    uint32_t gmm_lds_values = 8192;
     // read subsampling (subsample.h; tests, read at create): molecules of fewer reads than ss_wave_min are drawn one per lane, up to
     // ss_wg_min one per wave, larger ones one per workgroup; ss_task_batch = tasks per batch, 0 = by memory
     uint32_t ss_wave_min = 64, ss_wg_min = 4096, ss_task_batch = 0;  // CRGPU_SS_WAVE_MIN, CRGPU_SS_WG_MIN, CRGPU_SS_TASK_BATCH

@@ -219,6 +219,39 @@ const std::vector<AbiStruct> &abi_table() {
               ABI_F(crgpu_matrix_summary_floats, dupe_frac),
               ABI_F(crgpu_matrix_summary_floats, reads_per_cell),
               ABI_F(crgpu_matrix_summary_floats, reads_cum_frac)),
+        ABI_S(crgpu_rpu_stats, ABI_F(crgpu_rpu_stats, mean),
+              ABI_F(crgpu_rpu_stats, cv),
+              ABI_F(crgpu_rpu_stats, median),
+              ABI_F(crgpu_rpu_stats, iqrnorm),
+              ABI_F(crgpu_rpu_stats, perc80),
+              ABI_F(crgpu_rpu_stats, pcr_dupe_reads_frac_on_target),
+              ABI_F(crgpu_rpu_stats, n_genes),
+              ABI_F(crgpu_rpu_stats, n_not_detected),
+              ABI_F(crgpu_rpu_stats, n_detected),
+              ABI_F(crgpu_rpu_stats, n_not_quantifiable),
+              ABI_F(crgpu_rpu_stats, n_quantifiable),
+              ABI_F(crgpu_rpu_stats, n_quantifiable_total)),
+        ABI_S(crgpu_rpu_gmm_args, ABI_F(crgpu_rpu_gmm_args, start_lk_out),
+              ABI_F(crgpu_rpu_gmm_args, start_iters_out),
+              ABI_F(crgpu_rpu_gmm_args, enriched_out),
+              ABI_F(crgpu_rpu_gmm_args, reserved)),
+        ABI_S(crgpu_rpu_gmm_result, ABI_F(crgpu_rpu_gmm_result, log_rpu_threshold),
+              ABI_F(crgpu_rpu_gmm_result, mu_high),
+              ABI_F(crgpu_rpu_gmm_result, mu_low),
+              ABI_F(crgpu_rpu_gmm_result, sd_high),
+              ABI_F(crgpu_rpu_gmm_result, sd_low),
+              ABI_F(crgpu_rpu_gmm_result, alpha_high),
+              ABI_F(crgpu_rpu_gmm_result, alpha_low),
+              ABI_F(crgpu_rpu_gmm_result, n_targeted_enriched),
+              ABI_F(crgpu_rpu_gmm_result, n_targeted_not_enriched),
+              ABI_F(crgpu_rpu_gmm_result, n_offtgt_enriched),
+              ABI_F(crgpu_rpu_gmm_result, n_offtgt_not_enriched),
+              ABI_F(crgpu_rpu_gmm_result, max_lk),
+              ABI_F(crgpu_rpu_gmm_result, fit_ms),
+              ABI_F(crgpu_rpu_gmm_result, winner),
+              ABI_F(crgpu_rpu_gmm_result, n_starts),
+              ABI_F(crgpu_rpu_gmm_result, fitted),
+              ABI_F(crgpu_rpu_gmm_result, in_lds)),
         ABI_S(crgpu_aggregates_info, ABI_F(crgpu_aggregates_info, n_antibodies),
               ABI_F(crgpu_aggregates_info, n_signal),
               ABI_F(crgpu_aggregates_info, top_k),
@@ -311,6 +344,8 @@ extern "C" int crgpu_create(crgpu_ctx **out, int device_id, int n_ranks, int ran
     if (const char *b = getenv("CRGPU_ORDMAG_BATCH")) ctx->ordmag_batch = (uint32_t)strtoul(b, nullptr, 10);  // tests: small batches of the cell call
     if (const char *f = getenv("CRGPU_ED_LDS_FEATURES")) ctx->ed_lds_features = (uint32_t)strtoul(f, nullptr, 10);  // tests: 0 = counters in global memory
     if (const char *f = getenv("CRGPU_MS_LDS_FEATURES")) ctx->ms_lds_features = (uint32_t)strtoul(f, nullptr, 10);  // tests: several slices on a small matrix; 0 = counters in device memory
+    if (const char *f = getenv("CRGPU_FM_LDS_FEATURES")) ctx->fm_lds_features = (uint32_t)strtoul(f, nullptr, 10);  // tests: several slices on a small feature set; 0 = counters in device memory
+    if (const char *f = getenv("CRGPU_GMM_LDS_VALUES")) ctx->gmm_lds_values = (uint32_t)strtoul(f, nullptr, 10);    // tests: 0 = the mixture fit reads its values from device memory
     if (const char *r = getenv("CRGPU_AGG_LDS_ROWS")) ctx->agg_lds_rows = (uint32_t)strtoul(r, nullptr, 10);  // tests: several slices of signal rows; 0 = the rank table in device memory
     if (const char *v = getenv("CRGPU_SS_WAVE_MIN")) ctx->ss_wave_min = (uint32_t)strtoul(v, nullptr, 10);  // tests: reach the wave path of the subsampling draw
     if (const char *v = getenv("CRGPU_SS_WG_MIN")) ctx->ss_wg_min = (uint32_t)strtoul(v, nullptr, 10);      // ... and its workgroup path

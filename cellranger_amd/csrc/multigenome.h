@@ -307,27 +307,6 @@ static double mg_infer(int64_t m, int64_t g0, int64_t g1) {
     const double mle = (double)m / p, cap = (double)(m + g0 + g1);
     return cap < mle ? cap : mle;
 }
-// numpy's pairwise sum of a contiguous f64 array (what np.mean adds up with)
-static double mg_pairwise_sum(const double *a, size_t n) {
-    if (n < 8) {
-        double r = 0.0;
-        for (size_t i = 0; i < n; i++) r += a[i];
-        return r;
-    }
-    if (n <= 128) {
-        double r[8];
-        for (int j = 0; j < 8; j++) r[j] = a[j];
-        size_t i = 8;
-        for (; i < n - (n % 8); i += 8)
-            for (int j = 0; j < 8; j++) r[j] += a[i + j];
-        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-        for (; i < n; i++) res += a[i];
-        return res;
-    }
-    size_t n2 = n / 2;
-    n2 -= n2 % 8;
-    return mg_pairwise_sum(a, n2) + mg_pairwise_sum(a + n2, n - n2);
-}
 // np.percentile(sorted, 100 q), linear
 static double mg_percentile_sorted(const std::vector<double> &s, double q) {
     const size_t M = s.size();
@@ -343,7 +322,7 @@ extern "C" int crgpu_multigenome_summary(const int64_t *boot_counts, uint32_t bo
     std::vector<double> boot(bootstraps);
     for (uint32_t s = 0; s < bootstraps; s++) boot[s] = mg_infer(boot_counts[3 * s], boot_counts[3 * s + 1], boot_counts[3 * s + 2]);
     if (boot_out) std::copy(boot.begin(), boot.end(), boot_out);
-    const double mean = mg_pairwise_sum(boot.data(), bootstraps) / (double)bootstraps, dn = (double)n;
+    const double mean = cr_pairwise_sum(boot.data(), bootstraps) / (double)bootstraps, dn = (double)n;
     res->n = n;
     res->boot_mean = mean;
     res->inferred_multiplets = (int64_t)std::nearbyint(mean);  // round(): half to even

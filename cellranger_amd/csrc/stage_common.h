@@ -59,6 +59,41 @@ int cr_molecule_order(crgpu_ctx *ctx, const crgpu_counts *c, std::vector<uint64_
 // robust_divide of the reference's metrics: NaN for a zero denominator
 static inline double cr_robust_divide(double a, double b) { return b == 0.0 ? std::nan("") : a / b; }
 
+// np.sum of a contiguous f64 array: numpy's pairwise sum (blocks of at most 128 values, eight interleaved partial sums)
+static double cr_pairwise_sum(const double *a, size_t n) {
+    if (n < 8) {
+        double r = 0.0;
+        for (size_t i = 0; i < n; i++) r += a[i];
+        return r;
+    }
+    if (n <= 128) {
+        double r[8];
+        for (int j = 0; j < 8; j++) r[j] = a[j];
+        size_t i = 8;
+        for (; i < n - (n % 8); i += 8)
+            for (int j = 0; j < 8; j++) r[j] += a[i + j];
+        double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        for (; i < n; i++) res += a[i];
+        return res;
+    }
+    size_t n2 = n / 2;
+    n2 -= n2 % 8;
+    return cr_pairwise_sum(a, n2) + cr_pairwise_sum(a + n2, n - n2);
+}
+// np.percentile(sorted x, 100 q) with the linear rule: virtual index (n - 1) q, numpy's _lerp; x is not empty
+static inline double cr_quantile_sorted(const std::vector<double> &x, double q) {
+    const size_t n = x.size();
+    const double vi = (double)(n - 1) * q, fl = std::floor(vi);
+    const size_t p = (size_t)fl, nx = p + 1 < n ? p + 1 : n - 1;
+    const double a = x[p], b = x[nx], t = vi - fl, d = b - a;
+    return t >= 0.5 ? b - d * (1.0 - t) : a + d * t;
+}
+// np.median of sorted x: the mean of the two middle values; x is not empty
+static inline double cr_median_sorted(const std::vector<double> &x) {
+    const size_t n = x.size();
+    return n % 2 ? x[n / 2] : (x[n / 2 - 1] + x[n / 2]) / 2.0;
+}
+
 __device__ __forceinline__ uint64_t lowmask(uint32_t bits) { return bits >= 64 ? ~0ull : ((1ull << bits) - 1ull); }
 
 static inline int read_u32(crgpu_ctx *ctx, const uint32_t *d, uint32_t *h) {

@@ -5,6 +5,7 @@ any of them (a missing library / GPU raises CrgpuError).
 """
 import csv
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -753,6 +754,95 @@ def aggregate_metrics(agg):
     return out
 
 
+RPU_STAT_NAMES = ("mean", "cv", "median", "iqrnorm", "perc80")
+RPU_STAT_SUFFIXES = ("_cells_on_target", "_on_target", "_cells_off_target", "_off_target")      # the index of crgpu_rpu_stats' arrays
+MIN_RPU_THRESHOLD = 2.5      # calculate_targeted_metrics/__init__.py:48
+
+
+def targeted_rpu_stats(num_umis, num_reads, num_umis_cells, num_reads_cells, is_targeted, is_gex=None):
+    """crgpu_targeted_rpu_stats (host, no context): the reads-per-UMI statistics of get_mean_per_gene_rpu_metrics under the
+    reference's metric names, multi_cdna_pcr_dupe_reads_frac_on_target, the gene counts of get_enrichment_metrics (:167-215), and
+    the quantifiable features: q_feature (u32), q_value = log10(num_reads_cells / num_umis_cells), q_label (1 = targeted)"""
+    a = [np.ascontiguousarray(x, dtype=np.uint64) for x in (num_umis, num_reads, num_umis_cells, num_reads_cells)]
+    F = len(a[0])
+    tg = np.ascontiguousarray(is_targeted, dtype=np.uint8)
+    gx = None if is_gex is None else np.ascontiguousarray(is_gex, dtype=np.uint8)
+    if any(len(x) != F for x in a) or len(tg) != F or (gx is not None and len(gx) != F):
+        raise ValueError("targeted_rpu_stats: one entry per feature")
+    st = _lib.RpuStats()
+    qf, qv, ql = np.zeros(F, np.uint32), np.zeros(F, np.float64), np.zeros(F, np.uint8)
+    rc = _lib.load().crgpu_targeted_rpu_stats(F, ptr(a[0]), ptr(a[1]), ptr(a[2]), ptr(a[3]), ptr(tg), ptr(gx), C.byref(st), ptr(qf), ptr(qv), ptr(ql))
+    if rc != 0:
+        raise CrgpuError(rc, (_lib.load().crgpu_last_error(None) or b"").decode())
+    out = {}
+    for k, suffix in enumerate(RPU_STAT_SUFFIXES):
+        for name in RPU_STAT_NAMES:
+            out["%s_reads_per_umi_per_gene%s" % (name, suffix)] = getattr(st, name)[k]
+    out["multi_cdna_pcr_dupe_reads_frac_on_target"] = st.pcr_dupe_reads_frac_on_target
+    for k, suffix in enumerate(("_on_target", "_off_target")):
+        out["num_genes_not_detected" + suffix] = int(st.n_not_detected[k])
+        out["num_genes_detected" + suffix] = int(st.n_detected[k])
+        out["num_genes_not_quantifiable" + suffix] = int(st.n_not_quantifiable[k])
+        out["num_genes" + suffix] = int(st.n_genes[k])
+        out["num_genes_quantifiable" + suffix] = int(st.n_quantifiable[k])
+    nq = int(st.n_quantifiable_total)
+    out["q_feature"], out["q_value"], out["q_label"] = qf[:nq].copy(), qv[:nq].copy(), ql[:nq].copy()
+    # The reference takes this column with numpy's log10, which is not the C library's to the last bit (about one value in six
+    # differs by an ulp).  The Python layer hands the fit numpy's values, so that the threshold is the reference's bit for bit.
+    out["q_value"] = np.log10(a[3][qf[:nq]].astype(np.float64) / a[2][qf[:nq]].astype(np.float64))
+    return out
+
+
+def targeted_metrics(ctx, tallies, is_targeted, summary, num_cells, total_reads, targeted_conf_mapped_reads_frac,
+                     untargeted_conf_mapped_reads_frac, is_gex=None, target_class=0):
+    """The `summary` dict of CALCULATE_TARGETED_METRICS' join (calculate_targeted_metrics/__init__.py:305-385, is_spatial False)
+    under the reference's metric names, and the per-feature enriched_rpu column (f64 per Gene Expression feature in feature order:
+    1 / 0, NaN where the reference writes NaN).  tallies: Counts.feature_metrics (summed over the ranks of a sharded well);
+    summary: a Context.matrix_summary of the FILTERED cells whose class `target_class` holds the target features (its per-cell
+    medians are median_umis_per_cell_on_target / median_genes_per_cell_on_target), or the two medians as a pair; num_cells,
+    total_reads and the two basic_counter_summary fractions come from the caller.  The enrichment call runs on the device
+    (Context.rpu_gmm); the disable_rpu_enrichments rule (:123-155, MIN_RPU_THRESHOLD 2.5) is applied."""
+    nan = float("nan")
+    st = targeted_rpu_stats(tallies["num_umis"], tallies["num_reads"], tallies["num_umis_cells"], tallies["num_reads_cells"], is_targeted, is_gex)
+    if isinstance(summary, MatrixSummary):
+        fl = summary.floats(target_class)
+        med_umis, med_genes = fl["counts_median"], fl["genes_median"]
+    else:
+        med_umis, med_genes = (float(x) for x in summary)
+    frac = float(targeted_conf_mapped_reads_frac)      # (may be NaN)
+    s = {"median_umis_per_cell_on_target": med_umis, "median_genes_per_cell_on_target": med_genes,
+         "total_targeted_reads_per_filtered_bc": _robust_divide(frac * total_reads, num_cells),
+         "multi_frac_conf_transcriptomic_reads_on_target": targeted_conf_mapped_reads_frac,
+         "multi_frac_conf_transcriptomic_reads_off_target": untargeted_conf_mapped_reads_frac}
+    s.update({k: v for k, v in st.items() if not k.startswith("q_") and not k.startswith("num_genes")})
+    key = s["mean_reads_per_umi_per_gene_cells_on_target"]
+    disable = math.isnan(key) or key < MIN_RPU_THRESHOLD
+    fit = ctx.rpu_gmm(st["q_value"], st["q_label"])
+    te, tn, oe, on = (fit[k] for k in ("n_targeted_enriched", "n_targeted_not_enriched", "n_offtgt_enriched", "n_offtgt_not_enriched"))
+    fracs = [f for f in (_robust_divide(oe, oe + te), _robust_divide(oe, oe + on)) if not math.isnan(f)]
+    m = {"log_rpu_threshold": fit["log_rpu_threshold"], "lrpu_fitted_mean_1": fit["mu_high"], "lrpu_fitted_mean_2": fit["mu_low"],
+         "lrpu_fitted_sd_1": fit["sd_high"], "lrpu_fitted_sd_2": fit["sd_low"], "lrpu_fitted_weight_1": fit["alpha_high"],
+         "lrpu_fitted_weight_2": fit["alpha_low"], "frac_on_target_genes_enriched": _robust_divide(te, te + tn),
+         "frac_off_target_genes_enriched": min(fracs) if fracs else nan,      # np.nanmin
+         "num_rpu_enriched_genes_on_target": te, "num_rpu_non_enriched_genes_on_target": tn,
+         "num_rpu_enriched_genes_off_target": oe, "num_rpu_non_enriched_genes_off_target": on}
+    thr = fit["log_rpu_threshold"]
+    if not math.isnan(thr) and disable:      # the enrichments look bad because the depth is too low: do not report them
+        f_on, f_off = m["frac_on_target_genes_enriched"], m["frac_off_target_genes_enriched"]
+        if math.isnan(f_on) or f_on < 0.5 or (not math.isnan(f_off) and f_off > 0.5):
+            m = {k: nan for k in m}
+            thr = nan
+    s.update(m)
+    s.update({k: v for k, v in st.items() if k.startswith("num_genes")})
+    gex = np.ones(len(np.asarray(is_targeted)), bool) if is_gex is None else np.asarray(is_gex).astype(bool)
+    uc, rc_ = np.asarray(tallies["num_umis_cells"], np.float64)[gex], np.asarray(tallies["num_reads_cells"], np.float64)[gex]
+    col = np.full(int(gex.sum()), nan)
+    if not math.isnan(thr):
+        with np.errstate(divide="ignore", invalid="ignore"):
+            col = (np.log10(rc_ / uc) > thr).astype(np.float64)      # NaN > thr is False, as in pandas
+    return s, col
+
+
 def ordmag_candidates(max_expected_cells=1 << 18):
     """the recovered-cells grid of estimate_recovered_cells_ordmag (cell_calling_helpers.py:879-880); host only"""
     out, n = np.zeros(2000, np.int64), C.c_uint32()
@@ -916,6 +1006,20 @@ class Counts:
         self.ctx._check(self.ctx.L.crgpu_probe_metrics_dev(self.ctx.h, self.h, n_probes, _p(d_cells), d_cells.size, ptr(all_),
                                                            ptr(filt)))
         return all_, filt
+
+    def feature_metrics(self, n_features, cell_ranks, libs=0):
+        """collapse_feature_counts (pandas_utils.py:571-661) over the molecule table: dict of num_umis, num_reads, num_umis_cells,
+        num_reads_cells (numpy u64 per feature) over the molecules of the libraries `libs` (an index or several:
+        filter_library_idx); the `_cells` sums over the barcodes of cell_ranks (strictly ascending canonical ranks, the union of
+        the pass-filter barcodes of those libraries; numpy, DeviceArray or None).  Sharded counts give this rank's share: add the
+        shares with Context.allreduce_sum."""
+        if cell_ranks is None:
+            cell_ranks = np.zeros(0, np.uint32)
+        d_cells = cell_ranks if isinstance(cell_ranks, DeviceArray) else self.ctx.upload(np.ascontiguousarray(cell_ranks, dtype=np.uint32))
+        out = {k: np.zeros(int(n_features), np.uint64) for k in ("num_umis", "num_reads", "num_umis_cells", "num_reads_cells")}
+        self.ctx._check(self.ctx.L.crgpu_feature_metrics_dev(self.ctx.h, self.h, int(n_features), _lib_mask("feature_metrics", libs),
+                                                             _p(d_cells) if d_cells.size else None, d_cells.size, *(ptr(v) for v in out.values())))
+        return out
 
     def subsample(self, rates, task_types, cell_ranks, n_genomes=1, feature_genome=None, cell_genome_mask=None, feature_mask=None,
                   seed=1, n_features=None):
@@ -1732,6 +1836,28 @@ class Context:
                                                     _p(reads), ptr(per_f), ptr(ge2), structs, C.byref(r_all), C.byref(r_union), _p(cpc), _p(gpc)))
         have = reads is not None
         return MatrixSummary(self, list(structs), per_f, ge2, r_all.value if have else None, r_union.value if have else None, n_cells, cpc, gpc)
+
+    def rpu_gmm(self, values, labels, want_starts=False):
+        """fit_enrichments(tgt_label, values, method=BOTH_TIED) (targeted/gmm.py:116-183) on the device: values = log10 reads per
+        UMI of the quantifiable genes (f64), labels = 1 for a targeted gene.  -> dict of the seven RpuFitParams (sd_high / sd_low
+        are the tied PRECISION, as the reference reports them), the four ClassStats (f64, NaN where the reference has NaN),
+        `enriched` (u8 per gene: value >= threshold), winner, n_starts, max_lk, fitted, in_lds, fit_ms; want_starts adds start_lk
+        (f64[5152]) and start_iters (u32[5152])."""
+        v = np.ascontiguousarray(values, dtype=np.float64).reshape(-1)
+        lab = np.ascontiguousarray(labels).astype(np.uint8).reshape(-1)
+        if len(v) != len(lab):
+            raise ValueError("rpu_gmm: one label per value")
+        enriched = np.zeros(len(v), np.uint8)
+        lk = np.zeros(_lib.GMM_STARTS, np.float64) if want_starts else None
+        it = np.zeros(_lib.GMM_STARTS, np.uint32) if want_starts else None
+        a = _lib.RpuGmmArgs(start_lk_out=ptr(lk), start_iters_out=ptr(it), enriched_out=ptr(enriched) if len(v) else None, reserved=0)
+        res = _lib.RpuGmmResult()
+        self._check(self.L.crgpu_rpu_gmm_dev(self.h, ptr(v) if len(v) else None, ptr(lab) if len(v) else None, len(v), C.byref(a), C.byref(res)))
+        out = {name: getattr(res, name) for name, _ in _lib.RpuGmmResult._fields_}
+        out["enriched"] = enriched
+        if want_starts:
+            out["start_lk"], out["start_iters"] = lk, it
+        return out
 
     def call_additional_cells(self, m, call, low, high, emptydrops_minimum_umis=500, num_sims=10000, max_adj_pvalue=0.01, seed=0,
                               feature_mask=None, sim_table=None, keep_sim_table=False, keep_profile=True):

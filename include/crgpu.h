@@ -1035,6 +1035,82 @@ int crgpu_filter_cells_mito_dev(crgpu_ctx *ctx, const uint32_t *d_mito_umis_per_
                                 const uint64_t *d_cell_cols, uint64_t n_cells, double max_mito_percent, uint64_t **d_kept_cols_out,
                                 uint64_t *n_kept_out, uint64_t **d_removed_cols_out, uint64_t *n_removed_out);
 
+/* ---- targeted wells: per-feature tallies, reads-per-UMI statistics and the enrichment call ----------------------------------------
+ * Replaces the arithmetic of CALCULATE_TARGETED_METRICS (mro/rna/stages/targeted/calculate_targeted_metrics/__init__.py) for a
+ * targeted Gene Expression well whose counts were made under crgpu_set_target_filter.
+ *   crgpu_feature_metrics_dev  pandas_utils.collapse_feature_counts (lib/python/cellranger/pandas_utils.py:571-661) over the molecule
+ *                              table of `counts`: per feature the molecules (num_umis) and their reads (num_reads) of the
+ *                              libraries l with bit l of lib_mask (filter_library_idx), and the same over the molecules whose
+ *                              barcode is in d_cell_ranks (num_umis_cells, num_reads_cells).  d_cell_ranks: DEVICE u32[n_cells],
+ *                              strictly ascending canonical ranks (checked as crgpu_probe_metrics_dev checks them).  The reference
+ *                              ORs the pass-filter barcodes of all selected libraries (pandas_utils.py:609-618), so ONE list, the
+ *                              union, is the faithful interface.  Every output is a host u64[n_features] and may be NULL.
+ *                              CRGPU_EINVAL: an empty lib_mask, a library beyond the key layout, n_features other than the key
+ *                              layout's, ranks that do not ascend.  Empty counts or n_cells == 0 is no error.  For sharded counts
+ *                              the rank's share is returned: add the shares with crgpu_allreduce_sum_i64.  Dense barcode keys
+ *                              (CRGPU_OPT_DENSE_BARCODE_KEYS) and per-read UMI lengths are handled.  The sums are 64 bits wide;
+ *                              they are collected per run of equal (barcode, feature) in slices of the workgroups' LDS and added
+ *                              up from a slab of plain stores; CRGPU_FM_LDS_FEATURES=<n> in the environment when the context is
+ *                              created (tests) fixes the features per slice, 0 = counters in device memory.  No result depends on it.
+ *   crgpu_targeted_rpu_stats   host only, no context.  is_targeted / is_gex: u8[n_features] (is_gex NULL = every feature is Gene
+ *                              Expression; the reference drops the other rows first).  Index k of the five arrays of
+ *                              crgpu_rpu_stats: 0 on-target in cells, 1 on-target all barcodes, 2 off-target in cells, 3 off-target
+ *                              all barcodes -- mean, cv, median, iqr / median and the 80th percentile of num_reads / num_umis over
+ *                              the features of the class with num_umis_cells >= CRGPU_TARGETED_MIN_UMIS
+ *                              (get_mean_per_gene_rpu_metrics); an empty selection gives 0.0.  Divisions follow robust_divide (NaN for
+ *                              a zero divisor); 0 / 0 of the all-barcodes column is NaN and left out, as pandas' skipna does.
+ *                              median, percentile and iqr use numpy's linear rule between two order statistics; mean and std add
+ *                              in numpy's pairwise order.  Index k of the gene counts: 0 on target, 1 off target
+ *                              (get_enrichment_metrics:167-215).  q_*_out (each nullable, room for n_features entries): the
+ *                              quantifiable features in ascending order with log10(num_reads_cells / num_umis_cells) and their
+ *                              label (1 = targeted): the input of crgpu_rpu_gmm_dev; their number is n_quantifiable_total.
+ *   crgpu_rpu_gmm_dev          fit_enrichments(tgt_label, values, method = BOTH_TIED) (lib/python/cellranger/targeted/gmm.py) as a
+ *                              whole: values host f64[n] (finite, else CRGPU_EINVAL), labels host u8[n].  The guards (:145-169)
+ *                              return the reference's NaN pattern without a launch.  Otherwise CRGPU_GMM_STARTS independent EM fits
+ *                              of the 1-D two-component tied mixture (scikit-learn's iteration: reg_covar 1e-6, nk + 10 eps, lower
+ *                              bound = mean logsumexp of the previous parameters, tol 1e-3, at most 100 iterations) run on the
+ *                              device, one workgroup per start; the first of the likeliest starts wins.  Every sum is reduced in
+ *                              an order that depends on n alone: a start's result depends neither on the grid, nor on the other
+ *                              starts, nor on the run.  CRGPU_GMM_LDS_VALUES=<n> (environment, at creation; tests) is the largest n
+ *                              whose values a workgroup keeps in LDS (default 8192), 0 = always device memory.  No result depends
+ *                              on it.  When max(values) == 0 the reference's rule yields 10202 starts; all run, the per-start
+ *                              arrays receive the first CRGPU_GMM_STARTS.
+ *     QUIRK kept: sd_high and sd_low are what the reference reports for the tied model -- the PRECISION, twice (gmm.py:86-90).
+ * NOT covered: BOTH_SPHERICAL and OFFTARGETS_ONLY (the stage uses neither), collapse_feature_counts(downsample=...), the CSV writer. */
+#define CRGPU_TARGETED_MIN_UMIS 10 /* MIN_UMIS */
+#define CRGPU_GMM_STARTS 5152      /* 1 + 101 * 102 / 2 */
+struct crgpu_rpu_stats {
+    double mean[4], cv[4], median[4], iqrnorm[4], perc80[4];
+    double pcr_dupe_reads_frac_on_target;  /* multi_cdna_pcr_dupe_reads_frac_on_target */
+    uint64_t n_genes[2], n_not_detected[2], n_detected[2], n_not_quantifiable[2], n_quantifiable[2];
+    uint64_t n_quantifiable_total;
+};
+typedef struct crgpu_rpu_stats crgpu_rpu_stats;
+struct crgpu_rpu_gmm_args {
+    double *start_lk_out;      /* host f64[CRGPU_GMM_STARTS] or NULL: the log-likelihood of every start (NaN: not run) */
+    uint32_t *start_iters_out; /* host u32[CRGPU_GMM_STARTS] or NULL: its EM iterations */
+    uint8_t *enriched_out;     /* host u8[n] or NULL: values >= log_rpu_threshold */
+    uint64_t reserved;         /* 0 */
+};
+typedef struct crgpu_rpu_gmm_args crgpu_rpu_gmm_args;
+struct crgpu_rpu_gmm_result {
+    double log_rpu_threshold, mu_high, mu_low, sd_high, sd_low, alpha_high, alpha_low; /* RpuFitParams; sd_*: the precision (quirk) */
+    double n_targeted_enriched, n_targeted_not_enriched, n_offtgt_enriched, n_offtgt_not_enriched; /* ClassStats, NaN as the reference */
+    double max_lk;  /* the winner's log-likelihood */
+    double fit_ms;  /* host time from the launch of the fits until they have finished (the copies of the results not included) */
+    uint32_t winner, n_starts; /* the winning start (0xFFFFFFFF: no fit) of n_starts */
+    uint32_t fitted, in_lds;   /* 1: the mixture ran; 1: the values were kept in LDS */
+};
+typedef struct crgpu_rpu_gmm_result crgpu_rpu_gmm_result;
+int crgpu_feature_metrics_dev(crgpu_ctx *ctx, crgpu_counts *counts, uint32_t n_features, uint32_t lib_mask, const uint32_t *d_cell_ranks,
+                              uint64_t n_cells, uint64_t *umis_out, uint64_t *reads_out, uint64_t *umis_cells_out,
+                              uint64_t *reads_cells_out);
+int crgpu_targeted_rpu_stats(uint32_t n_features, const uint64_t *num_umis, const uint64_t *num_reads, const uint64_t *num_umis_cells,
+                             const uint64_t *num_reads_cells, const uint8_t *is_targeted, const uint8_t *is_gex, crgpu_rpu_stats *out,
+                             uint32_t *q_feature_out, double *q_value_out, uint8_t *q_label_out);
+int crgpu_rpu_gmm_dev(crgpu_ctx *ctx, const double *values, const uint8_t *labels, uint32_t n, const crgpu_rpu_gmm_args *args,
+                      crgpu_rpu_gmm_result *result);
+
 /* ---- cell calling: the non-ambient ("EmptyDrops") barcodes behind the initial call ---------------------------------------------
  * Replaces find_nonambient_barcodes (lib/python/cellranger/cell_calling.py:144-263) as call_additional_cells runs it
  * (cell_calling_helpers.py:575-668) for ONE genome / GEM group; the caller loops and passes a feature mask.

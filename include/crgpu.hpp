@@ -1114,6 +1114,63 @@ inline crgpu_matrix_summary_floats matrix_summary_stats(const MatrixSummary &s, 
     return matrix_summary_stats(s.classes.at(k), s.classes.at(k).reads_cells, s.reads_all);
 }
 
+// ---- a targeted well (CALCULATE_TARGETED_METRICS): tallies, reads-per-UMI statistics, the enrichment call --------------------------------
+static_assert(sizeof(crgpu_rpu_stats) == 256, "crgpu_rpu_stats changed: bump CRGPU_ABI_VERSION and every binding");
+static_assert(sizeof(crgpu_rpu_gmm_args) == 32, "crgpu_rpu_gmm_args changed: bump CRGPU_ABI_VERSION and every binding");
+static_assert(sizeof(crgpu_rpu_gmm_result) == 120, "crgpu_rpu_gmm_result changed: bump CRGPU_ABI_VERSION and every binding");
+struct FeatureMetrics {  // pandas_utils.collapse_feature_counts: per feature
+    std::vector<uint64_t> num_umis, num_reads, num_umis_cells, num_reads_cells;
+};
+/// crgpu_feature_metrics_dev on `counts` (DupBuilder::build(&counts)): lib_mask = filter_library_idx as bits; cell_ranks: strictly
+/// ascending canonical ranks, the union of the pass-filter barcodes of those libraries
+inline FeatureMetrics feature_metrics(Context &ctx, crgpu_counts *counts, uint32_t n_features, const std::vector<uint32_t> &cell_ranks = {},
+                                      uint32_t lib_mask = 1u) {
+    FeatureMetrics out;
+    out.num_umis.assign(n_features, 0), out.num_reads.assign(n_features, 0), out.num_umis_cells.assign(n_features, 0), out.num_reads_cells.assign(n_features, 0);
+    detail::DeviceCopy<uint32_t> d_cells(ctx, cell_ranks);
+    ctx.check(crgpu_feature_metrics_dev(ctx.get(), counts, n_features, lib_mask, cell_ranks.empty() ? nullptr : d_cells.get(), cell_ranks.size(),
+                                        out.num_umis.data(), out.num_reads.data(), out.num_umis_cells.data(), out.num_reads_cells.data()));
+    return out;
+}
+struct TargetedRpuStats {
+    crgpu_rpu_stats stats;
+    std::vector<uint32_t> q_feature;  // the quantifiable features, ascending ...
+    std::vector<double> q_value;      // ... log10(num_reads_cells / num_umis_cells) ...
+    std::vector<uint8_t> q_label;     // ... 1 = targeted: the input of rpu_gmm
+};
+/// crgpu_targeted_rpu_stats (host): is_gex empty = every feature is Gene Expression
+inline TargetedRpuStats targeted_rpu_stats(const FeatureMetrics &t, const std::vector<uint8_t> &is_targeted, const std::vector<uint8_t> &is_gex = {}) {
+    const size_t F = t.num_umis.size();
+    if (t.num_reads.size() != F || t.num_umis_cells.size() != F || t.num_reads_cells.size() != F || is_targeted.size() != F || (!is_gex.empty() && is_gex.size() != F))
+        throw Error(CRGPU_EINVAL, "targeted_rpu_stats: shapes");
+    TargetedRpuStats out;
+    out.q_feature.resize(F), out.q_value.resize(F), out.q_label.resize(F);
+    const int rc = crgpu_targeted_rpu_stats((uint32_t)F, t.num_umis.data(), t.num_reads.data(), t.num_umis_cells.data(), t.num_reads_cells.data(), is_targeted.data(),
+                                            is_gex.empty() ? nullptr : is_gex.data(), &out.stats, out.q_feature.data(), out.q_value.data(), out.q_label.data());
+    if (rc != CRGPU_OK) throw Error(rc, crgpu_last_error(nullptr));
+    const size_t nq = out.stats.n_quantifiable_total;
+    out.q_feature.resize(nq), out.q_value.resize(nq), out.q_label.resize(nq);
+    return out;
+}
+struct RpuGmm {
+    crgpu_rpu_gmm_result result;       // sd_high / sd_low: the tied PRECISION, as the reference reports it (gmm.py:86-90)
+    std::vector<uint8_t> enriched;     // per gene: value >= log_rpu_threshold
+    std::vector<double> start_lk;      // [CRGPU_GMM_STARTS] when asked for
+    std::vector<uint32_t> start_iters;
+};
+/// crgpu_rpu_gmm_dev: fit_enrichments(labels, values, method = BOTH_TIED)
+inline RpuGmm rpu_gmm(Context &ctx, const std::vector<double> &values, const std::vector<uint8_t> &labels, bool want_starts = false) {
+    if (values.size() != labels.size() || values.size() > 0xFFFFFFFFull) throw Error(CRGPU_EINVAL, "rpu_gmm: one label per value");
+    RpuGmm out;
+    out.enriched.assign(values.size(), 0);
+    if (want_starts) out.start_lk.assign(CRGPU_GMM_STARTS, 0.0), out.start_iters.assign(CRGPU_GMM_STARTS, 0);
+    crgpu_rpu_gmm_args a{want_starts ? out.start_lk.data() : nullptr, want_starts ? out.start_iters.data() : nullptr,
+                         values.empty() ? nullptr : out.enriched.data(), 0};
+    ctx.check(crgpu_rpu_gmm_dev(ctx.get(), values.empty() ? nullptr : values.data(), labels.empty() ? nullptr : labels.data(), (uint32_t)values.size(), &a,
+                                &out.result));
+    return out;
+}
+
 // ---- protein aggregates of an antibody / antigen well; the closing filters of a cell call ---------------------------------------------
 static_assert(sizeof(crgpu_aggregates_info) == 48, "crgpu_aggregates_info changed: bump CRGPU_ABI_VERSION and every binding");
 /// int(np.round(n_signal * _calculate_fraction_to_use(n_signal)))
