@@ -62,19 +62,11 @@ extern "C" int crgpu_aggregate_min_antibodies(uint32_t n_signal, uint32_t *out) 
     return CRGPU_OK;
 }
 
-// np.quantile(x, q) of n sorted values, q = i / 4: numpy's virtual index (n - 1) q and its _lerp
-static inline double ag_quantile(const std::vector<uint32_t> &x, double q) {
-    const double vi = (double)(x.size() - 1) * q, fl = std::floor(vi), t = vi - fl;
-    const size_t lo = (size_t)fl, hi = std::min(lo + 1, x.size() - 1);
-    const double a = (double)x[lo], b = (double)x[hi], d = b - a;
-    return t < 0.5 ? a + d * t : b - d * (1.0 - t);
-}
-
 extern "C" int crgpu_antigen_outlier_threshold(const uint32_t *top_counts, uint32_t n, double *q1_out, double *q3_out, double *threshold_out) {
     if (!top_counts || !n || !threshold_out) return cr_fail(nullptr, CRGPU_EINVAL, "crgpu_antigen_outlier_threshold: at least one count and an output");
     std::vector<uint32_t> x(top_counts, top_counts + n);
     std::sort(x.begin(), x.end());
-    const double q3 = ag_quantile(x, 0.75), q1 = ag_quantile(x, 0.25);
+    const double q3 = cr_quantile_sorted(x, 0.75), q1 = cr_quantile_sorted(x, 0.25);
     const double iqr = q3 - q1, spread = iqr * 3.0;
     if (q1_out) *q1_out = q1;
     if (q3_out) *q3_out = q3;
@@ -183,17 +175,6 @@ __global__ __launch_bounds__(256) void k_ag_sort_rows(const uint32_t *__restrict
 }
 
 // ---- pass 2: the place of every signal-antibody entry among the candidates of its row -------------------------------------------------
-// the number of x[0 .. n) below v, x ascending
-template <typename T>
-__device__ __forceinline__ uint32_t ag_count_below(const T *x, uint32_t n, T v) {
-    uint32_t lo = 0, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (x[mid] < v) lo = mid + 1u; else hi = mid;
-    }
-    return lo;
-}
-
 // LDS: workgroup blockIdx.x = s * G + w holds the signal rows [s * rows, min(n_signal, (s + 1) * rows)); bounds[2 s], bounds[2 s + 1]
 // = the features of the first of them and one past the last.  !LDS: every workgroup takes all rows from device memory.
 template <bool LDS>
@@ -234,10 +215,10 @@ __global__ __launch_bounds__(AG_WG) void k_ag_rank(const long long *__restrict__
             // the row's nnz and the column counters.  Nearly every entry of a well lies below the lowest counted candidate.
             const uint32_t z = zeros[r];
             if (z < Kc && key > k[z]) {
-                const uint32_t p = z + 1u + ag_count_below(k + z + 1u, Kc - z - 1u, key);
+                const uint32_t p = z + 1u + cr_lower_bound(k + z + 1u, Kc - z - 1u, key);  // the pairs of the row below this entry
                 atomicAdd(LDS ? &s_cnt[(r - r0) * K1 + p] : &cnt[(size_t)r * K1 + p], 1u);
             }
-            if (sparse[r]) atomicAdd(&cnt2[(size_t)r * K1 + ag_count_below(cols_sorted, Kc, (uint32_t)c)], 1u);
+            if (sparse[r]) atomicAdd(&cnt2[(size_t)r * K1 + cr_lower_bound(cols_sorted, Kc, (uint32_t)c)], 1u);
         }
     }
     if (LDS) {
@@ -712,28 +693,6 @@ extern "C" int crgpu_sum_u32_dev(crgpu_ctx *ctx, const uint32_t *d_values, uint6
 }
 
 // ---- the closing filters of a cell call ------------------------------------------------------------------------------------------------
-// flag bit 0: a column >= V, bit 1: the list does not ascend strictly
-__global__ __launch_bounds__(256) void k_ag_check_cols(const uint64_t *__restrict__ cols, uint64_t n, uint64_t V, uint32_t *__restrict__ flag) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += stride) {
-        if (cols[k] >= V) atomicOr(flag, 1u);
-        if (k && cols[k - 1] >= cols[k]) atomicOr(flag, 2u);
-    }
-}
-static int ag_check_cols(crgpu_ctx *ctx, const char *who, const uint64_t *d_cols, uint64_t n, uint64_t V) {
-    CR_REQUIRE(ctx, n <= V && (d_cols || !n), CRGPU_EINVAL, "%s: the cell call does not fit the %llu columns", who, (unsigned long long)V);
-    CR_REQUIRE(ctx, V < 0xFFFFFFFFull, CRGPU_ERANGE, "%s: fewer than 2^32 - 1 columns", who);
-    if (!n) return CRGPU_OK;
-    uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, flag = 0;
-    CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
-    hipLaunchKernelGGL(k_ag_check_cols, dim3(cr_grid(n, 256)), dim3(256), 0, ctx->stream, d_cols, n, V, d_flag);
-    CR_HIP(ctx, hipGetLastError());
-    CR_TRY(read_u32(ctx, d_flag, &flag));
-    CR_REQUIRE(ctx, !(flag & 1u), CRGPU_EINVAL, "%s: a cell column is out of range", who);
-    CR_REQUIRE(ctx, !(flag & 2u), CRGPU_EINVAL, "%s: the cell columns do not ascend strictly", who);
-    return CRGPU_OK;
-}
-
 // cell k of the list stays (keep) or leaves (!keep): the ONE compaction of both filters, the order of the list preserved
 struct AgCellFlag {
     const uint64_t *cols;
@@ -764,8 +723,16 @@ static int ag_filter_cells(crgpu_ctx *ctx, const char *who, AgCellFlag flag, uin
     *d_kept = nullptr, *n_kept = 0;
     if (d_removed) *d_removed = nullptr, *n_removed = 0;
     CR_REQUIRE(ctx, flag.total || !n_cells, CRGPU_EINVAL, "%s: NULL counts", who);
-    CR_TRY(ag_check_cols(ctx, who, flag.cols, n_cells, V));
-    uint32_t *d_total = ctx->d_scalars + CR_SCALAR_TOTAL;
+    CR_REQUIRE(ctx, n_cells <= V && (flag.cols || !n_cells), CRGPU_EINVAL, "%s: the cell call does not fit the %llu columns", who, (unsigned long long)V);
+    CR_REQUIRE(ctx, V < 0xFFFFFFFFull, CRGPU_ERANGE, "%s: fewer than 2^32 - 1 columns", who);
+    uint32_t *d_total = ctx->d_scalars + CR_SCALAR_TOTAL, *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, bad = 0;
+    if (n_cells) {  // the list: in range, strictly ascending
+        CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
+        cr_check_columns<true>(ctx, flag.cols, n_cells, V, MarkNone{}, d_flag);
+        CR_HIP(ctx, hipGetLastError());
+        CR_TRY(read_u32(ctx, d_flag, &bad));
+        CR_TRY(cr_list_verdict(ctx, bad, who, "cell column"));
+    }
     for (int pass = 0; pass < (d_removed ? 2 : 1); pass++) {
         flag.keep = pass == 0;
         uint64_t *d = nullptr;

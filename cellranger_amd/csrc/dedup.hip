@@ -2680,20 +2680,7 @@ extern "C" void crgpu_counts_free(crgpu_ctx *ctx, crgpu_counts *c) {
 // trimmed list; MERGE_MOLECULES' join (cr_aggr/src/merge_molecules.rs:131-330) then concatenates the samples with
 // barcode_idx shifted by the number of barcodes retained before (bc_idx_offsets).  The H5 container, the gem-group /
 // library look-up tables (two tiny maps applied per row) and the metrics JSON stay with the host.
-// flag[c] = 1 for the listed columns (flag == NULL: the list is only checked); bad: a column out of range.  Also the cells of
-// EmptyDrops and of the Flex GEM passes (cr_mark_columns, stage_common.h)
-__global__ __launch_bounds__(256) void k_mark_columns(const uint64_t *__restrict__ cols, uint64_t n, uint64_t V, uint8_t *__restrict__ flag,
-                                                      uint32_t *__restrict__ bad) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += stride) {
-        const uint64_t c = cols[k];
-        if (c >= V) *bad = 1u;
-        else if (flag) flag[c] = 1u;
-    }
-}
-void cr_mark_columns(crgpu_ctx *ctx, const uint64_t *d_cols, uint64_t n, uint64_t V, uint8_t *d_flag, uint32_t *d_bad) {
-    hipLaunchKernelGGL(k_mark_columns, dim3(cr_grid(n, 256)), dim3(256), 0, ctx->stream, d_cols, n, V, d_flag, d_bad);
-}
+// The barcodes to keep are marked by cr_check_columns (stage_common.h): flag[c] = 1 for a listed barcode, *d_bad for one out of range
 struct EmitRetained {
     uint32_t *retained, *newpos;
     struct Pre {};
@@ -2733,10 +2720,10 @@ extern "C" int crgpu_trim_molecule_barcodes_dev(crgpu_ctx *ctx, uint64_t *d_barc
         if (n_pass) {
             CR_TRY(dmalloc(ctx, pf_b, n_pass * sizeof(uint64_t)));
             CR_HIP(ctx, hipMemcpyAsync(pf_b.p, pass_filter_idx_inout, n_pass * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-            cr_mark_columns(ctx, pf_b.as<uint64_t>(), n_pass, n_barcodes, flag, d_bad);
+            cr_check_columns<false>(ctx, pf_b.as<uint64_t>(), n_pass, n_barcodes, MarkByte{flag}, d_bad);
         }
         if (!pass_only && n_molecules)
-            cr_mark_columns(ctx, d_barcode_idx_inout, n_molecules, n_barcodes, flag, d_bad);
+            cr_check_columns<false>(ctx, d_barcode_idx_inout, n_molecules, n_barcodes, MarkByte{flag}, d_bad);
         CR_HIP(ctx, hipGetLastError());
         if (n_barcodes)
             CR_TRY(compact(ctx, CandFlag{flag}, EmitRetained{ret_b.as<uint32_t>(), pos_b.as<uint32_t>()}, n_barcodes, ctx->d_sort_hist, d_total));
@@ -2753,7 +2740,7 @@ extern "C" int crgpu_trim_molecule_barcodes_dev(crgpu_ctx *ctx, uint64_t *d_barc
             DevBuf chk_b;
             CR_TRY(dmalloc(ctx, chk_b, n_barcodes + 1));
             CR_HIP(ctx, hipMemsetAsync(chk_b.p, 0, n_barcodes + 1, ctx->stream));
-            cr_mark_columns(ctx, d_barcode_idx_inout, n_molecules, n_barcodes, chk_b.as<uint8_t>(), d_bad);
+            cr_check_columns<false>(ctx, d_barcode_idx_inout, n_molecules, n_barcodes, MarkByte{chk_b.as<uint8_t>()}, d_bad);
             std::vector<uint8_t> used(n_barcodes), keep(n_barcodes);
             CR_TRY(crgpu_memcpy_d2h(ctx, used.data(), chk_b.p, n_barcodes));
             CR_TRY(crgpu_memcpy_d2h(ctx, keep.data(), flag, n_barcodes));

@@ -660,7 +660,7 @@ static int ed_run(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const uint8_t *feat
     DevBuf cell_b;
     CR_TRY(dmalloc(ctx, cell_b, V));
     CR_HIP(ctx, hipMemsetAsync(cell_b.p, 0, V, ctx->stream));
-    cr_mark_columns(ctx, d_cell_cols, n_cells, V, cell_b.as<uint8_t>(), d_flag);
+    cr_check_columns<false>(ctx, d_cell_cols, n_cells, V, MarkByte{cell_b.as<uint8_t>()}, d_flag);
     CR_HIP(ctx, hipGetLastError());
     if (thr <= 0xFFFFFFFFull) {
         CR_TRY(cr_pool_alloc(ctx, (void **)&out->d_eval_cols, V * sizeof(uint64_t)));

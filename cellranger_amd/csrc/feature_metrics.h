@@ -11,7 +11,7 @@
 //
 // The table is ordered by (barcode, feature, library, UMI): the molecules of a barcode are contiguous (a SEGMENT) with ascending
 // features, a feature's molecules are spread over every barcode, and a gene of every cell is one hot address.  So
-//   1. the segment starts come from one compaction over d_mkeys (as the probe counts take them);
+//   1. the segment starts come from one compaction over d_mkeys (cr_barcode_segments);
 //   2. the membership of a barcode in the cell list is decided ONCE per segment (k_fm_seg_cells: a thread per segment searches
 //      d_cell_ranks); k_fm_pass gives every segment to one wave, which loads the bounds and the membership of its next segment
 //      one segment ahead.  Every run of equal (barcode, feature) is added up inside the wave first (a segmented
@@ -29,7 +29,6 @@
 #include <algorithm>
 #include <cmath>
 
-#include "probe_counts.h"  // SegHeadFlag, EmitSegStart, k_pc_not_ascending
 #include "stage_common.h"
 
 #define FM_WG 1024u  // threads of a pass workgroup: 16 waves, one segment each
@@ -78,11 +77,7 @@ __global__ __launch_bounds__(256) void k_fm_seg_cells(const uint64_t *__restrict
     if (s >= n_seg) return;
     const uint64_t bc = keys[seg_start[s]] >> sh_bc;
     const uint32_t r = back ? (bc < n_back ? back[bc] : NONE32) : (uint32_t)bc;
-    uint64_t x = 0, y = n_cells;
-    while (x < y) {
-        const uint64_t mid = (x + y) >> 1;
-        if (cells[mid] < r) x = mid + 1; else y = mid;
-    }
+    const uint64_t x = cr_lower_bound(cells, n_cells, r);
     seg_cell[s] = x < n_cells && cells[x] == r && (back || bc <= 0xFFFFFFFFull);
 }
 
@@ -202,30 +197,14 @@ extern "C" int crgpu_feature_metrics_dev(crgpu_ctx *ctx, crgpu_counts *c, uint32
     uint64_t *outs[4] = {umis_out, reads_out, umis_cells_out, reads_cells_out};
     for (uint64_t *o : outs)
         if (o && nf) memset(o, 0, nf * sizeof(uint64_t));
-    uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, differ = 0;
-    if (n_cells > 1) {  // checked the way crgpu_probe_metrics_dev checks them
-        CrTimer t(ctx, CRGPU_T_DEDUP, n_cells);
-        CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
-        hipLaunchKernelGGL(k_pc_not_ascending, dim3(cr_grid(n_cells, 256)), dim3(256), 0, ctx->stream, d_cell_ranks, n_cells, d_flag);
-        CR_HIP(ctx, hipGetLastError());
-        CR_TRY(read_u32(ctx, d_flag, &differ));
-        CR_REQUIRE(ctx, !differ, CRGPU_EINVAL, "crgpu_feature_metrics_dev: the cell barcode ranks must be strictly ascending");
-    }
+    CR_TRY(cr_require_ascending_ranks(ctx, d_cell_ranks, n_cells, "crgpu_feature_metrics_dev", "cell barcode rank"));
     if (!nm || !nf) return CRGPU_OK;
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "");
     // ---- the segments: one per barcode with a molecule ----
-    const uint64_t n_bc = c->d_back ? c->n_back : c->n_canon;
-    const uint64_t seg_max = nm < n_bc ? nm : n_bc;
     DevBuf seg_b, cell_b, out_b, slab_b, carry_b;
-    CR_TRY(dmalloc(ctx, seg_b, (seg_max + 1) * sizeof(uint32_t)));
-    uint32_t *seg_start = seg_b.as<uint32_t>(), *d_total = ctx->d_scalars + CR_SCALAR_TOTAL, n_seg = 0;
-    {
-        CrTimer t(ctx, CRGPU_T_DEDUP, nm);
-        CR_TRY(compact(ctx, SegHeadFlag{c->d_mkeys, L.sh_bc()}, EmitSegStart{seg_start}, nm, ctx->d_sort_hist, d_total));
-    }
-    CR_TRY(read_u32(ctx, d_total, &n_seg));
-    CR_REQUIRE(ctx, n_seg >= 1 && n_seg <= seg_max, CRGPU_EHIP, "crgpu_feature_metrics_dev: %u barcode segments for at most %llu barcodes", n_seg,
-               (unsigned long long)seg_max);
+    uint32_t n_seg = 0;
+    CR_TRY(cr_barcode_segments(ctx, c, "crgpu_feature_metrics_dev", seg_b, &n_seg));
+    const uint32_t *seg_start = seg_b.as<uint32_t>();
     const FmKeys K{L.sh_bc(), L.sh_feat(), L.bits_feat, L.sh_libid(), L.bits_lib, n_features};
     CR_TRY(dmalloc(ctx, out_b, 4 * nf * sizeof(unsigned long long)));
     CR_TRY(dmalloc(ctx, cell_b, n_seg));
@@ -233,7 +212,6 @@ extern "C" int crgpu_feature_metrics_dev(crgpu_ctx *ctx, crgpu_counts *c, uint32
     const uint64_t n_groups = ((uint64_t)n_seg + FM_WAVES - 1) / FM_WAVES;
     {
         CrTimer t(ctx, CRGPU_T_DEDUP, nm);
-        CR_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)(seg_start + n_seg), (int)(uint32_t)nm, 1, ctx->stream));  // the end of the last segment
         hipLaunchKernelGGL(k_fm_seg_cells, dim3((n_seg + 255u) / 256u), dim3(256), 0, ctx->stream, c->d_mkeys, seg_start, n_seg, L.sh_bc(), d_cell_ranks, n_cells,
                            c->d_back, c->n_back, cell_b.as<uint8_t>());
         if (lds) {

@@ -4,7 +4,7 @@
 // (lib/python/cellranger/rna/report_matrix.py:76-387): sum_masked / count_ge_masked of the views (feature mask x barcode mask) of
 // the RAW matrix (cellranger/sparse.py:36-168) and top_n (matrix.py:55-67).  A class is one (feature type, genome) pair.
 //
-//   1. k_ms_cell_index: cellidx[c] = k + 1 for the k-th listed cell (0: not a cell); the list is checked on the way.
+//   1. cr_check_columns with MarkPlace: cellidx[c] = k + 1 for the k-th listed cell (0: not a cell); the list is checked on the way.
 //   2. k_ms_pass, ONE pass over all columns, one wave per column (the loads of MS_UNROLL rounds of 64 entries are issued together, the
 //      bounds of the wave's next column one column ahead: the pass waits for loads, not for the LDS): per class the column's sum and its entries >= 1 (static
 //      accumulators per lane, a wave reduction per class the column holds) feed the class totals (lane k keeps class k, one LDS
@@ -42,21 +42,6 @@
 #define MS_T_WORDS 5u
 #define MS_T_SEEN (CRGPU_MS_MAX_CLASSES * MS_T_WORDS)  // entries the pass looked at: == nnz when the rows ascend
 #define MS_T_TOTAL (MS_T_SEEN + 1u)
-
-// flag bit 0: a column out of range, bit 1: the list does not ascend strictly
-__global__ __launch_bounds__(256) void k_ms_cell_index(const uint64_t *__restrict__ cols, uint64_t n, uint64_t V, uint32_t *__restrict__ cellidx,
-                                                       uint32_t *__restrict__ flag) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += stride) {
-        const uint64_t c = cols[k];
-        if (c >= V) {
-            atomicOr(flag, 1u);
-            continue;
-        }
-        if (k && cols[k - 1] >= c) atomicOr(flag, 2u);
-        cellidx[c] = (uint32_t)k + 1u;
-    }
-}
 
 template <int NC, bool LDS>
 __global__ __launch_bounds__(MS_WG) void k_ms_pass(const long long *__restrict__ indptr, const int32_t *__restrict__ indices,
@@ -343,13 +328,10 @@ extern "C" int crgpu_matrix_summary_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *
         CR_TRY(crgpu_memcpy_h2d(ctx, mask_b.p, h_mask.data(), h_mask.size() * sizeof(uint32_t)));
         uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, flag[3] = {0, 0, 0};  // the list, the pass, the per-cell sums
         CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(flag), ctx->stream));
-        if (n_cells) {
-            hipLaunchKernelGGL(k_ms_cell_index, dim3(cr_grid(n_cells, 256)), dim3(256), 0, ctx->stream, d_cell_cols, n_cells, V, idx_b.as<uint32_t>(), d_flag);
-            CR_HIP(ctx, hipGetLastError());
-        }
+        cr_check_columns<true>(ctx, d_cell_cols, n_cells, V, MarkPlace{idx_b.as<uint32_t>()}, d_flag);
+        CR_HIP(ctx, hipGetLastError());
         CR_TRY(read_u32(ctx, d_flag, &flag[0]));
-        CR_REQUIRE(ctx, !(flag[0] & 1u), CRGPU_EINVAL, "crgpu_matrix_summary_dev: a cell column is out of range");
-        CR_REQUIRE(ctx, !(flag[0] & 2u), CRGPU_EINVAL, "crgpu_matrix_summary_dev: the cell columns do not ascend strictly");
+        CR_TRY(cr_list_verdict(ctx, flag[0], "crgpu_matrix_summary_dev", "cell column"));
         const uint64_t n_pc = (uint64_t)n_classes * (n_cells ? n_cells : 1);
         const uint64_t nf1 = n_features ? n_features : 1;
         CR_TRY(dmalloc(ctx, tot_b, (MS_T_TOTAL + 2 + CRGPU_MS_MAX_CLASSES + 6 * CRGPU_MS_MAX_CLASSES) * sizeof(unsigned long long)));
@@ -546,10 +528,9 @@ extern "C" int crgpu_matrix_dev_reads_per_column(crgpu_ctx *ctx, const crgpu_mat
 }
 
 // ---- the floats of _report (host, f64, unfused; no context) -----------------------------------------------------------------------
-// np.percentile(x, 25 i) of n sorted values from x[floor((n - 1) i / 4)] = a and its right neighbour b (numpy's _lerp)
+// np.percentile(x, 25 i) of n sorted values from x[floor((n - 1) i / 4)] = a and its right neighbour b: the fraction in integers
 static inline double ms_percentile(uint64_t n, uint32_t i, uint32_t a, uint32_t b) {
-    const double t = (double)((n - 1) * i % 4) / 4.0, d = (double)b - (double)a;
-    return t < 0.5 ? (double)a + d * t : (double)b - d * (1.0 - t);
+    return cr_lerp((double)a, (double)b, (double)((n - 1) * i % 4) / 4.0);
 }
 static void ms_summarize(uint64_t n, uint64_t sum, uint64_t sq_hi, uint64_t sq_lo, const uint32_t *q, double *mean, double *median, double *cv, double *iqr,
                          double *stddev) {

@@ -1,6 +1,6 @@
 // molecule_stages.hip -- the analysis stages that read the molecule table of a crgpu_counts: one translation unit, because
-// normalize_depth.h launches the draw kernels of subsample.h and these, like feature_metrics.h, check their cell lists with the
-// kernel of probe_counts.h.  rpu_gmm.h (the enrichment call behind the tallies of feature_metrics.h) rides along.
+// normalize_depth.h launches the draw kernels of subsample.h.  The barcode segments and the check of a cell list are those of
+// stage_common.h; rpu_gmm.h (the enrichment call behind the tallies of feature_metrics.h) rides along.
 // Every header names what it uses; the order below is of no consequence.
 #include "feature_metrics.h"
 #include "normalize_depth.h"

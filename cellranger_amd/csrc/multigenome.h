@@ -147,10 +147,6 @@ __host__ __device__ __forceinline__ void mg_p10_ranks(uint32_t M, uint32_t *k_lo
     *k_hi = *k_lo + 1u < M ? *k_lo + 1u : M - 1u;
     *g = v - fl;
 }
-__host__ __device__ __forceinline__ double mg_lerp(double x_lo, double x_hi, double g) {
-    const double d = x_hi - x_lo;
-    return g >= 0.5 ? x_hi - d * (1.0 - g) : x_lo + d * g;
-}
 
 #define MG_ITEMS 8
 // C_all[rows][n]: the scanned multiplicities of the samples of one batch, in place order.  Outputs per sample (row index + the
@@ -201,8 +197,8 @@ __global__ __launch_bounds__(256) void k_mg_sample(const uint32_t *__restrict__ 
         double t0 = 10.0, t1 = 10.0;  // DEFAULT_MULTIPLET_THRESHOLD
         int32_t br = CRGPU_MG_BRANCH_DEFAULT;
         if (both) {
-            t0 = mg_lerp((double)s_stat[0], (double)s_stat[1], gA);
-            t1 = mg_lerp((double)s_stat[2], (double)s_stat[3], gB);
+            t0 = cr_lerp((double)s_stat[0], (double)s_stat[1], gA);
+            t1 = cr_lerp((double)s_stat[2], (double)s_stat[3], gB);
             br = CRGPU_MG_BRANCH_PERCENTILES;
         }
         const double lo = t0 < t1 ? t0 : t1, hi = t0 < t1 ? t1 : t0;
@@ -256,7 +252,7 @@ __global__ __launch_bounds__(256) void k_mg_sample(const uint32_t *__restrict__ 
             __syncthreads();
             if (s_carry > k[1]) break;  // uniform: both ranks are behind
         }
-        if (tid == 0) s_thr[0] = s_thr[1] = mg_lerp((double)s_sumstat[0], (double)s_sumstat[1], g);
+        if (tid == 0) s_thr[0] = s_thr[1] = cr_lerp((double)s_sumstat[0], (double)s_sumstat[1], g);
         __syncthreads();
     }
     const double t0 = s_thr[0], t1 = s_thr[1];
@@ -307,13 +303,6 @@ static double mg_infer(int64_t m, int64_t g0, int64_t g1) {
     const double mle = (double)m / p, cap = (double)(m + g0 + g1);
     return cap < mle ? cap : mle;
 }
-// np.percentile(sorted, 100 q), linear
-static double mg_percentile_sorted(const std::vector<double> &s, double q) {
-    const size_t M = s.size();
-    const double v = (double)(M - 1) * q, fl = std::floor(v);
-    const size_t lo = (size_t)fl, hi = lo + 1 < M ? lo + 1 : M - 1;
-    return mg_lerp(s[lo], s[hi], v - fl);
-}
 
 extern "C" int crgpu_multigenome_summary(const int64_t *boot_counts, uint32_t bootstraps, uint64_t n, double *boot_out,
                                          crgpu_multigenome_result *res) {
@@ -332,8 +321,8 @@ extern "C" int crgpu_multigenome_summary(const int64_t *boot_counts, uint32_t bo
     res->rate_bounds_set = bootstraps > 1;
     if (bootstraps > 1) {
         std::sort(boot.begin(), boot.end());
-        res->multiplet_rate_lb = cr_robust_divide(mg_percentile_sorted(boot, 2.5 / 100.0), dn);
-        res->multiplet_rate_ub = cr_robust_divide(mg_percentile_sorted(boot, 97.5 / 100.0), dn);
+        res->multiplet_rate_lb = cr_robust_divide(cr_quantile_sorted(boot, 2.5 / 100.0), dn);
+        res->multiplet_rate_ub = cr_robust_divide(cr_quantile_sorted(boot, 97.5 / 100.0), dn);
     }
     return CRGPU_OK;
 }

@@ -23,7 +23,6 @@
 // Nothing is floating point on the device and nothing depends on timing or on the two thresholds of the draw.
 #pragma once
 
-#include "probe_counts.h"
 #include "stage_common.h"
 #include "subsample.h"
 
@@ -44,11 +43,7 @@ __global__ __launch_bounds__(256) void k_nd_cell_table(const uint32_t *__restric
         const uint32_t r = cells[ci];
         uint32_t b = r;
         if (back) {  // CRGPU_OPT_DENSE_BARCODE_KEYS: the field holds the column, back[column] = rank (ascending)
-            uint32_t lo = 0, hi = n_bc;
-            while (lo < hi) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (back[mid] < r) lo = mid + 1; else hi = mid;
-            }
+            const uint32_t lo = cr_lower_bound(back, n_bc, r);
             if (lo >= n_bc || back[lo] != r) continue;
             b = lo;
         }
@@ -168,14 +163,8 @@ static int nd_run(crgpu_ctx *ctx, crgpu_counts *c, const crgpu_normalize_depth_a
     for (int64_t *p : {a->reads_per_lib, a->kept_reads_per_lib, a->kept_molecules_per_lib})
         if (p) memset(p, 0, (size_t)NL * sizeof(int64_t));
 
-    uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, *d_total = ctx->d_scalars + CR_SCALAR_TOTAL, differ = 0;
-    if (NC > 1) {
-        CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
-        hipLaunchKernelGGL(k_pc_not_ascending, dim3(cr_grid(NC, 256)), dim3(256), 0, ctx->stream, a->d_cell_ranks, NC, d_flag);
-        CR_HIP(ctx, hipGetLastError());
-        CR_TRY(read_u32(ctx, d_flag, &differ));
-        CR_REQUIRE(ctx, !differ, CRGPU_EINVAL, "crgpu_normalize_depth_dev: the cell barcode ranks must be strictly ascending");
-    }
+    uint32_t *d_total = ctx->d_scalars + CR_SCALAR_TOTAL;
+    CR_TRY(cr_require_ascending_ranks(ctx, a->d_cell_ranks, NC, "crgpu_normalize_depth_dev", "cell barcode rank"));
     if (!nm) return a->matrix ? crgpu_assemble_matrix_dev(ctx, nullptr, nullptr, nullptr, 0, a->matrix) : CRGPU_OK;
 
     const uint32_t wave_min = std::min<uint32_t>(std::max<uint32_t>(ctx->ss_wave_min, 1u), SS_WAVE_MIN_MAX);

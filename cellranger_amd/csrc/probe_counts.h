@@ -49,21 +49,6 @@ __device__ __forceinline__ uint32_t pc_code(int32_t p, uint32_t n_probes, bool *
     return p < 0 ? PC_NONE : (uint32_t)p;
 }
 
-struct SegHeadFlag {  // first molecule of a barcode
-    const uint64_t *keys;
-    uint32_t shift;
-    __device__ __forceinline__ bool operator()(uint64_t i) const {
-        const uint64_t prev = keys[i ? i - 1 : 0];
-        return (i == 0) | ((keys[i] >> shift) != (prev >> shift));
-    }
-};
-struct EmitSegStart {
-    uint32_t *start;
-    struct Pre {};
-    __device__ __forceinline__ Pre pre(uint64_t) const { return Pre(); }
-    __device__ __forceinline__ void operator()(uint64_t i, uint32_t o, Pre) const { start[o] = (uint32_t)i; }
-};
-
 // One thread per segment: its route.  Segments of the two workgroup classes are appended to lists (their order is of no
 // consequence: a segment's place in d_sp is fixed); a segment of the global route gets room for its keys (glob_off) and one
 // work item per PC_CHUNK molecules.
@@ -312,24 +297,15 @@ static int probe_triplets_ensure(crgpu_ctx *ctx, crgpu_counts *c, uint32_t n_pro
         return CRGPU_OK;
     }
     const KeyLayout &L = c->layout;
-    const uint64_t n_bc = c->d_back ? c->n_back : c->n_canon;
-    const uint64_t seg_max = nm < n_bc ? nm : n_bc;
     uint32_t *d_block = ctx->d_sort_hist, *d_total = ctx->d_scalars + CR_SCALAR_TOTAL;
     DevBuf seg_b, ctl_b, sp_b;
-    CR_TRY(dmalloc(ctx, seg_b, (seg_max + 1) * sizeof(uint32_t)));
     CR_TRY(dmalloc(ctx, ctl_b, PC_CTL_WORDS * sizeof(uint32_t)));
     CR_TRY(dmalloc(ctx, sp_b, nm * sizeof(uint32_t)));
-    uint32_t *seg_start = seg_b.as<uint32_t>(), *ctl = ctl_b.as<uint32_t>(), *sp = sp_b.as<uint32_t>();
+    uint32_t *ctl = ctl_b.as<uint32_t>(), *sp = sp_b.as<uint32_t>();
     uint32_t n_seg = 0;
-    {
-        CrTimer t(ctx, CRGPU_T_DEDUP, nm);
-        CR_HIP(ctx, hipMemsetAsync(ctl, 0, PC_CTL_WORDS * sizeof(uint32_t), ctx->stream));
-        CR_TRY(compact(ctx, SegHeadFlag{c->d_mkeys, L.sh_bc()}, EmitSegStart{seg_start}, nm, d_block, d_total));
-    }
-    CR_TRY(read_u32(ctx, d_total, &n_seg));
-    CR_REQUIRE(ctx, n_seg >= 1 && n_seg <= seg_max, CRGPU_EHIP, "%s: %u barcode segments for at most %llu barcodes", who, n_seg,
-               (unsigned long long)seg_max);
-    const uint32_t nm32 = (uint32_t)nm;
+    CR_HIP(ctx, hipMemsetAsync(ctl, 0, PC_CTL_WORDS * sizeof(uint32_t), ctx->stream));
+    CR_TRY(cr_barcode_segments(ctx, c, who, seg_b, &n_seg));
+    uint32_t *seg_start = seg_b.as<uint32_t>();
     const uint32_t cap = ctx->probe_seg_cap < PC_BIG_CAP ? ctx->probe_seg_cap : PC_BIG_CAP;
     // lists: workgroup classes (a segment there has more than PC_WAVE_CAP molecules), global route (chunks of PC_CHUNK)
     const uint64_t list_max = nm / PC_WAVE_CAP + 1, chunk_max = nm / PC_CHUNK + n_seg;
@@ -342,7 +318,6 @@ static int probe_triplets_ensure(crgpu_ctx *ctx, crgpu_counts *c, uint32_t n_pro
     uint32_t h_ctl[PC_CTL_WORDS];
     {
         CrTimer t(ctx, CRGPU_T_DEDUP);
-        CR_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)(seg_start + n_seg), (int)nm32, 1, ctx->stream));  // the end of the last segment
         hipLaunchKernelGGL(k_pc_classify, dim3((n_seg + 255u) / 256u), dim3(256), 0, ctx->stream, seg_start, n_seg, cap,
                            mid_b.as<uint32_t>(), big_b.as<uint32_t>(), goff_b.as<uint32_t>(), cseg_b.as<uint32_t>(),
                            cfirst_b.as<uint32_t>(), ctl);
@@ -466,11 +441,6 @@ extern "C" int crgpu_counts_probe_triplets(crgpu_ctx *ctx, crgpu_counts *c, uint
 }
 
 // ---- probe x barcode matrix (write_probe_matrix_h5_helper, probe_barcode_matrix.rs:176-262) ------------------------------
-__global__ __launch_bounds__(256) void k_pc_not_ascending(const uint32_t *__restrict__ r, uint64_t n, uint32_t *__restrict__ flag) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i + 1 < n; i += stride)
-        if (r[i] >= r[i + 1]) *flag = 1u;
-}
 // per column: the range of triplets of its barcode (empty when the barcode has none)
 __global__ __launch_bounds__(256) void k_pc_column_ranges(const uint32_t *__restrict__ col_rank, uint64_t n_cols,
                                                           const uint32_t *__restrict__ t_bc, uint64_t nt, uint32_t *__restrict__ first,
@@ -478,18 +448,9 @@ __global__ __launch_bounds__(256) void k_pc_column_ranges(const uint32_t *__rest
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n_cols; c += stride) {
         const uint32_t r = col_rank[c];
-        uint64_t lo = 0, hi = nt;
-        while (lo < hi) {
-            const uint64_t mid = (lo + hi) >> 1;
-            if (t_bc[mid] < r) lo = mid + 1; else hi = mid;
-        }
-        uint64_t lo2 = lo, hi2 = nt;
-        while (lo2 < hi2) {
-            const uint64_t mid = (lo2 + hi2) >> 1;
-            if (t_bc[mid] <= r) lo2 = mid + 1; else hi2 = mid;
-        }
+        const uint64_t lo = cr_lower_bound(t_bc, nt, r);
         first[c] = (uint32_t)lo;
-        len[c] = (uint32_t)(lo2 - lo);
+        len[c] = (uint32_t)cr_upper_bound(t_bc + lo, nt - lo, r);
     }
 }
 // one wave per column: a contiguous copy of its triplets (off = the scanned lengths)
@@ -522,19 +483,17 @@ extern "C" int crgpu_assemble_probe_matrix_dev(crgpu_ctx *ctx, crgpu_counts *c, 
     DevBuf rank_b, first_b, len_b;
     uint64_t V = n_sample;
     if (d_sample_ranks) {
-        uint32_t differ = 0;
+        uint32_t flag = 0;
         CR_TRY(dmalloc(ctx, rank_b, (V ? V : 1) * sizeof(uint32_t)));
         {
             CrTimer t(ctx, CRGPU_T_MATRIX, V);
             CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
-            if (V) {
-                CR_HIP(ctx, hipMemcpyAsync(rank_b.p, d_sample_ranks, V * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
-                hipLaunchKernelGGL(k_pc_not_ascending, dim3(cr_grid(V, 256)), dim3(256), 0, ctx->stream, rank_b.as<uint32_t>(), V, d_flag);
-            }
+            if (V) CR_HIP(ctx, hipMemcpyAsync(rank_b.p, d_sample_ranks, V * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
+            cr_check_ranks(ctx, rank_b.as<uint32_t>(), V, d_flag);
             CR_HIP(ctx, hipGetLastError());
         }
-        CR_TRY(read_u32(ctx, d_flag, &differ));
-        CR_REQUIRE(ctx, !differ, CRGPU_EINVAL, "crgpu_assemble_probe_matrix_dev: the sample's barcode ranks must be strictly ascending");
+        CR_TRY(read_u32(ctx, d_flag, &flag));
+        CR_TRY(cr_list_verdict(ctx, flag, "crgpu_assemble_probe_matrix_dev", "sample barcode rank"));
     } else {
         SeenFlag seen;
         seen.ct.n = 0;
@@ -597,11 +556,7 @@ __global__ __launch_bounds__(256) void k_pc_probe_sums(const uint32_t *__restric
         if (p >= n_probes) continue;
         const unsigned long long n = t_cnt[i];
         atomicAdd(&all[p], n);
-        uint64_t lo = 0, hi = n_cells;
-        while (lo < hi) {
-            const uint64_t mid = (lo + hi) >> 1;
-            if (cells[mid] < r) lo = mid + 1; else hi = mid;
-        }
+        const uint64_t lo = cr_lower_bound(cells, n_cells, r);
         if (lo < n_cells && cells[lo] == r) atomicAdd(&filtered[p], n);
     }
 }
@@ -613,7 +568,7 @@ extern "C" int crgpu_probe_metrics_dev(crgpu_ctx *ctx, crgpu_counts *c, uint32_t
     CR_REQUIRE(ctx, d_cell_ranks || n_cells == 0, CRGPU_EINVAL, "crgpu_probe_metrics_dev: NULL cell ranks");
     CR_TRY(probe_triplets_ensure(ctx, c, n_probes, "crgpu_probe_metrics_dev"));
     if (!n_probes) return CRGPU_OK;
-    uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, differ = 0;
+    uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, flag = 0;
     DevBuf sums_b;
     const uint64_t bytes = (uint64_t)n_probes * sizeof(unsigned long long);
     CR_TRY(dmalloc(ctx, sums_b, 2 * bytes));
@@ -622,15 +577,14 @@ extern "C" int crgpu_probe_metrics_dev(crgpu_ctx *ctx, crgpu_counts *c, uint32_t
         CrTimer t(ctx, CRGPU_T_DEDUP, c->n_pt);
         CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
         CR_HIP(ctx, hipMemsetAsync(sums_b.p, 0, 2 * bytes, ctx->stream));
-        if (n_cells > 1)
-            hipLaunchKernelGGL(k_pc_not_ascending, dim3(cr_grid(n_cells, 256)), dim3(256), 0, ctx->stream, d_cell_ranks, n_cells, d_flag);
+        cr_check_ranks(ctx, d_cell_ranks, n_cells, d_flag);
         if (c->n_pt)
             hipLaunchKernelGGL(k_pc_probe_sums, dim3(cr_grid(c->n_pt, 256)), dim3(256), 0, ctx->stream, c->d_pt_bc, c->d_pt_probe, c->d_pt_count,
                                c->n_pt, n_probes, d_cell_ranks, n_cells, all, filtered);
         CR_HIP(ctx, hipGetLastError());
     }
-    CR_TRY(read_u32(ctx, d_flag, &differ));
-    CR_REQUIRE(ctx, !differ, CRGPU_EINVAL, "crgpu_probe_metrics_dev: the cell barcode ranks must be strictly ascending");
+    CR_TRY(read_u32(ctx, d_flag, &flag));
+    CR_TRY(cr_list_verdict(ctx, flag, "crgpu_probe_metrics_dev", "cell barcode rank"));
     if (umis_in_all_barcodes_out) CR_TRY(crgpu_memcpy_d2h(ctx, umis_in_all_barcodes_out, all, bytes));
     if (umis_in_filtered_barcodes_out) CR_TRY(crgpu_memcpy_d2h(ctx, umis_in_filtered_barcodes_out, filtered, bytes));
     return CRGPU_OK;

@@ -380,12 +380,10 @@ extern "C" int crgpu_rtl_gem_runs_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m,
     CR_HIP(ctx, hipMemsetAsync(cell_b.p, 0, V, ctx->stream));
     uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, flag = 0;
     CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
-    if (n_cells) {
-        cr_mark_columns(ctx, d_cell_cols, n_cells, V, cell_b.as<uint8_t>(), d_flag);
-        CR_HIP(ctx, hipGetLastError());
-    }
+    cr_check_columns<false>(ctx, d_cell_cols, n_cells, V, MarkByte{cell_b.as<uint8_t>()}, d_flag);
+    CR_HIP(ctx, hipGetLastError());
     CR_TRY(read_u32(ctx, d_flag, &flag));
-    CR_REQUIRE(ctx, !flag, CRGPU_EINVAL, "crgpu_rtl_gem_runs_dev: a cell column is out of range");
+    CR_TRY(cr_list_verdict(ctx, flag, "crgpu_rtl_gem_runs_dev", "cell column"));
     CR_TRY(dmalloc(ctx, out_b, RT_O_WORDS * sizeof(unsigned long long)));
     unsigned long long *d_out = out_b.as<unsigned long long>();
     CR_HIP(ctx, hipMemsetAsync(d_out, 0, RT_O_WORDS * sizeof(unsigned long long), ctx->stream));
@@ -490,10 +488,10 @@ extern "C" int crgpu_rtl_medians_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, 
     CR_REQUIRE(ctx, d_sums && d_cell_cols, CRGPU_EINVAL, "crgpu_rtl_medians_dev: NULL d_sums or d_cell_cols");
     uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, flag = 0, *d_total = ctx->d_scalars + CR_SCALAR_TOTAL, N = 0;
     CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
-    cr_mark_columns(ctx, d_cell_cols, n_cells, V, nullptr, d_flag);
+    cr_check_columns<false>(ctx, d_cell_cols, n_cells, V, MarkNone{}, d_flag);
     CR_HIP(ctx, hipGetLastError());
     CR_TRY(read_u32(ctx, d_flag, &flag));
-    CR_REQUIRE(ctx, !flag, CRGPU_EINVAL, "crgpu_rtl_medians_dev: a cell column is out of range");
+    CR_TRY(cr_list_verdict(ctx, flag, "crgpu_rtl_medians_dev", "cell column"));
     DevBuf key_b, keyt_b, cnt_b;
     CR_TRY(dmalloc(ctx, key_b, n_cells * sizeof(uint64_t)));
     CR_TRY(dmalloc(ctx, keyt_b, n_cells * sizeof(uint64_t)));

@@ -1,6 +1,7 @@
 // stage_common.h -- what the count stage (dedup.hip) and the analysis stages behind it (molecule_stages.hip on a crgpu_counts,
-// matrix_stages.hip on a crgpu_matrix_dev) share: the two opaque result types, pooled temporaries, the stream compaction and
-// the few host functions one of these units defines for the others.
+// matrix_stages.hip on a crgpu_matrix_dev) share: the two opaque result types, the stream compaction, the barcode segments of the
+// molecule table, the search in an ascending array, the checks of a caller's column or rank list, numpy's percentile, and the few
+// host functions one of these units defines for the others.  A kernel defined here is a template: the header is part of three units.
 #pragma once
 
 #include <cmath>
@@ -50,8 +51,6 @@ struct MatrixDevImpl {
 int cr_new_matrix_dev(crgpu_ctx *ctx, uint64_t V, uint64_t nnz, MatrixDevImpl **out);
 // launch only: indptr[i] = off[i] for i < n, indptr[n] = total
 void cr_offsets_to_indptr(crgpu_ctx *ctx, const uint32_t *d_off, uint64_t n, uint32_t total, long long *d_indptr);
-// launch only: flag[c] = 1 for every listed column c < V (flag == NULL: the list is only checked); *bad = 1 for a column >= V
-void cr_mark_columns(crgpu_ctx *ctx, const uint64_t *d_cols, uint64_t n, uint64_t V, uint8_t *d_flag, uint32_t *d_bad);
 // the molecule table on the host in the order ALIGN_AND_COUNT emits it: order[o] = device position of the o-th UmiCount
 int cr_molecule_order(crgpu_ctx *ctx, const crgpu_counts *c, std::vector<uint64_t> &keys, std::vector<uint32_t> &reads,
                       std::vector<uint32_t> &order);
@@ -80,21 +79,48 @@ static double cr_pairwise_sum(const double *a, size_t n) {
     n2 -= n2 % 8;
     return cr_pairwise_sum(a, n2) + cr_pairwise_sum(a + n2, n - n2);
 }
-// np.percentile(sorted x, 100 q) with the linear rule: virtual index (n - 1) q, numpy's _lerp; x is not empty
-static inline double cr_quantile_sorted(const std::vector<double> &x, double q) {
+// numpy's _lerp: a + (b - a) t, taken from b's side for t >= 0.5
+__host__ __device__ __forceinline__ double cr_lerp(double a, double b, double t) {
+    const double d = b - a;
+    return t >= 0.5 ? b - d * (1.0 - t) : a + d * t;
+}
+// np.percentile(sorted x, 100 q) with the linear rule: virtual index (n - 1) q; x is not empty, its elements are taken as f64
+template <typename T>
+static inline double cr_quantile_sorted(const std::vector<T> &x, double q) {
     const size_t n = x.size();
     const double vi = (double)(n - 1) * q, fl = std::floor(vi);
     const size_t p = (size_t)fl, nx = p + 1 < n ? p + 1 : n - 1;
-    const double a = x[p], b = x[nx], t = vi - fl, d = b - a;
-    return t >= 0.5 ? b - d * (1.0 - t) : a + d * t;
+    return cr_lerp((double)x[p], (double)x[nx], vi - fl);
 }
 // np.median of sorted x: the mean of the two middle values; x is not empty
-static inline double cr_median_sorted(const std::vector<double> &x) {
+template <typename T>
+static inline double cr_median_sorted(const std::vector<T> &x) {
     const size_t n = x.size();
-    return n % 2 ? x[n / 2] : (x[n / 2 - 1] + x[n / 2]) / 2.0;
+    return n % 2 ? (double)x[n / 2] : ((double)x[n / 2 - 1] + (double)x[n / 2]) / 2.0;
 }
 
 __device__ __forceinline__ uint64_t lowmask(uint32_t bits) { return bits >= 64 ? ~0ull : ((1ull << bits) - 1ull); }
+
+// x[0 .. n) ascending: the first index with x[i] >= v (cr_lower_bound) or x[i] > v (cr_upper_bound), else n = the number of elements
+// below v / not above v.  The index type is that of n.
+template <typename T, typename I>
+__device__ __forceinline__ I cr_lower_bound(const T *x, I n, T v) {
+    I lo = 0, hi = n;
+    while (lo < hi) {
+        const I mid = lo + ((hi - lo) >> 1);
+        if (x[mid] < v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+template <typename T, typename I>
+__device__ __forceinline__ I cr_upper_bound(const T *x, I n, T v) {
+    I lo = 0, hi = n;
+    while (lo < hi) {
+        const I mid = lo + ((hi - lo) >> 1);
+        if (x[mid] <= v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
 
 static inline int read_u32(crgpu_ctx *ctx, const uint32_t *d, uint32_t *h) {
     return crgpu_memcpy_d2h(ctx, h, d, sizeof(uint32_t));
@@ -221,6 +247,96 @@ struct CandFlag {
     const uint8_t *cand;
     __device__ __forceinline__ bool operator()(uint64_t k) const { return cand[k] != 0; }
 };
+struct SegHeadFlag {  // first molecule of a barcode
+    const uint64_t *keys;
+    uint32_t shift;
+    __device__ __forceinline__ bool operator()(uint64_t i) const {
+        const uint64_t prev = keys[i ? i - 1 : 0];
+        return (i == 0) | ((keys[i] >> shift) != (prev >> shift));
+    }
+};
+struct EmitSegStart {
+    uint32_t *start;
+    struct Pre {};
+    __device__ __forceinline__ Pre pre(uint64_t) const { return Pre(); }
+    __device__ __forceinline__ void operator()(uint64_t i, uint32_t o, Pre) const { start[o] = (uint32_t)i; }
+};
+
+// The barcode segments of the molecule table (ordered by barcode first; 1 <= n_molecules < 2^32 - 1): seg_b[s] = the first molecule
+// of the s-th barcode with a molecule, seg_b[*n_seg] = n_molecules.  One compaction and one read-back.
+static int cr_barcode_segments(crgpu_ctx *ctx, const crgpu_counts *c, const char *who, DevBuf &seg_b, uint32_t *n_seg) {
+    const uint64_t nm = c->n_molecules, n_bc = c->d_back ? c->n_back : c->n_canon;
+    const uint64_t seg_max = nm < n_bc ? nm : n_bc;
+    uint32_t *d_total = ctx->d_scalars + CR_SCALAR_TOTAL;
+    CR_TRY(dmalloc(ctx, seg_b, (seg_max + 1) * sizeof(uint32_t)));
+    {
+        CrTimer t(ctx, CRGPU_T_DEDUP, nm);
+        CR_TRY(compact(ctx, SegHeadFlag{c->d_mkeys, c->layout.sh_bc()}, EmitSegStart{seg_b.as<uint32_t>()}, nm, ctx->d_sort_hist, d_total));
+    }
+    CR_TRY(read_u32(ctx, d_total, n_seg));
+    CR_REQUIRE(ctx, *n_seg >= 1 && *n_seg <= seg_max, CRGPU_EHIP, "%s: %u barcode segments for at most %llu barcodes", who, *n_seg,
+               (unsigned long long)seg_max);
+    CR_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)(seg_b.as<uint32_t>() + *n_seg), (int)(uint32_t)nm, 1, ctx->stream));  // the end of the last segment
+    return CRGPU_OK;
+}
+
+// ---- a caller's list, checked on the device ----------------------------------------------------------------------------------
+// Column list: flag bit 0 for a column >= V, with ASCEND bit 1 for a column that is not above its predecessor; every column < V goes
+// to the mark functor with its place in the list.
+#define CR_LIST_RANGE 1u
+#define CR_LIST_ORDER 2u
+struct MarkNone {
+    __device__ __forceinline__ void operator()(uint64_t, uint64_t) const {}
+};
+struct MarkByte {  // flag[c] = 1
+    uint8_t *flag;
+    __device__ __forceinline__ void operator()(uint64_t, uint64_t c) const { flag[c] = 1u; }
+};
+struct MarkPlace {  // idx[c] = place + 1 (0: not listed)
+    uint32_t *idx;
+    __device__ __forceinline__ void operator()(uint64_t k, uint64_t c) const { idx[c] = (uint32_t)k + 1u; }
+};
+template <bool ASCEND, typename Mark>
+__global__ __launch_bounds__(256) void k_check_columns(const uint64_t *__restrict__ cols, uint64_t n, uint64_t V, Mark mark, uint32_t *__restrict__ flag) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += stride) {
+        const uint64_t c = cols[k];
+        if (ASCEND && k && cols[k - 1] >= c) atomicOr(flag, CR_LIST_ORDER);
+        if (c >= V) atomicOr(flag, CR_LIST_RANGE);
+        else mark(k, c);
+    }
+}
+// Rank list: CR_LIST_ORDER for a rank that is not above its predecessor.  A template only for the one-definition rule.
+template <typename T>
+__global__ __launch_bounds__(256) void k_check_ranks(const T *__restrict__ r, uint64_t n, uint32_t *__restrict__ flag) {
+    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i + 1 < n; i += stride)
+        if (r[i] >= r[i + 1]) atomicOr(flag, CR_LIST_ORDER);
+}
+// launch only; *d_flag was zeroed on the stream.  n == 0 launches nothing
+template <bool ASCEND, typename Mark>
+static inline void cr_check_columns(crgpu_ctx *ctx, const uint64_t *d_cols, uint64_t n, uint64_t V, Mark mark, uint32_t *d_flag) {
+    if (n) hipLaunchKernelGGL((k_check_columns<ASCEND, Mark>), dim3(cr_grid(n, 256)), dim3(256), 0, ctx->stream, d_cols, n, V, mark, d_flag);
+}
+static inline void cr_check_ranks(crgpu_ctx *ctx, const uint32_t *d_ranks, uint64_t n, uint32_t *d_flag) {
+    if (n > 1) hipLaunchKernelGGL(k_check_ranks<uint32_t>, dim3(cr_grid(n, 256)), dim3(256), 0, ctx->stream, d_ranks, n, d_flag);
+}
+// the verdict on the flag word read back: `what` names an element of the list ("cell column", "cell barcode rank")
+static inline int cr_list_verdict(crgpu_ctx *ctx, uint32_t flag, const char *who, const char *what) {
+    CR_REQUIRE(ctx, !(flag & CR_LIST_RANGE), CRGPU_EINVAL, "%s: a %s is out of range", who, what);
+    CR_REQUIRE(ctx, !(flag & CR_LIST_ORDER), CRGPU_EINVAL, "%s: the %ss must be strictly ascending", who, what);
+    return CRGPU_OK;
+}
+// a rank list checked on its own: zero the flag, launch, read back, verdict
+static int cr_require_ascending_ranks(crgpu_ctx *ctx, const uint32_t *d_ranks, uint64_t n, const char *who, const char *what) {
+    if (n < 2) return CRGPU_OK;
+    uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, flag = 0;
+    CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
+    cr_check_ranks(ctx, d_ranks, n, d_flag);
+    CR_HIP(ctx, hipGetLastError());
+    CR_TRY(read_u32(ctx, d_flag, &flag));
+    return cr_list_verdict(ctx, flag, who, what);
+}
 
 // ---- the barcode index: the canonical barcodes with a count in some library (barcode_index.rs:20-53) ----
 struct CountTables {

@@ -1,5 +1,5 @@
 // subsample.h -- read subsampling of the molecule table: the tallies behind the saturation curves (part of
-// molecule_stages.hip: works on crgpu_counts; the barcode segments and the ascending check are those of probe_counts.h).
+// molecule_stages.hip: works on crgpu_counts; the barcode segments and the ascending check are those of stage_common.h).
 //
 // Replaces run_subsampling / _run_subsample_task (lib/python/cellranger/subsample.py:430-654) for one chunk that holds the whole
 // table, compute_target_depths / make_subsamplings / _subsampling_for_depth (:140-309, crgpu_subsample_plan) and the per-task
@@ -10,7 +10,7 @@
 //
 //   1. prep     one pass over the table: libraries present, any_reads, and the molecules of many reads put on two lists (one
 //               buffer of n_molecules words, the wave list from the front, the workgroup list from the back);
-//   2. groups   barcode group starts by compaction (SegHeadFlag of probe_counts.h); per group the cell index (a search in
+//   2. groups   barcode group starts by compaction (cr_barcode_segments); per group the cell index (a search in
 //               d_cell_ranks) and the genomes it is a cell of;
 //   3. draw     per batch of at most 64 tasks: kept[task][molecule] (u32).  Thresholds of (library, task) sit in LDS; a lane
 //               counts per task in 8-bit fields of eight 64-bit registers, at most 63 Philox blocks (252 words) before they are
@@ -28,7 +28,6 @@
 #include <cmath>
 
 #include "philox.h"
-#include "probe_counts.h"
 #include "stage_common.h"
 
 #define SS_THREADS 256u
@@ -234,11 +233,7 @@ __global__ __launch_bounds__(256) void k_ss_groups(const uint64_t *__restrict__ 
     uint32_t ci = NONE32, gm = 0u;
     if (!back || b < n_back) {
         const uint32_t r = back ? back[b] : b;
-        uint64_t lo = 0, hi = n_cells;
-        while (lo < hi) {
-            const uint64_t mid = (lo + hi) >> 1;
-            if (cells[mid] < r) lo = mid + 1; else hi = mid;
-        }
+        const uint64_t lo = cr_lower_bound(cells, n_cells, r);
         if (lo < n_cells && cells[lo] == r) {
             ci = (uint32_t)lo;
             gm = cgm ? cgm[lo] : 0xFFFFFFFFu;
@@ -372,14 +367,7 @@ static int ss_run(crgpu_ctx *ctx, crgpu_counts *c, const crgpu_subsample_args *a
     if (a->total_features_det && T) memset(a->total_features_det, 0, (size_t)T * G * F * sizeof(int64_t));
     if (a->any_reads) memset(a->any_reads, 0, (size_t)NL * G);
 
-    uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, *d_total = ctx->d_scalars + CR_SCALAR_TOTAL, differ = 0;
-    if (NC > 1) {
-        CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
-        hipLaunchKernelGGL(k_pc_not_ascending, dim3(cr_grid(NC, 256)), dim3(256), 0, ctx->stream, a->d_cell_ranks, NC, d_flag);
-        CR_HIP(ctx, hipGetLastError());
-        CR_TRY(read_u32(ctx, d_flag, &differ));
-        CR_REQUIRE(ctx, !differ, CRGPU_EINVAL, "crgpu_subsample_dev: the cell barcode ranks must be strictly ascending");
-    }
+    CR_TRY(cr_require_ascending_ranks(ctx, a->d_cell_ranks, NC, "crgpu_subsample_dev", "cell barcode rank"));
     if (!nm) return CRGPU_OK;
 
     const uint32_t wave_min = std::min<uint32_t>(std::max<uint32_t>(ctx->ss_wave_min, 1u), SS_WAVE_MIN_MAX);
@@ -454,24 +442,15 @@ static int ss_run(crgpu_ctx *ctx, crgpu_counts *c, const crgpu_subsample_args *a
     if (active.empty() || !n_used) return CRGPU_OK;
 
     // 2. barcode groups
-    const uint64_t n_bc = c->d_back ? c->n_back : c->n_canon;
-    const uint64_t seg_max = nm < n_bc ? nm : n_bc;
     DevBuf seg_b, scell_b, sgm_b;
-    CR_TRY(dmalloc(ctx, seg_b, (seg_max + 1) * sizeof(uint32_t)));
-    uint32_t *seg_start = seg_b.as<uint32_t>(), n_seg = 0;
-    {
-        CrTimer t(ctx, CRGPU_T_DEDUP, nm);
-        CR_TRY(compact(ctx, SegHeadFlag{c->d_mkeys, L.sh_bc()}, EmitSegStart{seg_start}, nm, ctx->d_sort_hist, d_total));
-    }
-    CR_TRY(read_u32(ctx, d_total, &n_seg));
-    CR_REQUIRE(ctx, n_seg >= 1 && n_seg <= seg_max, CRGPU_EHIP, "crgpu_subsample_dev: %u barcode groups for at most %llu barcodes", n_seg,
-               (unsigned long long)seg_max);
+    uint32_t n_seg = 0;
+    CR_TRY(cr_barcode_segments(ctx, c, "crgpu_subsample_dev", seg_b, &n_seg));
+    const uint32_t *seg_start = seg_b.as<uint32_t>();
     if (res) res->n_groups = n_seg;
     CR_TRY(dmalloc(ctx, scell_b, (uint64_t)n_seg * sizeof(uint32_t)));
     CR_TRY(dmalloc(ctx, sgm_b, (uint64_t)n_seg * sizeof(uint32_t)));
     {
         CrTimer t(ctx, CRGPU_T_DEDUP, n_seg);
-        CR_HIP(ctx, hipMemsetD32Async((hipDeviceptr_t)(seg_start + n_seg), (int)(uint32_t)nm, 1, ctx->stream));  // the end of the last group
         hipLaunchKernelGGL(k_ss_groups, dim3((n_seg + 255u) / 256u), dim3(256), 0, ctx->stream, c->d_mkeys, L.sh_bc(), seg_start, n_seg, c->d_back,
                            c->n_back, a->d_cell_ranks, NC, cgm_b.as<uint32_t>(), scell_b.as<uint32_t>(), sgm_b.as<uint32_t>());
         CR_HIP(ctx, hipGetLastError());
@@ -693,7 +672,7 @@ static void ss_mean_median(std::vector<int64_t> &v, double *mean, double *median
     for (int64_t x : v) sum += (double)x;  // (exact below 2^53, whatever the order)
     *mean = sum / (double)n;
     std::sort(v.begin(), v.end());
-    *median = n & 1 ? (double)v[n / 2] : ((double)v[n / 2 - 1] + (double)v[n / 2]) / 2.0;
+    *median = cr_median_sorted(v);
 }
 
 extern "C" int crgpu_subsample_summary(uint32_t n_tasks, uint32_t n_genomes, uint64_t n_cells, uint32_t n_features, const uint8_t *task_type,
