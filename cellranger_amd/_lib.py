@@ -286,6 +286,27 @@ class RpuGmmResult(C.Structure):
                                           "max_lk", "fit_ms")] + [(n, C.c_uint32) for n in ("winner", "n_starts", "fitted", "in_lds")]
 
 
+class JibesSetup(C.Structure):
+    """crgpu_jibes_setup"""
+    _fields_ = [("estimated_cells", C.c_double)] + [(n, C.c_uint32) for n in ("n_states", "k_let_limited", "max_multiplets", "max_modeled_k_let")]
+
+
+class JibesFitArgs(C.Structure):
+    """crgpu_jibes_fit_args"""
+    _fields_ = [(n, C.c_void_p) for n in ("bg", "fg", "sd", "freqs")] + [
+        (n, C.c_double) for n in ("blank_prob", "estimated_cells", "abs_tol", "rel_tol", "confidence")] + [
+        (n, C.c_uint32) for n in ("n_gems", "max_k_lets", "max_reps", "flags")] + [
+        (n, C.c_void_p) for n in ("probs_out", "assignment_out", "assignment_prob_out", "ml_state_out", "posterior_out")] + [("reserved", C.c_uint64)]
+
+
+class JibesFitResult(C.Structure):
+    """crgpu_jibes_fit_result"""
+    _fields_ = [(n, C.c_double * 16) for n in ("bg", "fg", "sd")] + [("ll", C.c_double), ("fit_ms", C.c_double)] + [
+        (n, C.c_uint32) for n in ("iterations", "converged", "n_states", "k_let_limited")]
+
+
+JIBES_MAX_TAGS, JIBES_MAX_K_LETS, JIBES_MAX_STATES, JIBES_NEAR_ZERO, JIBES_CANT_CONVERGE = 16, 3, 970, 12, 1
+JIBES_EXCLUDE_BLANKS, JIBES_NO_CONFIDENCE = 1, 2
 MS_MAX_CLASSES, MS_NO_CLASS, MS_TOP_N = 32, 255, 5
 TARGETED_MIN_UMIS, GMM_STARTS = 10, 5152
 AGG_KIND_OTHER, AGG_KIND_ANTIBODY, AGG_KIND_ANTIGEN = 0, 1, 2
@@ -435,6 +456,12 @@ SYMBOLS = {
     "crgpu_feature_metrics_dev": (_i, [_vp, _vp, _u32, _u32, _vp, _u64, _vp, _vp, _vp, _vp]),
     "crgpu_targeted_rpu_stats": (_i, [_u32, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(RpuStats), _vp, _vp, _vp]),
     "crgpu_rpu_gmm_dev": (_i, [_vp, _vp, _vp, _u32, C.POINTER(RpuGmmArgs), C.POINTER(RpuGmmResult)]),
+    "crgpu_jibes_expected_cells": (_i, [_u64, _u32, C.POINTER(_dbl)]),
+    "crgpu_jibes_latent_states": (_i, [_u64, _u32, _u32, _u32, _dbl, _vp, C.POINTER(JibesSetup)]),
+    "crgpu_jibes_log_prior": (_i, [_vp, _u32, _u32, _dbl, _u32, _u32, _u32, _u32, _dbl, _vp, _vp]),
+    "crgpu_jibes_initial_parameters": (_i, [_vp, _u64, _u32, _vp, _vp, _vp, _vp]),
+    "crgpu_jibes_tag_counts_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, _u32, _vp, _vp, _vp, C.POINTER(_u64), _vp]),
+    "crgpu_jibes_fit_dev": (_i, [_vp, _vp, _u64, _u32, C.POINTER(JibesFitArgs), C.POINTER(JibesFitResult)]),
     "crgpu_aggregate_min_antibodies": (_i, [_u32, C.POINTER(_u32)]),
     "crgpu_antigen_outlier_threshold": (_i, [_vp, _u32, C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_dbl)]),
     "crgpu_aggregates_by_counts_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, _u32, _vp, _vp, _u32, C.POINTER(_u32),

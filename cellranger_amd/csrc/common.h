@@ -239,6 +239,7 @@ struct crgpu_ctx {
     // multi-genome bootstrap (multigenome.h; tests, read at create): samples per batch, 0 = by memory; largest n whose row of
     // multiplicities a sample's workgroup holds in LDS (128 KiB of the CU's 160; 0 = always device memory)
     uint32_t mg_batch = 0, mg_lds_cells = 32768;  // CRGPU_MG_BATCH, CRGPU_MG_LDS_CELLS
+    uint32_t jibes_batch = 0;  // CRGPU_JIBES_BATCH (tests, read at create): EM rounds enqueued between two reads of the stop latch (jibes.h), 0 = the default of 8
     uint32_t ed_lds_features = 0xFFFFFFFFu;  // CRGPU_ED_LDS_FEATURES (tests, read at create): largest n_eval_features the EmptyDrops simulation counts in LDS
     uint32_t ms_lds_features = 0xFFFFFFFFu;  // CRGPU_MS_LDS_FEATURES (tests, read at create): features per LDS slice of the matrix summary, 0 = counters in device memory
     uint32_t agg_lds_rows = 0xFFFFFFFFu;     // CRGPU_AGG_LDS_ROWS (tests, read at create): signal rows per LDS slice of the aggregate rank pass (unset: one slice or none), 0 = the table in device memory

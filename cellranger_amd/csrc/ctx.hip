@@ -263,6 +263,39 @@ const std::vector<AbiStruct> &abi_table() {
               ABI_F(crgpu_aggregates_info, in_lds),
               ABI_F(crgpu_aggregates_info, reserved),
               ABI_F(crgpu_aggregates_info, rank_ms)),
+        ABI_S(crgpu_jibes_setup, ABI_F(crgpu_jibes_setup, estimated_cells),
+              ABI_F(crgpu_jibes_setup, n_states),
+              ABI_F(crgpu_jibes_setup, k_let_limited),
+              ABI_F(crgpu_jibes_setup, max_multiplets),
+              ABI_F(crgpu_jibes_setup, max_modeled_k_let)),
+        ABI_S(crgpu_jibes_fit_args, ABI_F(crgpu_jibes_fit_args, bg),
+              ABI_F(crgpu_jibes_fit_args, fg),
+              ABI_F(crgpu_jibes_fit_args, sd),
+              ABI_F(crgpu_jibes_fit_args, freqs),
+              ABI_F(crgpu_jibes_fit_args, blank_prob),
+              ABI_F(crgpu_jibes_fit_args, estimated_cells),
+              ABI_F(crgpu_jibes_fit_args, abs_tol),
+              ABI_F(crgpu_jibes_fit_args, rel_tol),
+              ABI_F(crgpu_jibes_fit_args, confidence),
+              ABI_F(crgpu_jibes_fit_args, n_gems),
+              ABI_F(crgpu_jibes_fit_args, max_k_lets),
+              ABI_F(crgpu_jibes_fit_args, max_reps),
+              ABI_F(crgpu_jibes_fit_args, flags),
+              ABI_F(crgpu_jibes_fit_args, probs_out),
+              ABI_F(crgpu_jibes_fit_args, assignment_out),
+              ABI_F(crgpu_jibes_fit_args, assignment_prob_out),
+              ABI_F(crgpu_jibes_fit_args, ml_state_out),
+              ABI_F(crgpu_jibes_fit_args, posterior_out),
+              ABI_F(crgpu_jibes_fit_args, reserved)),
+        ABI_S(crgpu_jibes_fit_result, ABI_F(crgpu_jibes_fit_result, bg),
+              ABI_F(crgpu_jibes_fit_result, fg),
+              ABI_F(crgpu_jibes_fit_result, sd),
+              ABI_F(crgpu_jibes_fit_result, ll),
+              ABI_F(crgpu_jibes_fit_result, fit_ms),
+              ABI_F(crgpu_jibes_fit_result, iterations),
+              ABI_F(crgpu_jibes_fit_result, converged),
+              ABI_F(crgpu_jibes_fit_result, n_states),
+              ABI_F(crgpu_jibes_fit_result, k_let_limited)),
     };
     return t;
 }
@@ -337,6 +370,7 @@ extern "C" int crgpu_create(crgpu_ctx **out, int device_id, int n_ranks, int ran
     }
     if (const char *cap = getenv("CRGPU_PROBE_SEG_CAP")) ctx->probe_seg_cap = (uint32_t)strtoul(cap, nullptr, 10);  // tests: force the global route
     if (const char *b = getenv("CRGPU_MG_BATCH")) ctx->mg_batch = (uint32_t)strtoul(b, nullptr, 10);  // tests: small batches of the multi-genome bootstrap
+    if (const char *b = getenv("CRGPU_JIBES_BATCH")) ctx->jibes_batch = (uint32_t)strtoul(b, nullptr, 10);  // tests: EM rounds between two reads of the stop latch
     if (const char *b = getenv("CRGPU_MG_LDS_CELLS")) {  // tests: the LDS / device-memory seam
         const unsigned long v = strtoul(b, nullptr, 10);
         ctx->mg_lds_cells = v < 32768ul ? (uint32_t)v : 32768u;

@@ -4,6 +4,7 @@
 #include "aggregates.h"
 #include "cell_calling.h"
 #include "emptydrops.h"
+#include "jibes.h"
 #include "matrix_summary.h"
 #include "multigenome.h"
 #include "rtl_tags.h"

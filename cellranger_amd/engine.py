@@ -843,6 +843,109 @@ def targeted_metrics(ctx, tallies, is_targeted, summary, num_cells, total_reads,
     return s, col
 
 
+# ---- cell-multiplexed (CMO) wells: the JIBES tag caller ---------------------------------------------------------------------------
+N_G = 95000      # feature/throughputs.py
+G19_N_GEMS = {"MT": N_G, "LT": 9500, "HT": 190000}
+JIBES_MIN_CONFIDENCE = 0.9
+JIBES_MULTIPLET, JIBES_BLANK, JIBES_UNASSIGNED = "Multiplet", "Blank", "Unassigned"
+
+
+class CellEstimateCantConverge(RuntimeError):
+    """the reference's CellEstimateCantConvergeException"""
+
+
+def jibes_expected_cells(n, n_gems=N_G):
+    """feature_assigner.calculate_expected_total_cells as a bracketed root (crgpu_jibes_expected_cells, host only)"""
+    out = C.c_double()
+    rc = _lib.load().crgpu_jibes_expected_cells(int(n), int(n_gems), C.byref(out))
+    if rc == _lib.JIBES_CANT_CONVERGE:
+        raise CellEstimateCantConverge("Could not converge on an accurate cell estimate.")
+    if rc != 0:
+        raise _lib.CrgpuError(rc, "crgpu_jibes_expected_cells")
+    return out.value
+
+
+def jibes_latent_states(n, k, n_gems=N_G, max_k_lets=3, estimated_cells=None, blank_prob=0.04, freqs=None):
+    """JibesEMO3::new and calculate_latent_state_weights (host only) -> dict(states u8[z, k], prior f64[z], k_let_limited,
+    max_multiplets, max_modeled_k_let, estimated_cells).  estimated_cells None: jibes_expected_cells(n, n_gems)."""
+    L = _lib.load()
+    est = jibes_expected_cells(n, n_gems) if estimated_cells is None else float(estimated_cells)
+    su = _lib.JibesSetup()
+    states = np.zeros((_lib.JIBES_MAX_STATES, max(int(k), 1)), np.uint8)
+    rc = L.crgpu_jibes_latent_states(int(n), int(k), int(n_gems), int(max_k_lets), est, ptr(states), C.byref(su))
+    if rc != 0:
+        raise _lib.CrgpuError(rc, "crgpu_jibes_latent_states: k = %d, max_k_lets = %d" % (k, max_k_lets))
+    states = np.ascontiguousarray(states.reshape(-1)[:su.n_states * k].reshape(su.n_states, k))
+    fr = None if freqs is None else np.ascontiguousarray(freqs, dtype=np.float64)
+    prior = np.zeros(su.n_states, np.float64)
+    rc = L.crgpu_jibes_log_prior(ptr(states), su.n_states, int(k), est, int(n_gems), int(max_k_lets), su.k_let_limited, su.max_modeled_k_let,
+                                 float(blank_prob), ptr(fr), ptr(prior))
+    if rc != 0:
+        raise _lib.CrgpuError(rc, "crgpu_jibes_log_prior")
+    return dict(states=states, prior=prior, k_let_limited=bool(su.k_let_limited), max_multiplets=int(su.max_multiplets),
+                max_modeled_k_let=int(su.max_modeled_k_let), estimated_cells=est)
+
+
+def jibes_initial_parameters(y, calls):
+    """jibes.create_initial_parameters (host only): y f64[n, k], calls per barcode a tag index or -1 -> (bg, fg, sd)"""
+    y = np.ascontiguousarray(y, dtype=np.float64)
+    if y.ndim != 2:
+        raise ValueError("jibes_initial_parameters: y is n x k")
+    calls = np.ascontiguousarray(calls, dtype=np.int32)
+    if len(calls) != len(y):
+        raise ValueError("jibes_initial_parameters: one call per barcode")
+    k = y.shape[1]
+    bg, fg, sd = np.zeros(k), np.zeros(k), np.zeros(k)
+    rc = _lib.load().crgpu_jibes_initial_parameters(ptr(y) if len(y) else None, len(y), k, ptr(calls) if len(y) else None, ptr(bg), ptr(fg), ptr(sd))
+    if rc != 0:
+        raise _lib.CrgpuError(rc, "crgpu_jibes_initial_parameters")
+    return bg, fg, sd
+
+
+def call_tags_jibes(ctx, filtered, tag_rows, valid_tags, prelim_calls, throughput="MT", confidence=None, exclude_blanks_from_posterior=False,
+                    tag_names=None, n_gems=None, n_features=None, estimated_cells=None, abs_tol=0.1, rel_tol=1e-7, max_reps=50000):
+    """run_assignment_stage + JibesTagAssigner.get_tag_assignments on the filtered MatrixDev: tag_rows = the feature rows of the
+    Multiplexing Capture library (ascending), valid_tags = a mask over them (the tags the marginal caller saw), prelim_calls = per
+    barcode of the matrix an index into the VALID tags or -1 (the marginal caller's call when it is one tag).  Near-zero barcodes
+    (<= 12 counts over ALL tag rows) are Blank with probability 1 and never enter the fit.
+    -> dict(table = the per-barcode columns of the fit (see Context.jibes_fit) for the kept barcodes, kept, near_zero,
+    barcodes_per_tag (per valid tag the matrix columns assigned to it; a Multiplet goes to every tag of its most likely multiplet
+    state), non_singlets {Blank, Unassigned, Multiplet} with the near-zero barcodes appended to Blank, snr {snr_<tag>: fg / sd},
+    fit)."""
+    confidence = JIBES_MIN_CONFIDENCE if confidence is None else confidence
+    n_gems = G19_N_GEMS.get(throughput, N_G) if n_gems is None else n_gems
+    valid = np.asarray(valid_tags, bool)
+    if len(valid) != len(tag_rows) or not valid.any():
+        raise ValueError("call_tags_jibes: valid_tags is a mask over tag_rows with at least one tag set")
+    names = ["tag%d" % i for i in range(len(valid))] if tag_names is None else [n.decode() if isinstance(n, bytes) else n for n in tag_names]
+    names = [n for n, v in zip(names, valid) if v]
+    tab = ctx.jibes_tag_counts(filtered, tag_rows, n_features)
+    kept, near_zero = tab["kept"], tab["near_zero"]
+    y = np.ascontiguousarray(tab["log_counts"][kept][:, valid])
+    calls = np.asarray(prelim_calls, np.int32)[kept]
+    bg, fg, sd = jibes_initial_parameters(y, calls)
+    fit = ctx.jibes_fit(y, bg, fg, sd, n_gems=n_gems, estimated_cells=estimated_cells, abs_tol=abs_tol, rel_tol=rel_tol, max_reps=max_reps,
+                        confidence=confidence, exclude_blanks_from_posterior=exclude_blanks_from_posterior)
+    k = y.shape[1]
+    states = fit["states"]
+    per_tag = [[] for _ in range(k)]
+    non = {JIBES_BLANK: [], JIBES_UNASSIGNED: [], JIBES_MULTIPLET: []}
+    for i, a in enumerate(fit["assignment"].tolist()):
+        bc = int(kept[i])
+        if a < k:
+            per_tag[a].append(bc)
+        elif a == k:
+            non[JIBES_MULTIPLET].append(bc)
+            for t in np.nonzero(states[fit["ml_state"][i]])[0]:
+                per_tag[int(t)].append(bc)
+        else:
+            non[JIBES_BLANK if a == k + 1 else JIBES_UNASSIGNED].append(bc)
+    non[JIBES_BLANK] += [int(b) for b in near_zero]
+    snr = {"snr_" + n: float(fit["fg"][t] / fit["sd"][t]) for t, n in enumerate(names)}
+    return dict(table={q: fit[q] for q in ("probs", "assignment", "assignment_prob", "ml_state")}, kept=kept, near_zero=near_zero,
+                barcodes_per_tag=dict(zip(names, per_tag)), non_singlets=non, snr=snr, fit=fit, tag_names=names)
+
+
 def ordmag_candidates(max_expected_cells=1 << 18):
     """the recovered-cells grid of estimate_recovered_cells_ordmag (cell_calling_helpers.py:879-880); host only"""
     out, n = np.zeros(2000, np.int64), C.c_uint32()
@@ -1858,6 +1961,81 @@ class Context:
         if want_starts:
             out["start_lk"], out["start_iters"] = lk, it
         return out
+
+    # ---- cell-multiplexed (CMO) wells ------------------------------------------------------------------
+    def jibes_tag_counts(self, m, tag_rows, n_features=None):
+        """the tag table of the filtered MatrixDev `m` (JibesTagAssigner.__init__): tag_rows = the feature rows of the Multiplexing
+        Capture library, ascending -> dict(counts i32[V, n_rows], row_sums u64[V], near_zero / kept = the columns whose sum over ALL
+        tag rows is <= 12 / above, log_counts f64[V, n_rows] = np.log10(counts + 1.0), taken by numpy as the reference takes it)"""
+        rows = np.ascontiguousarray(tag_rows, dtype=np.uint32)
+        if n_features is None:
+            n_features = getattr(self, "n_features", None)
+            if n_features is None:
+                raise ValueError("jibes_tag_counts: pass n_features")
+        V = m.n_barcodes
+        counts, sums = np.zeros((V, len(rows)), np.int32), np.zeros(V, np.uint64)
+        nz, kept, n_nz = np.zeros(V, np.uint64), np.zeros(V, np.uint64), C.c_uint64()
+        self._check(self.L.crgpu_jibes_tag_counts_dev(self.h, m._mv, ptr(rows), len(rows), int(n_features), ptr(counts), ptr(sums), ptr(nz), C.byref(n_nz),
+                                                      ptr(kept)))
+        return dict(counts=counts, row_sums=sums, near_zero=nz[:n_nz.value].copy(), kept=kept[:V - n_nz.value].copy(),
+                    log_counts=np.log10(counts + 1.0))
+
+    def jibes_fit(self, y, bg, fg, sd, n_gems=N_G, estimated_cells=None, blank_prob=0.04, freqs=None, max_k_lets=3, max_reps=50000, abs_tol=1e-2,
+                  rel_tol=1e-7, confidence=JIBES_MIN_CONFIDENCE, exclude_blanks_from_posterior=False, apply_confidence=True, want_posterior=False):
+        """perform_EM of jibes_o3 and get_assignment_df on the device: y f64[n, k] = log10(count + 1), (bg, fg, sd) the initial model.
+        -> dict(bg, fg, sd, LL, iterations, converged, n_states, k_let_limited, fit_ms, states u8[z, k], prior, estimated_cells,
+        probs f64[n, k + 2] (tags, Multiplet, Blank), assignment i32[n] (a tag, k = Multiplet, k + 1 = Blank, k + 2 = Unassigned),
+        assignment_prob, ml_state (index of the most likely Multiplet state); want_posterior adds posterior f64[n, z] (tests)."""
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        if y.ndim != 2:
+            raise ValueError("jibes_fit: y is n x k")
+        n, k = y.shape
+        m0 = [np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in (bg, fg, sd)]
+        if any(len(a) != k for a in m0):
+            raise ValueError("jibes_fit: the initial model has one value per tag")
+        fr = None if freqs is None else np.ascontiguousarray(freqs, dtype=np.float64)
+        if estimated_cells is None:
+            estimated_cells = jibes_expected_cells(n, n_gems)
+        a = _lib.JibesFitArgs(bg=ptr(m0[0]), fg=ptr(m0[1]), sd=ptr(m0[2]), freqs=ptr(fr), blank_prob=blank_prob, estimated_cells=estimated_cells,
+                              abs_tol=abs_tol, rel_tol=rel_tol, confidence=confidence, n_gems=n_gems, max_k_lets=max_k_lets, max_reps=max_reps,
+                              flags=(_lib.JIBES_EXCLUDE_BLANKS if exclude_blanks_from_posterior else 0) | (0 if apply_confidence else _lib.JIBES_NO_CONFIDENCE),
+                              reserved=0)
+        res = _lib.JibesFitResult()
+        post = None
+        lat = jibes_latent_states(n, k, n_gems, max_k_lets, estimated_cells, blank_prob, fr)      # refuses k > 16 and max_k_lets > 3 as the fit would
+        z = len(lat["states"])
+        probs, asst, aprob, ml = np.zeros((n, k + 2)), np.zeros(n, np.int32), np.zeros(n), np.zeros(n, np.uint32)
+        if want_posterior:
+            post = np.zeros((n, z))
+        if n:
+            a.probs_out, a.assignment_out, a.assignment_prob_out, a.ml_state_out, a.posterior_out = ptr(probs), ptr(asst), ptr(aprob), ptr(ml), ptr(post)
+        self._check(self.L.crgpu_jibes_fit_dev(self.h, ptr(y) if n else None, n, k, C.byref(a), C.byref(res)))
+        out = dict(bg=np.array(res.bg[:k]), fg=np.array(res.fg[:k]), sd=np.array(res.sd[:k]), LL=res.ll, iterations=int(res.iterations),
+                   converged=bool(res.converged), n_states=int(res.n_states), k_let_limited=bool(res.k_let_limited), fit_ms=res.fit_ms,
+                   states=lat["states"], prior=lat["prior"], estimated_cells=estimated_cells, probs=probs, assignment=asst, assignment_prob=aprob,
+                   ml_state=ml)
+        if want_posterior:
+            out["posterior"] = post
+        return out
+
+    def multigenome_jibes(self, counts0, counts1, n_gems=N_G):
+        """JIBESMultiGenome._infer_multiplets (analysis/jibes.py:396-442): the two count vectors as log10(count + 1), the initial
+        calls from the device classify_gems, the fit with its defaults and no confidence rule
+        -> (observed multiplets, infer_multiplets_from_observed, calls u8 per barcode as _lib.MG_*)"""
+        c0, c1 = (np.ascontiguousarray(x.to_host(x.size) if isinstance(x, DeviceArray) else x, dtype=np.uint32) for x in (counts0, counts1))
+        if len(c0) != len(c1):
+            raise ValueError("multigenome_jibes: counts0 and counts1 differ in length")
+        first = self.multigenome(c0, c1, bootstraps=1).call
+        if len(set(first.tolist())) <= 1:
+            return 0, 0.0, first
+        y = np.stack((np.log10(c0 + 1.0), np.log10(c1 + 1.0)), axis=1)
+        calls = np.where(first == _lib.MG_GENOME0, 0, np.where(first == _lib.MG_GENOME1, 1, -1)).astype(np.int32)
+        bg, fg, sd = jibes_initial_parameters(y, calls)
+        fit = self.jibes_fit(y, bg, fg, sd, n_gems=n_gems, apply_confidence=False)
+        a = fit["assignment"]
+        m, g0, g1 = int((a == 2).sum()), int((a == 0).sum()), int((a == 1).sum())
+        call = np.where(a == 0, _lib.MG_GENOME0, np.where(a == 1, _lib.MG_GENOME1, np.where(a == 2, _lib.MG_MULTIPLET, 255))).astype(np.uint8)
+        return m, float(multigenome_summary(np.array([[m, g0, g1]], np.int64), len(c0))[0][0]), call
 
     def call_additional_cells(self, m, call, low, high, emptydrops_minimum_umis=500, num_sims=10000, max_adj_pvalue=0.01, seed=0,
                               feature_mask=None, sim_table=None, keep_sim_table=False, keep_profile=True):

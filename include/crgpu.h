@@ -1498,6 +1498,111 @@ int crgpu_extract_features_dev(crgpu_ctx *ctx, int extractor, const uint8_t *d_r
 int crgpu_feature_counts_dev(crgpu_ctx *ctx, const uint32_t *d_feature, uint64_t n, uint32_t n_features, int64_t *counts_inout);
 int crgpu_compute_feature_dist(const int64_t *counts, const uint32_t *feature_type, uint32_t n_features, double *dist_out);
 
+/* ---- cell-multiplexed (CMO) wells: the JIBES tag caller ---------------------------------------------------------------------
+ * Replaces CALL_TAGS_JIBES (mro/rna/stages/feature/call_tags_jibes): cellranger.feature.jibes_tag_assigner over the EM fit of
+ * lib/rust/jibes_o3/src/lib.rs (where that and lib/python/cellranger/analysis/jibes_py.py differ, the Rust is followed).
+ * Host functions, no context:
+ *   crgpu_jibes_expected_cells     feature_assigner.calculate_expected_total_cells as a bracketed root: the x on the rising branch with
+ *                                  sum(get_multiplet_counts_unrounded(x, n_gems)) = n, by bisection (the reference minimises the squared
+ *                                  difference with scipy's BFGS and keeps where that stops; DESIGN.md has the measured difference).
+ *                                  Returns the POSITIVE status CRGPU_JIBES_CANT_CONVERGE where the reference raises
+ *                                  CellEstimateCantConvergeException (the squared difference cannot be brought to 2 or below).
+ *   crgpu_jibes_latent_states      JibesEMO3::new: the latent states of (n barcodes, k tags, n_gems, max_k_lets, estimated_cells) in the
+ *                                  order of combinatorics.generate_all_multiplets -- the blank state, the compositions of 1 ..
+ *                                  max_multiplets in generate_solutions order, [1] * k appended when limited --, states_out (nullable):
+ *                                  u8[n_states x k], room for CRGPU_JIBES_MAX_STATES x k.  max_multiplets = max(last index with
+ *                                  round(expected count) > 0, + 1, 2) capped at max_k_lets (the cap sets k_let_limited).
+ *                                  CRGPU_ERANGE: k > CRGPU_JIBES_MAX_TAGS, max_k_lets > CRGPU_JIBES_MAX_K_LETS; CRGPU_EINVAL: k or max_k_lets 0.
+ *   crgpu_jibes_log_prior          calculate_latent_state_weights: the Poisson k-let counts (pmf 1 .. 14, CORR_FACTOR 1.54) normalised over
+ *                                  the first max_modeled_k_let, the last entry the sum from index max_k_lets on when limited, then per
+ *                                  state sum(cnt ln freq) + the log multinomial coefficient + ln p(k-let) + ln(1 - blank); ln(blank) for
+ *                                  state 0.  freqs NULL: uniform.
+ *     QUIRK kept: with k <= max_k_lets and a limited model the overwritten last entry is an empty sum; its states get -inf.
+ *   crgpu_jibes_initial_parameters jibes.create_initial_parameters: y f64[n x k], calls i32[n] (a tag index, anything else = no single
+ *                                  tag): the background from the other singlets, max(0.6 + bg, mean) - bg, the fill-in for tags with
+ *                                  fewer than 2 calls (1.0 / 0.5 / 0.3 when all are), 0.2 for a zero sd; means in numpy's pairwise order.
+ * Device:
+ *   crgpu_jibes_tag_counts_dev     m: the filtered matrix; tag_rows: host u32[n_rows], the feature rows of the Multiplexing Capture
+ *                                  library, strictly ascending and below n_features (else CRGPU_EINVAL).  counts_out i32[V x n_rows]
+ *                                  (dense, barcode-major), row_sums_out u64[V], near_zero_out u64[<= V]: the columns whose sum over ALL
+ *                                  tag rows is <= CRGPU_JIBES_NEAR_ZERO (ascending), kept_out u64[<= V]: the others.  Every output is a
+ *                                  host array and may be NULL.  log10(count + 1) is left to the caller, so that a binding takes the
+ *                                  logarithm its reference takes (numpy's for the Python layer).
+ *   crgpu_jibes_fit_dev            perform_EM + get_assignment_df on y: host f64[n x k] (log10(count + 1) of the barcodes that are not
+ *                                  near zero, the valid tags only).  E step: prior + the tags' ln_pdf in TAG order, row maximum, exp,
+ *                                  normalise; LL = sum ln(marginal) + sum max.  M step: the closed-form 2 x 2 weighted least squares per
+ *                                  tag, slope clamped at 0.01 (the intercept is then re-estimated), residual variance over elem_11 under
+ *                                  the OLD posterior and the NEW coefficients, sd floor 1e-4.  Stop: rep > max_reps, else (not against
+ *                                  the initial -inf) abs_change < abs_tol or rel_change < rel_tol, strict.  n == 0: LL 0, converged,
+ *                                  foregrounds 0, no launch.  An initial foreground below 0.01 or a non-positive sd: CRGPU_EINVAL; k >
+ *                                  CRGPU_JIBES_MAX_TAGS or max_k_lets > CRGPU_JIBES_MAX_K_LETS: CRGPU_ERANGE.
+ *       on the device              a barcode's row of states is spread over the lanes of a wave and never stored; the states are 2 bits
+ *                                  per tag in LDS beside the prior; per barcode the k x 4 distinct log densities are computed once.  An
+ *                                  iteration is four ordinary launches (pass, close, residual pass, close); every cross-barcode sum is
+ *                                  reduced in one order that depends on (n, z, k) alone -- a lane over its (barcode, state) pairs, the
+ *                                  xor butterfly, the waves ascending, the 64-barcode chunks ascending from a slab of plain stores --,
+ *                                  so the results are bit-identical between runs.  The closing kernel evaluates the stop rule and
+ *                                  latches the stopping iteration; later launches return at once; the host enqueues
+ *                                  CRGPU_JIBES_BATCH=<n> iterations (environment, at creation; default 8) between two reads of the
+ *                                  latch.  No result depends on it.
+ *       outputs (host, nullable)   probs_out f64[n x (k + 2)]: per tag the states that hold only that tag, then Multiplet, then Blank;
+ *                                  assignment_out i32[n]: the first maximum in that order (k = Multiplet, k + 1 = Blank), k + 2 =
+ *                                  Unassigned where its probability -- divided by 1 - Blank for a candidate that is not Blank under
+ *                                  CRGPU_JIBES_EXCLUDE_BLANKS -- is below `confidence` (CRGPU_JIBES_NO_CONFIDENCE: no such rule, as
+ *                                  JIBESMultiGenome); assignment_prob_out f64[n]: the maximum itself; ml_state_out u32[n]: the first
+ *                                  maximum over the Multiplet states, as a state index; posterior_out f64[n x n_states] (tests).
+ * NOT covered: optimize_pop_freqs (the Rust asserts it off), the CSV / JSON / pickle writers, get_valid_tags, CALL_TAGS_MARGINAL (its
+ * calls are an input), get_frac_contaminant_tags and the fat-tail metric. */
+#define CRGPU_JIBES_MAX_TAGS 16
+#define CRGPU_JIBES_MAX_K_LETS 3
+#define CRGPU_JIBES_MAX_STATES 970 /* 1 + 16 + 136 + 816 + the unit vector */
+#define CRGPU_JIBES_NEAR_ZERO 12
+#define CRGPU_JIBES_CANT_CONVERGE 1
+#define CRGPU_JIBES_EXCLUDE_BLANKS 1u
+#define CRGPU_JIBES_NO_CONFIDENCE 2u
+struct crgpu_jibes_setup {
+    double estimated_cells;
+    uint32_t n_states, k_let_limited, max_multiplets, max_modeled_k_let;
+};
+typedef struct crgpu_jibes_setup crgpu_jibes_setup;
+struct crgpu_jibes_fit_args {
+    const double *bg;            /* the initial model: host f64[k] each */
+    const double *fg;
+    const double *sd;
+    const double *freqs;         /* host f64[k] or NULL: uniform */
+    double blank_prob;           /* 0.04 in the reference */
+    double estimated_cells;      /* crgpu_jibes_expected_cells(n, n_gems), or the reference's own value */
+    double abs_tol, rel_tol;     /* 1e-2 / 1e-7 by default; the stage passes abs_tol = 0.1 */
+    double confidence;           /* 0.9 */
+    uint32_t n_gems, max_k_lets; /* max_k_lets: 3 */
+    uint32_t max_reps, flags;    /* 50000; CRGPU_JIBES_* */
+    double *probs_out;
+    int32_t *assignment_out;
+    double *assignment_prob_out;
+    uint32_t *ml_state_out;
+    double *posterior_out;
+    uint64_t reserved;           /* 0 */
+};
+typedef struct crgpu_jibes_fit_args crgpu_jibes_fit_args;
+struct crgpu_jibes_fit_result {
+    double bg[16], fg[16], sd[16]; /* the final model */
+    double ll, fit_ms;             /* fit_ms: host time from the first launch until the latch was read as set */
+    uint32_t iterations, converged, n_states, k_let_limited;
+};
+typedef struct crgpu_jibes_fit_result crgpu_jibes_fit_result;
+int crgpu_jibes_expected_cells(uint64_t n, uint32_t n_gems, double *out);
+int crgpu_jibes_latent_states(uint64_t n, uint32_t k, uint32_t n_gems, uint32_t max_k_lets, double estimated_cells, uint8_t *states_out,
+                              crgpu_jibes_setup *out);
+int crgpu_jibes_log_prior(const uint8_t *states, uint32_t n_states, uint32_t k, double estimated_cells, uint32_t n_gems, uint32_t max_k_lets,
+                          uint32_t k_let_limited, uint32_t max_modeled_k_let, double blank_prob, const double *freqs, double *prior_out);
+int crgpu_jibes_initial_parameters(const double *y, uint64_t n, uint32_t k, const int32_t *calls, double *bg_out, double *fg_out,
+                                   double *sd_out);
+int crgpu_jibes_tag_counts_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const uint32_t *tag_rows, uint32_t n_rows, uint32_t n_features,
+                               int32_t *counts_out, uint64_t *row_sums_out, uint64_t *near_zero_out, uint64_t *n_near_zero_out,
+                               uint64_t *kept_out);
+int crgpu_jibes_fit_dev(crgpu_ctx *ctx, const double *y, uint64_t n, uint32_t k, const crgpu_jibes_fit_args *args,
+                        crgpu_jibes_fit_result *result);
+
 /* ---- synthetic workloads (bench / tests) ---------------------------------------------
  * Counter-based integer generator: read i of a given seed is identical on the host and on the
  * device.  Tables are host arrays built by cellranger_amd.synth. */

@@ -1171,6 +1171,58 @@ inline RpuGmm rpu_gmm(Context &ctx, const std::vector<double> &values, const std
     return out;
 }
 
+// ---- a cell-multiplexed (CMO) well: the JIBES tag caller (CALL_TAGS_JIBES) ---------------------------------------------------------------
+static_assert(sizeof(crgpu_jibes_setup) == 24, "crgpu_jibes_setup changed: bump CRGPU_ABI_VERSION and every binding");
+static_assert(sizeof(crgpu_jibes_fit_args) == 136, "crgpu_jibes_fit_args changed: bump CRGPU_ABI_VERSION and every binding");
+static_assert(sizeof(crgpu_jibes_fit_result) == 416, "crgpu_jibes_fit_result changed: bump CRGPU_ABI_VERSION and every binding");
+/// crgpu_jibes_expected_cells: throws Error(CRGPU_JIBES_CANT_CONVERGE, ...) where the reference raises CellEstimateCantConvergeException
+inline double jibes_expected_cells(uint64_t n, uint32_t n_gems) {
+    double out = 0.0;
+    const int rc = crgpu_jibes_expected_cells(n, n_gems, &out);
+    if (rc != CRGPU_OK) throw Error(rc, rc == CRGPU_JIBES_CANT_CONVERGE ? "Could not converge on an accurate cell estimate." : "jibes_expected_cells");
+    return out;
+}
+struct JibesLatentStates {
+    crgpu_jibes_setup setup;
+    std::vector<uint8_t> states;  // [n_states x k]
+    std::vector<double> prior;    // [n_states]
+};
+/// crgpu_jibes_latent_states + crgpu_jibes_log_prior with the uniform tag frequencies
+inline JibesLatentStates jibes_latent_states(uint64_t n, uint32_t k, uint32_t n_gems, double estimated_cells, uint32_t max_k_lets = 3, double blank_prob = 0.04) {
+    JibesLatentStates out;
+    out.states.assign((size_t)CRGPU_JIBES_MAX_STATES * (k ? k : 1), 0);
+    int rc = crgpu_jibes_latent_states(n, k, n_gems, max_k_lets, estimated_cells, out.states.data(), &out.setup);
+    if (rc != CRGPU_OK) throw Error(rc, "jibes_latent_states: 1 .. 16 tags, max_k_lets 1 .. 3");
+    out.states.resize((size_t)out.setup.n_states * k);
+    out.prior.assign(out.setup.n_states, 0.0);
+    rc = crgpu_jibes_log_prior(out.states.data(), out.setup.n_states, k, estimated_cells, n_gems, max_k_lets, out.setup.k_let_limited,
+                               out.setup.max_modeled_k_let, blank_prob, nullptr, out.prior.data());
+    if (rc != CRGPU_OK) throw Error(rc, "jibes_latent_states: the prior");
+    return out;
+}
+struct JibesFit {
+    crgpu_jibes_fit_result result;
+    std::vector<double> probs;             // [n x (k + 2)]: the tags, Multiplet, Blank
+    std::vector<int32_t> assignment;       // a tag, k = Multiplet, k + 1 = Blank, k + 2 = Unassigned
+    std::vector<double> assignment_prob;
+    std::vector<uint32_t> ml_state;        // the most likely Multiplet state, as a state index
+};
+/// crgpu_jibes_fit_dev: y [n x k] = log10(count + 1); (bg, fg, sd) the initial model; the reference's defaults otherwise
+inline JibesFit jibes_fit(Context &ctx, const std::vector<double> &y, uint32_t k, const std::vector<double> &bg, const std::vector<double> &fg,
+                          const std::vector<double> &sd, uint32_t n_gems, double estimated_cells, double abs_tol = 1e-2, double rel_tol = 1e-7,
+                          uint32_t max_reps = 50000, double confidence = 0.9, uint32_t flags = 0) {
+    if (!k || y.size() % k || bg.size() != k || fg.size() != k || sd.size() != k) throw Error(CRGPU_EINVAL, "jibes_fit: shapes");
+    const size_t n = y.size() / k;
+    JibesFit out;
+    out.probs.assign(n * (k + 2), 0.0), out.assignment.assign(n, 0), out.assignment_prob.assign(n, 0.0), out.ml_state.assign(n, 0);
+    crgpu_jibes_fit_args a{};
+    a.bg = bg.data(), a.fg = fg.data(), a.sd = sd.data(), a.blank_prob = 0.04, a.estimated_cells = estimated_cells;
+    a.abs_tol = abs_tol, a.rel_tol = rel_tol, a.confidence = confidence, a.n_gems = n_gems, a.max_k_lets = 3, a.max_reps = max_reps, a.flags = flags;
+    if (n) a.probs_out = out.probs.data(), a.assignment_out = out.assignment.data(), a.assignment_prob_out = out.assignment_prob.data(), a.ml_state_out = out.ml_state.data();
+    ctx.check(crgpu_jibes_fit_dev(ctx.get(), n ? y.data() : nullptr, n, k, &a, &out.result));
+    return out;
+}
+
 // ---- protein aggregates of an antibody / antigen well; the closing filters of a cell call ---------------------------------------------
 static_assert(sizeof(crgpu_aggregates_info) == 48, "crgpu_aggregates_info changed: bump CRGPU_ABI_VERSION and every binding");
 /// int(np.round(n_signal * _calculate_fraction_to_use(n_signal)))
