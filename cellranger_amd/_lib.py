@@ -305,6 +305,24 @@ class JibesFitResult(C.Structure):
         (n, C.c_uint32) for n in ("iterations", "converged", "n_states", "k_let_limited")]
 
 
+class MarginalRow(C.Structure):
+    """crgpu_marginal_row"""
+    _fields_ = [("status", C.c_uint32), ("in_lds", C.c_uint32), ("total_umis", C.c_uint64), ("cells_assigned", C.c_uint64),
+                ("umi_threshold_observed", C.c_int64)] + [
+        (n, C.c_double) for n in ("mean_low", "mean_high", "weight_low", "weight_high", "covariance", "lower_bound")] + [
+        (n, C.c_uint32) for n in ("winner", "n_iter", "n_distinct", "reserved")]
+
+
+class MarginalCalls(C.Structure):
+    """crgpu_marginal_calls"""
+    _fields_ = [("rows", C.POINTER(MarginalRow)), ("n_rows", C.c_uint32), ("reserved", C.c_uint32), ("n_barcodes", C.c_uint64),
+                ("n_assigned", C.c_uint64)] + [
+        (n, C.c_void_p) for n in ("d_indptr", "d_columns", "d_features_per_cell", "d_hist_offsets", "d_hist_values", "d_hist_counts")] + [
+        (n, C.c_uint64) for n in ("n_hist_slots", "cells_with_0", "cells_with_1", "cells_with_many", "cells_without_umis")] + [
+        (n, C.c_double) for n in ("ms_extract", "ms_histogram", "ms_fit", "ms_assign")]
+
+
+MC_INITS, MC_SKIPPED, MC_FITTED = 10, 0, 1
 JIBES_MAX_TAGS, JIBES_MAX_K_LETS, JIBES_MAX_STATES, JIBES_NEAR_ZERO, JIBES_CANT_CONVERGE = 16, 3, 970, 12, 1
 JIBES_EXCLUDE_BLANKS, JIBES_NO_CONFIDENCE = 1, 2
 MS_MAX_CLASSES, MS_NO_CLASS, MS_TOP_N = 32, 255, 5
@@ -462,6 +480,11 @@ SYMBOLS = {
     "crgpu_jibes_initial_parameters": (_i, [_vp, _u64, _u32, _vp, _vp, _vp, _vp]),
     "crgpu_jibes_tag_counts_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, _u32, _vp, _vp, _vp, C.POINTER(_u64), _vp]),
     "crgpu_jibes_fit_dev": (_i, [_vp, _vp, _u64, _u32, C.POINTER(JibesFitArgs), C.POINTER(JibesFitResult)]),
+    "crgpu_marginal_calls_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, _u32, _u32, _u32, C.POINTER(C.POINTER(MarginalCalls))]),
+    "crgpu_marginal_calls_free": (None, [_vp, C.POINTER(MarginalCalls)]),
+    "crgpu_tag_moments_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, _u32, _vp, _vp, _vp]),
+    "crgpu_tag_contaminants": (_i, [_u32, _u64, _vp, _vp, _vp, _vp, _u64, _dbl, _dbl, _vp, _vp]),
+    "crgpu_marginal_seed_draws": (_i, [_u64, _vp, _vp]),
     "crgpu_aggregate_min_antibodies": (_i, [_u32, C.POINTER(_u32)]),
     "crgpu_antigen_outlier_threshold": (_i, [_vp, _u32, C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_dbl)]),
     "crgpu_aggregates_by_counts_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, _u32, _vp, _vp, _u32, C.POINTER(_u32),

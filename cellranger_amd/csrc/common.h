@@ -248,6 +248,9 @@ struct crgpu_ctx {
     // device memory.  8192 values are 64 KB, two workgroups per CU: measured 0 - 3 % faster than L2 up to there, 17 % slower at 16 000
     // values, where one workgroup fills the LDS (profiles/targeted_metrics_throughput.txt)
     uint32_t gmm_lds_values = 8192;
+    // CRGPU_MC_LDS_VALUES (tests, read at create): largest number of distinct values whose histogram a (row, init) of the marginal
+    // caller keeps in LDS (marginal_calls.h; 16 bytes a value), 0 = always device memory.  No result depends on it.
+    uint32_t mc_lds_values = 4096;
     // read subsampling (subsample.h; tests, read at create): molecules of fewer reads than ss_wave_min are drawn one per lane, up to
     // ss_wg_min one per wave, larger ones one per workgroup; ss_task_batch = tasks per batch, 0 = by memory
     uint32_t ss_wave_min = 64, ss_wg_min = 4096, ss_task_batch = 0;  // CRGPU_SS_WAVE_MIN, CRGPU_SS_WG_MIN, CRGPU_SS_TASK_BATCH

@@ -296,6 +296,41 @@ const std::vector<AbiStruct> &abi_table() {
               ABI_F(crgpu_jibes_fit_result, converged),
               ABI_F(crgpu_jibes_fit_result, n_states),
               ABI_F(crgpu_jibes_fit_result, k_let_limited)),
+        ABI_S(crgpu_marginal_row, ABI_F(crgpu_marginal_row, status),
+              ABI_F(crgpu_marginal_row, in_lds),
+              ABI_F(crgpu_marginal_row, total_umis),
+              ABI_F(crgpu_marginal_row, cells_assigned),
+              ABI_F(crgpu_marginal_row, umi_threshold_observed),
+              ABI_F(crgpu_marginal_row, mean_low),
+              ABI_F(crgpu_marginal_row, mean_high),
+              ABI_F(crgpu_marginal_row, weight_low),
+              ABI_F(crgpu_marginal_row, weight_high),
+              ABI_F(crgpu_marginal_row, covariance),
+              ABI_F(crgpu_marginal_row, lower_bound),
+              ABI_F(crgpu_marginal_row, winner),
+              ABI_F(crgpu_marginal_row, n_iter),
+              ABI_F(crgpu_marginal_row, n_distinct),
+              ABI_F(crgpu_marginal_row, reserved)),
+        ABI_S(crgpu_marginal_calls, ABI_F(crgpu_marginal_calls, rows),
+              ABI_F(crgpu_marginal_calls, n_rows),
+              ABI_F(crgpu_marginal_calls, reserved),
+              ABI_F(crgpu_marginal_calls, n_barcodes),
+              ABI_F(crgpu_marginal_calls, n_assigned),
+              ABI_F(crgpu_marginal_calls, d_indptr),
+              ABI_F(crgpu_marginal_calls, d_columns),
+              ABI_F(crgpu_marginal_calls, d_features_per_cell),
+              ABI_F(crgpu_marginal_calls, d_hist_offsets),
+              ABI_F(crgpu_marginal_calls, d_hist_values),
+              ABI_F(crgpu_marginal_calls, d_hist_counts),
+              ABI_F(crgpu_marginal_calls, n_hist_slots),
+              ABI_F(crgpu_marginal_calls, cells_with_0),
+              ABI_F(crgpu_marginal_calls, cells_with_1),
+              ABI_F(crgpu_marginal_calls, cells_with_many),
+              ABI_F(crgpu_marginal_calls, cells_without_umis),
+              ABI_F(crgpu_marginal_calls, ms_extract),
+              ABI_F(crgpu_marginal_calls, ms_histogram),
+              ABI_F(crgpu_marginal_calls, ms_fit),
+              ABI_F(crgpu_marginal_calls, ms_assign)),
     };
     return t;
 }
@@ -380,6 +415,7 @@ extern "C" int crgpu_create(crgpu_ctx **out, int device_id, int n_ranks, int ran
     if (const char *f = getenv("CRGPU_MS_LDS_FEATURES")) ctx->ms_lds_features = (uint32_t)strtoul(f, nullptr, 10);  // tests: several slices on a small matrix; 0 = counters in device memory
     if (const char *f = getenv("CRGPU_FM_LDS_FEATURES")) ctx->fm_lds_features = (uint32_t)strtoul(f, nullptr, 10);  // tests: several slices on a small feature set; 0 = counters in device memory
     if (const char *f = getenv("CRGPU_GMM_LDS_VALUES")) ctx->gmm_lds_values = (uint32_t)strtoul(f, nullptr, 10);    // tests: 0 = the mixture fit reads its values from device memory
+    if (const char *f = getenv("CRGPU_MC_LDS_VALUES")) ctx->mc_lds_values = (uint32_t)strtoul(f, nullptr, 10);      // tests: 0 = the marginal caller reads its histograms from device memory
     if (const char *r = getenv("CRGPU_AGG_LDS_ROWS")) ctx->agg_lds_rows = (uint32_t)strtoul(r, nullptr, 10);  // tests: several slices of signal rows; 0 = the rank table in device memory
     if (const char *v = getenv("CRGPU_SS_WAVE_MIN")) ctx->ss_wave_min = (uint32_t)strtoul(v, nullptr, 10);  // tests: reach the wave path of the subsampling draw
     if (const char *v = getenv("CRGPU_SS_WG_MIN")) ctx->ss_wg_min = (uint32_t)strtoul(v, nullptr, 10);      // ... and its workgroup path

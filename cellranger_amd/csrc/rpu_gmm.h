@@ -30,9 +30,6 @@
 #include "stage_common.h"
 
 #define GMM_WG 256u
-#define GMM_MAX_ITER 100u
-#define GMM_TOL 1e-3
-#define GMM_REG 1e-6
 #define GMM_MIN_OFFTARGET_GENES 30u
 #define GMM_NSUM 5u
 #define GMM_OUT 6u  // per start: w0, w1, mu0, mu1, precision, lk
@@ -57,11 +54,7 @@ __device__ __forceinline__ void gmm_block_sum(double *v, double *s_red, double *
     __syncthreads();
 }
 
-__device__ __forceinline__ double gmm_logsumexp(double a0, double a1) {
-    const double m = a0 > a1 ? a0 : a1;
-    return log(exp(a0 - m) + exp(a1 - m)) + m;
-}
-#define GMM_LOG_2PI 1.8378770664093453  // np.log(2 * np.pi)
+// gmm_logsumexp and the constants of the EM iteration: stage_common.h (the marginal caller runs the same iteration)
 
 template <bool LDS>
 __global__ __launch_bounds__(GMM_WG) void k_gmm_fit(const double *__restrict__ values, uint32_t n, const double *__restrict__ start_means, uint32_t n_starts,

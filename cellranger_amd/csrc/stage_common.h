@@ -99,6 +99,17 @@ static inline double cr_median_sorted(const std::vector<T> &x) {
     return n % 2 ? (double)x[n / 2] : ((double)x[n / 2 - 1] + (double)x[n / 2]) / 2.0;
 }
 
+// scikit-learn's GaussianMixture EM for two 1-D components, as rpu_gmm.h (molecule_stages.hip) and marginal_calls.h
+// (matrix_stages.hip) both run it: max_iter, tol, reg_covar, log(2 pi) and the logsumexp of the two weighted log probabilities
+#define GMM_MAX_ITER 100u
+#define GMM_TOL 1e-3
+#define GMM_REG 1e-6
+#define GMM_LOG_2PI 1.8378770664093453  // np.log(2 * np.pi)
+__device__ __forceinline__ double gmm_logsumexp(double a0, double a1) {
+    const double m = a0 > a1 ? a0 : a1;
+    return log(exp(a0 - m) + exp(a1 - m)) + m;
+}
+
 __device__ __forceinline__ uint64_t lowmask(uint32_t bits) { return bits >= 64 ? ~0ull : ((1ull << bits) - 1ull); }
 
 // x[0 .. n) ascending: the first index with x[i] >= v (cr_lower_bound) or x[i] > v (cr_upper_bound), else n = the number of elements

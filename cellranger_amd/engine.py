@@ -946,6 +946,212 @@ def call_tags_jibes(ctx, filtered, tag_rows, valid_tags, prelim_calls, throughpu
                 barcodes_per_tag=dict(zip(names, per_tag)), non_singlets=non, snr=snr, fit=fit, tag_names=names)
 
 
+# ---- marginal calls of guides, antibodies and tags ----------------------------------------------------------------------------------
+GUIDE_UMI_THRESHOLD = 3
+MIN_COUNTS_PER_ANTIBODY = 1000
+ANTIBODY_ASSIGNMENT_LIST = (b"CD3", b"CD19", b"CD14")
+MIN_COUNTS_PER_TAG, COUNTS_DYNAMIC_RANGE, MAX_ALLOWED_PEARSON_CORRELATION = 1000, 50.0, 0.5
+NUM_TOTAL_TAGS = 14
+
+
+def _robust_divide(a, b):
+    return float("nan") if b == 0 else float(a) / float(b)
+
+
+def assignment_metadata(num_cells, n_single, n_multiple, n_without_umis):
+    """AssignmentMetadata of compute_generic_assignment_metadata (feature_assigner.py:234-269, 397-412) from the four integers"""
+    with_features = n_single + n_multiple
+    return dict(num_cells=int(num_cells), num_cells_without_features=int(num_cells - with_features),
+                frac_cells_without_features=_robust_divide(num_cells - with_features, num_cells),
+                num_cells_without_feature_umis=int(n_without_umis), frac_cells_without_feature_umis=_robust_divide(n_without_umis, num_cells),
+                num_singlets=int(n_single), frac_singlets=_robust_divide(n_single, num_cells), num_multiplets=int(n_multiple),
+                frac_multiplets=_robust_divide(n_multiple, num_cells))
+
+
+class MarginalCalls:
+    """crgpu_marginal_calls: the fit and the calls of every listed feature row (Context.marginal_calls).  per_feature: a dict of
+    numpy arrays, one value per row (status, in_lds, total_umis, cells_assigned, umi_threshold_observed, mean_low, mean_high,
+    weight_low, weight_high, covariance, lower_bound, winner, n_iter, n_distinct); the device arrays are downloaded on request."""
+
+    def __init__(self, ctx, view_ptr, feature_rows, umi_threshold):
+        self.ctx, self._v = ctx, view_ptr
+        v = view_ptr.contents
+        self.feature_rows, self.umi_threshold = np.array(feature_rows, np.uint32), int(umi_threshold)
+        self.n_rows, self.n_barcodes, self.n_assigned = int(v.n_rows), int(v.n_barcodes), int(v.n_assigned)
+        rows = np.ctypeslib.as_array(C.cast(v.rows, C.POINTER(C.c_uint8)), (self.n_rows * C.sizeof(_lib.MarginalRow),)).copy()
+        rec = rows.view(np.dtype([(n, {C.c_uint32: "<u4", C.c_uint64: "<u8", C.c_int64: "<i8", C.c_double: "<f8"}[t]) for n, t in _lib.MarginalRow._fields_]))
+        self.per_feature = {n: rec[n].copy() for n, _ in _lib.MarginalRow._fields_ if n != "reserved"}
+        self.cells_with_0, self.cells_with_1, self.cells_with_many = int(v.cells_with_0), int(v.cells_with_1), int(v.cells_with_many)
+        self.cells_without_umis = int(v.cells_without_umis)
+        self.phase_ms = dict(extract=v.ms_extract, histogram=v.ms_histogram, fit=v.ms_fit, assign=v.ms_assign)
+        self.has_histograms = bool(v.d_hist_offsets)
+
+    def _down(self, p, n, dtype):
+        out = np.zeros(n, dtype)
+        if n:
+            self.ctx._check(self.ctx.L.crgpu_memcpy_d2h(self.ctx.h, ptr(out), p, out.nbytes))
+        return out
+
+    def assignments(self):
+        """the assignment matrix as CSR over the listed rows -> (indptr i64[n_rows + 1], columns u32[n_assigned], ascending in a row)"""
+        v = self._v.contents
+        return self._down(v.d_indptr, self.n_rows + 1, np.int64), self._down(v.d_columns, self.n_assigned, np.uint32)
+
+    def cells_per_feature(self):
+        indptr, cols = self.assignments()
+        return [cols[indptr[p]:indptr[p + 1]] for p in range(self.n_rows)]
+
+    @property
+    def features_per_cell(self):
+        return self._down(self._v.contents.d_features_per_cell, self.n_barcodes, np.uint32)
+
+    def umi_thresholds(self):
+        """_compute_umi_thresholds: {place in the list: the lowest count among the cells assigned the feature}; rows without a call are left out"""
+        t = self.per_feature["umi_threshold_observed"]
+        return {p: int(t[p]) for p in range(self.n_rows) if self.per_feature["cells_assigned"][p] > 0}
+
+    def histogram(self, p):
+        """(values i32, multiplicities u32) of listed row p, values ascending, the zeros one bin (want_histograms)"""
+        if not self.has_histograms:
+            raise ValueError("MarginalCalls.histogram: the call was made without want_histograms")
+        v = self._v.contents
+        off = self._down(v.d_hist_offsets, self.n_rows + 1, np.int64)
+        nd = int(self.per_feature["n_distinct"][p])
+        isz = 4
+        return (self._down(v.d_hist_values + int(off[p]) * isz, nd, np.int32), self._down(v.d_hist_counts + int(off[p]) * isz, nd, np.uint32))
+
+    def metadata(self):
+        return assignment_metadata(self.n_barcodes, self.cells_with_1, self.cells_with_many, self.cells_without_umis)
+
+    def free(self):
+        if self._v is not None and self.ctx.h:
+            self.ctx.L.crgpu_marginal_calls_free(self.ctx.h, self._v)
+        self._v = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def tag_contaminants(sum_x, sum_xx, sum_xy, n_cells, order, min_counts=MIN_COUNTS_PER_TAG, dynamic_range=COUNTS_DYNAMIC_RANGE,
+                     max_cor=MAX_ALLOWED_PEARSON_CORRELATION):
+    """identify_contaminant_tags on the integer moments (crgpu_tag_contaminants, host only): order = the tags sorted by id as a
+    permutation -> (flags u8[n]: 0 kept, 1 contaminant, 2 dropped for zero UMIs; sources: per tag the list of its source tags)"""
+    sx, sxx = np.ascontiguousarray(sum_x, dtype=np.uint64), np.ascontiguousarray(sum_xx, dtype=np.uint64)
+    sxy, order = np.ascontiguousarray(sum_xy, dtype=np.uint64), np.ascontiguousarray(order, dtype=np.uint32)
+    n = len(sx)
+    flags, src = np.zeros(n, np.uint8), np.full((n, n), -1, np.int32)
+    rc = _lib.load().crgpu_tag_contaminants(n, int(n_cells), ptr(sx), ptr(sxx), ptr(sxy), ptr(order), int(min_counts), float(dynamic_range),
+                                            float(max_cor), ptr(flags), ptr(src))
+    if rc != 0:
+        raise _lib.CrgpuError(rc, "crgpu_tag_contaminants")
+    return flags, [[int(x) for x in row if x >= 0] for row in src]
+
+
+def marginal_seed_draws(V):
+    """test hook: (u f64[10, 3], first_cell u64[10]) of a fit over V cells"""
+    u, first = np.zeros((_lib.MC_INITS, 3)), np.zeros(_lib.MC_INITS, np.uint64)
+    rc = _lib.load().crgpu_marginal_seed_draws(int(V), ptr(u), ptr(first))
+    if rc != 0:
+        raise _lib.CrgpuError(rc, "crgpu_marginal_seed_draws")
+    return u, first
+
+
+def call_protospacers(ctx, filtered, guide_rows, n_features=None, report_prefix="CRISPR_"):
+    """GuideAssigner on the filtered MatrixDev: guide_rows = the feature rows of the CRISPR Guide Capture library (ascending); a cell
+    needs at least 3 UMIs of a guide.  -> dict(calls = MarginalCalls, metadata, metrics = the three frac_cells_with_*protospacer
+    values, summary = the integers and percentages of the four fixed rows of protospacer_calls_summary, umi_thresholds)"""
+    mc = ctx.marginal_calls(filtered, guide_rows, umi_threshold=GUIDE_UMI_THRESHOLD, n_features=n_features)
+    md = mc.metadata()
+    metrics = {report_prefix + "frac_cells_with_protospacer": md["frac_singlets"] + md["frac_multiplets"],
+               report_prefix + "frac_cells_with_single_protospacer": md["frac_singlets"],
+               report_prefix + "frac_cells_with_multiple_protospacer": md["frac_multiplets"]}
+    summary = {"No guide molecules": (md["num_cells_without_feature_umis"], 100 * md["frac_cells_without_feature_umis"]),
+               "No confident call": (md["num_cells_without_features"], 100 * md["frac_cells_without_features"]),
+               "1 protospacer assigned": (md["num_singlets"], 100 * md["frac_singlets"]),
+               "More than 1 protospacer assigned": (md["num_multiplets"], 100 * md["frac_multiplets"])}
+    return dict(calls=mc, metadata=md, metrics=metrics, summary=summary, umi_thresholds=mc.umi_thresholds())
+
+
+def call_antibodies(ctx, filtered, rows, ids, n_features=None, feature_bc_name="antibody", report_prefix="ANTIBODY_"):
+    """AntibodyOrAntigenAssigner on the filtered MatrixDev: rows / ids = the feature rows of the library (ascending) and their ids.
+    The reference calls only CD3, CD19 and CD14, and of those only a feature with at least 1000 UMIs: the host picks the rows (a
+    first call gives the totals, a second one the fits of the rows that remain).  -> dict(calls = MarginalCalls over `called_rows`
+    or None, called_rows, called_ids, metadata, metrics, umi_thresholds)"""
+    ids = [i if isinstance(i, bytes) else str(i).encode() for i in ids]
+    rows = np.asarray(rows, np.uint32)
+    pick = [k for k, i in enumerate(ids) if i in ANTIBODY_ASSIGNMENT_LIST]
+    mc = None
+    if pick:
+        first = ctx.marginal_calls(filtered, rows[pick], n_features=n_features)
+        keep = [k for j, k in enumerate(pick) if first.per_feature["total_umis"][j] >= MIN_COUNTS_PER_ANTIBODY]
+        if len(keep) == len(pick):
+            mc = first
+        else:
+            first.free()
+            pick = keep
+            mc = ctx.marginal_calls(filtered, rows[pick], n_features=n_features) if pick else None
+    all_rows = ctx.marginal_calls(filtered, rows, n_features=n_features) if mc is None or len(pick) != len(rows) else mc
+    without = all_rows.cells_without_umis      # get_num_cells_without_molecules: over the whole library
+    if all_rows is not mc:
+        all_rows.free()
+    md = assignment_metadata(filtered.n_barcodes, mc.cells_with_1 if mc else 0, mc.cells_with_many if mc else 0, without)
+    metrics = {report_prefix + "frac_cells_with_" + feature_bc_name: md["frac_singlets"] + md["frac_multiplets"],
+               report_prefix + "frac_cells_with_single_" + feature_bc_name: md["frac_singlets"],
+               report_prefix + "frac_cells_with_multiple_" + feature_bc_name: md["frac_multiplets"]}
+    return dict(calls=mc, called_rows=rows[pick], called_ids=[ids[k] for k in pick], metadata=md, metrics=metrics,
+                umi_thresholds=mc.umi_thresholds() if mc else {})
+
+
+def umi_interval_snr(values, counts, threshold):
+    """_get_umi_interval + the log10_snr column (feature_assigner.py:470-474, 492-505) on a histogram: np.percentile over the counts
+    the histogram stands for, rounded to 3 places"""
+    dense = np.repeat(np.asarray(values, np.int64), np.asarray(counts, np.int64))
+    noise, signal = dense[dense < threshold], dense[dense >= threshold]
+    q3 = np.percentile(noise, 75) if len(noise) else 0
+    q1 = np.percentile(signal, 25) if len(signal) else 0
+    return float(np.round(np.log10(q1 + 1) - np.log10(q3 + 1), 3))
+
+
+def call_tags_marginal(ctx, filtered, tag_rows, tag_ids, n_features=None):
+    """TagAssigner (CALL_TAGS_MARGINAL) on the filtered MatrixDev: tag_rows = the feature rows of the Multiplexing Capture library
+    (ascending), tag_ids their ids.  -> dict(calls = MarginalCalls over all tag rows, flags u8 per tag (0 kept, 1 contaminant, 2
+    dropped for zero UMIs), source_tags (per tag the ids it correlates with), log10_snr per tag (NaN without a call), umi_thresholds,
+    features_per_cell u32[V] over the tags that are not contaminants, metadata, nlet_observed i64[15] (cells with 0 .. 14 tags),
+    valid_tags bool per tag and prelim_calls i32[V]: what engine.call_tags_jibes takes)."""
+    ids = [i if isinstance(i, bytes) else str(i).encode() for i in tag_ids]
+    k = len(ids)
+    mc = ctx.marginal_calls(filtered, tag_rows, n_features=n_features, want_histograms=True)
+    sx, sxx, sxy = ctx.tag_moments(filtered, tag_rows, n_features=n_features)
+    order = np.array(sorted(range(k), key=lambda t: ids[t]), np.uint32)
+    flags, src = tag_contaminants(sx, sxx, sxy, filtered.n_barcodes, order)
+    indptr, cols = mc.assignments()
+    V = filtered.n_barcodes
+    thr = mc.per_feature["umi_threshold_observed"]
+    snr = np.full(k, np.nan)
+    for t in range(k):
+        if flags[t] != 2 and indptr[t + 1] > indptr[t]:
+            snr[t] = umi_interval_snr(*mc.histogram(t), int(thr[t]))
+    good = [t for t in range(k) if flags[t] == 0]
+    fpc = np.zeros(V, np.uint32)
+    for t in good:
+        np.add.at(fpc, cols[indptr[t]:indptr[t + 1]], 1)
+    md = assignment_metadata(V, int((fpc == 1).sum()), int((fpc > 1).sum()), mc.cells_without_umis)
+    nlet = np.bincount(np.minimum(fpc, NUM_TOTAL_TAGS + 1), minlength=NUM_TOTAL_TAGS + 2)[:NUM_TOTAL_TAGS + 1].astype(np.int64)
+    valid = np.array([flags[t] == 0 and indptr[t + 1] > indptr[t] for t in range(k)], bool)
+    place = np.cumsum(valid) - 1
+    prelim = np.full(V, -1, np.int32)
+    for t in np.flatnonzero(valid):
+        c = cols[indptr[t]:indptr[t + 1]]
+        c = c[fpc[c] == 1]
+        prelim[c] = place[t]
+    return dict(calls=mc, flags=flags, source_tags=[[ids[j] for j in s] for s in src], log10_snr=snr,
+                umi_thresholds={t: int(thr[t]) for t in range(k) if flags[t] != 2 and indptr[t + 1] > indptr[t]}, features_per_cell=fpc,
+                metadata=md, nlet_observed=nlet, valid_tags=valid, prelim_calls=prelim)
+
+
 def ordmag_candidates(max_expected_cells=1 << 18):
     """the recovered-cells grid of estimate_recovered_cells_ordmag (cell_calling_helpers.py:879-880); host only"""
     out, n = np.zeros(2000, np.int64), C.c_uint32()
@@ -1979,6 +2185,32 @@ class Context:
                                                       ptr(kept)))
         return dict(counts=counts, row_sums=sums, near_zero=nz[:n_nz.value].copy(), kept=kept[:V - n_nz.value].copy(),
                     log_counts=np.log10(counts + 1.0))
+
+    def marginal_calls(self, m, feature_rows, umi_threshold=1, n_features=None, want_histograms=False):
+        """call_presence_with_gmm_ab for every listed feature row of the filtered MatrixDev `m` (csrc/marginal_calls.h): feature_rows
+        ascending; a cell is assigned a feature when its count >= umi_threshold and falls to the mixture's upper component
+        -> MarginalCalls"""
+        rows = np.ascontiguousarray(feature_rows, dtype=np.uint32)
+        if n_features is None:
+            n_features = getattr(self, "n_features", None)
+            if n_features is None:
+                raise ValueError("marginal_calls: pass n_features")
+        out = C.POINTER(_lib.MarginalCalls)()
+        self._check(self.L.crgpu_marginal_calls_dev(self.h, m._mv, ptr(rows), len(rows), int(n_features), int(umi_threshold), 1 if want_histograms else 0,
+                                                    C.byref(out)))
+        return MarginalCalls(self, out, rows, umi_threshold)
+
+    def tag_moments(self, m, tag_rows, n_features=None):
+        """the exact sums over the cells of x, x^2 and x y for the listed tag rows (at most 16) -> (u64[n], u64[n], u64[n, n])"""
+        rows = np.ascontiguousarray(tag_rows, dtype=np.uint32)
+        if n_features is None:
+            n_features = getattr(self, "n_features", None)
+            if n_features is None:
+                raise ValueError("tag_moments: pass n_features")
+        n = len(rows)
+        sx, sxx, sxy = np.zeros(n, np.uint64), np.zeros(n, np.uint64), np.zeros((n, n), np.uint64)
+        self._check(self.L.crgpu_tag_moments_dev(self.h, m._mv, ptr(rows), n, int(n_features), ptr(sx), ptr(sxx), ptr(sxy)))
+        return sx, sxx, sxy
 
     def jibes_fit(self, y, bg, fg, sd, n_gems=N_G, estimated_cells=None, blank_prob=0.04, freqs=None, max_k_lets=3, max_reps=50000, abs_tol=1e-2,
                   rel_tol=1e-7, confidence=JIBES_MIN_CONFIDENCE, exclude_blanks_from_posterior=False, apply_confidence=True, want_posterior=False):

@@ -1551,8 +1551,8 @@ int crgpu_compute_feature_dist(const int64_t *counts, const uint32_t *feature_ty
  *                                  CRGPU_JIBES_EXCLUDE_BLANKS -- is below `confidence` (CRGPU_JIBES_NO_CONFIDENCE: no such rule, as
  *                                  JIBESMultiGenome); assignment_prob_out f64[n]: the maximum itself; ml_state_out u32[n]: the first
  *                                  maximum over the Multiplet states, as a state index; posterior_out f64[n x n_states] (tests).
- * NOT covered: optimize_pop_freqs (the Rust asserts it off), the CSV / JSON / pickle writers, get_valid_tags, CALL_TAGS_MARGINAL (its
- * calls are an input), get_frac_contaminant_tags and the fat-tail metric. */
+ * NOT covered: optimize_pop_freqs (the Rust asserts it off), the CSV / JSON / pickle writers, get_valid_tags (the
+ * marginal calls below give valid_tags and prelim_calls), get_frac_contaminant_tags and the fat-tail metric. */
 #define CRGPU_JIBES_MAX_TAGS 16
 #define CRGPU_JIBES_MAX_K_LETS 3
 #define CRGPU_JIBES_MAX_STATES 970 /* 1 + 16 + 136 + 816 + the unit vector */
@@ -1602,6 +1602,100 @@ int crgpu_jibes_tag_counts_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const 
                                uint64_t *kept_out);
 int crgpu_jibes_fit_dev(crgpu_ctx *ctx, const double *y, uint64_t n, uint32_t k, const crgpu_jibes_fit_args *args,
                         crgpu_jibes_fit_result *result);
+
+/* ---- marginal calls of guides, tags and antibodies: CALL_PROTOSPACERS, CALL_ANTIBODIES, CALL_TAGS_MARGINAL ------------------------
+ * "Is this feature present in this cell, above background": call_presence_with_gmm_ab (lib/python/cellranger/feature/
+ * feature_assigner.py:213-230), which GuideAssigner (umi_threshold 3), AntibodyOrAntigenAssigner and TagAssigner all come down to.
+ * Per feature row a tied two-component Gaussian mixture on log10(1 + count) over ALL cells -- scikit-learn 1.7.2's
+ * GaussianMixture(n_components=2, n_init=10, covariance_type="tied", random_state=0); older releases seed differently and are out
+ * of scope -- then predict; a cell is assigned when its count >= umi_threshold and its value falls to the component of the larger mean.
+ *   crgpu_marginal_calls_dev     m: the filtered matrix; feature_rows: host u32[n_rows], strictly ascending and below n_features
+ *                                (else CRGPU_EINVAL); umi_threshold >= 1 (else CRGPU_EINVAL: a zero is never assigned).  *out is
+ *                                library-owned (crgpu_marginal_calls_free).
+ *       row extraction           the entries of the listed rows as CSR, columns ascending (count, scan, scatter in CSC order, then
+ *                                the library's radix sort on whole, unique keys); counts are i32 and V < 2^31 - 1
+ *       histogram                per row (value, multiplicity), values ascending, the zeros one bin of V - nnz(row); x = log10(1 +
+ *                                value) comes from a HOST table for value < 65536 (the C library's log10, which is numpy's), from the
+ *                                device's log10 above
+ *       seeding per (row, init)  _kmeans_plusplus for k = 2 on the mean-centred data: the first centre is cell first_cell[init] (a zero
+ *                                when the row has no entry there); the two trial draws u * pot are located in the cumulative squared
+ *                                distance taken in CELL order -- a scan over the row's entries, a gap of g zeros adds g * d0 --; each
+ *                                candidate's potential from the histogram; the smaller wins, the first on a tie; only the chosen cell's
+ *                                VALUE enters what follows
+ *       Lloyd                    on the histogram: labels to the nearer centre (a tie to centre 0), weighted means, stop when the labels
+ *                                repeat or the squared shift is <= 1e-4 var(x) (then one relabel), at most 300 rounds (then one relabel);
+ *                                an empty cluster keeps its centre
+ *       EM                       the iteration of crgpu_rpu_gmm_dev weighted by the multiplicities: nk + 10 eps, tied covariance + 1e-6,
+ *                                lower bound = mean log-sum-exp under the previous parameters, stop at |change| < 1e-3 or after 100
+ *                                iterations; the winner is the first init with the strictly largest lower bound
+ *       predict                  per distinct value the argmax of the weighted log probabilities under the winner (a tie to component 0);
+ *                                the positive component is the argmax of the means
+ *       guards kept              a row whose maximum is 0, or V < 2: CRGPU_MC_SKIPPED, no calls
+ *       QUIRK kept               a row of ONE distinct value is fitted: its second cluster is empty (mean 0, weight of a few eps) and
+ *                                every cell whose count meets the threshold is called
+ *       on the device            a workgroup per (row, init): one wave for a row of <= 256 distinct values and <= 4096 entries, else four; the histogram in
+ *                                LDS up to CRGPU_MC_LDS_VALUES=<n> distinct values (environment, at creation; default 4096, 0 = always
+ *                                device memory).  Every sum has one order that depends on the row alone: no result depends on the
+ *                                switch, the grid, the other rows of the call or the run.  f64, unfused.
+ *   crgpu_marginal_row           status; in_lds; total_umis; cells_assigned; umi_threshold_observed (the minimum count among the
+ *                                assigned cells, -1 when none); the mean and weight of the low and the high component, the tied
+ *                                covariance; the winner's lower bound, init index and n_iter_; n_distinct (with the zero bin)
+ *   crgpu_marginal_calls         rows: host, one per listed row.  Device: the assignment matrix as CSR (d_indptr i64[n_rows + 1],
+ *                                d_columns u32[n_assigned] ascending inside a row), d_features_per_cell u32[V]; with want_histograms
+ *                                row p's histogram is d_hist_values / d_hist_counts[d_hist_offsets[p] .. + rows[p].n_distinct) (else
+ *                                NULL).  cells_with_0 / _1 / _many: cells by their number of assigned rows; cells_without_umis: cells
+ *                                with no UMI in any listed row (compute_generic_assignment_metadata).  ms_*: host time per phase.
+ *   crgpu_tag_moments_dev        the exact integer sums over the cells for the listed rows (at most CRGPU_JIBES_MAX_TAGS): sum_x_out
+ *                                u64[n], sum_xx_out u64[n], sum_xy_out u64[n x n] (symmetric, the diagonal = sum_xx); host arrays
+ *   crgpu_tag_contaminants       identify_contaminant_tags (feature_assigner.py:1102-1163), host only: a tag of zero UMIs is DROPPED
+ *                                (flag 2, no part in the correlations), one below min_counts (1000) or dynamic_range (50) times below the
+ *                                largest is a contaminant (flag 1); then every pair in `order` (the tags sorted by id, as a permutation
+ *                                of 0 .. n - 1) whose Pearson correlation over the n_cells cells is >= max_cor (0.5) marks the tag of
+ *                                fewer UMIs (the later one on a tie) and appends the other to its sources; a NaN correlation is skipped.
+ *                                flags_out u8[n]; sources_out i32[n x n]: row t lists t's source tags in the order met, -1 behind them.
+ *   crgpu_marginal_seed_draws    test hook, not a stable interface: u_out f64[30] = per init the double of choice() and the two of the
+ *                                trial candidates under RandomState(0); first_cell_out u64[10] = the cells choice(V, p = uniform) gives
+ * NOT covered: the CSV / JSON writers; the Poisson and "measurable" columns of the n-let frequency table and the efficiency metrics
+ * built on them; MEASURE_PERTURBATIONS; median and standard deviation of the UMIs per call group. */
+#define CRGPU_MC_INITS 10
+#define CRGPU_MC_SKIPPED 0u
+#define CRGPU_MC_FITTED 1u
+struct crgpu_marginal_row {
+    uint32_t status, in_lds;
+    uint64_t total_umis;
+    uint64_t cells_assigned;
+    int64_t umi_threshold_observed;
+    double mean_low, mean_high;
+    double weight_low, weight_high;
+    double covariance, lower_bound;
+    uint32_t winner, n_iter;      /* winner: 0xFFFFFFFF when not fitted */
+    uint32_t n_distinct, reserved;
+};
+typedef struct crgpu_marginal_row crgpu_marginal_row;
+struct crgpu_marginal_calls {
+    const crgpu_marginal_row *rows; /* host, n_rows */
+    uint32_t n_rows, reserved;
+    uint64_t n_barcodes, n_assigned;
+    const int64_t *d_indptr;
+    const uint32_t *d_columns;
+    const uint32_t *d_features_per_cell;
+    const int64_t *d_hist_offsets;  /* n_rows + 1 */
+    const int32_t *d_hist_values;
+    const uint32_t *d_hist_counts;
+    uint64_t n_hist_slots;
+    uint64_t cells_with_0, cells_with_1, cells_with_many, cells_without_umis;
+    double ms_extract, ms_histogram, ms_fit, ms_assign;
+};
+typedef struct crgpu_marginal_calls crgpu_marginal_calls;
+int crgpu_marginal_calls_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const uint32_t *feature_rows, uint32_t n_rows, uint32_t n_features,
+                             uint32_t umi_threshold, uint32_t want_histograms, crgpu_marginal_calls **out);
+void crgpu_marginal_calls_free(crgpu_ctx *ctx, crgpu_marginal_calls *r);
+int crgpu_tag_moments_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const uint32_t *tag_rows, uint32_t n_rows, uint32_t n_features,
+                          uint64_t *sum_x_out, uint64_t *sum_xx_out, uint64_t *sum_xy_out);
+int crgpu_tag_contaminants(uint32_t n_tags, uint64_t n_cells, const uint64_t *sum_x, const uint64_t *sum_xx, const uint64_t *sum_xy,
+                           const uint32_t *order, uint64_t min_counts, double dynamic_range, double max_cor, uint8_t *flags_out,
+                           int32_t *sources_out);
+int crgpu_marginal_seed_draws(uint64_t V, double *u_out, uint64_t *first_cell_out);
 
 /* ---- synthetic workloads (bench / tests) ---------------------------------------------
  * Counter-based integer generator: read i of a given seed is identical on the host and on the

@@ -1223,6 +1223,53 @@ inline JibesFit jibes_fit(Context &ctx, const std::vector<double> &y, uint32_t k
     return out;
 }
 
+// ---- marginal calls of guides, antibodies and tags ------------------------------------------------------------------------------------------
+static_assert(sizeof(crgpu_marginal_row) == 96, "crgpu_marginal_row changed: bump CRGPU_ABI_VERSION and every binding");
+static_assert(sizeof(crgpu_marginal_calls) == 152, "crgpu_marginal_calls changed: bump CRGPU_ABI_VERSION and every binding");
+struct MarginalCalls {
+    std::vector<crgpu_marginal_row> rows;   // one per listed feature row
+    std::vector<int64_t> indptr;            // the assignment matrix as CSR over the listed rows
+    std::vector<uint32_t> columns;          // ascending inside a row
+    std::vector<uint32_t> features_per_cell;
+    uint64_t cells_with_0 = 0, cells_with_1 = 0, cells_with_many = 0, cells_without_umis = 0;
+};
+/// crgpu_marginal_calls_dev with everything brought to the host: feature_rows strictly ascending; umi_threshold 3 for guides, 1 otherwise
+inline MarginalCalls marginal_calls(Context &ctx, const crgpu_matrix_dev *filtered, const std::vector<uint32_t> &feature_rows, uint32_t n_features,
+                                    uint32_t umi_threshold = 1) {
+    crgpu_marginal_calls *r = nullptr;
+    ctx.check(crgpu_marginal_calls_dev(ctx.get(), filtered, feature_rows.data(), (uint32_t)feature_rows.size(), n_features, umi_threshold, 0, &r));
+    MarginalCalls out;
+    out.rows.assign(r->rows, r->rows + r->n_rows);
+    out.cells_with_0 = r->cells_with_0, out.cells_with_1 = r->cells_with_1, out.cells_with_many = r->cells_with_many;
+    out.cells_without_umis = r->cells_without_umis;
+    int rc = detail::fetch(ctx, out.indptr, r->d_indptr, (uint64_t)r->n_rows + 1);
+    if (rc == CRGPU_OK) rc = detail::fetch(ctx, out.columns, r->d_columns, r->n_assigned);
+    if (rc == CRGPU_OK) rc = detail::fetch(ctx, out.features_per_cell, r->d_features_per_cell, r->n_barcodes);
+    crgpu_marginal_calls_free(ctx.get(), r);
+    ctx.check(rc);
+    return out;
+}
+struct TagContaminants {
+    std::vector<uint8_t> flags;                  // 0 kept, 1 contaminant, 2 dropped for zero UMIs
+    std::vector<std::vector<uint32_t>> sources;  // per tag its source tags in the order met
+};
+/// crgpu_tag_moments_dev + crgpu_tag_contaminants with the reference's constants: order = the tags sorted by id, as a permutation
+inline TagContaminants tag_contaminants(Context &ctx, const crgpu_matrix_dev *filtered, const std::vector<uint32_t> &tag_rows, uint32_t n_features,
+                                        const std::vector<uint32_t> &order) {
+    const uint32_t n = (uint32_t)tag_rows.size();
+    if (order.size() != n) throw Error(CRGPU_EINVAL, "tag_contaminants: one place per tag");
+    std::vector<uint64_t> sx(n), sxx(n), sxy((size_t)n * n);
+    ctx.check(crgpu_tag_moments_dev(ctx.get(), filtered, tag_rows.data(), n, n_features, sx.data(), sxx.data(), sxy.data()));
+    TagContaminants out;
+    out.flags.assign(n, 0), out.sources.assign(n, {});
+    std::vector<int32_t> src((size_t)n * n, -1);
+    const int rc = crgpu_tag_contaminants(n, filtered->n_barcodes, sx.data(), sxx.data(), sxy.data(), order.data(), 1000, 50.0, 0.5, out.flags.data(), src.data());
+    if (rc != CRGPU_OK) throw Error(rc, "tag_contaminants");
+    for (uint32_t t = 0; t < n; t++)
+        for (uint32_t j = 0; j < n && src[(size_t)t * n + j] >= 0; j++) out.sources[t].push_back((uint32_t)src[(size_t)t * n + j]);
+    return out;
+}
+
 // ---- protein aggregates of an antibody / antigen well; the closing filters of a cell call ---------------------------------------------
 static_assert(sizeof(crgpu_aggregates_info) == 48, "crgpu_aggregates_info changed: bump CRGPU_ABI_VERSION and every binding");
 /// int(np.round(n_signal * _calculate_fraction_to_use(n_signal)))
