@@ -322,6 +322,19 @@ class MarginalCalls(C.Structure):
         (n, C.c_double) for n in ("ms_extract", "ms_histogram", "ms_fit", "ms_assign")]
 
 
+class KmeansArgs(C.Structure):
+    """crgpu_kmeans_args"""
+    _fields_ = [("init", C.POINTER(C.c_void_p)), ("tol_factor", C.c_double), ("seed", C.c_uint32), ("max_iter", C.c_uint32)]
+
+
+class KmeansResult(C.Structure):
+    """crgpu_kmeans_result"""
+    _fields_ = [(n, C.c_void_p) for n in ("labels_out", "clusters_out", "centers_out", "sizes_out", "wss_out")] + [
+        (n, C.c_double) for n in ("inertia", "db_score", "fit_ms")] + [
+        (n, C.c_uint32) for n in ("n_iter", "strict", "relocations", "in_lds")]
+
+
+KM_MAX_K, KM_MAX_D, KM_MAX_LIST = 64, 128, 64
 MC_INITS, MC_SKIPPED, MC_FITTED = 10, 0, 1
 JIBES_MAX_TAGS, JIBES_MAX_K_LETS, JIBES_MAX_STATES, JIBES_NEAR_ZERO, JIBES_CANT_CONVERGE = 16, 3, 970, 12, 1
 JIBES_EXCLUDE_BLANKS, JIBES_NO_CONFIDENCE = 1, 2
@@ -485,6 +498,9 @@ SYMBOLS = {
     "crgpu_tag_moments_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, _u32, _vp, _vp, _vp]),
     "crgpu_tag_contaminants": (_i, [_u32, _u64, _vp, _vp, _vp, _vp, _u64, _dbl, _dbl, _vp, _vp]),
     "crgpu_marginal_seed_draws": (_i, [_u64, _vp, _vp]),
+    "crgpu_kmeans_dev": (_i, [_vp, _vp, _u64, _u32, _u64, _vp, _u32, C.POINTER(KmeansArgs), C.POINTER(KmeansResult)]),
+    "crgpu_kmeans_db_index": (_i, [_u32, _u32, _vp, _vp, _vp, C.POINTER(_dbl)]),
+    "crgpu_kmeans_seed_draws": (_i, [_u32, _u64, _u32, _vp, C.POINTER(_u64)]),
     "crgpu_aggregate_min_antibodies": (_i, [_u32, C.POINTER(_u32)]),
     "crgpu_antigen_outlier_threshold": (_i, [_vp, _u32, C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_dbl)]),
     "crgpu_aggregates_by_counts_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, _u32, _vp, _vp, _u32, C.POINTER(_u32),

@@ -251,6 +251,10 @@ struct crgpu_ctx {
     // CRGPU_MC_LDS_VALUES (tests, read at create): largest number of distinct values whose histogram a (row, init) of the marginal
     // caller keeps in LDS (marginal_calls.h; 16 bytes a value), 0 = always device memory.  No result depends on it.
     uint32_t mc_lds_values = 4096;
+    // CRGPU_KM_LDS_CENTERS (tests, read at create): largest K * d whose centres a workgroup of the k-means assign pass keeps in LDS
+    // (kmeans.h; at most 4096), 0 = always device memory.  CRGPU_KM_BATCH: Lloyd rounds enqueued between two reads of the stop
+    // latches, 0 = the default of 8.  No result depends on either.
+    uint32_t km_lds_centers = 4096, km_batch = 0;
     // read subsampling (subsample.h; tests, read at create): molecules of fewer reads than ss_wave_min are drawn one per lane, up to
     // ss_wg_min one per wave, larger ones one per workgroup; ss_task_batch = tasks per batch, 0 = by memory
     uint32_t ss_wave_min = 64, ss_wg_min = 4096, ss_task_batch = 0;  // CRGPU_SS_WAVE_MIN, CRGPU_SS_WG_MIN, CRGPU_SS_TASK_BATCH

@@ -331,6 +331,22 @@ const std::vector<AbiStruct> &abi_table() {
               ABI_F(crgpu_marginal_calls, ms_histogram),
               ABI_F(crgpu_marginal_calls, ms_fit),
               ABI_F(crgpu_marginal_calls, ms_assign)),
+        ABI_S(crgpu_kmeans_args, ABI_F(crgpu_kmeans_args, init),
+              ABI_F(crgpu_kmeans_args, tol_factor),
+              ABI_F(crgpu_kmeans_args, seed),
+              ABI_F(crgpu_kmeans_args, max_iter)),
+        ABI_S(crgpu_kmeans_result, ABI_F(crgpu_kmeans_result, labels_out),
+              ABI_F(crgpu_kmeans_result, clusters_out),
+              ABI_F(crgpu_kmeans_result, centers_out),
+              ABI_F(crgpu_kmeans_result, sizes_out),
+              ABI_F(crgpu_kmeans_result, wss_out),
+              ABI_F(crgpu_kmeans_result, inertia),
+              ABI_F(crgpu_kmeans_result, db_score),
+              ABI_F(crgpu_kmeans_result, fit_ms),
+              ABI_F(crgpu_kmeans_result, n_iter),
+              ABI_F(crgpu_kmeans_result, strict),
+              ABI_F(crgpu_kmeans_result, relocations),
+              ABI_F(crgpu_kmeans_result, in_lds)),
     };
     return t;
 }
@@ -416,6 +432,8 @@ extern "C" int crgpu_create(crgpu_ctx **out, int device_id, int n_ranks, int ran
     if (const char *f = getenv("CRGPU_FM_LDS_FEATURES")) ctx->fm_lds_features = (uint32_t)strtoul(f, nullptr, 10);  // tests: several slices on a small feature set; 0 = counters in device memory
     if (const char *f = getenv("CRGPU_GMM_LDS_VALUES")) ctx->gmm_lds_values = (uint32_t)strtoul(f, nullptr, 10);    // tests: 0 = the mixture fit reads its values from device memory
     if (const char *f = getenv("CRGPU_MC_LDS_VALUES")) ctx->mc_lds_values = (uint32_t)strtoul(f, nullptr, 10);      // tests: 0 = the marginal caller reads its histograms from device memory
+    if (const char *f = getenv("CRGPU_KM_LDS_CENTERS")) ctx->km_lds_centers = std::min<uint32_t>((uint32_t)strtoul(f, nullptr, 10), 4096u);  // tests: 0 = the k-means assign pass reads its centres from device memory
+    if (const char *b = getenv("CRGPU_KM_BATCH")) ctx->km_batch = (uint32_t)strtoul(b, nullptr, 10);                // tests: Lloyd rounds between two reads of the stop latches
     if (const char *r = getenv("CRGPU_AGG_LDS_ROWS")) ctx->agg_lds_rows = (uint32_t)strtoul(r, nullptr, 10);  // tests: several slices of signal rows; 0 = the rank table in device memory
     if (const char *v = getenv("CRGPU_SS_WAVE_MIN")) ctx->ss_wave_min = (uint32_t)strtoul(v, nullptr, 10);  // tests: reach the wave path of the subsampling draw
     if (const char *v = getenv("CRGPU_SS_WG_MIN")) ctx->ss_wg_min = (uint32_t)strtoul(v, nullptr, 10);      // ... and its workgroup path

@@ -5,6 +5,7 @@
 #include "cell_calling.h"
 #include "emptydrops.h"
 #include "jibes.h"
+#include "kmeans.h"
 #include "marginal_calls.h"
 #include "matrix_summary.h"
 #include "multigenome.h"

@@ -1059,6 +1059,53 @@ def marginal_seed_draws(V):
     return u, first
 
 
+def kmeans_trials(k):
+    """2 + int(np.log(k)): the trial candidates scikit-learn draws for each centre after the first"""
+    return 2 + int(math.log(k))
+
+
+def kmeans_seed_draws(seed, n, k):
+    """test hook: (u f64[1 + (k - 1) kmeans_trials(k)], first_cell) of a k-means fit over n cells under RandomState(seed)"""
+    u, first = np.zeros(1 + (k - 1) * kmeans_trials(k)), C.c_uint64(0)
+    rc = _lib.load().crgpu_kmeans_seed_draws(int(seed), int(n), int(k), ptr(u), C.byref(first))
+    if rc != 0:
+        raise _lib.CrgpuError(rc, "crgpu_kmeans_seed_draws")
+    return u, int(first.value)
+
+
+def kmeans_db_index(centers, wss, counts):
+    """compute_db_index from its per-cluster sums (crgpu_kmeans_db_index, host only) -> the Davies-Bouldin score"""
+    c = np.ascontiguousarray(centers, dtype=np.float64)
+    w, cnt = np.ascontiguousarray(wss, dtype=np.float64), np.ascontiguousarray(counts, dtype=np.uint64)
+    if c.ndim != 2 or len(w) != len(c) or len(cnt) != len(c):
+        raise ValueError("kmeans_db_index: centers is k x d, wss and counts have k values")
+    score = C.c_double(0.0)
+    rc = _lib.load().crgpu_kmeans_db_index(c.shape[0], c.shape[1], ptr(c), ptr(w), ptr(cnt), C.byref(score))
+    if rc != 0:
+        raise _lib.CrgpuError(rc, "crgpu_kmeans_db_index")
+    return score.value
+
+
+def kmeans_clustering_key(n_clusters, library_prefix=None):
+    """format_clustering_key for a k-means clustering; library_prefix "gene_expression" / "antibody_capture" goes in front"""
+    key = "kmeans_%d_clusters" % n_clusters
+    return "%s_%s" % (library_prefix, key) if library_prefix else key
+
+
+def run_kmeans(ctx, projection, max_clusters=10, min_clusters=2, seed=0, num_pcs=None, library_prefix=None):
+    """RUN_KMEANS for one library type: the cells x PCs projection clustered for K = min_clusters .. min(max_clusters, cells) in one
+    device call -> {clustering key: dict(clusters i32[n] 1-based by size, cluster_score, centers, num_clusters, global_sort_key)}"""
+    n = np.shape(projection)[0]
+    ks = list(range(min_clusters, min(max_clusters, n) + 1))      # split(): max_clusters = min(max_clusters, the number of barcodes)
+    if not ks:
+        return {}
+    out = {}
+    for r in ctx.kmeans(projection, ks, seed=seed, num_pcs=num_pcs):
+        out[kmeans_clustering_key(r["n_clusters"], library_prefix)] = dict(
+            clusters=r["clusters"], cluster_score=r["db_score"], centers=r["centers"], num_clusters=r["n_clusters"], global_sort_key=r["n_clusters"])
+    return out
+
+
 def call_protospacers(ctx, filtered, guide_rows, n_features=None, report_prefix="CRISPR_"):
     """GuideAssigner on the filtered MatrixDev: guide_rows = the feature rows of the CRISPR Guide Capture library (ascending); a cell
     needs at least 3 UMIs of a guide.  -> dict(calls = MarginalCalls, metadata, metrics = the three frac_cells_with_*protospacer
@@ -2199,6 +2246,51 @@ class Context:
         self._check(self.L.crgpu_marginal_calls_dev(self.h, m._mv, ptr(rows), len(rows), int(n_features), int(umi_threshold), 1 if want_histograms else 0,
                                                     C.byref(out)))
         return MarginalCalls(self, out, rows, umi_threshold)
+
+    def kmeans(self, projection, n_clusters, seed=0, num_pcs=None, init=None, max_iter=300, tol=1e-4):
+        """scikit-learn 1.7.2's KMeans(n_clusters = K, random_state = seed) with the reference's Davies-Bouldin score and relabel_by_size
+        (csrc/kmeans.h) for one K or a list of distinct K on the f64 projection [cells x PCs]; num_pcs takes the first columns as a view;
+        init: None, or one k x d array (n_clusters an int), or a list with None or an array per K (scikit-learn's init = array)
+        -> one dict per K: n_clusters, labels i32[n], clusters i32[n] (1-based, the largest first), centers f64[K, d], inertia, n_iter,
+        strict, relocations, sizes u64[K], wss f64[K], db_score, in_lds, fit_ms"""
+        x = np.ascontiguousarray(projection, dtype=np.float64)
+        if x.ndim != 2:
+            raise ValueError("kmeans: the projection is cells x PCs")
+        n, ld = x.shape
+        d = ld if num_pcs is None else int(num_pcs)
+        single = np.ndim(n_clusters) == 0
+        ks = np.ascontiguousarray([n_clusters] if single else n_clusters, dtype=np.uint32)
+        inits = [init] if single else (list(init) if init is not None else None)
+        a = _lib.KmeansArgs(init=None, tol_factor=float(tol), seed=int(seed), max_iter=int(max_iter))
+        keep = []
+        if inits is not None and any(i is not None for i in inits):
+            if len(inits) != len(ks):
+                raise ValueError("kmeans: one init (or None) per K")
+            arr = (C.c_void_p * len(ks))()
+            for p, i in enumerate(inits):
+                if i is None:
+                    continue
+                i = np.ascontiguousarray(i, dtype=np.float64)
+                if i.shape != (int(ks[p]), d):
+                    raise ValueError("kmeans: init of K = %d is %d x %d" % (ks[p], ks[p], d))
+                keep.append(i)
+                arr[p] = i.ctypes.data
+            a.init = C.cast(arr, C.POINTER(C.c_void_p))
+        res = (_lib.KmeansResult * len(ks))()
+        outs = []
+        for p, k in enumerate(ks):
+            k = int(k)
+            o = dict(n_clusters=k, labels=np.zeros(n, np.int32), clusters=np.zeros(n, np.int32), centers=np.zeros((k, d)),
+                     sizes=np.zeros(k, np.uint64), wss=np.zeros(k))
+            res[p].labels_out, res[p].clusters_out, res[p].centers_out = ptr(o["labels"]), ptr(o["clusters"]), ptr(o["centers"])
+            res[p].sizes_out, res[p].wss_out = ptr(o["sizes"]), ptr(o["wss"])
+            outs.append(o)
+        self._check(self.L.crgpu_kmeans_dev(self.h, ptr(x), n, d, ld, ptr(ks), len(ks), C.byref(a), res))
+        for p, o in enumerate(outs):
+            r = res[p]
+            o.update(inertia=r.inertia, db_score=r.db_score, fit_ms=r.fit_ms, n_iter=int(r.n_iter), strict=bool(r.strict),
+                     relocations=int(r.relocations), in_lds=bool(r.in_lds))
+        return outs
 
     def tag_moments(self, m, tag_rows, n_features=None):
         """the exact sums over the cells of x, x^2 and x y for the listed tag rows (at most 16) -> (u64[n], u64[n], u64[n, n])"""

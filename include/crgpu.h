@@ -1697,6 +1697,78 @@ int crgpu_tag_contaminants(uint32_t n_tags, uint64_t n_cells, const uint64_t *su
                            int32_t *sources_out);
 int crgpu_marginal_seed_draws(uint64_t V, double *u_out, uint64_t *first_cell_out);
 
+/* ---- k-means clustering of a dense projection: RUN_KMEANS --------------------------------------------------------------------------
+ * run_kmeans (lib/python/cellranger/analysis/kmeans.py:67-95) on a dense cells x PCs matrix, which any PCA can supply: scikit-learn
+ * 1.7.2's KMeans(n_clusters = K, random_state = seed) -- other releases seed or average differently and are out of scope --, then
+ * compute_db_index (kmeans.py:29-64) and relabel_by_size (clustering.py:137-146).  One call fits a LIST of K values on one matrix.
+ *   crgpu_kmeans_dev             x: host f64, row i at x + i * ld, ld >= d (a view of the first d columns of a wider matrix); ks: host
+ *                                u32[n_ks], distinct; results: n_ks structs whose *_out pointers the caller has set (NULL = not wanted).
+ *                                1 <= K <= CRGPU_KM_MAX_K, 1 <= d <= CRGPU_KM_MAX_D, K <= n < 2^31, 1 <= n_ks <= CRGPU_KM_MAX_LIST,
+ *                                max_iter >= 1, every value finite; anything else is CRGPU_EINVAL (scikit-learn raises for n < K).
+ *       centring                 X_mean = the sum over the rows in row order / n; the fit works on X - X_mean; squared norms in
+ *                                dimension order; tol = tol_factor * mean(np.var(X, axis = 0))
+ *       seeding                  _kmeans_plusplus under RandomState(seed): the first centre is choice(n, p = 1 / n); each further one
+ *                                draws 2 + int(log K) values u * potential, located in the cumulative sum of the closest squared
+ *                                distances (cell order, clipped to n - 1); per candidate the potential of min(closest, distance to
+ *                                it); the smallest wins, the first on a tie.  The host draws the doubles, the device does the rest;
+ *                                its cumulative sum is taken in three levels of 64, so its rounding is not numpy's serial one.
+ *                                With init[p] != NULL (scikit-learn's init = array, n_init = 1) the centres are init[p] - X_mean
+ *                                and nothing is drawn.
+ *       Lloyd                    label = argmin ||c||^2 - 2 x.c, the dot product in dimension order, the first centre on a tie; sums
+ *                                and weights per cluster; empty clusters relocated as _relocate_empty_clusters_dense does -- the
+ *                                points farthest from their own old centre, ordered by (distance, index) descending, go to the
+ *                                empty clusters in ascending order; nothing when the largest distance is 0 --; averages; shift per
+ *                                cluster = sqrt(sum d^2); stop when the labels repeat (strict), when sum(shift^2) <= tol or after
+ *                                max_iter rounds (both followed by one relabel); inertia = the direct sum of ||x - c_label||^2;
+ *                                X_mean is added back to the centres
+ *       QUIRKS kept              a potential of 0 sends every draw to cell 0; a cluster of weight 0 takes the row of the first
+ *                                heaviest cluster as _average_centers meets it (averaged when that cluster's index is lower, the
+ *                                raw sum otherwise); shift and inertia add four dimensions at a time
+ *       on the device            a round is four launches for the whole list; the assign pass reads a tile of 256 cells once for
+ *                                every K, the other kernels take the position in the list as their second grid dimension; a K that
+ *                                has stopped does no work.  The stop rule is latched on the device and read once per
+ *                                CRGPU_KM_BATCH=<n> rounds (environment, at creation; default 8).  The centres of one K sit in LDS
+ *                                while K * d <= CRGPU_KM_LDS_CENTERS=<n> (environment, at creation; default and at most 4096, 0 =
+ *                                always device memory).  Every sum over cells is 256-cell partials in a slab of plain stores, added
+ *                                in an order that depends on n alone: no floating-point atomic; no result depends on the run, on
+ *                                either switch, or on the other values of the list.  f64, unfused.
+ *   crgpu_kmeans_result          labels_out i32[n] (scikit-learn's labels_); clusters_out i32[n] (1-based, relabel_by_size: the
+ *                                largest cluster is 1, equal sizes keep their order); centers_out f64[K x d]; sizes_out u64[K];
+ *                                wss_out f64[K]; inertia; db_score; fit_ms (host time of the whole call, the same in every result);
+ *                                n_iter = n_iter_; strict = 1 when the labels repeated; relocations = points moved to empty
+ *                                clusters; in_lds
+ *   crgpu_kmeans_db_index        compute_db_index from its sums, host only: wss and counts per cluster on the UNCENTRED matrix and
+ *                                the centres as returned; a count of 0 becomes 1; scatter = sqrt(wss / count); centre distances
+ *                                below 1e-3 become 1e-3; the score is the mean of the row maxima of (s_i + s_j) / d_ij off the diagonal
+ *   crgpu_kmeans_seed_draws      test hook, not a stable interface: u_out f64[1 + (K - 1)(2 + int(log K))] = the doubles of
+ *                                RandomState(seed) in the order the seeding uses them; *first_cell_out = the cell choice() gives
+ * NOT covered: the num_bcs subsample (the caller passes the rows), the H5 and CSV writers, sample_weight, Elkan, sparse input,
+ * n_init > 1, float32, and PCA itself. */
+#define CRGPU_KM_MAX_K 64
+#define CRGPU_KM_MAX_D 128
+#define CRGPU_KM_MAX_LIST 64
+struct crgpu_kmeans_args {
+    const double **init;       /* NULL, or n_ks pointers: init[p] NULL or f64[ks[p] x d] */
+    double tol_factor;         /* 1e-4 */
+    uint32_t seed, max_iter;   /* 0, 300 */
+};
+typedef struct crgpu_kmeans_args crgpu_kmeans_args;
+struct crgpu_kmeans_result {
+    int32_t *labels_out;
+    int32_t *clusters_out;
+    double *centers_out;
+    uint64_t *sizes_out;
+    double *wss_out;
+    double inertia, db_score, fit_ms;
+    uint32_t n_iter, strict;
+    uint32_t relocations, in_lds;
+};
+typedef struct crgpu_kmeans_result crgpu_kmeans_result;
+int crgpu_kmeans_dev(crgpu_ctx *ctx, const double *x, uint64_t n, uint32_t d, uint64_t ld, const uint32_t *ks, uint32_t n_ks,
+                     const crgpu_kmeans_args *args, crgpu_kmeans_result *results);
+int crgpu_kmeans_db_index(uint32_t k, uint32_t d, const double *centers, const double *wss, const uint64_t *counts, double *score);
+int crgpu_kmeans_seed_draws(uint32_t seed, uint64_t n, uint32_t k, double *u_out, uint64_t *first_cell_out);
+
 /* ---- synthetic workloads (bench / tests) ---------------------------------------------
  * Counter-based integer generator: read i of a given seed is identical on the host and on the
  * device.  Tables are host arrays built by cellranger_amd.synth. */

@@ -1270,6 +1270,57 @@ inline TagContaminants tag_contaminants(Context &ctx, const crgpu_matrix_dev *fi
     return out;
 }
 
+// ---- k-means clustering of a dense projection (RUN_KMEANS) -----------------------------------------------------------------------------------
+static_assert(sizeof(crgpu_kmeans_args) == 24, "crgpu_kmeans_args changed: bump CRGPU_ABI_VERSION and every binding");
+static_assert(sizeof(crgpu_kmeans_result) == 80, "crgpu_kmeans_result changed: bump CRGPU_ABI_VERSION and every binding");
+struct KmeansFit {
+    uint32_t n_clusters = 0, n_iter = 0, relocations = 0;
+    bool strict = false, in_lds = false;
+    double inertia = 0.0, db_score = 0.0, fit_ms = 0.0;
+    std::vector<int32_t> labels;     // scikit-learn's labels_
+    std::vector<int32_t> clusters;   // 1-based, the largest cluster first (relabel_by_size)
+    std::vector<double> centers;     // n_clusters x d
+    std::vector<uint64_t> sizes;
+    std::vector<double> wss;
+};
+/// crgpu_kmeans_dev for a list of distinct K on x (n rows of stride ld, the first d columns); inits: empty, or per K an empty vector
+/// (k-means++) or K x d centres (scikit-learn's init = array)
+inline std::vector<KmeansFit> kmeans(Context &ctx, const double *x, uint64_t n, uint32_t d, uint64_t ld, const std::vector<uint32_t> &ks, uint32_t seed = 0,
+                                     const std::vector<std::vector<double>> &inits = {}, uint32_t max_iter = 300, double tol_factor = 1e-4) {
+    const size_t m = ks.size();
+    if (!inits.empty() && inits.size() != m) throw Error(CRGPU_EINVAL, "kmeans: one init (or an empty vector) per K");
+    std::vector<const double *> ip(m, nullptr);
+    for (size_t p = 0; p < inits.size(); p++) {
+        if (inits[p].empty()) continue;
+        if (inits[p].size() != (size_t)ks[p] * d) throw Error(CRGPU_EINVAL, "kmeans: an init is K x d");
+        ip[p] = inits[p].data();
+    }
+    crgpu_kmeans_args a = {inits.empty() ? nullptr : ip.data(), tol_factor, seed, max_iter};
+    std::vector<KmeansFit> out(m);
+    std::vector<crgpu_kmeans_result> res(m);
+    for (size_t p = 0; p < m; p++) {
+        KmeansFit &f = out[p];
+        f.n_clusters = ks[p];
+        f.labels.assign(n, 0), f.clusters.assign(n, 0), f.centers.assign((size_t)ks[p] * d, 0.0), f.sizes.assign(ks[p], 0), f.wss.assign(ks[p], 0.0);
+        res[p] = crgpu_kmeans_result{f.labels.data(), f.clusters.data(), f.centers.data(), f.sizes.data(), f.wss.data(), 0.0, 0.0, 0.0, 0, 0, 0, 0};
+    }
+    ctx.check(crgpu_kmeans_dev(ctx.get(), x, n, d, ld, ks.data(), (uint32_t)m, &a, res.data()));
+    for (size_t p = 0; p < m; p++) {
+        KmeansFit &f = out[p];
+        f.inertia = res[p].inertia, f.db_score = res[p].db_score, f.fit_ms = res[p].fit_ms;
+        f.n_iter = res[p].n_iter, f.relocations = res[p].relocations, f.strict = res[p].strict != 0, f.in_lds = res[p].in_lds != 0;
+    }
+    return out;
+}
+/// compute_db_index from the per-cluster sums
+inline double kmeans_db_index(uint32_t k, uint32_t d, const std::vector<double> &centers, const std::vector<double> &wss, const std::vector<uint64_t> &counts) {
+    double score = 0.0;
+    if (centers.size() != (size_t)k * d || wss.size() != k || counts.size() != k) throw Error(CRGPU_EINVAL, "kmeans_db_index: centers is k x d, wss and counts k");
+    const int rc = crgpu_kmeans_db_index(k, d, centers.data(), wss.data(), counts.data(), &score);
+    if (rc != CRGPU_OK) throw Error(rc, "kmeans_db_index");
+    return score;
+}
+
 // ---- protein aggregates of an antibody / antigen well; the closing filters of a cell call ---------------------------------------------
 static_assert(sizeof(crgpu_aggregates_info) == 48, "crgpu_aggregates_info changed: bump CRGPU_ABI_VERSION and every binding");
 /// int(np.round(n_signal * _calculate_fraction_to_use(n_signal)))
