@@ -217,7 +217,8 @@ int crgpu_combine_segments_dev(crgpu_ctx *ctx, int lib, const uint32_t *const *d
 /* ---- packing (ASCII -> 2-bit + N-flagged quality) ----------------------------------------------
  * Device-side part of RnaProcessor::process_read's slicing (cr_types/src/rna_read.rs:103-138,
  * 352-366): seq/qual are n x len ASCII (device).  packed_out n x u32, qualn_out n x len bytes,
- * flags_inout (nullable) n bytes: CRGPU_FLAG_CB_HAS_N is OR-ed in when a base is N. */
+ * flags_inout (nullable) n bytes: CRGPU_FLAG_CB_HAS_N is OR-ed in when a base is N.  Every byte other than 'A', 'C',
+ * 'G', 'T' is an N here (lower case, IUPAC letters, 0); qualities above 127 are stored as 127. */
 int crgpu_pack_dev(crgpu_ctx *ctx, const uint8_t *d_seq, const uint8_t *d_qual, uint64_t n, uint32_t len,
                    uint32_t *d_packed_out, uint8_t *d_qualn_out, uint8_t *d_flags_inout);
 /* The same from whole read rows as the FASTQ holds them (R1: row_stride bytes of sequence / quality per read): packs
@@ -257,6 +258,8 @@ int crgpu_shard_metrics_dev(crgpu_ctx *ctx, const uint32_t *d_cb, const uint8_t 
  *                                 read2_*, i1_*, i2_*: make_shard_metrics.rs:266-279,355-392), as counts;
  *   crgpu_homopolymer_metrics_dev {A,C,G,T}_perfect_homopolymer (:281-300): reads whose R1 OR R2 (d_r2_rows nullable) holds
  *                                 run_len (HOMOPOLYMER_LENGTH = 15) equal bases in a row; out4 = counts for A, C, G, T.
+ * Only the letter 'N' counts as an N base here (crgpu_pack_dev takes every byte other than A, C, G, T for one); lengths
+ * above row_stride are cut to it.
  * PatternCheck lives in an un-vendored crate: "the pattern occurs in the read" is the reading taken; parity unpinned. */
 typedef struct {
     uint64_t n_bases, bases;      /* frac_n_bases */
@@ -272,7 +275,8 @@ int crgpu_homopolymer_metrics_dev(crgpu_ctx *ctx, const uint8_t *d_r1_rows, uint
  * of d_seq_rows / d_qual_rows (row_stride bytes each, zero-padded; longer reads are cut and reported through d_len),
  * d_len_out[r] (nullable) = its length in the file.  A record whose header does not start with '@', whose third line does
  * not start with '+' or whose sequence and quality differ in length makes the call fail (CRGPU_EINVAL), as does a line
- * count that is not a multiple of four.  max_records: room in the row buffers (CRGPU_ERANGE beyond). */
+ * count that is not a multiple of four.  An empty header or third line fails likewise; empty sequence and quality lines
+ * are accepted (length 0).  On failure *n_records_out is 0.  max_records: room in the row buffers (CRGPU_ERANGE beyond). */
 int crgpu_fastq_to_rows_dev(crgpu_ctx *ctx, const uint8_t *d_text, uint64_t n_bytes, uint32_t row_stride, uint64_t max_records,
                             uint8_t *d_seq_rows, uint8_t *d_qual_rows, uint32_t *d_len_out, uint64_t *n_records_out);
 
