@@ -2011,14 +2011,13 @@ static int correct_dev_impl(crgpu_ctx *ctx, const uint32_t *d_cb, const uint8_t 
     CR_REQUIRE(ctx, ctx->canon_set, CRGPU_ESTATE, "crgpu_correct: no whitelist set");
     CR_REQUIRE(ctx, ctx->n_segments == 0, CRGPU_ESTATE,
                "crgpu_correct: this context holds a segmented barcode space; run the barcode stage on the segment contexts");
+    ctx->k2_sorted_reads = ctx->k2_record_reads = 0;  // which records path this call takes, if any (crgpu_get_stat)
     if (n == 0) return CRGPU_OK;
     CR_REQUIRE(ctx, d_cb && d_idx_inout, CRGPU_EINVAL, "crgpu_correct: NULL buffer");
     CR_REQUIRE(ctx, n < 0xFFFFFFFFull, CRGPU_ERANGE, "crgpu_correct: batches are limited to 2^32-2 reads");
     cr_dense_drop(ctx);  // the CORRECTED table changes
     if (ctx->cb_len == 16 && d_qualn)
         CR_REQUIRE(ctx, (uintptr_t)d_qualn % 16 == 0, CRGPU_EINVAL, "crgpu_correct: quality buffer must be 16-byte aligned");
-    // NotNan::try_from(threshold).ok()? (corrector.rs:152): a NaN threshold corrects nothing
-    if (ctx->confidence_threshold != ctx->confidence_threshold) return CRGPU_OK;
     // the records K1 left for exactly these buffers (consumed here: a second call scans idx again) also say which
     // library the call is about; otherwise the flag bytes do
     MissRecords *recp = nullptr;
@@ -2042,6 +2041,12 @@ static int correct_dev_impl(crgpu_ctx *ctx, const uint32_t *d_cb, const uint8_t 
     CrTimer t(ctx, CRGPU_T_CORRECT, n);
     CR_HIP(ctx, hipMemsetAsync(n_miss, 0, sizeof(unsigned long long), ctx->stream));
     if (d_corrected_out) CR_HIP(ctx, hipMemsetAsync(d_corrected_out, 0, n, ctx->stream));
+    // NotNan::try_from(threshold).ok()? (corrector.rs:152): a NaN threshold corrects nothing -- the flags say so, and the
+    // records of pass A are used up as by any other call
+    if (ctx->confidence_threshold != ctx->confidence_threshold) {
+        if (use_rec) cr_drop_miss_records(ctx, rec);
+        return CRGPU_OK;
+    }
     // expected_errors < f64::MAX is always true for a finite sum: skip the sum for the default
     const bool check_expected = d_qualn && !fake_quals && ctx->max_expected_errors < 1.7976931348623157e308;
     const K2Params P{d_qualn, ctx->cb_len, ctx->d_ptab, ctx->max_expected_errors, ctx->confidence_threshold, check_expected,
@@ -2074,6 +2079,7 @@ static int correct_dev_impl(crgpu_ctx *ctx, const uint32_t *d_cb, const uint8_t 
             hipLaunchKernelGGL(k_region_offsets, dim3(1), dim3(1024), 0, ctx->stream, rec.d_count, rec.regions, d_o);
             rc = crgpu_memcpy_d2h(ctx, &total, d_o + rec.regions, sizeof(total));  // 0 when the records overflowed
         }
+        if (rc == CRGPU_OK) ctx->k2_sorted_reads = total;
         if (rc == CRGPU_OK && total) {
             const uint64_t bytes = (uint64_t)total * sizeof(uint32_t);
             if (dmalloc(ctx, k, bytes) != CRGPU_OK || dmalloc(ctx, v, bytes) != CRGPU_OK || dmalloc(ctx, kt, bytes) != CRGPU_OK ||
@@ -2141,6 +2147,7 @@ static int correct_dev_impl(crgpu_ctx *ctx, const uint32_t *d_cb, const uint8_t 
         if (hipGetLastError() != hipSuccess) rc = cr_fail(ctx, CRGPU_EHIP, "crgpu_correct: launch failed");
         uint32_t total = 0;
         if (rc == CRGPU_OK && staged) rc = crgpu_memcpy_d2h(ctx, &total, d_off + rec.regions, sizeof(total));
+        if (rc == CRGPU_OK) ctx->k2_record_reads = staged ? total : ~0ull;  // (the atomics fallback reads nothing back)
         if (rc == CRGPU_OK && staged && total) {
             WlViewSet vc = vs;
             vc.v[0].valid = vc.v[0].corrected;  // k_hist_buckets adds to `valid` of the call's library (v[0])

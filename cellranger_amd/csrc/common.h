@@ -228,6 +228,7 @@ struct crgpu_ctx {
     uint64_t rl_counts_from_finish = 0;    // count calls whose run-length pass skipped its count launch (tile counts from the finishing step)
     uint64_t sort_refinished = 0;          // sorts whose finishing pass met a run too long for it and that were redone on all bits
     uint64_t k1_split_rounds = 0;          // table rounds of K1 whose histogram was split (table slots in LDS + staged cold hits)
+    uint64_t k2_sorted_reads = 0, k2_record_reads = 0;  // recorded misses of the last pass B: in barcode order / in record order
     uint64_t feature_resumed_reads = 0;    // captures a pass with a distribution took from the records of the pass without one
     uint64_t feature_fast_launches = 0;    // crgpu_extract_features_dev calls that took k_extract_tethered_lds
     uint64_t feature_reads_requeued = 0;   // reads k_extract_features handed to the wide-map launch

@@ -503,6 +503,12 @@ extern "C" int crgpu_get_stat(crgpu_ctx *ctx, int which, uint64_t *value_out) {
         case CRGPU_STAT_K1_SPLIT_ROUNDS:
             *value_out = ctx->k1_split_rounds;
             return CRGPU_OK;
+        case CRGPU_STAT_K2_SORTED_READS:
+            *value_out = ctx->k2_sorted_reads;
+            return CRGPU_OK;
+        case CRGPU_STAT_K2_RECORD_READS:
+            *value_out = ctx->k2_record_reads;
+            return CRGPU_OK;
         case CRGPU_STAT_COMM_BYTES_C1:
         case CRGPU_STAT_COMM_BYTES_C2:
         case CRGPU_STAT_COMM_BYTES_C3:

@@ -132,6 +132,9 @@ int crgpu_invalidate(crgpu_ctx *ctx);
 #define CRGPU_STAT_PROBE_SEGMENTS_WORKGROUP 13 /* ... in LDS, one workgroup each (<= 32768 molecules) */
 #define CRGPU_STAT_PROBE_SEGMENTS_GLOBAL 14    /* ... through the device radix sort (larger ones; all above CRGPU_PROBE_SEG_CAP) */
 #define CRGPU_STAT_RL_COUNTS_FROM_FINISH 15 /* count calls whose run-length pass took its tile counts from the finishing step of the sort */
+#define CRGPU_STAT_K2_SORTED_READS 16 /* recorded misses the last crgpu_correct* call worked off in barcode order (0: that path was not taken) */
+#define CRGPU_STAT_K2_RECORD_READS 17 /* ... in record order (0: not taken, or the records had overflowed and the scan took over; all ones: taken,
+                                       * but the number was not read back -- lists of more than 31 x 32768 barcodes count by atomics) */
 int crgpu_get_stat(crgpu_ctx *ctx, int which, uint64_t *value_out);
 /* ctx may be NULL: returns the message of the last failed crgpu_create on this thread. */
 const char *crgpu_last_error(const crgpu_ctx *ctx);
