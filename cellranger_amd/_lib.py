@@ -334,7 +334,27 @@ class KmeansResult(C.Structure):
         (n, C.c_uint32) for n in ("n_iter", "strict", "relocations", "in_lds")]
 
 
+class SseqArgs(C.Structure):
+    """crgpu_sseq_args"""
+    _fields_ = [(n, C.c_uint32) for n in ("n_features", "wave_min", "wg_min", "reserved")]
+
+
+class SseqParamsInfo(C.Structure):
+    """crgpu_sseq_params_info"""
+    _fields_ = [(n, C.c_void_p) for n in ("size_factors_out", "mean_out", "var_out", "phi_mm_out", "phi_out", "use_out")] + [
+        ("zeta_hat", C.c_double), ("delta", C.c_double), ("n_cells", C.c_uint64), ("n_features", C.c_uint32), ("n_used", C.c_uint32)]
+
+
+class SseqResult(C.Structure):
+    """crgpu_sseq_result"""
+    _fields_ = [(n, C.c_void_p) for n in ("sums_in_out", "sums_out_out", "norm_mean_in_out", "norm_mean_out_out", "log2_fold_change_out", "p_values_out",
+                                           "adjusted_p_values_out", "below_median_out", "s_a_out", "s_b_out", "n_exact_out", "n_asymptotic_out")] + [
+        (n, C.c_uint64) for n in ("n_terms", "n_short", "n_wave", "n_workgroup")] + [
+        (n, C.c_double) for n in ("ms_sums", "ms_exact", "ms_asymptotic", "ms_bh")]
+
+
 KM_MAX_K, KM_MAX_D, KM_MAX_LIST = 64, 128, 64
+SSEQ_MAX_K, SSEQ_BIG_COUNT = 4096, 900
 MC_INITS, MC_SKIPPED, MC_FITTED = 10, 0, 1
 JIBES_MAX_TAGS, JIBES_MAX_K_LETS, JIBES_MAX_STATES, JIBES_NEAR_ZERO, JIBES_CANT_CONVERGE = 16, 3, 970, 12, 1
 JIBES_EXCLUDE_BLANKS, JIBES_NO_CONFIDENCE = 1, 2
@@ -501,6 +521,11 @@ SYMBOLS = {
     "crgpu_kmeans_dev": (_i, [_vp, _vp, _u64, _u32, _u64, _vp, _u32, C.POINTER(KmeansArgs), C.POINTER(KmeansResult)]),
     "crgpu_kmeans_db_index": (_i, [_u32, _u32, _vp, _vp, _vp, C.POINTER(_dbl)]),
     "crgpu_kmeans_seed_draws": (_i, [_u32, _u64, _u32, _vp, C.POINTER(_u64)]),
+    "crgpu_sseq_params_dev": (_i, [_vp, C.POINTER(MatrixDevView), C.POINTER(SseqArgs), C.POINTER(_vp)]),
+    "crgpu_sseq_params_free": (None, [_vp, _vp]),
+    "crgpu_sseq_params_get": (_i, [_vp, _vp, C.POINTER(SseqParamsInfo)]),
+    "crgpu_sseq_diffexp_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _vp, _u32, C.POINTER(SseqArgs), C.POINTER(SseqResult)]),
+    "crgpu_sseq_adjust_bh": (_i, [_vp, _u64, _vp]),
     "crgpu_aggregate_min_antibodies": (_i, [_u32, C.POINTER(_u32)]),
     "crgpu_antigen_outlier_threshold": (_i, [_vp, _u32, C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_dbl)]),
     "crgpu_aggregates_by_counts_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, _u32, _vp, _vp, _u32, C.POINTER(_u32),

@@ -347,6 +347,41 @@ const std::vector<AbiStruct> &abi_table() {
               ABI_F(crgpu_kmeans_result, strict),
               ABI_F(crgpu_kmeans_result, relocations),
               ABI_F(crgpu_kmeans_result, in_lds)),
+        ABI_S(crgpu_sseq_args, ABI_F(crgpu_sseq_args, n_features),
+              ABI_F(crgpu_sseq_args, wave_min),
+              ABI_F(crgpu_sseq_args, wg_min),
+              ABI_F(crgpu_sseq_args, reserved)),
+        ABI_S(crgpu_sseq_params_info, ABI_F(crgpu_sseq_params_info, size_factors_out),
+              ABI_F(crgpu_sseq_params_info, mean_out),
+              ABI_F(crgpu_sseq_params_info, var_out),
+              ABI_F(crgpu_sseq_params_info, phi_mm_out),
+              ABI_F(crgpu_sseq_params_info, phi_out),
+              ABI_F(crgpu_sseq_params_info, use_out),
+              ABI_F(crgpu_sseq_params_info, zeta_hat),
+              ABI_F(crgpu_sseq_params_info, delta),
+              ABI_F(crgpu_sseq_params_info, n_cells),
+              ABI_F(crgpu_sseq_params_info, n_features),
+              ABI_F(crgpu_sseq_params_info, n_used)),
+        ABI_S(crgpu_sseq_result, ABI_F(crgpu_sseq_result, sums_in_out),
+              ABI_F(crgpu_sseq_result, sums_out_out),
+              ABI_F(crgpu_sseq_result, norm_mean_in_out),
+              ABI_F(crgpu_sseq_result, norm_mean_out_out),
+              ABI_F(crgpu_sseq_result, log2_fold_change_out),
+              ABI_F(crgpu_sseq_result, p_values_out),
+              ABI_F(crgpu_sseq_result, adjusted_p_values_out),
+              ABI_F(crgpu_sseq_result, below_median_out),
+              ABI_F(crgpu_sseq_result, s_a_out),
+              ABI_F(crgpu_sseq_result, s_b_out),
+              ABI_F(crgpu_sseq_result, n_exact_out),
+              ABI_F(crgpu_sseq_result, n_asymptotic_out),
+              ABI_F(crgpu_sseq_result, n_terms),
+              ABI_F(crgpu_sseq_result, n_short),
+              ABI_F(crgpu_sseq_result, n_wave),
+              ABI_F(crgpu_sseq_result, n_workgroup),
+              ABI_F(crgpu_sseq_result, ms_sums),
+              ABI_F(crgpu_sseq_result, ms_exact),
+              ABI_F(crgpu_sseq_result, ms_asymptotic),
+              ABI_F(crgpu_sseq_result, ms_bh)),
     };
     return t;
 }

@@ -10,3 +10,4 @@
 #include "matrix_summary.h"
 #include "multigenome.h"
 #include "rtl_tags.h"
+#include "sseq.h"

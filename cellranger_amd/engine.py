@@ -223,6 +223,35 @@ class MatrixDev:
             pass
 
 
+class SseqParams:
+    """crgpu_sseq_params: the sSeq parameters of one matrix, resident on the device (Context.sseq_params)"""
+
+    def __init__(self, ctx, h, n_cells, n_features):
+        self.ctx, self._h, self.n_cells, self.n_features = ctx, h, n_cells, n_features
+
+    def download(self):
+        """-> dict(size_factors f64[N], mean_g, var_g, phi_mm_g, phi_g f64[G], use_g bool[G], zeta_hat, delta, n_used)"""
+        N, G = self.n_cells, self.n_features
+        o = dict(size_factors=np.zeros(N), mean_g=np.zeros(G), var_g=np.zeros(G), phi_mm_g=np.zeros(G), phi_g=np.zeros(G))
+        use = np.zeros(G, np.uint8)
+        info = _lib.SseqParamsInfo(size_factors_out=ptr(o["size_factors"]), mean_out=ptr(o["mean_g"]), var_out=ptr(o["var_g"]),
+                                   phi_mm_out=ptr(o["phi_mm_g"]), phi_out=ptr(o["phi_g"]), use_out=ptr(use))
+        self.ctx._check(self.ctx.L.crgpu_sseq_params_get(self.ctx.h, self._h, C.byref(info)))
+        o.update(use_g=use != 0, zeta_hat=info.zeta_hat, delta=info.delta, n_used=int(info.n_used))
+        return o
+
+    def free(self):
+        if self._h is not None and self.ctx.h:
+            self.ctx.L.crgpu_sseq_params_free(self.ctx.h, self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class CellCall:
     """Result of Context.call_cells_ordmag: `cols` = the called columns (DeviceArray of u64, ascending positions in the count
     vector / the matrix the counts came from), `n_cells`, `metrics` = crgpu_ordmag_result as a dict (BarcodeFilterResults of
@@ -1106,6 +1135,48 @@ def run_kmeans(ctx, projection, max_clusters=10, min_clusters=2, seed=0, num_pcs
     return out
 
 
+def sseq_adjust_bh(p):
+    """adjust_pvalue_bh (crgpu_sseq_adjust_bh, host only): Benjamini-Hochberg adjusted p-values in the order of p"""
+    p = np.ascontiguousarray(p, dtype=np.float64)
+    q = np.zeros(len(p))
+    rc = _lib.load().crgpu_sseq_adjust_bh(ptr(p), len(p), ptr(q))
+    if rc != 0:
+        raise _lib.CrgpuError(rc, "crgpu_sseq_adjust_bh")
+    return q
+
+
+def differential_expression_header(n_clusters, cluster_names=None):
+    """the header of differential_expression.csv as save_differential_expression_csv writes it: two feature columns, then three per
+    cluster (cluster_names: the perturbation names of MEASURE_PERTURBATIONS' tables)"""
+    header = ["Feature ID", "Feature Name"]
+    for i in range(n_clusters):
+        if cluster_names is None:
+            header += ["Cluster %d Mean Counts" % (i + 1), "Cluster %d Log2 fold change" % (i + 1), "Cluster %d Adjusted p value" % (i + 1)]
+        else:
+            header += ["Perturbation %s, Mean Counts" % cluster_names[i], "Perturbation %s, Log2 fold change" % cluster_names[i],
+                       "Perturbation %s, Adjusted p value" % cluster_names[i]]
+    return header
+
+
+def run_differential_expression(ctx, m, clusterings, params=None, n_features=None):
+    """RUN_DIFFERENTIAL_EXPRESSION for one library type: m = the filtered MatrixDev restricted to that type's rows
+    (Context.select_features_dev); clusterings = {key: clusters i32[cells], 1-based} or engine.run_kmeans's dict.  The sSeq parameters
+    are computed once (or taken from params) -> {key: f64[G, 3 K]}, per cluster norm_mean_a, log2_fold_change, adjusted_p_value"""
+    own = params is None
+    if own:
+        params = ctx.sseq_params(m, n_features=n_features)
+    try:
+        out = {}
+        for key, clusters in clusterings.items():
+            if isinstance(clusters, dict):
+                clusters = clusters["clusters"]
+            out[key] = ctx.sseq_diffexp(m, params, clusters)["data"]
+        return out
+    finally:
+        if own:
+            params.free()
+
+
 def call_protospacers(ctx, filtered, guide_rows, n_features=None, report_prefix="CRISPR_"):
     """GuideAssigner on the filtered MatrixDev: guide_rows = the feature rows of the CRISPR Guide Capture library (ascending); a cell
     needs at least 3 UMIs of a guide.  -> dict(calls = MarginalCalls, metadata, metrics = the three frac_cells_with_*protospacer
@@ -1882,7 +1953,9 @@ class Context:
         mask = np.ascontiguousarray(np.asarray(feature_mask) != 0, dtype=np.uint8)
         mv = C.POINTER(_lib.MatrixDevView)()
         self._check(self.L.crgpu_select_features_dev(self.h, m._mv, ptr(mask), len(mask), C.byref(mv)))
-        return MatrixDev(self, mv)
+        out = MatrixDev(self, mv)
+        out.n_features = int(mask.sum())      # the rows that are left (Context.sseq_params reads it)
+        return out
 
     # ---- cell calling ----------------------------------------------------------------------------------
     def column_sums(self, m, feature_mask=None):
@@ -2291,6 +2364,45 @@ class Context:
             o.update(inertia=r.inertia, db_score=r.db_score, fit_ms=r.fit_ms, n_iter=int(r.n_iter), strict=bool(r.strict),
                      relocations=int(r.relocations), in_lds=bool(r.in_lds))
         return outs
+
+    def sseq_params(self, m, n_features=None):
+        """compute_sseq_params of the MatrixDev `m` (features x cells, one feature type: select_features_dev) on the device
+        (csrc/sseq.h) -> SseqParams; n_features = the rows of m (default: what select_features_dev left, else the context's n_features)"""
+        if n_features is None:
+            n_features = getattr(m, "n_features", None) or getattr(self, "n_features", None)
+            if n_features is None:
+                raise ValueError("sseq_params: pass n_features")
+        a = _lib.SseqArgs(n_features=int(n_features))
+        h = C.c_void_p()
+        self._check(self.L.crgpu_sseq_params_dev(self.h, m._mv, C.byref(a), C.byref(h)))
+        self.sseq_params_computed = getattr(self, "sseq_params_computed", 0) + 1
+        return SseqParams(self, h, m.n_barcodes, int(n_features))
+
+    def sseq_diffexp(self, m, params, clusters, n_clusters=None, wave_min=0, wg_min=0):
+        """sseq_differential_expression of every cluster (1-based labels i32[cells]) against all other cells -> dict of [K, G] arrays
+        sums_in, sums_out (u64), norm_mean_in, norm_mean_out, log2_fold_change, p_values, adjusted_p_values (f64), below_median (u8: the
+        side of the median an asymptotic test took, 255 = none), per cluster s_a, s_b, n_exact, n_asymptotic, the counts n_terms, n_short,
+        n_wave, n_workgroup, the times ms_*, and data f64[G, 3 K] = per cluster norm_mean_in, log2_fold_change, adjusted_p_values.
+        wave_min / wg_min: the class thresholds of the exact tests (0 = default); no result depends on them"""
+        lab = np.ascontiguousarray(clusters, dtype=np.int32)
+        if lab.ndim != 1 or len(lab) != m.n_barcodes:
+            raise ValueError("sseq_diffexp: one label per cell")
+        K = int(lab.max()) if n_clusters is None and len(lab) else int(n_clusters or 0)
+        G = params.n_features
+        Ka = max(K, 1)
+        o = dict(sums_in=np.zeros((Ka, G), np.uint64), sums_out=np.zeros((Ka, G), np.uint64), norm_mean_in=np.zeros((Ka, G)),
+                 norm_mean_out=np.zeros((Ka, G)), log2_fold_change=np.zeros((Ka, G)), p_values=np.zeros((Ka, G)),
+                 adjusted_p_values=np.zeros((Ka, G)), below_median=np.zeros((Ka, G), np.uint8), s_a=np.zeros(Ka), s_b=np.zeros(Ka),
+                 n_exact=np.zeros(Ka, np.uint64), n_asymptotic=np.zeros(Ka, np.uint64))
+        r = _lib.SseqResult(**{("below_median_out" if k == "below_median" else k + "_out"): ptr(v) for k, v in o.items()})
+        a = _lib.SseqArgs(n_features=G, wave_min=int(wave_min), wg_min=int(wg_min))
+        self._check(self.L.crgpu_sseq_diffexp_dev(self.h, m._mv, params._h, ptr(lab), K, C.byref(a), C.byref(r)))
+        o.update(n_clusters=K, n_terms=int(r.n_terms), n_short=int(r.n_short), n_wave=int(r.n_wave), n_workgroup=int(r.n_workgroup),
+                 ms_sums=r.ms_sums, ms_exact=r.ms_exact, ms_asymptotic=r.ms_asymptotic, ms_bh=r.ms_bh)
+        data = np.zeros((G, 3 * K))
+        data[:, 0::3], data[:, 1::3], data[:, 2::3] = o["norm_mean_in"].T, o["log2_fold_change"].T, o["adjusted_p_values"].T
+        o["data"] = data
+        return o
 
     def tag_moments(self, m, tag_rows, n_features=None):
         """the exact sums over the cells of x, x^2 and x y for the listed tag rows (at most 16) -> (u64[n], u64[n], u64[n, n])"""

@@ -1776,6 +1776,101 @@ int crgpu_kmeans_dev(crgpu_ctx *ctx, const double *x, uint64_t n, uint32_t d, ui
 int crgpu_kmeans_db_index(uint32_t k, uint32_t d, const double *centers, const double *wss, const uint64_t *counts, double *score);
 int crgpu_kmeans_seed_draws(uint32_t seed, uint64_t n, uint32_t k, double *u_out, uint64_t *first_cell_out);
 
+/* ---- sSeq differential expression of clusters: RUN_DIFFERENTIAL_EXPRESSION -------------------------------------------------------
+ * Every cluster of a labelling against all other cells, on the filtered matrix restricted to one feature type
+ * (crgpu_select_features_dev): per gene the normalised mean, the log2 fold change and the adjusted p-value -- the three columns per
+ * cluster of differential_expression.csv.  The reference (lib/rust/cr_ana/src/stages/diff_exp_stage.rs, lib/python/cellranger/
+ * analysis/diffexp.py) gives the call order, estimate_size_factors, adjust_pvalue_bh, big_count = 900, SSEQ_ZETA_QUANTILE = 0.995 and
+ * the G x 3K layout; its numerics live in the external diff_exp crate, WHOSE SOURCE WAS NOT AVAILABLE.  This stage follows the
+ * published algorithm (Yu et al. 2013, Bioinformatics 29:1275-1282) as the pure-Python diffexp.py of open-source Cell Ranger 3 had
+ * it; the restatement below is the specification (tests/sseq_numpy.py), pinned against exact arithmetic.  No parity with the crate
+ * is claimed.
+ *   parameters, once per matrix  x: features x cells, G >= 3, 2 <= N < 2^31, u32 counts
+ *       size_factors             counts_per_cell / np.median(counts_per_cell); a cell without counts is CRGPU_EINVAL
+ *       per gene                 xn = x / size_factors[c]; mean = sum xn / N; var = sum xn^2 / N - mean^2; use = var > 0
+ *                                phi_mm = max(0, (N var - mean S) / (mean^2 S)) with S = sum 1 / size_factors, 0 when not used
+ *       zeta_hat                 np.percentile(phi_mm[use], 99.5), the linear rule
+ *       delta                    (sum (phi_mm - mean(phi_mm))^2 / (G - 1)) / (sum (phi_mm - zeta_hat)^2 / (G - 2)), the sums over the
+ *                                used genes, G the number of ALL genes (a quirk that is kept)
+ *       phi                      (1 - delta) phi_mm + delta zeta_hat for a used gene when any phi_mm > 0, else 0 (delta is then
+ *                                NaN, as the Python's 0 / 0); NaN for a gene that is not used.  No used gene, or a zero
+ *                                denominator of delta while some phi_mm > 0, is CRGPU_EINVAL
+ *   per cluster (A = its cells, B = every other cell)
+ *       s_a, s_b                 the sums of the size factors, in cell order; x_a, x_b = the sums of the counts (u64)
+ *       norm_mean                x_a / s_a, x_b / s_b; log2_fold_change = log2((1 + x_a) / (1 + s_a)) - log2((1 + x_b) / (1 + s_b))
+ *       exact test               unless x_a > 900 and x_b > 900: with T = x_a + x_b, l_i = lp(i; s_a mu, phi / s_a) + lp(T - i;
+ *                                s_b mu, phi / s_b), lp(k; m, f) = lgamma(r + k) - lgamma(r) - lgamma(k + 1) + k log(m / (r + m)) +
+ *                                r log(r / (r + m)), r = 1 / f (f == 0: k log m - m - lgamma(k + 1));
+ *                                p = sum over l_i <= l_obs of exp(l_i) / sum exp(l_i), l_obs = l_(x_a).  l_i is a pure function
+ *                                of (i, T - i): with s_a == s_b the mirrored term is bit-equal and is counted too
+ *       asymptotic test          alpha = s_a mu / (1 + phi mu), beta = (s_b / s_a) alpha, med = the median of Beta(alpha, beta);
+ *                                (x_a + 0.5) / T < med: p = 2 I((x_a + 0.5) / T; alpha, beta), else p = 2 I((x_b + 0.5) / T; beta,
+ *                                alpha); not clipped
+ *       adjusted p               adjust_pvalue_bh over the used genes: q = min(1, running minimum from the largest p downwards of
+ *                                (n / rank) p); equal p get equal q.  A gene that is not used: p = adjusted p = 1
+ *   on the device                the per-gene sums go over the transposed entries (one radix sort) in column order, a wave per
+ *                                gene, lanes joined by a fixed tree; the group sums are u64 atomics.  The exact tests are the hot
+ *                                path; every test of T + 1 terms is added in ONE order that depends on T alone (term i in slot
+ *                                i % 256, slots in ascending i, joined by a fixed tree), whichever of the three kernels takes it:
+ *                                up to wave_min - 1 (at most 16) terms 16 lanes a test, from wg_min terms a workgroup a test, a
+ *                                wave a test between.  The thresholds are fields of crgpu_sseq_args, NOT environment switches, and
+ *                                change no bit of any result; nor do the run, or the other clusters of the labelling.
+ *   crgpu_sseq_params_dev        *params_out: library-owned, release with crgpu_sseq_params_free; the parameters stay on the device
+ *   crgpu_sseq_params_get        downloads what the caller set a pointer for (NULL = not wanted)
+ *   crgpu_sseq_diffexp_dev       labels: host i32[N], 1 .. n_clusters, every cluster with a cell; results [n_clusters][G] row-major
+ *                                into the pointers the caller set (NULL = not wanted); below_median_out u8: 1 / 0 = the side of
+ *                                the median an asymptotic test took, 255 = no asymptotic test
+ *   crgpu_sseq_adjust_bh         adjust_pvalue_bh on the host, no context
+ *   refused with CRGPU_EINVAL before any device work: a NULL argument, G < 3, N < 2, n_clusters < 2 or > CRGPU_SSEQ_MAX_K, a label
+ *   outside 1 .. n_clusters, an empty cluster, parameters of a matrix of another shape
+ * NOT covered: get_local_sseq_params and the pairwise comparisons of MEASURE_PERTURBATIONS, the H5 and CSV writers, PCA, parity with
+ * the diff_exp crate. */
+#define CRGPU_SSEQ_MAX_K 4096
+struct crgpu_sseq_args {
+    uint32_t n_features;   /* G: the rows of the matrix (crgpu_sseq_diffexp_dev: 0 or the G of the parameters) */
+    uint32_t wave_min;     /* exact tests of fewer terms share a wave; 0 = 17, at most 17, 1 = none */
+    uint32_t wg_min;       /* exact tests of at least this many terms take a workgroup; 0 = 4096 */
+    uint32_t reserved;
+};
+typedef struct crgpu_sseq_args crgpu_sseq_args;
+struct crgpu_sseq_params_info {
+    double *size_factors_out;   /* f64[N] */
+    double *mean_out;           /* f64[G] each */
+    double *var_out;
+    double *phi_mm_out;
+    double *phi_out;
+    uint8_t *use_out;           /* u8[G] */
+    double zeta_hat, delta;
+    uint64_t n_cells;
+    uint32_t n_features, n_used;
+};
+typedef struct crgpu_sseq_params_info crgpu_sseq_params_info;
+struct crgpu_sseq_result {
+    uint64_t *sums_in_out;              /* u64[K][G] each */
+    uint64_t *sums_out_out;
+    double *norm_mean_in_out;           /* f64[K][G] each */
+    double *norm_mean_out_out;
+    double *log2_fold_change_out;
+    double *p_values_out;
+    double *adjusted_p_values_out;
+    uint8_t *below_median_out;          /* u8[K][G] */
+    double *s_a_out;                    /* f64[K] each */
+    double *s_b_out;
+    uint64_t *n_exact_out;              /* u64[K] each */
+    uint64_t *n_asymptotic_out;
+    uint64_t n_terms;                   /* terms of all exact tests */
+    uint64_t n_short, n_wave, n_workgroup; /* exact tests per kernel */
+    double ms_sums, ms_exact, ms_asymptotic, ms_bh; /* host time of the four phases */
+};
+typedef struct crgpu_sseq_result crgpu_sseq_result;
+typedef struct crgpu_sseq_params crgpu_sseq_params;
+int crgpu_sseq_params_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const crgpu_sseq_args *args, crgpu_sseq_params **params_out);
+void crgpu_sseq_params_free(crgpu_ctx *ctx, crgpu_sseq_params *params);
+int crgpu_sseq_params_get(crgpu_ctx *ctx, const crgpu_sseq_params *params, crgpu_sseq_params_info *info);
+int crgpu_sseq_diffexp_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const crgpu_sseq_params *params, const int32_t *labels,
+                           uint32_t n_clusters, const crgpu_sseq_args *args, crgpu_sseq_result *result);
+int crgpu_sseq_adjust_bh(const double *p, uint64_t n, double *q_out);
+
 /* ---- synthetic workloads (bench / tests) ---------------------------------------------
  * Counter-based integer generator: read i of a given seed is identical on the host and on the
  * device.  Tables are host arrays built by cellranger_amd.synth. */

@@ -1321,6 +1321,81 @@ inline double kmeans_db_index(uint32_t k, uint32_t d, const std::vector<double> 
     return score;
 }
 
+// ---- sSeq differential expression of clusters (RUN_DIFFERENTIAL_EXPRESSION) -----------------------------------------------------------------
+static_assert(sizeof(crgpu_sseq_args) == 16, "crgpu_sseq_args changed: bump CRGPU_ABI_VERSION and every binding");
+static_assert(sizeof(crgpu_sseq_params_info) == 80, "crgpu_sseq_params_info changed: bump CRGPU_ABI_VERSION and every binding");
+static_assert(sizeof(crgpu_sseq_result) == 160, "crgpu_sseq_result changed: bump CRGPU_ABI_VERSION and every binding");
+/// adjust_pvalue_bh on the host
+inline std::vector<double> sseq_adjust_bh(const std::vector<double> &p) {
+    std::vector<double> q(p.size());
+    const int rc = crgpu_sseq_adjust_bh(p.data(), p.size(), q.data());
+    if (rc != CRGPU_OK) throw Error(rc, "sseq_adjust_bh");
+    return q;
+}
+struct SseqParamValues {
+    std::vector<double> size_factors, mean, var, phi_mm, phi;  // phi: NaN for a gene that is not used
+    std::vector<uint8_t> use;
+    double zeta_hat = 0.0, delta = 0.0;
+    uint32_t n_used = 0;
+};
+/// crgpu_sseq_params of one matrix (features x cells, one feature type), resident on the device
+class SseqParams {
+public:
+    SseqParams(Context &ctx, const crgpu_matrix_dev *m, uint32_t n_features) : ctx_(ctx), n_cells_(m ? m->n_barcodes : 0), n_features_(n_features) {
+        crgpu_sseq_args a = {n_features, 0, 0, 0};
+        ctx.check(crgpu_sseq_params_dev(ctx.get(), m, &a, &p_));
+    }
+    ~SseqParams() { crgpu_sseq_params_free(ctx_.get(), p_); }
+    SseqParams(const SseqParams &) = delete;
+    SseqParams &operator=(const SseqParams &) = delete;
+    const crgpu_sseq_params *get() const { return p_; }
+    uint64_t n_cells() const { return n_cells_; }
+    uint32_t n_features() const { return n_features_; }
+    SseqParamValues download() const {
+        SseqParamValues v;
+        v.size_factors.assign(n_cells_, 0.0), v.mean.assign(n_features_, 0.0), v.var.assign(n_features_, 0.0), v.phi_mm.assign(n_features_, 0.0);
+        v.phi.assign(n_features_, 0.0), v.use.assign(n_features_, 0);
+        crgpu_sseq_params_info info = {v.size_factors.data(), v.mean.data(), v.var.data(), v.phi_mm.data(), v.phi.data(), v.use.data(), 0.0, 0.0, 0, 0, 0};
+        ctx_.check(crgpu_sseq_params_get(ctx_.get(), p_, &info));
+        v.zeta_hat = info.zeta_hat, v.delta = info.delta, v.n_used = info.n_used;
+        return v;
+    }
+
+private:
+    Context &ctx_;
+    crgpu_sseq_params *p_ = nullptr;
+    uint64_t n_cells_;
+    uint32_t n_features_;
+};
+struct SseqDiffexp {
+    uint32_t n_clusters = 0, n_features = 0;
+    std::vector<uint64_t> sums_in, sums_out;  // [K][G]
+    std::vector<double> norm_mean_in, norm_mean_out, log2_fold_change, p_values, adjusted_p_values;  // [K][G]
+    std::vector<uint8_t> below_median;        // [K][G]: 1 / 0 = the side an asymptotic test took, 255 = none
+    std::vector<double> s_a, s_b;             // [K]
+    std::vector<uint64_t> n_exact, n_asymptotic;
+    uint64_t n_terms = 0, n_short = 0, n_wave = 0, n_workgroup = 0;
+};
+/// crgpu_sseq_diffexp_dev: every cluster of the 1-based labels against all other cells; wave_min / wg_min = the class thresholds of the
+/// exact tests (0 = default), which change no result
+inline SseqDiffexp sseq_diffexp(Context &ctx, const crgpu_matrix_dev *m, const SseqParams &params, const std::vector<int32_t> &labels, uint32_t n_clusters,
+                                uint32_t wave_min = 0, uint32_t wg_min = 0) {
+    if (!m || labels.size() != m->n_barcodes) throw Error(CRGPU_EINVAL, "sseq_diffexp: one label per cell");
+    SseqDiffexp o;
+    o.n_clusters = n_clusters, o.n_features = params.n_features();
+    const size_t K = n_clusters ? n_clusters : 1, KG = K * params.n_features();
+    o.sums_in.assign(KG, 0), o.sums_out.assign(KG, 0), o.norm_mean_in.assign(KG, 0.0), o.norm_mean_out.assign(KG, 0.0), o.log2_fold_change.assign(KG, 0.0);
+    o.p_values.assign(KG, 0.0), o.adjusted_p_values.assign(KG, 0.0), o.below_median.assign(KG, 0), o.s_a.assign(K, 0.0), o.s_b.assign(K, 0.0);
+    o.n_exact.assign(K, 0), o.n_asymptotic.assign(K, 0);
+    crgpu_sseq_result r = {o.sums_in.data(), o.sums_out.data(), o.norm_mean_in.data(), o.norm_mean_out.data(), o.log2_fold_change.data(), o.p_values.data(),
+                           o.adjusted_p_values.data(), o.below_median.data(), o.s_a.data(), o.s_b.data(), o.n_exact.data(), o.n_asymptotic.data(),
+                           0, 0, 0, 0, 0.0, 0.0, 0.0, 0.0};
+    crgpu_sseq_args a = {params.n_features(), wave_min, wg_min, 0};
+    ctx.check(crgpu_sseq_diffexp_dev(ctx.get(), m, params.get(), labels.data(), n_clusters, &a, &r));
+    o.n_terms = r.n_terms, o.n_short = r.n_short, o.n_wave = r.n_wave, o.n_workgroup = r.n_workgroup;
+    return o;
+}
+
 // ---- protein aggregates of an antibody / antigen well; the closing filters of a cell call ---------------------------------------------
 static_assert(sizeof(crgpu_aggregates_info) == 48, "crgpu_aggregates_info changed: bump CRGPU_ABI_VERSION and every binding");
 /// int(np.round(n_signal * _calculate_fraction_to_use(n_signal)))
