@@ -353,7 +353,24 @@ class SseqResult(C.Structure):
         (n, C.c_double) for n in ("ms_sums", "ms_exact", "ms_asymptotic", "ms_bh")]
 
 
+class KnnArgs(C.Structure):
+    """crgpu_knn_args"""
+    _fields_ = [("query_start", C.c_uint64), ("n_queries", C.c_uint64)] + [
+        (n, C.c_uint32) for n in ("capacity", "force_device", "cand_tile", "reserved")]
+
+
+class KnnResult(C.Structure):
+    """crgpu_knn_result"""
+    _fields_ = [(n, C.c_void_p) for n in ("indices_out", "distances_out", "sorted_out")] + [
+        (n, C.c_double) for n in ("fit_ms", "select_ms", "sort_ms")] + [
+        (n, C.c_uint64) for n in ("compactions", "selections", "survivors", "pairs_evaluated")] + [
+        (n, C.c_uint32) for n in ("in_lds", "capacity", "query_tiles", "cand_tile")]
+
+
 KM_MAX_K, KM_MAX_D, KM_MAX_LIST = 64, 128, 64
+KNN_MAX_K, KNN_MAX_CAPACITY = 1024, 4096
+GRAPHCLUST_NEIGHBORS_DEFAULT, GRAPHCLUST_NEIGHBOR_A_DEFAULT, GRAPHCLUST_NEIGHBOR_B_DEFAULT = 1, -230.0, 120.0
+NN_QUERIES_PER_CHUNK = 15000
 SSEQ_MAX_K, SSEQ_BIG_COUNT = 4096, 900
 MC_INITS, MC_SKIPPED, MC_FITTED = 10, 0, 1
 JIBES_MAX_TAGS, JIBES_MAX_K_LETS, JIBES_MAX_STATES, JIBES_NEAR_ZERO, JIBES_CANT_CONVERGE = 16, 3, 970, 12, 1
@@ -526,6 +543,8 @@ SYMBOLS = {
     "crgpu_sseq_params_get": (_i, [_vp, _vp, C.POINTER(SseqParamsInfo)]),
     "crgpu_sseq_diffexp_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _vp, _u32, C.POINTER(SseqArgs), C.POINTER(SseqResult)]),
     "crgpu_sseq_adjust_bh": (_i, [_vp, _u64, _vp]),
+    "crgpu_knn_dev": (_i, [_vp, _vp, _u64, _u32, _u64, _u32, C.POINTER(KnnArgs), C.POINTER(KnnResult)]),
+    "crgpu_graphclust_num_neighbors": (_i, [_u64, _u32, _dbl, _dbl, C.POINTER(_u32)]),
     "crgpu_aggregate_min_antibodies": (_i, [_u32, C.POINTER(_u32)]),
     "crgpu_antigen_outlier_threshold": (_i, [_vp, _u32, C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_dbl)]),
     "crgpu_aggregates_by_counts_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, _u32, _vp, _vp, _u32, C.POINTER(_u32),

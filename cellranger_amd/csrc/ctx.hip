@@ -382,6 +382,26 @@ const std::vector<AbiStruct> &abi_table() {
               ABI_F(crgpu_sseq_result, ms_exact),
               ABI_F(crgpu_sseq_result, ms_asymptotic),
               ABI_F(crgpu_sseq_result, ms_bh)),
+        ABI_S(crgpu_knn_args, ABI_F(crgpu_knn_args, query_start),
+              ABI_F(crgpu_knn_args, n_queries),
+              ABI_F(crgpu_knn_args, capacity),
+              ABI_F(crgpu_knn_args, force_device),
+              ABI_F(crgpu_knn_args, cand_tile),
+              ABI_F(crgpu_knn_args, reserved)),
+        ABI_S(crgpu_knn_result, ABI_F(crgpu_knn_result, indices_out),
+              ABI_F(crgpu_knn_result, distances_out),
+              ABI_F(crgpu_knn_result, sorted_out),
+              ABI_F(crgpu_knn_result, fit_ms),
+              ABI_F(crgpu_knn_result, select_ms),
+              ABI_F(crgpu_knn_result, sort_ms),
+              ABI_F(crgpu_knn_result, compactions),
+              ABI_F(crgpu_knn_result, selections),
+              ABI_F(crgpu_knn_result, survivors),
+              ABI_F(crgpu_knn_result, pairs_evaluated),
+              ABI_F(crgpu_knn_result, in_lds),
+              ABI_F(crgpu_knn_result, capacity),
+              ABI_F(crgpu_knn_result, query_tiles),
+              ABI_F(crgpu_knn_result, cand_tile)),
     };
     return t;
 }

@@ -5,6 +5,7 @@ any of them (a missing library / GPU raises CrgpuError).
 """
 import csv
 import ctypes as C
+import io
 import math
 import os
 
@@ -1132,6 +1133,91 @@ def run_kmeans(ctx, projection, max_clusters=10, min_clusters=2, seed=0, num_pcs
     for r in ctx.kmeans(projection, ks, seed=seed, num_pcs=num_pcs):
         out[kmeans_clustering_key(r["n_clusters"], library_prefix)] = dict(
             clusters=r["clusters"], cluster_score=r["db_score"], centers=r["centers"], num_clusters=r["n_clusters"], global_sort_key=r["n_clusters"])
+    return out
+
+
+def graphclust_num_neighbors(n, num_neighbors=None, neighbor_a=None, neighbor_b=None):
+    """split() of RUN_GRAPH_CLUSTERING (crgpu_graphclust_num_neighbors, host only): int(max(num_neighbors, np.round(a + b * log10(n))))
+    clamped to [1, n - 1]; None = the reference's defaults 1, -230.0, 120.0"""
+    k = C.c_uint32(0)
+    rc = _lib.load().crgpu_graphclust_num_neighbors(
+        int(n), int(_lib.GRAPHCLUST_NEIGHBORS_DEFAULT if num_neighbors is None else num_neighbors),
+        float(_lib.GRAPHCLUST_NEIGHBOR_A_DEFAULT if neighbor_a is None else neighbor_a),
+        float(_lib.GRAPHCLUST_NEIGHBOR_B_DEFAULT if neighbor_b is None else neighbor_b), C.byref(k))
+    if rc != 0:
+        raise _lib.CrgpuError(rc, "crgpu_graphclust_num_neighbors")
+    return int(k.value)
+
+
+def louvain_labels(num_barcodes, use_bcs, pairs):
+    """load_louvain_results: pairs = the (node, community) lines of the louvain binary's output, every level of the hierarchy in turn.
+    The first occurrence of a node wins; ids are 1-based; a barcode that was not used gets 0 -> i64[num_barcodes]"""
+    labels = np.zeros(int(num_barcodes), dtype=np.int64)
+    use_bcs = np.asarray(use_bcs)
+    seen = set()
+    for node, community in pairs:
+        node = int(node)
+        if node in seen:
+            continue
+        seen.add(node)
+        labels[use_bcs[node]] = 1 + int(community)
+    return labels
+
+
+def relabel_by_size(labels):
+    """relabel_by_size (clustering.py): label l becomes 1 + the rank of l among all labels 0 .. max by descending size; equal sizes
+    keep their ascending order.  Label 0 (a barcode that was not used) takes part in the ranking as it does in the reference, so with
+    unused barcodes around no cluster is called by their rank"""
+    labels = np.asarray(labels)
+    by_size = np.argsort(-np.bincount(labels), kind="stable")
+    rank = np.empty(len(by_size), dtype=np.int64)
+    rank[by_size] = np.arange(len(by_size))
+    return 1 + rank[labels]
+
+
+def write_louvain_edges(file, nn_indptr, nn_indices):
+    """pipe_unweighted_edgelist_to_convert's lines: "%d\\t%d\\n" per entry of the neighbour matrix in CSR order (row, then column
+    ascending), which is the order nn.tocoo() gives `convert`; file: anything with write(), text or bytes -> the number of lines"""
+    indptr, indices = np.asarray(nn_indptr, dtype=np.int64), np.asarray(nn_indices, dtype=np.int64)
+    binary = "b" in getattr(file, "mode", "") or isinstance(file, (io.BytesIO, io.BufferedIOBase, io.RawIOBase))
+    rows = np.repeat(np.arange(len(indptr) - 1, dtype=np.int64), np.diff(indptr))
+    step = 1 << 16
+    for lo in range(0, len(indices), step):
+        text = "".join("%d\t%d\n" % ij for ij in zip(rows[lo:lo + step].tolist(), indices[lo:lo + step].tolist()))
+        file.write(text.encode("ascii") if binary else text)
+    return len(indices)
+
+
+def run_graph_clustering(ctx, projection, num_neighbors=None, neighbor_a=None, neighbor_b=None, input_pcs=None, louvain=None,
+                         num_barcodes=None, use_bcs=None, queries_per_call=_lib.NN_QUERIES_PER_CHUNK):
+    """RUN_GRAPH_CLUSTERING up to the Louvain binary: k by split()'s rule, the exact k nearest neighbours of every row of the cells x PCs
+    projection (Context.knn, in calls of queries_per_call rows as the reference's chunks), the neighbour matrix of join()
+    -> dict(num_neighbors, indices i32[n, k] by rank, distances f64[n, k], nn_indptr i64[n + 1], nn_indices i32[n k] (row-wise
+    ascending: the CSR matrix of merge_nearest_neighbors, every value 1), nn_nodes, nn_links, nn_density, pairs_evaluated, fit_ms).
+    louvain: None, or a callable (row, col) -> the (node, community) pairs of the binary's output for that edge list; then also labels
+    (louvain_labels(num_barcodes, use_bcs, pairs); default every row in order) and clusters (relabel_by_size(labels))"""
+    x = np.asarray(projection)
+    if x.ndim != 2:
+        raise ValueError("run_graph_clustering: the projection is cells x PCs")
+    n = x.shape[0]
+    d = x.shape[1] if input_pcs is None else min(x.shape[1], int(input_pcs))
+    k = graphclust_num_neighbors(n, num_neighbors, neighbor_a, neighbor_b)
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    ind, dist, srt = np.zeros((n, k), np.int32), np.zeros((n, k)), np.zeros((n, k), np.int32)
+    pairs_evaluated, fit_ms = 0, 0.0
+    for q0 in range(0, n, int(queries_per_call)):
+        r = ctx.knn(x, k, num_pcs=d, query_start=q0, n_queries=min(int(queries_per_call), n - q0))
+        q1 = q0 + len(r["indices"])
+        ind[q0:q1], dist[q0:q1], srt[q0:q1] = r["indices"], r["distances"], r["sorted_indices"]
+        pairs_evaluated += r["pairs_evaluated"]
+        fit_ms += r["fit_ms"]
+    out = dict(num_neighbors=k, indices=ind, distances=dist, nn_indptr=np.arange(n + 1, dtype=np.int64) * k, nn_indices=srt.reshape(-1),
+               nn_nodes=n, nn_links=n * k, nn_density=(n * k) / float(n * n), pairs_evaluated=pairs_evaluated, fit_ms=fit_ms)
+    if louvain is not None:
+        row = np.repeat(np.arange(n, dtype=np.int64), k)
+        pairs = louvain(row, out["nn_indices"].astype(np.int64))
+        out["labels"] = louvain_labels(n if num_barcodes is None else num_barcodes, np.arange(n) if use_bcs is None else use_bcs, pairs)
+        out["clusters"] = relabel_by_size(out["labels"])
     return out
 
 
@@ -2364,6 +2450,34 @@ class Context:
             o.update(inertia=r.inertia, db_score=r.db_score, fit_ms=r.fit_ms, n_iter=int(r.n_iter), strict=bool(r.strict),
                      relocations=int(r.relocations), in_lds=bool(r.in_lds))
         return outs
+
+    def knn(self, projection, k, num_pcs=None, query_start=0, n_queries=None, capacity=0, force_device=False, cand_tile=0):
+        """BallTree(x).query(rows, k + 1) then [:, 1:] of scikit-learn 1.7.2, exactly and by brute force on the device (csrc/knn.hip): for
+        the rows query_start .. query_start + n_queries (default: to the end) of the f64 projection [cells x PCs] the k entries after
+        the first in the order of the pairs (d2, index) over all rows; num_pcs takes the first columns as a view.  A row with an exact
+        duplicate of lower index keeps itself as a neighbour.  capacity / force_device / cand_tile: test seams, no result depends on them
+        -> dict(indices i32[q, k] by rank, distances f64[q, k], sorted_indices i32[q, k] ascending per row, compactions, selections,
+        survivors, pairs_evaluated, in_lds, capacity, query_tiles, cand_tile, fit_ms, select_ms, sort_ms)"""
+        x = np.ascontiguousarray(projection, dtype=np.float64)
+        if x.ndim != 2:
+            raise ValueError("knn: the projection is cells x PCs")
+        n, ld = x.shape
+        d = ld if num_pcs is None else int(num_pcs)
+        q0 = int(query_start)
+        nq = n - q0 if n_queries is None else int(n_queries)
+        if q0 < 0 or nq < 1 or q0 + nq > n:
+            raise ValueError("knn: queries %d + %d of %d rows" % (q0, nq, n))
+        k = int(k)
+        if not 1 <= k <= _lib.KNN_MAX_K:      # the output arrays need a shape; the library refuses the rest
+            raise ValueError("knn: k = %d, 1 to %d" % (k, _lib.KNN_MAX_K))
+        o = dict(indices=np.zeros((nq, k), np.int32), distances=np.zeros((nq, k)), sorted_indices=np.zeros((nq, k), np.int32))
+        a = _lib.KnnArgs(query_start=q0, n_queries=nq, capacity=int(capacity), force_device=1 if force_device else 0, cand_tile=int(cand_tile))
+        r = _lib.KnnResult(indices_out=ptr(o["indices"]), distances_out=ptr(o["distances"]), sorted_out=ptr(o["sorted_indices"]))
+        self._check(self.L.crgpu_knn_dev(self.h, ptr(x), n, d, ld, k, C.byref(a), C.byref(r)))
+        o.update(compactions=int(r.compactions), selections=int(r.selections), survivors=int(r.survivors), pairs_evaluated=int(r.pairs_evaluated),
+                 in_lds=bool(r.in_lds), capacity=int(r.capacity), query_tiles=int(r.query_tiles), cand_tile=int(r.cand_tile), fit_ms=r.fit_ms,
+                 select_ms=r.select_ms, sort_ms=r.sort_ms)
+        return o
 
     def sseq_params(self, m, n_features=None):
         """compute_sseq_params of the MatrixDev `m` (features x cells, one feature type: select_features_dev) on the device

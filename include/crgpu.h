@@ -1871,6 +1871,75 @@ int crgpu_sseq_diffexp_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const crgp
                            uint32_t n_clusters, const crgpu_sseq_args *args, crgpu_sseq_result *result);
 int crgpu_sseq_adjust_bh(const double *p, uint64_t n, double *q_out);
 
+/* ---- exact k-nearest-neighbour graph of a dense projection: the query of RUN_GRAPH_CLUSTERING ---------------------------------------
+ * stages/analyzer/run_graph_clustering/__init__.py: split() fixes the number of neighbours and cuts the rows into chunks of 15 000,
+ * main() queries one chunk, join() merges the chunks, prints nn_nodes, nn_links and nn_density and feeds the edge list to Louvain.
+ * The query is compute_nearest_neighbors (lib/python/cellranger/analysis/graphclust.py:39-62): scikit-learn 1.7.2's
+ * BallTree(x, leaf_size = 40).query(rows, k + 1), then [:, 1:]; merge_nearest_neighbors (graphclust.py:95-106) sums the chunks into
+ * one matrix whose row i holds a 1 at each neighbour of i.  The tree only prunes: leaf size 2 or 40, the result is the same.
+ *   crgpu_knn_dev                x: host f64, row i at x + i * ld, ld >= d (a view of the first d columns of a wider matrix); the k
+ *                                nearest rows of every query row.  2 <= n < 2^31, 1 <= d <= CRGPU_KM_MAX_D, 1 <= k <= min(n - 1,
+ *                                CRGPU_KNN_MAX_K), every value finite, the query range inside the rows; anything else is
+ *                                CRGPU_EINVAL before the device is touched.
+ *       d2(i, j)                 the sum over t = 0 .. d - 1 of (x_it - x_jt) * (x_it - x_jt), in that order, f64, unfused.  The form
+ *                                |x|^2 - 2 x.y + |y|^2 is used nowhere, not even as a filter.
+ *       the neighbours of i      the k entries AFTER THE FIRST in the ascending order of the pairs (d2(i, j), j) over ALL rows j, i
+ *                                included.  TIE RULE: equal d2, the lower index first -- a total order, so the result is a pure
+ *                                function of x: bit-identical between runs, between a query range and the whole, whatever the seams
+ *                                below are set to and whatever the other rows' results are.  On tie-free input this is BallTree's
+ *                                answer index for index; on tied input its distances (the tree breaks ties by its own traversal).
+ *       QUIRK kept               the first pair is dropped, not the pair (0, i): a row with an exact duplicate of lower index drops
+ *                                the duplicate and keeps ITSELF as a neighbour at distance 0
+ *       distance                 the correctly rounded square root of d2
+ *       on the device            brute force over tiles (csrc/knn.hip): a workgroup owns 64 queries, a lane a query; candidate tiles
+ *                                stream through LDS.  A query keeps a bound, the (k + 1)-th smallest d2 of its last selection, and
+ *                                a buffer of `capacity` pairs with d2 <= bound, in LDS when 64 of them fit 48 KiB, else in device
+ *                                memory.  Before a buffer could overflow, every buffer of the workgroup is cut to its k + 1
+ *                                smallest pairs by an exact sort, which tightens the bound (a "compaction").  One final sort per
+ *                                row by (bits of d2, j).  No floating-point atomic.
+ *   crgpu_knn_args               query_start, n_queries: the rows queried (0, 0 = all) -- the reference's row_start and its chunk;
+ *                                the outputs have n_queries rows.  Test seams, FIELDS and not environment switches, 0 = the default,
+ *                                none moves a bit of a result: capacity = pairs of a query's buffer (k + 5 .. 4096; default the
+ *                                power of two from 2 (k + 1) up, at least 64); force_device = 1 keeps the buffers in device
+ *                                memory whatever their size; cand_tile = candidate rows per LDS tile (a multiple of 4, up to
+ *                                min(256, 2560 / d))
+ *   crgpu_knn_result             pointers the caller sets, NULL = not wanted: indices_out i32[n_queries x k] by rank,
+ *                                distances_out f64[n_queries x k], sorted_out i32[n_queries x k] = each row's neighbours in
+ *                                ascending index order: the `indices` of the CSR matrix merge_nearest_neighbors builds (indptr[i]
+ *                                = i * k, every value 1), which nn.tocoo() walks in this same order -- the edge list `convert`
+ *                                reads.  fit_ms = host time of the call; select_ms, sort_ms = device time of the pass over the
+ *                                candidates and of the final sort; compactions = times a workgroup cut its buffers; selections =
+ *                                buffers cut; survivors = pairs appended; pairs_evaluated = n_queries * n; in_lds; capacity;
+ *                                query_tiles = workgroups of 64 queries; cand_tile
+ *   crgpu_graphclust_num_neighbors  host only, split()'s rule: int(max(num_neighbors, np.round(a + b * log10(n)))), numpy's round half
+ *                                to even, clamped to [1, n - 1]; the reference's defaults are 1, -230.0, 120.0
+ *                                (analysis/constants.py); n < 2 is CRGPU_EINVAL
+ * NOT covered: Louvain and `convert` (bin/louvain is a serial, seeded, external binary whose source the reference does not carry: the
+ * host runs it on the edge list this stage delivers), the SNN similarity (the reference itself raises on it), the num_bcs subsample
+ * (the caller passes the rows), MERGE_CLUSTERS, the H5 and CSV writers, float32, and PCA itself. */
+#define CRGPU_KNN_MAX_K 1024
+struct crgpu_knn_args {
+    uint64_t query_start, n_queries;   /* 0, 0 = every row */
+    uint32_t capacity;                 /* seam: pairs of a query's buffer, 0 = default */
+    uint32_t force_device;             /* seam: 1 = the buffers in device memory */
+    uint32_t cand_tile;                /* seam: candidate rows per LDS tile, 0 = default */
+    uint32_t reserved;
+};
+typedef struct crgpu_knn_args crgpu_knn_args;
+struct crgpu_knn_result {
+    int32_t *indices_out;
+    double *distances_out;
+    int32_t *sorted_out;
+    double fit_ms, select_ms, sort_ms;
+    uint64_t compactions, selections, survivors, pairs_evaluated;
+    uint32_t in_lds, capacity;
+    uint32_t query_tiles, cand_tile;
+};
+typedef struct crgpu_knn_result crgpu_knn_result;
+int crgpu_knn_dev(crgpu_ctx *ctx, const double *x, uint64_t n, uint32_t d, uint64_t ld, uint32_t k, const crgpu_knn_args *args,
+                  crgpu_knn_result *result);
+int crgpu_graphclust_num_neighbors(uint64_t n, uint32_t num_neighbors, double a, double b, uint32_t *k_out);
+
 /* ---- synthetic workloads (bench / tests) ---------------------------------------------
  * Counter-based integer generator: read i of a given seed is identical on the host and on the
  * device.  Tables are host arrays built by cellranger_amd.synth. */

@@ -1396,6 +1396,37 @@ inline SseqDiffexp sseq_diffexp(Context &ctx, const crgpu_matrix_dev *m, const S
     return o;
 }
 
+// ---- exact k-nearest-neighbour graph of a dense projection: the query of RUN_GRAPH_CLUSTERING -----------------------------------------
+static_assert(sizeof(crgpu_knn_args) == 32, "crgpu_knn_args changed: bump CRGPU_ABI_VERSION and every binding");
+static_assert(sizeof(crgpu_knn_result) == 96, "crgpu_knn_result changed: bump CRGPU_ABI_VERSION and every binding");
+/// split()'s rule: int(max(num_neighbors, np.round(a + b * log10(n)))) clamped to [1, n - 1]
+inline uint32_t graphclust_num_neighbors(uint64_t n, uint32_t num_neighbors = 1, double a = -230.0, double b = 120.0) {
+    uint32_t k = 0;
+    const int rc = crgpu_graphclust_num_neighbors(n, num_neighbors, a, b, &k);
+    if (rc != CRGPU_OK) throw Error(rc, "graphclust_num_neighbors");
+    return k;
+}
+struct Knn {
+    uint64_t n_queries = 0;
+    uint32_t k = 0;
+    std::vector<int32_t> indices, sorted_indices;  // [n_queries][k]: by rank; ascending (the CSR row of merge_nearest_neighbors)
+    std::vector<double> distances;                 // [n_queries][k]
+    crgpu_knn_result info{};                       // the counters and times; its pointers are those of the vectors above
+};
+/// crgpu_knn_dev on x (n rows of stride ld, the first d columns): BallTree.query(rows, k + 1)[:, 1:] for the rows query_start ..
+/// query_start + n_queries (0, 0 = all); capacity / force_device / cand_tile = the test seams (0 = default), which change no result
+inline Knn knn(Context &ctx, const double *x, uint64_t n, uint32_t d, uint64_t ld, uint32_t k, uint64_t query_start = 0, uint64_t n_queries = 0,
+               uint32_t capacity = 0, uint32_t force_device = 0, uint32_t cand_tile = 0) {
+    Knn o;
+    o.n_queries = (query_start == 0 && n_queries == 0) ? n : n_queries, o.k = k;
+    const size_t m = (size_t)o.n_queries * k;
+    o.indices.assign(m, 0), o.sorted_indices.assign(m, 0), o.distances.assign(m, 0.0);
+    crgpu_knn_args a = {query_start, n_queries, capacity, force_device, cand_tile, 0};
+    o.info = crgpu_knn_result{o.indices.data(), o.distances.data(), o.sorted_indices.data(), 0.0, 0.0, 0.0, 0, 0, 0, 0, 0, 0, 0, 0};
+    ctx.check(crgpu_knn_dev(ctx.get(), x, n, d, ld, k, &a, &o.info));
+    return o;
+}
+
 // ---- protein aggregates of an antibody / antigen well; the closing filters of a cell call ---------------------------------------------
 static_assert(sizeof(crgpu_aggregates_info) == 48, "crgpu_aggregates_info changed: bump CRGPU_ABI_VERSION and every binding");
 /// int(np.round(n_signal * _calculate_fraction_to_use(n_signal)))
