@@ -367,8 +367,33 @@ class KnnResult(C.Structure):
         (n, C.c_uint32) for n in ("in_lds", "capacity", "query_tiles", "cand_tile")]
 
 
+class KnnCrossArgs(C.Structure):
+    """crgpu_knn_cross_args"""
+    _fields_ = [(n, C.c_uint64) for n in ("query_start", "n_queries", "cand_start", "n_cands")] + [
+        (n, C.c_uint32) for n in ("capacity", "force_device", "cand_tile", "reserved")]
+
+
+class BcStep(C.Structure):
+    """crgpu_bc_step"""
+    _fields_ = [(n, C.c_void_p) for n in ("cur_rows", "mnn_cur", "mnn_ref", "corr_out")] + [("n_cur", C.c_uint64), ("n_mnn", C.c_uint64)]
+
+
+class BcArgs(C.Structure):
+    """crgpu_bc_args"""
+    _fields_ = [(n, C.c_uint32) for n in ("pair_tile", "row_tile", "slab_rows", "reserved")]
+
+
+class BcResult(C.Structure):
+    """crgpu_bc_result"""
+    _fields_ = [("step_ms_out", C.c_void_p)] + [
+        (n, C.c_double) for n in ("fit_ms", "upload_ms", "download_ms", "gather_ms", "accumulate_ms", "finish_ms", "apply_ms")] + [
+        (n, C.c_uint64) for n in ("pairs_evaluated", "chunks", "zero_den_rows")] + [(n, C.c_uint32) for n in ("pair_tile", "row_tile")]
+
+
 KM_MAX_K, KM_MAX_D, KM_MAX_LIST = 64, 128, 64
 KNN_MAX_K, KNN_MAX_CAPACITY = 1024, 4096
+BC_PAIR_CHUNK, BC_LDS_BYTES, BC_MAX_PAIR_TILE = 2048, 73728, 64
+CBC_KNN, CBC_ALPHA, CBC_SIGMA, CBC_REALIGN_PANORAMA = 10, 0.1, 150.0, False
 GRAPHCLUST_NEIGHBORS_DEFAULT, GRAPHCLUST_NEIGHBOR_A_DEFAULT, GRAPHCLUST_NEIGHBOR_B_DEFAULT = 1, -230.0, 120.0
 NN_QUERIES_PER_CHUNK = 15000
 SSEQ_MAX_K, SSEQ_BIG_COUNT = 4096, 900
@@ -545,6 +570,9 @@ SYMBOLS = {
     "crgpu_sseq_adjust_bh": (_i, [_vp, _u64, _vp]),
     "crgpu_knn_dev": (_i, [_vp, _vp, _u64, _u32, _u64, _u32, C.POINTER(KnnArgs), C.POINTER(KnnResult)]),
     "crgpu_graphclust_num_neighbors": (_i, [_u64, _u32, _dbl, _dbl, C.POINTER(_u32)]),
+    "crgpu_knn_cross_dev": (_i, [_vp, _vp, _u64, _u32, _u64, _u32, C.POINTER(KnnCrossArgs), C.POINTER(KnnResult)]),
+    "crgpu_mnn_pairs": (_i, [_vp, _u64, _u64, _vp, _u64, _u64, _u32, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "crgpu_batch_correct_dev": (_i, [_vp, _vp, _u64, _u32, _u64, _dbl, C.POINTER(BcStep), _u32, _vp, C.POINTER(BcArgs), C.POINTER(BcResult)]),
     "crgpu_aggregate_min_antibodies": (_i, [_u32, C.POINTER(_u32)]),
     "crgpu_antigen_outlier_threshold": (_i, [_vp, _u32, C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_dbl)]),
     "crgpu_aggregates_by_counts_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, _u32, _vp, _vp, _u32, C.POINTER(_u32),

@@ -402,6 +402,37 @@ const std::vector<AbiStruct> &abi_table() {
               ABI_F(crgpu_knn_result, capacity),
               ABI_F(crgpu_knn_result, query_tiles),
               ABI_F(crgpu_knn_result, cand_tile)),
+        ABI_S(crgpu_knn_cross_args, ABI_F(crgpu_knn_cross_args, query_start),
+              ABI_F(crgpu_knn_cross_args, n_queries),
+              ABI_F(crgpu_knn_cross_args, cand_start),
+              ABI_F(crgpu_knn_cross_args, n_cands),
+              ABI_F(crgpu_knn_cross_args, capacity),
+              ABI_F(crgpu_knn_cross_args, force_device),
+              ABI_F(crgpu_knn_cross_args, cand_tile),
+              ABI_F(crgpu_knn_cross_args, reserved)),
+        ABI_S(crgpu_bc_step, ABI_F(crgpu_bc_step, cur_rows),
+              ABI_F(crgpu_bc_step, mnn_cur),
+              ABI_F(crgpu_bc_step, mnn_ref),
+              ABI_F(crgpu_bc_step, corr_out),
+              ABI_F(crgpu_bc_step, n_cur),
+              ABI_F(crgpu_bc_step, n_mnn)),
+        ABI_S(crgpu_bc_args, ABI_F(crgpu_bc_args, pair_tile),
+              ABI_F(crgpu_bc_args, row_tile),
+              ABI_F(crgpu_bc_args, slab_rows),
+              ABI_F(crgpu_bc_args, reserved)),
+        ABI_S(crgpu_bc_result, ABI_F(crgpu_bc_result, step_ms_out),
+              ABI_F(crgpu_bc_result, fit_ms),
+              ABI_F(crgpu_bc_result, upload_ms),
+              ABI_F(crgpu_bc_result, download_ms),
+              ABI_F(crgpu_bc_result, gather_ms),
+              ABI_F(crgpu_bc_result, accumulate_ms),
+              ABI_F(crgpu_bc_result, finish_ms),
+              ABI_F(crgpu_bc_result, apply_ms),
+              ABI_F(crgpu_bc_result, pairs_evaluated),
+              ABI_F(crgpu_bc_result, chunks),
+              ABI_F(crgpu_bc_result, zero_den_rows),
+              ABI_F(crgpu_bc_result, pair_tile),
+              ABI_F(crgpu_bc_result, row_tile)),
     };
     return t;
 }

@@ -10,6 +10,9 @@
 // QUIRK kept (it is the reference's): the FIRST pair is dropped, not the pair of the row itself.  A row with an exact duplicate of
 // lower index drops the duplicate and keeps itself as a neighbour at distance 0.
 //
+// crgpu_knn_cross_dev is find_knn of CORRECT_CHEMISTRY_BATCH (lib/python/cellranger/analysis/batch_correction.py:106-115): the same two
+// kernels with a candidate range, an index base and a drop count of 0 in KnnShape -- the first k pairs over the candidate rows alone.
+//
 // Launch structure.  Brute force over tiles, no pruning by any expansion of the norm.
 //   k_knn_select   a workgroup owns 64 queries, lane = query, the query's row in registers (d <= 16) or transposed in LDS.  Candidate
 //                  tiles stream through LDS; wave w takes candidates w, w + 4, ...: every lane reads the same LDS address.  A query
@@ -19,8 +22,8 @@
 //                  step of at most capacity - (k + 1) candidates the workgroup looks whether a buffer could overflow in it; if one
 //                  could, every such buffer and every buffer more than half full is cut to its k + 1 smallest by a bitonic sort in
 //                  LDS, which tightens the bound.  A pair of the final answer is never above a bound, ties included.
-//   k_knn_final    a workgroup a query: the buffer sorted by (d2, j); ranks 1 .. k are the answer; the root; the same k indices
-//                  sorted ascending (the CSR row of merge_nearest_neighbors).
+//   k_knn_final    a workgroup a query: the buffer sorted by (d2, j); ranks 1 .. k are the answer (0 .. k - 1 of a cross query); the
+//                  root; the same k indices sorted ascending (the CSR row of merge_nearest_neighbors).
 // No floating-point atomic anywhere; the only atomics are the LDS slot counters and three u64 event counters.
 #include <algorithm>
 #include <chrono>
@@ -39,8 +42,11 @@
 #define KNN_LDS_BUF 49152u    // bytes of LDS the 64 buffers may take
 #define KNN_PAD_KEY 0xFFFFFFFFFFFFFFFFull
 
+// The device matrix holds the rows the call needs; q0, nq: the query rows in it; c0, nc: the candidate rows in it; ibase: what is added
+// to a candidate's position among the candidates to give the index reported; drop: pairs left out at the head of the order (1:
+// crgpu_knn_dev, 0: crgpu_knn_cross_dev); K = k + drop pairs are kept per query.
 struct KnnShape {
-    uint32_t n, d, q0, nq, K, cap, tile, step, in_lds;
+    uint32_t d, q0, nq, c0, nc, ibase, drop, K, cap, tile, step, in_lds;
 };
 
 // ---- host: the rule of split() ---------------------------------------------------------------------------------------------------
@@ -128,10 +134,10 @@ __global__ __launch_bounds__(KNN_WG) void k_knn_select(const double *__restrict_
     uint32_t events = 0, cuts = 0;
     unsigned long long appended = 0;
 
-    for (uint32_t c0 = 0; c0 < s.n; c0 += s.tile) {
-        const uint32_t m = s.n - c0 < s.tile ? s.n - c0 : s.tile;
+    for (uint32_t c0 = 0; c0 < s.nc; c0 += s.tile) {
+        const uint32_t m = s.nc - c0 < s.tile ? s.nc - c0 : s.tile;
         __syncthreads();  // the previous tile is done with
-        for (uint32_t e = tid; e < m * d; e += KNN_WG) s_y[e] = x[(size_t)c0 * d + e];
+        for (uint32_t e = tid; e < m * d; e += KNN_WG) s_y[e] = x[(size_t)(s.c0 + c0) * d + e];
         __syncthreads();
         for (uint32_t s0 = 0; s0 < m; s0 += s.step) {
             const uint32_t s1 = s0 + s.step < m ? s0 + s.step : m;
@@ -173,7 +179,7 @@ __global__ __launch_bounds__(KNN_WG) void k_knn_select(const double *__restrict_
                 const uint64_t key = (uint64_t)__double_as_longlong(a);
                 if (live && key <= bound) {
                     const uint32_t pos = atomicAdd(&s_cnt[lane], 1u);
-                    if (pos < cap) bk[pos] = key, bi[pos] = c0 + c;  // pos < cap by the step rule; the test keeps a fault out of memory
+                    if (pos < cap) bk[pos] = key, bi[pos] = s.ibase + c0 + c;  // pos < cap by the step rule; the test keeps a fault out of memory
                     appended++;
                 }
             }
@@ -200,7 +206,7 @@ __global__ __launch_bounds__(KNN_WG) void k_knn_final(KnnShape s, const uint64_t
                                                       const uint32_t *__restrict__ gcnt, int32_t *__restrict__ ind, double *__restrict__ dist,
                                                       int32_t *__restrict__ sorted, uint32_t *__restrict__ bad) {
     extern __shared__ double knn_lds[];
-    const uint32_t q = blockIdx.x, tid = threadIdx.x, K = s.K, k = K - 1u, cap = s.cap;
+    const uint32_t q = blockIdx.x, tid = threadIdx.x, K = s.K, drop = s.drop, k = K - drop, cap = s.cap;
     uint64_t *sk = (uint64_t *)knn_lds;
     uint32_t *si = (uint32_t *)(sk + knn_pow2(cap));
     const uint32_t cnt = gcnt[q];
@@ -215,9 +221,9 @@ __global__ __launch_bounds__(KNN_WG) void k_knn_final(KnnShape s, const uint64_t
         const uint32_t e = tid + r * KNN_WG;
         mine[r] = 0xFFFFFFFFu;
         if (e < k) {
-            mine[r] = si[e + 1u];
+            mine[r] = si[e + drop];
             ind[(size_t)q * k + e] = (int32_t)mine[r];
-            dist[(size_t)q * k + e] = sqrt(__longlong_as_double((long long)sk[e + 1u]));
+            dist[(size_t)q * k + e] = sqrt(__longlong_as_double((long long)sk[e + drop]));
         }
     }
     // the same k indices ascending
@@ -252,48 +258,50 @@ static uint32_t knn_host_pow2(uint32_t v) {
     return p;
 }
 
-extern "C" int crgpu_knn_dev(crgpu_ctx *ctx, const double *x, uint64_t n, uint32_t d, uint64_t ld, uint32_t k, const crgpu_knn_args *a,
-                             crgpu_knn_result *res) {
-    if (!ctx || !x || !a || !res) return CRGPU_EINVAL;
-    CR_ENTER(ctx);
-    // every refusal below comes before the device is touched
-    CR_REQUIRE(ctx, n >= 2 && n < (1ull << 31), CRGPU_EINVAL, "crgpu_knn_dev: %llu rows, 2 to 2^31 - 1", (unsigned long long)n);
-    CR_REQUIRE(ctx, d >= 1 && d <= CRGPU_KM_MAX_D && ld >= d, CRGPU_EINVAL, "crgpu_knn_dev: %u dimensions (1 to %u) in rows of %llu", d, CRGPU_KM_MAX_D,
-               (unsigned long long)ld);
-    CR_REQUIRE(ctx, k >= 1 && k <= CRGPU_KNN_MAX_K && k < n, CRGPU_EINVAL, "crgpu_knn_dev: k = %u, 1 to min(%u, the %llu rows - 1)", k, CRGPU_KNN_MAX_K,
-               (unsigned long long)n);
-    const bool all = a->query_start == 0 && a->n_queries == 0;
-    const uint64_t q0 = a->query_start, nq = all ? n : a->n_queries;
-    CR_REQUIRE(ctx, nq >= 1 && q0 < n && nq <= n - q0, CRGPU_EINVAL, "crgpu_knn_dev: queries %llu + %llu of %llu rows", (unsigned long long)q0,
-               (unsigned long long)a->n_queries, (unsigned long long)n);
-    const uint32_t K = k + 1u;
-    // the buffer: by default the power of two from 2 (k + 1) up, at least 64
-    uint32_t cap = a->capacity ? a->capacity : std::min(KNN_MAX_CAP, std::max(64u, knn_host_pow2(2u * K)));
-    CR_REQUIRE(ctx, cap >= K + KNN_WAVES && cap <= KNN_MAX_CAP, CRGPU_EINVAL, "crgpu_knn_dev: a buffer of %u pairs, k + 5 = %u to %u", cap, K + KNN_WAVES,
-               KNN_MAX_CAP);
+// What the two entry points share, after each has checked its own arguments: the rows [q0, q0 + nq) query the rows [c0, c0 + nc).
+// all_rows: the whole matrix goes to the device (crgpu_knn_dev); else the query rows and behind them the candidate rows
+// (crgpu_knn_cross_dev), and a candidate's index is reported as c0 + its position.
+struct KnnCall {
+    const char *who;
+    uint64_t n, ld, q0, nq, c0, nc;
+    uint32_t d, k, drop, capacity, force_device, cand_tile, reserved;
+    bool all_rows;
+};
+static int knn_run(crgpu_ctx *ctx, const double *x, const KnnCall &c, crgpu_knn_result *res) {
+    const uint32_t d = c.d, k = c.k, K = k + c.drop;
+    const uint64_t nq = c.nq;
+    // the buffer: by default the power of two from 2 K up, at least 64
+    uint32_t cap = c.capacity ? c.capacity : std::min(KNN_MAX_CAP, std::max(64u, knn_host_pow2(2u * K)));
+    CR_REQUIRE(ctx, cap >= K + KNN_WAVES && cap <= KNN_MAX_CAP, CRGPU_EINVAL, "%s: a buffer of %u pairs, k + %u = %u to %u", c.who, cap, c.drop + KNN_WAVES,
+               K + KNN_WAVES, KNN_MAX_CAP);
     const uint32_t tile_max = std::max(KNN_WAVES, std::min(KNN_MAX_TILE, (KNN_TILE_DOUBLES / d) & ~(KNN_WAVES - 1u)));
-    const uint32_t tile = a->cand_tile ? a->cand_tile : tile_max;
+    const uint32_t tile = c.cand_tile ? c.cand_tile : tile_max;
     CR_REQUIRE(ctx, tile >= KNN_WAVES && tile <= tile_max && tile % KNN_WAVES == 0u, CRGPU_EINVAL,
-               "crgpu_knn_dev: a candidate tile of %u rows, a multiple of %u up to %u for %u dimensions", tile, KNN_WAVES, tile_max, d);
-    CR_REQUIRE(ctx, a->force_device <= 1u && a->reserved == 0u, CRGPU_EINVAL, "crgpu_knn_dev: force_device is 0 or 1, reserved 0");
+               "%s: a candidate tile of %u rows, a multiple of %u up to %u for %u dimensions", c.who, tile, KNN_WAVES, tile_max, d);
+    CR_REQUIRE(ctx, c.force_device <= 1u && c.reserved == 0u, CRGPU_EINVAL, "%s: force_device is 0 or 1, reserved 0", c.who);
     const auto t0 = std::chrono::steady_clock::now();
-    std::vector<double> xp((size_t)n * d);  // the first d columns, packed; an infinity or a NaN is refused
-    for (uint64_t i = 0; i < n; i++)
-        for (uint32_t t = 0; t < d; t++) {
-            const double v = x[i * ld + t];
-            CR_REQUIRE(ctx, std::isfinite(v), CRGPU_EINVAL, "crgpu_knn_dev: x[%llu, %u] is not finite", (unsigned long long)i, t);
-            xp[i * d + t] = v;
-        }
+    // the first d columns of the rows that are used, packed; an infinity or a NaN is refused
+    const uint64_t seg_lo[2] = {c.all_rows ? 0 : c.q0, c.c0}, seg_n[2] = {c.all_rows ? c.n : c.nq, c.all_rows ? 0 : c.nc};
+    std::vector<double> xp((size_t)(seg_n[0] + seg_n[1]) * d);
+    size_t at = 0;
+    for (int g = 0; g < 2; g++)
+        for (uint64_t i = seg_lo[g]; i < seg_lo[g] + seg_n[g]; i++)
+            for (uint32_t t = 0; t < d; t++) {
+                const double v = x[i * c.ld + t];
+                CR_REQUIRE(ctx, std::isfinite(v), CRGPU_EINVAL, "%s: x[%llu, %u] is not finite", c.who, (unsigned long long)i, t);
+                xp[at++] = v;
+            }
 
     KnnShape s;
-    s.n = (uint32_t)n, s.d = d, s.q0 = (uint32_t)q0, s.nq = (uint32_t)nq, s.K = K, s.cap = cap, s.tile = tile;
+    s.d = d, s.q0 = (uint32_t)(c.all_rows ? c.q0 : 0), s.nq = (uint32_t)nq, s.c0 = (uint32_t)(c.all_rows ? c.c0 : c.nq), s.nc = (uint32_t)c.nc;
+    s.ibase = (uint32_t)(c.all_rows ? 0 : c.c0), s.drop = c.drop, s.K = K, s.cap = cap, s.tile = tile;
     s.step = std::min(tile, (cap - K) & ~(KNN_WAVES - 1u));
-    s.in_lds = (!a->force_device && (uint64_t)KNN_QT * cap * 12u <= KNN_LDS_BUF) ? 1u : 0u;
+    s.in_lds = (!c.force_device && (uint64_t)KNN_QT * cap * 12u <= KNN_LDS_BUF) ? 1u : 0u;
     const bool reg = d <= KNN_DR;
     const uint32_t p2cap = knn_host_pow2(cap), n_tiles = (s.nq + KNN_QT - 1u) / KNN_QT;
     const size_t lds_final = (size_t)p2cap * 12u;
     const size_t lds_select = ((size_t)tile * d + (reg ? 0u : (size_t)d * KNN_QT)) * sizeof(double) + lds_final + (s.in_lds ? (size_t)KNN_QT * cap * 12u : 0u);
-    CR_REQUIRE(ctx, lds_select <= 160u * 1024u - 1024u, CRGPU_EHIP, "crgpu_knn_dev: %llu bytes of LDS", (unsigned long long)lds_select);
+    CR_REQUIRE(ctx, lds_select <= 160u * 1024u - 1024u, CRGPU_EHIP, "%s: %llu bytes of LDS", c.who, (unsigned long long)lds_select);
 
     DevBuf x_b, key_b, idx_b, cnt_b, ctr_b, ind_b, dist_b, sorted_b;
     const uint64_t rows = (uint64_t)n_tiles * KNN_QT;
@@ -332,7 +340,7 @@ extern "C" int crgpu_knn_dev(crgpu_ctx *ctx, const double *x, uint64_t n, uint32
 
     uint64_t ctr[4] = {0, 0, 0, 0};
     CR_TRY(crgpu_memcpy_d2h(ctx, ctr, ctr_b.p, sizeof(ctr)));
-    CR_REQUIRE(ctx, (uint32_t)ctr[3] == 0u, CRGPU_EHIP, "crgpu_knn_dev: a query's buffer lost its count");
+    CR_REQUIRE(ctx, (uint32_t)ctr[3] == 0u, CRGPU_EHIP, "%s: a query's buffer lost its count", c.who);
     if (res->indices_out) CR_TRY(crgpu_memcpy_d2h(ctx, res->indices_out, ind_b.p, nq * k * sizeof(int32_t)));
     if (res->distances_out) CR_TRY(crgpu_memcpy_d2h(ctx, res->distances_out, dist_b.p, nq * k * sizeof(double)));
     if (res->sorted_out) CR_TRY(crgpu_memcpy_d2h(ctx, res->sorted_out, sorted_b.p, nq * k * sizeof(int32_t)));
@@ -342,7 +350,48 @@ extern "C" int crgpu_knn_dev(crgpu_ctx *ctx, const double *x, uint64_t n, uint32
     CR_HIP(ctx, hipEventElapsedTime(&ms_b, ev[1], ev[2]));
     res->select_ms = ms_a, res->sort_ms = ms_b;
     res->fit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    res->compactions = ctr[0], res->selections = ctr[1], res->survivors = ctr[2], res->pairs_evaluated = nq * n;
+    res->compactions = ctr[0], res->selections = ctr[1], res->survivors = ctr[2], res->pairs_evaluated = nq * c.nc;
     res->in_lds = s.in_lds, res->capacity = cap, res->query_tiles = n_tiles, res->cand_tile = tile;
     return CRGPU_OK;
 }
+
+extern "C" int crgpu_knn_dev(crgpu_ctx *ctx, const double *x, uint64_t n, uint32_t d, uint64_t ld, uint32_t k, const crgpu_knn_args *a,
+                             crgpu_knn_result *res) {
+    if (!ctx || !x || !a || !res) return CRGPU_EINVAL;
+    CR_ENTER(ctx);
+    // every refusal below and in knn_run comes before the device is touched
+    CR_REQUIRE(ctx, n >= 2 && n < (1ull << 31), CRGPU_EINVAL, "crgpu_knn_dev: %llu rows, 2 to 2^31 - 1", (unsigned long long)n);
+    CR_REQUIRE(ctx, d >= 1 && d <= CRGPU_KM_MAX_D && ld >= d, CRGPU_EINVAL, "crgpu_knn_dev: %u dimensions (1 to %u) in rows of %llu", d, CRGPU_KM_MAX_D,
+               (unsigned long long)ld);
+    CR_REQUIRE(ctx, k >= 1 && k <= CRGPU_KNN_MAX_K && k < n, CRGPU_EINVAL, "crgpu_knn_dev: k = %u, 1 to min(%u, the %llu rows - 1)", k, CRGPU_KNN_MAX_K,
+               (unsigned long long)n);
+    const bool all = a->query_start == 0 && a->n_queries == 0;
+    const uint64_t q0 = a->query_start, nq = all ? n : a->n_queries;
+    CR_REQUIRE(ctx, nq >= 1 && q0 < n && nq <= n - q0, CRGPU_EINVAL, "crgpu_knn_dev: queries %llu + %llu of %llu rows", (unsigned long long)q0,
+               (unsigned long long)a->n_queries, (unsigned long long)n);
+    const KnnCall c = {"crgpu_knn_dev", n, ld, q0, nq, 0, n, d, k, 1u, a->capacity, a->force_device, a->cand_tile, a->reserved, true};
+    return knn_run(ctx, x, c, res);
+}
+
+// find_knn(cur_matrix, ref_matrix, knn) of CORRECT_CHEMISTRY_BATCH: the k first pairs (d2, j) over the candidate rows alone, nothing
+// dropped, the indices global row numbers (include/crgpu.h)
+extern "C" int crgpu_knn_cross_dev(crgpu_ctx *ctx, const double *x, uint64_t n, uint32_t d, uint64_t ld, uint32_t k, const crgpu_knn_cross_args *a,
+                                   crgpu_knn_result *res) {
+    if (!ctx || !x || !a || !res) return CRGPU_EINVAL;
+    CR_ENTER(ctx);
+    CR_REQUIRE(ctx, n >= 1 && n < (1ull << 31), CRGPU_EINVAL, "crgpu_knn_cross_dev: %llu rows, 1 to 2^31 - 1", (unsigned long long)n);
+    CR_REQUIRE(ctx, d >= 1 && d <= CRGPU_KM_MAX_D && ld >= d, CRGPU_EINVAL, "crgpu_knn_cross_dev: %u dimensions (1 to %u) in rows of %llu", d,
+               CRGPU_KM_MAX_D, (unsigned long long)ld);
+    CR_REQUIRE(ctx, a->n_queries >= 1 && a->query_start < n && a->n_queries <= n - a->query_start, CRGPU_EINVAL,
+               "crgpu_knn_cross_dev: queries %llu + %llu of %llu rows", (unsigned long long)a->query_start, (unsigned long long)a->n_queries,
+               (unsigned long long)n);
+    CR_REQUIRE(ctx, a->n_cands >= 1 && a->cand_start < n && a->n_cands <= n - a->cand_start, CRGPU_EINVAL,
+               "crgpu_knn_cross_dev: candidates %llu + %llu of %llu rows", (unsigned long long)a->cand_start, (unsigned long long)a->n_cands,
+               (unsigned long long)n);
+    CR_REQUIRE(ctx, k >= 1 && k <= CRGPU_KNN_MAX_K && k <= a->n_cands, CRGPU_EINVAL, "crgpu_knn_cross_dev: k = %u, 1 to min(%u, the %llu candidates)", k,
+               CRGPU_KNN_MAX_K, (unsigned long long)a->n_cands);
+    const KnnCall c = {"crgpu_knn_cross_dev", n, ld, a->query_start, a->n_queries, a->cand_start, a->n_cands, d, k, 0u, a->capacity, a->force_device,
+                       a->cand_tile, a->reserved, false};
+    return knn_run(ctx, x, c, res);
+}
+

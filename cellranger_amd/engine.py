@@ -3,11 +3,13 @@
 The product path: every method ends in a libcrgpu call; there is no CPU implementation behind
 any of them (a missing library / GPU raises CrgpuError).
 """
+import collections
 import csv
 import ctypes as C
 import io
 import math
 import os
+import time
 
 import numpy as np
 
@@ -1219,6 +1221,162 @@ def run_graph_clustering(ctx, projection, num_neighbors=None, neighbor_a=None, n
         out["labels"] = louvain_labels(n if num_barcodes is None else num_barcodes, np.arange(n) if use_bcs is None else use_bcs, pairs)
         out["clusters"] = relabel_by_size(out["labels"])
     return out
+
+
+def mnn_pairs(a, start_i, b, start_j):
+    """mutual_nn[(i, j)] of CORRECT_CHEMISTRY_BATCH's join() (crgpu_mnn_pairs, host only): a i32[n_i, k] = the neighbours in batch j (global
+    rows, batch j = the rows from start_j) of the rows start_i .. of batch i, b i32[n_j, k] the other direction
+    -> (pairs i32[m, 2] in ascending (row of i, row of j) order, distinct rows of i, distinct rows of j)"""
+    a, b = np.ascontiguousarray(a, dtype=np.int32), np.ascontiguousarray(b, dtype=np.int32)
+    if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1]:
+        raise ValueError("mnn_pairs: two lists of k neighbours per row")
+    pairs = np.zeros((a.size, 2), np.int32)
+    m, n_first, n_second = C.c_uint64(), C.c_uint64(), C.c_uint64()
+    rc = _lib.load().crgpu_mnn_pairs(ptr(a), a.shape[0], int(start_i), ptr(b), b.shape[0], int(start_j), a.shape[1], ptr(pairs), len(pairs),
+                                     C.byref(m), C.byref(n_first), C.byref(n_second))
+    if rc != 0:
+        raise _lib.CrgpuError(rc, "crgpu_mnn_pairs")
+    return pairs[:m.value].copy(), int(n_first.value), int(n_second.value)
+
+
+def batch_effect_score(ctx, projection, batch_ids, knn_neighbors=None, knn_frac=0.01, max_num_bcs=10000):
+    """batch_effect_score (analysis/batch_correction.py:20-103): per row the share of its k nearest rows with its own batch id, rescaled so
+    that 1 = the batches mix and the number of batches = they are apart; the mean over the rows.  More than max_num_bcs rows are
+    subsampled WITH replacement as the reference does (RandomState(0).choice, sorted); NaN when that loses a batch or leaves one with
+    fewer than two rows.  k = knn_neighbors or ceil(knn_frac * rows).  The neighbours are Context.knn's (its first-pair drop is the
+    reference's knn_idx[:, 1:]); the fractions and the mean are numpy on the host.  k > 1024 or k >= rows: ValueError"""
+    if knn_neighbors is None and knn_frac is None:
+        raise ValueError("batch_effect_score: one of knn_neighbors or knn_frac")
+    x, ids = np.asarray(projection, dtype=np.float64), np.asarray(batch_ids)
+    num_bcs = x.shape[0]
+    if x.ndim != 2 or ids.shape != (num_bcs,):
+        raise ValueError("batch_effect_score: one batch id per row of the cells x PCs projection")
+    n_orig = len(np.unique(ids))
+    if max_num_bcs is not None and num_bcs > max_num_bcs:
+        select = np.random.RandomState(0).choice(num_bcs, max_num_bcs)
+        select.sort()
+        x, ids, num_bcs = x[select], ids[select], len(select)
+    names, inverse, counts = np.unique(ids, return_inverse=True, return_counts=True)
+    if len(names) != n_orig or counts.min() < 2:
+        return float("nan")
+    k = int(knn_neighbors) if knn_neighbors is not None else int(np.ceil(knn_frac * num_bcs))
+    if not 1 <= k <= _lib.KNN_MAX_K or k >= num_bcs:
+        raise ValueError("batch_effect_score: k = %d, 1 to min(%d, the %d rows - 1)" % (k, _lib.KNN_MAX_K, num_bcs))
+    null_frac = np.array([(c - 1) / (num_bcs - 1) for c in counts.tolist()])[inverse]
+    max_frac = np.array([min(c - 1, k) / k for c in counts.tolist()])[inverse]
+    knn_idx = ctx.knn(np.ascontiguousarray(x), k)["indices"]
+    same_frac = np.mean(ids[:, None] == ids[knn_idx], axis=1)
+    local = 1 + (len(names) - 1) * (same_frac - null_frac) / (max_frac - null_frac)
+    return float(np.mean(local))
+
+
+def cbc_schedule(ranges, mutual_nn, overlap, alpha=_lib.CBC_ALPHA, realign_panorama=_lib.CBC_REALIGN_PANORAMA):
+    """the panorama loop of CORRECT_CHEMISTRY_BATCH's join() as host code that only produces the merge schedule (it depends on the
+    overlaps alone, so it is known before any correction).  ranges: per batch its (first row, end row); mutual_nn: {(i, j): i32[m, 2]},
+    overlap: {(i, j): float}, both in (i, j) order -> (align_orders, steps); a step = dict(ref_batches, cur_batches, cur_rows i32,
+    mnn_cur i32, mnn_ref i32): the pairs in ascending (cur, ref) order"""
+    align_orders = [key for key, v in sorted(overlap.items(), key=lambda kv: kv[1], reverse=True) if v > alpha]
+    size = lambda pano: sum(ranges[b][1] - ranges[b][0] for b in pano)  # noqa: E731
+    panoramas, count, steps = [], collections.defaultdict(int), []
+    for i, j in align_orders:
+        at = {}
+        for idx, pano in enumerate(panoramas):
+            for b in (i, j):
+                if b in pano:
+                    assert b not in at, "batch is found in multiple panorama"
+                    at[b] = idx
+        for b in (i, j):
+            if b not in at:
+                panoramas.append({b})
+                at[b] = len(panoramas) - 1
+        pi, pj = at[i], at[j]
+        if realign_panorama:
+            count[i] += 1
+            count[j] += 1
+            if count[i] > 3 and count[j] > 3:
+                continue
+        elif pi == pj:
+            continue
+        if size(panoramas[pi]) < size(panoramas[pj]):       # the larger panorama is the reference
+            pi, pj = pj, pi
+        cur_batches, ref_batches = sorted(panoramas[pj]), sorted(panoramas[pi])
+        cur_rows = np.concatenate([np.arange(ranges[b][0], ranges[b][1], dtype=np.int32) for b in cur_batches])
+        matches = [np.zeros((0, 2), np.int32)]
+        for ref in ref_batches:
+            for cur in cur_batches:
+                if ref < cur and (ref, cur) in mutual_nn:
+                    matches.append(np.asarray(mutual_nn[(ref, cur)], np.int32).reshape(-1, 2)[:, ::-1])
+                if ref > cur and (cur, ref) in mutual_nn:
+                    matches.append(np.asarray(mutual_nn[(cur, ref)], np.int32).reshape(-1, 2))
+        matches = np.concatenate(matches)
+        matches = matches[np.lexsort((matches[:, 1], matches[:, 0]))]
+        steps.append(dict(ref_batches=ref_batches, cur_batches=cur_batches, cur_rows=cur_rows, mnn_cur=np.ascontiguousarray(matches[:, 0]),
+                          mnn_ref=np.ascontiguousarray(matches[:, 1])))
+        if pi != pj:
+            panoramas[pi].update(panoramas[pj])
+            panoramas.pop(pj)
+    return align_orders, steps
+
+
+def correct_chemistry_batch(ctx, projection, batch_ids, knn=_lib.CBC_KNN, alpha=_lib.CBC_ALPHA, sigma=_lib.CBC_SIGMA,
+                            realign_panorama=_lib.CBC_REALIGN_PANORAMA, n_batch_ids=None):
+    """CORRECT_CHEMISTRY_BATCH (stages/analyzer/correct_chemistry_batch): split()'s reorder (the batches in id order 0 .. n_batch_ids - 1,
+    empty ids skipped), one Context.knn_cross per ordered pair of batches, mnn_pairs and the overlap per unordered pair, align_orders,
+    the merge schedule (cbc_schedule), ONE Context.batch_correct with that schedule, both scores, the order put back
+    -> dict(aligned f64 in the input's row order, batch_score_before, batch_score_after, mutual_nn {(i, j): i32[m, 2]}, overlap,
+    align_orders, steps [dict(ref_batches, cur_batches, n_cur, n_mnn)], need_reorder, ranges, knn_ms, mnn_ms, score_ms, correct =
+    Context.batch_correct's counters and times).  A batch smaller than knn: ValueError (the reference pairs the wrong rows there)"""
+    x, ids = np.ascontiguousarray(projection, dtype=np.float64), np.asarray(batch_ids)
+    if x.ndim != 2 or ids.shape != (x.shape[0],) or not np.issubdtype(ids.dtype, np.integer):
+        raise ValueError("correct_chemistry_batch: one integer batch id per row of the cells x PCs projection")
+    nb = int(ids.max()) + 1 if n_batch_ids is None else int(n_batch_ids)
+    if ids.min() < 0 or ids.max() >= nb:
+        raise ValueError("correct_chemistry_batch: batch ids 0 .. %d" % (nb - 1))
+    order, ranges, reordered_ids, base = [], [], [], 0
+    for b_id in range(nb):
+        rows = np.where(ids == b_id)[0]
+        if len(rows) == 0:
+            continue
+        if len(rows) < knn:
+            raise ValueError("correct_chemistry_batch: batch %d has %d rows, fewer than knn = %d" % (b_id, len(rows), knn))
+        order.append(rows)
+        ranges.append((base, base + len(rows)))
+        reordered_ids.append(np.full(len(rows), b_id, ids.dtype))
+        base += len(rows)
+    order, idx_to_batch_id = np.concatenate(order), np.concatenate(reordered_ids)
+    need_reorder = not bool(np.all(np.diff(order) >= 0))
+    if need_reorder:
+        x = np.ascontiguousarray(x[order])
+    t0 = time.perf_counter()
+    score_before = batch_effect_score(ctx, x, idx_to_batch_id)
+    score_ms = (time.perf_counter() - t0) * 1e3
+    nn, knn_ms = {}, 0.0
+    for i, (lo_i, hi_i) in enumerate(ranges):
+        for j, (lo_j, hi_j) in enumerate(ranges):
+            if i != j:
+                r = ctx.knn_cross(x, knn, lo_i, hi_i - lo_i, lo_j, hi_j - lo_j)
+                nn[(i, j)] = r["indices"]
+                knn_ms += r["fit_ms"]
+    t0 = time.perf_counter()
+    mutual_nn, overlap = collections.OrderedDict(), collections.OrderedDict()
+    for i in range(len(ranges)):
+        for j in range(i + 1, len(ranges)):
+            pairs, n_first, n_second = mnn_pairs(nn[(i, j)], ranges[i][0], nn[(j, i)], ranges[j][0])
+            mutual_nn[(i, j)] = pairs
+            overlap[(i, j)] = max(float(n_first) / (ranges[i][1] - ranges[i][0]), float(n_second) / (ranges[j][1] - ranges[j][0]))
+    align_orders, steps = cbc_schedule(ranges, mutual_nn, overlap, alpha, realign_panorama)
+    mnn_ms = (time.perf_counter() - t0) * 1e3
+    res = ctx.batch_correct(x, steps, sigma)
+    aligned = res.pop("aligned")
+    t0 = time.perf_counter()
+    score_after = batch_effect_score(ctx, aligned, idx_to_batch_id)
+    score_ms += (time.perf_counter() - t0) * 1e3
+    if need_reorder:
+        aligned = aligned[np.argsort(order)]
+    return dict(aligned=aligned, batch_score_before=score_before, batch_score_after=score_after, mutual_nn=mutual_nn, overlap=overlap,
+                align_orders=align_orders, steps=[dict(ref_batches=s["ref_batches"], cur_batches=s["cur_batches"], n_cur=len(s["cur_rows"]),
+                                                       n_mnn=len(s["mnn_cur"])) for s in steps],
+                need_reorder=need_reorder, ranges=ranges, knn_ms=knn_ms, mnn_ms=mnn_ms, score_ms=score_ms, correct=res)
 
 
 def sseq_adjust_bh(p):
@@ -2477,6 +2635,69 @@ class Context:
         o.update(compactions=int(r.compactions), selections=int(r.selections), survivors=int(r.survivors), pairs_evaluated=int(r.pairs_evaluated),
                  in_lds=bool(r.in_lds), capacity=int(r.capacity), query_tiles=int(r.query_tiles), cand_tile=int(r.cand_tile), fit_ms=r.fit_ms,
                  select_ms=r.select_ms, sort_ms=r.sort_ms)
+        return o
+
+    def knn_cross(self, projection, k, query_start, n_queries, cand_start, n_cands, num_pcs=None, capacity=0, force_device=False, cand_tile=0):
+        """find_knn(cur_matrix, ref_matrix, knn) of CORRECT_CHEMISTRY_BATCH = BallTree(ref).query(cur, k), exactly and by brute force on
+        the device (crgpu_knn_cross_dev, csrc/knn.hip): for the rows query_start .. + n_queries of the f64 projection [cells x PCs] the
+        first k entries in the order of the pairs (d2, index) over the rows cand_start .. + n_cands ALONE; nothing is dropped; the
+        indices are global row numbers.  k > n_cands is refused.  capacity / force_device / cand_tile: test seams, no result depends on
+        them -> the dict of Context.knn (pairs_evaluated = n_queries * n_cands)"""
+        x = np.ascontiguousarray(projection, dtype=np.float64)
+        if x.ndim != 2:
+            raise ValueError("knn_cross: the projection is cells x PCs")
+        n, ld = x.shape
+        d = ld if num_pcs is None else int(num_pcs)
+        q0, nq, c0, nc, k = int(query_start), int(n_queries), int(cand_start), int(n_cands), int(k)
+        if q0 < 0 or nq < 1 or q0 + nq > n or c0 < 0 or nc < 1 or c0 + nc > n:
+            raise ValueError("knn_cross: queries %d + %d, candidates %d + %d of %d rows" % (q0, nq, c0, nc, n))
+        if not 1 <= k <= _lib.KNN_MAX_K:      # the output arrays need a shape; the library refuses the rest
+            raise ValueError("knn_cross: k = %d, 1 to %d" % (k, _lib.KNN_MAX_K))
+        o = dict(indices=np.zeros((nq, k), np.int32), distances=np.zeros((nq, k)), sorted_indices=np.zeros((nq, k), np.int32))
+        a = _lib.KnnCrossArgs(query_start=q0, n_queries=nq, cand_start=c0, n_cands=nc, capacity=int(capacity), force_device=1 if force_device else 0,
+                              cand_tile=int(cand_tile))
+        r = _lib.KnnResult(indices_out=ptr(o["indices"]), distances_out=ptr(o["distances"]), sorted_out=ptr(o["sorted_indices"]))
+        self._check(self.L.crgpu_knn_cross_dev(self.h, ptr(x), n, d, ld, k, C.byref(a), C.byref(r)))
+        o.update(compactions=int(r.compactions), selections=int(r.selections), survivors=int(r.survivors), pairs_evaluated=int(r.pairs_evaluated),
+                 in_lds=bool(r.in_lds), capacity=int(r.capacity), query_tiles=int(r.query_tiles), cand_tile=int(r.cand_tile), fit_ms=r.fit_ms,
+                 select_ms=r.select_ms, sort_ms=r.sort_ms)
+        return o
+
+    def batch_correct(self, projection, steps, sigma=_lib.CBC_SIGMA, num_pcs=None, want_corr=False, pair_tile=0, row_tile=0, slab_rows=0):
+        """a merge schedule of CORRECT_CHEMISTRY_BATCH with the matrix resident on the device (crgpu_batch_correct_dev,
+        csrc/batch_correction.hip).  steps: a list of dict(cur_rows, mnn_cur, mnn_ref) (or such triples): per step corr =
+        correction_vector(x, cur_rows, mnn_cur, mnn_ref, sigma) from the matrix as it stands, then x[cur_rows] += corr.  No step: the
+        matrix comes back bit for bit.  A cur row whose weights all underflow gets NaN, as numpy gives.  pair_tile / row_tile /
+        slab_rows: test seams, no result depends on them
+        -> dict(aligned f64[n, d], corr (want_corr: a list of f64[n_cur, d]), step_ms f64[steps, 4] = gather, accumulate, finish, apply,
+        fit_ms, upload_ms, download_ms, gather_ms, accumulate_ms, finish_ms, apply_ms, pairs_evaluated, chunks, zero_den_rows, pair_tile,
+        row_tile)"""
+        x = np.ascontiguousarray(projection, dtype=np.float64)
+        if x.ndim != 2:
+            raise ValueError("batch_correct: the projection is cells x PCs")
+        n, ld = x.shape
+        d = ld if num_pcs is None else int(num_pcs)
+        if not 1 <= d <= ld:
+            raise ValueError("batch_correct: %d of %d columns" % (d, ld))
+        lists = []
+        for s in steps:
+            cur, mc, mr = (s["cur_rows"], s["mnn_cur"], s["mnn_ref"]) if isinstance(s, dict) else s
+            cur, mc, mr = (np.ascontiguousarray(v, dtype=np.int32).reshape(-1) for v in (cur, mc, mr))
+            if len(mc) != len(mr):
+                raise ValueError("batch_correct: mnn_cur and mnn_ref pair up")
+            lists.append((cur, mc, mr, np.zeros((len(cur), d)) if want_corr else None))
+        arr = (_lib.BcStep * max(len(lists), 1))()
+        for i, (cur, mc, mr, corr) in enumerate(lists):
+            arr[i] = _lib.BcStep(cur_rows=ptr(cur), mnn_cur=ptr(mc), mnn_ref=ptr(mr), corr_out=ptr(corr), n_cur=len(cur), n_mnn=len(mc))
+        aligned, step_ms = np.zeros((n, d)), np.zeros((max(len(lists), 1), 4))
+        a = _lib.BcArgs(pair_tile=int(pair_tile), row_tile=int(row_tile), slab_rows=int(slab_rows))
+        r = _lib.BcResult(step_ms_out=ptr(step_ms))
+        self._check(self.L.crgpu_batch_correct_dev(self.h, ptr(x), n, d, ld, float(sigma), arr, len(lists), ptr(aligned), C.byref(a), C.byref(r)))
+        o = dict(aligned=aligned, step_ms=step_ms[:len(lists)], fit_ms=r.fit_ms, upload_ms=r.upload_ms, download_ms=r.download_ms, gather_ms=r.gather_ms,
+                 accumulate_ms=r.accumulate_ms, finish_ms=r.finish_ms, apply_ms=r.apply_ms, pairs_evaluated=int(r.pairs_evaluated), chunks=int(r.chunks),
+                 zero_den_rows=int(r.zero_den_rows), pair_tile=int(r.pair_tile), row_tile=int(r.row_tile))
+        if want_corr:
+            o["corr"] = [c for _, _, _, c in lists]
         return o
 
     def sseq_params(self, m, n_features=None):

@@ -1940,6 +1940,110 @@ int crgpu_knn_dev(crgpu_ctx *ctx, const double *x, uint64_t n, uint32_t d, uint6
                   crgpu_knn_result *result);
 int crgpu_graphclust_num_neighbors(uint64_t n, uint32_t num_neighbors, double a, double b, uint32_t *k_out);
 
+/* ---- CORRECT_CHEMISTRY_BATCH: batch-balanced neighbours, mutual nearest neighbours, the correction of the merged batches ----------------
+ * mro/rna/stages/analyzer/correct_chemistry_batch/__init__.py and lib/python/cellranger/analysis/batch_correction.py: split() puts the
+ * rows of a batch next to each other, main() queries every other batch for the cbc_knn nearest rows of each row of its own (find_knn),
+ * join() intersects the two directions of a batch pair (mutual_nn), ranks the pairs by overlap_percentage, stitches panoramas in that
+ * order and moves the smaller panorama of a merge by correction_vector; batch_effect_score before and after.
+ *   crgpu_knn_cross_dev          find_knn(cur_matrix, ref_matrix, knn) = BallTree(ref, leaf_size = 40).query(cur, k): x, n, d, ld as
+ *                                crgpu_knn_dev (after split()'s reorder the batches are row ranges of ONE matrix).  The result of a
+ *                                query row is the first k entries of the ascending order of the pairs (d2, j) over the CANDIDATE
+ *                                rows only; NOTHING is dropped (crgpu_knn_dev drops the first pair); d2, the TIE RULE and the root as
+ *                                crgpu_knn_dev's.  The indices are GLOBAL row numbers (the reference's nn_idx_right +=
+ *                                barcode_index_left).  1 <= k <= min(n_cands, CRGPU_KNN_MAX_K), both ranges inside the rows (they
+ *                                may overlap), every value of the two ranges finite; anything else is CRGPU_EINVAL before the device
+ *                                is touched.  Bit-identical between runs, between a query range and a larger one, under every seam.
+ *   crgpu_knn_cross_args         query_start, n_queries, cand_start, n_cands: the two row ranges (no default: n_queries, n_cands >= 1);
+ *                                capacity, force_device, cand_tile: the seams of crgpu_knn_args (capacity from k + 4); reserved 0.
+ *                                The result is a crgpu_knn_result: pairs_evaluated = n_queries * n_cands.
+ *   crgpu_mnn_pairs              host only, no context.  A batch pair i < j: batch i = the rows start_i .. start_i + n_i, batch j the
+ *                                rows start_j .. start_j + n_j; a: i32[n_i x k], row r = the neighbours of row start_i + r in batch j
+ *                                (global indices); b: i32[n_j x k] likewise into batch i.  The mutual pairs (p, q): q in a[p] AND p
+ *                                in b[q], as a set, written in ascending (p, q) order to pairs_out i32[.][2] (NULL = counted only;
+ *                                capacity rows, n_i * k always suffices; more pairs than capacity is CRGPU_EINVAL with *n_pairs_out
+ *                                set), *n_first_out = distinct p, *n_second_out = distinct q.  This is mutual_nn[(i, j)] = nn_ij &
+ *                                {(y, x) for x, y in nn_ji} and the two set sizes of overlap_percentage (the caller divides by the
+ *                                batch sizes and takes the larger).  The stage's main() files the pairs of EARLIER batches under
+ *                                later keys too (from_idx / to_idx grow across its loop): the intersection removes them, because
+ *                                every first element of nn_ij lies in batch i and every second element of the reversed nn_ji in
+ *                                batch j, so only pairs between i and j survive.  An index outside its batch is CRGPU_EINVAL.
+ *   crgpu_batch_correct_dev      a whole merge schedule with the matrix resident on the device.  x: host f64, n x d, leading
+ *                                dimension ld, const; x_out: host f64 n x d (packed), the aligned matrix; steps: n_steps descriptors,
+ *                                run in order.  n_steps = 0 returns x bit for bit; one step with corr_out set is correction_vector.
+ *       a step                   gamma = 0.5 * sigma (the reference's gamma = 0.5 * sigma; the name is the reference's, it is no
+ *                                width).  For a cur row c (cur_rows, distinct: the rows that move) and a pair p (mnn_cur[p],
+ *                                mnn_ref[p]):  y_p = x[mnn_cur[p]];  b_p = x[mnn_ref[p]] - y_p;  w_cp = exp((-gamma) * d2(x_c, y_p)),
+ *                                d2 as above.  The pairs are cut into chunks of CRGPU_BC_PAIR_CHUNK consecutive pairs; within a
+ *                                chunk num_t adds w_cp * b_pt and den adds w_cp, both left to right from 0.0; the chunks' partials
+ *                                are then added left to right; corr_ct = num_t / den.  Every product and sum unfused, f64.  So the
+ *                                value is a pure function of (x, the lists, sigma): bit-identical between runs, between a sub-list
+ *                                of cur_rows and the whole, and under every seam.  All corr of a step are computed from the matrix
+ *                                as it stood at the step's start, then x[cur_rows] += corr (with cbc_realign_panorama the cur and
+ *                                ref rows overlap).  The caller supplies the pair order; the reference's is a Python set's and
+ *                                only moves the order of the sums.
+ *       QUIRK kept               a row whose weights all underflow has den = 0 and gets NaN (0 / 0), as numpy gives.  No maximum is
+ *                                subtracted in the exponent: that would turn the reference's NaN into a number.
+ *       on the device            per step (csrc/batch_correction.hip): a gather kernel makes Y and B (n_mnn x d each); the
+ *                                accumulate kernel has one workgroup per (tile of row_tile cur rows, pair chunk): tiles of pair_tile
+ *                                pairs of Y, then of B, stream through LDS; first the tile's weights go to LDS, several pairs per
+ *                                read of a row's coordinate; then a thread owns 4 rows by up to 4 dimensions in registers and walks
+ *                                the tile's pairs in ascending order; the chunk's partial num[d] and den go to a slab with plain
+ *                                stores; a finish kernel adds the chunks in order and divides; an apply kernel adds into x.  No
+ *                                floating-point atomic.
+ *   crgpu_bc_step                cur_rows i32[n_cur], mnn_cur, mnn_ref i32[n_mnn] each, corr_out f64[n_cur x d] or NULL
+ *   crgpu_bc_args                seams, FIELDS and not environment switches, 0 = the default, none moves a bit: pair_tile = pairs per
+ *                                LDS tile (a multiple of 8 up to what 72 KiB of LDS hold for d and row_tile, at most 64); row_tile =
+ *                                cur rows per workgroup (16, 32 or 64; default 32); slab_rows = cur rows whose partials are kept at
+ *                                a time (a multiple of row_tile; default by memory); reserved 0
+ *   crgpu_bc_result              step_ms_out: f64[n_steps x 4] or NULL, per step the device time of gather, accumulate, finish, apply;
+ *                                their totals; fit_ms = host time of the call, upload_ms, download_ms; pairs_evaluated = the sum of
+ *                                n_cur * n_mnn; chunks = the sum of the steps' pair chunks; zero_den_rows = rows that got 0 / 0;
+ *                                pair_tile, row_tile of the last step
+ *   refused with CRGPU_EINVAL before the device is touched: d = 0 or d > CRGPU_KM_MAX_D, ld < d, n = 0 or n >= 2^31, a non-finite value,
+ *   a non-finite or negative sigma, an index outside the rows, repeated cur_rows, n_mnn = 0 or n_cur = 0 in a step, a NULL that is not
+ *   optional (x, x_out, args, result, steps when n_steps > 0, a step's three lists), an illegal seam.
+ * NOT covered: batches smaller than knn (k > n_cands is refused on purpose: the reference takes min(ref rows, knn) neighbours but
+ * repeats the left indices cbc_knn times, so its zip pairs the wrong rows), the H5, CSV and pickle writers, float32, and PCA itself. */
+#define CRGPU_BC_PAIR_CHUNK 2048
+struct crgpu_knn_cross_args {
+    uint64_t query_start, n_queries;   /* the query rows */
+    uint64_t cand_start, n_cands;      /* the candidate rows */
+    uint32_t capacity;                 /* seam: pairs of a query's buffer, 0 = default */
+    uint32_t force_device;             /* seam: 1 = the buffers in device memory */
+    uint32_t cand_tile;                /* seam: candidate rows per LDS tile, 0 = default */
+    uint32_t reserved;
+};
+typedef struct crgpu_knn_cross_args crgpu_knn_cross_args;
+struct crgpu_bc_step {
+    const int32_t *cur_rows;           /* i32[n_cur], distinct */
+    const int32_t *mnn_cur;            /* i32[n_mnn] each */
+    const int32_t *mnn_ref;
+    double *corr_out;                  /* f64[n_cur x d] or NULL */
+    uint64_t n_cur, n_mnn;
+};
+typedef struct crgpu_bc_step crgpu_bc_step;
+struct crgpu_bc_args {
+    uint32_t pair_tile;                /* seam: pairs per LDS tile, 0 = default */
+    uint32_t row_tile;                 /* seam: cur rows per workgroup, 0 = default */
+    uint32_t slab_rows;                /* seam: cur rows whose partials are kept at a time, 0 = default */
+    uint32_t reserved;
+};
+typedef struct crgpu_bc_args crgpu_bc_args;
+struct crgpu_bc_result {
+    double *step_ms_out;               /* f64[n_steps x 4] or NULL */
+    double fit_ms, upload_ms, download_ms;
+    double gather_ms, accumulate_ms, finish_ms, apply_ms;
+    uint64_t pairs_evaluated, chunks, zero_den_rows;
+    uint32_t pair_tile, row_tile;
+};
+typedef struct crgpu_bc_result crgpu_bc_result;
+int crgpu_knn_cross_dev(crgpu_ctx *ctx, const double *x, uint64_t n, uint32_t d, uint64_t ld, uint32_t k, const crgpu_knn_cross_args *args,
+                        crgpu_knn_result *result);
+int crgpu_mnn_pairs(const int32_t *a, uint64_t n_i, uint64_t start_i, const int32_t *b, uint64_t n_j, uint64_t start_j, uint32_t k,
+                    int32_t *pairs_out, uint64_t capacity, uint64_t *n_pairs_out, uint64_t *n_first_out, uint64_t *n_second_out);
+int crgpu_batch_correct_dev(crgpu_ctx *ctx, const double *x, uint64_t n, uint32_t d, uint64_t ld, double sigma, const crgpu_bc_step *steps,
+                            uint32_t n_steps, double *x_out, const crgpu_bc_args *args, crgpu_bc_result *result);
+
 /* ---- synthetic workloads (bench / tests) ---------------------------------------------
  * Counter-based integer generator: read i of a given seed is identical on the host and on the
  * device.  Tables are host arrays built by cellranger_amd.synth. */

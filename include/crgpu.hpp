@@ -1427,6 +1427,67 @@ inline Knn knn(Context &ctx, const double *x, uint64_t n, uint32_t d, uint64_t l
     return o;
 }
 
+// ---- CORRECT_CHEMISTRY_BATCH: batch-balanced neighbours, mutual nearest neighbours, the correction of the merged batches ---------------
+static_assert(sizeof(crgpu_knn_cross_args) == 48, "crgpu_knn_cross_args changed: bump CRGPU_ABI_VERSION and every binding");
+static_assert(sizeof(crgpu_bc_step) == 48, "crgpu_bc_step changed: bump CRGPU_ABI_VERSION and every binding");
+static_assert(sizeof(crgpu_bc_args) == 16, "crgpu_bc_args changed: bump CRGPU_ABI_VERSION and every binding");
+static_assert(sizeof(crgpu_bc_result) == 96, "crgpu_bc_result changed: bump CRGPU_ABI_VERSION and every binding");
+/// crgpu_knn_cross_dev: find_knn(cur, ref, k) = BallTree(ref).query(cur, k) for the query rows query_start .. + n_queries against the
+/// candidate rows cand_start .. + n_cands ALONE; nothing dropped, global indices; capacity / force_device / cand_tile = the test seams
+inline Knn knn_cross(Context &ctx, const double *x, uint64_t n, uint32_t d, uint64_t ld, uint32_t k, uint64_t query_start, uint64_t n_queries,
+                     uint64_t cand_start, uint64_t n_cands, uint32_t capacity = 0, uint32_t force_device = 0, uint32_t cand_tile = 0) {
+    Knn o;
+    o.n_queries = n_queries, o.k = k;
+    const size_t m = (size_t)n_queries * k;
+    o.indices.assign(m, 0), o.sorted_indices.assign(m, 0), o.distances.assign(m, 0.0);
+    crgpu_knn_cross_args a = {query_start, n_queries, cand_start, n_cands, capacity, force_device, cand_tile, 0};
+    o.info = crgpu_knn_result{o.indices.data(), o.distances.data(), o.sorted_indices.data(), 0.0, 0.0, 0.0, 0, 0, 0, 0, 0, 0, 0, 0};
+    ctx.check(crgpu_knn_cross_dev(ctx.get(), x, n, d, ld, k, &a, &o.info));
+    return o;
+}
+struct MnnPairs {
+    std::vector<int32_t> pairs;                    // [n][2]: (row of batch i, row of batch j), ascending
+    uint64_t n_first = 0, n_second = 0;            // distinct rows of i, of j: the numerators of overlap_percentage
+};
+/// crgpu_mnn_pairs (host only): a = [n_i][k] neighbours in batch j of the rows start_i .., b = [n_j][k] the other direction, global indices
+inline MnnPairs mnn_pairs(const std::vector<int32_t> &a, uint64_t start_i, const std::vector<int32_t> &b, uint64_t start_j, uint32_t k) {
+    MnnPairs o;
+    uint64_t n = 0;
+    o.pairs.assign(2 * a.size() + 2, 0);
+    const int rc = k ? crgpu_mnn_pairs(a.data(), a.size() / k, start_i, b.data(), b.size() / k, start_j, k, o.pairs.data(), a.size(), &n, &o.n_first, &o.n_second)
+                     : CRGPU_EINVAL;
+    if (rc != CRGPU_OK) throw Error(rc, "mnn_pairs");
+    o.pairs.resize(2 * n);
+    return o;
+}
+struct BcStep {
+    std::vector<int32_t> cur_rows, mnn_cur, mnn_ref;
+};
+struct BatchCorrect {
+    std::vector<double> aligned;                   // [n][d]
+    std::vector<std::vector<double>> corr;         // per step [n_cur][d] (want_corr)
+    std::vector<double> step_ms;                   // [steps][4]: gather, accumulate, finish, apply
+    crgpu_bc_result info{};
+};
+/// crgpu_batch_correct_dev: the steps in order, corr from the matrix as it stands at a step's start, then x[cur_rows] += corr;
+/// pair_tile / row_tile / slab_rows = the test seams (0 = default), which change no result
+inline BatchCorrect batch_correct(Context &ctx, const double *x, uint64_t n, uint32_t d, uint64_t ld, double sigma, const std::vector<BcStep> &steps,
+                                  bool want_corr = false, uint32_t pair_tile = 0, uint32_t row_tile = 0, uint32_t slab_rows = 0) {
+    BatchCorrect o;
+    o.aligned.assign((size_t)n * d, 0.0), o.step_ms.assign(4 * steps.size() + 4, 0.0), o.corr.resize(want_corr ? steps.size() : 0);
+    std::vector<crgpu_bc_step> st(steps.size() + 1);
+    for (size_t i = 0; i < steps.size(); i++) {
+        if (want_corr) o.corr[i].assign(steps[i].cur_rows.size() * d, 0.0);
+        st[i] = crgpu_bc_step{steps[i].cur_rows.data(), steps[i].mnn_cur.data(), steps[i].mnn_ref.data(), want_corr ? o.corr[i].data() : nullptr,
+                              steps[i].cur_rows.size(), std::min(steps[i].mnn_cur.size(), steps[i].mnn_ref.size())};
+    }
+    crgpu_bc_args a = {pair_tile, row_tile, slab_rows, 0};
+    o.info.step_ms_out = o.step_ms.data();
+    ctx.check(crgpu_batch_correct_dev(ctx.get(), x, n, d, ld, sigma, st.data(), (uint32_t)steps.size(), o.aligned.data(), &a, &o.info));
+    o.step_ms.resize(4 * steps.size());
+    return o;
+}
+
 // ---- protein aggregates of an antibody / antigen well; the closing filters of a cell call ---------------------------------------------
 static_assert(sizeof(crgpu_aggregates_info) == 48, "crgpu_aggregates_info changed: bump CRGPU_ABI_VERSION and every binding");
 /// int(np.round(n_signal * _calculate_fraction_to_use(n_signal)))
