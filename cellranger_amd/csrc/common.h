@@ -97,6 +97,8 @@ struct FeatureExtractorSet {
     bool t_pre_dots = false, t_suf_dots = false;  // prefix / suffix are wildcards only
     // up to four leading literal characters of the suffix (else of the prefix): a floating pattern is first looked for by them
     uint32_t t_needle = 0, t_needle_len = 0, t_needle_off = 0;
+    // a feature of 32 T packs to the value the LDS set keeps for an empty slot: such an extractor takes the generic kernel
+    bool t_has_empty_key = false;
 };
 
 // Captures that the one-pattern extraction kernel found no exact feature for, kept by a call WITHOUT a feature distribution

@@ -311,6 +311,7 @@ __global__ __launch_bounds__(256) void k_extract_features_queued(const FxView v,
 //     queued per workgroup and corrected with every lane busy; only they touch the quality rows (in global memory).
 // Same results as fx_match_read for an extractor with one tethered pattern; tests/test_gpu_feature_extract.py runs both.
 #define FXT_EMPTY 0xFFFFFFFFFFFFFFFFull
+#define FXT_LDS_BYTES (160u * 1024u - 512u)  // dynamic LDS a workgroup may take (the kernel's static part is below 512 bytes)
 struct FxtParams {
     uint32_t read, anchor5, anchor3, pre_len, suf_len, L, n_feat;
     uint32_t pre_dots, suf_dots;  // the prefix / suffix hold wildcards only: nothing to compare
@@ -960,6 +961,7 @@ extern "C" int crgpu_set_feature_extractor(crgpu_ctx *ctx, int extractor, const 
         X.t_n_feat = (uint32_t)P0.feats.size();
         X.t_pre_dots = P0.prefix.find_first_not_of('.') == std::string::npos;
         X.t_suf_dots = P0.suffix.find_first_not_of('.') == std::string::npos;
+        X.t_has_empty_key = std::find(key.begin(), key.end(), (uint64_t)FXT_EMPTY) != key.end();
         const std::string &src = (!P0.suffix.empty() && P0.suffix[0] != '.') ? P0.suffix : P0.prefix;
         if (!src.empty() && src[0] != '.') {
             uint32_t len = 0;
@@ -1045,7 +1047,8 @@ extern "C" int crgpu_extract_features_dev(crgpu_ctx *ctx, int extractor, const u
              (const uint32_t *)(base + X.off_hb_f)};
     FxRows r1{d_r1_seq, d_r1_qual, d_r1_len, r1_stride}, r2{d_r2_seq, d_r2_qual, d_r2_len, r2_stride};
     // ---- one tethered pattern: wave-per-rows kernel with the table in LDS (k_extract_tethered_lds) ----------------------
-    if (X.one_tethered && X.t_n_feat <= 4096u && !getenv("CRGPU_FEATURES_GLOBAL")) {
+    // (a feature of 32 T equals FXT_EMPTY: the LDS set cannot hold it, so that extractor stays with the generic kernel)
+    if (X.one_tethered && X.t_n_feat <= 4096u && !X.t_has_empty_key && !getenv("CRGPU_FEATURES_GLOBAL")) {
         const FxRows &R = X.t_read ? r2 : r1;
         const uint32_t need = X.t_pre_len + X.t_L + X.t_suf_len;
         const bool aligned = R.stride % 4 == 0 && (uintptr_t)R.seq % 4 == 0;
@@ -1057,7 +1060,14 @@ extern "C" int crgpu_extract_features_dev(crgpu_ctx *ctx, int extractor, const u
         }
         else if (X.t_anchor3 && !R.len && need <= R.stride) win_lo = (R.stride - need) & ~3u;
         const uint32_t win_dw = (win_hi - win_lo) / 4u;
-        if (aligned && win_dw >= 1 && win_dw <= 64u && R.stride >= 4 && X.t_pre_len + X.t_suf_len <= 256u) {
+        uint32_t slots = 64;
+        while (slots < 2u * X.t_n_feat) slots <<= 1;  // load factor <= 0.5
+        // dynamic LDS of either kernel size; a large table under a wide window does not fit: the generic kernel takes the call
+        const bool halves = X.has_dist && X.t_n_feat <= 1024u && X.t_L >= 2;
+        const size_t lds = X.t_n_feat <= 1024u
+                               ? (size_t)slots * 12 + (halves ? (size_t)X.t_n_feat * 24 : 0) + (size_t)4 * 64 * (win_dw | 1u) * 4 + 8 + 2 * 256 * sizeof(FxtPending)
+                               : (size_t)slots * 12 + (size_t)16 * 64 * (win_dw | 1u) * 4 + 8 + 2 * 1024 * sizeof(FxtPending);
+        if (aligned && win_dw >= 1 && win_dw <= 64u && R.stride >= 4 && X.t_pre_len + X.t_suf_len <= 256u && lds <= FXT_LDS_BYTES) {
             FxtParams P{};
             P.read = X.t_read;
             P.anchor5 = X.t_anchor5;
@@ -1079,16 +1089,13 @@ extern "C" int crgpu_extract_features_dev(crgpu_ctx *ctx, int extractor, const u
                 while (P.quad_lanes < (win_dw + 3u) / 4u) P.quad_lanes <<= 1;
             }
             P.prefetch = P.quad_lanes == 1u || P.quad_lanes == 2u;
-            uint32_t slots = 64;
-            while (slots < 2u * X.t_n_feat) slots <<= 1;  // load factor <= 0.5
             P.slot_mask = slots - 1u;
             if (X.t_needle_len && !X.t_anchor5 && !X.t_anchor3) {  // anchored patterns have one start: nothing to skip
                 P.needle = X.t_needle;
                 P.needle_mask = X.t_needle_len >= 4 ? 0xFFFFFFFFu : ((1u << (8u * X.t_needle_len)) - 1u);
                 P.needle_off = X.t_needle_off;
             }
-            P.halves = X.has_dist && X.t_n_feat <= 1024u && X.t_L >= 2;
-            const size_t half_bytes = P.halves ? (size_t)X.t_n_feat * 24 : 0;
+            P.halves = halves;
             // first pass of the two-pass flow (no distribution, by-products allowed): keep the captures without exact feature
             FxtPending *d_recs = (FxtPending *)resume.d_recs;
             unsigned long long *d_rec_count = (unsigned long long *)(ctx->d_scalars + CR_SCALAR_REC_COUNT);
@@ -1108,13 +1115,11 @@ extern "C" int crgpu_extract_features_dev(crgpu_ctx *ctx, int extractor, const u
             const uint64_t work = n_recs_in ? n_recs_in : n;
             CrTimer t(ctx, CRGPU_T_FEATURE, work);
             if (X.t_n_feat <= 1024u) {
-                const size_t lds = (size_t)slots * 12 + half_bytes + (size_t)4 * 64 * P.pitch * 4 + 8 + 2 * 256 * sizeof(FxtPending);
                 cr_allow_lds(ctx, (const void *)k_extract_tethered_lds<256>, lds);
                 hipLaunchKernelGGL(k_extract_tethered_lds<256>, dim3(cr_grid(work, 256, 256u * 4u)), dim3(256), lds, ctx->stream, v, P,
                                    d_pe, R, n, d_feature_out, d_n_ids_out, d_capture_out, rec_cap || n_recs_in ? d_recs : nullptr, d_rec_count,
                                    rec_cap, n_recs_in);
             } else {
-                const size_t lds = (size_t)slots * 12 + (size_t)16 * 64 * P.pitch * 4 + 8 + 2 * 1024 * sizeof(FxtPending);
                 cr_allow_lds(ctx, (const void *)k_extract_tethered_lds<1024>, lds);
                 hipLaunchKernelGGL(k_extract_tethered_lds<1024>, dim3(cr_grid(work, 1024, 256u)), dim3(1024), lds, ctx->stream, v, P, d_pe,
                                    R, n, d_feature_out, d_n_ids_out, d_capture_out, rec_cap || n_recs_in ? d_recs : nullptr, d_rec_count,
