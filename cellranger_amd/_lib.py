@@ -390,7 +390,24 @@ class BcResult(C.Structure):
         (n, C.c_uint64) for n in ("pairs_evaluated", "chunks", "zero_den_rows")] + [(n, C.c_uint32) for n in ("pair_tile", "row_tile")]
 
 
+class PcaArgs(C.Structure):
+    """crgpu_pca_args"""
+    _fields_ = [("pca_bc_indices", C.c_void_p), ("n_pca_bcs", C.c_uint64), ("start", C.c_void_p), ("n_start", C.c_uint64)] + [
+        (n, C.c_uint32) for n in ("n_components", "pca_features", "min_count_threshold", "seed", "wave_block", "dot_parts_per_block", "reserved0",
+                                  "reserved1")]
+
+
+class PcaResult(C.Structure):
+    """crgpu_pca_result"""
+    _fields_ = [(n, C.c_void_p) for n in ("transformed_out", "components_out", "variance_explained_out", "dispersion_out", "features_selected_out",
+                                           "d_out")] + [
+        (n, C.c_double) for n in ("fit_ms", "prepare_ms", "lanczos_ms", "project_ms")] + [
+        (n, C.c_uint64) for n in ("n_thresholded_barcodes", "n_pca_barcodes")] + [
+        (n, C.c_uint32) for n in ("status", "n_components", "n_used_features", "n_thresholded_features", "it", "mprod", "m_b", "reserved")]
+
+
 KM_MAX_K, KM_MAX_D, KM_MAX_LIST = 64, 128, 64
+PCA_MAX_COMPONENTS, PCA_DEFAULT_THRESHOLD, PCA_OK, PCA_NULL_AXIS, PCA_RANK_TOO_SMALL = 128, 2, 0, 1, 2
 KNN_MAX_K, KNN_MAX_CAPACITY = 1024, 4096
 BC_PAIR_CHUNK, BC_LDS_BYTES, BC_MAX_PAIR_TILE = 2048, 73728, 64
 CBC_KNN, CBC_ALPHA, CBC_SIGMA, CBC_REALIGN_PANORAMA = 10, 0.1, 150.0, False
@@ -573,6 +590,10 @@ SYMBOLS = {
     "crgpu_knn_cross_dev": (_i, [_vp, _vp, _u64, _u32, _u64, _u32, C.POINTER(KnnCrossArgs), C.POINTER(KnnResult)]),
     "crgpu_mnn_pairs": (_i, [_vp, _u64, _u64, _vp, _u64, _u64, _u32, _vp, _u64, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
     "crgpu_batch_correct_dev": (_i, [_vp, _vp, _u64, _u32, _u64, _dbl, C.POINTER(BcStep), _u32, _vp, C.POINTER(BcArgs), C.POINTER(BcResult)]),
+    "crgpu_pca_dev": (_i, [_vp, C.POINTER(MatrixDevView), _u32, C.POINTER(PcaArgs), C.POINTER(PcaResult)]),
+    "crgpu_legacy_randn": (_i, [_u32, _u64, _vp]),
+    "crgpu_normalized_dispersion": (_i, [_vp, _vp, _u64, _u32, _vp]),
+    "crgpu_small_svd": (_i, [_vp, _u32, _vp, _vp, _vp]),
     "crgpu_aggregate_min_antibodies": (_i, [_u32, C.POINTER(_u32)]),
     "crgpu_antigen_outlier_threshold": (_i, [_vp, _u32, C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_dbl)]),
     "crgpu_aggregates_by_counts_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, _u32, _vp, _vp, _u32, C.POINTER(_u32),

@@ -433,6 +433,38 @@ const std::vector<AbiStruct> &abi_table() {
               ABI_F(crgpu_bc_result, zero_den_rows),
               ABI_F(crgpu_bc_result, pair_tile),
               ABI_F(crgpu_bc_result, row_tile)),
+        ABI_S(crgpu_pca_args, ABI_F(crgpu_pca_args, pca_bc_indices),
+              ABI_F(crgpu_pca_args, n_pca_bcs),
+              ABI_F(crgpu_pca_args, start),
+              ABI_F(crgpu_pca_args, n_start),
+              ABI_F(crgpu_pca_args, n_components),
+              ABI_F(crgpu_pca_args, pca_features),
+              ABI_F(crgpu_pca_args, min_count_threshold),
+              ABI_F(crgpu_pca_args, seed),
+              ABI_F(crgpu_pca_args, wave_block),
+              ABI_F(crgpu_pca_args, dot_parts_per_block),
+              ABI_F(crgpu_pca_args, reserved0),
+              ABI_F(crgpu_pca_args, reserved1)),
+        ABI_S(crgpu_pca_result, ABI_F(crgpu_pca_result, transformed_out),
+              ABI_F(crgpu_pca_result, components_out),
+              ABI_F(crgpu_pca_result, variance_explained_out),
+              ABI_F(crgpu_pca_result, dispersion_out),
+              ABI_F(crgpu_pca_result, features_selected_out),
+              ABI_F(crgpu_pca_result, d_out),
+              ABI_F(crgpu_pca_result, fit_ms),
+              ABI_F(crgpu_pca_result, prepare_ms),
+              ABI_F(crgpu_pca_result, lanczos_ms),
+              ABI_F(crgpu_pca_result, project_ms),
+              ABI_F(crgpu_pca_result, n_thresholded_barcodes),
+              ABI_F(crgpu_pca_result, n_pca_barcodes),
+              ABI_F(crgpu_pca_result, status),
+              ABI_F(crgpu_pca_result, n_components),
+              ABI_F(crgpu_pca_result, n_used_features),
+              ABI_F(crgpu_pca_result, n_thresholded_features),
+              ABI_F(crgpu_pca_result, it),
+              ABI_F(crgpu_pca_result, mprod),
+              ABI_F(crgpu_pca_result, m_b),
+              ABI_F(crgpu_pca_result, reserved)),
     };
     return t;
 }

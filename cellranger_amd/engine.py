@@ -1138,6 +1138,59 @@ def run_kmeans(ctx, projection, max_clusters=10, min_clusters=2, seed=0, num_pcs
     return out
 
 
+class MatrixRankTooSmall(Exception):
+    """run_pca's MatrixRankTooSmallException: min(features, barcodes) after thresholding < n_components at the threshold 2"""
+
+
+class NullAxisMatrix(Exception):
+    """NullAxisMatrixError of select_axes_above_threshold: no barcode, or no feature, with a sum above the threshold"""
+
+
+def run_pca(ctx, m, n_components=10, pca_features=None, pca_bc_indices=None, seed=0, n_features=None, **seams):
+    """RUN_PCA for one library type (mro/rna/stages/analyzer/run_pca/__init__.py:57-80): Context.pca of the filtered MatrixDev `m` (one
+    feature type: select_features_dev) at the threshold 2 and, after MatrixRankTooSmall or NullAxisMatrix, at the threshold 0, where
+    n_components is reduced to min(features, barcodes) -> the dict of Context.pca with retried = the second call was needed.  Its
+    `projection` goes into run_kmeans, run_graph_clustering and correct_chemistry_batch unchanged.  A NullAxisMatrix of the second call
+    is raised.  pca_bc_indices are positions among the barcodes THE CALL's threshold leaves"""
+    try:
+        r = ctx.pca(m, n_components, pca_features, pca_bc_indices, seed, _lib.PCA_DEFAULT_THRESHOLD, n_features=n_features, **seams)
+        r["retried"] = False
+    except (MatrixRankTooSmall, NullAxisMatrix):
+        r = ctx.pca(m, n_components, pca_features, pca_bc_indices, seed, 0, n_features=n_features, **seams)
+        r["retried"] = True
+    return r
+
+
+def legacy_randn(seed, n):
+    """np.random.RandomState(seed).randn(n) by the library (crgpu_legacy_randn, host only)"""
+    out = np.zeros(int(n))
+    rc = _lib.load().crgpu_legacy_randn(int(seed), int(n), ptr(out))
+    if rc != 0:
+        raise ValueError("legacy_randn: refused (%d)" % rc)
+    return out
+
+
+def normalized_dispersion(mu, var, nbins=20):
+    """get_normalized_dispersion by the library (crgpu_normalized_dispersion, host only)"""
+    mu, var = np.ascontiguousarray(mu, dtype=np.float64), np.ascontiguousarray(var, dtype=np.float64)
+    out = np.zeros(len(mu))
+    rc = _lib.load().crgpu_normalized_dispersion(ptr(mu), ptr(var), len(mu), int(nbins), ptr(out))
+    if rc != 0:
+        raise ValueError("normalized_dispersion: refused (%d)" % rc)
+    return out
+
+
+def small_svd(b):
+    """B = U diag(s) Vt by the library's one-sided Jacobi (crgpu_small_svd, host only) -> (U, s, Vt)"""
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    n = len(b)
+    u, s, vt = np.zeros((n, n)), np.zeros(n), np.zeros((n, n))
+    rc = _lib.load().crgpu_small_svd(ptr(b), n, ptr(u), ptr(s), ptr(vt))
+    if rc != 0:
+        raise ValueError("small_svd: refused (%d)" % rc)
+    return u, s, vt
+
+
 def graphclust_num_neighbors(n, num_neighbors=None, neighbor_a=None, neighbor_b=None):
     """split() of RUN_GRAPH_CLUSTERING (crgpu_graphclust_num_neighbors, host only): int(max(num_neighbors, np.round(a + b * log10(n))))
     clamped to [1, n - 1]; None = the reference's defaults 1, -230.0, 120.0"""
@@ -2698,6 +2751,50 @@ class Context:
                  zero_den_rows=int(r.zero_den_rows), pair_tile=int(r.pair_tile), row_tile=int(r.row_tile))
         if want_corr:
             o["corr"] = [c for _, _, _, c in lists]
+        return o
+
+    def pca(self, m, n_components=10, pca_features=None, pca_bc_indices=None, seed=0, min_count_threshold=0, start=None, n_features=None,
+            wave_block=0, dot_parts_per_block=0, want_projection=True):
+        """run_pca of the filtered MatrixDev `m` (features x barcodes, one feature type: select_features_dev) at ONE threshold on the device
+        (csrc/pca.hip): thresholding, the dispersion order of the features, IRLBA on the centred and scaled log matrix, the projection of
+        every barcode -> dict(transformed_pca_matrix = projection f64[barcodes, n_components], components f64[n_components, features],
+        variance_explained, dispersion (NaN = removed by the threshold), features_selected (rows of m in the order of org_cols_used), d, it,
+        mprod, m_b, n_components (reduced to min(features, barcodes) when the threshold is not 2), the counts and the times).
+        pca_features None = every thresholded feature; pca_bc_indices: ascending positions among the thresholded barcodes, None = all;
+        start: the first Lanczos vector before normalisation (None: RandomState(seed).randn).  MatrixRankTooSmall / NullAxisMatrix as the
+        reference raises them.  wave_block / dot_parts_per_block: seams, no result depends on them.  The sign of a component is the
+        library's (include/crgpu.h, SIGN OF A COMPONENT), not LAPACK's"""
+        if n_features is None:
+            n_features = getattr(m, "n_features", None) or getattr(self, "n_features", None)
+            if n_features is None:
+                raise ValueError("pca: pass n_features")
+        G, V, nc = int(n_features), int(m.n_barcodes), int(n_components)
+        if not 1 <= nc <= _lib.PCA_MAX_COMPONENTS:      # the output arrays need a shape; the library refuses the rest
+            raise ValueError("pca: n_components = %d, 1 to %d" % (nc, _lib.PCA_MAX_COMPONENTS))
+        bcs = None if pca_bc_indices is None else np.ascontiguousarray(pca_bc_indices, dtype=np.uint64)
+        st = None if start is None else np.ascontiguousarray(start, dtype=np.float64)
+        o = dict(transformed_pca_matrix=np.zeros((V, nc)) if want_projection else None, components=np.zeros((nc, G)), variance_explained=np.zeros(nc),
+                 dispersion=np.zeros(G), features_selected=np.zeros(G, np.int32), d=np.zeros(nc))
+        a = _lib.PcaArgs(pca_bc_indices=ptr(bcs), n_pca_bcs=0 if bcs is None else len(bcs), start=ptr(st), n_start=0 if st is None else len(st),
+                         n_components=nc, pca_features=int(pca_features or 0), min_count_threshold=int(min_count_threshold), seed=int(seed),
+                         wave_block=int(wave_block), dot_parts_per_block=int(dot_parts_per_block))
+        r = _lib.PcaResult(**{k + "_out": ptr(v) for k, v in o.items() if k != "transformed_pca_matrix"})
+        r.transformed_out = ptr(o["transformed_pca_matrix"])
+        self._check(self.L.crgpu_pca_dev(self.h, m._mv, G, C.byref(a), C.byref(r)))
+        if r.status == _lib.PCA_NULL_AXIS:
+            raise NullAxisMatrix("pca: no barcode or no feature with a sum above %d" % min_count_threshold)
+        if r.status == _lib.PCA_RANK_TOO_SMALL:
+            raise MatrixRankTooSmall("Matrix rank is too small")
+        nu = int(r.n_components)
+        if want_projection:      # the rows were written with the stride of the components used
+            o["transformed_pca_matrix"] = np.ascontiguousarray(o["transformed_pca_matrix"].ravel()[:V * nu].reshape(V, nu))
+        o["components"] = np.ascontiguousarray(o["components"].ravel()[:nu * G].reshape(nu, G))
+        o["variance_explained"], o["d"] = o["variance_explained"][:nu], o["d"][:nu]
+        o["features_selected"] = o["features_selected"][:int(r.n_used_features)]
+        o.update(projection=o["transformed_pca_matrix"], n_components=nu, it=int(r.it), mprod=int(r.mprod), m_b=int(r.m_b),
+                 n_used_features=int(r.n_used_features), n_thresholded_features=int(r.n_thresholded_features),
+                 n_thresholded_barcodes=int(r.n_thresholded_barcodes), n_pca_barcodes=int(r.n_pca_barcodes), min_count_threshold=int(min_count_threshold),
+                 fit_ms=r.fit_ms, prepare_ms=r.prepare_ms, lanczos_ms=r.lanczos_ms, project_ms=r.project_ms)
         return o
 
     def sseq_params(self, m, n_features=None):

@@ -2044,6 +2044,110 @@ int crgpu_mnn_pairs(const int32_t *a, uint64_t n_i, uint64_t start_i, const int3
 int crgpu_batch_correct_dev(crgpu_ctx *ctx, const double *x, uint64_t n, uint32_t d, uint64_t ld, double sigma, const crgpu_bc_step *steps,
                             uint32_t n_steps, double *x_out, const crgpu_bc_args *args, crgpu_bc_result *result);
 
+/* ---- RUN_PCA: the dispersion order of the features, IRLBA, the projection (csrc/pca.hip) ----------------------------------------------
+ * The stage the sections above leave out ("PCA itself"): run_pca with normalize_and_transpose (lib/python/cellranger/analysis/pca.py:49-209,
+ * 212-229), normalize_by_umi, summarize_columns and get_normalized_dispersion (analysis/stats.py), irlb (analysis/irlb.py:61-231) and
+ * select_axes_above_threshold (matrix.py:788-810), on a filtered crgpu_matrix_dev restricted to ONE feature type
+ * (crgpu_select_features_dev).  Its transformed_pca_matrix is the projection crgpu_kmeans_dev, crgpu_knn_dev, crgpu_knn_cross_dev and
+ * crgpu_batch_correct_dev take.  All of it f64; the mean and variance of a feature follow scikit-learn 1.7.2's mean_variance_axis.
+ *   crgpu_pca_dev                m: features x barcodes, n_features its rows.  In the reference's order: the barcodes with a sum above
+ *                                min_count_threshold, then the features whose sum over THOSE barcodes is above it; the dispersion of the
+ *                                thresholded matrix (normalised by UMI, not logged); the features np.argsort(dispersion, kind =
+ *                                "stable")[-pca_features:] -- NaN after every number, equal values by index -- in that order (it fixes
+ *                                which entry of the start vector a feature gets, also when every feature is used); the PCA matrix of the
+ *                                barcodes pca_bc_indices of the thresholded ones and those features, log2(1 + count * median / sum),
+ *                                centred and scaled by ITS mean and standard deviation (variance 0 becomes 1); irlb with tol = 1e-4,
+ *                                maxit = 50, m_b = min(nu + 20, 3 nu, min(shape)), k = min(max(conv + nu, k), m_b - 3), invcheck with
+ *                                2 eps, smax; the projection of EVERY barcode of m with the full matrix's OWN median, centre and scale.
+ *   crgpu_pca_args               pca_bc_indices: host, n_pca_bcs strictly ascending positions among the thresholded barcodes, NULL / 0 =
+ *                                all of them; start: host, n_start = the number of used features values, finite, NULL / 0 = the
+ *                                reference's np.random.RandomState(seed).randn (crgpu_legacy_randn); n_components 1 ..
+ *                                CRGPU_PCA_MAX_COMPONENTS; pca_features 0 = every thresholded feature (the stage's default), a larger
+ *                                number is cut to them; min_count_threshold (the stage: 2, then 0).  Seams, fields and NOT environment
+ *                                switches, no bit of a result depends on them: wave_block = threads of a workgroup of the wave-per-row
+ *                                kernels (64, 128, 256; 0 = 256), dot_parts_per_block = 256-row partials of the dots a workgroup takes
+ *                                (1 .. 64; 0 = 1; the partial itself stays 256 rows); reserved0, reserved1 = 0.
+ *   crgpu_pca_result             pointers the caller sets, NULL = not wanted (without transformed_out the full matrix is not prepared):
+ *                                transformed_out f64[n_barcodes x n_components] row-major with the stride of the n_components USED
+ *                                (room for args.n_components); components_out f64[n_components x n_features], 0 outside the used
+ *                                features; variance_explained_out, d_out f64[n_components]; dispersion_out f64[n_features], NaN for the
+ *                                features the threshold removed; features_selected_out i32[n_used_features] (room for n_features): the
+ *                                rows of org_cols_used in that order.  status: CRGPU_PCA_OK; CRGPU_PCA_NULL_AXIS (no barcode or no feature
+ *                                above the threshold: NullAxisMatrixError) or CRGPU_PCA_RANK_TOO_SMALL (min(features, barcodes) <
+ *                                n_components at the threshold CRGPU_PCA_DEFAULT_THRESHOLD: MatrixRankTooSmallException) -- the call
+ *                                returns CRGPU_OK, nothing else is written, the stage then calls again with the threshold 0, where
+ *                                n_components is reduced to min(features, barcodes) instead.  n_components, n_used_features,
+ *                                n_thresholded_features, n_thresholded_barcodes, n_pca_barcodes; it (restarts) and mprod (products) as
+ *                                irlb returns them, m_b; the times of the whole call and of preparation / Lanczos / projection.
+ *   crgpu_legacy_randn           host, no context: np.random.RandomState(seed).randn(n) bit for bit -- MT19937 seeded by init_genrand,
+ *                                53-bit doubles from two words, the legacy polar method with its cached second value
+ *   crgpu_normalized_dispersion  host, no context: get_normalized_dispersion(mu, var, nbins) -- np.percentile (linear) at 0, 100 // nbins,
+ *                                ..., the appended maximum, np.unique, binned_statistic's medians twice (left-closed bins, the last one
+ *                                closed on both sides), the raw dispersion when one quantile is left; x / 0 and 0 / 0 as IEEE has them
+ *   crgpu_small_svd              host, no context: B (row-major n x n, n <= 148, finite) = U diag(s) Vt by one-sided Jacobi in f64, s
+ *                                descending, U and Vt row-major
+ *   on the device                three preparations (thresholded, PCA, full matrix: they have different medians, centres and scales): the
+ *                                sums per barcode from crgpu_matrix_dev_column_sums, their median through the radix sort, the values in
+ *                                barcode order and, by one radix sort of feature * N + barcode keys, in feature order; a wave per feature
+ *                                for mean and variance; the two products of the implicit operator A - 1 c^T, a wave per cell and a wave
+ *                                per feature; dots over partials of 256 rows written to a slab and added in order; the projection, a wave
+ *                                per barcode.  Lane l takes the entries l, l + 64, ..., the lanes are joined by the tree 32, 16, ..., 1:
+ *                                the sum order of an output element depends on the number of its entries alone.  No floating-point
+ *                                atomic, no graph capture, no cooperative launch; the loop of irlb is the host's, it reads two scalars
+ *                                (s, fn) a step.  Results are bit-identical between runs and under every seam.
+ *   QUIRKS kept (the reference's): ZERO-COUNT BARCODE -- a barcode of the full matrix without counts has no entries, its factor x / 0 is
+ *                                never used, its projection row is -(c / s)[cols] . v.  START VECTOR NORM -- the start vector is divided by
+ *                                the Frobenius norm of the whole V, which is the vector's own norm.  THRESHOLD ORDER -- thresholding comes
+ *                                before any subsetting (pca_bc_indices, pca_features) and is not repeated.  After maxit restarts the
+ *                                restart products are applied and the last SVD is used once more, as the reference's loop leaves it.
+ *   SIGN OF A COMPONENT          NOT the reference's bit for bit: the reference takes the sign LAPACK gives a singular pair of B, which
+ *                                nothing specifies.  The rule here is crgpu_small_svd's: row-cyclic one-sided Jacobi from V = I, no sign
+ *                                normalised; a function of B alone, so the signs are the same between runs and under every seam.  The
+ *                                stages behind the projection use distances only and do not see a sign.
+ *   refused with CRGPU_EINVAL before the device is touched: n_components = 0 or > CRGPU_PCA_MAX_COMPONENTS, fewer than 2 features or
+ *   barcodes or 2^31 or more, a list without its length (or the reverse), pca_bc_indices that do not ascend, a start value that is not
+ *   finite, an illegal seam, a NULL context, matrix, args or result; after thresholding: a PCA matrix smaller than 2 x 2, a
+ *   pca_bc_indices entry beyond the thresholded barcodes, n_start other than the used features.  CRGPU_ERANGE: 2^32 or more entries, a
+ *   barcode sum beyond 32 bits.  CRGPU_ESTATE: a restart with m_b < 3 (the reference indexes from the end there).
+ * Not covered by this stage: the `pca_bcs` random subsample (the caller passes pca_bc_indices, ascending, as the other stages take their
+ * rows), the H5 and CSV writers, the memory model of split(), float32, normalize_by_idf and the LSA / PLSA reductions. */
+#define CRGPU_PCA_MAX_COMPONENTS 128
+#define CRGPU_PCA_DEFAULT_THRESHOLD 2
+#define CRGPU_PCA_OK 0
+#define CRGPU_PCA_NULL_AXIS 1
+#define CRGPU_PCA_RANK_TOO_SMALL 2
+struct crgpu_pca_args {
+    const uint64_t *pca_bc_indices;    /* u64[n_pca_bcs] or NULL */
+    uint64_t n_pca_bcs;
+    const double *start;               /* f64[n_start] or NULL */
+    uint64_t n_start;
+    uint32_t n_components;
+    uint32_t pca_features;             /* 0 = every thresholded feature */
+    uint32_t min_count_threshold;
+    uint32_t seed;
+    uint32_t wave_block;               /* seam: threads of a workgroup of the wave-per-row kernels, 0 = default */
+    uint32_t dot_parts_per_block;      /* seam: partials of the dots a workgroup takes, 0 = default */
+    uint32_t reserved0, reserved1;
+};
+typedef struct crgpu_pca_args crgpu_pca_args;
+struct crgpu_pca_result {
+    double *transformed_out;           /* f64[n_barcodes x n_components] or NULL */
+    double *components_out;            /* f64[n_components x n_features] or NULL */
+    double *variance_explained_out;    /* f64[n_components] or NULL */
+    double *dispersion_out;            /* f64[n_features] or NULL */
+    int32_t *features_selected_out;    /* i32[n_used_features] or NULL */
+    double *d_out;                     /* f64[n_components] or NULL */
+    double fit_ms, prepare_ms, lanczos_ms, project_ms;
+    uint64_t n_thresholded_barcodes, n_pca_barcodes;
+    uint32_t status, n_components, n_used_features, n_thresholded_features;
+    uint32_t it, mprod, m_b, reserved;
+};
+typedef struct crgpu_pca_result crgpu_pca_result;
+int crgpu_pca_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, uint32_t n_features, const crgpu_pca_args *args, crgpu_pca_result *result);
+int crgpu_legacy_randn(uint32_t seed, uint64_t n, double *out);
+int crgpu_normalized_dispersion(const double *mu, const double *var, uint64_t n, uint32_t nbins, double *out);
+int crgpu_small_svd(const double *B, uint32_t n, double *U, double *s, double *Vt);
+
 /* ---- synthetic workloads (bench / tests) ---------------------------------------------
  * Counter-based integer generator: read i of a given seed is identical on the host and on the
  * device.  Tables are host arrays built by cellranger_amd.synth. */

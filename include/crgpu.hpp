@@ -1488,6 +1488,43 @@ inline BatchCorrect batch_correct(Context &ctx, const double *x, uint64_t n, uin
     return o;
 }
 
+// ---- RUN_PCA: the dispersion order of the features, IRLBA, the projection ----------------------------------------------------------------
+static_assert(sizeof(crgpu_pca_args) == 64, "crgpu_pca_args changed: bump CRGPU_ABI_VERSION and every binding");
+static_assert(sizeof(crgpu_pca_result) == 128, "crgpu_pca_result changed: bump CRGPU_ABI_VERSION and every binding");
+struct Pca {
+    std::vector<double> transformed;               // [n_barcodes][n_components]
+    std::vector<double> components;                // [n_components][n_features], 0 outside the used features
+    std::vector<double> variance_explained, d;     // [n_components]
+    std::vector<double> dispersion;                // [n_features], NaN for the features the threshold removed
+    std::vector<int32_t> features_selected;        // the rows of org_cols_used, in that order
+    crgpu_pca_result info{};                       // status (CRGPU_PCA_*), n_components as used, it, mprod, the times
+};
+/// crgpu_pca_dev on a filtered matrix of one feature type: run_pca at ONE threshold.  info.status != CRGPU_PCA_OK: nothing was computed
+/// (the stage then calls again with min_count_threshold = 0).  wave_block / dot_parts_per_block = the test seams, which change no result
+inline Pca pca(Context &ctx, const crgpu_matrix_dev *m, uint32_t n_features, uint32_t n_components = 10, uint32_t pca_features = 0,
+               const std::vector<uint64_t> &pca_bc_indices = {}, uint32_t seed = 0, uint32_t min_count_threshold = CRGPU_PCA_DEFAULT_THRESHOLD,
+               const std::vector<double> &start = {}, uint32_t wave_block = 0, uint32_t dot_parts_per_block = 0) {
+    Pca o;
+    const uint32_t nc = n_components ? n_components : 1u;
+    o.transformed.assign((size_t)m->n_barcodes * nc, 0.0), o.components.assign((size_t)nc * n_features, 0.0);
+    o.variance_explained.assign(nc, 0.0), o.d.assign(nc, 0.0), o.dispersion.assign(n_features, 0.0), o.features_selected.assign(n_features, 0);
+    crgpu_pca_args a = {pca_bc_indices.empty() ? nullptr : pca_bc_indices.data(), pca_bc_indices.size(), start.empty() ? nullptr : start.data(), start.size(),
+                        n_components, pca_features, min_count_threshold, seed, wave_block, dot_parts_per_block, 0, 0};
+    o.info = crgpu_pca_result{o.transformed.data(), o.components.data(), o.variance_explained.data(), o.dispersion.data(), o.features_selected.data(),
+                              o.d.data(), 0.0, 0.0, 0.0, 0.0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    ctx.check(crgpu_pca_dev(ctx.get(), m, n_features, &a, &o.info));
+    const uint32_t nu = o.info.status == CRGPU_PCA_OK ? o.info.n_components : 0u;
+    o.transformed.resize((size_t)m->n_barcodes * nu), o.components.resize((size_t)nu * n_features);
+    o.variance_explained.resize(nu), o.d.resize(nu), o.features_selected.resize(o.info.status == CRGPU_PCA_OK ? o.info.n_used_features : 0u);
+    return o;
+}
+/// np.random.RandomState(seed).randn(n), bit for bit (host only)
+inline std::vector<double> legacy_randn(uint32_t seed, uint64_t n) {
+    std::vector<double> out(n);
+    if (crgpu_legacy_randn(seed, n, out.data()) != CRGPU_OK) throw Error(CRGPU_EINVAL, "legacy_randn");
+    return out;
+}
+
 // ---- protein aggregates of an antibody / antigen well; the closing filters of a cell call ---------------------------------------------
 static_assert(sizeof(crgpu_aggregates_info) == 48, "crgpu_aggregates_info changed: bump CRGPU_ABI_VERSION and every binding");
 /// int(np.round(n_signal * _calculate_fraction_to_use(n_signal)))
