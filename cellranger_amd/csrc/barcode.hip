@@ -242,7 +242,7 @@ __global__ __launch_bounds__(256) void k_lib_mask(const uint8_t *__restrict__ fl
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
         m |= 1u << (flags[i] & CRGPU_FLAG_LIB_MASK);
-    for (int o = 32; o > 0; o >>= 1) m |= __shfl_xor(m, o);
+    m = wave_or(m);
     if ((threadIdx.x & 63u) == 0u && m) atomicOr(mask_out, m);
 }
 
@@ -492,7 +492,7 @@ __global__ __launch_bounds__(256) void k_match_binned(const WlViewSet vs, const 
                 s += c[k];
             }
             uint32_t tot;
-            uint32_t run = block_excl_scan_256(s, lds, &tot);
+            uint32_t run = block_excl_scan<256>(s, lds, &tot);
             if (tid == 0) tile_hits = tot;
 #pragma unroll
             for (int k = 0; k < MB_BPT; k++) {
@@ -635,11 +635,7 @@ __global__ __launch_bounds__(256) void k_hot_build(const uint32_t *__restrict__ 
             }
     }
     if (sums) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            all += __shfl_xor(all, d);
-            hot += __shfl_xor(hot, d);
-        }
+        all = wave_sum(all), hot = wave_sum(hot);
         if ((threadIdx.x & 63u) == 0u) {
             atomicAdd(&sums[0], all);
             atomicAdd(&sums[1], hot);
@@ -1005,12 +1001,7 @@ __global__ __launch_bounds__(256) void k_stage_idx(const BinPlan plan, const uin
                 tot += c[w];
             }
             if (tid == SI_MISS_BUCKET) tot = 0;
-            uint32_t x = tot;
-#pragma unroll
-            for (int d = 1; d < 32; d <<= 1) {
-                const uint32_t y = __shfl_up(x, d);
-                if (tid >= (uint32_t)d) x += y;
-            }
+            const uint32_t x = wave_incl_scan<32>(tot, tid);
             uint32_t run = x - tot;
             tstart[tid] = run;
             if (tid == 30) tile_hits = x;  // buckets 0..30 are the hit buckets
@@ -1839,12 +1830,7 @@ __global__ __launch_bounds__(64 * KS_WAVES) void k_correct_sorted(const WlViewSe
                     const uint32_t lo = s_run[wv][lane >> 1][1u + 2u * (lane & 1u)], hi = s_run[wv][lane >> 1][2u + 2u * (lane & 1u)];
                     cnt = hi > lo ? (hi - (lo & ~1u) + 7u) / 8u : 0u;
                 }
-                uint32_t inc = cnt;
-#pragma unroll
-                for (uint32_t d = 1; d < 2u * KS_HEADS; d <<= 1) {
-                    const uint32_t y = __shfl_up(inc, d);
-                    if (lane >= d) inc += y;
-                }
+                const uint32_t inc = wave_incl_scan<2u * KS_HEADS>(cnt, lane);  // (lanes beyond: not used)
                 if (lane < 2u * KS_HEADS) s_first[wv][lane] = inc - cnt;
                 if (lane == 2u * KS_HEADS - 1u) s_first[wv][2 * KS_HEADS] = inc;
             }

@@ -4,41 +4,87 @@
 
 #include <cstdint>
 
-// Exclusive prefix of `v` over the 256 threads of a workgroup (4 waves); *total_out = block sum.
-// `lds` must hold >= 8 uint32.  Contains two barriers; every thread must call it.
-__device__ __forceinline__ uint32_t block_excl_scan_256(uint32_t v, uint32_t *lds, uint32_t *total_out) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t x = v;
+// Everything here assumes wave64: lane = threadIdx.x & 63, wave = threadIdx.x >> 6.
+
+// ---- one wave -------------------------------------------------------------------------------------------------------------
+// Butterfly reductions over the 64 lanes of a wave, distances 32 down to 1.  All 64 lanes must call them (an inactive lane's
+// register is read by its partner); the result is in every lane, and for the f64 forms it is the same bit pattern in every
+// lane, because the two partners of a step add (or compare) the same two operands.
+// Sum of 32-bit values, modulo 2^32: widen the argument where 64 values may not fit.
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 #pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d);
-        if (lane >= (uint32_t)d) x += y;
-    }
-    if (lane == 63u) lds[wave] = x;
-    __syncthreads();
-    uint32_t wpre = 0, tot = 0;
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+// 64 bits travel as two 32-bit shuffles
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
 #pragma unroll
-    for (uint32_t w = 0; w < 4; w++) {
-        const uint32_t t = lds[w];
-        if (w < wave) wpre += t;
-        tot += t;
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t lo = __shfl_xor((uint32_t)v, d), hi = __shfl_xor((uint32_t)(v >> 32), d);
+        v += ((unsigned long long)hi << 32) | lo;
     }
-    __syncthreads();  // lds may be reused by the caller's next call
-    if (total_out) *total_out = tot;
-    return wpre + x - v;
+    return v;
+}
+__device__ __forceinline__ long long wave_sum(long long v) { return (long long)wave_sum((unsigned long long)v); }
+// f64: step d adds lane ^ d's partial sum to the lane's own, so lane 0 computes ((((x0 + x32) + (x16 + x48)) + ...): the order
+// of a __shfl_down tree read at lane 0
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+// or / min / max, for the types the kernels use
+__device__ __forceinline__ uint32_t wave_or(uint32_t v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v |= __shfl_xor(v, d);
+    return v;
+}
+__device__ __forceinline__ uint32_t wave_min(uint32_t v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t o = __shfl_xor(v, d);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const int o = __shfl_xor(v, d);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+__device__ __forceinline__ double wave_max(double v) {  // fmax: a NaN loses against a number
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v = fmax(v, __shfl_xor(v, d));
+    return v;
 }
 
-// Same for a workgroup of THREADS threads (a multiple of 64, at most 1024).  `lds` >= THREADS/64 uint32.
+// Inclusive prefix sum of `v` over lanes 0 .. WIDTH - 1 of a wave (Hillis-Steele, __shfl_up by 1, 2, 4, .. WIDTH / 2; WIDTH a
+// power of two, 2 .. 64).  `lane` = the caller's lane.  May be called inside `if (lane < WIDTH)`: only the lanes below WIDTH
+// need to be active, their results are defined, and no lane reads a register of a lane >= WIDTH.  f64: lane i adds, at step d,
+// the partial sum of lanes (i - 2d, i - d] to its own of (i - d, i] -- `own + lower`, in this order of steps.
+template <uint32_t WIDTH = 64, typename T>
+__device__ __forceinline__ T wave_incl_scan(T v, uint32_t lane) {
+    static_assert(WIDTH >= 2 && WIDTH <= 64 && (WIDTH & (WIDTH - 1)) == 0, "WIDTH: a power of two, 2 .. 64");
+#pragma unroll
+    for (int d = 1; d < (int)WIDTH; d <<= 1) {
+        const T y = __shfl_up(v, d);
+        if (lane >= (uint32_t)d) v += y;
+    }
+    return v;
+}
+
+// ---- one workgroup --------------------------------------------------------------------------------------------------------
+// Exclusive prefix of `v` over a workgroup of THREADS threads (a multiple of 64, at most 1024); *total_out (nullable) = block
+// sum, in every thread.  `lds` >= THREADS/64 uint32.  Every thread must call it.  One barrier between the waves' totals and
+// their use, and a trailing one so that `lds` may be reused at once.
 // TRAILING_BARRIER = false: the caller guarantees a barrier of its own before anybody writes `lds` again.
 template <uint32_t THREADS, bool TRAILING_BARRIER = true>
 __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *lds, uint32_t *total_out) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d);
-        if (lane >= (uint32_t)d) x += y;
-    }
+    const uint32_t x = wave_incl_scan(v, lane);
     if (lane == 63u) lds[wave] = x;
     __syncthreads();
     uint32_t wpre = 0, tot = 0;
@@ -53,13 +99,46 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *lds, u
     return wpre + x - v;
 }
 
+// The sum of the WAVES words at `lds` (any thread).
+template <uint32_t WAVES>
+__device__ __forceinline__ uint32_t lds_sum(const uint32_t *lds) {
+    uint32_t t = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < WAVES; w++) t += lds[w];
+    return t;
+}
+// The count tail of a two-pass compaction: wave sum of `c`, lane 0 of every wave stores one word to lds[wave], ONE barrier, and
+// thread 0 stores the sum of the WAVES words to *out (the same address in every thread).  `lds` >= WAVES uint32.  Every thread
+// of the workgroup of WAVES waves must call it; no trailing barrier.
+template <uint32_t WAVES>
+__device__ __forceinline__ void block_sum_to_first(uint32_t c, uint32_t *lds, uint32_t *out) {
+    c = wave_sum(c);
+    if ((threadIdx.x & 63u) == 0) lds[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) *out = lds_sum<WAVES>(lds);
+}
+
+// The write tail of a two-pass compaction: threads 0 .. N - 1 (lanes of wave 0; N a power of two, 2 .. 64) replace the N counts
+// at `ws` (LDS) by their exclusive prefix, and thread N - 1 stores their sum to *total (LDS).  Any thread may call it; the
+// others do nothing.  NO barrier inside: the caller has one between the writes of the counts and this call, and one between
+// this call and the reads of the prefixes and of *total.
+template <uint32_t N>
+__device__ __forceinline__ void block_scan_words(uint32_t *ws, uint32_t *total) {
+    if (threadIdx.x < N) {
+        const uint32_t v = ws[threadIdx.x];
+        const uint32_t x = wave_incl_scan<N>(v, threadIdx.x);
+        ws[threadIdx.x] = x - v;
+        if (threadIdx.x == N - 1) *total = x;
+    }
+}
+
 // Reserve `my_count` consecutive output slots for this thread with ONE global atomic per workgroup
 // call (a single hot counter serialises at the memory side: one atomic per wave is ~300 k same-
 // address atomics for 20 M reads).  `lds` >= 10 uint32 (8-byte aligned).  Every thread must call it.
 __device__ __forceinline__ unsigned long long block_reserve_256(uint32_t my_count, unsigned long long *counter,
                                                                 uint32_t *lds) {
     uint32_t total;
-    const uint32_t pre = block_excl_scan_256(my_count, lds, &total);
+    const uint32_t pre = block_excl_scan<256>(my_count, lds, &total);
     unsigned long long *base_s = reinterpret_cast<unsigned long long *>(lds + 8);
     if (threadIdx.x == 0) *base_s = total ? atomicAdd(counter, (unsigned long long)total) : 0ull;
     __syncthreads();
@@ -132,28 +211,10 @@ __device__ __forceinline__ unsigned long long wave_lookback(const unsigned long 
             continue;  // somebody in front of the first inclusive prefix has not published yet: same window again
         }
         unsigned long long v = lane <= first ? (sv & ((1ull << 62) - 1ull)) : 0ull;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-        excl += v;
+        excl += wave_sum(v);
         if (first < 64u) return excl;
         end -= 64;
     }
-}
-
-// Sum of `v` over the 64 lanes of a wave, in every lane (all lanes must call it).  64 bits travel as two 32-bit shuffles.
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t lo = __shfl_xor((uint32_t)v, d), hi = __shfl_xor((uint32_t)(v >> 32), d);
-        v += ((unsigned long long)hi << 32) | lo;
-    }
-    return v;
-}
-// ... of 32-bit values, modulo 2^32: widen the argument where 64 values may not fit
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
 }
 
 // The first i in [lo, hi) with idx[i] >= target (hi: none), idx ascending there; one wave, 64 samples per round.  Every position

@@ -166,12 +166,8 @@ __global__ __launch_bounds__(256) void k_column_sums(const long long *__restrict
             }
             if (take) acc += (uint32_t)data[i];
         }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const uint32_t lo = __shfl_xor((uint32_t)acc, d), hi = __shfl_xor((uint32_t)(acc >> 32), d);
-            acc += ((unsigned long long)hi << 32) | lo;
-            bad |= __shfl_xor(bad, d);
-        }
+        acc = wave_sum(acc);
+        bad = wave_or(bad);
         if (lane == 0) {
             if (acc > 0xFFFFFFFFull) bad |= 1u;
             sums[c] = (uint32_t)acc;
@@ -293,12 +289,7 @@ __global__ __launch_bounds__(256) void k_om_row_scan(uint32_t *__restrict__ h, u
             sum += v[j];
             v[j] = sum;
         }
-        uint32_t x = sum;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(x, d);
-            if (lane >= (uint32_t)d) x += y;
-        }
+        const uint32_t x = wave_incl_scan(sum, lane);
         if (lane == 63) ws[wave] = x;
         __syncthreads();
         uint32_t pre = carry_s + x - sum, tot = 0;

@@ -248,12 +248,7 @@ __global__ __launch_bounds__(256) void k_build_keys(const KL kl, const uint32_t 
           __syncthreads();
           if (threadIdx.x < KEY_ITEMS * 4) {  // one wave: exclusive scan of the 64 (slot, wave) counts + the look-back
               const uint32_t v = s_ws[threadIdx.x];
-              uint32_t x = v;
-#pragma unroll
-              for (int d = 1; d < KEY_ITEMS * 4; d <<= 1) {
-                  const uint32_t y = __shfl_up(x, d);
-                  if (threadIdx.x >= (uint32_t)d) x += y;
-              }
+              const uint32_t x = wave_incl_scan<KEY_ITEMS * 4>(v, threadIdx.x);
               s_ws[threadIdx.x] = x - v;
               const uint32_t total = __shfl(x, 63);
               if (threadIdx.x == 0 && c > 0)
@@ -797,15 +792,11 @@ __global__ __launch_bounds__(CP_BLOCK) void k_rl_count(const uint64_t *__restric
             c += (head && i < hi) ? 1u : 0u;
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
+    // block_sum_to_first spelled out: see profiles/wave_primitives_resources.txt
+    c = wave_sum(c);
     if (lane == 0) ws[wave] = c;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t t = 0;
-        for (int w = 0; w < CP_WAVES; w++) t += ws[w];
-        block_counts[blockIdx.x] = t;
-    }
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = lds_sum<CP_WAVES>(ws);
 }
 
 __global__ __launch_bounds__(CP_BLOCK) void k_rl_write(const uint64_t *__restrict__ keys, const uint32_t shift, const uint64_t n,
@@ -839,14 +830,11 @@ __global__ __launch_bounds__(CP_BLOCK) void k_rl_write(const uint64_t *__restric
             if (lane == 0) ws[wave * CP_ITEMS + j] = (uint32_t)__popcll(m);
         }
         __syncthreads();
-        if (threadIdx.x < CP_ITEMS * CP_WAVES) {  // 32 lanes of wave 0: exclusive scan in (wave, slot) order = key order
+        // 32 lanes of wave 0: exclusive scan in (wave, slot) order = key order (block_scan_words spelled out: see
+        // profiles/wave_primitives_resources.txt)
+        if (threadIdx.x < CP_ITEMS * CP_WAVES) {
             const uint32_t v = ws[threadIdx.x];
-            uint32_t x = v;
-#pragma unroll
-            for (int d = 1; d < CP_ITEMS * CP_WAVES; d <<= 1) {
-                const uint32_t y = __shfl_up(x, d);
-                if (threadIdx.x >= (uint32_t)d) x += y;
-            }
+            const uint32_t x = wave_incl_scan<CP_ITEMS * CP_WAVES>(v, threadIdx.x);
             ws[threadIdx.x] = x - v;
             if (threadIdx.x == CP_ITEMS * CP_WAVES - 1) round_total = x;
         }
@@ -968,24 +956,15 @@ __global__ __launch_bounds__(CP_BLOCK) void k_mt_count(const Flag flag, const ui
             ch += h ? 1u : 0u;
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        cm += __shfl_xor(cm, d);
-        ch += __shfl_xor(ch, d);
-    }
+    cm = wave_sum(cm), ch = wave_sum(ch);  // two counters behind one barrier: block_sum_to_first twice would need two
     if (lane == 0) {
         ws[wave] = cm;
         ws[CP_WAVES + wave] = ch;
     }
     __syncthreads();
     if (threadIdx.x == 0) {
-        uint32_t tm = 0, th = 0;
-        for (int w = 0; w < CP_WAVES; w++) {
-            tm += ws[w];
-            th += ws[CP_WAVES + w];
-        }
-        mol_counts[blockIdx.x] = tm;
-        head_counts[blockIdx.x] = th;
+        mol_counts[blockIdx.x] = lds_sum<CP_WAVES>(ws);
+        head_counts[blockIdx.x] = lds_sum<CP_WAVES>(ws + CP_WAVES);
     }
 }
 
@@ -1041,17 +1020,7 @@ __global__ __launch_bounds__(CP_BLOCK) void k_mt_write(const Flag flag, const Em
             if (lane == 0) ws[wave * CP_ITEMS + j] = (uint32_t)__popcll(mm) | ((uint32_t)__popcll(mh) << 16);
         }
         __syncthreads();
-        if (threadIdx.x < CP_ITEMS * CP_WAVES) {  // 32 lanes of wave 0: exclusive scan in (wave, slot) order = key order
-            const uint32_t v = ws[threadIdx.x];
-            uint32_t x = v;
-#pragma unroll
-            for (int d = 1; d < CP_ITEMS * CP_WAVES; d <<= 1) {
-                const uint32_t y = __shfl_up(x, d);
-                if (threadIdx.x >= (uint32_t)d) x += y;
-            }
-            ws[threadIdx.x] = x - v;
-            if (threadIdx.x == CP_ITEMS * CP_WAVES - 1) round_total = x;
-        }
+        block_scan_words<CP_ITEMS * CP_WAVES>(ws, &round_total);  // 32 lanes of wave 0: exclusive scan in (wave, slot) order = key order
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < CP_ITEMS; j++)

@@ -201,11 +201,7 @@ __global__ __launch_bounds__(256) void k_ed_observed(const uint64_t *__restrict_
             if ((uint32_t)x > nmax) continue;  // total then differs from umis[k] <= nmax, or umis[k] > nmax: flagged below
             acc += (double)x * logp[f] - lgam[x];
         }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            acc += __shfl_xor(acc, d);
-            total += __shfl_xor(total, d);
-        }
+        acc = wave_sum(acc), total = wave_sum(total);
         if (lane == 0) {
             const uint32_t N = umis[k];
             if (N > nmax || total != N) *flag = 1u; else out[k] = lgam[N] + acc;
@@ -276,11 +272,7 @@ __global__ __launch_bounds__(ED_SIM_THREADS) void k_ed_simulate(EdSimArgs a) {
                     acc += a.lp[j] - a.lc[c];  // c < hi <= dn[D - 1]
                 }
             }
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {
-                const uint32_t x = __shfl_xor((uint32_t)acc, d), y = __shfl_xor((uint32_t)((unsigned long long)acc >> 32), d);
-                acc += (long long)(((unsigned long long)y << 32) | x);
-            }
+            acc = wave_sum(acc);
             if (lane == 0 && acc != 0) atomicAdd(&s_acc[i % 3u], (unsigned long long)acc);
             __syncthreads();
             running += (long long)s_acc[i % 3u];
@@ -306,8 +298,7 @@ __global__ __launch_bounds__(256) void k_ed_count_lower(const double *__restrict
         const double o = obs[c];
         uint32_t k = 0;
         for (uint32_t s = lane; s < S; s += 64) k += t[s] < o ? 1u : 0u;
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) k += __shfl_xor(k, d);
+        k = wave_sum(k);
         if (lane == 0) n_lower[c] = k;
     }
 }

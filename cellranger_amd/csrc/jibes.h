@@ -290,17 +290,6 @@ extern "C" int crgpu_jibes_tag_counts_dev(crgpu_ctx *ctx, const crgpu_matrix_dev
 }
 
 // ---- the fit -------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ double jb_wave_sum(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-    return v;
-}
-__device__ __forceinline__ double jb_wave_max(double v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v = fmax(v, __shfl_xor(v, d));
-    return v;
-}
-
 __global__ void k_jb_init(JbState *st) {
     const uint32_t t = threadIdx.x;
     if (t < JB_MAXK) st->lnsd[t] = log(st->sd[t]);
@@ -360,14 +349,14 @@ __global__ __launch_bounds__(JB_WG) void k_jb_pass(const double *__restrict__ y,
             s_row[s] = v;
             mx = fmax(mx, v);
         }
-        mx = jb_wave_max(mx);
+        mx = wave_max(mx);
         double sum = 0.0;
         for (uint32_t s = lane; s < z; s += 64u) {
             const double e = exp(s_row[s] - mx);
             s_row[s] = e;
             sum += e;
         }
-        const double marg = jb_wave_sum(sum);
+        const double marg = wave_sum(sum);
         if (MODE == 0) {
             if (live) a_lnm += log(marg), a_max += mx;
             double r = 0.0, pa[KP], pb[KP];
@@ -383,7 +372,7 @@ __global__ __launch_bounds__(JB_WG) void k_jb_pass(const double *__restrict__ y,
                     pa[t] += px, pb[t] += px * x;
                 }
             }
-            const double row_sum = jb_wave_sum(r);  // the reference's tag_cnt * row.sum(): the whole row, the same value in every lane
+            const double row_sum = wave_sum(r);  // the reference's tag_cnt * row.sum(): the whole row, the same value in every lane
             if (live) {
                 a_11 += row_sum;
 #pragma unroll
@@ -423,7 +412,7 @@ __global__ __launch_bounds__(JB_WG) void k_jb_pass(const double *__restrict__ y,
             for (uint32_t c = 0; c < k + 2u; c++) {
                 double part = 0.0;
                 for (uint32_t s = lane; s < z; s += 64u) part += s_cls[s] == c ? s_row[s] : 0.0;
-                part = jb_wave_sum(part);
+                part = wave_sum(part);
                 if (lane == c) mine = part;
             }
 #pragma unroll
@@ -462,13 +451,13 @@ __global__ __launch_bounds__(JB_WG) void k_jb_pass(const double *__restrict__ y,
         if (lane == 0u) s_red[wave][0] = a_lnm, s_red[wave][1] = a_max, s_red[wave][2] = a_11;
 #pragma unroll
         for (uint32_t t = 0; t < KP; t++) {
-            const double f = a_first[t], sc = jb_wave_sum(a_second[t]), e12 = jb_wave_sum(a_12[t]), e22 = jb_wave_sum(a_22[t]);
+            const double f = a_first[t], sc = wave_sum(a_second[t]), e12 = wave_sum(a_12[t]), e22 = wave_sum(a_22[t]);
             if (lane == 0u) s_red[wave][3u + 4u * t] = f, s_red[wave][4u + 4u * t] = sc, s_red[wave][5u + 4u * t] = e12, s_red[wave][6u + 4u * t] = e22;
         }
     } else {
 #pragma unroll
         for (uint32_t t = 0; t < KP; t++) {
-            const double f = jb_wave_sum(a_first[t]);
+            const double f = wave_sum(a_first[t]);
             if (lane == 0u) s_red[wave][t] = f;
         }
     }

@@ -146,11 +146,6 @@ __device__ __forceinline__ double km_np_sum(const double *a, uint32_t n) {
     for (; i < n; i++) res += a[i];
     return res;
 }
-__device__ __forceinline__ double km_wave_sum(double v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s);
-    return v;
-}
 // the squared distance of the seeding (euclidean_distances): ((-2 x.y) + ||y||^2) + ||x||^2, not below 0
 __device__ __forceinline__ double km_seed_dist(const double *x, const double *y, uint32_t d, double xx, double yy) {
     double dot = 0.0;
@@ -285,7 +280,7 @@ __global__ __launch_bounds__(KM_WG) void k_km_seed_cand(const double *__restrict
             v = km_seed_dist(xc + (size_t)i * d, s_y + (size_t)t * d, d, xi, s_yy[t]);
             v = cl < v ? cl : v;
         }
-        v = km_wave_sum(v);
+        v = wave_sum(v);
         if ((tid & 63u) == 0u) s_red[tid >> 6][t] = v;
     }
     __syncthreads();

@@ -30,6 +30,7 @@
 #include <cmath>
 #include <vector>
 
+#include "block_utils.h"
 #include "common.h"
 
 #define KNN_WG 256u
@@ -196,7 +197,7 @@ __global__ __launch_bounds__(KNN_WG) void k_knn_select(const double *__restrict_
             }
         }
     if (tid < KNN_QT) gcnt[qt0 + tid] = s_cnt[tid];
-    for (int sh = 32; sh >= 1; sh >>= 1) appended += __shfl_xor(appended, sh);
+    appended = wave_sum(appended);
     if (lane == 0u) atomicAdd(&counters[2], appended);
     if (tid == 0u) atomicAdd(&counters[0], (unsigned long long)events), atomicAdd(&counters[1], (unsigned long long)cuts);
 }

@@ -197,8 +197,7 @@ __global__ __launch_bounds__(256) void k_mc_hist(const uint64_t *__restrict__ ke
         run += all;
         __syncthreads();
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
+    sum = wave_sum(sum);
     if (lane == 0u) s_sum[wave] = sum;
     __syncthreads();  // also: every hpos of the row is written
     if (zeros && tid == 0u) hval[base] = 0, hx[base] = 0.0, hmul[base] = (uint32_t)(V - n);
@@ -211,10 +210,7 @@ __global__ __launch_bounds__(256) void k_mc_hist(const uint64_t *__restrict__ ke
 template <uint32_t NW, uint32_t N>
 __device__ __forceinline__ void mc_block_sum(double *v, double *s_red) {
 #pragma unroll
-    for (uint32_t k = 0; k < N; k++) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) v[k] += __shfl_xor(v[k], d);
-    }
+    for (uint32_t k = 0; k < N; k++) v[k] = wave_sum(v[k]);
     if (NW == 1u) return;
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     __syncthreads();  // s_red of the sum before is read by now
@@ -231,11 +227,7 @@ __device__ __forceinline__ void mc_block_sum(double *v, double *s_red) {
 // the smallest code over the workgroup (NONE32: none)
 template <uint32_t NW>
 __device__ __forceinline__ uint32_t mc_block_min(uint32_t c, uint32_t *s_min) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        const uint32_t o = __shfl_xor(c, d);
-        c = o < c ? o : c;
-    }
+    c = wave_min(c);
     if (NW == 1u) return c;
     __syncthreads();
     if ((threadIdx.x & 63u) == 0u) s_min[threadIdx.x >> 6] = c;
@@ -285,12 +277,7 @@ __device__ __forceinline__ uint32_t mc_locate(const McFitArgs &a, uint32_t lo, u
             de = (xe - c0) * (xe - c0);
             gapd = (double)gap * d0;
         }
-        double s = gapd + de;  // inclusive scan: lanes, then the waves before, then the tiles before
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const double o = __shfl_up(s, d);
-            if (lane >= (uint32_t)d) s += o;
-        }
+        double s = wave_incl_scan(gapd + de, lane);  // inclusive scan: lanes, then the waves before, then the tiles before
         if (NW > 1u) {
             __syncthreads();
             if (lane == 63u) s_scan[wave] = s;
@@ -498,12 +485,7 @@ __global__ __launch_bounds__(256) void k_mc_assign(const uint32_t *__restrict__ 
         hpos[base + k] = on ? 1u : 0u;
         if (on) cnt += hmul[base + k], mn = v < mn ? v : mn;
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        cnt += __shfl_xor(cnt, d);
-        const uint32_t om = __shfl_xor(mn, d);
-        mn = om < mn ? om : mn;
-    }
+    cnt = wave_sum(cnt), mn = wave_min(mn);
     if (lane == 0u) s_cnt[wave] = cnt, s_mn[wave] = mn;
     __syncthreads();
     if (tid == 0u) {
@@ -582,8 +564,7 @@ __global__ __launch_bounds__(256) void k_mc_cells(const long long *__restrict__ 
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
 #pragma unroll
     for (uint32_t k = 0; k < 4u; k++) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) t[k] += __shfl_xor(t[k], d);
+        t[k] = wave_sum(t[k]);
         if (lane == 0u) s_t[k][wave] = t[k];
     }
     __syncthreads();

@@ -3,6 +3,7 @@
 // Reference: MakeShardVisitor::visit_processed_read, cr_lib/src/make_shard_metrics.rs:263-332; frac_n_bases /
 // frac_q30_bases :355-392; thresholds :20-23; RnaRead::barcode_min_qual / umi_min_qual cr_types/src/rna_read.rs:738-749;
 // UmiInfo validity umi/src/info.rs:20-37.  PercentMetrics are returned as numerator / denominator counts.
+#include "block_utils.h"
 #include "common.h"
 
 #define SM_FIELDS 18
@@ -91,8 +92,7 @@ __global__ __launch_bounds__(256) void k_shard_metrics(const uint32_t *__restric
     }
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     for (int f = 0; f < SM_FIELDS; f++) {
-        unsigned long long x = a[f];
-        for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d);
+        const unsigned long long x = wave_sum(a[f]);
         if (lane == 0) s[wave][f] = x;
     }
     __syncthreads();
@@ -159,8 +159,7 @@ __global__ __launch_bounds__(256) void k_rows_metrics(const uint8_t *__restrict_
         }
     }
     for (int f = 0; f < 4; f++) {
-        unsigned long long x = a[f];
-        for (int d = 32; d >= 1; d >>= 1) x += __shfl_xor(x, d);
+        const unsigned long long x = wave_sum(a[f]);
         if (lane == 0) s[wave][f] = x;
     }
     __syncthreads();
@@ -284,10 +283,7 @@ __global__ __launch_bounds__(256) void k_nl_count(const uint8_t *__restrict__ te
     const uint64_t lo = (uint64_t)blockIdx.x * tile, hi = lo + tile < n ? lo + tile : n;
     uint32_t c = 0;
     for (uint64_t i = lo + threadIdx.x; i < hi; i += 256) c += text[i] == '\n';
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
-    if ((threadIdx.x & 63u) == 0) ws[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) block_counts[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
+    block_sum_to_first<4>(c, ws, &block_counts[blockIdx.x]);
 }
 // positions of the line feeds, ascending: rounds of 256 consecutive bytes, stable inside a round by ballot ranks
 __global__ __launch_bounds__(256) void k_nl_write(const uint8_t *__restrict__ text, uint64_t n, uint64_t tile,

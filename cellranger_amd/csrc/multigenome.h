@@ -101,12 +101,7 @@ __global__ __launch_bounds__(256) void k_mg_keys(const uint32_t *__restrict__ c0
         nA += s == MG_SEG_A;
         nB += s == MG_SEG_B;
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        nA += __shfl_xor(nA, d);
-        nB += __shfl_xor(nB, d);
-        over |= __shfl_xor(over, d);
-    }
+    nA = wave_sum(nA), nB = wave_sum(nB), over = wave_or(over);
     if ((threadIdx.x & 63u) == 0) {
         if (nA) atomicAdd(&info[0], nA);
         if (nB) atomicAdd(&info[1], nB);
@@ -223,12 +218,7 @@ __global__ __launch_bounds__(256) void k_mg_sample(const uint32_t *__restrict__ 
                 sum += q0 + j < n ? mult(pp2[q0 + j]) : 0u;
                 v[j] = sum;
             }
-            uint32_t x = sum;
-#pragma unroll
-            for (int d = 1; d < 64; d <<= 1) {
-                const uint32_t y = __shfl_up(x, d);
-                if (lane >= (uint32_t)d) x += y;
-            }
+            const uint32_t x = wave_incl_scan(sum, lane);
             if (lane == 63) s_ws[wave] = x;
             __syncthreads();
             uint32_t pre = s_carry + x - sum, tot = 0;
@@ -276,11 +266,7 @@ __global__ __launch_bounds__(256) void k_mg_sample(const uint32_t *__restrict__ 
     }
 #pragma unroll
     for (int r = 0; r < (OBS ? 7 : 3); r++) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            const uint32_t lo = __shfl_xor((uint32_t)acc[r], d), hi = __shfl_xor((uint32_t)(acc[r] >> 32), d);
-            acc[r] += ((unsigned long long)hi << 32) | lo;
-        }
+        acc[r] = wave_sum(acc[r]);
         if (lane == 0) s_red[wave][r] = acc[r];
     }
     __syncthreads();

@@ -403,11 +403,7 @@ __global__ __launch_bounds__(256) void k_sf_count(const long long *__restrict__ 
             else
                 n += new_row[f] != NONE32;
         }
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            n += __shfl_xor(n, d);
-            bad |= __shfl_xor(bad, d);
-        }
+        n = wave_sum(n), bad = wave_or(bad);
         if (lane == 0) {
             cnt[c] = n;
             if (bad) *flag = 1u;

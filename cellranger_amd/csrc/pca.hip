@@ -268,13 +268,6 @@ extern "C" int crgpu_small_svd(const double *B, uint32_t n, double *U, double *s
     return CRGPU_OK;
 }
 
-// ---- device: the tree over the lanes of a wave ------------------------------------------------------------------------------------
-__device__ __forceinline__ double pca_wave_tree(double a) {
-#pragma unroll
-    for (uint32_t off = 32u; off >= 1u; off >>= 1) a += __shfl_down(a, off);
-    return a;  // lane 0 holds the sum
-}
-
 // ---- device: the preparation --------------------------------------------------------------------------------------------------------
 // cnt[b] = the entries of barcode b (column bcs[b], or b) whose row maps to a used feature (fmap NULL: every row); sums[b] = sums_all[column]
 __global__ __launch_bounds__(PCA_WG) void k_pca_count(const long long *__restrict__ indptr, const int32_t *__restrict__ indices, const uint32_t *__restrict__ bcs,
@@ -291,8 +284,7 @@ __global__ __launch_bounds__(PCA_WG) void k_pca_count(const long long *__restric
             if (r >= G) atomicOr(flag, 1u);
             else if (!fmap || fmap[r] >= 0) n++;
         }
-#pragma unroll
-        for (uint32_t off = 32u; off >= 1u; off >>= 1) n += __shfl_xor(n, off);
+        n = wave_sum(n);
         if (lane == 0u) cnt[b] = n, sums[b] = sums_all[c];
     }
 }
@@ -367,14 +359,14 @@ __global__ __launch_bounds__(PCA_WG) void k_pca_meanvar(const uint64_t *__restri
         const uint64_t lo = tptr[f], hi = tptr[f + 1];
         double sum = 0.0;
         for (uint64_t i = lo + lane; i < hi; i += 64u) sum += tval[i];
-        sum = pca_wave_tree(sum);
+        sum = wave_sum(sum);
         const double mean = __shfl(sum, 0) / n;
         double corr = 0.0, var = 0.0;
         for (uint64_t i = lo + lane; i < hi; i += 64u) {
             const double diff = tval[i] - mean;
             corr += diff, var += diff * diff;
         }
-        corr = pca_wave_tree(corr), var = pca_wave_tree(var);
+        corr = wave_sum(corr), var = wave_sum(var);
         if (lane == 0u) {
             const double n_zero = (double)(N - (hi - lo));
             if (hi - lo != N) corr -= n_zero * mean;
@@ -399,7 +391,7 @@ __global__ __launch_bounds__(PCA_WG) void k_pca_av(const uint64_t *__restrict__ 
         const uint64_t lo = rowptr[c], hi = rowptr[c + 1];
         double a = 0.0;
         for (uint64_t i = lo + lane; i < hi; i += 64u) a += val[i] * v[col[i]];
-        a = pca_wave_tree(a);
+        a = wave_sum(a);
         if (lane == 0u) w[c] = a - cv;
     }
 }
@@ -414,7 +406,7 @@ __global__ __launch_bounds__(PCA_WG) void k_pca_atw(const uint64_t *__restrict__
         const uint64_t lo = tptr[f], hi = tptr[f + 1];
         double a = 0.0;
         for (uint64_t i = lo + lane; i < hi; i += 64u) a += tval[i] * w[tcell[i]];
-        a = pca_wave_tree(a);
+        a = wave_sum(a);
         if (lane == 0u) f_out[f] = a - sw * center[f];
     }
 }
@@ -437,7 +429,7 @@ __global__ __launch_bounds__(PCA_WG) void k_pca_dots(const double *__restrict__ 
             double a = 0.0;
 #pragma unroll
             for (uint32_t u = 0; u < 4u; u++) a += r0 + 64u * u < n ? yv[u] * x[r0 + 64u * u] : 0.0;
-            a = pca_wave_tree(a);
+            a = wave_sum(a);
             if (lane == 0u) slab[(size_t)part * ncols + c] = a;
         }
     }
@@ -505,7 +497,7 @@ __global__ __launch_bounds__(PCA_WG) void k_pca_project(const uint64_t *__restri
             }
 #pragma unroll
             for (uint32_t u = 0; u < PCA_PROJ_CHUNK; u++) {
-                const double t = pca_wave_tree(a[u]);
+                const double t = wave_sum(a[u]);
                 if (lane == 0u && c0 + u < nu) out[b * nu + c0 + u] = t - cv[c0 + u];
             }
         }

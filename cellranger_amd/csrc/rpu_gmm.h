@@ -39,8 +39,7 @@ __device__ __forceinline__ void gmm_block_sum(double *v, double *s_red, double *
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
 #pragma unroll
     for (uint32_t k = 0; k < GMM_NSUM; k++) {
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) v[k] += __shfl_xor(v[k], d);
+        v[k] = wave_sum(v[k]);
         if (lane == 0u) s_red[k * 4u + wave] = v[k];
     }
     __syncthreads();

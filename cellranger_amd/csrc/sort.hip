@@ -72,12 +72,8 @@ __global__ __launch_bounds__(1024) void k_scan_small(uint32_t *__restrict__ data
     for (uint64_t base = 0; base < n; base += 1024) {
         const uint64_t i = base + tid;
         const uint32_t v = i < n ? data[i] : 0u;
-        uint32_t x = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t y = __shfl_up(x, d);
-            if (lane >= (uint32_t)d) x += y;
-        }
+        // block_excl_scan<1024, false> spelled out: see profiles/wave_primitives_resources.txt
+        const uint32_t x = wave_incl_scan(v, lane);
         if (lane == 63) wave_sums[wave] = x;
         __syncthreads();
         uint32_t wpre = 0, tot = 0;
@@ -176,7 +172,7 @@ __global__ __launch_bounds__(256) void k_scan_digits(uint32_t *__restrict__ bloc
         const uint32_t i = base + threadIdx.x;
         const uint32_t v = i < n_blocks ? row[i] : 0u;
         uint32_t tot;
-        const uint32_t pre = block_excl_scan_256(v, lds, &tot);
+        const uint32_t pre = block_excl_scan<256>(v, lds, &tot);
         if (i < n_blocks) row[i] = carry + pre;
         carry += tot;
     }
@@ -978,11 +974,7 @@ __global__ __launch_bounds__(256) void k_tile_heads(const uint32_t *__restrict__
     const uint64_t s1 = s0 + spans_per_tile < n_spans ? s0 + spans_per_tile : n_spans;
     uint32_t c = 0;
     for (uint64_t i = s0 + threadIdx.x; i < s1; i += 256) c += span_heads[i];
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
-    if ((threadIdx.x & 63u) == 0) ws[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) tile_heads[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
+    block_sum_to_first<4>(c, ws, &tile_heads[blockIdx.x]);
 }
 // a repair's change of the head count of tile t: into the workgroup's LDS counters when t is one of theirs, else to memory
 #define RH_LDS 68u  // tiles a workgroup of k_repair_runs can meet: RR_WORDS * 64 keys / the smallest tile (2048 keys) + the edges

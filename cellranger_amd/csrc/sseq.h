@@ -291,11 +291,7 @@ __global__ __launch_bounds__(SQ_WG) void k_sq_row_sums(const uint64_t *__restric
         const double v = (double)vals[i] / sf[keys[i] - (uint64_t)g * N];
         s1 += v, s2 += v * v;
     }
-#pragma unroll
-    for (uint32_t off = 32u; off >= 1u; off >>= 1) {
-        const double o1 = __shfl_down(s1, off), o2 = __shfl_down(s2, off);
-        s1 += o1, s2 += o2;
-    }
+    s1 = wave_sum(s1), s2 = wave_sum(s2);  // lane 0 of the butterfly adds what a __shfl_down tree adds, in its order
     if (lane == 0u) s1_out[g] = s1, s2_out[g] = s2;
 }
 // sums[label - 1][row] += count: a wave per cell

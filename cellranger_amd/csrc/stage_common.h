@@ -168,15 +168,7 @@ __global__ __launch_bounds__(CP_BLOCK) void k_cp_count(Flag flag, uint64_t n, ui
             c += (f[j] && i < hi) ? 1u : 0u;
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d);
-    if ((threadIdx.x & 63u) == 0) ws[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t t = 0;
-        for (int w = 0; w < CP_WAVES; w++) t += ws[w];
-        block_counts[blockIdx.x] = t;
-    }
+    block_sum_to_first<CP_WAVES>(c, ws, &block_counts[blockIdx.x]);
 }
 
 // Stable: inside a round the output order is (item slot, wave, lane) == ascending input index.
@@ -208,17 +200,7 @@ __global__ __launch_bounds__(CP_BLOCK) void k_cp_write(Flag flag, Emit emit, uin
             if (lane == 0) ws[j * CP_WAVES + wave] = (uint32_t)__popcll(m);
         }
         __syncthreads();
-        if (threadIdx.x < CP_ITEMS * CP_WAVES) {  // 32 lanes of wave 0: exclusive scan in (slot, wave) order
-            const uint32_t v = ws[threadIdx.x];
-            uint32_t x = v;
-#pragma unroll
-            for (int d = 1; d < CP_ITEMS * CP_WAVES; d <<= 1) {
-                const uint32_t y = __shfl_up(x, d);
-                if (threadIdx.x >= (uint32_t)d) x += y;
-            }
-            ws[threadIdx.x] = x - v;
-            if (threadIdx.x == CP_ITEMS * CP_WAVES - 1) round_total = x;
-        }
+        block_scan_words<CP_ITEMS * CP_WAVES>(ws, &round_total);  // 32 lanes of wave 0: exclusive scan in (slot, wave) order
         __syncthreads();
 #pragma unroll
         for (int j = 0; j < CP_ITEMS; j++) {

@@ -117,14 +117,8 @@ __device__ __forceinline__ void ss_wave_sum(const SsAcc &acc, uint32_t ng, unsig
     for (int g = 0; g < 8; g++) {
         lo[g] = hi[g] = 0ull;
         if ((uint32_t)g < ng) {
-            unsigned long long x = acc.a[g] & 0x00FF00FF00FF00FFull, y = (acc.a[g] >> 8) & 0x00FF00FF00FF00FFull;
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {
-                x += __shfl_xor(x, d);
-                y += __shfl_xor(y, d);
-            }
-            lo[g] = x;
-            hi[g] = y;
+            lo[g] = wave_sum(acc.a[g] & 0x00FF00FF00FF00FFull);
+            hi[g] = wave_sum((acc.a[g] >> 8) & 0x00FF00FF00FF00FFull);
         }
     }
 }
@@ -307,14 +301,8 @@ __global__ __launch_bounds__(256) void k_ss_tally(SsTally a) {
 #pragma unroll
         for (int g = 0; g < 8; g++)
             if ((uint32_t)g < a.G) {
-                unsigned long long r = rp[g];
-                uint32_t u = um[g], d = fd[g];
-#pragma unroll
-                for (int x = 32; x >= 1; x >>= 1) {
-                    r += __shfl_xor(r, x);
-                    u += __shfl_xor(u, x);
-                    d += __shfl_xor(d, x);
-                }
+                const unsigned long long r = wave_sum(rp[g]);
+                const uint32_t u = wave_sum(um[g]), d = wave_sum(fd[g]);
                 const bool cell = ci != NONE32 && ((gmask >> g) & 1u);
                 if (lane == 0 && !(type == CRGPU_SS_CELLS_ONLY && !cell)) {
                     const uint64_t tg = (uint64_t)t * a.G + g;

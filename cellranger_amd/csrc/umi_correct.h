@@ -266,13 +266,7 @@ __global__ __launch_bounds__(256, UC_MIN_WG) void k_correct_umis_tiled(const KL 
             else if (tn - tid * 64u < 64u) mk &= (1ull << (tn - tid * 64u)) - 1ull;
             uint32_t tf = mk ? tid * 64u + (uint32_t)__ffsll((long long)mk) - 1u : UC_NOHEAD;   // UC_NOHEAD is the maximum
             int tl = mk ? (int)(tid * 64u + 63u - (uint32_t)__clzll((long long)mk)) : -1;
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {
-                const uint32_t y = __shfl_xor(tf, d);
-                const int z = __shfl_xor(tl, d);
-                tf = tf < y ? tf : y;
-                tl = tl > z ? tl : z;
-            }
+            tf = wave_min(tf), tl = wave_max(tl);
             if (tid == 0) {
                 tile_first[tile] = tf;
                 tile_last[tile] = tl >= 0 ? (uint32_t)tl : UC_NOHEAD;
