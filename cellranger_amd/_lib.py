@@ -406,7 +406,24 @@ class PcaResult(C.Structure):
         (n, C.c_uint32) for n in ("status", "n_components", "n_used_features", "n_thresholded_features", "it", "mprod", "m_b", "reserved")]
 
 
+class TsneArgs(C.Structure):
+    """crgpu_tsne_args"""
+    _fields_ = [("eta", C.c_double)] + [
+        (n, C.c_uint32) for n in ("first_iter", "n_iters", "max_iter", "stop_lying_iter", "mom_switch_iter", "row_tile", "cand_tile", "slab_rows",
+                                  "wave_row_len", "reserved")]
+
+
+class TsneResult(C.Structure):
+    """crgpu_tsne_result"""
+    _fields_ = [(n, C.c_void_p) for n in ("beta_out", "steps_out", "cond_out", "indptr_out", "indices_out", "values_out", "grad_out")] + [
+        (n, C.c_double) for n in ("sum_q", "kl", "p_total", "fit_ms", "search_ms", "csr_ms", "loop_ms", "repulse_ms")] + [
+        (n, C.c_uint64) for n in ("nnz", "pairs_evaluated")] + [
+        (n, C.c_uint32) for n in ("row_tile", "cand_tile", "slab_rows", "wave_row_len", "n_chunks", "n_groups", "max_steps", "reserved")]
+
+
 KM_MAX_K, KM_MAX_D, KM_MAX_LIST = 64, 128, 64
+TSNE_CAND_CHUNK, TSNE_MAX_FEATURES = 4096, 128
+TSNE_PERPLEXITY, TSNE_THETA, TSNE_MAX_ITER, TSNE_STOP_LYING_ITER, TSNE_MOM_SWITCH_ITER, TSNE_ETA = 30, 0.5, 1000, 250, 250, 200.0
 PCA_MAX_COMPONENTS, PCA_DEFAULT_THRESHOLD, PCA_OK, PCA_NULL_AXIS, PCA_RANK_TOO_SMALL = 128, 2, 0, 1, 2
 KNN_MAX_K, KNN_MAX_CAPACITY = 1024, 4096
 BC_PAIR_CHUNK, BC_LDS_BYTES, BC_MAX_PAIR_TILE = 2048, 73728, 64
@@ -594,6 +611,9 @@ SYMBOLS = {
     "crgpu_legacy_randn": (_i, [_u32, _u64, _vp]),
     "crgpu_normalized_dispersion": (_i, [_vp, _vp, _u64, _u32, _vp]),
     "crgpu_small_svd": (_i, [_vp, _u32, _vp, _vp, _vp]),
+    "crgpu_tsne_affinities_dev": (_i, [_vp, _vp, _vp, _u64, _u32, _dbl, C.POINTER(TsneArgs), C.POINTER(TsneResult)]),
+    "crgpu_tsne_gradient_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _u32, _dbl, C.POINTER(TsneArgs), C.POINTER(TsneResult)]),
+    "crgpu_tsne_dev": (_i, [_vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, C.POINTER(TsneArgs), C.POINTER(TsneResult)]),
     "crgpu_aggregate_min_antibodies": (_i, [_u32, C.POINTER(_u32)]),
     "crgpu_antigen_outlier_threshold": (_i, [_vp, _u32, C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_dbl)]),
     "crgpu_aggregates_by_counts_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, _u32, _vp, _vp, _u32, C.POINTER(_u32),

@@ -433,6 +433,42 @@ const std::vector<AbiStruct> &abi_table() {
               ABI_F(crgpu_bc_result, zero_den_rows),
               ABI_F(crgpu_bc_result, pair_tile),
               ABI_F(crgpu_bc_result, row_tile)),
+        ABI_S(crgpu_tsne_args, ABI_F(crgpu_tsne_args, eta),
+              ABI_F(crgpu_tsne_args, first_iter),
+              ABI_F(crgpu_tsne_args, n_iters),
+              ABI_F(crgpu_tsne_args, max_iter),
+              ABI_F(crgpu_tsne_args, stop_lying_iter),
+              ABI_F(crgpu_tsne_args, mom_switch_iter),
+              ABI_F(crgpu_tsne_args, row_tile),
+              ABI_F(crgpu_tsne_args, cand_tile),
+              ABI_F(crgpu_tsne_args, slab_rows),
+              ABI_F(crgpu_tsne_args, wave_row_len),
+              ABI_F(crgpu_tsne_args, reserved)),
+        ABI_S(crgpu_tsne_result, ABI_F(crgpu_tsne_result, beta_out),
+              ABI_F(crgpu_tsne_result, steps_out),
+              ABI_F(crgpu_tsne_result, cond_out),
+              ABI_F(crgpu_tsne_result, indptr_out),
+              ABI_F(crgpu_tsne_result, indices_out),
+              ABI_F(crgpu_tsne_result, values_out),
+              ABI_F(crgpu_tsne_result, grad_out),
+              ABI_F(crgpu_tsne_result, sum_q),
+              ABI_F(crgpu_tsne_result, kl),
+              ABI_F(crgpu_tsne_result, p_total),
+              ABI_F(crgpu_tsne_result, fit_ms),
+              ABI_F(crgpu_tsne_result, search_ms),
+              ABI_F(crgpu_tsne_result, csr_ms),
+              ABI_F(crgpu_tsne_result, loop_ms),
+              ABI_F(crgpu_tsne_result, repulse_ms),
+              ABI_F(crgpu_tsne_result, nnz),
+              ABI_F(crgpu_tsne_result, pairs_evaluated),
+              ABI_F(crgpu_tsne_result, row_tile),
+              ABI_F(crgpu_tsne_result, cand_tile),
+              ABI_F(crgpu_tsne_result, slab_rows),
+              ABI_F(crgpu_tsne_result, wave_row_len),
+              ABI_F(crgpu_tsne_result, n_chunks),
+              ABI_F(crgpu_tsne_result, n_groups),
+              ABI_F(crgpu_tsne_result, max_steps),
+              ABI_F(crgpu_tsne_result, reserved)),
         ABI_S(crgpu_pca_args, ABI_F(crgpu_pca_args, pca_bc_indices),
               ABI_F(crgpu_pca_args, n_pca_bcs),
               ABI_F(crgpu_pca_args, start),

@@ -1276,6 +1276,92 @@ def run_graph_clustering(ctx, projection, num_neighbors=None, neighbor_a=None, n
     return out
 
 
+def get_tsne_name(feature_type, n_components):
+    """get_tsne_name of stages/analyzer/run_tsne: "gene_expression_2-d\""""
+    return "%s_%d-d" % (feature_type.replace(" ", "_").lower(), n_components)
+
+
+def get_tsne_key(feature_type, n_components):
+    """get_tsne_key of stages/analyzer/run_tsne: the bare number for Gene Expression (pre-3.0 HDF5 files), else "antibody_capture_2\""""
+    if feature_type == "Gene Expression":
+        return str(n_components)
+    return "%s_%d" % (feature_type.replace(" ", "_").lower(), n_components)
+
+
+def tsne_feature_input(m, n_features=None):
+    """The t-SNE input of the feature types without a PCA (antibody-only and the other non-gene-expression types of
+    stages/analyzer/run_tsne): the dense cells x features matrix log2(1 + count) of a filtered MatrixDev, made on the host from
+    MatrixDev.download().  More than 128 features: ValueError (the neighbour search takes at most 128 columns)"""
+    _, indptr, indices, data = m.download()
+    n_cells = len(indptr) - 1
+    F = int(n_features) if n_features is not None else (int(indices.max()) + 1 if len(indices) else 1)
+    if F > _lib.TSNE_MAX_FEATURES:
+        raise ValueError("tsne_feature_input: %d features, at most %d" % (F, _lib.TSNE_MAX_FEATURES))
+    if len(indices) and int(indices.max()) >= F:
+        raise ValueError("tsne_feature_input: feature %d of %d" % (int(indices.max()), F))
+    x = np.zeros((n_cells, F))
+    cols = np.repeat(np.arange(n_cells, dtype=np.int64), np.diff(indptr))
+    x[cols, indices] = np.log2(1 + data)
+    return x
+
+
+def tsne_normalize(x):
+    """bh_tsne's input normalisation: every column minus its mean (the left-to-right sum over the rows, divided by their number), then
+    everything divided by the largest |x| (an all-zero matrix stays as it is)"""
+    x = np.array(x, dtype=np.float64)
+    x -= np.cumsum(x, axis=0)[-1] / x.shape[0]
+    top = np.abs(x).max()
+    return x / top if top > 0 else x
+
+
+def run_tsne(ctx, matrix, tsne_dims=2, input_pcs=None, perplexity=_lib.TSNE_PERPLEXITY, theta=_lib.TSNE_THETA, max_iter=_lib.TSNE_MAX_ITER,
+             stop_lying_iter=_lib.TSNE_STOP_LYING_ITER, mom_switch_iter=_lib.TSNE_MOM_SWITCH_ITER, seed=0, init=None,
+             feature_type="Gene Expression", queries_per_call=_lib.NN_QUERIES_PER_CHUNK):
+    """RUN_TSNE (stages/analyzer/run_tsne, analysis/bhtsne.py) of a cells x columns f64 matrix, at most 128 columns after input_pcs: the
+    stage's rules (perplexity = min(perplexity, max(1, -1 + (N - 1) / 3)); all zeros when N - 1 < 3 * perplexity, without a launch),
+    tsne_normalize, Context.knn at K = floor(3 * perplexity) in calls of queries_per_call rows, Context.tsne_affinities, Context.tsne.
+    The repulsion is exact: theta is taken for signature parity and IGNORED (0 and the default give the same bits).  The start is
+    legacy_randn(seed, N * dims) * 1e-4, row-major, or init [N x dims]; the packages' own generators are not reproduced
+    -> dict(embedding f64[N, dims], kl, perplexity_used, name, key, num_neighbors, nnz, max_steps, knn_ms, affinities_ms, loop_ms,
+    repulse_ms, pairs_evaluated)"""
+    x = np.asarray(matrix, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError("run_tsne: the matrix is cells x columns")
+    if input_pcs is not None:
+        x = x[:, :int(input_pcs)]
+    dims = int(tsne_dims)
+    if dims not in (2, 3):
+        raise ValueError("run_tsne: %d dimensions, 2 or 3" % dims)
+    N = x.shape[0]
+    perplexity = min(perplexity, max(1, -1 + float(N - 1) / 3))
+    out = dict(embedding=np.zeros((N, dims)), kl=0.0, perplexity_used=perplexity, name=get_tsne_name(feature_type, dims),
+               key=get_tsne_key(feature_type, dims), num_neighbors=0, nnz=0, max_steps=0, knn_ms=0.0, affinities_ms=0.0, loop_ms=0.0, repulse_ms=0.0,
+               pairs_evaluated=0)
+    if N - 1 < 3 * perplexity:
+        return out
+    if x.shape[1] > _lib.TSNE_MAX_FEATURES:
+        raise ValueError("run_tsne: %d columns, at most %d" % (x.shape[1], _lib.TSNE_MAX_FEATURES))
+    x = np.ascontiguousarray(tsne_normalize(x))
+    K = int(3 * perplexity)
+    ind, dist = np.zeros((N, K), np.int32), np.zeros((N, K))
+    for q0 in range(0, N, int(queries_per_call)):
+        r = ctx.knn(x, K, query_start=q0, n_queries=min(int(queries_per_call), N - q0))
+        ind[q0:q0 + len(r["indices"])], dist[q0:q0 + len(r["indices"])] = r["indices"], r["distances"]
+        out["knn_ms"] += r["fit_ms"]
+    P = ctx.tsne_affinities(ind, dist, perplexity)
+    if init is None:
+        y = (legacy_randn(seed, N * dims) * 1e-4).reshape(N, dims)
+    else:
+        y = np.array(init, dtype=np.float64)
+        if y.shape != (N, dims):
+            raise ValueError("run_tsne: init is %d x %d" % (N, dims))
+    r = ctx.tsne(P["indptr"], P["indices"], P["values"], y, first_iter=0, n_iters=int(max_iter), max_iter=int(max_iter),
+                 stop_lying_iter=int(stop_lying_iter), mom_switch_iter=int(mom_switch_iter))
+    out.update(embedding=r["y"], kl=r["kl"], num_neighbors=K, nnz=P["nnz"], max_steps=P["max_steps"], affinities_ms=P["fit_ms"], loop_ms=r["loop_ms"],
+               repulse_ms=r["repulse_ms"], pairs_evaluated=r["pairs_evaluated"])
+    return out
+
+
 def mnn_pairs(a, start_i, b, start_j):
     """mutual_nn[(i, j)] of CORRECT_CHEMISTRY_BATCH's join() (crgpu_mnn_pairs, host only): a i32[n_i, k] = the neighbours in batch j (global
     rows, batch j = the rows from start_j) of the rows start_i .. of batch i, b i32[n_j, k] the other direction
@@ -2714,6 +2800,93 @@ class Context:
         o.update(compactions=int(r.compactions), selections=int(r.selections), survivors=int(r.survivors), pairs_evaluated=int(r.pairs_evaluated),
                  in_lds=bool(r.in_lds), capacity=int(r.capacity), query_tiles=int(r.query_tiles), cand_tile=int(r.cand_tile), fit_ms=r.fit_ms,
                  select_ms=r.select_ms, sort_ms=r.sort_ms)
+        return o
+
+    @staticmethod
+    def _tsne_report(r):
+        return dict(sum_q=r.sum_q, kl=r.kl, p_total=r.p_total, fit_ms=r.fit_ms, search_ms=r.search_ms, csr_ms=r.csr_ms, loop_ms=r.loop_ms,
+                    repulse_ms=r.repulse_ms, nnz=int(r.nnz), pairs_evaluated=int(r.pairs_evaluated), row_tile=int(r.row_tile), cand_tile=int(r.cand_tile),
+                    slab_rows=int(r.slab_rows), wave_row_len=int(r.wave_row_len), n_chunks=int(r.n_chunks), n_groups=int(r.n_groups),
+                    max_steps=int(r.max_steps))
+
+    @staticmethod
+    def _tsne_csr(who, indptr, indices, values):
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        indices, values = np.ascontiguousarray(indices, dtype=np.int32), np.ascontiguousarray(values, dtype=np.float64)
+        if indptr.ndim != 1 or len(indptr) < 2 or indices.ndim != 1 or indices.shape != values.shape or int(indptr[-1]) != len(indices):
+            raise ValueError("%s: indptr i64[n + 1], indices and values of indptr[n] entries each" % who)
+        return indptr, indices, values
+
+    def tsne_affinities(self, nn_indices, nn_distances, perplexity):
+        """The perplexity search and the symmetrised sparse P of Barnes-Hut t-SNE on the device (crgpu_tsne_affinities_dev,
+        csrc/tsne.hip) from Context.knn's indices and distances [n, k] at k = floor(3 * perplexity): per row the bisection on beta
+        (start 1, at most 200 steps, |H - log(perplexity)| < 1e-5), the union of both directions with the value (p_ij + p_ji) / 2, CSR
+        with ascending indices, the values divided by their total (256-entry partials, then the partials ascending)
+        -> dict(beta f64[n], steps u32[n], cond f64[n, k] by rank, indptr i64[n + 1], indices i32[nnz], values f64[nnz], p_total,
+        max_steps, nnz, fit_ms, search_ms, csr_ms, ...)"""
+        ind, dist = np.ascontiguousarray(nn_indices, dtype=np.int32), np.ascontiguousarray(nn_distances, dtype=np.float64)
+        if ind.ndim != 2 or ind.shape != dist.shape:
+            raise ValueError("tsne_affinities: indices and distances of one shape [n, k]")
+        n, k = ind.shape
+        if not 1 <= k <= _lib.KNN_MAX_K or 2 * n * k >= 1 << 32:      # the output arrays need a shape; the library refuses the rest
+            raise ValueError("tsne_affinities: k = %d, 1 to %d, and fewer than 2^31 pairs" % (k, _lib.KNN_MAX_K))
+        o = dict(beta=np.zeros(n), steps=np.zeros(n, np.uint32), cond=np.zeros((n, k)), indptr=np.zeros(n + 1, np.int64))
+        indices, values = np.zeros(2 * n * k, np.int32), np.zeros(2 * n * k)
+        a = _lib.TsneArgs()
+        r = _lib.TsneResult(beta_out=ptr(o["beta"]), steps_out=ptr(o["steps"]), cond_out=ptr(o["cond"]), indptr_out=ptr(o["indptr"]),
+                            indices_out=ptr(indices), values_out=ptr(values))
+        self._check(self.L.crgpu_tsne_affinities_dev(self.h, ptr(ind), ptr(dist), n, k, float(perplexity), C.byref(a), C.byref(r)))
+        o.update(self._tsne_report(r))
+        o.update(indices=indices[:o["nnz"]].copy(), values=values[:o["nnz"]].copy())
+        return o
+
+    def tsne_gradient(self, indptr, indices, values, y, exaggeration=1.0, row_tile=0, cand_tile=0, slab_rows=0, wave_row_len=0):
+        """bh_tsne's gradient (a quarter of the analytic one), Z and the cost at y [n, 2 or 3] for a CSR P, with exact repulsion over all
+        n (n - 1) ordered pairs (crgpu_tsne_gradient_dev): dC = pos - neg / Z in the one sum order of include/crgpu.h.  row_tile /
+        cand_tile / slab_rows / wave_row_len: test seams, no result depends on them
+        -> dict(grad f64[n, dims], sum_q, kl, pairs_evaluated, the seams used, n_chunks, n_groups, fit_ms)"""
+        indptr, indices, values = self._tsne_csr("tsne_gradient", indptr, indices, values)
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        n = len(indptr) - 1
+        if y.ndim != 2 or y.shape[0] != n:
+            raise ValueError("tsne_gradient: y is %d x dims" % n)
+        grad = np.zeros_like(y)
+        a = _lib.TsneArgs(row_tile=int(row_tile), cand_tile=int(cand_tile), slab_rows=int(slab_rows), wave_row_len=int(wave_row_len))
+        r = _lib.TsneResult(grad_out=ptr(grad))
+        self._check(self.L.crgpu_tsne_gradient_dev(self.h, ptr(indptr), ptr(indices), ptr(values), ptr(y), n, y.shape[1], float(exaggeration),
+                                                   C.byref(a), C.byref(r)))
+        o = self._tsne_report(r)
+        o["grad"] = grad
+        return o
+
+    def tsne(self, indptr, indices, values, y, uY=None, gains=None, first_iter=0, n_iters=None, max_iter=_lib.TSNE_MAX_ITER,
+             stop_lying_iter=_lib.TSNE_STOP_LYING_ITER, mom_switch_iter=_lib.TSNE_MOM_SWITCH_ITER, eta=_lib.TSNE_ETA, row_tile=0, cand_tile=0,
+             slab_rows=0, wave_row_len=0):
+        """The descent of bh_tsne on a CSR P on the device (crgpu_tsne_dev): the iterations first_iter .. first_iter + n_iters (default:
+        to max_iter) from y [n, 2 or 3], uY (default 0) and gains (default 1); exaggeration 12 before stop_lying_iter, momentum 0.5
+        before mom_switch_iter and 0.8 from it on, eta 200.  The inputs are not written.  A run cut into two calls (pass y, uY, gains of
+        the first on) equals one call bit for bit.  The seams as Context.tsne_gradient
+        -> dict(y, uY, gains f64[n, dims], kl and sum_q at y, loop_ms, repulse_ms, pairs_evaluated, ...)"""
+        indptr, indices, values = self._tsne_csr("tsne", indptr, indices, values)
+        n = len(indptr) - 1
+        y = np.array(y, dtype=np.float64, order="C")
+        if y.ndim != 2 or y.shape[0] != n:
+            raise ValueError("tsne: y is %d x dims" % n)
+        uY = np.zeros_like(y) if uY is None else np.array(uY, dtype=np.float64, order="C")
+        gains = np.ones_like(y) if gains is None else np.array(gains, dtype=np.float64, order="C")
+        if uY.shape != y.shape or gains.shape != y.shape:
+            raise ValueError("tsne: uY and gains have the shape of y")
+        n_iters = int(max_iter) - int(first_iter) if n_iters is None else int(n_iters)
+        if first_iter < 0 or n_iters < 0:
+            raise ValueError("tsne: iterations %d + %d" % (first_iter, n_iters))
+        a = _lib.TsneArgs(eta=float(eta), first_iter=int(first_iter), n_iters=n_iters, max_iter=int(max_iter), stop_lying_iter=int(stop_lying_iter),
+                          mom_switch_iter=int(mom_switch_iter), row_tile=int(row_tile), cand_tile=int(cand_tile), slab_rows=int(slab_rows),
+                          wave_row_len=int(wave_row_len))
+        r = _lib.TsneResult()
+        self._check(self.L.crgpu_tsne_dev(self.h, ptr(indptr), ptr(indices), ptr(values), n, y.shape[1], ptr(y), ptr(uY), ptr(gains), C.byref(a),
+                                          C.byref(r)))
+        o = self._tsne_report(r)
+        o.update(y=y, uY=uY, gains=gains)
         return o
 
     def batch_correct(self, projection, steps, sigma=_lib.CBC_SIGMA, num_pcs=None, want_corr=False, pair_tile=0, row_tile=0, slab_rows=0):

@@ -1427,6 +1427,41 @@ inline Knn knn(Context &ctx, const double *x, uint64_t n, uint32_t d, uint64_t l
     return o;
 }
 
+// ---- RUN_TSNE: the perplexity search, the symmetrised sparse P, the exact gradient and the descent -------------------------------------
+static_assert(sizeof(crgpu_tsne_args) == 48, "crgpu_tsne_args changed: bump CRGPU_ABI_VERSION and every binding");
+static_assert(sizeof(crgpu_tsne_result) == 168, "crgpu_tsne_result changed: bump CRGPU_ABI_VERSION and every binding");
+struct TsneAffinities {
+    std::vector<double> beta, values;              // [n]; [nnz]
+    std::vector<uint32_t> steps;                   // [n]
+    std::vector<int64_t> indptr;                   // [n + 1]
+    std::vector<int32_t> indices;                  // [nnz], ascending within a row
+    crgpu_tsne_result info{};
+};
+/// crgpu_tsne_affinities_dev on the neighbours knn() delivers at k = floor(3 * perplexity): the symmetrised P as CSR, its values add to 1
+inline TsneAffinities tsne_affinities(Context &ctx, const int32_t *nn_indices, const double *nn_distances, uint64_t n, uint32_t k, double perplexity) {
+    TsneAffinities o;
+    const size_t room = (size_t)2 * n * k;
+    o.beta.assign(n, 0.0), o.steps.assign(n, 0), o.indptr.assign(n + 1, 0), o.indices.assign(room, 0), o.values.assign(room, 0.0);
+    crgpu_tsne_args a{};
+    o.info.beta_out = o.beta.data(), o.info.steps_out = o.steps.data(), o.info.indptr_out = o.indptr.data();
+    o.info.indices_out = o.indices.data(), o.info.values_out = o.values.data();
+    ctx.check(crgpu_tsne_affinities_dev(ctx.get(), nn_indices, nn_distances, n, k, perplexity, &a, &o.info));
+    o.indices.resize(o.info.nnz), o.values.resize(o.info.nnz);
+    return o;
+}
+/// crgpu_tsne_dev: the iterations first_iter .. first_iter + n_iters of max_iter on y, uY, gains ([n][dims], in and out); returns the
+/// counters, info.kl the cost at the y the call ends on
+inline crgpu_tsne_result tsne_run(Context &ctx, const TsneAffinities &p, uint32_t dims, std::vector<double> &y, std::vector<double> &uY,
+                                  std::vector<double> &gains, uint32_t first_iter, uint32_t n_iters, uint32_t max_iter = 1000,
+                                  uint32_t stop_lying_iter = 250, uint32_t mom_switch_iter = 250) {
+    crgpu_tsne_args a{};
+    a.first_iter = first_iter, a.n_iters = n_iters, a.max_iter = max_iter, a.stop_lying_iter = stop_lying_iter, a.mom_switch_iter = mom_switch_iter;
+    crgpu_tsne_result r{};
+    ctx.check(crgpu_tsne_dev(ctx.get(), p.indptr.data(), p.indices.data(), p.values.data(), p.indptr.size() - 1, dims, y.data(), uY.data(), gains.data(),
+                             &a, &r));
+    return r;
+}
+
 // ---- CORRECT_CHEMISTRY_BATCH: batch-balanced neighbours, mutual nearest neighbours, the correction of the merged batches ---------------
 static_assert(sizeof(crgpu_knn_cross_args) == 48, "crgpu_knn_cross_args changed: bump CRGPU_ABI_VERSION and every binding");
 static_assert(sizeof(crgpu_bc_step) == 48, "crgpu_bc_step changed: bump CRGPU_ABI_VERSION and every binding");
