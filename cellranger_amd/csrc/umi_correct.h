@@ -30,15 +30,20 @@
 //      against which every key of the segment is probed.
 #pragma once
 
-// 1024-key tiles: 28 KB of LDS, five workgroups per CU.  The kernel waits at its barriers most of the time
-// (SQ_WAIT_ANY 73 % of the wave cycles), so residency beats tile size: 2048-key tiles (57 KB, two per CU) were
-// 12 % slower on the whole dedup stage even though fewer segments cross a tile edge.
+// 1024-key tiles: 28 KB of LDS, five workgroups per CU.  The kernel waits most of the time (SQ_WAIT_ANY 73 % of the wave
+// cycles: at its barriers and, until the loads of a tile were all requested ahead of their first use, for four dependent
+// round trips per tile -- profiles/umi_staging_phases.txt), so residency beats tile size: 2048-key tiles (57 KB, two per CU)
+// were 12 % slower on the whole dedup stage even though fewer segments cross a tile edge.
 #ifndef UC_ITEMS
 #define UC_ITEMS 4
 #endif
 #define UC_TILE (256 * UC_ITEMS)
 #ifndef UC_MIN_WG
-#define UC_MIN_WG 1   // second launch-bounds argument: workgroups per CU the register allocation has to allow
+// second launch-bounds argument: the waves per SIMD the register allocation has to allow.  A 256-thread workgroup puts one wave on
+// each of the four SIMDs of a CU, so here (and only with this workgroup size) it is also the workgroups per CU, UC_GRID_WG.  The
+// staged loads of a whole tile in flight take the unconstrained allocation to 103 VGPRs, one more than five waves per SIMD
+// leave; bounded, the kernel takes 90 and no scratch.
+#define UC_MIN_WG 5
 #endif
 #define UC_BLOCKS (UC_TILE / 64)
 #ifndef UC_SMALL
@@ -147,6 +152,40 @@ struct Best {
     }
 };
 
+// -DUC_PHASE_TIMING: thread 0 of every workgroup adds the shader-clock ticks of each phase of a tile ([0] loads arrived, [1] heads
+// + LDS stores, [2] head scan, [3] bounds + inserts, [4] search, [5] hash clear, [6] tiles) and of an edge boundary ([14] the walk
+// over the boundaries up to one that owns a segment of this instantiation, [9] hash clear + staging, [10] inserts, [11] search,
+// [12] segments; both instantiations into the same counters; a boundary that hands its segment to the giant kernels has no mark
+// of its own, its time goes to [14] of the next segment) to g_uc_phase
+// (attribution builds only, scripts/umi_phases.py; crgpu_debug_uc_phases reads and clears the counters)
+#ifdef UC_PHASE_TIMING
+__device__ unsigned long long g_uc_phase[16];
+#define UC_PH_BEGIN() unsigned long long ph_t = __builtin_readcyclecounter()
+#define UC_PH(i)                                                            \
+    do {                                                                    \
+        if (threadIdx.x == 0) {                                             \
+            const unsigned long long t_ = __builtin_readcyclecounter();     \
+            atomicAdd(&g_uc_phase[i], t_ - ph_t);                           \
+            ph_t = t_;                                                      \
+        }                                                                   \
+    } while (0)
+#define UC_PH_COUNT(i)                                          \
+    do {                                                        \
+        if (threadIdx.x == 0) atomicAdd(&g_uc_phase[i], 1ull);  \
+    } while (0)
+#define UC_PH_ARRIVED() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+extern "C" int crgpu_debug_uc_phases(unsigned long long *out16) {
+    unsigned long long z[16] = {0};
+    if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_uc_phase), sizeof(z)) != hipSuccess) return -1;
+    return hipMemcpyToSymbol(HIP_SYMBOL(g_uc_phase), z, sizeof(z)) == hipSuccess ? 0 : -1;
+}
+#else
+#define UC_PH_BEGIN() ((void)0)
+#define UC_PH(i) ((void)0)
+#define UC_PH_COUNT(i) ((void)0)
+#define UC_PH_ARRIVED() ((void)0)
+#endif
+
 // best Hamming-1 neighbour of the key at LDS position `self` among the members of segment [s, e) staged in
 // LDS (s_umi sorted ascending inside the segment).  Returns the LDS position or `self`.
 template <uint32_t BUCKETS, uint32_t POSBITS>
@@ -205,36 +244,55 @@ __global__ __launch_bounds__(256, UC_MIN_WG) void k_correct_umis_tiled(const KL 
     const uint64_t n_tiles = (nd + UC_TILE - 1) / UC_TILE;
     for (uint32_t h = tid; h < UC_BUCKETS * 8; h += 256) s_hash[h] = UC_EMPTY;
     if (tid == 0) s_any_long = 0;
+    UC_PH_BEGIN();
     for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const uint64_t t0 = tile * UC_TILE;
         const uint32_t tn = nd - t0 < UC_TILE ? (uint32_t)(nd - t0) : UC_TILE;
-        // ---- stage (coalesced; lane l of round r holds position 256*r + tid) + head flags ----
+        // ---- stage (coalesced; lane l of round r holds position 256*r + tid): every load of the tile is requested before the
+        // first one is used, from addresses clamped into [0, nd - 1]; what the clamped lanes hold is never looked at.  (One
+        // round's loads behind `p < tn`, consumed by that round's ballot, made a tile wait for UC_ITEMS round trips in turn.)
+        const uint64_t last_key = nd - 1;
+        uint64_t key[UC_ITEMS], left[UC_ITEMS];
+        uint32_t pos[UC_ITEMS], end[UC_ITEMS];
+#pragma unroll
+        for (int r = 0; r < UC_ITEMS; r++) {
+            const uint64_t k = t0 + (uint32_t)r * 256u + tid < last_key ? t0 + (uint32_t)r * 256u + tid : last_key;
+            key[r] = ukey[k];
+            left[r] = ukey[k ? k - 1 : 0];  // the previous key is the neighbouring lane's load (same cache line)
+            pos[r] = upos[k];
+            end[r] = upos[k < last_key ? k + 1 : last_key];
+        }
+        uint64_t halo = 0, halo_left = 0;  // thread 0 alone looks at them (the branch depends on no loaded value)
+        if (tid == 0) {
+            halo = ukey[t0 + UC_TILE < last_key ? t0 + UC_TILE : last_key];
+            halo_left = ukey[t0 + UC_TILE - 1 < last_key ? t0 + UC_TILE - 1 : last_key];
+        }
+        UC_PH_ARRIVED();
+        UC_PH(0);
+        // ---- head flags, UMI and read count of every position ----
 #pragma unroll
         for (int r = 0; r < UC_ITEMS; r++) {
             const uint32_t p = (uint32_t)r * 256u + tid;
-            bool head = false;
+            bool head = p == tn;  // the padding behind the last key closes the last segment
             if (p < tn) {
-                const uint64_t key = ukey[t0 + p];
-                const uint64_t pre = key >> kl.sh_lib;
-                // the previous key is the neighbouring lane's load (same cache line)
-                head = (t0 + p == 0) || (ukey[t0 + p - 1] >> kl.sh_lib) != pre;
-                s_umi[p] = (uint32_t)((key >> kl.sh_umi) & umi_mask);
-                const uint32_t end = t0 + p + 1 < nd ? upos[t0 + p + 1] : (uint32_t)n_keys;
+                const uint64_t pre = key[r] >> kl.sh_lib;
+                head = (t0 + p == 0) || (left[r] >> kl.sh_lib) != pre;
+                s_umi[p] = (uint32_t)((key[r] >> kl.sh_umi) & umi_mask);
+                const uint32_t e = t0 + p + 1 < nd ? end[r] : (uint32_t)n_keys;
                 const uint32_t lib = (uint32_t)((pre >> kl.bits_ulen) & lowmask(kl.bits_lib));
                 // UmiCorrection::Disable for Multiplexing Capture (aligner.rs:315-318)
-                s_cnt[p] = (end - upos[t0 + p]) | (((kl.mux_mask >> lib) & 1u) ? UC_NOCORR : 0u);
-            } else {
-                head = p == tn;  // the padding behind the last key closes the last segment
+                s_cnt[p] = (e - pos[r]) | (((kl.mux_mask >> lib) & 1u) ? UC_NOCORR : 0u);
             }
             const unsigned long long m = __ballot(head);
             if (lane == 0) s_heads[p >> 6] = m;
         }
         if (tid == 0) {
-            bool hh = true;  // the end of the array closes the segment
-            if (t0 + UC_TILE < nd) hh = (ukey[t0 + UC_TILE] >> kl.sh_lib) != (ukey[t0 + UC_TILE - 1] >> kl.sh_lib);
+            // the end of the array closes the segment
+            const bool hh = t0 + UC_TILE < nd ? (halo >> kl.sh_lib) != (halo_left >> kl.sh_lib) : true;
             s_halo_head = hh ? 1u : 0u;
         }
         __syncthreads();
+        UC_PH(1);
         if (tid < 64) {
             // one wave, lane b = block b of 64 keys: the last segment head before each block and the first one behind it
             // (prefix maximum / suffix minimum over the blocks by shuffles -- sixteen lanes looping over sixteen masks
@@ -273,6 +331,7 @@ __global__ __launch_bounds__(256, UC_MIN_WG) void k_correct_umis_tiled(const KL 
             }
         }
         __syncthreads();
+        UC_PH(2);
         // ---- segment bounds of every key; members of long in-tile segments enter the hash set ----
         bool inserted = false;
 #pragma unroll
@@ -294,6 +353,7 @@ __global__ __launch_bounds__(256, UC_MIN_WG) void k_correct_umis_tiled(const KL 
         }
         if (inserted) s_any_long = 1;
         __syncthreads();
+        UC_PH(3);
         // ---- one key per lane per round; segments that cross a tile edge belong to k_correct_umis_edges ----
 #pragma unroll 1
         for (int r = 0; r < UC_ITEMS; r++) {
@@ -317,11 +377,14 @@ __global__ __launch_bounds__(256, UC_MIN_WG) void k_correct_umis_tiled(const KL 
             if (target != NONE32) move_reads(corr, st, inc_all, minidx, k, target, my_cnt);
         }
         __syncthreads();
+        UC_PH(4);
         if (s_any_long) {
             for (uint32_t h = tid; h < UC_BUCKETS * 8; h += 256) s_hash[h] = UC_EMPTY;
             __syncthreads();
             if (tid == 0) s_any_long = 0;
         }
+        UC_PH(5);
+        UC_PH_COUNT(6);
     }
 }
 
@@ -343,6 +406,9 @@ __global__ __launch_bounds__(EdgeCfg<SMALL>::THREADS) void k_correct_umis_edges(
     const uint64_t umi_mask = lowmask(kl.bits_umi);
     const UmiSplit sp = umi_split(kl.umi_len);
     const uint64_t n_tiles = (nd + UC_TILE - 1) / UC_TILE;
+    UC_PH_BEGIN();
+    // (The head words and first keys of four boundaries requested together, and the staging below in batches of four positions
+    // per thread, were measured: both instantiations 4 % slower alone on the stream, profiles/umi_staging_phases.txt.)
     for (uint64_t t = (uint64_t)blockIdx.x + 1; t < n_tiles; t += gridDim.x) {
         // every thread reads the same few words: the branches below are uniform across the workgroup
         const uint32_t tf = tile_first[t];
@@ -369,6 +435,7 @@ __global__ __launch_bounds__(EdgeCfg<SMALL>::THREADS) void k_correct_umis_edges(
         if (m <= CAP) {
             const uint32_t mm = (uint32_t)m;
             const bool use_hash = mm > UC_SMALL;
+            UC_PH(14);
             if (use_hash)
                 for (uint32_t h = tid; h < BUCKETS * 8; h += UE_T) s_hash[h] = UC_EMPTY;
             for (uint32_t p = tid; p < mm; p += UE_T) {
@@ -377,11 +444,13 @@ __global__ __launch_bounds__(EdgeCfg<SMALL>::THREADS) void k_correct_umis_edges(
                 s_cnt[p] = run_count(upos, nd, n_keys, k);
             }
             __syncthreads();
+            UC_PH(9);
             if (use_hash) {
                 for (uint32_t p = tid; p < mm; p += UE_T)
                     uc_insert<BUCKETS, POSBITS>(s_hash, 0u, s_umi[p] & sp.lo_mask, p);
                 __syncthreads();
             }
+            UC_PH(10);
             for (uint32_t p = tid; p < mm; p += UE_T) {
                 const uint32_t my_cnt = s_cnt[p];
                 const uint32_t bp = best_neighbour_lds<BUCKETS, POSBITS>(s_umi, s_cnt, s_hash, nullptr, 0u, mm, 0u, p,
@@ -389,6 +458,8 @@ __global__ __launch_bounds__(EdgeCfg<SMALL>::THREADS) void k_correct_umis_edges(
                 if (bp != p) move_reads(corr, st, inc_all, minidx, s + p, (uint32_t)(s + bp), my_cnt);
             }
             __syncthreads();
+            UC_PH(11);
+            UC_PH_COUNT(12);
             continue;
         }
         // ---- larger than the LDS budget: one work item per chunk of CAP keys for the k_giant_* kernels, so that a
