@@ -20,13 +20,13 @@
 // The entry points of a context are serialised (CR_ENTER) and each one zeroes the words it takes before it uses them, so two
 // users of one word only have to be entry points that never run inside each other.
 #define CR_SCALAR_MISS_COUNT 0         // u64 (2 words): reads left to the correction pass (barcode.hip)
-#define CR_SCALAR_KEY_COUNT 8          // u64 (2 words): keys the key builder wrote (dedup.hip)
+#define CR_SCALAR_KEY_COUNT 8          // u64 (2 words): keys the key builder wrote (keys.hip)
 #define CR_SCALAR_TOTAL 16             // 1 word, anybody: the total of a compaction or of cr_scan_small, read back before the next one
                                        // (the feature extraction keeps the length of its queue here)
 #define CR_SCALAR_TRIPLET_TOTAL 17     // 1 word: the count stage's triplet total, alive beside CR_SCALAR_TOTAL (dedup.hip)
 #define CR_SCALAR_LIB_MASK 28          // 1 word: the libraries that occur in a flag array (barcode.hip)
 #define CR_SCALAR_N_WITHOUT_FLAGS 40   // 1 word: reads that came without flags (barcode.hip)
-#define CR_SCALAR_KEY_TICKET 44        // 1 word: chunk tickets of the ordered key builder (dedup.hip)
+#define CR_SCALAR_KEY_TICKET 44        // 1 word: chunk tickets of the ordered key builder (keys.hip)
 // The flag words of the entry point that runs: "an input was refused", or a small count.  Most entry points take the first word
 // only; the Flex tags (rtl_tags.h) take 2 words, the matrix summary (matrix_summary.h) takes 3 (48 .. 50).  EmptyDrops takes
 // word 48 as its flag and names word 49 by itself (CR_SCALAR_FLAG_AUX: the largest row, then the ambient barcodes used).  These
@@ -171,7 +171,7 @@ struct KeyHistograms {
 // matrix column: the canonical barcodes with a non-zero VALID or CORRECTED count in any library, ascending --
 // cr_types/src/barcode_index.rs:20-53) instead of its rank on the whitelist: ~2 * 10^5 values (18 bits) where the
 // 3M-february-2018 list needs 23 and a GelBeadAndProbe product space 24+.  Built from the tables when the first key is
-// built, dropped by everything that changes a table (dedup.hip: cr_dense_ensure / cr_dense_drop).
+// built, dropped by everything that changes a table (cr_dense_ensure in matrix_dev.hip, cr_dense_drop in ctx.hip).
 struct DenseIndex {
     bool on = false, valid = false;
     uint32_t V = 0;               // columns
@@ -319,7 +319,7 @@ struct CrEnter {
 #define CR_ENTER(ctx) CrEnter _cr_enter(ctx)
 // forget every by-product kept for the next call (K1's miss records, the key histograms)
 void cr_invalidate(crgpu_ctx *ctx);
-// dedup.hip: (re)build the dense barcode index from the tables when the option is on (no-op otherwise) / forget it
+// (re)build the dense barcode index from the tables when the option is on (no-op otherwise; matrix_dev.hip) / forget it (ctx.hip)
 int cr_dense_ensure(crgpu_ctx *ctx);
 void cr_dense_drop(crgpu_ctx *ctx);
 void cr_dense_free(crgpu_ctx *ctx);

@@ -1,9 +1,10 @@
-// dedup.hip -- count stage: molecule keys, run-length grouping, UMI correction, low-support
-// filtering and (barcode, feature) counting on sorted 64-bit keys; then the device matrix (assembly,
-// sum, column selection).  The analysis stages behind it are molecule_stages.hip and matrix_stages.hip.
+// dedup.hip -- count stage: run-length grouping, UMI correction, low-support filtering and (barcode, feature)
+// counting on sorted 64-bit molecule keys, and what a caller reads from the counts.  The keys are built in
+// keys.hip; the device matrix made of the triplets is matrix_dev.hip, and the analysis stages behind it are
+// molecule_stages.hip and matrix_stages.hip.
 //
 // Replaces, per (barcode, library type) group of the reference:
-//   UmiInfo::new                      umi/src/info.rs:20-37        (validity of each UMI)
+//   UmiInfo::new                      umi/src/info.rs:20-37        (validity of each UMI; keys.hip)
 //   DupBuilder::observe               tx_annotation/src/mark_dups.rs:128-155
 //   correct_umis                      mark_dups.rs:19-59
 //   BarcodeDupMarker::new             mark_dups.rs:202-277  (two-phase count move)
@@ -19,620 +20,8 @@
 //   * a (barcode, feature) segment is one matrix entry.
 // Low-support grouping needs (barcode, library, UMI) across features: the DISTINCT keys are sorted a
 // second time by a 32-bit hash of that triple (index as payload) and re-checked exactly.
+#include "keys.h"
 #include "stage_common.h"
-// ------------------------------------------------------------------------------------------------
-// key layout
-// ------------------------------------------------------------------------------------------------
-extern "C" int crgpu_set_key_layout(crgpu_ctx *ctx, uint32_t n_features, uint32_t umi_len, uint32_t n_libs,
-                                    uint32_t multiplexing_lib_mask) {
-    if (!ctx) return CRGPU_EINVAL;
-    CR_ENTER(ctx);
-    CR_REQUIRE(ctx, ctx->canon_set, CRGPU_ESTATE, "crgpu_set_key_layout: set the whitelist first");
-    CR_REQUIRE(ctx, n_features >= 1, CRGPU_EINVAL, "n_features must be >= 1");
-    CR_REQUIRE(ctx, umi_len >= 1 && umi_len <= 16, CRGPU_ERANGE, "umi_len must be 1..16");
-    CR_REQUIRE(ctx, n_libs >= 1 && n_libs <= CRGPU_MAX_LIB, CRGPU_EINVAL, "n_libs must be 1..%d", CRGPU_MAX_LIB);
-    KeyLayout L;
-    L.bits_bc = cr_ceil_log2(ctx->n_canon);
-    L.bits_feat = cr_ceil_log2(n_features);
-    L.bits_lib = cr_ceil_log2(n_libs);
-    L.bits_umi = 2 * umi_len;
-    L.n_features = n_features;
-    L.umi_len = umi_len;
-    L.umi_min_len = umi_len;
-    L.n_libs = n_libs;
-    L.mux_mask = multiplexing_lib_mask;
-    // with CRGPU_OPT_DENSE_BARCODE_KEYS the barcode field shrinks to the columns that occur (known when the first key is built)
-    CR_REQUIRE(ctx, L.total_bits() <= 64 || (ctx->dense.on && L.total_bits() - L.bits_bc + 1u <= 64u), CRGPU_ERANGE,
-               "molecule key needs %u bits (barcode %u + feature %u + library %u + umi %u + 1) > 64%s", L.total_bits(),
-               L.bits_bc, L.bits_feat, L.bits_lib, L.bits_umi,
-               ctx->dense.on ? "" : " (CRGPU_OPT_DENSE_BARCODE_KEYS shortens the barcode field to the barcodes that occur)");
-    L.set = true;
-    cr_dense_drop(ctx);
-    ctx->dense.canon_bits = L.bits_bc;
-    ctx->layout = L;
-    cr_invalidate(ctx);
-    return CRGPU_OK;
-}
-
-// targeted gene expression: DupBuilder::build(.., targeted_umi_min_read_count) + FeatureReference::target_set
-// (mark_dups.rs:156-169,311-320; the threshold comes from _slfe_matrix_computer.mro:122-140).  on_target: n_features bytes
-// (host), non-zero = the feature is in the target set; NULL or min_read_count == 0 switches the filter off.
-extern "C" int crgpu_set_target_filter(crgpu_ctx *ctx, const uint8_t *on_target, uint32_t n_features, uint64_t min_read_count) {
-    if (!ctx) return CRGPU_EINVAL;
-    CR_ENTER(ctx);
-    CR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    if (ctx->d_on_target) CR_HIP(ctx, hipFree(ctx->d_on_target));
-    ctx->d_on_target = nullptr;
-    ctx->n_target_features = 0;
-    ctx->target_min_reads = 0;
-    if (!on_target || !min_read_count || !n_features) return CRGPU_OK;
-    CR_HIP(ctx, hipMalloc((void **)&ctx->d_on_target, n_features));
-    CR_HIP(ctx, hipMemcpy(ctx->d_on_target, on_target, n_features, hipMemcpyHostToDevice));
-    ctx->n_target_features = n_features;
-    ctx->target_min_reads = min_read_count;
-    return CRGPU_OK;
-}
-
-// Per-read UMI lengths (UmiExtractor::extract_umi, cr_types/src/rna_read.rs:103-138: a read that ends early keeps
-// max(min(read_len - offset, length), min_length) bases): UMIs of different lengths are different UmiSeqs, so the length
-// becomes part of the key -- a tag (umi_len - length) right above the UMI bits.  Call after crgpu_set_key_layout.
-extern "C" int crgpu_set_umi_min_len(crgpu_ctx *ctx, uint32_t umi_min_len) {
-    if (!ctx) return CRGPU_EINVAL;
-    CR_ENTER(ctx);
-    CR_REQUIRE(ctx, ctx->layout.set, CRGPU_ESTATE, "crgpu_set_umi_min_len: call crgpu_set_key_layout first");
-    KeyLayout L = ctx->layout;
-    CR_REQUIRE(ctx, umi_min_len >= 1 && umi_min_len <= L.umi_len, CRGPU_EINVAL, "umi_min_len must be 1..umi_len (%u)", L.umi_len);
-    L.umi_min_len = umi_min_len;
-    L.bits_ulen = cr_ceil_log2(L.umi_len - umi_min_len + 1);
-    cr_dense_drop(ctx);
-    L.bits_bc = ctx->dense.canon_bits;
-    CR_REQUIRE(ctx, L.total_bits() <= 64 || (ctx->dense.on && L.total_bits() - L.bits_bc + 1u <= 64u), CRGPU_ERANGE,
-               "molecule key needs %u bits with %u bits of UMI length > 64", L.total_bits(), L.bits_ulen);
-    ctx->layout = L;
-    cr_invalidate(ctx);
-    return CRGPU_OK;
-}
-
-struct KL {  // device copy of the layout
-    uint32_t sh_umi, sh_lib, sh_feat, sh_bc, bits_umi, bits_lib, bits_feat, bits_bc, umi_len, n_features, n_libs, mux_mask;
-    uint32_t bits_ulen, sh_libid, umi_min_len;
-};
-static KL make_kl(const KeyLayout &L) {
-    return KL{L.sh_umi(), L.sh_lib(), L.sh_feat(), L.sh_bc(), L.bits_umi, L.bits_lib, L.bits_feat, L.bits_bc,
-              L.umi_len, L.n_features, L.n_libs, L.mux_mask, L.bits_ulen, L.sh_libid(), L.umi_min_len};
-}
-typedef uint32_t cr_v4u32 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ uint4 ld_stream4(const uint4 *p) {  // 16-byte load that does not stay in the caches
-    const cr_v4u32 v = __builtin_nontemporal_load(reinterpret_cast<const cr_v4u32 *>(p));
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-// CRGPU_OPT_DENSE_BARCODE_KEYS: column of a whitelist rank in the BarcodeIndex, or CRGPU_MISS (DenseIndex::d_fwd)
-__device__ __forceinline__ uint32_t dense_column(const uint4 *__restrict__ fwd, uint32_t rank) {
-    const uint4 e = fwd[rank >> 6];
-    const unsigned long long bits = ((unsigned long long)e.y << 32) | e.x;
-    const uint32_t bit = rank & 63u;
-    if (!((bits >> bit) & 1ull)) return CRGPU_MISS;
-    return e.z + (uint32_t)__popcll(bits & ((1ull << bit) - 1ull));
-}
-
-// ------------------------------------------------------------------------------------------------
-// build keys (compacting)
-// ------------------------------------------------------------------------------------------------
-#define KEY_ITEMS 16
-#define KEY_BATCH 4  // reads whose loads are issued together: the kernel is bound by load latency, not bandwidth
-// a row of UMI qualities as LQW dwords (rows of 4k bytes are dword aligned); LQW = 0: byte path
-template <int LQW>
-struct __attribute__((aligned(4))) QRow {
-    uint32_t w[LQW ? LQW : 1];
-};
-// ORDERED (the keys travel with their read ordinals: the DupInfo paths): the compaction keeps the read order -- chunks
-// are handed out by a ticket counter and get their output offset from a decoupled look-back over `status` (one word
-// per chunk: flag in the top two bits, 1 = this chunk's count, 2 = inclusive prefix), so equal keys leave in qname
-// order.  The sharded path relies on it: the owner of a barcode sees only the position of a key in its receive buffer.
-// Without ORDERED a chunk reserves its space with one atomic and the chunks land in arrival order.
-#define BK_AGG (1ull << 62)
-#define BK_INC (2ull << 62)
-template <int LQW, bool HIST, bool ORDERED = false>
-__global__ __launch_bounds__(256) void k_build_keys(const KL kl, const uint32_t *__restrict__ bc_idx,
-                                                    const uint32_t *__restrict__ umi, const uint8_t *__restrict__ umi_q,
-                                                    const uint32_t *__restrict__ feature, const uint8_t *__restrict__ flags,
-                                                    uint64_t n, uint64_t *__restrict__ keys_out,
-                                                    uint32_t *__restrict__ vals_out,
-                                                    unsigned long long *__restrict__ n_out, const SweepPlan plan,
-                                                    uint32_t *__restrict__ ghist, unsigned long long *__restrict__ status,
-                                                    uint32_t *__restrict__ ticket, const uint8_t *__restrict__ ulen,
-                                                    const uint4 *__restrict__ dense_fwd, uint32_t *__restrict__ n_unknown,
-                                                    uint32_t *__restrict__ lb_abort) {
-    // lb_abort: the watchdog word of the ORDERED look-back (block_utils.h)
-    // dense_fwd (nullable): barcode rank -> column of the BarcodeIndex (CRGPU_OPT_DENSE_BARCODE_KEYS)
-    // ulen (nullable, byte path LQW == 0 only): the UMI length of every read, umi_min_len .. umi_len
-    __shared__ __attribute__((aligned(8))) uint32_t lds[10];
-    __shared__ unsigned long long s_c;  // ORDERED: the chunk of this round, then its output offset
-    __shared__ uint32_t s_ws[KEY_ITEMS * 4];  // ORDERED: kept keys of (item slot, wave), then their exclusive prefix
-    // ghist != NULL: the digits of every emitted key are counted for all passes of the sort that follows, which
-    // then needs no histogram read of its own (k_global_hist)
-    __shared__ uint32_t s_hist[HIST ? OS_MAX_PASSES * RADIX_MAX : 1];
-    if (HIST) {
-        for (uint32_t x = threadIdx.x; x < plan.n_passes * RADIX_MAX; x += 256) s_hist[x] = 0;
-        __syncthreads();
-    }
-    const uint32_t L = kl.umi_len;
-    const uint64_t chunk = 256ull * KEY_ITEMS;
-    const uint64_t n_chunks = (n + chunk - 1) / chunk;
-    const uint32_t umi_mask = (uint32_t)lowmask(kl.bits_umi), adj_mask = (uint32_t)lowmask(kl.bits_umi - 2u);
-    for (uint64_t c = blockIdx.x;; c += gridDim.x) {
-      if (ORDERED) {
-          if (threadIdx.x == 0) s_c = atomicAdd(ticket, 1u);
-          __syncthreads();
-          c = s_c;
-          __syncthreads();
-      }
-      if (c >= n_chunks) break;  // uniform
-      uint64_t keys[KEY_ITEMS];
-      uint32_t mask = 0;
-#pragma unroll
-      for (int j0 = 0; j0 < KEY_ITEMS; j0 += KEY_BATCH) {
-        // every field of KEY_BATCH reads is requested before any is looked at (no load sits behind a branch)
-        uint32_t vb[KEY_BATCH], vf[KEY_BATCH], vfl[KEY_BATCH], vu[KEY_BATCH], vl[KEY_BATCH];
-        QRow<LQW> vq[KEY_BATCH];
-#pragma unroll
-        for (int jj = 0; jj < KEY_BATCH; jj++) {
-            const uint64_t i = c * chunk + (uint64_t)(j0 + jj) * 256 + threadIdx.x;
-            const bool ok = i < n;
-            vb[jj] = ok ? bc_idx[i] : CRGPU_MISS;
-            vf[jj] = ok ? feature[i] : CRGPU_NO_FEATURE;
-            vfl[jj] = (ok && flags) ? flags[i] : 0u;
-            vu[jj] = ok ? umi[i] : 0u;
-            vl[jj] = (LQW == 0 && ok && ulen) ? ulen[i] : L;
-            if (LQW) {
-                if (ok) vq[jj] = *reinterpret_cast<const QRow<LQW> *>(umi_q + i * (uint64_t)(4 * LQW));
-                else
-                    for (int k = 0; k < (LQW ? LQW : 1); k++) vq[jj].w[k] = 0u;
-            }
-        }
-#pragma unroll
-        for (int jj = 0; jj < KEY_BATCH; jj++) {
-            const int j = j0 + jj;
-            const uint64_t i = c * chunk + (uint64_t)j * 256 + threadIdx.x;
-            uint32_t b = vb[jj];
-            const uint32_t f = vf[jj], fl = vfl[jj];
-            const uint32_t lib = fl & CRGPU_FLAG_LIB_MASK;
-            if (dense_fwd && b != CRGPU_MISS) {
-                b = dense_column(dense_fwd, b);
-                if (b == CRGPU_MISS) atomicAdd(n_unknown, 1u);  // a barcode without reads in the tables: the call fails
-            }
-            bool keep = b != CRGPU_MISS && f != CRGPU_NO_FEATURE && f < kl.n_features && lib < kl.n_libs;
-            // this read's UMI length (a length outside umi_min_len .. umi_len: the reference's check_range fails, no UMI)
-            const uint32_t Li = LQW == 0 ? vl[jj] : L;
-            if (LQW == 0 && (Li < kl.umi_min_len || Li > L)) keep = false;
-            const uint32_t Lc = (LQW == 0 && Li >= 1u && Li <= L) ? Li : L;
-            const uint32_t u = vu[jj] & (LQW == 0 ? (uint32_t)lowmask(2u * Lc) : umi_mask);
-            // UmiInfo::new (umi/src/info.rs:20-37)
-            bool has_n = false, low_q = false;
-            if (LQW) {
-#pragma unroll
-                for (int k = 0; k < (LQW ? LQW : 1); k++) {
-                    const uint32_t w = vq[jj].w[k];
-                    has_n |= (w & 0x80808080u) != 0u;
-#pragma unroll
-                    for (int bb = 0; bb < 4; bb++) low_q |= (uint8_t)(((w >> (8 * bb)) & 0x7Fu) - 33u) < 10u;
-                }
-            } else if (keep) {
-                for (uint32_t k = 0; k < Lc; k++) {
-                    const uint32_t q = umi_q[i * L + k];
-                    has_n |= (q & 0x80u) != 0u;
-                    low_q |= (uint8_t)((q & 0x7Fu) - 33u) < 10u;  // u8 wrapping subtraction, UMI_MIN_QV = 10
-                }
-            }
-            // is_homopolymer: every adjacent pair equal (true for a 1-base UMI)
-            const bool homopolymer = ((u ^ (u >> 2)) & (LQW == 0 ? (uint32_t)lowmask(2u * Lc - 2u) : adj_mask)) == 0u;
-            keep = keep && !(has_n || homopolymer || low_q);
-            keys[j] = ((uint64_t)b << kl.sh_bc) | ((uint64_t)f << kl.sh_feat) | ((uint64_t)lib << kl.sh_libid) |
-                      ((uint64_t)(L - Lc) << kl.sh_lib) | ((uint64_t)u << kl.sh_umi) | ((fl & CRGPU_FLAG_NONTXOMIC) ? 1ull : 0ull);
-            if (keep) mask |= 1u << j;
-            if (HIST && keep)
-                for (uint32_t p = 0; p < plan.n_passes; p++)
-                    atomicAdd(&s_hist[p * RADIX_MAX + ((uint32_t)(keys[j] >> plan.shift[p]) & plan.mask[p])], 1u);
-        }
-      }
-      if (ORDERED) {
-          // stable inside the chunk, too: output order = (item slot, wave, lane) = ascending read index
-          uint32_t below[KEY_ITEMS];
-          const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-#pragma unroll
-          for (int j = 0; j < KEY_ITEMS; j++) {
-              const unsigned long long m = __ballot((mask >> j) & 1u);
-              below[j] = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-              if (lane == 0) s_ws[j * 4 + wave] = (uint32_t)__popcll(m);
-          }
-          __syncthreads();
-          if (threadIdx.x < KEY_ITEMS * 4) {  // one wave: exclusive scan of the 64 (slot, wave) counts + the look-back
-              const uint32_t v = s_ws[threadIdx.x];
-              const uint32_t x = wave_incl_scan<KEY_ITEMS * 4>(v, threadIdx.x);
-              s_ws[threadIdx.x] = x - v;
-              const uint32_t total = __shfl(x, 63);
-              if (threadIdx.x == 0 && c > 0)
-                  __hip_atomic_store(&status[c], BK_AGG | total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-              // every lower ticket is held by a workgroup that is running or done: the chain always moves on
-              const unsigned long long excl = wave_lookback(status, c, lb_abort);
-              if (threadIdx.x == 0) {
-                  if (excl != WAVE_LOOKBACK_ABORTED) {
-                      __hip_atomic_store(&status[c], BK_INC | (excl + total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                      if (c + 1 == n_chunks) *n_out = excl + total;
-                  }
-                  s_c = excl;
-              }
-          }
-          __syncthreads();
-          const unsigned long long base = s_c;
-          if (base == WAVE_LOOKBACK_ABORTED) break;  // uniform: the host reports the stall (lb_abort is set)
-#pragma unroll
-          for (int j = 0; j < KEY_ITEMS; j++)
-              if (mask & (1u << j)) {
-                  const unsigned long long o = base + s_ws[j * 4 + wave] + below[j];
-                  keys_out[o] = keys[j];
-                  if (vals_out) vals_out[o] = (uint32_t)(c * chunk + (uint64_t)j * 256 + threadIdx.x);  // read ordinal
-              }
-          __syncthreads();
-      } else {
-          // one global atomic per 4096-read chunk (same-address atomics saturate near 88 per microsecond); inside a wave
-          // the kept keys leave item slot by item slot, so that a store instruction writes consecutive addresses
-          const unsigned long long o = block_reserve_256((uint32_t)__popc(mask), n_out, lds);
-          unsigned long long wo = __shfl(o, 0);  // the wave's base = the offset of its first lane
-          const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-          for (int j = 0; j < KEY_ITEMS; j++) {
-              const bool k = (mask >> j) & 1u;
-              const unsigned long long m = __ballot(k);
-              if (k) {
-                  const unsigned long long p = wo + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-                  keys_out[p] = keys[j];
-                  if (vals_out) vals_out[p] = (uint32_t)(c * chunk + (uint64_t)j * 256 + threadIdx.x);  // read ordinal
-              }
-              wo += (uint32_t)__popcll(m);
-          }
-      }
-    }
-    if (HIST) {
-        __syncthreads();
-        for (uint32_t x = threadIdx.x; x < plan.n_passes * RADIX_MAX; x += 256)
-            if (s_hist[x]) atomicAdd(&ghist[x], s_hist[x]);
-    }
-}
-
-// ---- the same for the common case, four consecutive reads per lane --------------------------------------------------------
-// k_build_keys is bound by the number of loads in flight, not by bytes (five loads of 1 to 12 bytes per read).  Here a lane
-// takes four consecutive reads with 16-byte loads: barcode ranks, features and UMIs as one uint4 each, the four flag bytes
-// as one dword, the four quality rows (4 * LQW dwords) as LQW uint4 -- 1.75 loads per read instead of 5.  Keys only (no
-// ordinals, fixed UMI length, dword quality rows), n a multiple of 4, 16-byte aligned arrays; everything else takes
-// k_build_keys.  The kept keys leave in thread-major order inside a chunk, as there: the sort does not care.
-#ifndef KEY_VB
-#define KEY_VB 1
-#endif
-template <int LQW, bool HIST>
-__global__ __launch_bounds__(256) void k_build_keys_v4(const KL kl, const uint32_t *__restrict__ bc_idx, const uint32_t *__restrict__ umi,
-                                                       const uint8_t *__restrict__ umi_q, const uint32_t *__restrict__ feature,
-                                                       const uint8_t *__restrict__ flags, uint64_t n, uint64_t *__restrict__ keys_out,
-                                                       unsigned long long *__restrict__ n_out, const SweepPlan plan,
-                                                       uint32_t *__restrict__ ghist, const uint4 *__restrict__ dense_fwd,
-                                                       uint32_t *__restrict__ n_unknown) {
-    static_assert(LQW >= 1 && LQW <= 4, "dword quality rows");
-    __shared__ __attribute__((aligned(8))) uint32_t lds[10];
-    __shared__ uint32_t s_hist[HIST ? OS_MAX_PASSES * RADIX_MAX : 1];
-    if (HIST) {
-        for (uint32_t x = threadIdx.x; x < plan.n_passes * RADIX_MAX; x += 256) s_hist[x] = 0;
-        __syncthreads();
-    }
-    constexpr int NV = KEY_ITEMS / 4;  // vectors of four reads per thread and chunk
-    const uint32_t L = kl.umi_len;
-    const uint64_t chunk = 256ull * KEY_ITEMS;
-    const uint64_t n_chunks = (n + chunk - 1) / chunk;
-    const uint64_t n_vec = n / 4;  // n is a multiple of 4
-    const uint32_t umi_mask = (uint32_t)lowmask(kl.bits_umi), adj_mask = (uint32_t)lowmask(kl.bits_umi - 2u);
-    const uint4 *__restrict__ bc4 = reinterpret_cast<const uint4 *>(bc_idx);
-    const uint4 *__restrict__ ft4 = reinterpret_cast<const uint4 *>(feature);
-    const uint4 *__restrict__ um4 = reinterpret_cast<const uint4 *>(umi);
-    const uint32_t *__restrict__ fl4 = reinterpret_cast<const uint32_t *>(flags);
-    const uint4 *__restrict__ q4 = reinterpret_cast<const uint4 *>(umi_q);
-    for (uint64_t c = blockIdx.x; c < n_chunks; c += gridDim.x) {
-        uint64_t keys[KEY_ITEMS];
-        uint32_t mask = 0;
-#pragma unroll
-      for (int v0 = 0; v0 < NV; v0 += KEY_VB) {  // KEY_VB vectors' loads are in flight together
-        uint4 vb[KEY_VB], vf[KEY_VB], vu[KEY_VB], vq[KEY_VB][LQW];
-        uint32_t vfl[KEY_VB];
-#pragma unroll
-        for (int vv = 0; vv < KEY_VB; vv++) {
-            const int v = v0 + vv;
-            const uint64_t iv = c * (chunk / 4) + (uint64_t)v * 256 + threadIdx.x;  // index of the vector
-            const uint64_t ic = iv < n_vec ? iv : n_vec - 1;                         // loads from a clamped address
-            if (dense_fwd) {
-                // the rank -> column table has to stay in L2 beside 33 bytes of touch-once input per read: those go past it
-                vb[vv] = ld_stream4(bc4 + ic);
-                vf[vv] = ld_stream4(ft4 + ic);
-                vu[vv] = ld_stream4(um4 + ic);
-                vfl[vv] = fl4 ? __builtin_nontemporal_load(fl4 + ic) : 0u;
-#pragma unroll
-                for (int k = 0; k < LQW; k++) vq[vv][k] = ld_stream4(q4 + ic * LQW + k);
-            } else {
-                vb[vv] = bc4[ic];
-                vf[vv] = ft4[ic];
-                vu[vv] = um4[ic];
-                vfl[vv] = fl4 ? fl4[ic] : 0u;
-#pragma unroll
-                for (int k = 0; k < LQW; k++) vq[vv][k] = q4[ic * LQW + k];
-            }
-        }
-#pragma unroll
-        for (int vv = 0; vv < KEY_VB; vv++) {
-            const int v = v0 + vv;
-            const uint64_t iv = c * (chunk / 4) + (uint64_t)v * 256 + threadIdx.x;
-            uint32_t b4[4] = {vb[vv].x, vb[vv].y, vb[vv].z, vb[vv].w};
-            if (dense_fwd) {  // rank -> column (four independent gathers from a table that stays in L2)
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const uint32_t rk = b4[r];
-                    const uint32_t c = dense_column(dense_fwd, rk != CRGPU_MISS ? rk : 0u);
-                    if (rk != CRGPU_MISS && c == CRGPU_MISS && iv < n_vec) atomicAdd(n_unknown, 1u);
-                    b4[r] = rk != CRGPU_MISS ? c : CRGPU_MISS;
-                }
-            }
-            const uint32_t f4[4] = {vf[vv].x, vf[vv].y, vf[vv].z, vf[vv].w};
-            const uint32_t u4[4] = {vu[vv].x, vu[vv].y, vu[vv].z, vu[vv].w};
-            uint32_t qw[4 * LQW];
-#pragma unroll
-            for (int k = 0; k < LQW; k++) {
-                qw[4 * k + 0] = vq[vv][k].x;
-                qw[4 * k + 1] = vq[vv][k].y;
-                qw[4 * k + 2] = vq[vv][k].z;
-                qw[4 * k + 3] = vq[vv][k].w;
-            }
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const int j = v * 4 + r;
-                const uint32_t b = b4[r], f = f4[r], fl = (vfl[vv] >> (8 * r)) & 0xFFu;
-                const uint32_t lib = fl & CRGPU_FLAG_LIB_MASK;
-                bool keep = iv < n_vec && b != CRGPU_MISS && f != CRGPU_NO_FEATURE && f < kl.n_features && lib < kl.n_libs;
-                const uint32_t u = u4[r] & umi_mask;
-                // UmiInfo::new (umi/src/info.rs:20-37)
-                bool has_n = false, low_q = false;
-#pragma unroll
-                for (int k = 0; k < LQW; k++) {
-                    const uint32_t w = qw[r * LQW + k];
-                    has_n |= (w & 0x80808080u) != 0u;
-#pragma unroll
-                    for (int bb = 0; bb < 4; bb++) low_q |= (uint8_t)(((w >> (8 * bb)) & 0x7Fu) - 33u) < 10u;
-                }
-                const bool homopolymer = ((u ^ (u >> 2)) & adj_mask) == 0u;
-                keep = keep && !(has_n || homopolymer || low_q);
-                keys[j] = ((uint64_t)b << kl.sh_bc) | ((uint64_t)f << kl.sh_feat) | ((uint64_t)lib << kl.sh_libid) |
-                          ((uint64_t)u << kl.sh_umi) | ((fl & CRGPU_FLAG_NONTXOMIC) ? 1ull : 0ull);
-                if (keep) mask |= 1u << j;
-                if (HIST && keep)
-                    for (uint32_t p = 0; p < plan.n_passes; p++)
-                        atomicAdd(&s_hist[p * RADIX_MAX + ((uint32_t)(keys[j] >> plan.shift[p]) & plan.mask[p])], 1u);
-            }
-        }
-      }
-        // one reservation per workgroup and chunk; inside a wave the kept keys leave item slot by item slot, so that a store
-        // instruction writes consecutive addresses (thread-major order made 64 separate 100-byte pieces of every store)
-        const unsigned long long o = block_reserve_256((uint32_t)__popc(mask), n_out, lds);
-        unsigned long long wo = __shfl(o, 0);  // the wave's base = the offset of its first lane
-        const uint32_t lane = threadIdx.x & 63u;
-#pragma unroll
-        for (int j = 0; j < KEY_ITEMS; j++) {
-            const bool k = (mask >> j) & 1u;
-            const unsigned long long m = __ballot(k);
-            if (k) keys_out[wo + (uint32_t)__popcll(m & ((1ull << lane) - 1ull))] = keys[j];
-            wo += (uint32_t)__popcll(m);
-        }
-    }
-    if (HIST) {
-        __syncthreads();
-        for (uint32_t x = threadIdx.x; x < plan.n_passes * RADIX_MAX; x += 256)
-            if (s_hist[x]) atomicAdd(&ghist[x], s_hist[x]);
-    }
-    (void)L;
-}
-
-static int build_keys_impl(crgpu_ctx *ctx, const crgpu_records *recs, uint64_t *d_keys_out, uint32_t *d_vals_out,
-                           uint64_t *n_keys_out) {
-    if (!ctx || !recs || !n_keys_out) return CRGPU_EINVAL;
-    CR_REQUIRE(ctx, ctx->layout.set, CRGPU_ESTATE, "crgpu_build_keys: call crgpu_set_key_layout first");
-    CR_REQUIRE(ctx, recs->umi_len == ctx->layout.umi_len, CRGPU_EINVAL, "records umi_len %u != layout umi_len %u",
-               recs->umi_len, ctx->layout.umi_len);
-    *n_keys_out = 0;
-    if (recs->n == 0) return CRGPU_OK;
-    CR_REQUIRE(ctx, recs->n <= 0x7FFFFFFFull, CRGPU_ERANGE, "crgpu_build_keys: at most 2^31-1 records per call");
-    CR_REQUIRE(ctx, recs->d_bc_idx && recs->d_umi && recs->d_umi_qualn && recs->d_feature && d_keys_out, CRGPU_EINVAL,
-               "crgpu_build_keys: NULL buffer");
-    CR_REQUIRE(ctx, !recs->d_umi_len || ctx->layout.bits_ulen || ctx->layout.umi_min_len == ctx->layout.umi_len, CRGPU_ESTATE,
-               "crgpu_build_keys: per-read UMI lengths need crgpu_set_umi_min_len");
-    CR_REQUIRE(ctx, (recs->umi_len & 3u) != 0u || (uintptr_t)recs->d_umi_qualn % 4 == 0, CRGPU_EINVAL,
-               "crgpu_build_keys: the UMI quality buffer must be 4-byte aligned");
-    unsigned long long *d_n = (unsigned long long *)(ctx->d_scalars + CR_SCALAR_KEY_COUNT);
-    bool append = false;
-    const uint64_t n_before = ctx->ghist.n;
-    CR_TRY(cr_dense_ensure(ctx));  // CRGPU_OPT_DENSE_BARCODE_KEYS: the BarcodeIndex of the tables as they stand (else nothing)
-    const uint4 *d_fwd = ctx->dense.valid ? ctx->dense.d_fwd : nullptr;
-    uint32_t *d_unknown = ctx->d_scalars + CR_SCALAR_BAD_INDEX, *d_lb_abort = ctx->d_scalars + CR_SCALAR_LOOKBACK_ABORT;
-    {
-        CrTimer t(ctx, CRGPU_T_KEYS, recs->n);
-        CR_HIP(ctx, hipMemsetAsync(d_n, 0, sizeof(*d_n), ctx->stream));
-        CR_HIP(ctx, hipMemsetAsync(d_unknown, 0, 2 * sizeof(uint32_t), ctx->stream));
-        const KL kl = make_kl(ctx->layout);
-        // keys only (no read ordinals): count the sort's digit histograms on the way (1024 workgroups keep the
-        // flush at a few million atomics)
-        KeyHistograms &gh = ctx->ghist;
-        const bool had = gh.valid;
-        gh.valid = false;
-        SweepPlan plan;
-        uint32_t widths[OS_MAX_PASSES];
-        memset(&plan, 0, sizeof(plan));
-        uint32_t *d_hist = nullptr;
-        if (ctx->trust_buffers && !getenv("CRGPU_NO_KEY_HIST") && cr_sweep_plan(cr_sort_low_bits(ctx->layout.total_bits(), ctx->layout.bits_umi), ctx->layout.total_bits(), &plan, widths)) {
-            if (!gh.d_hist) CR_TRY(cr_pool_alloc(ctx, (void **)&gh.d_hist, (size_t)OS_MAX_PASSES * RADIX_MAX * sizeof(uint32_t)));
-            d_hist = gh.d_hist;
-            // a call that writes its keys right behind the previous call's (the libraries of a well, one after the other, into
-            // one buffer) adds to that call's histograms: the sort of the whole buffer then still finds them
-            append = had && !d_vals_out && gh.d_keys + gh.n == d_keys_out && memcmp(&gh.plan, &plan, sizeof(plan)) == 0;
-            if (!append) CR_HIP(ctx, hipMemsetAsync(d_hist, 0, (size_t)OS_MAX_PASSES * RADIX_MAX * sizeof(uint32_t), ctx->stream));
-        }
-#ifndef KEY_GRID_HIST
-#define KEY_GRID_HIST 1024u
-#endif
-        const dim3 grid(cr_grid(recs->n, 256, d_hist ? KEY_GRID_HIST : 256u * 8u));
-        // with ordinals: order-preserving compaction (tickets + look-back status, one word per 4096-read chunk)
-        DevBuf status_b;
-        unsigned long long *d_status = nullptr;
-        uint32_t *d_ticket = ctx->d_scalars + CR_SCALAR_KEY_TICKET;
-        if (d_vals_out) {
-            const uint64_t n_chunks = (recs->n + 256ull * KEY_ITEMS - 1) / (256ull * KEY_ITEMS);
-            CR_TRY(dmalloc(ctx, status_b, n_chunks * sizeof(unsigned long long)));
-            d_status = status_b.as<unsigned long long>();
-            CR_HIP(ctx, hipMemsetAsync(d_status, 0, n_chunks * sizeof(unsigned long long), ctx->stream));
-            CR_HIP(ctx, hipMemsetAsync(d_ticket, 0, sizeof(uint32_t), ctx->stream));
-        }
-#define CR_BUILD_KEYS(LQW)                                                                                                  \
-    if (d_vals_out && d_hist)                                                                                               \
-        hipLaunchKernelGGL((k_build_keys<LQW, true, true>), grid, dim3(256), 0, ctx->stream, kl, recs->d_bc_idx, recs->d_umi, \
-                           recs->d_umi_qualn, recs->d_feature, recs->d_flags, recs->n, d_keys_out, d_vals_out, d_n, plan, d_hist, \
-                           d_status, d_ticket, recs->d_umi_len, d_fwd, d_unknown, d_lb_abort);                                          \
-    else if (d_vals_out)                                                                                                    \
-        hipLaunchKernelGGL((k_build_keys<LQW, false, true>), grid, dim3(256), 0, ctx->stream, kl, recs->d_bc_idx, recs->d_umi, \
-                           recs->d_umi_qualn, recs->d_feature, recs->d_flags, recs->n, d_keys_out, d_vals_out, d_n, plan, d_hist, \
-                           d_status, d_ticket, recs->d_umi_len, d_fwd, d_unknown, d_lb_abort);                                          \
-    else if (d_hist)                                                                                                        \
-        hipLaunchKernelGGL((k_build_keys<LQW, true>), grid, dim3(256), 0, ctx->stream, kl, recs->d_bc_idx, recs->d_umi,     \
-                           recs->d_umi_qualn, recs->d_feature, recs->d_flags, recs->n, d_keys_out, d_vals_out, d_n, plan, d_hist, \
-                           d_status, d_ticket, recs->d_umi_len, d_fwd, d_unknown, d_lb_abort);                                          \
-    else                                                                                                                    \
-        hipLaunchKernelGGL((k_build_keys<LQW, false>), grid, dim3(256), 0, ctx->stream, kl, recs->d_bc_idx, recs->d_umi,    \
-                           recs->d_umi_qualn, recs->d_feature, recs->d_flags, recs->n, d_keys_out, d_vals_out, d_n, plan, d_hist, \
-                           d_status, d_ticket, recs->d_umi_len, d_fwd, d_unknown, d_lb_abort)
-        // four reads per lane with 16-byte loads where the layout allows it (see k_build_keys_v4); the 1 - 3 reads behind the
-        // last multiple of four go through the scalar kernel, appended by the same counter
-        const bool aligned16 = ((uintptr_t)recs->d_bc_idx | (uintptr_t)recs->d_umi | (uintptr_t)recs->d_feature |
-                                (uintptr_t)recs->d_umi_qualn) % 16 == 0 && (uintptr_t)recs->d_flags % 4 == 0;
-        const uint32_t lqw = (recs->umi_len & 3u) == 0u ? recs->umi_len / 4u : 0u;
-        if (!d_vals_out && !recs->d_umi_len && lqw >= 1 && lqw <= 4 && aligned16 && recs->n >= 4096) {
-            const uint64_t n4 = recs->n & ~3ull;
-#define CR_BUILD_KEYS_V4(LQW)                                                                                                  \
-    if (d_hist)                                                                                                                \
-        hipLaunchKernelGGL((k_build_keys_v4<LQW, true>), grid, dim3(256), 0, ctx->stream, kl, recs->d_bc_idx, recs->d_umi,      \
-                           recs->d_umi_qualn, recs->d_feature, recs->d_flags, n4, d_keys_out, d_n, plan, d_hist, d_fwd, d_unknown); \
-    else                                                                                                                       \
-        hipLaunchKernelGGL((k_build_keys_v4<LQW, false>), grid, dim3(256), 0, ctx->stream, kl, recs->d_bc_idx, recs->d_umi,     \
-                           recs->d_umi_qualn, recs->d_feature, recs->d_flags, n4, d_keys_out, d_n, plan, d_hist, d_fwd, d_unknown)
-            switch (lqw) {
-                case 1: CR_BUILD_KEYS_V4(1); break;
-                case 2: CR_BUILD_KEYS_V4(2); break;
-                case 3: CR_BUILD_KEYS_V4(3); break;
-                default: CR_BUILD_KEYS_V4(4); break;
-            }
-#undef CR_BUILD_KEYS_V4
-            if (n4 < recs->n) {
-                const uint64_t rest = recs->n - n4;
-                const uint8_t *tail_flags = recs->d_flags ? recs->d_flags + n4 : nullptr;
-                if (d_hist)
-                    hipLaunchKernelGGL((k_build_keys<0, true>), dim3(1), dim3(256), 0, ctx->stream, kl, recs->d_bc_idx + n4, recs->d_umi + n4,
-                                       recs->d_umi_qualn + n4 * recs->umi_len, recs->d_feature + n4, tail_flags, rest, d_keys_out,
-                                       (uint32_t *)nullptr, d_n, plan, d_hist, d_status, d_ticket, (const uint8_t *)nullptr, d_fwd, d_unknown, d_lb_abort);
-                else
-                    hipLaunchKernelGGL((k_build_keys<0, false>), dim3(1), dim3(256), 0, ctx->stream, kl, recs->d_bc_idx + n4, recs->d_umi + n4,
-                                       recs->d_umi_qualn + n4 * recs->umi_len, recs->d_feature + n4, tail_flags, rest, d_keys_out,
-                                       (uint32_t *)nullptr, d_n, plan, d_hist, d_status, d_ticket, (const uint8_t *)nullptr, d_fwd, d_unknown, d_lb_abort);
-            }
-        } else
-        switch (recs->d_umi_len ? 0u : recs->umi_len) {  // per-read lengths: the byte path
-            case 4: CR_BUILD_KEYS(1); break;
-            case 8: CR_BUILD_KEYS(2); break;
-            case 12: CR_BUILD_KEYS(3); break;
-            case 16: CR_BUILD_KEYS(4); break;
-            default: CR_BUILD_KEYS(0); break;
-        }
-        if (d_hist) {
-            if (!append) gh.d_keys = d_keys_out;
-            gh.plan = plan;
-            gh.valid = true;  // gh.n is filled in below, once the number of keys is known
-        }
-#undef CR_BUILD_KEYS
-        CR_HIP(ctx, hipGetLastError());
-    }
-    unsigned long long h = 0;
-    CR_TRY(crgpu_memcpy_d2h(ctx, &h, d_n, sizeof(h)));
-    if (d_vals_out) {
-        uint32_t stalled = 0;
-        CR_TRY(crgpu_memcpy_d2h(ctx, &stalled, d_lb_abort, sizeof(stalled)));
-        if (stalled) {
-            ctx->ghist.valid = false;
-            return cr_fail(ctx, CRGPU_EHIP, "crgpu_build_keys: the look-back of the order-preserving compaction stalled (watchdog); "
-                                            "nothing was hung, the keys of this call are incomplete");
-        }
-    }
-    if (d_fwd) {
-        uint32_t unknown = 0;
-        CR_TRY(crgpu_memcpy_d2h(ctx, &unknown, d_unknown, sizeof(unknown)));
-        if (unknown) {
-            ctx->ghist.valid = false;
-            return cr_fail(ctx, CRGPU_ESTATE, "crgpu_build_keys: %u records carry a barcode that has no read in the VALID / CORRECTED tables "
-                           "(CRGPU_OPT_DENSE_BARCODE_KEYS needs the tables of the whole well before the first key is built)", unknown);
-        }
-    }
-    *n_keys_out = h;
-    ctx->ghist.n = append ? n_before + h : h;
-    return CRGPU_OK;
-}
-
-extern "C" int crgpu_build_keys_dev(crgpu_ctx *ctx, const crgpu_records *recs, uint64_t *d_keys_out,
-                                    uint64_t *n_keys_out) {
-    if (!ctx) return CRGPU_EINVAL;
-    CR_ENTER(ctx);
-    return build_keys_impl(ctx, recs, d_keys_out, nullptr, n_keys_out);
-}
-
-extern "C" int crgpu_partition_keys_dev(crgpu_ctx *ctx, const uint64_t *d_keys, uint64_t n, uint32_t n_ranks,
-                                        const uint32_t *bounds, uint64_t *d_keys_out, uint64_t *counts_out) {
-    if (!ctx || !counts_out) return CRGPU_EINVAL;
-    CR_ENTER(ctx);
-    CR_REQUIRE(ctx, ctx->layout.set, CRGPU_ESTATE, "crgpu_partition_keys: call crgpu_set_key_layout first");
-    CR_REQUIRE(ctx, n == 0 || (d_keys && d_keys_out), CRGPU_EINVAL, "crgpu_partition_keys: NULL buffer");
-    cr_invalidate(ctx);
-    CR_TRY(cr_dense_ensure(ctx));
-    return cr_partition_by_owner(ctx, d_keys, d_keys_out, n, ctx->layout.sh_bc(), n_ranks, bounds, counts_out);
-}
-
-// Histogram-balanced owner ranges: bounds_out[0] = 0, bounds_out[n_ranks] = n_canon, and every range holds
-// about the same number of reads according to the VALID + CORRECTED tables of all libraries (call it after the
-// tables have been all-reduced so that every rank derives the same bounds).
-extern "C" int crgpu_balanced_bounds(crgpu_ctx *ctx, uint32_t n_ranks, uint32_t *bounds_out) {
-    if (!ctx || !bounds_out) return CRGPU_EINVAL;
-    CR_ENTER(ctx);
-    CR_REQUIRE(ctx, ctx->canon_set, CRGPU_ESTATE, "crgpu_balanced_bounds: no whitelist set");
-    CR_REQUIRE(ctx, n_ranks >= 1 && n_ranks <= 256, CRGPU_EINVAL, "crgpu_balanced_bounds: n_ranks must be 1..256");
-    const uint32_t W = ctx->n_canon;
-    std::vector<uint64_t> tot(W, 0);
-    std::vector<uint32_t> tmp(W);
-    for (int l = 0; l < CRGPU_MAX_LIB; l++) {
-        if (!ctx->wl[l].set) continue;
-        for (int which = 0; which < 2; which++) {
-            CR_TRY(crgpu_memcpy_d2h(ctx, tmp.data(), which ? ctx->wl[l].d_corrected : ctx->wl[l].d_valid, sizeof(uint32_t) * W));
-            for (uint32_t r = 0; r < W; r++) tot[r] += tmp[r];
-        }
-    }
-    uint64_t total = 0;
-    for (uint32_t r = 0; r < W; r++) total += tot[r];
-    bounds_out[0] = 0;
-    uint64_t acc = 0;
-    uint32_t r = 0;
-    for (uint32_t k = 1; k < n_ranks; k++) {
-        const uint64_t want = total * k / n_ranks;
-        while (r < W && acc + tot[r] <= want) acc += tot[r++];
-        bounds_out[k] = r;
-    }
-    bounds_out[n_ranks] = W;
-    return CRGPU_OK;
-}
 
 // ---- per-key state after UMI correction ---------------------------------------------------------------------------------
 // st[k] (16 bits, zeroed before the kernels run): bit 0 = key k is corrected away (corr[k] holds its target -- corr is
@@ -2074,379 +1463,6 @@ extern "C" int crgpu_count_records_sharded_dev(crgpu_ctx *ctx, const crgpu_recor
     CR_HIP(ctx, hipGetLastError());
     CR_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the temporaries above go back to the pool
     if (*out) (*out)->sharded = W > 1;
-    return CRGPU_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// K6 on the device: barcode index + CSC (barcode_index.rs:20-53, count_matrix.rs:382-448)
-// ------------------------------------------------------------------------------------------------
-
-// ---- CRGPU_OPT_DENSE_BARCODE_KEYS: the BarcodeIndex of the tables as they stand (cr_types/src/barcode_index.rs:20-53) ------
-int cr_dense_ensure(crgpu_ctx *ctx) {
-    DenseIndex &D = ctx->dense;
-    if (!D.on || D.valid) return CRGPU_OK;
-    CR_REQUIRE(ctx, ctx->canon_set && ctx->layout.set, CRGPU_ESTATE, "dense barcode keys: whitelist and key layout first");
-    const uint32_t W = ctx->n_canon;
-    SeenFlag seen;
-    seen.ct.n = 0;
-    for (int l = 0; l < CRGPU_MAX_LIB; l++)
-        if (ctx->wl[l].set) {
-            seen.ct.t[seen.ct.n++] = ctx->wl[l].d_valid;
-            seen.ct.t[seen.ct.n++] = ctx->wl[l].d_corrected;
-        }
-    if (!D.d_fwd) CR_HIP(ctx, hipMalloc((void **)&D.d_fwd, (((size_t)W + 63) / 64) * sizeof(uint4)));
-    if (!D.d_back) CR_HIP(ctx, hipMalloc((void **)&D.d_back, (size_t)W * sizeof(uint32_t)));
-    uint32_t *d_total = ctx->d_scalars + CR_SCALAR_TOTAL;
-    uint32_t V = 0;
-    {
-        CrTimer t(ctx, CRGPU_T_KEYS);
-        CR_TRY(compact(ctx, seen, EmitCol{D.d_back}, W, ctx->d_sort_hist, d_total));
-    }
-    CR_TRY(read_u32(ctx, d_total, &V));
-    KeyLayout L = ctx->layout;
-    L.bits_bc = V > 1 ? cr_ceil_log2(V) : 1u;
-    CR_REQUIRE(ctx, L.total_bits() <= 64, CRGPU_ERANGE,
-               "molecule key needs %u bits even with %u barcodes in the index (barcode %u + feature %u + library %u + umi %u + 1) > 64",
-               L.total_bits(), V, L.bits_bc, L.bits_feat, L.bits_lib, L.bits_umi + L.bits_ulen);
-    D.h_back.resize(V);
-    if (V) CR_TRY(crgpu_memcpy_d2h(ctx, D.h_back.data(), D.d_back, (uint64_t)V * sizeof(uint32_t)));
-    {   // rank/select table on the host (V set bits, W / 64 words): 16 bytes per 64 ranks
-        const size_t n_words = ((size_t)W + 63) / 64;
-        std::vector<uint4> t(n_words, make_uint4(0u, 0u, 0u, 0u));
-        for (uint32_t c = 0; c < V; c++) {
-            const uint32_t r = D.h_back[c];
-            if (r & 32u) t[r >> 6].y |= 1u << (r & 31u); else t[r >> 6].x |= 1u << (r & 31u);
-        }
-        uint32_t run = 0;
-        for (size_t w = 0; w < n_words; w++) {
-            t[w].z = run;
-            run += (uint32_t)__builtin_popcount(t[w].x) + (uint32_t)__builtin_popcount(t[w].y);
-        }
-        CR_TRY(crgpu_memcpy_h2d(ctx, D.d_fwd, t.data(), n_words * sizeof(uint4)));
-    }
-    D.V = V;
-    D.valid = true;
-    ctx->layout = L;
-    ctx->ghist.valid = false;
-    return CRGPU_OK;
-}
-
-__global__ __launch_bounds__(256) void k_csc(const uint32_t *__restrict__ col_rank, uint64_t n_cols,
-                                             const uint32_t *__restrict__ t_bc, const uint32_t *__restrict__ t_feat,
-                                             const uint32_t *__restrict__ t_cnt, uint64_t nt,
-                                             long long *__restrict__ indptr, int32_t *__restrict__ indices,
-                                             int32_t *__restrict__ data) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    const uint64_t tid = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    // indptr[c] = first triplet whose barcode rank >= col_rank[c]; columns without counts get empty ranges
-    for (uint64_t c = tid; c <= n_cols; c += stride) {
-        if (c == n_cols) {
-            indptr[c] = (long long)nt;
-            continue;
-        }
-        const uint32_t r = col_rank[c];
-        uint64_t lo = 0, hi = nt;
-        while (lo < hi) {
-            const uint64_t mid = (lo + hi) >> 1;
-            if (t_bc[mid] < r) lo = mid + 1; else hi = mid;
-        }
-        indptr[c] = (long long)lo;
-    }
-    for (uint64_t i = tid; i < nt; i += stride) {
-        indices[i] = (int32_t)t_feat[i];
-        data[i] = (int32_t)t_cnt[i];
-    }
-}
-
-extern "C" int crgpu_assemble_matrix_dev(crgpu_ctx *ctx, const uint32_t *d_bc, const uint32_t *d_feature,
-                                         const uint32_t *d_count, uint64_t n_triplets, crgpu_matrix_dev **out) {
-    if (!ctx || !out) return CRGPU_EINVAL;
-    CR_ENTER(ctx);
-    *out = nullptr;
-    CR_REQUIRE(ctx, ctx->canon_set, CRGPU_ESTATE, "crgpu_assemble_matrix_dev: no whitelist set");
-    CR_REQUIRE(ctx, n_triplets == 0 || (d_bc && d_feature && d_count), CRGPU_EINVAL, "NULL triplets");
-    CR_REQUIRE(ctx, n_triplets < 0xFFFFFFFFull, CRGPU_ERANGE, "too many triplets");
-    SeenFlag seen;
-    seen.ct.n = 0;
-    for (int l = 0; l < CRGPU_MAX_LIB; l++)
-        if (ctx->wl[l].set) {
-            seen.ct.t[seen.ct.n++] = ctx->wl[l].d_valid;
-            seen.ct.t[seen.ct.n++] = ctx->wl[l].d_corrected;
-        }
-    MatrixDevImpl *m = new (std::nothrow) MatrixDevImpl();
-    if (!m) return cr_fail(ctx, CRGPU_ENOMEM, "out of host memory");
-    struct Guard {
-        crgpu_ctx *c;
-        MatrixDevImpl *m;
-        bool armed = true;
-        ~Guard() {
-            if (armed) crgpu_matrix_dev_free(c, &m->view);
-        }
-    } guard{ctx, m};
-    const uint32_t W = ctx->n_canon;
-    CR_TRY(cr_pool_alloc(ctx, (void **)&m->d_rank, (size_t)W * sizeof(uint32_t)));
-    uint32_t *d_total = ctx->d_scalars + CR_SCALAR_TOTAL;
-    uint32_t V = 0;
-    {
-        CrTimer t(ctx, CRGPU_T_MATRIX);
-        CR_TRY(compact(ctx, seen, EmitCol{m->d_rank}, W, ctx->d_sort_hist, d_total));
-    }
-    CR_TRY(read_u32(ctx, d_total, &V));
-    CR_TRY(cr_pool_alloc(ctx, (void **)&m->d_indptr, ((size_t)V + 1) * sizeof(long long)));
-    CR_TRY(cr_pool_alloc(ctx, (void **)&m->d_indices, n_triplets * sizeof(int32_t)));
-    CR_TRY(cr_pool_alloc(ctx, (void **)&m->d_data, n_triplets * sizeof(int32_t)));
-    {
-        CrTimer t(ctx, CRGPU_T_MATRIX);
-        const uint64_t work = n_triplets > V ? n_triplets : (uint64_t)V + 1;
-        hipLaunchKernelGGL(k_csc, dim3(cr_grid(work, 256)), dim3(256), 0, ctx->stream, m->d_rank, (uint64_t)V, d_bc, d_feature,
-                           d_count, n_triplets, m->d_indptr, m->d_indices, m->d_data);
-        CR_HIP(ctx, hipGetLastError());
-    }
-    m->view.n_barcodes = V;
-    m->view.nnz = n_triplets;
-    m->view.d_barcode_rank = m->d_rank;
-    m->view.d_indptr = (const int64_t *)m->d_indptr;
-    m->view.d_indices = m->d_indices;
-    m->view.d_data = m->d_data;
-    guard.armed = false;
-    *out = &m->view;
-    return CRGPU_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// aggr-style post-processing on the device
-// ------------------------------------------------------------------------------------------------
-// merge of two index-sorted columns; WRITE = false counts the merged entries
-template <bool WRITE>
-__global__ __launch_bounds__(256) void k_sum_columns(uint64_t n_cols, const long long *__restrict__ pa, const int32_t *__restrict__ ia,
-                                                     const int32_t *__restrict__ da, const long long *__restrict__ pb,
-                                                     const int32_t *__restrict__ ib, const int32_t *__restrict__ db,
-                                                     uint32_t *__restrict__ cnt, const uint32_t *__restrict__ off,
-                                                     int32_t *__restrict__ io, int32_t *__restrict__ dout) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t c = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; c < n_cols; c += stride) {
-        long long i = pa[c], j = pb[c];
-        const long long ie = pa[c + 1], je = pb[c + 1];
-        uint32_t o = WRITE ? off[c] : 0u;
-        while (i < ie || j < je) {
-            const int32_t ra = i < ie ? ia[i] : 0x7FFFFFFF, rb = j < je ? ib[j] : 0x7FFFFFFF;
-            if (WRITE) {
-                io[o] = ra < rb ? ra : rb;
-                dout[o] = (ra <= rb ? da[i] : 0) + (rb <= ra ? db[j] : 0);
-            }
-            o++;
-            i += ra <= rb;
-            j += rb <= ra;
-        }
-        if (!WRITE) cnt[c] = o;
-    }
-}
-__global__ __launch_bounds__(256) void k_ranks_differ(const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, uint64_t n,
-                                                      uint32_t *__restrict__ flag) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-        if (a[i] != b[i]) *flag = 1u;
-}
-__global__ __launch_bounds__(256) void k_offsets_to_indptr(const uint32_t *__restrict__ off, uint64_t n, uint32_t total,
-                                                           long long *__restrict__ indptr) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i <= n; i += stride)
-        indptr[i] = i < n ? (long long)off[i] : (long long)total;
-}
-void cr_offsets_to_indptr(crgpu_ctx *ctx, const uint32_t *d_off, uint64_t n, uint32_t total, long long *d_indptr) {
-    hipLaunchKernelGGL(k_offsets_to_indptr, dim3(cr_grid(n + 1, 256)), dim3(256), 0, ctx->stream, d_off, n, total, d_indptr);
-}
-// a column position outside [0, V) (a device list is not checked on the host) is reported through *bad and reads nothing
-__global__ __launch_bounds__(256) void k_selected_lengths(const long long *__restrict__ indptr, const uint64_t *__restrict__ cols,
-                                                          uint64_t n_sel, uint64_t V, const uint32_t *__restrict__ rank_in,
-                                                          uint32_t *__restrict__ len, uint32_t *__restrict__ rank_out,
-                                                          uint32_t *__restrict__ bad) {
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < n_sel; k += stride) {
-        const uint64_t c = cols[k];
-        if (c >= V) {
-            *bad = 1u;
-            len[k] = 0u;
-            rank_out[k] = 0u;
-            continue;
-        }
-        len[k] = (uint32_t)(indptr[c + 1] - indptr[c]);
-        rank_out[k] = rank_in[c];
-    }
-}
-// one wave per selected column: a contiguous copy of its entries
-__global__ __launch_bounds__(256) void k_copy_columns(const long long *__restrict__ indptr, const uint64_t *__restrict__ cols,
-                                                      uint64_t n_sel, const uint32_t *__restrict__ off,
-                                                      const int32_t *__restrict__ ia, const int32_t *__restrict__ da,
-                                                      int32_t *__restrict__ io, int32_t *__restrict__ dout) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t wave0 = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = ((uint64_t)gridDim.x * blockDim.x) >> 6;
-    for (uint64_t k = wave0; k < n_sel; k += n_waves) {
-        const uint64_t c = cols[k];
-        const long long s = indptr[c], e = indptr[c + 1];
-        const uint32_t o = off[k];
-        for (long long i = s + lane; i < e; i += 64) {
-            io[o + (i - s)] = ia[i];
-            dout[o + (i - s)] = da[i];
-        }
-    }
-}
-
-int cr_new_matrix_dev(crgpu_ctx *ctx, uint64_t V, uint64_t nnz, MatrixDevImpl **out) {
-    MatrixDevImpl *m = new (std::nothrow) MatrixDevImpl();
-    if (!m) return cr_fail(ctx, CRGPU_ENOMEM, "out of host memory");
-    int rc = cr_pool_alloc(ctx, (void **)&m->d_rank, (V ? V : 1) * sizeof(uint32_t));
-    if (rc == CRGPU_OK) rc = cr_pool_alloc(ctx, (void **)&m->d_indptr, (V + 1) * sizeof(long long));
-    if (rc == CRGPU_OK) rc = cr_pool_alloc(ctx, (void **)&m->d_indices, (nnz ? nnz : 1) * sizeof(int32_t));
-    if (rc == CRGPU_OK) rc = cr_pool_alloc(ctx, (void **)&m->d_data, (nnz ? nnz : 1) * sizeof(int32_t));
-    if (rc != CRGPU_OK) {
-        crgpu_matrix_dev_free(ctx, &m->view);
-        return rc;
-    }
-    m->view.n_barcodes = V;
-    m->view.nnz = nnz;
-    m->view.d_barcode_rank = m->d_rank;
-    m->view.d_indptr = (const int64_t *)m->d_indptr;
-    m->view.d_indices = m->d_indices;
-    m->view.d_data = m->d_data;
-    *out = m;
-    return CRGPU_OK;
-}
-
-// CountMatrix.merge / merge_matrices (lib/python/cellranger/matrix.py:479-482,1319-1329): element-wise sum of two matrices
-// of the same shape -- here two device CSCs over the same columns (same barcode ranks in the same order).
-extern "C" int crgpu_sum_matrices_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *a, const crgpu_matrix_dev *b, crgpu_matrix_dev **out) {
-    if (!ctx || !out) return CRGPU_EINVAL;
-    CR_ENTER(ctx);
-    *out = nullptr;
-    CR_REQUIRE(ctx, a && b, CRGPU_EINVAL, "crgpu_sum_matrices_dev: NULL matrix");
-    CR_REQUIRE(ctx, a->n_barcodes == b->n_barcodes, CRGPU_EINVAL, "crgpu_sum_matrices_dev: %llu vs %llu columns",
-               (unsigned long long)a->n_barcodes, (unsigned long long)b->n_barcodes);
-    CR_REQUIRE(ctx, a->nnz + b->nnz < 0xFFFFFFFFull, CRGPU_ERANGE, "crgpu_sum_matrices_dev: too many entries");
-    const uint64_t V = a->n_barcodes;
-    uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, *d_total = ctx->d_scalars + CR_SCALAR_TOTAL;
-    DevBuf cnt_b;
-    CR_TRY(dmalloc(ctx, cnt_b, (V + 1) * sizeof(uint32_t)));
-    uint32_t *cnt = cnt_b.as<uint32_t>();
-    const long long *pa = (const long long *)a->d_indptr, *pb = (const long long *)b->d_indptr;
-    uint32_t differ = 0, total = 0;
-    {
-        CrTimer t(ctx, CRGPU_T_MATRIX, a->nnz + b->nnz);
-        CR_HIP(ctx, hipMemsetAsync(d_flag, 0, sizeof(uint32_t), ctx->stream));
-        if (V) {
-            hipLaunchKernelGGL(k_ranks_differ, dim3(cr_grid(V, 256)), dim3(256), 0, ctx->stream, a->d_barcode_rank, b->d_barcode_rank, V, d_flag);
-            hipLaunchKernelGGL(k_sum_columns<false>, dim3(cr_grid(V, 256)), dim3(256), 0, ctx->stream, V, pa, a->d_indices, a->d_data, pb,
-                               b->d_indices, b->d_data, cnt, (const uint32_t *)nullptr, (int32_t *)nullptr, (int32_t *)nullptr);
-        }
-        CR_HIP(ctx, hipGetLastError());
-        CR_TRY(cr_scan_small(ctx, cnt, V, d_total));
-    }
-    CR_TRY(read_u32(ctx, d_flag, &differ));
-    CR_REQUIRE(ctx, !differ, CRGPU_EINVAL, "crgpu_sum_matrices_dev: the matrices hold different barcodes");
-    CR_TRY(read_u32(ctx, d_total, &total));
-    MatrixDevImpl *m = nullptr;
-    CR_TRY(cr_new_matrix_dev(ctx, V, total, &m));
-    {
-        CrTimer t(ctx, CRGPU_T_MATRIX);
-        if (V) {
-            CR_HIP(ctx, hipMemcpyAsync(m->d_rank, a->d_barcode_rank, V * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
-            hipLaunchKernelGGL(k_sum_columns<true>, dim3(cr_grid(V, 256)), dim3(256), 0, ctx->stream, V, pa, a->d_indices, a->d_data, pb,
-                               b->d_indices, b->d_data, (uint32_t *)nullptr, cnt, m->d_indices, m->d_data);
-        }
-        cr_offsets_to_indptr(ctx, cnt, V, total, m->d_indptr);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
-            crgpu_matrix_dev_free(ctx, &m->view);
-            return cr_fail(ctx, CRGPU_EHIP, "crgpu_sum_matrices_dev: kernel failed");
-        }
-    }
-    *out = &m->view;
-    return CRGPU_OK;
-}
-
-// CountMatrix.select_barcodes (matrix.py:860-875): the columns at the positions d_cols (device) in the given order.
-static int select_columns_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *a, const uint64_t *d_cols, uint64_t n_cols, const char *who,
-                              crgpu_matrix_dev **out) {
-    DevBuf len_b, rank_b;
-    CR_TRY(dmalloc(ctx, len_b, (n_cols + 1) * sizeof(uint32_t)));
-    CR_TRY(dmalloc(ctx, rank_b, (n_cols ? n_cols : 1) * sizeof(uint32_t)));
-    uint32_t *d_total = ctx->d_scalars + CR_SCALAR_TOTAL, *d_bad = ctx->d_scalars + CR_SCALAR_FLAG, total = 0, bad = 0;
-    const long long *pa = (const long long *)a->d_indptr;
-    {
-        CrTimer t(ctx, CRGPU_T_MATRIX, n_cols);
-        CR_HIP(ctx, hipMemsetAsync(d_bad, 0, sizeof(uint32_t), ctx->stream));
-        if (n_cols)
-            hipLaunchKernelGGL(k_selected_lengths, dim3(cr_grid(n_cols, 256)), dim3(256), 0, ctx->stream, pa, d_cols, n_cols, a->n_barcodes,
-                               a->d_barcode_rank, len_b.as<uint32_t>(), rank_b.as<uint32_t>(), d_bad);
-        CR_HIP(ctx, hipGetLastError());
-        CR_TRY(cr_scan_small(ctx, len_b.as<uint32_t>(), n_cols, d_total));
-    }
-    CR_TRY(read_u32(ctx, d_bad, &bad));
-    CR_REQUIRE(ctx, !bad, CRGPU_EINVAL, "%s: a column is out of range", who);
-    CR_TRY(read_u32(ctx, d_total, &total));
-    MatrixDevImpl *m = nullptr;
-    CR_TRY(cr_new_matrix_dev(ctx, n_cols, total, &m));
-    {
-        CrTimer t(ctx, CRGPU_T_MATRIX);
-        if (n_cols) {
-            CR_HIP(ctx, hipMemcpyAsync(m->d_rank, rank_b.p, n_cols * sizeof(uint32_t), hipMemcpyDeviceToDevice, ctx->stream));
-            hipLaunchKernelGGL(k_copy_columns, dim3(cr_grid(n_cols * 64, 256)), dim3(256), 0, ctx->stream, pa, d_cols, n_cols,
-                               len_b.as<uint32_t>(), a->d_indices, a->d_data, m->d_indices, m->d_data);
-        }
-        cr_offsets_to_indptr(ctx, len_b.as<uint32_t>(), n_cols, total, m->d_indptr);
-        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) {
-            crgpu_matrix_dev_free(ctx, &m->view);
-            return cr_fail(ctx, CRGPU_EHIP, "%s: kernel failed", who);
-        }
-    }
-    *out = &m->view;
-    return CRGPU_OK;
-}
-
-// ... with `cols` a host array of column positions
-extern "C" int crgpu_select_barcodes_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *a, const uint64_t *cols, uint64_t n_cols,
-                                         crgpu_matrix_dev **out) {
-    if (!ctx || !out) return CRGPU_EINVAL;
-    CR_ENTER(ctx);
-    *out = nullptr;
-    CR_REQUIRE(ctx, a && (cols || n_cols == 0), CRGPU_EINVAL, "crgpu_select_barcodes_dev: NULL argument");
-    for (uint64_t k = 0; k < n_cols; k++)
-        CR_REQUIRE(ctx, cols[k] < a->n_barcodes, CRGPU_EINVAL, "crgpu_select_barcodes_dev: column %llu out of range",
-                   (unsigned long long)cols[k]);
-    DevBuf cols_b;
-    CR_TRY(dmalloc(ctx, cols_b, (n_cols ? n_cols : 1) * sizeof(uint64_t)));
-    if (n_cols) CR_HIP(ctx, hipMemcpyAsync(cols_b.p, cols, n_cols * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    return select_columns_dev(ctx, a, cols_b.as<uint64_t>(), n_cols, "crgpu_select_barcodes_dev", out);
-}
-
-// ... with a device list (the called cells of crgpu_call_cells_ordmag_dev: the filtered matrix)
-extern "C" int crgpu_select_barcodes_cols_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *a, const uint64_t *d_cols, uint64_t n_cols,
-                                              crgpu_matrix_dev **out) {
-    if (!ctx || !out) return CRGPU_EINVAL;
-    CR_ENTER(ctx);
-    *out = nullptr;
-    CR_REQUIRE(ctx, a && (d_cols || n_cols == 0), CRGPU_EINVAL, "crgpu_select_barcodes_cols_dev: NULL argument");
-    return select_columns_dev(ctx, a, d_cols, n_cols, "crgpu_select_barcodes_cols_dev", out);
-}
-
-extern "C" void crgpu_matrix_dev_free(crgpu_ctx *ctx, crgpu_matrix_dev *mv) {
-    if (!mv || !ctx) return;
-    CR_ENTER(ctx);
-    MatrixDevImpl *m = reinterpret_cast<MatrixDevImpl *>(mv);  // view is the first member
-    cr_pool_free(ctx, m->d_rank);
-    cr_pool_free(ctx, m->d_indptr);
-    cr_pool_free(ctx, m->d_indices);
-    cr_pool_free(ctx, m->d_data);
-    delete m;
-}
-
-extern "C" int crgpu_matrix_dev_download(crgpu_ctx *ctx, const crgpu_matrix_dev *mv, uint32_t *rank_out, int64_t *indptr_out,
-                                         int32_t *indices_out, int32_t *data_out) {
-    if (!ctx || !mv) return CRGPU_EINVAL;
-    CR_ENTER(ctx);
-    if (rank_out) CR_TRY(crgpu_memcpy_d2h(ctx, rank_out, mv->d_barcode_rank, mv->n_barcodes * sizeof(uint32_t)));
-    if (indptr_out) CR_TRY(crgpu_memcpy_d2h(ctx, indptr_out, mv->d_indptr, (mv->n_barcodes + 1) * sizeof(int64_t)));
-    if (indices_out) CR_TRY(crgpu_memcpy_d2h(ctx, indices_out, mv->d_indices, mv->nnz * sizeof(int32_t)));
-    if (data_out) CR_TRY(crgpu_memcpy_d2h(ctx, data_out, mv->d_data, mv->nnz * sizeof(int32_t)));
     return CRGPU_OK;
 }
 

@@ -1,4 +1,5 @@
-// matrix.hip -- barcode index, CSC assembly and Matrix Market text (host side of the boundary).
+// matrix.hip -- barcode index, CSC assembly and Matrix Market text on the host (the host side of the boundary; the matrix that
+// stays on the device is matrix_dev.hip).
 //
 // Replaces BarcodeIndex::new / from_iter (cr_types/src/barcode_index.rs:20-53),
 // write_matrix_h5_helper's CSC construction (cr_h5/src/count_matrix.rs:382-448) and

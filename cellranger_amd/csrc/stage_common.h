@@ -1,7 +1,8 @@
-// stage_common.h -- what the count stage (dedup.hip) and the analysis stages behind it (molecule_stages.hip on a crgpu_counts,
-// matrix_stages.hip on a crgpu_matrix_dev) share: the two opaque result types, the stream compaction, the barcode segments of the
-// molecule table, the search in an ascending array, the checks of a caller's column or rank list, numpy's percentile, and the few
-// host functions one of these units defines for the others.  A kernel defined here is a template: the header is part of three units.
+// stage_common.h -- what the count stage (keys.hip, dedup.hip), the device matrix (matrix_dev.hip) and the analysis stages behind
+// them (molecule_stages.hip on a crgpu_counts, matrix_stages.hip on a crgpu_matrix_dev) share: the two opaque result types, the
+// stream compaction, the barcode segments of the molecule table, the search in an ascending array, the checks of a caller's column
+// or rank list, numpy's percentile, and the few host functions one of these units defines for the others.  A kernel defined here is
+// a template: the header is part of several units.
 #pragma once
 
 #include <cmath>
@@ -45,13 +46,13 @@ struct MatrixDevImpl {
     int32_t *d_indices = nullptr, *d_data = nullptr;
 };
 
-// Defined in dedup.hip for the stage units as well: a kernel that is not a template has one definition in one unit, and
+// Defined in one unit for the stage units as well: a kernel that is not a template has one definition in one unit, and
 // another unit reaches it through a host function.
-// A matrix of V columns and nnz entries with nothing in it yet
+// matrix_dev.hip: a matrix of V columns and nnz entries with nothing in it yet
 int cr_new_matrix_dev(crgpu_ctx *ctx, uint64_t V, uint64_t nnz, MatrixDevImpl **out);
-// launch only: indptr[i] = off[i] for i < n, indptr[n] = total
+// matrix_dev.hip, launch only: indptr[i] = off[i] for i < n, indptr[n] = total
 void cr_offsets_to_indptr(crgpu_ctx *ctx, const uint32_t *d_off, uint64_t n, uint32_t total, long long *d_indptr);
-// the molecule table on the host in the order ALIGN_AND_COUNT emits it: order[o] = device position of the o-th UmiCount
+// dedup.hip: the molecule table on the host in the order ALIGN_AND_COUNT emits it: order[o] = device position of the o-th UmiCount
 int cr_molecule_order(crgpu_ctx *ctx, const crgpu_counts *c, std::vector<uint64_t> &keys, std::vector<uint32_t> &reads,
                       std::vector<uint32_t> &order);
 
