@@ -421,9 +421,25 @@ class TsneResult(C.Structure):
         (n, C.c_uint32) for n in ("row_tile", "cand_tile", "slab_rows", "wave_row_len", "n_chunks", "n_groups", "max_steps", "reserved")]
 
 
+class UmapArgs(C.Structure):
+    """crgpu_umap_args"""
+    _fields_ = [(n, C.c_double) for n in ("a", "b", "gamma", "initial_alpha")] + [("seed", C.c_uint64)] + [
+        (n, C.c_uint32) for n in ("first_epoch", "n_run", "n_epochs", "negative_sample_rate", "wave_row_len", "rows_per_wg", "reserved0", "reserved1")]
+
+
+class UmapResult(C.Structure):
+    """crgpu_umap_result"""
+    _fields_ = [(n, C.c_void_p) for n in ("rho_out", "sigma_out", "steps_out", "indptr_out", "indices_out", "values_out", "delta_out")] + [
+        (n, C.c_double) for n in ("wmax", "fit_ms", "search_ms", "csr_ms", "loop_ms")] + [
+        (n, C.c_uint64) for n in ("nnz", "n_active", "n_negative")] + [
+        (n, C.c_uint32) for n in ("wave_row_len", "rows_per_wg", "max_steps", "reserved")]
+
+
 KM_MAX_K, KM_MAX_D, KM_MAX_LIST = 64, 128, 64
 TSNE_CAND_CHUNK, TSNE_MAX_FEATURES = 4096, 128
 TSNE_PERPLEXITY, TSNE_THETA, TSNE_MAX_ITER, TSNE_STOP_LYING_ITER, TSNE_MOM_SWITCH_ITER, TSNE_ETA = 30, 0.5, 1000, 250, 250, 200.0
+UMAP_SLOTS, UMAP_MAX_RATE, UMAP_MAX_FEATURES = 16, 8, 128
+UMAP_N_NEIGHBORS, UMAP_MIN_DIST, UMAP_SPREAD, UMAP_NEGATIVE_SAMPLE_RATE, UMAP_METRICS = 30, 0.3, 1.0, 5, ("correlation", "pearson", "cosine", "euclidean")
 PCA_MAX_COMPONENTS, PCA_DEFAULT_THRESHOLD, PCA_OK, PCA_NULL_AXIS, PCA_RANK_TOO_SMALL = 128, 2, 0, 1, 2
 KNN_MAX_K, KNN_MAX_CAPACITY = 1024, 4096
 BC_PAIR_CHUNK, BC_LDS_BYTES, BC_MAX_PAIR_TILE = 2048, 73728, 64
@@ -614,6 +630,9 @@ SYMBOLS = {
     "crgpu_tsne_affinities_dev": (_i, [_vp, _vp, _vp, _u64, _u32, _dbl, C.POINTER(TsneArgs), C.POINTER(TsneResult)]),
     "crgpu_tsne_gradient_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _u64, _u32, _dbl, C.POINTER(TsneArgs), C.POINTER(TsneResult)]),
     "crgpu_tsne_dev": (_i, [_vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, C.POINTER(TsneArgs), C.POINTER(TsneResult)]),
+    "crgpu_umap_ab": (_i, [_dbl, _dbl, C.POINTER(_dbl), C.POINTER(_dbl)]),
+    "crgpu_umap_graph_dev": (_i, [_vp, _vp, _vp, _u64, _u32, _u32, C.POINTER(UmapResult)]),
+    "crgpu_umap_epochs_dev": (_i, [_vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, C.POINTER(UmapArgs), C.POINTER(UmapResult)]),
     "crgpu_aggregate_min_antibodies": (_i, [_u32, C.POINTER(_u32)]),
     "crgpu_antigen_outlier_threshold": (_i, [_vp, _u32, C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_dbl)]),
     "crgpu_aggregates_by_counts_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, _u32, _vp, _vp, _u32, C.POINTER(_u32),

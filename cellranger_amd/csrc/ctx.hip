@@ -469,6 +469,38 @@ const std::vector<AbiStruct> &abi_table() {
               ABI_F(crgpu_tsne_result, n_groups),
               ABI_F(crgpu_tsne_result, max_steps),
               ABI_F(crgpu_tsne_result, reserved)),
+        ABI_S(crgpu_umap_args, ABI_F(crgpu_umap_args, a),
+              ABI_F(crgpu_umap_args, b),
+              ABI_F(crgpu_umap_args, gamma),
+              ABI_F(crgpu_umap_args, initial_alpha),
+              ABI_F(crgpu_umap_args, seed),
+              ABI_F(crgpu_umap_args, first_epoch),
+              ABI_F(crgpu_umap_args, n_run),
+              ABI_F(crgpu_umap_args, n_epochs),
+              ABI_F(crgpu_umap_args, negative_sample_rate),
+              ABI_F(crgpu_umap_args, wave_row_len),
+              ABI_F(crgpu_umap_args, rows_per_wg),
+              ABI_F(crgpu_umap_args, reserved0),
+              ABI_F(crgpu_umap_args, reserved1)),
+        ABI_S(crgpu_umap_result, ABI_F(crgpu_umap_result, rho_out),
+              ABI_F(crgpu_umap_result, sigma_out),
+              ABI_F(crgpu_umap_result, steps_out),
+              ABI_F(crgpu_umap_result, indptr_out),
+              ABI_F(crgpu_umap_result, indices_out),
+              ABI_F(crgpu_umap_result, values_out),
+              ABI_F(crgpu_umap_result, delta_out),
+              ABI_F(crgpu_umap_result, wmax),
+              ABI_F(crgpu_umap_result, fit_ms),
+              ABI_F(crgpu_umap_result, search_ms),
+              ABI_F(crgpu_umap_result, csr_ms),
+              ABI_F(crgpu_umap_result, loop_ms),
+              ABI_F(crgpu_umap_result, nnz),
+              ABI_F(crgpu_umap_result, n_active),
+              ABI_F(crgpu_umap_result, n_negative),
+              ABI_F(crgpu_umap_result, wave_row_len),
+              ABI_F(crgpu_umap_result, rows_per_wg),
+              ABI_F(crgpu_umap_result, max_steps),
+              ABI_F(crgpu_umap_result, reserved)),
         ABI_S(crgpu_pca_args, ABI_F(crgpu_pca_args, pca_bc_indices),
               ABI_F(crgpu_pca_args, n_pca_bcs),
               ABI_F(crgpu_pca_args, start),

@@ -1362,6 +1362,107 @@ def run_tsne(ctx, matrix, tsne_dims=2, input_pcs=None, perplexity=_lib.TSNE_PERP
     return out
 
 
+def get_umap_name(feature_type, n_components):
+    """get_tsne_name with EmbeddingType::Umap (cr_ana/src/types.rs): "gene_expression_2-d\""""
+    return get_tsne_name(feature_type, n_components)
+
+
+def get_umap_key(feature_type, n_components):
+    """get_tsne_key with EmbeddingType::Umap: the bare number for Gene Expression, else "antibody_capture_2\""""
+    return get_tsne_key(feature_type, n_components)
+
+
+def umap_ab(min_dist=_lib.UMAP_MIN_DIST, spread=_lib.UMAP_SPREAD):
+    """umap-learn's find_ab_params (crgpu_umap_ab, host only): the least-squares fit of 1 / (1 + a x^(2b)) to x < min_dist ? 1 :
+    exp(-(x - min_dist) / spread) at linspace(0, 3 spread, 300) -> (a, b)"""
+    a, b = C.c_double(), C.c_double()
+    rc = _lib.load().crgpu_umap_ab(float(min_dist), float(spread), C.byref(a), C.byref(b))
+    if rc != 0:
+        raise _lib.CrgpuError(rc, "crgpu_umap_ab")
+    return a.value, b.value
+
+
+def umap_metric_input(x, metric="correlation"):
+    """The rows the neighbour search of RUN_UMAP runs on -> (rows f64[n, d], angular).  correlation / pearson: every row minus its own
+    mean (the left-to-right sum over the columns, divided by their number), then divided by its Euclidean norm (the square root of the
+    left-to-right sum of squares); cosine: the division alone; a row of norm 0 stays the zero vector; between unit rows ||u - v||^2 =
+    2 (1 - corr), so the dissimilarity of a pair is 0.5 * (dist * dist) (angular True).  euclidean: the rows as they are.  Any other
+    name: ValueError"""
+    if metric not in _lib.UMAP_METRICS:
+        raise ValueError("umap_metric_input: the metric %r, one of %s" % (metric, ", ".join(_lib.UMAP_METRICS)))
+    x = np.array(x, dtype=np.float64)
+    if metric == "euclidean":
+        return x, False
+    if metric != "cosine":
+        x -= (np.cumsum(x, axis=1)[:, -1] / x.shape[1])[:, None]
+    norm = np.sqrt(np.cumsum(x * x, axis=1)[:, -1])
+    return x / np.where(norm > 0, norm, 1.0)[:, None], True
+
+
+def umap_rescale(y):
+    """umap-learn's rescale of the start: every column to [0, 10] as 10 * (y - min) / (max - min); a constant column becomes 0"""
+    y = np.array(y, dtype=np.float64)
+    lo, hi = y.min(axis=0), y.max(axis=0)
+    span = hi - lo
+    return np.where(span > 0, 10.0 * (y - lo) / np.where(span > 0, span, 1.0), 0.0)
+
+
+def run_umap(ctx, matrix, umap_dims=2, input_pcs=None, n_neighbors=_lib.UMAP_N_NEIGHBORS, min_dist=_lib.UMAP_MIN_DIST, metric="correlation", seed=0,
+             n_epochs=None, init=None, feature_type="Gene Expression", queries_per_call=_lib.NN_QUERIES_PER_CHUNK):
+    """RUN_UMAP (cr_ana/src/stages/umap.rs) of a cells x columns f64 matrix, at most 128 columns after input_pcs: n_neighbors =
+    min(n_neighbors, N - 1), spread 1, umap_metric_input, Context.knn at k = n_neighbors - 1 in calls of queries_per_call rows (the
+    point itself is the first of n_neighbors), Context.umap_graph, umap_ab, Context.umap_epochs over all n_epochs (default 500 up to
+    10 000 cells, else 200).  The start is init [N x dims] or the first dims columns of the matrix, every column rescaled to [0, 10]
+    (umap_rescale); spectral initialisation is not covered.  N < 3: all zeros without a launch
+    -> dict(embedding f64[N, dims], a, b, n_epochs, num_neighbors, nnz, max_steps, name, key, knn_ms, graph_ms, loop_ms, n_active,
+    n_negative)"""
+    x = np.asarray(matrix, dtype=np.float64)
+    if x.ndim != 2:
+        raise ValueError("run_umap: the matrix is cells x columns")
+    if input_pcs is not None:
+        x = x[:, :int(input_pcs)]
+    dims = int(umap_dims)
+    if dims not in (2, 3):
+        raise ValueError("run_umap: %d dimensions, 2 or 3" % dims)
+    if metric not in _lib.UMAP_METRICS:
+        raise ValueError("run_umap: the metric %r, one of %s" % (metric, ", ".join(_lib.UMAP_METRICS)))
+    N = x.shape[0]
+    n_neighbors = min(int(n_neighbors), N - 1)
+    n_epochs = (500 if N <= 10000 else 200) if n_epochs is None else int(n_epochs)
+    a, b = umap_ab(min_dist, _lib.UMAP_SPREAD)
+    out = dict(embedding=np.zeros((N, dims)), a=a, b=b, n_epochs=n_epochs, num_neighbors=max(n_neighbors, 0), nnz=0, max_steps=0,
+               name=get_umap_name(feature_type, dims), key=get_umap_key(feature_type, dims), knn_ms=0.0, graph_ms=0.0, loop_ms=0.0, n_active=0,
+               n_negative=0)
+    if N < 3:
+        return out
+    if n_neighbors < 2:
+        raise ValueError("run_umap: %d neighbours, at least 2 (the point itself is the first)" % n_neighbors)
+    if x.shape[1] > _lib.UMAP_MAX_FEATURES:
+        raise ValueError("run_umap: %d columns, at most %d" % (x.shape[1], _lib.UMAP_MAX_FEATURES))
+    if init is None:
+        if x.shape[1] < dims:
+            raise ValueError("run_umap: %d columns give no start of %d dimensions" % (x.shape[1], dims))
+        y = x[:, :dims]
+    else:
+        y = np.asarray(init, dtype=np.float64)
+        if y.shape != (N, dims):
+            raise ValueError("run_umap: init is %d x %d" % (N, dims))
+    y = umap_rescale(y)
+    rows, angular = umap_metric_input(x, metric)
+    rows = np.ascontiguousarray(rows)
+    k = n_neighbors - 1
+    ind, dist = np.zeros((N, k), np.int32), np.zeros((N, k))
+    for q0 in range(0, N, int(queries_per_call)):
+        r = ctx.knn(rows, k, query_start=q0, n_queries=min(int(queries_per_call), N - q0))
+        ind[q0:q0 + len(r["indices"])], dist[q0:q0 + len(r["indices"])] = r["indices"], r["distances"]
+        out["knn_ms"] += r["fit_ms"]
+    g = ctx.umap_graph(ind, 0.5 * (dist * dist) if angular else dist, n_epochs)
+    r = ctx.umap_epochs(g["indptr"], g["indices"], g["values"], y, a, b, seed=seed, n_epochs=n_epochs)
+    out.update(embedding=r["y"], nnz=g["nnz"], max_steps=g["max_steps"], graph_ms=g["fit_ms"], loop_ms=r["loop_ms"], n_active=r["n_active"],
+               n_negative=r["n_negative"])
+    return out
+
+
 def mnn_pairs(a, start_i, b, start_j):
     """mutual_nn[(i, j)] of CORRECT_CHEMISTRY_BATCH's join() (crgpu_mnn_pairs, host only): a i32[n_i, k] = the neighbours in batch j (global
     rows, batch j = the rows from start_j) of the rows start_i .. of batch i, b i32[n_j, k] the other direction
@@ -2887,6 +2988,70 @@ class Context:
                                           C.byref(r)))
         o = self._tsne_report(r)
         o.update(y=y, uY=uY, gains=gains)
+        return o
+
+    @staticmethod
+    def _umap_report(r):
+        return dict(wmax=r.wmax, fit_ms=r.fit_ms, search_ms=r.search_ms, csr_ms=r.csr_ms, loop_ms=r.loop_ms, nnz=int(r.nnz), n_active=int(r.n_active),
+                    n_negative=int(r.n_negative), wave_row_len=int(r.wave_row_len), rows_per_wg=int(r.rows_per_wg), max_steps=int(r.max_steps))
+
+    def umap_graph(self, nn_indices, nn_distances, n_epochs):
+        """The fuzzy kNN graph of UMAP on the device (crgpu_umap_graph_dev, csrc/umap.hip) from neighbour indices and dissimilarities
+        [n, k] by rank: per row rho (the first distance > 0) and the search for sigma (at most 64 steps, |psum - log2(k + 1)| < 1e-5,
+        floored at 1e-3 of the mean distance), the memberships, the union of both directions with the value (a + b) - a * b (twin
+        entries carry equal bits), pruned below wmax / n_epochs, CSR with ascending indices
+        -> dict(rho f64[n], sigma f64[n], steps u32[n], indptr i64[n + 1], indices i32[nnz], values f64[nnz], wmax, max_steps, nnz,
+        fit_ms, search_ms, csr_ms, ...)"""
+        ind, dist = np.ascontiguousarray(nn_indices, dtype=np.int32), np.ascontiguousarray(nn_distances, dtype=np.float64)
+        if ind.ndim != 2 or ind.shape != dist.shape:
+            raise ValueError("umap_graph: indices and distances of one shape [n, k]")
+        n, k = ind.shape
+        if not 1 <= k <= _lib.KNN_MAX_K or 2 * n * k >= 1 << 32:      # the output arrays need a shape; the library refuses the rest
+            raise ValueError("umap_graph: k = %d, 1 to %d, and fewer than 2^31 pairs" % (k, _lib.KNN_MAX_K))
+        if not 0 <= int(n_epochs) < 1 << 32:
+            raise ValueError("umap_graph: %d epochs" % n_epochs)
+        o = dict(rho=np.zeros(n), sigma=np.zeros(n), steps=np.zeros(n, np.uint32), indptr=np.zeros(n + 1, np.int64))
+        indices, values = np.zeros(2 * n * k, np.int32), np.zeros(2 * n * k)
+        r = _lib.UmapResult(rho_out=ptr(o["rho"]), sigma_out=ptr(o["sigma"]), steps_out=ptr(o["steps"]), indptr_out=ptr(o["indptr"]),
+                            indices_out=ptr(indices), values_out=ptr(values))
+        self._check(self.L.crgpu_umap_graph_dev(self.h, ptr(ind), ptr(dist), n, k, int(n_epochs), C.byref(r)))
+        o.update(self._umap_report(r))
+        o.update(indices=indices[:o["nnz"]].copy(), values=values[:o["nnz"]].copy())
+        return o
+
+    def umap_epochs(self, indptr, indices, values, y, a, b, seed=0, first_epoch=0, n_run=None, n_epochs=500, epoch_of_next_sample=None,
+                    epoch_of_next_negative_sample=None, gamma=1.0, initial_alpha=1.0, negative_sample_rate=_lib.UMAP_NEGATIVE_SAMPLE_RATE,
+                    want_delta=False, wave_row_len=0, rows_per_wg=0):
+        """The epochs first_epoch .. first_epoch + n_run (default: to n_epochs) of UMAP's layout on a CSR graph on the device
+        (crgpu_umap_epochs_dev) in the per-epoch batch form of include/crgpu.h: every term from y [n, 2 or 3] as it stood at the
+        epoch's start, negative samples from Philox stream `epoch` with key seed.  At first_epoch 0 the library sets the two schedule
+        states; a later call takes those of the call before it.  The inputs are not written.  A run cut into two calls equals one
+        call bit for bit.  wave_row_len / rows_per_wg: test seams, no result depends on them
+        -> dict(y f64[n, dims], epoch_of_next_sample, epoch_of_next_negative_sample f64[nnz], delta (want_delta: of the last epoch),
+        n_active, n_negative, wmax, loop_ms, fit_ms, ...)"""
+        indptr, indices, values = self._tsne_csr("umap_epochs", indptr, indices, values)
+        n = len(indptr) - 1
+        y = np.array(y, dtype=np.float64, order="C")
+        if y.ndim != 2 or y.shape[0] != n:
+            raise ValueError("umap_epochs: y is %d x dims" % n)
+        n_run = int(n_epochs) - int(first_epoch) if n_run is None else int(n_run)
+        if first_epoch < 0 or n_run < 0 or n_epochs < 0:
+            raise ValueError("umap_epochs: epochs %d + %d of %d" % (first_epoch, n_run, n_epochs))
+        if first_epoch and (epoch_of_next_sample is None or epoch_of_next_negative_sample is None):
+            raise ValueError("umap_epochs: a call that does not start at epoch 0 takes the two schedule states")
+        state = [np.zeros(len(values)) if s is None or not first_epoch else np.array(s, dtype=np.float64, order="C")
+                 for s in (epoch_of_next_sample, epoch_of_next_negative_sample)]
+        if state[0].shape != values.shape or state[1].shape != values.shape:
+            raise ValueError("umap_epochs: the schedule states have one value per entry")
+        delta = np.zeros_like(y) if want_delta else None
+        args = _lib.UmapArgs(a=float(a), b=float(b), gamma=float(gamma), initial_alpha=float(initial_alpha), seed=int(seed), first_epoch=int(first_epoch),
+                             n_run=n_run, n_epochs=int(n_epochs), negative_sample_rate=int(negative_sample_rate), wave_row_len=int(wave_row_len),
+                             rows_per_wg=int(rows_per_wg))
+        r = _lib.UmapResult(delta_out=ptr(delta) if want_delta else None)
+        self._check(self.L.crgpu_umap_epochs_dev(self.h, ptr(indptr), ptr(indices), ptr(values), n, y.shape[1], ptr(y), ptr(state[0]), ptr(state[1]),
+                                                 C.byref(args), C.byref(r)))
+        o = self._umap_report(r)
+        o.update(y=y, epoch_of_next_sample=state[0], epoch_of_next_negative_sample=state[1], delta=delta)
         return o
 
     def batch_correct(self, projection, steps, sigma=_lib.CBC_SIGMA, num_pcs=None, want_corr=False, pair_tile=0, row_tile=0, slab_rows=0):

@@ -2248,6 +2248,119 @@ int crgpu_tsne_gradient_dev(crgpu_ctx *ctx, const int64_t *indptr, const int32_t
 int crgpu_tsne_dev(crgpu_ctx *ctx, const int64_t *indptr, const int32_t *indices, const double *values, uint64_t n, uint32_t dims, double *y,
                    double *uY, double *gains, const crgpu_tsne_args *args, crgpu_tsne_result *result);
 
+/* ---- RUN_UMAP: the fuzzy kNN graph, the sampled epochs of the layout, the fit of the curve (csrc/umap.hip) ---------------------------
+ * lib/rust/cr_ana/src/stages/umap.rs (wired in mro/rna/sc_rna_analyzer.mro; the projection websummary/analysis_tab_core.py draws) hands
+ * the projection to the crate umap-rs.  The reference carries no source of it, so what follows is the published algorithm (McInnes et
+ * al., as umap-learn states it), restated here and in tests/umap_numpy.py; no bit parity with the crate is claimed.  The stage's rules:
+ * n_neighbors = min(30, N - 1), min_dist 0.3, spread 1, 2 components (3 accepted), the metric correlation / pearson (default), cosine
+ * or euclidean.  The neighbour search is crgpu_knn_dev at k = n_neighbors - 1 on rows prepared on the host (correlation: minus the
+ * row's mean, divided by its norm; cosine: the division alone; a row of norm 0 stays 0; the dissimilarity is 0.5 * (dist * dist) = 1 -
+ * corr); umap-learn counts the point itself as the first of n_neighbors, crgpu_knn_dev drops the first pair: the same rule with the same
+ * duplicate QUIRK.  All of it f64, unfused, no floating-point atomic.
+ *   crgpu_umap_graph_dev         nn_indices i32[n x k], nn_distances f64[n x k] (host, by rank; the indices of a row distinct, the
+ *                                distances finite and not negative), n_epochs >= 1 (it sets the prune alone).
+ *       rho                      per row the first distance > 0 by rank, 0 when there is none.
+ *       the search               lo = 0, hi = inf, mid = 1, at most 64 steps.  A step: psum = sum_j (d_j - rho > 0 ? exp(-((d_j - rho)
+ *                                / mid)) : 1.0), left to right over the ranks from 0.0; it stops when |psum - log2(k + 1)| < 1e-5; else,
+ *                                psum above the target: hi = mid, mid = (lo + hi) / 2; otherwise lo = mid, and mid doubles while hi is
+ *                                still inf, else mid = (lo + hi) / 2.  steps_out = the evaluations (1 .. 64).  log2(k + 1) is the host's.
+ *       the floor                sigma = max(mid, 1e-3 * m); rho > 0: m = the row's distance sum (left to right over the ranks) /
+ *                                (k + 1); else m = the total of all distances / (n (k + 1)).
+ *       membership               1.0 when d - rho <= 0 or sigma == 0, else exp(-((d - rho) / sigma)).
+ *       the union                of (i, j) and (j, i) over all neighbour pairs, the value (a + b) - a * b with an absent direction
+ *                                counted as 0 (set_op_mix_ratio 1); CSR with ascending j per row (one radix sort of i * n + j keys,
+ *                                equal keys merged).  The value is commutative: (i, j) and (j, i) carry the same bits, and the epochs
+ *                                rely on it.
+ *       the prune                wmax = the largest value; entries below wmax / n_epochs are dropped and the CSR is compacted.
+ *       QUIRKS kept              a row whose k distances are all 0 has rho = 0, psum = k at every step, runs its 64 steps and takes the
+ *                                all-distances floor; a row that names itself (crgpu_knn_dev's duplicate QUIRK) gives the entry
+ *                                (i, i) with the value (a + a) - a * a, which is scheduled like any other and pulls nothing.
+ *       ONE SUM ORDER            psum and a row's distance sum: left to right over the ranks; the total of all distances: the row sums
+ *                                over partials of 256 consecutive rows left to right from 0.0, then the partials ascending.
+ *   crgpu_umap_ab                (host) the least-squares fit of 1 / (1 + a x^(2b)) to the curve x < min_dist ? 1 : exp(-(x - min_dist)
+ *                                / spread) at the 300 points linspace(0, 3 spread, 300): Levenberg-Marquardt from (1, 1) until a step
+ *                                is below 1e-12 of the parameters; the 2 x 2 normal equations are solved directly.
+ *   crgpu_umap_epochs_dev        the epochs first_epoch .. first_epoch + n_run - 1 of n_epochs on a CSR graph whose twin entries carry
+ *                                equal bits (crgpu_umap_graph_dev's; not checked).  y f64[n x dims] (row-major, dims 2 or 3),
+ *                                epoch_of_next_sample and epoch_of_next_negative_sample f64[nnz]: host, in and out.  Per entry
+ *                                eps = wmax / w, epns = eps / rate (wmax = the largest value of the CSR given); at first_epoch == 0 the
+ *                                library sets the two states to eps and epns, whatever the arrays hold.  A run cut into two calls
+ *                                equals one call bit for bit.
+ *       the per-epoch batch form every term of epoch n is computed from y as it stood at the epoch's start (Jacobi over vertices), so
+ *                                the step is a pure function (y, state, n) -> (y', state').  umap-learn's own loop is sequential and
+ *                                its parallel mode an unordered race; neither can be a contract.
+ *       the step                 alpha = initial_alpha * (1.0 - n / n_epochs).  Row i walks its entries left to right; an entry
+ *                                e = (i, j) with eons_e <= n is active.  Attraction: v = y_i - y_j, d2 = sum v_t^2 in dimension order,
+ *                                p = pow(d2, b), c = d2 > 0 ? ((-2 a b) * (p / d2)) / (a * p + 1) : 0, delta_t += 2.0 * clip(c * v_t),
+ *                                clip to [-4, 4]; the factor 2 is the tail-side move of the twin entry (j, i), which is active in the
+ *                                same epochs with the same term; then eons_e += eps_e.  Negatives: n_neg = (int) floor((n - eonns_e) /
+ *                                epns_e); for s = 0 .. n_neg - 1 ascending the vertex kk = word % n, the word being word
+ *                                e * CRGPU_UMAP_SLOTS + s of Philox stream n with key seed: element e * 16 + s of np.random.Philox(
+ *                                counter=[0, n, 0, 0], key=[seed, 0]).random_raw(); kk == i contributes nothing, else v = y_i - y_kk,
+ *                                c = d2 > 0 ? (2 gamma b) / ((0.001 + d2) * (a * pow(d2, b) + 1)) : 0, delta_t += clip(c * v_t); then
+ *                                eonns_e += n_neg * epns_e.  n_neg <= 2 rate - 1 <= 15.  After the row y'_i = y_i + alpha * delta.
+ *                                (-2 a b) = (-2.0 * a) * b and (2 gamma b) = (2.0 * gamma) * b are the host's products.
+ *       ONE SUM ORDER            a row's terms are added in (entry, attraction, then s ascending) order from 0.0, so neither seam
+ *                                moves a bit; pow is OCML's, so a host restatement agrees to its last bits and not beyond.
+ *   crgpu_umap_args              a, b (crgpu_umap_ab); gamma (0 = 1); initial_alpha (0 = 1); seed; first_epoch, n_run, n_epochs;
+ *                                negative_sample_rate (0 = 5; 1 .. CRGPU_UMAP_MAX_RATE).  Seams, FIELDS and not environment switches,
+ *                                0 = the default, neither moves a bit of a result: wave_row_len = CSR entries from which a row is
+ *                                walked by a wave instead of a lane (default 32); rows_per_wg = threads of a workgroup = the rows of
+ *                                one in the lane-per-row launch (64, 128, 256; default 256); reserved0, reserved1 0.
+ *   crgpu_umap_result            pointers the caller sets, NULL = not wanted.  Graph: rho_out f64[n], sigma_out f64[n], steps_out
+ *                                u32[n], indptr_out i64[n + 1], indices_out i32[room for 2 n k], values_out f64[room for 2 n k].
+ *                                Epochs: delta_out f64[n x dims] = delta of the call's last epoch.  wmax; fit_ms = host time of the
+ *                                call; search_ms, csr_ms, loop_ms = device time; nnz; n_active = active entries and n_negative =
+ *                                negative samples over the call; the seams used; max_steps = the longest search.
+ *   on the device                the search: a lane per row.  An epoch: one kernel in two launches, a lane per row below wave_row_len
+ *                                entries and a wave per row from it on (the lanes compute 64 terms at a time, which are then added in
+ *                                term order), y double-buffered, the states updated in place by the entry's one owner.  No atomic, no
+ *                                graph capture, no cooperative launch; the host reads nothing inside the loop.
+ *   refused with CRGPU_EINVAL before the device is touched: n < 2 or n >= 2^31, k = 0 or k > min(n - 1, CRGPU_KNN_MAX_K), n_epochs = 0,
+ *   dims other than 2 or 3, a value that is not finite, a negative distance, a neighbour outside the rows or named twice by a row, CSR
+ *   indices outside the rows or not strictly ascending, a CSR value that is not positive, an indptr that does not start at 0, shrinks
+ *   or holds 2^59 entries or more (nnz * 16 < 2^63), a or b not positive, gamma or initial_alpha negative, a negative sample rate above
+ *   CRGPU_UMAP_MAX_RATE, epochs beyond n_epochs, rows_per_wg other than 64, 128, 256, a reserved field that is not 0, a negative
+ *   min_dist, a spread that is not positive, a NULL that is not optional.  CRGPU_ERANGE: 2^31 or more neighbour pairs.
+ * NOT covered: spectral initialisation (the start is the caller's or the first dims columns of the input, every column rescaled to
+ * [0, 10], in the Python layer), the crate's own random stream and its Original / Parallel variants, set_op_mix_ratio != 1 and
+ * local_connectivity != 1, the H5 and CSV writers, float32, inputs wider than 128 columns (crgpu_knn_dev's limit), approximate
+ * neighbour search. */
+#define CRGPU_UMAP_SLOTS 16
+#define CRGPU_UMAP_MAX_RATE 8
+struct crgpu_umap_args {
+    double a, b;                       /* the curve 1 / (1 + a x^(2b)) */
+    double gamma;                      /* 0 = 1 */
+    double initial_alpha;              /* 0 = 1 */
+    uint64_t seed;
+    uint32_t first_epoch, n_run, n_epochs;
+    uint32_t negative_sample_rate;     /* 0 = 5 */
+    uint32_t wave_row_len;             /* seam: CSR entries from which a row gets a wave, 0 = default */
+    uint32_t rows_per_wg;              /* seam: threads of a workgroup, 0 = default */
+    uint32_t reserved0, reserved1;
+};
+typedef struct crgpu_umap_args crgpu_umap_args;
+struct crgpu_umap_result {
+    double *rho_out;                   /* f64[n] or NULL */
+    double *sigma_out;                 /* f64[n] or NULL */
+    uint32_t *steps_out;               /* u32[n] or NULL */
+    int64_t *indptr_out;               /* i64[n + 1] or NULL */
+    int32_t *indices_out;              /* i32[2 n k] or NULL */
+    double *values_out;                /* f64[2 n k] or NULL */
+    double *delta_out;                 /* f64[n x dims] or NULL */
+    double wmax;
+    double fit_ms, search_ms, csr_ms, loop_ms;
+    uint64_t nnz, n_active, n_negative;
+    uint32_t wave_row_len, rows_per_wg, max_steps, reserved;
+};
+typedef struct crgpu_umap_result crgpu_umap_result;
+int crgpu_umap_ab(double min_dist, double spread, double *a_out, double *b_out);
+int crgpu_umap_graph_dev(crgpu_ctx *ctx, const int32_t *nn_indices, const double *nn_distances, uint64_t n, uint32_t k, uint32_t n_epochs,
+                         crgpu_umap_result *result);
+int crgpu_umap_epochs_dev(crgpu_ctx *ctx, const int64_t *indptr, const int32_t *indices, const double *values, uint64_t n, uint32_t dims, double *y,
+                          double *epoch_of_next_sample, double *epoch_of_next_negative_sample, const crgpu_umap_args *args,
+                          crgpu_umap_result *result);
+
 /* ---- synthetic workloads (bench / tests) ---------------------------------------------
  * Counter-based integer generator: read i of a given seed is identical on the host and on the
  * device.  Tables are host arrays built by cellranger_amd.synth. */

@@ -1462,6 +1462,41 @@ inline crgpu_tsne_result tsne_run(Context &ctx, const TsneAffinities &p, uint32_
     return r;
 }
 
+// ---- RUN_UMAP: the fuzzy kNN graph and the sampled epochs of the layout ---------------------------------------------------------------
+static_assert(sizeof(crgpu_umap_args) == 72, "crgpu_umap_args changed: bump CRGPU_ABI_VERSION and every binding");
+static_assert(sizeof(crgpu_umap_result) == 136, "crgpu_umap_result changed: bump CRGPU_ABI_VERSION and every binding");
+struct UmapGraph {
+    std::vector<double> rho, sigma, values;        // [n]; [n]; [nnz]
+    std::vector<uint32_t> steps;                   // [n]
+    std::vector<int64_t> indptr;                   // [n + 1]
+    std::vector<int32_t> indices;                  // [nnz], ascending within a row
+    crgpu_umap_result info{};
+};
+/// crgpu_umap_graph_dev on the neighbours knn() delivers at k = n_neighbors - 1: the pruned fuzzy union as CSR, twin entries equal bit for bit
+inline UmapGraph umap_graph(Context &ctx, const int32_t *nn_indices, const double *nn_distances, uint64_t n, uint32_t k, uint32_t n_epochs) {
+    UmapGraph o;
+    const size_t room = (size_t)2 * n * k;
+    o.rho.assign(n, 0.0), o.sigma.assign(n, 0.0), o.steps.assign(n, 0), o.indptr.assign(n + 1, 0), o.indices.assign(room, 0), o.values.assign(room, 0.0);
+    o.info.rho_out = o.rho.data(), o.info.sigma_out = o.sigma.data(), o.info.steps_out = o.steps.data(), o.info.indptr_out = o.indptr.data();
+    o.info.indices_out = o.indices.data(), o.info.values_out = o.values.data();
+    ctx.check(crgpu_umap_graph_dev(ctx.get(), nn_indices, nn_distances, n, k, n_epochs, &o.info));
+    o.indices.resize(o.info.nnz), o.values.resize(o.info.nnz);
+    return o;
+}
+/// crgpu_umap_epochs_dev: the epochs first_epoch .. first_epoch + n_run of n_epochs on y ([n][dims]) and the two schedule states ([nnz]),
+/// all in and out; a, b from crgpu_umap_ab; returns the counters
+inline crgpu_umap_result umap_run(Context &ctx, const UmapGraph &g, uint32_t dims, std::vector<double> &y, std::vector<double> &next_sample,
+                                  std::vector<double> &next_negative, double a, double b, uint64_t seed, uint32_t first_epoch, uint32_t n_run,
+                                  uint32_t n_epochs) {
+    crgpu_umap_args args{};
+    args.a = a, args.b = b, args.seed = seed, args.first_epoch = first_epoch, args.n_run = n_run, args.n_epochs = n_epochs;
+    next_sample.resize(g.values.size()), next_negative.resize(g.values.size());
+    crgpu_umap_result r{};
+    ctx.check(crgpu_umap_epochs_dev(ctx.get(), g.indptr.data(), g.indices.data(), g.values.data(), g.indptr.size() - 1, dims, y.data(), next_sample.data(),
+                                    next_negative.data(), &args, &r));
+    return r;
+}
+
 // ---- CORRECT_CHEMISTRY_BATCH: batch-balanced neighbours, mutual nearest neighbours, the correction of the merged batches ---------------
 static_assert(sizeof(crgpu_knn_cross_args) == 48, "crgpu_knn_cross_args changed: bump CRGPU_ABI_VERSION and every binding");
 static_assert(sizeof(crgpu_bc_step) == 48, "crgpu_bc_step changed: bump CRGPU_ABI_VERSION and every binding");
