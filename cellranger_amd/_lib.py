@@ -435,10 +435,24 @@ class UmapResult(C.Structure):
         (n, C.c_uint32) for n in ("wave_row_len", "rows_per_wg", "max_steps", "reserved")]
 
 
+class LouvainArgs(C.Structure):
+    """crgpu_louvain_args"""
+    _fields_ = [(n, C.c_uint32) for n in ("symmetrize", "max_rounds", "wave_deg_max", "lds_deg_max", "batch", "reserved0")] + [("levels_capacity", C.c_uint64)]
+
+
+class LouvainResult(C.Structure):
+    """crgpu_louvain_result"""
+    _fields_ = [(n, C.c_void_p) for n in ("levels_out", "level0_out", "final_out", "level_nodes_out", "level_communities_out", "level_rounds_out",
+                                          "level_S_out", "level_ms_out")] + [("M", C.c_int64)] + [(n, C.c_uint64) for n in ("levels_needed", "nnz")] + [
+        (n, C.c_double) for n in ("fit_ms", "union_ms", "rounds_ms", "aggregate_ms")] + [
+        (n, C.c_uint32) for n in ("n_levels", "wave_deg_max", "lds_deg_max", "batch")]
+
+
 KM_MAX_K, KM_MAX_D, KM_MAX_LIST = 64, 128, 64
 TSNE_CAND_CHUNK, TSNE_MAX_FEATURES = 4096, 128
 TSNE_PERPLEXITY, TSNE_THETA, TSNE_MAX_ITER, TSNE_STOP_LYING_ITER, TSNE_MOM_SWITCH_ITER, TSNE_ETA = 30, 0.5, 1000, 250, 250, 200.0
 UMAP_SLOTS, UMAP_MAX_RATE, UMAP_MAX_FEATURES = 16, 8, 128
+LOUVAIN_MAX_LEVELS, LOUVAIN_MAX_ROUNDS, LOUVAIN_WAVE_DEG_MAX, LOUVAIN_LDS_DEG_MAX, LOUVAIN_BATCH = 64, 1000, 127, 2047, 8
 UMAP_N_NEIGHBORS, UMAP_MIN_DIST, UMAP_SPREAD, UMAP_NEGATIVE_SAMPLE_RATE, UMAP_METRICS = 30, 0.3, 1.0, 5, ("correlation", "pearson", "cosine", "euclidean")
 PCA_MAX_COMPONENTS, PCA_DEFAULT_THRESHOLD, PCA_OK, PCA_NULL_AXIS, PCA_RANK_TOO_SMALL = 128, 2, 0, 1, 2
 KNN_MAX_K, KNN_MAX_CAPACITY = 1024, 4096
@@ -633,6 +647,8 @@ SYMBOLS = {
     "crgpu_umap_ab": (_i, [_dbl, _dbl, C.POINTER(_dbl), C.POINTER(_dbl)]),
     "crgpu_umap_graph_dev": (_i, [_vp, _vp, _vp, _u64, _u32, _u32, C.POINTER(UmapResult)]),
     "crgpu_umap_epochs_dev": (_i, [_vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, C.POINTER(UmapArgs), C.POINTER(UmapResult)]),
+    "crgpu_louvain_dev": (_i, [_vp, _vp, _vp, _vp, _u64, C.POINTER(LouvainArgs), C.POINTER(LouvainResult)]),
+    "crgpu_modularity": (_i, [_vp, _vp, _vp, _u64, _vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "crgpu_aggregate_min_antibodies": (_i, [_u32, C.POINTER(_u32)]),
     "crgpu_antigen_outlier_threshold": (_i, [_vp, _u32, C.POINTER(_dbl), C.POINTER(_dbl), C.POINTER(_dbl)]),
     "crgpu_aggregates_by_counts_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, _u32, _vp, _vp, _u32, C.POINTER(_u32),

@@ -501,6 +501,32 @@ const std::vector<AbiStruct> &abi_table() {
               ABI_F(crgpu_umap_result, rows_per_wg),
               ABI_F(crgpu_umap_result, max_steps),
               ABI_F(crgpu_umap_result, reserved)),
+        ABI_S(crgpu_louvain_args, ABI_F(crgpu_louvain_args, symmetrize),
+              ABI_F(crgpu_louvain_args, max_rounds),
+              ABI_F(crgpu_louvain_args, wave_deg_max),
+              ABI_F(crgpu_louvain_args, lds_deg_max),
+              ABI_F(crgpu_louvain_args, batch),
+              ABI_F(crgpu_louvain_args, reserved0),
+              ABI_F(crgpu_louvain_args, levels_capacity)),
+        ABI_S(crgpu_louvain_result, ABI_F(crgpu_louvain_result, levels_out),
+              ABI_F(crgpu_louvain_result, level0_out),
+              ABI_F(crgpu_louvain_result, final_out),
+              ABI_F(crgpu_louvain_result, level_nodes_out),
+              ABI_F(crgpu_louvain_result, level_communities_out),
+              ABI_F(crgpu_louvain_result, level_rounds_out),
+              ABI_F(crgpu_louvain_result, level_S_out),
+              ABI_F(crgpu_louvain_result, level_ms_out),
+              ABI_F(crgpu_louvain_result, M),
+              ABI_F(crgpu_louvain_result, levels_needed),
+              ABI_F(crgpu_louvain_result, nnz),
+              ABI_F(crgpu_louvain_result, fit_ms),
+              ABI_F(crgpu_louvain_result, union_ms),
+              ABI_F(crgpu_louvain_result, rounds_ms),
+              ABI_F(crgpu_louvain_result, aggregate_ms),
+              ABI_F(crgpu_louvain_result, n_levels),
+              ABI_F(crgpu_louvain_result, wave_deg_max),
+              ABI_F(crgpu_louvain_result, lds_deg_max),
+              ABI_F(crgpu_louvain_result, batch)),
         ABI_S(crgpu_pca_args, ABI_F(crgpu_pca_args, pca_bc_indices),
               ABI_F(crgpu_pca_args, n_pca_bcs),
               ABI_F(crgpu_pca_args, start),

@@ -1243,6 +1243,28 @@ def write_louvain_edges(file, nn_indptr, nn_indices):
     return len(indices)
 
 
+def louvain_pairs(result):
+    """The (node, community) lines `louvain -l -1` would print for Context.louvain's result: every level in turn, a level's nodes
+    ascending -> a list of (int, int); louvain_labels keeps the first occurrence of a node, which is its level-0 line"""
+    return [(i, int(c)) for level in result["levels"] for i, c in enumerate(np.asarray(level).tolist())]
+
+
+def modularity(indptr, indices, labels, weights=None):
+    """The exact modularity of a labelling (labels >= 0) of a symmetric CSR graph, a self-loop once, weights None = 1
+    (crgpu_modularity, host only): S = sum_C (in_C * M - tot_C^2) and M = the sum of all entries as integers -> (S, M, Q = S / M^2)"""
+    indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+    indices, labels = np.ascontiguousarray(indices, dtype=np.int32), np.ascontiguousarray(labels, dtype=np.int32)
+    n = len(indptr) - 1
+    if n < 1 or len(labels) != n or len(indices) < indptr[-1] or (weights is not None and len(weights) != len(indices)):
+        raise ValueError("modularity: indptr of n + 1, n labels, indices and weights of indptr[n] elements")
+    w = None if weights is None else np.ascontiguousarray(weights, dtype=np.uint32)
+    S, M = C.c_int64(0), C.c_int64(0)
+    rc = _lib.load().crgpu_modularity(ptr(indptr), ptr(indices), None if w is None else ptr(w), n, ptr(labels), C.byref(S), C.byref(M))
+    if rc != 0:
+        raise ValueError("modularity: refused (%d)" % rc)
+    return int(S.value), int(M.value), S.value / float(M.value) ** 2
+
+
 def run_graph_clustering(ctx, projection, num_neighbors=None, neighbor_a=None, neighbor_b=None, input_pcs=None, louvain=None,
                          num_barcodes=None, use_bcs=None, queries_per_call=_lib.NN_QUERIES_PER_CHUNK):
     """RUN_GRAPH_CLUSTERING up to the Louvain binary: k by split()'s rule, the exact k nearest neighbours of every row of the cells x PCs
@@ -1250,7 +1272,13 @@ def run_graph_clustering(ctx, projection, num_neighbors=None, neighbor_a=None, n
     -> dict(num_neighbors, indices i32[n, k] by rank, distances f64[n, k], nn_indptr i64[n + 1], nn_indices i32[n k] (row-wise
     ascending: the CSR matrix of merge_nearest_neighbors, every value 1), nn_nodes, nn_links, nn_density, pairs_evaluated, fit_ms).
     louvain: None, or a callable (row, col) -> the (node, community) pairs of the binary's output for that edge list; then also labels
-    (louvain_labels(num_barcodes, use_bcs, pairs); default every row in order) and clusters (relabel_by_size(labels))"""
+    (louvain_labels(num_barcodes, use_bcs, pairs); default every row in order) and clusters (relabel_by_size(labels)).
+    louvain="device": Context.louvain on the neighbour matrix (the published algorithm in synchronous integer rounds, no parity with
+    bin/louvain); labels = level 0 plus 1 (0 for a barcode that was not used) = louvain_labels(.., louvain_pairs(result)), clusters =
+    relabel_by_size(labels), final_clusters = the same of the last level, levels = the partition of every level, modularity = Q per
+    level, louvain = Context.louvain's dict"""
+    if isinstance(louvain, str) and louvain != "device":
+        raise ValueError("run_graph_clustering: louvain is None, a callable or \"device\"")
     x = np.asarray(projection)
     if x.ndim != 2:
         raise ValueError("run_graph_clustering: the projection is cells x PCs")
@@ -1268,7 +1296,16 @@ def run_graph_clustering(ctx, projection, num_neighbors=None, neighbor_a=None, n
         fit_ms += r["fit_ms"]
     out = dict(num_neighbors=k, indices=ind, distances=dist, nn_indptr=np.arange(n + 1, dtype=np.int64) * k, nn_indices=srt.reshape(-1),
                nn_nodes=n, nn_links=n * k, nn_density=(n * k) / float(n * n), pairs_evaluated=pairs_evaluated, fit_ms=fit_ms)
-    if louvain is not None:
+    if isinstance(louvain, str):
+        r = ctx.louvain(out["nn_indptr"], out["nn_indices"], symmetrize=True)
+        use = np.arange(n) if use_bcs is None else np.asarray(use_bcs)
+        out["labels"] = np.zeros(n if num_barcodes is None else int(num_barcodes), dtype=np.int64)
+        out["labels"][use] = 1 + r["level0"].astype(np.int64)      # load_louvain_results: the first occurrence of a node is its level-0 line
+        final = np.zeros(len(out["labels"]), dtype=np.int64)
+        final[use] = 1 + r["final"].astype(np.int64)
+        out.update(clusters=relabel_by_size(out["labels"]), final_clusters=relabel_by_size(final), levels=r["levels"],
+                   modularity=[S / float(r["M"]) ** 2 for S in r["S"]], louvain=r)
+    elif louvain is not None:
         row = np.repeat(np.arange(n, dtype=np.int64), k)
         pairs = louvain(row, out["nn_indices"].astype(np.int64))
         out["labels"] = louvain_labels(n if num_barcodes is None else num_barcodes, np.arange(n) if use_bcs is None else use_bcs, pairs)
@@ -3053,6 +3090,51 @@ class Context:
         o = self._umap_report(r)
         o.update(y=y, epoch_of_next_sample=state[0], epoch_of_next_negative_sample=state[1], delta=delta)
         return o
+
+    def louvain(self, indptr, indices, weights=None, symmetrize=True, max_rounds=None, wave_deg_max=0, lds_deg_max=0, batch=0):
+        """Louvain on the device (crgpu_louvain_dev, csrc/louvain.hip): the published algorithm in the synchronous integer rounds of
+        include/crgpu.h on a CSR graph.  symmetrize=True (the stage): the union of both directions of an unweighted neighbour matrix,
+        weights None; False: a symmetric CSR with ascending columns and weights >= 1 (None = 1).  Two runs and tests/louvain_numpy.py
+        agree bit for bit; no parity with bin/louvain.  wave_deg_max / lds_deg_max / batch: test seams, no result depends on them
+        -> dict(levels: a list of i32[nodes of the level], nodes, communities, rounds, S: lists per level, M, level0 i32[n], final
+        i32[n], nnz, fit_ms, union_ms, rounds_ms, aggregate_ms, level_ms: per level the host time of its rounds, wave_deg_max, lds_deg_max,
+        batch)"""
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        if indptr.ndim != 1 or len(indptr) < 2:
+            raise ValueError("louvain: indptr of n + 1 elements, n >= 1")
+        n = len(indptr) - 1
+        raw = np.asarray(indices)
+        if raw.size and (raw.min() < -(1 << 31) or raw.max() >= 1 << 31):
+            raise ValueError("louvain: an index outside the nodes")
+        indices = np.ascontiguousarray(raw, dtype=np.int32)
+        if indices.ndim != 1 or len(indices) < indptr[-1]:
+            raise ValueError("louvain: indices of indptr[n] elements")
+        w = None
+        if weights is not None:
+            w = np.asarray(weights)
+            if w.shape != indices.shape or (w.size and (w.min() < 0 or w.max() >= 1 << 32)):
+                raise ValueError("louvain: one u32 weight per entry")
+            w = np.ascontiguousarray(w, dtype=np.uint32)
+        capacity = 4 * n + 64
+        while True:
+            flat, level0, final = np.zeros(capacity, np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+            per = [np.zeros(_lib.LOUVAIN_MAX_LEVELS, np.uint32) for _ in range(3)] + [np.zeros(_lib.LOUVAIN_MAX_LEVELS, np.int64),
+                                                                                          np.zeros(_lib.LOUVAIN_MAX_LEVELS)]
+            args = _lib.LouvainArgs(symmetrize=1 if symmetrize else 0, max_rounds=0 if max_rounds is None else int(max_rounds),
+                                    wave_deg_max=int(wave_deg_max), lds_deg_max=int(lds_deg_max), batch=int(batch), levels_capacity=capacity)
+            r = _lib.LouvainResult(levels_out=ptr(flat), level0_out=ptr(level0), final_out=ptr(final), level_nodes_out=ptr(per[0]),
+                                   level_communities_out=ptr(per[1]), level_rounds_out=ptr(per[2]), level_S_out=ptr(per[3]), level_ms_out=ptr(per[4]))
+            self._check(self.L.crgpu_louvain_dev(self.h, ptr(indptr), ptr(indices), None if w is None else ptr(w), n, C.byref(args), C.byref(r)))
+            if r.levels_needed <= capacity:
+                break
+            capacity = int(r.levels_needed)      # a pure function of its input: the second call gives the same levels
+        nl = int(r.n_levels)
+        nodes = [int(v) for v in per[0][:nl]]
+        starts = np.concatenate([[0], np.cumsum(nodes)]).astype(np.int64)
+        return dict(levels=[flat[starts[l]:starts[l + 1]].copy() for l in range(nl)], nodes=nodes, communities=[int(v) for v in per[1][:nl]],
+                    rounds=[int(v) for v in per[2][:nl]], S=[int(v) for v in per[3][:nl]], level_ms=[float(v) for v in per[4][:nl]], M=int(r.M), level0=level0, final=final, nnz=int(r.nnz),
+                    fit_ms=r.fit_ms, union_ms=r.union_ms, rounds_ms=r.rounds_ms, aggregate_ms=r.aggregate_ms, wave_deg_max=int(r.wave_deg_max),
+                    lds_deg_max=int(r.lds_deg_max), batch=int(r.batch))
 
     def batch_correct(self, projection, steps, sigma=_lib.CBC_SIGMA, num_pcs=None, want_corr=False, pair_tile=0, row_tile=0, slab_rows=0):
         """a merge schedule of CORRECT_CHEMISTRY_BATCH with the matrix resident on the device (crgpu_batch_correct_dev,

@@ -2361,6 +2361,98 @@ int crgpu_umap_epochs_dev(crgpu_ctx *ctx, const int64_t *indptr, const int32_t *
                           double *epoch_of_next_sample, double *epoch_of_next_negative_sample, const crgpu_umap_args *args,
                           crgpu_umap_result *result);
 
+/* ---- RUN_GRAPH_CLUSTERING: Louvain in exact integer rounds, the modularity of a labelling (csrc/louvain.hip) -------------------------
+ * lib/python/cellranger/analysis/graphclust.py pipes "%d\t%d\n" lines of the neighbour matrix into bin/convert, runs bin/louvain -q 0
+ * -l -1 -s <seed> and keeps, in load_louvain_results, the first occurrence of every node: the level-0 partition.  The reference carries
+ * the source of neither binary, so what follows is the published algorithm (Blondel et al. 2008); no parity with the binary is claimed.
+ * The serial algorithm visits the nodes in a seeded random order and its parallel forms are unordered races; neither can be a contract.
+ * The contract here is a synchronous round in which every quantity is an integer: a round is a pure function of the labels at its
+ * start, every comparison is exact, every sum is order-independent.  The device, tests/louvain_numpy.py and a rerun agree bit for bit.
+ *   the graph                    a CSR: indptr i64[n + 1], indices i32, weights u32 or NULL (host).
+ *       symmetrize = 1           the stage; weights must be NULL.  For i != j, A_ij = A_ji = 1 when j is in row i or i is in row j;
+ *                                A_ii = 1 when i is in row i (crgpu_knn_dev's duplicate QUIRK); duplicates within a row collapse.  Built
+ *                                as RUN_UMAP builds its union: the keys i * n + j of both directions, one radix sort, the heads of the
+ *                                runs as a CSR.  This is what the public Louvain package's `convert` is believed to make of an
+ *                                unweighted edge list; that is not verified against the binary.
+ *       symmetrize = 0           a CSR that is symmetric already: the columns of a row strictly ascending, weights >= 1 (NULL = 1) and
+ *                                equal in both directions, a self-loop once.  Checked on the device, refused otherwise.  This is the
+ *                                form of the aggregated levels.
+ *   degrees and limits           k_i = sum_j A_ij with the diagonal counted once, M = sum_i k_i.  1 <= n < 2^31, 1 <= M < 2^31 (so
+ *                                every entry is below 2^31 and fewer than 2^31 entries are taken).  Every product below fits i64.
+ *   a round                      at a level with the nodes 0 .. n_L - 1 and the labels c (c_i = i at the start), all of it read from c:
+ *                                tot_C = sum_{c_i = C} k_i, size_C = the nodes labelled C.  The candidates of node i are its own
+ *                                community and the community of every neighbour j != i; w_i(C) = sum_{j != i, c_j = C} A_ij;
+ *                                tot'_i(C) = tot_C - k_i for C == c_i, else tot_C; G_i(C) = w_i(C) * M - tot'_i(C) * k_i in i64.  The
+ *                                best candidate is the maximum of the triple (G, C == own, -C); it is a proposal when it is not the
+ *                                node's own community.  THE SINGLETON RULE: a proposal is dropped when size[own] == 1, size[best] == 1
+ *                                and best > own (the node stays, no second choice is tried); without it two singletons swap places
+ *                                for ever.  The surviving proposals are applied at once: c'.
+ *       S                        S(c) = sum_C (in_C * M - tot_C^2), in_C = sum_{c_i = c_j = C} A_ij over ordered pairs with the
+ *                                diagonal once, so the modularity is Q = S / M^2.  No proposal survives or S(c') <= S(c): the level
+ *                                ends with c and c' is discarded.  Otherwise c = c' and the round counts.  After max_rounds counted
+ *                                rounds (0 = 1000) the level ends.  S rises strictly, so a level ends whatever the graph.
+ *   between levels               the labels are renumbered densely in ascending order of the community id; the next level's graph is
+ *                                A'_CD = sum_{c_i = C, c_j = D} A_ij, so A'_CC = in_C, k'_C = tot_C and M is unchanged (asserted): one
+ *                                radix sort of the keys C * n_C + D and a sum over the runs.  The algorithm ends at the first level
+ *                                without a counted round; that level is not reported, unless it is level 0, which is then reported as
+ *                                the identity.  At most CRGPU_LOUVAIN_MAX_LEVELS levels are reported.
+ *   crgpu_louvain_args           symmetrize; max_rounds (0 = 1000); levels_capacity = the i32 elements levels_out has room for.  Seams,
+ *                                FIELDS and not environment switches, 0 = the default, no result depends on them: wave_deg_max = rows
+ *                                up to it take a wave with a table in LDS (default and limit 127); lds_deg_max = rows up to it take a
+ *                                workgroup with a table in LDS (default and limit 2047), longer rows a workgroup with a table in
+ *                                device memory; batch = the rounds launched between two reads of the stop latch (default 8);
+ *                                reserved0 0.
+ *   crgpu_louvain_result         pointers the caller sets, NULL = not wanted: levels_out i32[levels_capacity] = the partitions of the
+ *                                levels one after the other, level l with the nodes of level l (a level that does not fit is left
+ *                                out, levels_needed counts it all the same: call again with that capacity); level0_out i32[n];
+ *                                final_out i32[n] = level 0 composed through every level; level_nodes_out, level_communities_out,
+ *                                level_rounds_out u32[64], level_S_out i64[64], level_ms_out f64[64] = the host time of the level's
+ *                                rounds.  M; levels_needed; nnz = the entries of the level-0
+ *                                graph; fit_ms = host time of the call, union_ms, rounds_ms, aggregate_ms = its share up to the
+ *                                level-0 degrees, in the rounds, between the levels (host clock between reads that wait for the
+ *                                device); n_levels; the seams used.
+ *   crgpu_modularity             (host) the exact S and M of any labelling (labels >= 0) of a symmetric CSR (weights NULL = 1); the
+ *                                symmetry is the caller's.
+ *   on the device                integer hash tables with atomicCAS on the key and atomicAdd on the weight: the sums are integers and
+ *                                the maximum is over a total order, so no insertion order reaches a result.  tot, size and both sums
+ *                                of S by integer atomicAdd.  The labels are double-buffered; the stop rule is latched on the device
+ *                                and rounds after the latch are no-ops.  No floating point, no graph capture, no cooperative launch.
+ *   refused with CRGPU_EINVAL before the device is touched: n = 0 or n >= 2^31, an indptr that does not start at 0 or shrinks, an index
+ *   outside the nodes, no entry at all, weights with symmetrize = 1, symmetrize above 1, a seam above its limit, reserved0 not 0, a NULL
+ *   that is not optional; after the device's check: columns that are not strictly ascending, a weight of 0, a missing or unequal twin
+ *   entry.  CRGPU_ERANGE: 2^31 entries or more, M >= 2^31.
+ * NOT covered: the binary's random visiting order and its seed, its -q and -l options, the SNN similarity, MERGE_CLUSTERS. */
+#define CRGPU_LOUVAIN_MAX_LEVELS 64
+struct crgpu_louvain_args {
+    uint32_t symmetrize;               /* 1 = the stage: the union of both directions, every weight 1 */
+    uint32_t max_rounds;               /* 0 = 1000 */
+    uint32_t wave_deg_max;             /* seam, 0 = default */
+    uint32_t lds_deg_max;              /* seam, 0 = default */
+    uint32_t batch;                    /* seam, 0 = default */
+    uint32_t reserved0;
+    uint64_t levels_capacity;          /* i32 elements of levels_out */
+};
+typedef struct crgpu_louvain_args crgpu_louvain_args;
+struct crgpu_louvain_result {
+    int32_t *levels_out;               /* i32[levels_capacity] or NULL */
+    int32_t *level0_out;               /* i32[n] or NULL */
+    int32_t *final_out;                /* i32[n] or NULL */
+    uint32_t *level_nodes_out;         /* u32[64] or NULL */
+    uint32_t *level_communities_out;   /* u32[64] or NULL */
+    uint32_t *level_rounds_out;        /* u32[64] or NULL */
+    int64_t *level_S_out;              /* i64[64] or NULL */
+    double *level_ms_out;              /* f64[64] or NULL */
+    int64_t M;
+    uint64_t levels_needed, nnz;
+    double fit_ms, union_ms, rounds_ms, aggregate_ms;
+    uint32_t n_levels, wave_deg_max, lds_deg_max, batch;
+};
+typedef struct crgpu_louvain_result crgpu_louvain_result;
+int crgpu_louvain_dev(crgpu_ctx *ctx, const int64_t *indptr, const int32_t *indices, const uint32_t *weights, uint64_t n,
+                      const crgpu_louvain_args *args, crgpu_louvain_result *result);
+int crgpu_modularity(const int64_t *indptr, const int32_t *indices, const uint32_t *weights, uint64_t n, const int32_t *labels, int64_t *S_out,
+                     int64_t *M_out);
+
 /* ---- synthetic workloads (bench / tests) ---------------------------------------------
  * Counter-based integer generator: read i of a given seed is identical on the host and on the
  * device.  Tables are host arrays built by cellranger_amd.synth. */

@@ -1497,6 +1497,44 @@ inline crgpu_umap_result umap_run(Context &ctx, const UmapGraph &g, uint32_t dim
     return r;
 }
 
+// ---- RUN_GRAPH_CLUSTERING: Louvain in exact integer rounds -------------------------------------------------------------------------------
+static_assert(sizeof(crgpu_louvain_args) == 32, "crgpu_louvain_args changed: bump CRGPU_ABI_VERSION and every binding");
+static_assert(sizeof(crgpu_louvain_result) == 136, "crgpu_louvain_result changed: bump CRGPU_ABI_VERSION and every binding");
+struct LouvainClusters {
+    std::vector<std::vector<int32_t>> levels;      // the partition of every level, level l over the nodes of level l
+    std::vector<int32_t> level0, final_labels;     // [n]; [n]: level 0 composed through every level
+    std::vector<uint32_t> nodes, communities, rounds;  // per level
+    std::vector<int64_t> S;                        // per level: Q = S / M^2
+    std::vector<double> ms;                        // per level: host time of its rounds
+    crgpu_louvain_result info{};
+};
+/// crgpu_louvain_dev on a CSR (symmetrize: the union of both directions of an unweighted neighbour matrix, weights NULL): the published
+/// algorithm in synchronous integer rounds, no parity with bin/louvain
+inline LouvainClusters louvain(Context &ctx, const int64_t *indptr, const int32_t *indices, const uint32_t *weights, uint64_t n, bool symmetrize = true,
+                               uint32_t max_rounds = 0) {
+    LouvainClusters o;
+    std::vector<int32_t> flat((size_t)4 * n + 64);
+    o.level0.assign(n, 0), o.final_labels.assign(n, 0);
+    o.nodes.assign(CRGPU_LOUVAIN_MAX_LEVELS, 0), o.communities.assign(CRGPU_LOUVAIN_MAX_LEVELS, 0), o.rounds.assign(CRGPU_LOUVAIN_MAX_LEVELS, 0);
+    o.S.assign(CRGPU_LOUVAIN_MAX_LEVELS, 0), o.ms.assign(CRGPU_LOUVAIN_MAX_LEVELS, 0.0);
+    crgpu_louvain_args args{};
+    args.symmetrize = symmetrize ? 1u : 0u, args.max_rounds = max_rounds;
+    for (;;) {
+        args.levels_capacity = flat.size();
+        o.info = crgpu_louvain_result{};
+        o.info.levels_out = flat.data(), o.info.level0_out = o.level0.data(), o.info.final_out = o.final_labels.data();
+        o.info.level_nodes_out = o.nodes.data(), o.info.level_communities_out = o.communities.data(), o.info.level_rounds_out = o.rounds.data();
+        o.info.level_S_out = o.S.data(), o.info.level_ms_out = o.ms.data();
+        ctx.check(crgpu_louvain_dev(ctx.get(), indptr, indices, weights, n, &args, &o.info));
+        if (o.info.levels_needed <= flat.size()) break;
+        flat.assign(o.info.levels_needed, 0);      // the run is a pure function of its input: the second call gives the same levels
+    }
+    o.nodes.resize(o.info.n_levels), o.communities.resize(o.info.n_levels), o.rounds.resize(o.info.n_levels), o.S.resize(o.info.n_levels), o.ms.resize(o.info.n_levels);
+    size_t at = 0;
+    for (uint32_t l = 0; l < o.info.n_levels; at += o.nodes[l++]) o.levels.emplace_back(flat.begin() + at, flat.begin() + at + o.nodes[l]);
+    return o;
+}
+
 // ---- CORRECT_CHEMISTRY_BATCH: batch-balanced neighbours, mutual nearest neighbours, the correction of the merged batches ---------------
 static_assert(sizeof(crgpu_knn_cross_args) == 48, "crgpu_knn_cross_args changed: bump CRGPU_ABI_VERSION and every binding");
 static_assert(sizeof(crgpu_bc_step) == 48, "crgpu_bc_step changed: bump CRGPU_ABI_VERSION and every binding");
