@@ -198,17 +198,6 @@ __global__ __launch_bounds__(BC_WG) void k_bc_apply(double *__restrict__ x, cons
 }
 
 // ---- the entry point -------------------------------------------------------------------------------------------------------------
-struct BcEvents {  // two events of the context's pool, given back at scope exit
-    crgpu_ctx *ctx;
-    hipEvent_t e[2];
-    explicit BcEvents(crgpu_ctx *c) : ctx(c) {
-        for (int i = 0; i < 2; i++) e[i] = cr_take_event(c);
-    }
-    ~BcEvents() {
-        for (int i = 0; i < 2; i++)
-            if (e[i]) ctx->event_pool.push_back(e[i]);
-    }
-};
 // device time of what was enqueued since BC_BEGIN, added to *acc; waits for it
 #define BC_BEGIN(ctx, ev) CR_HIP(ctx, hipEventRecord((ev)[0], (ctx)->stream))
 #define BC_END(ctx, ev, acc)                                         \
@@ -280,7 +269,7 @@ extern "C" int crgpu_batch_correct_dev(crgpu_ctx *ctx, const double *x, uint64_t
     res->pairs_evaluated = pairs_evaluated, res->chunks = chunks, res->zero_den_rows = 0, res->pair_tile = P, res->row_tile = R;
     if (n_steps == 0) {  // nothing moves: the matrix as it came
         std::memcpy(x_out, xp.data(), xp.size() * sizeof(double));
-        res->fit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        res->fit_ms = cr_ms_since(t0);
         return CRGPU_OK;
     }
     // the lists of all steps, one behind the other
@@ -318,9 +307,9 @@ extern "C" int crgpu_batch_correct_dev(crgpu_ctx *ctx, const double *x, uint64_t
     CR_TRY(crgpu_memcpy_h2d(ctx, mc_b.p, h_mc.data(), sum_mnn * sizeof(int32_t)));
     CR_TRY(crgpu_memcpy_h2d(ctx, mr_b.p, h_mr.data(), sum_mnn * sizeof(int32_t)));
     CR_HIP(ctx, hipMemsetAsync(ctr_b.p, 0, sizeof(uint64_t), ctx->stream));
-    res->upload_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_up).count();
+    res->upload_ms = cr_ms_since(t_up);
 
-    BcEvents events(ctx);
+    CrEvents<2> events(ctx);
     hipEvent_t *ev = events.e;
     cr_allow_lds(ctx, (const void *)k_bc_accumulate, lds);
     uint64_t ac = 0, am = 0;
@@ -353,7 +342,7 @@ extern "C" int crgpu_batch_correct_dev(crgpu_ctx *ctx, const double *x, uint64_t
         if (q.corr_out) {
             const auto t_dn = std::chrono::steady_clock::now();
             CR_TRY(crgpu_memcpy_d2h(ctx, q.corr_out, corr_b.p, (uint64_t)n_cur * d * sizeof(double)));
-            res->download_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_dn).count();
+            res->download_ms += cr_ms_since(t_dn);
         }
         res->gather_ms += ms[0], res->accumulate_ms += ms[1], res->finish_ms += ms[2], res->apply_ms += ms[3];
         if (res->step_ms_out) std::copy(ms, ms + 4, res->step_ms_out + 4 * (size_t)st);
@@ -363,8 +352,8 @@ extern "C" int crgpu_batch_correct_dev(crgpu_ctx *ctx, const double *x, uint64_t
     uint64_t zero_den = 0;
     CR_TRY(crgpu_memcpy_d2h(ctx, &zero_den, ctr_b.p, sizeof(zero_den)));
     CR_TRY(crgpu_memcpy_d2h(ctx, x_out, x_b.p, xp.size() * sizeof(double)));
-    res->download_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_dn).count();
+    res->download_ms += cr_ms_since(t_dn);
     res->zero_den_rows = zero_den;
-    res->fit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    res->fit_ms = cr_ms_since(t0);
     return CRGPU_OK;
 }

@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -409,6 +410,24 @@ static inline int dmalloc(crgpu_ctx *ctx, DevBuf &b, uint64_t bytes) {
 }
 
 hipEvent_t cr_take_event(crgpu_ctx *ctx);  // an event of the ledger's pool (ctx.hip)
+template <int N>
+struct CrEvents {  // N events of the context's pool, given back at scope exit
+    crgpu_ctx *ctx;
+    hipEvent_t e[N];
+    explicit CrEvents(crgpu_ctx *c) : ctx(c) {
+        for (int i = 0; i < N; i++) e[i] = cr_take_event(c);
+    }
+    ~CrEvents() {
+        for (int i = 0; i < N; i++)
+            if (e[i]) ctx->event_pool.push_back(e[i]);
+    }
+    CrEvents(const CrEvents &) = delete;
+    CrEvents &operator=(const CrEvents &) = delete;
+};
+// host milliseconds since t0
+static inline double cr_ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
 // timing scope: records a HIP event pair around the launches of one family when enabled
 struct CrTimer {
     crgpu_ctx *ctx;

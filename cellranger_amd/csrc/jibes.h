@@ -645,7 +645,7 @@ extern "C" int crgpu_jibes_fit_dev(crgpu_ctx *ctx, const double *y, uint64_t n, 
         if (h.stopped) break;
         CR_REQUIRE(ctx, rounds < rounds_max, CRGPU_EHIP, "crgpu_jibes_fit_dev: no stop after %llu rounds", (unsigned long long)rounds);
     }
-    res->fit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    res->fit_ms = cr_ms_since(t0);
     res->ll = h.ll, res->iterations = h.iterations, res->converged = h.converged;
     for (uint32_t t = 0; t < k; t++) res->bg[t] = h.bg[t], res->fg[t] = h.fg[t], res->sd[t] = h.sd[t];
     {

@@ -815,7 +815,7 @@ extern "C" int crgpu_kmeans_dev(crgpu_ctx *ctx, const double *x, uint64_t n, uin
     std::vector<double> fout((size_t)n_ks * fw);
     CR_TRY(crgpu_memcpy_d2h(ctx, fout.data(), fout_b.p, fout.size() * sizeof(double)));
     CR_TRY(crgpu_memcpy_d2h(ctx, cen_h.data(), cen_b.p, cen_h.size() * sizeof(double)));
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const double ms = cr_ms_since(t0);
     for (uint32_t p = 0; p < n_ks; p++) {
         crgpu_kmeans_result &r = res[p];
         const uint32_t K = ks[p];

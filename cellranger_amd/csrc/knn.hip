@@ -242,17 +242,6 @@ __global__ __launch_bounds__(KNN_WG) void k_knn_final(KnnShape s, const uint64_t
 }
 
 // ---- the entry point -------------------------------------------------------------------------------------------------------------
-struct KnnEvents {  // three events of the context's pool, given back at scope exit
-    crgpu_ctx *ctx;
-    hipEvent_t e[3];
-    explicit KnnEvents(crgpu_ctx *c) : ctx(c) {
-        for (int i = 0; i < 3; i++) e[i] = cr_take_event(c);
-    }
-    ~KnnEvents() {
-        for (int i = 0; i < 3; i++)
-            if (e[i]) ctx->event_pool.push_back(e[i]);
-    }
-};
 static uint32_t knn_host_pow2(uint32_t v) {
     uint32_t p = 2u;
     while (p < v) p <<= 1;
@@ -319,7 +308,7 @@ static int knn_run(crgpu_ctx *ctx, const double *x, const KnnCall &c, crgpu_knn_
     unsigned long long *d_ctr = ctr_b.as<unsigned long long>();
     uint32_t *d_bad = (uint32_t *)(d_ctr + 3);
 
-    KnnEvents events(ctx);
+    CrEvents<3> events(ctx);
     hipEvent_t *ev = events.e;
     CR_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
     if (reg) {
@@ -350,7 +339,7 @@ static int knn_run(crgpu_ctx *ctx, const double *x, const KnnCall &c, crgpu_knn_
     CR_HIP(ctx, hipEventElapsedTime(&ms_a, ev[0], ev[1]));
     CR_HIP(ctx, hipEventElapsedTime(&ms_b, ev[1], ev[2]));
     res->select_ms = ms_a, res->sort_ms = ms_b;
-    res->fit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    res->fit_ms = cr_ms_since(t0);
     res->compactions = ctr[0], res->selections = ctr[1], res->survivors = ctr[2], res->pairs_evaluated = nq * c.nc;
     res->in_lds = s.in_lds, res->capacity = cap, res->query_tiles = n_tiles, res->cand_tile = tile;
     return CRGPU_OK;

@@ -6,7 +6,8 @@
 // tests/louvain_numpy.py restates.  No parity with the binary is claimed.  No floating point below the timings.
 //
 // Launch structure.
-//   k_lv_keys / one radix sort / compaction of the run heads / k_lv_csr     the union of both directions (symmetrize = 1), as umap.hip
+//   k_lv_keys / one radix sort / compaction of the run heads / k_keys_to_csr   the union of both directions (symmetrize = 1): the path
+//                                                                          of graph_common.h, as tsne.hip and umap.hip take it
 //   k_lv_check                                                             symmetrize = 0: ascending columns, weights >= 1, the twin entry
 //   k_lv_degrees                                                           a wave per node: k_i, M, the longest row
 //   a round = k_lv_prep, k_lv_round<0 | 1 | 2>, k_lv_inside, k_lv_squares, k_lv_decide
@@ -18,14 +19,14 @@
 //     k_lv_decide  one thread: S(c') from the two integer sums; the round counts and the buffers swap when S rises, else the level is
 //                  latched as stopped and every later launch of the batch returns at once.  The host reads the latch once per batch.
 //   between levels: the dense renumbering by a compaction of the used ids, the keys C * n_C + D, one radix sort, the run heads, the run
-//   sums by integer atomicAdd, the CSR.
+//   sums by integer atomicAdd, k_keys_to_csr.
 #include <algorithm>
 #include <chrono>
 #include <climits>
 #include <unordered_map>
 #include <vector>
 
-#include "stage_common.h"
+#include "graph_common.h"
 
 #define LV_WG 256u
 #define LV_WAVES (LV_WG / 64u)
@@ -80,10 +81,6 @@ __global__ __launch_bounds__(LV_WG) void k_lv_keys(const long long *__restrict__
         keys[2 * e] = i * n + j, keys[2 * e + 1] = j * n + i;
     }
 }
-struct LvHeadFlag {  // the first of a run of equal keys
-    const uint64_t *keys;
-    __device__ __forceinline__ bool operator()(uint64_t i) const { return (i == 0) | (keys[i] != keys[i ? i - 1 : 0]); }
-};
 struct LvEmitKey {
     const uint64_t *keys;
     uint64_t *ckeys;
@@ -91,16 +88,6 @@ struct LvEmitKey {
     __device__ __forceinline__ Pre pre(uint64_t) const { return Pre(); }
     __device__ __forceinline__ void operator()(uint64_t i, uint32_t o, Pre) const { ckeys[o] = keys[i]; }
 };
-// the CSR of sorted distinct keys i * n + j; weights (or NULL) = 1
-__global__ __launch_bounds__(LV_WG) void k_lv_csr(const uint64_t *__restrict__ ckeys, uint64_t nnz, uint32_t n, long long *__restrict__ indptr,
-                                                  int32_t *__restrict__ indices, uint32_t *__restrict__ weights) {
-    const uint64_t stride = (uint64_t)gridDim.x * LV_WG, t0 = (uint64_t)blockIdx.x * LV_WG + threadIdx.x;
-    for (uint64_t r = t0; r <= n; r += stride) indptr[r] = (long long)cr_lower_bound(ckeys, nnz, r * (uint64_t)n);
-    for (uint64_t e = t0; e < nnz; e += stride) {
-        indices[e] = (int32_t)(ckeys[e] % n);
-        if (weights) weights[e] = 1u;
-    }
-}
 // symmetrize = 0 (indices in range, indptr in order: the host's checks): the columns of a row strictly ascending, weights >= 1, the twin
 // entry (j, i) present with the same weight.  A row that is out of order may hide its twin from the search; it is refused for the order.
 __global__ __launch_bounds__(LV_WG) void k_lv_check(const long long *__restrict__ indptr, const int32_t *__restrict__ indices,
@@ -397,23 +384,10 @@ __global__ __launch_bounds__(LV_WG) void k_lv_run_sums(const uint64_t *__restric
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------------
-static double lv_ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-// what both entry points ask of a CSR before anything else: -> 0, or the message's argument
-static const char *lv_check_csr(const int64_t *indptr, const int32_t *indices, uint64_t n) {
-    if (indptr[0] != 0) return "indptr[0] is not 0";
-    for (uint64_t i = 0; i < n; i++)
-        if (indptr[i + 1] < indptr[i] || indptr[i + 1] >= (1ll << 32)) return "indptr shrinks or holds 2^32 entries or more";
-    for (int64_t e = 0; e < indptr[n]; e++)
-        if (indices[e] < 0 || (uint64_t)indices[e] >= n) return "an index outside the nodes";
-    return nullptr;
-}
-
 extern "C" int crgpu_modularity(const int64_t *indptr, const int32_t *indices, const uint32_t *weights, uint64_t n, const int32_t *labels, int64_t *S_out,
                                 int64_t *M_out) {
     if (!indptr || !labels || !S_out || !M_out || n < 1 || n >= (1ull << 31) || (!indices && indptr[n] != 0)) return CRGPU_EINVAL;
-    if (lv_check_csr(indptr, indices, n)) return CRGPU_EINVAL;
+    if (cr_csr_fault(indptr, indices, n, 32u, false).kind != CSR_FINE) return CRGPU_EINVAL;
     for (uint64_t i = 0; i < n; i++)
         if (labels[i] < 0) return CRGPU_EINVAL;
     uint64_t M = 0, inside = 0;
@@ -476,8 +450,7 @@ extern "C" int crgpu_louvain_dev(crgpu_ctx *ctx, const int64_t *indptr, const in
     CR_REQUIRE(ctx, a->wave_deg_max <= LV_WAVE_DEG_CAP && a->lds_deg_max <= LV_WG_DEG_CAP, CRGPU_EINVAL, "%s: wave_deg_max at most %u, lds_deg_max at most %u",
                who, LV_WAVE_DEG_CAP, LV_WG_DEG_CAP);
     CR_REQUIRE(ctx, indices || indptr[n] == 0, CRGPU_EINVAL, "%s: indices is NULL", who);
-    const char *why = lv_check_csr(indptr, indices, n);
-    CR_REQUIRE(ctx, !why, CRGPU_EINVAL, "%s: %s", who, why);
+    CR_TRY(cr_check_csr(ctx, who, indptr, indices, n, 32u, false));  // the order of the columns: k_lv_check
     const uint64_t nnz_in = (uint64_t)indptr[n];
     CR_REQUIRE(ctx, nnz_in >= 1, CRGPU_EINVAL, "%s: a graph without an entry has M = 0", who);
     CR_REQUIRE(ctx, nnz_in < (1ull << 31), CRGPU_ERANGE, "%s: %llu entries, fewer than 2^31 (M < 2^31)", who, (unsigned long long)nnz_in);
@@ -510,18 +483,14 @@ extern "C" int crgpu_louvain_dev(crgpu_ctx *ctx, const int64_t *indptr, const in
         hipLaunchKernelGGL(k_lv_keys, dim3(cr_grid(nnz_in, LV_WG)), dim3(LV_WG), 0, ctx->stream, in_ptr.as<long long>(), in_ind.as<int32_t>(), (uint32_t)n, nnz_in,
                            keys_b.as<uint64_t>());
         CR_HIP(ctx, hipGetLastError());
-        bool in_tmp = false;
-        CR_TRY(cr_radix_sort_u64(ctx, keys_b.as<uint64_t>(), keyt_b.as<uint64_t>(), nullptr, nullptr, n_keys, 0, std::max(1u, cr_ceil_log2(n * n)), &in_tmp));
-        const uint64_t *d_keys = in_tmp ? keyt_b.as<uint64_t>() : keys_b.as<uint64_t>();
-        CR_TRY(compact(ctx, LvHeadFlag{d_keys}, LvEmitKey{d_keys, ckeys_b.as<uint64_t>()}, n_keys, d_block, d_count));
+        SortedKeys sk;
+        CR_TRY(cr_sort_keys(ctx, keys_b.as<uint64_t>(), keyt_b.as<uint64_t>(), nullptr, nullptr, n_keys, cr_ceil_log2(n * n), &sk));
         uint32_t merged = 0;
-        CR_TRY(read_u32(ctx, d_count, &merged));
-        CR_REQUIRE(ctx, merged >= 1 && merged <= n_keys, CRGPU_EHIP, "%s: %u merged entries of %llu", who, merged, (unsigned long long)n_keys);
+        CR_TRY(cr_merge_runs(ctx, sk.keys, LvEmitKey{sk.keys, ckeys_b.as<uint64_t>()}, n_keys, d_block, 1, n_keys, who, "merged entries", &merged));
         ga.n = gb.n = (uint32_t)n, ga.nnz = merged;
         CR_TRY(lv_alloc_graph(ctx, ga, n, merged));
         CR_TRY(lv_alloc_graph(ctx, gb, n, merged));
-        hipLaunchKernelGGL(k_lv_csr, dim3(cr_grid(std::max<uint64_t>(merged, n + 1), LV_WG)), dim3(LV_WG), 0, ctx->stream, (const uint64_t *)ckeys_b.as<uint64_t>(),
-                           (uint64_t)merged, (uint32_t)n, ga.ptr.as<long long>(), ga.ind.as<int32_t>(), ga.w.as<uint32_t>());
+        cr_keys_to_csr(ctx, ckeys_b.as<uint64_t>(), merged, (uint32_t)n, ga.ptr.as<long long>(), ga.ind.as<int32_t>(), ga.w.as<uint32_t>());
         CR_HIP(ctx, hipGetLastError());
     } else {
         ga.n = gb.n = (uint32_t)n, ga.nnz = nnz_in;
@@ -549,7 +518,7 @@ extern "C" int crgpu_louvain_dev(crgpu_ctx *ctx, const int64_t *indptr, const in
     const uint64_t M = state.M;
     CR_REQUIRE(ctx, M >= 1 && M < (1ull << 31), CRGPU_ERANGE, "%s: M = %llu, 1 to 2^31 - 1", who, (unsigned long long)M);
     res->M = (int64_t)M, res->nnz = ga.nnz;
-    res->union_ms = lv_ms_since(t0);
+    res->union_ms = cr_ms_since(t0);
 
     DevBuf lab0, lab1, tot0, tot1, size0, size1, newid_b, dense_b, comp_b, list1_b, list2_b;
     for (DevBuf *b : {&lab0, &lab1, &tot0, &tot1, &size0, &size1, &newid_b, &dense_b, &comp_b, &list1_b, &list2_b}) CR_TRY(dmalloc(ctx, *b, n * sizeof(uint32_t)));
@@ -597,7 +566,7 @@ extern "C" int crgpu_louvain_dev(crgpu_ctx *ctx, const int64_t *indptr, const in
             CR_HIP(ctx, hipGetLastError());
             CR_TRY(crgpu_memcpy_d2h(ctx, &state, d_st, sizeof(LvState)));
         } while (!state.stopped);
-        const double level_ms = lv_ms_since(t_level);
+        const double level_ms = cr_ms_since(t_level);
         res->rounds_ms += level_ms;
         if (state.rounds == 0u && level) break;  // the first level without a counted round is not reported, unless it is level 0
 
@@ -627,29 +596,24 @@ extern "C" int crgpu_louvain_dev(crgpu_ctx *ctx, const int64_t *indptr, const in
         hipLaunchKernelGGL(k_lv_agg_keys, dim3(cr_grid(g->nnz, LV_WG)), dim3(LV_WG), 0, ctx->stream, gv, g->nnz, (const int32_t *)dense_b.as<int32_t>(), n_c,
                            keys_b.as<uint64_t>(), perm_b.as<uint32_t>());
         CR_HIP(ctx, hipGetLastError());
-        bool in_tmp = false;
-        CR_TRY(cr_radix_sort_u64(ctx, keys_b.as<uint64_t>(), keyt_b.as<uint64_t>(), perm_b.as<uint32_t>(), permt_b.as<uint32_t>(), g->nnz, 0,
-                                 std::max(1u, cr_ceil_log2((uint64_t)n_c * n_c)), &in_tmp));
-        const uint64_t *d_keys = in_tmp ? keyt_b.as<uint64_t>() : keys_b.as<uint64_t>();
-        const uint32_t *d_perm = in_tmp ? permt_b.as<uint32_t>() : perm_b.as<uint32_t>();
-        CR_TRY(compact(ctx, LvHeadFlag{d_keys}, LvEmitKey{d_keys, ckeys_b.as<uint64_t>()}, g->nnz, d_block, d_count));
+        SortedKeys sk;
+        CR_TRY(cr_sort_keys(ctx, keys_b.as<uint64_t>(), keyt_b.as<uint64_t>(), perm_b.as<uint32_t>(), permt_b.as<uint32_t>(), g->nnz, cr_ceil_log2((uint64_t)n_c * n_c),
+                            &sk));
         uint32_t runs = 0;
-        CR_TRY(read_u32(ctx, d_count, &runs));
-        CR_REQUIRE(ctx, runs >= 1 && runs <= g->nnz, CRGPU_EHIP, "%s: %u entries of the aggregated graph from %llu", who, runs, (unsigned long long)g->nnz);
+        CR_TRY(cr_merge_runs(ctx, sk.keys, LvEmitKey{sk.keys, ckeys_b.as<uint64_t>()}, g->nnz, d_block, 1, g->nnz, who, "entries of the aggregated graph", &runs));
         CR_HIP(ctx, hipMemsetAsync(spare->w.p, 0, (uint64_t)runs * sizeof(uint32_t), ctx->stream));
-        hipLaunchKernelGGL(k_lv_run_sums, dim3(cr_grid((g->nnz + LV_RUN_CHUNK - 1u) / LV_RUN_CHUNK, LV_WG)), dim3(LV_WG), 0, ctx->stream, d_keys, d_perm,
+        hipLaunchKernelGGL(k_lv_run_sums, dim3(cr_grid((g->nnz + LV_RUN_CHUNK - 1u) / LV_RUN_CHUNK, LV_WG)), dim3(LV_WG), 0, ctx->stream, sk.keys, sk.perm,
                            (const uint32_t *)gv.weights, g->nnz, (const uint64_t *)ckeys_b.as<uint64_t>(), (uint64_t)runs, spare->w.as<uint32_t>());
-        hipLaunchKernelGGL(k_lv_csr, dim3(cr_grid(std::max<uint64_t>(runs, (uint64_t)n_c + 1u), LV_WG)), dim3(LV_WG), 0, ctx->stream,
-                           (const uint64_t *)ckeys_b.as<uint64_t>(), (uint64_t)runs, n_c, spare->ptr.as<long long>(), spare->ind.as<int32_t>(), (uint32_t *)nullptr);
+        cr_keys_to_csr(ctx, ckeys_b.as<uint64_t>(), runs, n_c, spare->ptr.as<long long>(), spare->ind.as<int32_t>(), nullptr);
         CR_HIP(ctx, hipGetLastError());
         spare->n = n_c, spare->nnz = runs;
         std::swap(g, spare);
         CR_TRY(lv_degrees(ctx, *g, d_st, &state));
         CR_REQUIRE(ctx, state.M == M, CRGPU_EHIP, "%s: the aggregated graph has M = %llu, not %llu", who, (unsigned long long)state.M, (unsigned long long)M);
-        res->aggregate_ms += lv_ms_since(t_agg);
+        res->aggregate_ms += cr_ms_since(t_agg);
     }
     if (res->final_out) CR_TRY(crgpu_memcpy_d2h(ctx, res->final_out, comp_b.p, n * sizeof(int32_t)));
     CR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    res->fit_ms = lv_ms_since(t0);
+    res->fit_ms = cr_ms_since(t0);
     return CRGPU_OK;
 }

@@ -593,7 +593,6 @@ static int mc_run(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const uint32_t *fea
     for (auto &r : im->rows) r.umi_threshold_observed = -1, r.winner = NONE32;
     im->view.n_rows = n_rows, im->view.n_barcodes = V;
     const auto clk = [] { return std::chrono::steady_clock::now(); };
-    const auto ms_since = [](std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); };
     uint32_t *d_flag = ctx->d_scalars + CR_SCALAR_FLAG, flag = 0;
     uint32_t *d_total = ctx->d_scalars + CR_SCALAR_TOTAL;
     // ---- extraction ----
@@ -660,7 +659,7 @@ static int mc_run(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const uint32_t *fea
     hipLaunchKernelGGL(k_mc_rowptr, dim3((n_rows + 256u) / 256u), dim3(256), 0, ctx->stream, keys_col, (uint64_t)n_ent, n_rows, rp_b.as<uint32_t>());
     CR_HIP(ctx, hipGetLastError());
     CR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    im->view.ms_extract = ms_since(t0);
+    im->view.ms_extract = cr_ms_since(t0);
     // ---- histograms ----
     t0 = clk();
     {
@@ -682,7 +681,7 @@ static int mc_run(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const uint32_t *fea
     CR_TRY(crgpu_memcpy_d2h(ctx, rowptr.data(), rp_b.p, rowptr.size() * sizeof(uint32_t)));
     CR_TRY(crgpu_memcpy_d2h(ctx, nd.data(), nd_b.p, nd.size() * sizeof(uint32_t)));
     CR_TRY(crgpu_memcpy_d2h(ctx, total.data(), tot_b.p, total.size() * sizeof(uint64_t)));
-    im->view.ms_histogram = ms_since(t0);
+    im->view.ms_histogram = cr_ms_since(t0);
     // ---- the fit: the rows in four classes (one wave or four, LDS or device memory) ----
     t0 = clk();
     std::vector<uint32_t> cls[4], fit_rows;
@@ -743,7 +742,7 @@ static int mc_run(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const uint32_t *fea
         }
     }
     CR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    im->view.ms_fit = ms_since(t0);
+    im->view.ms_fit = cr_ms_since(t0);
     // ---- predict and assign ----
     t0 = clk();
     const uint32_t n_fit = (uint32_t)fit_rows.size();
@@ -802,7 +801,7 @@ static int mc_run(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const uint32_t *fea
         im->view.n_hist_slots = n_slots;
     }
     CR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    im->view.ms_assign = ms_since(t0);
+    im->view.ms_assign = cr_ms_since(t0);
     im->view.rows = im->rows.data();
     im->view.d_indptr = (const int64_t *)im->d_indptr, im->view.d_columns = (const uint32_t *)im->d_columns;
     im->view.d_features_per_cell = (const uint32_t *)im->d_fpc;

@@ -221,15 +221,9 @@ static int nd_run(crgpu_ctx *ctx, crgpu_counts *c, const crgpu_normalize_depth_a
         CR_TRY(dmalloc(ctx, mask_b, (uint64_t)n_bc * sizeof(uint32_t)));
     }
     uint32_t *kept = kept_b.as<uint32_t>();
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    struct Events {
-        hipEvent_t *e;
-        ~Events() {
-            for (int k = 0; k < 3; k++)
-                if (e[k]) (void)hipEventDestroy(e[k]);
-        }
-    } events{ev};
-    for (int k = 0; k < 3; k++) CR_HIP(ctx, hipEventCreate(&ev[k]));
+    CrEvents<3> events(ctx);
+    hipEvent_t *ev = events.e;
+    CR_REQUIRE(ctx, ev[0] && ev[1] && ev[2], CRGPU_EHIP, "crgpu_normalize_depth_dev: no event");
 
     // 2. draw, 3. sums
     const NdTally ta{K, kept, fclass_b.as<uint8_t>(), mask_b.as<uint32_t>(), L.sh_bc(), n_bc, tab_b.as<uint32_t>(), sums_b.as<unsigned long long>()};

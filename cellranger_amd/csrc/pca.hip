@@ -505,10 +505,6 @@ __global__ __launch_bounds__(PCA_WG) void k_pca_project(const uint64_t *__restri
 }
 
 // ---- host: the preparation --------------------------------------------------------------------------------------------------------------
-static inline double pca_ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 struct PcaPrep {  // a normalised sub-matrix, cells x features, in both orders
     uint64_t N = 0, nnz = 0;
     uint32_t F = 0;
@@ -908,10 +904,10 @@ extern "C" int crgpu_pca_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, uint32_t
         if (a->start) std::copy(a->start, a->start + n_pf, start.begin());
         else CR_TRY(crgpu_legacy_randn(a->seed, n_pf, start.data()));
         CR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        res->prepare_ms = pca_ms_since(t0);
+        res->prepare_ms = cr_ms_since(t0);
         const auto t1 = std::chrono::steady_clock::now();
         CR_TRY(pca_irlb(ctx, P, center, start, nu, wg, ppb, d, v, &res->it, &res->mprod, &res->m_b));
-        res->lanczos_ms = pca_ms_since(t1);
+        res->lanczos_ms = cr_ms_since(t1);
     }
     if (res->d_out) std::copy(d.begin(), d.end(), res->d_out);
     if (res->variance_explained_out)
@@ -952,8 +948,8 @@ extern "C" int crgpu_pca_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, uint32_t
                            fmap_b.as<int32_t>(), v_b.as<double>(), nu, cv_b.as<double>(), out_b.as<double>());
         CR_HIP(ctx, hipGetLastError());
         CR_TRY(crgpu_memcpy_d2h(ctx, res->transformed_out, out_b.p, V * nu * sizeof(double)));
-        res->project_ms = pca_ms_since(t2);
+        res->project_ms = cr_ms_since(t2);
     }
-    res->fit_ms = pca_ms_since(t0);
+    res->fit_ms = cr_ms_since(t0);
     return CRGPU_OK;
 }

@@ -237,7 +237,7 @@ extern "C" int crgpu_rpu_gmm_dev(crgpu_ctx *ctx, const double *values, const uin
         CR_HIP(ctx, hipGetLastError());
     }
     CR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    res->fit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    res->fit_ms = cr_ms_since(t0);
     std::vector<double> h_out((size_t)n_starts * GMM_OUT);
     std::vector<uint32_t> h_it(n_starts);
     CR_TRY(crgpu_memcpy_d2h(ctx, h_out.data(), out_b.p, h_out.size() * sizeof(double)));

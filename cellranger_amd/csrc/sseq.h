@@ -346,10 +346,6 @@ __global__ __launch_bounds__(SQ_WG) void k_sq_bh_close(const uint64_t *__restric
 }
 
 // ---- the entry points ----------------------------------------------------------------------------------------------------------------------
-static inline double sq_ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 extern "C" void crgpu_sseq_params_free(crgpu_ctx *ctx, crgpu_sseq_params *p) {
     if (!p) return;
     if (ctx) {
@@ -527,7 +523,7 @@ extern "C" int crgpu_sseq_diffexp_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m,
     }
     std::vector<uint64_t> xin(KG);
     CR_TRY(crgpu_memcpy_d2h(ctx, xin.data(), sums_b.p, KG * sizeof(uint64_t)));
-    res->ms_sums = sq_ms_since(t0);
+    res->ms_sums = cr_ms_since(t0);
 
     // per cluster the sums of the size factors, in cell order; per gene the total
     std::vector<double> s_a(K, 0.0), s_b(K, 0.0);
@@ -599,7 +595,7 @@ extern "C" int crgpu_sseq_diffexp_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m,
         CR_HIP(ctx, hipGetLastError());
     }
     CR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    res->ms_exact = sq_ms_since(t0);
+    res->ms_exact = cr_ms_since(t0);
 
     t0 = std::chrono::steady_clock::now();
     if (!t_big.empty()) {
@@ -609,7 +605,7 @@ extern "C" int crgpu_sseq_diffexp_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m,
         CR_HIP(ctx, hipGetLastError());
     }
     CR_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    res->ms_asymptotic = sq_ms_since(t0);
+    res->ms_asymptotic = cr_ms_since(t0);
 
     // Benjamini-Hochberg over the used genes of every cluster
     t0 = std::chrono::steady_clock::now();
@@ -639,7 +635,7 @@ extern "C" int crgpu_sseq_diffexp_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m,
         CR_HIP(ctx, hipGetLastError());
         CR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
-    res->ms_bh = sq_ms_since(t0);
+    res->ms_bh = cr_ms_since(t0);
 
     // what the caller asked for
     if (res->p_values_out) CR_TRY(crgpu_memcpy_d2h(ctx, res->p_values_out, p_b.p, KG * sizeof(double)));

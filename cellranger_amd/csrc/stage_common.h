@@ -3,6 +3,9 @@
 // stream compaction, the barcode segments of the molecule table, the search in an ascending array, the checks of a caller's column
 // or rank list, numpy's percentile, and the few host functions one of these units defines for the others.  A kernel defined here is
 // a template: the header is part of several units.
+// graph_common.h builds on this header for the stages on the kNN graph (tsne.hip, umap.hip, louvain.hip): the pair keys of a neighbour
+// list, the run-head flag of equal keys, the sort and the merge of the runs, the CSR from the merged keys, the ordered column sum, and
+// the host checks of a caller's neighbour lists and CSR.
 #pragma once
 
 #include <cmath>

@@ -457,19 +457,9 @@ static int ss_run(crgpu_ctx *ctx, crgpu_counts *c, const crgpu_subsample_args *a
     CR_TRY(dmalloc(ctx, out_b, (uint64_t)nb_max * words_per_task * sizeof(unsigned long long)));
     CR_TRY(dmalloc(ctx, thr_b, (uint64_t)CRGPU_MAX_LIB * SS_MAX_BATCH * sizeof(unsigned long long)));
     CR_TRY(dmalloc(ctx, type_b, SS_MAX_BATCH));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    CR_HIP(ctx, hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) {
-        (void)hipEventDestroy(e0);
-        return cr_fail(ctx, CRGPU_EHIP, "crgpu_subsample_dev: no event");
-    }
-    struct Events {
-        hipEvent_t a, b;
-        ~Events() {
-            (void)hipEventDestroy(a);
-            (void)hipEventDestroy(b);
-        }
-    } events{e0, e1};
+    CrEvents<2> events(ctx);
+    const hipEvent_t e0 = events.e[0], e1 = events.e[1];
+    CR_REQUIRE(ctx, e0 && e1, CRGPU_EHIP, "crgpu_subsample_dev: no event");
     std::vector<unsigned long long> h_thr((size_t)CRGPU_MAX_LIB * SS_MAX_BATCH), h_tot, h_tfd;
     std::vector<uint8_t> h_type(SS_MAX_BATCH);
     double draw_ms = 0.0;

@@ -6,10 +6,11 @@
 //
 // Launch structure.
 //   k_tsne_search      a lane per row: the bisection on beta over the row's k squared distances, sums left to right over the ranks
-//   k_tsne_keys        two keys per neighbour pair, i * n + j and j * n + i, the pair's number as payload; one radix sort
-//   compaction         the first of a run of equal keys is emitted: (value + the other direction's or 0) / 2; k_tsne_indptr by search
-//   k_tsne_colparts / k_tsne_colfinal   column sums over partials of 256 rows, left to right, then the partials ascending (one sum order
-//                      for the total of P, Z, the column means of Y and the cost)
+//   k_pair_keys        (graph_common.h) two keys per neighbour pair, i * n + j and j * n + i, the pair's number as payload; one radix sort
+//   compaction         the first of a run of equal keys is emitted: (value + the other direction's or 0) / 2; k_keys_to_csr
+//                      (graph_common.h) by search
+//   k_colparts / k_colfinal   (graph_common.h) column sums over partials of 256 rows, left to right, then the partials ascending (one
+//                      sum order for the total of P, Z, the column means of Y and the cost)
 //   k_tsne_repulse     one workgroup per (row tile, candidate chunk of CRGPU_TSNE_CAND_CHUNK rows), a lane a row with its coordinates in
 //                      registers; candidate tiles stream through LDS, every lane reads the same address; no norm expansion; the chunk's
 //                      partial (z, neg[dims]) goes to a slab with plain stores
@@ -27,10 +28,9 @@
 #include <cmath>
 #include <vector>
 
-#include "stage_common.h"
+#include "graph_common.h"
 
 #define TSNE_WG 256u
-#define TSNE_PART_ROWS 256u        // rows of a partial of the column sums: fixed, no seam moves it
 #define TSNE_MAX_STEPS 200u        // steps of the search at the most
 #define TSNE_TOL 1e-5
 #define TSNE_MAX_CAND_TILE 1024u   // candidates of an LDS tile at the most: 24 KiB at 3 dimensions
@@ -72,19 +72,6 @@ __global__ __launch_bounds__(TSNE_WG) void k_tsne_search(const double *__restric
 }
 
 // ---- the symmetrised P ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(TSNE_WG) void k_tsne_keys(const int32_t *__restrict__ nn, uint32_t n, uint32_t k, uint64_t *__restrict__ keys,
-                                                       uint32_t *__restrict__ perm) {
-    const uint64_t total = (uint64_t)n * k;
-    for (uint64_t e = (uint64_t)blockIdx.x * TSNE_WG + threadIdx.x; e < total; e += (uint64_t)gridDim.x * TSNE_WG) {
-        const uint64_t i = e / k, j = (uint64_t)(uint32_t)nn[e];
-        keys[2 * e] = i * n + j, keys[2 * e + 1] = j * n + i;
-        perm[2 * e] = (uint32_t)(2 * e), perm[2 * e + 1] = (uint32_t)(2 * e + 1);
-    }
-}
-struct TsneHeadFlag {  // the first of a run of equal keys
-    const uint64_t *keys;
-    __device__ __forceinline__ bool operator()(uint64_t i) const { return (i == 0) | (keys[i] != keys[i ? i - 1 : 0]); }
-};
 // A key occurs once per direction at the most (a row's neighbours are distinct), so a run has one or two members and the order of the
 // two does not reach the sum.
 struct TsneEmitMerged {
@@ -104,36 +91,9 @@ struct TsneEmitMerged {
         values[o] = (a + b) / 2.0;
     }
 };
-__global__ __launch_bounds__(TSNE_WG) void k_tsne_indptr(const uint64_t *__restrict__ ckeys, uint64_t nnz, uint32_t n, long long *__restrict__ indptr,
-                                                         int32_t *__restrict__ indices) {
-    const uint64_t stride = (uint64_t)gridDim.x * TSNE_WG, t0 = (uint64_t)blockIdx.x * TSNE_WG + threadIdx.x;
-    for (uint64_t r = t0; r <= n; r += stride) indptr[r] = (long long)cr_lower_bound(ckeys, nnz, r * (uint64_t)n);
-    for (uint64_t e = t0; e < nnz; e += stride) indices[e] = (int32_t)(ckeys[e] % n);
-}
 __global__ __launch_bounds__(TSNE_WG) void k_tsne_divide(double *__restrict__ v, uint64_t nnz, const double *__restrict__ total) {
     const double t = total[0];
     for (uint64_t e = (uint64_t)blockIdx.x * TSNE_WG + threadIdx.x; e < nnz; e += (uint64_t)gridDim.x * TSNE_WG) v[e] = v[e] / t;
-}
-
-// ---- the column sums -----------------------------------------------------------------------------------------------------------------
-// parts[part * ncols + c] = a[r * ld + c] over the rows r of the partial, left to right from 0.0
-__global__ __launch_bounds__(TSNE_WG) void k_tsne_colparts(const double *__restrict__ a, uint64_t n, uint32_t ld, uint32_t ncols, uint64_t n_parts,
-                                                           double *__restrict__ parts) {
-    const uint64_t total = n_parts * ncols;
-    for (uint64_t e = (uint64_t)blockIdx.x * TSNE_WG + threadIdx.x; e < total; e += (uint64_t)gridDim.x * TSNE_WG) {
-        const uint64_t part = e / ncols, r0 = part * TSNE_PART_ROWS, r1 = r0 + TSNE_PART_ROWS < n ? r0 + TSNE_PART_ROWS : n;
-        const uint32_t c = (uint32_t)(e % ncols);
-        double s = 0.0;
-        for (uint64_t r = r0; r < r1; r++) s += a[r * ld + c];
-        parts[e] = s;
-    }
-}
-__global__ __launch_bounds__(64) void k_tsne_colfinal(const double *__restrict__ parts, uint64_t n_parts, uint32_t ncols, double *__restrict__ out) {
-    const uint32_t c = threadIdx.x;
-    if (c >= ncols) return;
-    double s = 0.0;
-    for (uint64_t p = 0; p < n_parts; p++) s += parts[p * ncols + c];
-    out[c] = s;
 }
 
 // ---- the gradient --------------------------------------------------------------------------------------------------------------------
@@ -297,21 +257,6 @@ __global__ __launch_bounds__(TSNE_WG) void k_tsne_kl(const long long *__restrict
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------------
-struct TsneEvents {  // four events of the context's pool, given back at scope exit
-    crgpu_ctx *ctx;
-    hipEvent_t e[4];
-    explicit TsneEvents(crgpu_ctx *c) : ctx(c) {
-        for (int i = 0; i < 4; i++) e[i] = cr_take_event(c);
-    }
-    ~TsneEvents() {
-        for (int i = 0; i < 4; i++)
-            if (e[i]) ctx->event_pool.push_back(e[i]);
-    }
-};
-static double tsne_ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // the seams of a call, checked
 struct TsneSeams {
     uint32_t row_tile, cand_tile, slab_rows, wave_row_len;
@@ -328,33 +273,15 @@ static int tsne_seams(crgpu_ctx *ctx, const char *who, const crgpu_tsne_args *a,
     return CRGPU_OK;
 }
 
-// indptr, indices, values of a caller: 0 at the start, rows that do not shrink, fewer than 2^32 entries, indices inside the rows and
-// strictly ascending within a row, finite values
-static int tsne_check_csr(crgpu_ctx *ctx, const char *who, const int64_t *indptr, const int32_t *indices, const double *values, uint64_t n, uint64_t *nnz_out) {
-    CR_REQUIRE(ctx, indptr[0] == 0, CRGPU_EINVAL, "%s: indptr[0] = %lld", who, (long long)indptr[0]);
-    for (uint64_t i = 0; i < n; i++)
-        CR_REQUIRE(ctx, indptr[i + 1] >= indptr[i] && indptr[i + 1] < (1ll << 32), CRGPU_EINVAL, "%s: indptr[%llu] = %lld after %lld", who,
-                   (unsigned long long)(i + 1), (long long)indptr[i + 1], (long long)indptr[i]);
-    for (uint64_t i = 0; i < n; i++)
-        for (int64_t e = indptr[i]; e < indptr[i + 1]; e++) {
-            CR_REQUIRE(ctx, indices[e] >= 0 && (uint64_t)indices[e] < n, CRGPU_EINVAL, "%s: indices[%lld] = %d outside the rows", who, (long long)e, indices[e]);
-            CR_REQUIRE(ctx, e == indptr[i] || indices[e] > indices[e - 1], CRGPU_EINVAL, "%s: the indices of row %llu must be strictly ascending", who,
-                       (unsigned long long)i);
-            CR_REQUIRE(ctx, std::isfinite(values[e]), CRGPU_EINVAL, "%s: values[%lld] is not finite", who, (long long)e);
-        }
-    *nnz_out = (uint64_t)indptr[n];
-    return CRGPU_OK;
-}
 static int tsne_check_finite(crgpu_ctx *ctx, const char *who, const char *what, const double *v, uint64_t count) {
     for (uint64_t e = 0; e < count; e++) CR_REQUIRE(ctx, std::isfinite(v[e]), CRGPU_EINVAL, "%s: %s[%llu] is not finite", who, what, (unsigned long long)e);
     return CRGPU_OK;
 }
-
-// the column sums of a (n rows of ld doubles, the first ncols of each) into out (device, ncols doubles); parts: room for the partials
-static void tsne_colsums(crgpu_ctx *ctx, const double *a, uint64_t n, uint32_t ld, uint32_t ncols, double *parts, double *out) {
-    const uint64_t n_parts = (n + TSNE_PART_ROWS - 1u) / TSNE_PART_ROWS;
-    hipLaunchKernelGGL(k_tsne_colparts, dim3(cr_grid(n_parts * ncols, TSNE_WG)), dim3(TSNE_WG), 0, ctx->stream, a, n, ld, ncols, n_parts, parts);
-    hipLaunchKernelGGL(k_tsne_colfinal, dim3(1), dim3(64), 0, ctx->stream, (const double *)parts, n_parts, ncols, out);
+// indptr, indices, values of a caller: the structure (fewer than 2^32 entries, indices strictly ascending within a row), finite values
+static int tsne_check_csr(crgpu_ctx *ctx, const char *who, const int64_t *indptr, const int32_t *indices, const double *values, uint64_t n, uint64_t *nnz_out) {
+    CR_TRY(cr_check_csr(ctx, who, indptr, indices, n, 32u, true));
+    *nnz_out = (uint64_t)indptr[n];
+    return tsne_check_finite(ctx, who, "values", values, *nnz_out);
 }
 
 // What the gradient and the loop share: P and Y on the device and the buffers of an iteration
@@ -370,7 +297,7 @@ struct TsneState {
 static int tsne_state(crgpu_ctx *ctx, TsneState &S, const int64_t *indptr, const int32_t *indices, const double *values, const double *y, uint64_t n,
                       uint32_t dims, uint64_t nnz, const TsneSeams &seams) {
     S.n = (uint32_t)n, S.dims = dims, S.nnz = nnz, S.seams = seams, S.n_chunks = (uint32_t)((n + CRGPU_TSNE_CAND_CHUNK - 1u) / CRGPU_TSNE_CAND_CHUNK);
-    const uint64_t yb = n * dims * sizeof(double), n_parts = (n + TSNE_PART_ROWS - 1u) / TSNE_PART_ROWS;
+    const uint64_t yb = n * dims * sizeof(double), n_parts = (n + GRAPH_PART_ROWS - 1u) / GRAPH_PART_ROWS;
     CR_TRY(dmalloc(ctx, S.indptr, (n + 1) * sizeof(int64_t)));
     CR_TRY(dmalloc(ctx, S.indices, std::max<uint64_t>(1, nnz) * sizeof(int32_t)));
     CR_TRY(dmalloc(ctx, S.values, std::max<uint64_t>(1, nnz) * sizeof(double)));
@@ -406,7 +333,7 @@ static int tsne_repulsion(crgpu_ctx *ctx, TsneState &S, hipEvent_t *ev) {
                            S.n_chunks, DIMS + 1u, S.rep.as<double>());
     }
     if (ev) CR_HIP(ctx, hipEventRecord(ev[1], ctx->stream));
-    tsne_colsums(ctx, S.rep.as<double>(), S.n, DIMS + 1u, 1u, S.parts.as<double>(), S.zq());
+    cr_colsums(ctx, S.rep.as<double>(), S.n, DIMS + 1u, 1u, S.parts.as<double>(), S.zq());
     CR_HIP(ctx, hipGetLastError());
     return CRGPU_OK;
 }
@@ -427,7 +354,7 @@ template <uint32_t DIMS>
 static int tsne_cost(crgpu_ctx *ctx, TsneState &S) {
     hipLaunchKernelGGL(k_tsne_kl<DIMS>, dim3(cr_grid(S.n, TSNE_WG)), dim3(TSNE_WG), 0, ctx->stream, S.indptr.as<long long>(), S.indices.as<int32_t>(),
                        S.values.as<double>(), S.Y.as<double>(), S.zq(), S.n, S.rowkl.as<double>());
-    tsne_colsums(ctx, S.rowkl.as<double>(), S.n, 1u, 1u, S.parts.as<double>(), S.klq());
+    cr_colsums(ctx, S.rowkl.as<double>(), S.n, 1u, 1u, S.parts.as<double>(), S.klq());
     CR_HIP(ctx, hipGetLastError());
     return CRGPU_OK;
 }
@@ -446,7 +373,7 @@ static int tsne_loop(crgpu_ctx *ctx, TsneState &S, const crgpu_tsne_args *a, dou
         CR_TRY(tsne_repulsion<DIMS>(ctx, S, it + 1u == a->n_iters ? ev + 2 : nullptr));
         TsneStep st = {iter < a->stop_lying_iter ? TSNE_EXAGGERATION : 1.0, iter < a->mom_switch_iter ? 0.5 : 0.8, eta, S.n, S.seams.wave_row_len, 1u};
         CR_TRY(tsne_attraction<DIMS>(ctx, S, st));
-        tsne_colsums(ctx, S.Ynew.as<double>(), S.n, DIMS, DIMS, S.parts.as<double>(), S.sums());
+        cr_colsums(ctx, S.Ynew.as<double>(), S.n, DIMS, DIMS, S.parts.as<double>(), S.sums());
         hipLaunchKernelGGL(k_tsne_centre, dim3(cr_grid((uint64_t)S.n * DIMS, TSNE_WG)), dim3(TSNE_WG), 0, ctx->stream, S.Ynew.as<double>(), (uint64_t)S.n, DIMS,
                            S.sums(), S.Y.as<double>());
     }
@@ -481,19 +408,7 @@ extern "C" int crgpu_tsne_affinities_dev(crgpu_ctx *ctx, const int32_t *nn_indic
     CR_REQUIRE(ctx, std::isfinite(perplexity) && perplexity >= 1.0, CRGPU_EINVAL, "%s: a perplexity of %g, finite and at least 1", who, perplexity);
     CR_REQUIRE(ctx, a->reserved == 0u, CRGPU_EINVAL, "%s: reserved is 0", who);
     CR_REQUIRE(ctx, 2 * n * k < (1ull << 32), CRGPU_ERANGE, "%s: %llu neighbour pairs, fewer than 2^31", who, (unsigned long long)(n * k));
-    {
-        std::vector<uint32_t> stamp(n, 0u);
-        for (uint64_t i = 0; i < n; i++)
-            for (uint32_t m = 0; m < k; m++) {
-                const int32_t j = nn_indices[i * k + m];
-                const double d = nn_distances[i * k + m];
-                CR_REQUIRE(ctx, j >= 0 && (uint64_t)j < n, CRGPU_EINVAL, "%s: nn_indices[%llu, %u] = %d outside the rows", who, (unsigned long long)i, m, j);
-                CR_REQUIRE(ctx, stamp[j] != (uint32_t)i + 1u, CRGPU_EINVAL, "%s: row %llu names row %d twice", who, (unsigned long long)i, j);
-                stamp[j] = (uint32_t)i + 1u;
-                CR_REQUIRE(ctx, std::isfinite(d) && d >= 0.0, CRGPU_EINVAL, "%s: nn_distances[%llu, %u] = %g, finite and not negative", who,
-                           (unsigned long long)i, m, d);
-            }
-    }
+    CR_TRY(cr_check_knn_lists(ctx, who, nn_indices, nn_distances, n, k));
     const auto t0 = std::chrono::steady_clock::now();
     tsne_clear(res);
     const uint64_t nk = n * k, n2 = 2 * nk;
@@ -512,36 +427,28 @@ extern "C" int crgpu_tsne_affinities_dev(crgpu_ctx *ctx, const int32_t *nn_indic
     CR_TRY(dmalloc(ctx, ind_b, n2 * sizeof(int32_t)));
     CR_TRY(dmalloc(ctx, ptr_b, (n + 1) * sizeof(int64_t)));
     CR_TRY(dmalloc(ctx, block_b, 4100 * sizeof(uint32_t)));
-    CR_TRY(dmalloc(ctx, parts_b, ((n2 + TSNE_PART_ROWS - 1u) / TSNE_PART_ROWS) * sizeof(double)));
+    CR_TRY(dmalloc(ctx, parts_b, ((n2 + GRAPH_PART_ROWS - 1u) / GRAPH_PART_ROWS) * sizeof(double)));
     CR_TRY(dmalloc(ctx, scal_b, 2 * sizeof(double)));
     CR_TRY(crgpu_memcpy_h2d(ctx, nn_b.p, nn_indices, nk * sizeof(int32_t)));
     CR_TRY(crgpu_memcpy_h2d(ctx, dist_b.p, nn_distances, nk * sizeof(double)));
 
-    TsneEvents events(ctx);
+    CrEvents<4> events(ctx);
     hipEvent_t *ev = events.e;
     CR_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
     hipLaunchKernelGGL(k_tsne_search, dim3((uint32_t)((n + TSNE_WG - 1u) / TSNE_WG)), dim3(TSNE_WG), 0, ctx->stream, dist_b.as<double>(), (uint32_t)n, k,
                        std::log(perplexity), beta_b.as<double>(), steps_b.as<uint32_t>(), cond_b.as<double>());
     CR_HIP(ctx, hipGetLastError());
     CR_HIP(ctx, hipEventRecord(ev[1], ctx->stream));
-    hipLaunchKernelGGL(k_tsne_keys, dim3(cr_grid(nk, TSNE_WG)), dim3(TSNE_WG), 0, ctx->stream, nn_b.as<int32_t>(), (uint32_t)n, k, keys_b.as<uint64_t>(),
-                       perm_b.as<uint32_t>());
+    cr_pair_keys(ctx, nn_b.as<int32_t>(), (uint32_t)n, k, keys_b.as<uint64_t>(), perm_b.as<uint32_t>());
     CR_HIP(ctx, hipGetLastError());
-    bool in_tmp = false;
-    CR_TRY(cr_radix_sort_u64(ctx, keys_b.as<uint64_t>(), keyt_b.as<uint64_t>(), perm_b.as<uint32_t>(), permt_b.as<uint32_t>(), n2, 0,
-                             std::max(1u, cr_ceil_log2(n * n)), &in_tmp));
-    const uint64_t *d_keys = in_tmp ? keyt_b.as<uint64_t>() : keys_b.as<uint64_t>();
-    const uint32_t *d_perm = in_tmp ? permt_b.as<uint32_t>() : perm_b.as<uint32_t>();
-    uint32_t *d_total = block_b.as<uint32_t>() + 4096;
-    CR_TRY(compact(ctx, TsneHeadFlag{d_keys}, TsneEmitMerged{d_keys, d_perm, cond_b.as<double>(), n2, ckeys_b.as<uint64_t>(), val_b.as<double>()}, n2,
-                   block_b.as<uint32_t>(), d_total));
+    SortedKeys sk;
+    CR_TRY(cr_sort_keys(ctx, keys_b.as<uint64_t>(), keyt_b.as<uint64_t>(), perm_b.as<uint32_t>(), permt_b.as<uint32_t>(), n2, cr_ceil_log2(n * n), &sk));
     uint32_t nnz32 = 0;
-    CR_TRY(read_u32(ctx, d_total, &nnz32));
+    CR_TRY(cr_merge_runs(ctx, sk.keys, TsneEmitMerged{sk.keys, sk.perm, cond_b.as<double>(), n2, ckeys_b.as<uint64_t>(), val_b.as<double>()}, n2,
+                         block_b.as<uint32_t>(), nk, n2, who, "merged entries", &nnz32));
     const uint64_t nnz = nnz32;
-    CR_REQUIRE(ctx, nnz >= nk && nnz <= n2, CRGPU_EHIP, "%s: %llu merged entries of %llu pairs", who, (unsigned long long)nnz, (unsigned long long)nk);
-    hipLaunchKernelGGL(k_tsne_indptr, dim3(cr_grid(std::max<uint64_t>(nnz, n + 1), TSNE_WG)), dim3(TSNE_WG), 0, ctx->stream, ckeys_b.as<uint64_t>(), nnz,
-                       (uint32_t)n, ptr_b.as<long long>(), ind_b.as<int32_t>());
-    tsne_colsums(ctx, val_b.as<double>(), nnz, 1u, 1u, parts_b.as<double>(), scal_b.as<double>());
+    cr_keys_to_csr(ctx, ckeys_b.as<uint64_t>(), nnz, (uint32_t)n, ptr_b.as<long long>(), ind_b.as<int32_t>(), nullptr);
+    cr_colsums(ctx, val_b.as<double>(), nnz, 1u, 1u, parts_b.as<double>(), scal_b.as<double>());
     hipLaunchKernelGGL(k_tsne_divide, dim3(cr_grid(nnz, TSNE_WG)), dim3(TSNE_WG), 0, ctx->stream, val_b.as<double>(), nnz, scal_b.as<double>());
     CR_HIP(ctx, hipGetLastError());
     CR_HIP(ctx, hipEventRecord(ev[2], ctx->stream));
@@ -561,7 +468,7 @@ extern "C" int crgpu_tsne_affinities_dev(crgpu_ctx *ctx, const int32_t *nn_indic
     CR_HIP(ctx, hipEventElapsedTime(&ms_b, ev[1], ev[2]));
     res->search_ms = ms_a, res->csr_ms = ms_b, res->nnz = nnz;
     res->max_steps = *std::max_element(steps.begin(), steps.end());
-    res->fit_ms = tsne_ms_since(t0);
+    res->fit_ms = cr_ms_since(t0);
     return CRGPU_OK;
 }
 
@@ -588,7 +495,7 @@ extern "C" int crgpu_tsne_gradient_dev(crgpu_ctx *ctx, const int64_t *indptr, co
     CR_TRY(crgpu_memcpy_d2h(ctx, &res->kl, S.klq(), sizeof(double)));
     tsne_report(res, S);
     res->pairs_evaluated = n * (n - 1);
-    res->fit_ms = tsne_ms_since(t0);
+    res->fit_ms = cr_ms_since(t0);
     return CRGPU_OK;
 }
 
@@ -617,7 +524,7 @@ extern "C" int crgpu_tsne_dev(crgpu_ctx *ctx, const int64_t *indptr, const int32
     const uint64_t yb = n * dims * sizeof(double);
     CR_TRY(crgpu_memcpy_h2d(ctx, S.uY.p, uY, yb));
     CR_TRY(crgpu_memcpy_h2d(ctx, S.gains.p, gains, yb));
-    TsneEvents events(ctx);
+    CrEvents<4> events(ctx);
     CR_TRY(dims == 2u ? tsne_loop<2>(ctx, S, a, eta, events.e) : tsne_loop<3>(ctx, S, a, eta, events.e));
     CR_TRY(crgpu_memcpy_d2h(ctx, y, S.Y.p, yb));
     CR_TRY(crgpu_memcpy_d2h(ctx, uY, S.uY.p, yb));
@@ -634,6 +541,6 @@ extern "C" int crgpu_tsne_dev(crgpu_ctx *ctx, const int64_t *indptr, const int32
     }
     tsne_report(res, S);
     res->pairs_evaluated = n * (n - 1) * ((uint64_t)a->n_iters + 1u);
-    res->fit_ms = tsne_ms_since(t0);
+    res->fit_ms = cr_ms_since(t0);
     return CRGPU_OK;
 }

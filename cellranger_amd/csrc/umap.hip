@@ -7,12 +7,13 @@
 //
 // Launch structure.
 //   k_umap_rows        a lane per row: the row's distance sum left to right over the ranks, rho = the first distance > 0
-//   k_umap_parts / k_umap_final   the total of the row sums over partials of 256 rows, left to right, then the partials ascending
+//   k_colparts / k_colfinal   (graph_common.h) the total of the row sums over partials of 256 rows, left to right, then the partials
+//                      ascending
 //   k_umap_search      a lane per row: the search for sigma over the row's k distances, the floor, the k memberships
-//   k_umap_keys        two keys per neighbour pair, i * n + j and j * n + i, the pair's number as payload; one radix sort
+//   k_pair_keys        (graph_common.h) two keys per neighbour pair, i * n + j and j * n + i, the pair's number as payload; one radix sort
 //   compaction         the first of a run of equal keys is emitted: (a + b) - a * b with the other direction's membership or 0
 //   k_umap_maxparts / k_umap_maxfinal   wmax and the prune threshold wmax / n_epochs (a maximum has no order)
-//   compaction         the entries at or above the threshold; k_umap_indptr by search
+//   compaction         the entries at or above the threshold; k_keys_to_csr (graph_common.h) by search
 //   k_umap_schedule    epoch 0: eps = wmax / w, the two states start at eps and eps / rate
 //   k_umap_epoch       one epoch: walks a row's CSR entries left to right, adds the terms of the active ones (the attraction, then the
 //                      negative samples in ascending order) and writes y + alpha * delta into a second Y; a lane per row below
@@ -27,11 +28,10 @@
 #include <cmath>
 #include <vector>
 
+#include "graph_common.h"
 #include "philox.h"
-#include "stage_common.h"
 
 #define UMAP_WG 256u
-#define UMAP_PART_ROWS 256u   // rows of a partial of the distance total: fixed, no seam moves it
 #define UMAP_MAX_STEPS 64u    // steps of the search at the most
 #define UMAP_TOL 1e-5
 #define UMAP_FLOOR 1e-3       // umap-learn's MIN_K_DIST_SCALE
@@ -49,21 +49,6 @@ __global__ __launch_bounds__(UMAP_WG) void k_umap_rows(const double *__restrict_
         rho = (rho == 0.0 && d[m] > 0.0) ? d[m] : rho;  // the first distance > 0 by rank
     }
     rho_out[i] = rho, rowsum[i] = s;
-}
-// parts[p] = a[r] over the rows r of the partial, left to right from 0.0; out[0] = the partials ascending
-__global__ __launch_bounds__(UMAP_WG) void k_umap_parts(const double *__restrict__ a, uint64_t n, uint64_t n_parts, double *__restrict__ parts) {
-    for (uint64_t p = (uint64_t)blockIdx.x * UMAP_WG + threadIdx.x; p < n_parts; p += (uint64_t)gridDim.x * UMAP_WG) {
-        const uint64_t r0 = p * UMAP_PART_ROWS, r1 = r0 + UMAP_PART_ROWS < n ? r0 + UMAP_PART_ROWS : n;
-        double s = 0.0;
-        for (uint64_t r = r0; r < r1; r++) s += a[r];
-        parts[p] = s;
-    }
-}
-__global__ __launch_bounds__(64) void k_umap_final(const double *__restrict__ parts, uint64_t n_parts, double *__restrict__ out) {
-    if (threadIdx.x) return;
-    double s = 0.0;
-    for (uint64_t p = 0; p < n_parts; p++) s += parts[p];
-    out[0] = s;
 }
 // sigma_out[i] = max(the search's mid, 1e-3 * m), steps_out[i] = evaluations of psum, memb[i * k + m] = the membership of rank m.
 // den_row = k + 1, den_all = n (k + 1), both exact in f64
@@ -103,19 +88,6 @@ __global__ __launch_bounds__(UMAP_WG) void k_umap_search(const double *__restric
     }
 }
 
-__global__ __launch_bounds__(UMAP_WG) void k_umap_keys(const int32_t *__restrict__ nn, uint32_t n, uint32_t k, uint64_t *__restrict__ keys,
-                                                       uint32_t *__restrict__ perm) {
-    const uint64_t total = (uint64_t)n * k;
-    for (uint64_t e = (uint64_t)blockIdx.x * UMAP_WG + threadIdx.x; e < total; e += (uint64_t)gridDim.x * UMAP_WG) {
-        const uint64_t i = e / k, j = (uint64_t)(uint32_t)nn[e];
-        keys[2 * e] = i * n + j, keys[2 * e + 1] = j * n + i;
-        perm[2 * e] = (uint32_t)(2 * e), perm[2 * e + 1] = (uint32_t)(2 * e + 1);
-    }
-}
-struct UmapHeadFlag {  // the first of a run of equal keys
-    const uint64_t *keys;
-    __device__ __forceinline__ bool operator()(uint64_t i) const { return (i == 0) | (keys[i] != keys[i ? i - 1 : 0]); }
-};
 // A key occurs once per direction at the most (a row's neighbours are distinct), so a run has one or two members; (a + b) - a * b is
 // commutative, so the order of the two does not reach the value and (i, j) and (j, i) carry the same bits.
 struct UmapEmitUnion {
@@ -168,12 +140,6 @@ struct UmapEmitKept {
     __device__ __forceinline__ Pre pre(uint64_t) const { return Pre(); }
     __device__ __forceinline__ void operator()(uint64_t i, uint32_t o, Pre) const { keys_out[o] = ckeys[i], values_out[o] = values[i]; }
 };
-__global__ __launch_bounds__(UMAP_WG) void k_umap_indptr(const uint64_t *__restrict__ ckeys, uint64_t nnz, uint32_t n, long long *__restrict__ indptr,
-                                                         int32_t *__restrict__ indices) {
-    const uint64_t stride = (uint64_t)gridDim.x * UMAP_WG, t0 = (uint64_t)blockIdx.x * UMAP_WG + threadIdx.x;
-    for (uint64_t r = t0; r <= n; r += stride) indptr[r] = (long long)cr_lower_bound(ckeys, nnz, r * (uint64_t)n);
-    for (uint64_t e = t0; e < nnz; e += stride) indices[e] = (int32_t)(ckeys[e] % n);
-}
 
 // ---- the epochs ----------------------------------------------------------------------------------------------------------------------
 struct UmapStep {
@@ -310,20 +276,6 @@ __global__ __launch_bounds__(UMAP_WG) void k_umap_epoch(const long long *__restr
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------------
-struct UmapEvents {  // three events of the context's pool, given back at scope exit
-    crgpu_ctx *ctx;
-    hipEvent_t e[3];
-    explicit UmapEvents(crgpu_ctx *c) : ctx(c) {
-        for (int i = 0; i < 3; i++) e[i] = cr_take_event(c);
-    }
-    ~UmapEvents() {
-        for (int i = 0; i < 3; i++)
-            if (e[i]) ctx->event_pool.push_back(e[i]);
-    }
-};
-static double umap_ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
 static void umap_clear(crgpu_umap_result *r) {
     r->wmax = r->fit_ms = r->search_ms = r->csr_ms = r->loop_ms = 0.0;
     r->nnz = r->n_active = r->n_negative = 0;
@@ -400,22 +352,10 @@ extern "C" int crgpu_umap_graph_dev(crgpu_ctx *ctx, const int32_t *nn_indices, c
                (unsigned long long)n);
     CR_REQUIRE(ctx, n_epochs >= 1, CRGPU_EINVAL, "%s: %u epochs, at least 1", who, n_epochs);
     CR_REQUIRE(ctx, 2 * n * k < (1ull << 32), CRGPU_ERANGE, "%s: %llu neighbour pairs, fewer than 2^31", who, (unsigned long long)(n * k));
-    {
-        std::vector<uint32_t> stamp(n, 0u);
-        for (uint64_t i = 0; i < n; i++)
-            for (uint32_t m = 0; m < k; m++) {
-                const int32_t j = nn_indices[i * k + m];
-                const double d = nn_distances[i * k + m];
-                CR_REQUIRE(ctx, j >= 0 && (uint64_t)j < n, CRGPU_EINVAL, "%s: nn_indices[%llu, %u] = %d outside the rows", who, (unsigned long long)i, m, j);
-                CR_REQUIRE(ctx, stamp[j] != (uint32_t)i + 1u, CRGPU_EINVAL, "%s: row %llu names row %d twice", who, (unsigned long long)i, j);
-                stamp[j] = (uint32_t)i + 1u;
-                CR_REQUIRE(ctx, std::isfinite(d) && d >= 0.0, CRGPU_EINVAL, "%s: nn_distances[%llu, %u] = %g, finite and not negative", who,
-                           (unsigned long long)i, m, d);
-            }
-    }
+    CR_TRY(cr_check_knn_lists(ctx, who, nn_indices, nn_distances, n, k));
     const auto t0 = std::chrono::steady_clock::now();
     umap_clear(res);
-    const uint64_t nk = n * k, n2 = 2 * nk, n_parts = (n + UMAP_PART_ROWS - 1u) / UMAP_PART_ROWS;
+    const uint64_t nk = n * k, n2 = 2 * nk, n_parts = (n + GRAPH_PART_ROWS - 1u) / GRAPH_PART_ROWS;
     const uint32_t max_blocks = 1024u;
     DevBuf nn_b, dist_b, rho_b, rowsum_b, sigma_b, steps_b, memb_b, keys_b, keyt_b, perm_b, permt_b, ckeys_b, val_b, kept_b, ind_b, ptr_b, block_b, parts_b, scal_b;
     CR_TRY(dmalloc(ctx, nn_b, nk * sizeof(int32_t)));
@@ -441,47 +381,39 @@ extern "C" int crgpu_umap_graph_dev(crgpu_ctx *ctx, const int32_t *nn_indices, c
     CR_TRY(crgpu_memcpy_h2d(ctx, dist_b.p, nn_distances, nk * sizeof(double)));
     double *d_total = scal_b.as<double>(), *d_wmax = scal_b.as<double>() + 2;  // d_wmax[0] = wmax, [1] = the threshold
 
-    UmapEvents events(ctx);
+    CrEvents<3> events(ctx);
     hipEvent_t *ev = events.e;
     const uint32_t row_grid = (uint32_t)((n + UMAP_WG - 1u) / UMAP_WG);
     CR_HIP(ctx, hipEventRecord(ev[0], ctx->stream));
     hipLaunchKernelGGL(k_umap_rows, dim3(row_grid), dim3(UMAP_WG), 0, ctx->stream, dist_b.as<double>(), (uint32_t)n, k, rho_b.as<double>(),
                        rowsum_b.as<double>());
-    hipLaunchKernelGGL(k_umap_parts, dim3(cr_grid(n_parts, UMAP_WG)), dim3(UMAP_WG), 0, ctx->stream, rowsum_b.as<double>(), n, n_parts, parts_b.as<double>());
-    hipLaunchKernelGGL(k_umap_final, dim3(1), dim3(64), 0, ctx->stream, parts_b.as<double>(), n_parts, d_total);
+    cr_colsums(ctx, rowsum_b.as<double>(), n, 1u, 1u, parts_b.as<double>(), d_total);
     hipLaunchKernelGGL(k_umap_search, dim3(row_grid), dim3(UMAP_WG), 0, ctx->stream, dist_b.as<double>(), rho_b.as<double>(), rowsum_b.as<double>(), d_total,
                        (uint32_t)n, k, std::log2((double)(k + 1u)), (double)(k + 1u), (double)n * (double)(k + 1u), sigma_b.as<double>(),
                        steps_b.as<uint32_t>(), memb_b.as<double>());
     CR_HIP(ctx, hipGetLastError());
     CR_HIP(ctx, hipEventRecord(ev[1], ctx->stream));
-    hipLaunchKernelGGL(k_umap_keys, dim3(cr_grid(nk, UMAP_WG)), dim3(UMAP_WG), 0, ctx->stream, nn_b.as<int32_t>(), (uint32_t)n, k, keys_b.as<uint64_t>(),
-                       perm_b.as<uint32_t>());
+    cr_pair_keys(ctx, nn_b.as<int32_t>(), (uint32_t)n, k, keys_b.as<uint64_t>(), perm_b.as<uint32_t>());
     CR_HIP(ctx, hipGetLastError());
-    bool in_tmp = false;
-    CR_TRY(cr_radix_sort_u64(ctx, keys_b.as<uint64_t>(), keyt_b.as<uint64_t>(), perm_b.as<uint32_t>(), permt_b.as<uint32_t>(), n2, 0,
-                             std::max(1u, cr_ceil_log2(n * n)), &in_tmp));
-    uint64_t *d_keys = in_tmp ? keyt_b.as<uint64_t>() : keys_b.as<uint64_t>(), *d_spare = in_tmp ? keys_b.as<uint64_t>() : keyt_b.as<uint64_t>();
-    const uint32_t *d_perm = in_tmp ? permt_b.as<uint32_t>() : perm_b.as<uint32_t>();
-    uint32_t *d_count = block_b.as<uint32_t>() + 4096;
-    CR_TRY(compact(ctx, UmapHeadFlag{d_keys}, UmapEmitUnion{d_keys, d_perm, memb_b.as<double>(), n2, ckeys_b.as<uint64_t>(), val_b.as<double>()}, n2,
-                   block_b.as<uint32_t>(), d_count));
+    SortedKeys sk;
+    CR_TRY(cr_sort_keys(ctx, keys_b.as<uint64_t>(), keyt_b.as<uint64_t>(), perm_b.as<uint32_t>(), permt_b.as<uint32_t>(), n2, cr_ceil_log2(n * n), &sk));
     uint32_t merged32 = 0;
-    CR_TRY(read_u32(ctx, d_count, &merged32));
+    CR_TRY(cr_merge_runs(ctx, sk.keys, UmapEmitUnion{sk.keys, sk.perm, memb_b.as<double>(), n2, ckeys_b.as<uint64_t>(), val_b.as<double>()}, n2,
+                         block_b.as<uint32_t>(), nk, n2, who, "merged entries", &merged32));
     const uint64_t merged = merged32;
-    CR_REQUIRE(ctx, merged >= nk && merged <= n2, CRGPU_EHIP, "%s: %llu merged entries of %llu pairs", who, (unsigned long long)merged, (unsigned long long)nk);
+    uint32_t *d_count = block_b.as<uint32_t>() + 4096;
     const uint32_t max_grid = cr_grid(merged, UMAP_WG, max_blocks);
     hipLaunchKernelGGL(k_umap_maxparts, dim3(max_grid), dim3(UMAP_WG), 0, ctx->stream, val_b.as<double>(), merged, parts_b.as<double>());
     hipLaunchKernelGGL(k_umap_maxfinal, dim3(1), dim3(64), 0, ctx->stream, parts_b.as<double>(), max_grid, (double)n_epochs, d_wmax);
     CR_HIP(ctx, hipGetLastError());
     // the kept entries: their keys into the sort's spare buffer
-    CR_TRY(compact(ctx, UmapKeepFlag{val_b.as<double>(), d_wmax}, UmapEmitKept{ckeys_b.as<uint64_t>(), val_b.as<double>(), d_spare, kept_b.as<double>()},
+    CR_TRY(compact(ctx, UmapKeepFlag{val_b.as<double>(), d_wmax}, UmapEmitKept{ckeys_b.as<uint64_t>(), val_b.as<double>(), sk.spare, kept_b.as<double>()},
                    merged, block_b.as<uint32_t>(), d_count));
     uint32_t nnz32 = 0;
     CR_TRY(read_u32(ctx, d_count, &nnz32));
     const uint64_t nnz = nnz32;
     CR_REQUIRE(ctx, nnz >= 1 && nnz <= merged, CRGPU_EHIP, "%s: %llu kept entries of %llu", who, (unsigned long long)nnz, (unsigned long long)merged);
-    hipLaunchKernelGGL(k_umap_indptr, dim3(cr_grid(std::max<uint64_t>(nnz, n + 1), UMAP_WG)), dim3(UMAP_WG), 0, ctx->stream, (const uint64_t *)d_spare, nnz,
-                       (uint32_t)n, ptr_b.as<long long>(), ind_b.as<int32_t>());
+    cr_keys_to_csr(ctx, sk.spare, nnz, (uint32_t)n, ptr_b.as<long long>(), ind_b.as<int32_t>(), nullptr);
     CR_HIP(ctx, hipGetLastError());
     CR_HIP(ctx, hipEventRecord(ev[2], ctx->stream));
 
@@ -500,7 +432,7 @@ extern "C" int crgpu_umap_graph_dev(crgpu_ctx *ctx, const int32_t *nn_indices, c
     CR_HIP(ctx, hipEventElapsedTime(&ms_b, ev[1], ev[2]));
     res->search_ms = ms_a, res->csr_ms = ms_b, res->nnz = nnz;
     res->max_steps = *std::max_element(steps.begin(), steps.end());
-    res->fit_ms = umap_ms_since(t0);
+    res->fit_ms = cr_ms_since(t0);
     return CRGPU_OK;
 }
 
@@ -524,21 +456,14 @@ extern "C" int crgpu_umap_epochs_dev(crgpu_ctx *ctx, const int64_t *indptr, cons
                a->n_run, a->n_epochs);
     CR_REQUIRE(ctx, wg == 64u || wg == 128u || wg == 256u, CRGPU_EINVAL, "%s: %u rows of a workgroup, 64, 128 or 256", who, wg);
     CR_REQUIRE(ctx, a->reserved0 == 0u && a->reserved1 == 0u, CRGPU_EINVAL, "%s: reserved is 0", who);
-    CR_REQUIRE(ctx, indptr[0] == 0, CRGPU_EINVAL, "%s: indptr[0] = %lld", who, (long long)indptr[0]);
-    for (uint64_t i = 0; i < n; i++)
-        CR_REQUIRE(ctx, indptr[i + 1] >= indptr[i] && indptr[i + 1] < (1ll << 59), CRGPU_EINVAL, "%s: indptr[%llu] = %lld after %lld", who,
-                   (unsigned long long)(i + 1), (long long)indptr[i + 1], (long long)indptr[i]);  // nnz * 16 < 2^63
+    CR_TRY(cr_check_csr(ctx, who, indptr, indices, n, 59u, true));  // nnz * 16 < 2^63
     const uint64_t nnz = (uint64_t)indptr[n];
     double wmax = 0.0;
-    for (uint64_t i = 0; i < n; i++)
-        for (int64_t e = indptr[i]; e < indptr[i + 1]; e++) {
-            CR_REQUIRE(ctx, indices[e] >= 0 && (uint64_t)indices[e] < n, CRGPU_EINVAL, "%s: indices[%lld] = %d outside the rows", who, (long long)e, indices[e]);
-            CR_REQUIRE(ctx, e == indptr[i] || indices[e] > indices[e - 1], CRGPU_EINVAL, "%s: the indices of row %llu must be strictly ascending", who,
-                       (unsigned long long)i);
-            CR_REQUIRE(ctx, std::isfinite(values[e]) && values[e] > 0.0, CRGPU_EINVAL, "%s: values[%lld] = %g, finite and positive", who, (long long)e,
-                       values[e]);
-            wmax = std::max(wmax, values[e]);
-        }
+    for (uint64_t e = 0; e < nnz; e++) {
+        CR_REQUIRE(ctx, std::isfinite(values[e]) && values[e] > 0.0, CRGPU_EINVAL, "%s: values[%llu] = %g, finite and positive", who, (unsigned long long)e,
+                   values[e]);
+        wmax = std::max(wmax, values[e]);
+    }
     for (uint64_t e = 0; e < n * dims; e++) CR_REQUIRE(ctx, std::isfinite(y[e]), CRGPU_EINVAL, "%s: y[%llu] is not finite", who, (unsigned long long)e);
     if (a->first_epoch)
         for (uint64_t e = 0; e < nnz; e++)
@@ -572,7 +497,7 @@ extern "C" int crgpu_umap_epochs_dev(crgpu_ctx *ctx, const int64_t *indptr, cons
     CR_HIP(ctx, hipMemsetAsync(counts_b.p, 0, 2 * n * sizeof(unsigned long long), ctx->stream));
     CR_HIP(ctx, hipMemsetAsync(delta_b.p, 0, yb, ctx->stream));
 
-    UmapEvents events(ctx);
+    CrEvents<3> events(ctx);
     CR_HIP(ctx, hipEventRecord(events.e[0], ctx->stream));
     if (nnz && !a->first_epoch)
         hipLaunchKernelGGL(k_umap_schedule, dim3(cr_grid(nnz, UMAP_WG)), dim3(UMAP_WG), 0, ctx->stream, val_b.as<double>(), nnz, wmax, (double)rate,
@@ -607,6 +532,6 @@ extern "C" int crgpu_umap_epochs_dev(crgpu_ctx *ctx, const int64_t *indptr, cons
     float ms = 0.0f;
     CR_HIP(ctx, hipEventElapsedTime(&ms, events.e[0], events.e[1]));
     res->loop_ms = ms;
-    res->fit_ms = umap_ms_since(t0);
+    res->fit_ms = cr_ms_since(t0);
     return CRGPU_OK;
 }

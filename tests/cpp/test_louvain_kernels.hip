@@ -2,17 +2,16 @@
 // Everything in louvain.hip is an integer, so everything here is compared bit for bit with a HOST ORDER MODEL written with std::map:
 // the round (the gather of w_i(C), the maximum of (G, C == own, -C), the singleton rule, the labels, tot, size and the count of moves
 // of the buffer it writes), both sums of S, the decision and the latch, the class lists, the union, the structure check, the degrees,
-// the dense renumbering, the composition and the aggregation.
+// the dense renumbering, the composition and the aggregation; and the shared k_keys_to_csr of graph_common.h on hand-made keys.
 //
 // louvain.hip is compiled here inside a namespace: the same text under the same flags (cellranger_amd.build.FLAGS), not the library's
 // object code.  The context, the pool, the scan and the radix sort come from libcrgpu.so.
 //
 //   test_louvain_kernels --host-only              every case without a device: the order model against hand-computed values and against
 //                                                 its own invariants (the tot of a round add up to M, S from a dense matrix)
-//   test_louvain_kernels --group round|levels
+//   test_louvain_kernels --group round|levels|csr
 // One line per case, "all tests passed" at the end; the first mismatch or HIP error ends the program with status 1.
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -21,100 +20,15 @@
 #include <string>
 #include <vector>
 
-#include "stage_common.h"
+#include "graph_common.h"
+#include "kernel_test.h"
 
 namespace louvain_under_test {
 #include "louvain.hip"
 }
 using namespace louvain_under_test;
 
-static const uint64_t GUARD = 64;
-
-[[noreturn]] static void die(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    std::fprintf(stdout, "FAIL ");
-    std::vfprintf(stdout, fmt, ap);
-    std::fprintf(stdout, "\n");
-    va_end(ap);
-    std::fflush(stdout);
-    std::exit(1);
-}
-static bool g_host_only = false;
-static int g_cases = 0;
 static uint64_t g_tie_own = 0, g_tie_other = 0, g_dropped = 0, g_one_label = 0;  // branches the model took
-static void case_done(const char *fmt, ...) {
-    char b[400];
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(b, sizeof(b), fmt, ap);
-    va_end(ap);
-    std::printf("ok   %s%s\n", b, g_host_only ? " (host only)" : "");
-    g_cases++;
-}
-template <typename T>
-static void same(const char *what, const std::vector<T> &got, const std::vector<T> &want) {
-    if (got.size() != want.size()) die("%s: %zu values against %zu", what, got.size(), want.size());
-    for (size_t i = 0; i < got.size(); i++)
-        if (got[i] != want[i]) die("%s[%zu]: %lld on the device, %lld in the order model", what, i, (long long)got[i], (long long)want[i]);
-}
-struct Rng {  // splitmix64
-    uint64_t s;
-    explicit Rng(uint64_t seed) : s(seed) {}
-    uint64_t next() {
-        uint64_t z = (s += 0x9E3779B97F4A7C15ull);
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        return z ^ (z >> 31);
-    }
-    uint32_t below(uint32_t n) { return (uint32_t)(next() % n); }
-};
-
-// ---- the device ----------------------------------------------------------------------------------------------------------------------
-struct Gpu {
-    crgpu_ctx *ctx = nullptr;
-    Gpu() {
-        const int rc = crgpu_create(&ctx, 0, 1, 0, nullptr);
-        if (rc != CRGPU_OK) die("crgpu_create -> %d: %s", rc, crgpu_last_error(nullptr));
-    }
-    ~Gpu() { crgpu_destroy(ctx); }
-    void ok(int rc, const char *what) const {
-        if (rc != CRGPU_OK) die("%s -> %d: %s", what, rc, crgpu_last_error(ctx));
-    }
-    void launched(const char *what) const {
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) die("launch of %s: %s", what, hipGetErrorString(e));
-    }
-};
-static Gpu *g_gpu = nullptr;
-#define GOK(call) g_gpu->ok((call), #call)
-// n elements and GUARD more behind them, filled with 0xFF before anything is launched; get() asserts that the guard came back untouched
-template <typename T>
-struct GBuf {
-    T *d = nullptr;
-    uint64_t n;
-    GBuf(uint64_t n_) : n(n_) {
-        void *p = nullptr;
-        GOK(crgpu_malloc(g_gpu->ctx, &p, (n + GUARD) * sizeof(T)));
-        d = (T *)p;
-        GOK(crgpu_memset(g_gpu->ctx, d, 0xFF, (n + GUARD) * sizeof(T)));
-    }
-    GBuf(const std::vector<T> &h) : GBuf(h.size()) {
-        if (n) GOK(crgpu_memcpy_h2d(g_gpu->ctx, d, h.data(), n * sizeof(T)));
-    }
-    GBuf(const GBuf &) = delete;
-    GBuf &operator=(const GBuf &) = delete;
-    ~GBuf() { (void)crgpu_free(g_gpu->ctx, d); }
-    std::vector<T> get(const char *what) const {
-        std::vector<T> h(n + GUARD);
-        GOK(crgpu_memcpy_d2h(g_gpu->ctx, h.data(), d, (n + GUARD) * sizeof(T)));
-        const unsigned char *g = (const unsigned char *)(h.data() + n);
-        for (uint64_t i = 0; i < GUARD * sizeof(T); i++)
-            if (g[i] != 0xFFu) die("%s: byte %llu behind the %llu elements of the buffer was written", what, (unsigned long long)i, (unsigned long long)n);
-        h.resize(n);
-        return h;
-    }
-};
 
 // ---- the order model -----------------------------------------------------------------------------------------------------------------
 struct Graph {  // a symmetric CSR, ascending columns, a self-loop once
@@ -455,13 +369,13 @@ static void levels_case(uint32_t n, uint32_t k, uint32_t groups, uint64_t seed) 
         bool in_tmp = false;
         GOK(cr_radix_sort_u64(ctx, d_keys.d, d_keyt.d, nullptr, nullptr, n_keys, 0, std::max(1u, cr_ceil_log2((uint64_t)n * n)), &in_tmp));
         const uint64_t *sorted = in_tmp ? d_keyt.d : d_keys.d;
-        GOK(compact(ctx, LvHeadFlag{sorted}, LvEmitKey{sorted, d_ckeys.d}, n_keys, d_block.d, d_count));
+        GOK(compact(ctx, KeyHeadFlag{sorted}, LvEmitKey{sorted, d_ckeys.d}, n_keys, d_block.d, d_count));
         uint32_t merged = 0;
         GOK(read_u32(ctx, d_count, &merged));
         if (merged != nnz) die("%u merged entries against %llu", merged, (unsigned long long)nnz);
-        hipLaunchKernelGGL(k_lv_csr, dim3(cr_grid(std::max<uint64_t>(nnz, n + 1), LV_WG)), dim3(LV_WG), 0, ctx->stream, (const uint64_t *)d_ckeys.d, nnz, n, d_ptr.d,
+        hipLaunchKernelGGL(k_keys_to_csr<uint32_t>, dim3(cr_grid(std::max<uint64_t>(nnz, n + 1), GRAPH_WG)), dim3(GRAPH_WG), 0, ctx->stream, (const uint64_t *)d_ckeys.d, nnz, n, d_ptr.d,
                            d_ind.d, d_w.d);
-        g_gpu->launched("k_lv_csr");
+        g_gpu->launched("k_keys_to_csr");
         same("the union's indptr", d_ptr.get("indptr"), g.indptr), same("the union's indices", d_ind.get("indices"), g.indices);
         same("the union's weights", d_w.get("weights"), g.weights);
         // the structure check: the union passes; a swapped pair, a zero weight, an unequal twin and a missing twin are flagged
@@ -552,14 +466,14 @@ static void levels_case(uint32_t n, uint32_t k, uint32_t groups, uint64_t seed) 
         GOK(cr_radix_sort_u64(ctx, d_keys.d, d_keyt.d, d_perm.d, d_permt.d, nnz, 0, std::max(1u, cr_ceil_log2((uint64_t)n_c * n_c)), &in_tmp));
         const uint64_t *skeys = in_tmp ? d_keyt.d : d_keys.d;
         const uint32_t *sperm = in_tmp ? d_permt.d : d_perm.d;
-        GOK(compact(ctx, LvHeadFlag{skeys}, LvEmitKey{skeys, d_ckeys.d}, nnz, d_block.d, d_count));
+        GOK(compact(ctx, KeyHeadFlag{skeys}, LvEmitKey{skeys, d_ckeys.d}, nnz, d_block.d, d_count));
         uint32_t runs = 0;
         GOK(read_u32(ctx, d_count, &runs));
         if (runs != ag.indices.size()) die("%u entries of the aggregated graph against %zu", runs, ag.indices.size());
         GOK(crgpu_memset(ctx, d_w2.d, 0, (uint64_t)runs * sizeof(uint32_t)));
         hipLaunchKernelGGL(k_lv_run_sums, dim3(cr_grid((nnz + LV_RUN_CHUNK - 1u) / LV_RUN_CHUNK, LV_WG)), dim3(LV_WG), 0, ctx->stream, skeys, sperm,
                            (const uint32_t *)d_w.d, nnz, (const uint64_t *)d_ckeys.d, (uint64_t)runs, d_w2.d);
-        hipLaunchKernelGGL(k_lv_csr, dim3(cr_grid(std::max<uint64_t>(runs, (uint64_t)n_c + 1u), LV_WG)), dim3(LV_WG), 0, ctx->stream, (const uint64_t *)d_ckeys.d,
+        hipLaunchKernelGGL(k_keys_to_csr<uint32_t>, dim3(cr_grid(std::max<uint64_t>(runs, (uint64_t)n_c + 1u), GRAPH_WG)), dim3(GRAPH_WG), 0, ctx->stream, (const uint64_t *)d_ckeys.d,
                            (uint64_t)runs, n_c, d_ptr2.d, d_ind2.d, (uint32_t *)nullptr);
         g_gpu->launched("the aggregation");
         same("the aggregated indptr", d_ptr2.get("indptr"), ag.indptr), same("the aggregated indices", d_ind2.get("indices"), ag.indices);
@@ -577,18 +491,68 @@ static void group_levels() {
     levels_case(1100, 40, 2, 4003);   // two communities: runs of hundreds of thousands of keys
 }
 
+// ---- the shared keys-to-CSR kernel ---------------------------------------------------------------------------------------------------
+// k_keys_to_csr (graph_common.h) through its launch helper on hand-made sorted distinct keys i * n + j, against a host loop that counts
+// the entries of every row; with the weights pointer every weight is 1, without it the weights buffer keeps its fill
+static void csr_case(const char *name, uint32_t n, const std::vector<uint64_t> &ckeys, const std::vector<long long> *indptr_by_hand) {
+    const uint64_t nnz = ckeys.size();
+    for (uint64_t e = 0; e < nnz; e++)
+        if (ckeys[e] >= (uint64_t)n * n || (e && ckeys[e - 1] >= ckeys[e])) die("%s: the keys are not sorted distinct keys of %u rows", name, n);
+    std::vector<long long> indptr(n + 1, 0);
+    std::vector<int32_t> indices(nnz);
+    for (uint64_t e = 0; e < nnz; e++) indptr[ckeys[e] / n + 1]++, indices[e] = (int32_t)(ckeys[e] % n);
+    for (uint32_t r = 0; r < n; r++) indptr[r + 1] += indptr[r];
+    if (indptr_by_hand && indptr != *indptr_by_hand) die("%s: the host loop's indptr is not the one written by hand", name);
+    if (!g_host_only)
+        for (int weighted = 0; weighted < 2; weighted++) {
+            GBuf<uint64_t> d_ckeys(ckeys);
+            GBuf<long long> d_ptr(n + 1);
+            GBuf<int32_t> d_ind(nnz);
+            GBuf<uint32_t> d_w(nnz);
+            cr_keys_to_csr(g_gpu->ctx, d_ckeys.d, nnz, n, d_ptr.d, d_ind.d, weighted ? d_w.d : nullptr);
+            g_gpu->launched("k_keys_to_csr");
+            same("indptr", d_ptr.get("indptr"), indptr), same("indices", d_ind.get("indices"), indices);
+            same("weights", d_w.get("weights"), std::vector<uint32_t>(nnz, weighted ? 1u : 0xFFFFFFFFu));
+            same("the keys read", d_ckeys.get("ckeys"), ckeys);
+        }
+    case_done("csr %-36s n %3u, %3llu entries, a grid for %llu threads, with and without weights", name, n, (unsigned long long)nnz,
+              (unsigned long long)std::max<uint64_t>(nnz, (uint64_t)n + 1u));
+}
+static void group_csr() {
+    {  // rows 0, 2 and 4 empty: at the start, in the middle and at the end; fewer entries than n + 1
+        const std::vector<long long> by_hand = {0, 0, 2, 2, 3, 3};
+        csr_case("empty rows at both ends and between", 5, {1 * 5 + 0, 1 * 5 + 4, 3 * 5 + 2}, &by_hand);
+    }
+    {
+        const std::vector<long long> by_hand = {0, 2, 4};
+        csr_case("every cell", 2, {0, 1, 2, 3}, &by_hand);
+    }
+    {  // row 7 holds the columns 0 .. 256, every other row one column: more entries than n + 1 and than a workgroup has threads
+        const uint32_t n = 300;
+        std::vector<uint64_t> keys;
+        for (uint32_t i = 0; i < n; i++) {
+            if (i == 7u)
+                for (uint32_t j = 0; j < 257u; j++) keys.push_back((uint64_t)i * n + j);
+            else keys.push_back((uint64_t)i * n + (i * 7u + 3u) % n);
+        }
+        if (keys.size() != 257u + 299u) die("the long row: %zu keys", keys.size());
+        csr_case("one row of 257 entries", n, keys, nullptr);
+    }
+}
+
 int main(int argc, char **argv) {
     std::string group;
     for (int i = 1; i < argc; i++) {
         if (!std::strcmp(argv[i], "--host-only")) g_host_only = true;
         else if (!std::strcmp(argv[i], "--group") && i + 1 < argc) group = argv[++i];
-        else die("usage: test_louvain_kernels --host-only | --group round|levels");
+        else die("usage: test_louvain_kernels --host-only | --group round|levels|csr");
     }
-    if (!g_host_only && group != "round" && group != "levels") die("usage: test_louvain_kernels --host-only | --group round|levels");
+    if (!g_host_only && group != "round" && group != "levels" && group != "csr") die("usage: test_louvain_kernels --host-only | --group round|levels|csr");
     Gpu *gpu = nullptr;
     if (!g_host_only) g_gpu = gpu = new Gpu();
     if (g_host_only || group == "round") group_round();
     if (g_host_only || group == "levels") group_levels();
+    if (g_host_only || group == "csr") group_csr();
     std::printf("branches: %llu ties of own and another, %llu ties of two others, %llu dropped proposals, %llu rows with one label around them\n",
                 (unsigned long long)g_tie_own, (unsigned long long)g_tie_other, (unsigned long long)g_dropped, (unsigned long long)g_one_label);
     delete gpu;

@@ -28,13 +28,12 @@
 #include <numeric>
 #include <vector>
 
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 
-#include "stage_common.h"
+#include "kernel_test.h"
 
 namespace pca_under_test {
 #include "pca.hip"
@@ -60,52 +59,12 @@ static const uint32_t WG = PCA_WG;              // threads of the fixed-size lau
 static const uint32_t PR = PCA_PART_ROWS;       // rows of a partial of the dots
 static const uint32_t PC = PCA_PROJ_CHUNK;      // components a pass of the projection keeps in registers
 static const uint32_t WPW = PCA_WG / CR_WAVE;   // waves of a workgroup of the dots
-static const uint64_t GUARD = 64;
 
-[[noreturn]] static void die(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    std::fprintf(stdout, "FAIL ");
-    std::vfprintf(stdout, fmt, ap);
-    std::fprintf(stdout, "\n");
-    va_end(ap);
-    std::fflush(stdout);
-    std::exit(1);
-}
 static uint64_t bits(double x) {
     uint64_t b;
     std::memcpy(&b, &x, 8);
     return b;
 }
-static bool g_host_only = false;
-static int g_cases = 0;
-static void case_done(const char *fmt, ...) {
-    char b[400];
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(b, sizeof(b), fmt, ap);
-    va_end(ap);
-    std::printf("ok   %s\n", b);
-    g_cases++;
-}
-
-struct Rng {  // splitmix64
-    uint64_t s;
-    explicit Rng(uint64_t seed) : s(seed) {}
-    uint64_t next() {
-        uint64_t z = (s += 0x9E3779B97F4A7C15ull);
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        return z ^ (z >> 31);
-    }
-    uint64_t below(uint64_t m) { return next() % m; }
-    double unit() { return ((double)(next() >> 11) + 0.5) * 0x1.0p-53; }  // (0, 1)
-    double normal() { return std::sqrt(-2.0 * std::log(unit())) * std::cos(6.283185307179586 * unit()); }
-    double nonzero() {  // a normal value away from 0
-        const double x = normal();
-        return x < 0.0 ? x - 0.25 : x + 0.25;
-    }
-};
 enum VecKind { VEC_NORMAL = 0, VEC_DECADES = 1, VEC_UNIT = 2 };
 static const char *VEC_NAMES[3] = {"normal", "decades", "unit"};
 // VEC_DECADES: alternating signs over twelve decades, so that the order of a sum shows in its bits
@@ -119,55 +78,6 @@ static std::vector<double> make_vec(uint64_t n, VecKind kind, uint64_t unit_at, 
     return v;
 }
 
-// ---- the device ---------------------------------------------------------------------------------------------------------------
-struct Gpu {
-    crgpu_ctx *ctx = nullptr;
-    Gpu() {
-        const int rc = crgpu_create(&ctx, 0, 1, 0, nullptr);
-        if (rc != CRGPU_OK) die("crgpu_create -> %d: %s", rc, crgpu_last_error(nullptr));
-    }
-    ~Gpu() { crgpu_destroy(ctx); }
-    void ok(int rc, const char *what) const {
-        if (rc != CRGPU_OK) die("%s -> %d: %s", what, rc, crgpu_last_error(ctx));
-    }
-    void launched(const char *what) const {
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) die("launch of %s: %s", what, hipGetErrorString(e));
-    }
-};
-static Gpu *g_gpu = nullptr;
-#define GOK(call) g_gpu->ok((call), #call)
-
-// n elements and GUARD more behind them, all filled with one byte before anything is launched: 0xFF makes every f64 a NaN, 0xA5 an
-// integer no case expects.  get() asserts that the guard came back untouched.
-template <typename T>
-struct GBuf {
-    T *d = nullptr;
-    uint64_t n;
-    int fill;
-    GBuf(uint64_t n_, int fill_) : n(n_), fill(fill_) {
-        void *p = nullptr;
-        GOK(crgpu_malloc(g_gpu->ctx, &p, (n + GUARD) * sizeof(T)));
-        d = (T *)p;
-        GOK(crgpu_memset(g_gpu->ctx, d, fill, (n + GUARD) * sizeof(T)));
-    }
-    GBuf(const std::vector<T> &h, int fill_) : GBuf(h.size(), fill_) {
-        if (n) GOK(crgpu_memcpy_h2d(g_gpu->ctx, d, h.data(), n * sizeof(T)));
-    }
-    void zero() { GOK(crgpu_memset(g_gpu->ctx, d, 0, n * sizeof(T))); }  // an accumulator: the elements 0, the guard as it was
-    GBuf(const GBuf &) = delete;
-    GBuf &operator=(const GBuf &) = delete;
-    ~GBuf() { (void)crgpu_free(g_gpu->ctx, d); }
-    std::vector<T> get(const char *what) const {
-        std::vector<T> h(n + GUARD);
-        GOK(crgpu_memcpy_d2h(g_gpu->ctx, h.data(), d, (n + GUARD) * sizeof(T)));
-        const unsigned char *g = (const unsigned char *)(h.data() + n);
-        for (uint64_t i = 0; i < GUARD * sizeof(T); i++)
-            if (g[i] != (unsigned char)fill) die("%s: byte %llu behind the %llu elements of the buffer was written", what, (unsigned long long)i, (unsigned long long)n);
-        h.resize(n);
-        return h;
-    }
-};
 template <typename T>
 static std::vector<T> download(const void *d, uint64_t n) {
     std::vector<T> h(n);
@@ -227,17 +137,6 @@ static void judge(const char *what, uint64_t idx, double model, const double *de
     const long double dev_err = fabsl((long double)got - ref);
     if (!(dev_err <= bound)) die("%s [%llu]: %.17g is %.3Lg from the reference %.21Lg, the bound is %.3Lg", what, (unsigned long long)idx, got, dev_err, ref, bound);
     if (bound > 0.0L && dev_err / bound > g_worst) g_worst = dev_err / bound, g_worst_at = what;
-}
-static void same_bits(const char *what, const std::vector<double> &got, const std::vector<double> &want) {
-    if (got.size() != want.size()) die("%s: %zu values, expected %zu", what, got.size(), want.size());
-    for (size_t i = 0; i < got.size(); i++)
-        if (bits(got[i]) != bits(want[i])) die("%s [%zu]: %a, expected %a", what, i, got[i], want[i]);
-}
-template <typename T>
-static void same_ints(const char *what, const std::vector<T> &got, const std::vector<T> &want) {
-    if (got.size() != want.size()) die("%s: %zu values, expected %zu", what, got.size(), want.size());
-    for (size_t i = 0; i < got.size(); i++)
-        if (got[i] != want[i]) die("%s [%zu]: %llu, expected %llu", what, i, (unsigned long long)got[i], (unsigned long long)want[i]);
 }
 static int64_t ulp_distance(double a, double b) {  // both finite and of one sign
     const int64_t x = (int64_t)bits(a), y = (int64_t)bits(b);
@@ -575,27 +474,27 @@ static void run_prepare(const Case &c, bool logged, uint32_t wg, Rng &rng) {
         for (uint32_t r = 0; r < c.G && c.has_fmap; r++) mask[r] = c.fmap[r] >= 0;
         GBuf<uint32_t> lib_sums(c.V, FILL_INT);
         GOK(crgpu_matrix_dev_column_sums(ctx, &D.m, c.has_fmap ? mask.data() : nullptr, c.G, lib_sums.d));
-        same_ints((name + " sums_all").c_str(), lib_sums.get("sums_all"), p.sums_all);
+        same((name + " sums_all").c_str(), lib_sums.get("sums_all"), p.sums_all);
     }
     const uint32_t *d_bcs = c.has_bcs ? D.bcs.d : nullptr;
     const int32_t *d_fmap = c.has_fmap ? D.fmap.d : nullptr;
     PcaPrep P;
     GOK(pca_prepare(ctx, &D.m, c.G, d_bcs, p.N, d_fmap, p.F, D.sums_all.d, logged, wg, P));
     if (P.N != p.N || P.F != p.F || P.nnz != p.nnz) die("%s: N, F, nnz = %llu, %u, %llu, expected %llu, %u, %llu", name.c_str(), (unsigned long long)P.N, P.F, (unsigned long long)P.nnz, (unsigned long long)p.N, p.F, (unsigned long long)p.nnz);
-    same_ints((name + " rowptr").c_str(), download<uint64_t>(P.rowptr.p, p.N + 1), p.rowptr);
-    same_ints((name + " col").c_str(), download<uint32_t>(P.col.p, p.nnz), p.col);
-    same_ints((name + " sorted keys").c_str(), download<uint64_t>(P.d_keys(), p.nnz), p.keys_sorted);
-    same_ints((name + " sorted entry numbers").c_str(), download<uint32_t>(P.d_perm(), p.nnz), p.tpos);
+    same((name + " rowptr").c_str(), download<uint64_t>(P.rowptr.p, p.N + 1), p.rowptr);
+    same((name + " col").c_str(), download<uint32_t>(P.col.p, p.nnz), p.col);
+    same((name + " sorted keys").c_str(), download<uint64_t>(P.d_keys(), p.nnz), p.keys_sorted);
+    same((name + " sorted entry numbers").c_str(), download<uint32_t>(P.d_perm(), p.nnz), p.tpos);
     const std::vector<double> val = download<double>(P.val.p, p.nnz);
     for (uint64_t i = 0; i < p.nnz; i++)
         if (!std::isfinite(val[i])) die("%s: val[%llu] = %a", name.c_str(), (unsigned long long)i, val[i]);
     if (logged) check_logged(c, p, val.data());
-    else same_bits((name + " val = count * factor").c_str(), val, p.x);
+    else same((name + " val = count * factor").c_str(), val, p.x);
     p.val = val;  // from here on every check starts from the device's own values
     transpose_values(p);
-    same_ints((name + " tptr").c_str(), download<uint64_t>(P.tptr.p, (uint64_t)p.F + 1), p.tptr);
-    same_ints((name + " tcell").c_str(), download<uint32_t>(P.tcell.p, p.nnz), p.tcell);
-    same_bits((name + " tval").c_str(), download<double>(P.tval.p, p.nnz), p.tval);
+    same((name + " tptr").c_str(), download<uint64_t>(P.tptr.p, (uint64_t)p.F + 1), p.tptr);
+    same((name + " tcell").c_str(), download<uint32_t>(P.tcell.p, p.nnz), p.tcell);
+    same((name + " tval").c_str(), download<double>(P.tval.p, p.nnz), p.tval);
     if (P.mean.size() != p.F || P.var.size() != p.F) die("%s: %zu means, %zu variances", name.c_str(), P.mean.size(), P.var.size());
     check_meanvar(name, p, P.mean.data(), P.var.data());
 
@@ -609,8 +508,8 @@ static void run_prepare(const Case &c, bool logged, uint32_t wg, Rng &rng) {
         GBuf<uint32_t> cnt(p.N, FILL_INT), sums(p.N, FILL_INT), flag(std::vector<uint32_t>(1, 0u), FILL_INT);
         hipLaunchKernelGGL(k_pca_count, dim3(2), dim3(wg), 0, st, D.indptr.d, D.indices.d, d_bcs, p.N, c.G, d_fmap, D.sums_all.d, cnt.d, sums.d, flag.d);
         g_gpu->launched("k_pca_count");
-        same_ints((name + " k_pca_count cnt").c_str(), cnt.get("cnt"), p.cnt);
-        same_ints((name + " k_pca_count sums").c_str(), sums.get("sums"), p.sums);
+        same((name + " k_pca_count cnt").c_str(), cnt.get("cnt"), p.cnt);
+        same((name + " k_pca_count sums").c_str(), sums.get("sums"), p.sums);
         if (flag.get("flag")[0] != 0u) die("%s: k_pca_count raised its flag", name.c_str());
     }
     GBuf<double> r_val(nnz, FILL_F64);
@@ -621,9 +520,9 @@ static void run_prepare(const Case &c, bool logged, uint32_t wg, Rng &rng) {
         hipLaunchKernelGGL(k_pca_fill, dim3(2), dim3(wg), 0, st, D.indptr.d, D.indices.d, D.data.d, d_bcs, p.N, c.G, d_fmap, d_factor.d, logged ? 1 : 0, d_rowptr.d,
                            r_col.d, r_val.d, keys.d, perm.d);
         g_gpu->launched("k_pca_fill");
-        same_ints((name + " k_pca_fill col").c_str(), r_col.get("col"), p.col);
-        same_bits((name + " k_pca_fill val").c_str(), r_val.get("val"), p.val);
-        same_ints((name + " k_pca_fill keys").c_str(), keys.get("keys"), p.keys);
+        same((name + " k_pca_fill col").c_str(), r_col.get("col"), p.col);
+        same((name + " k_pca_fill val").c_str(), r_val.get("val"), p.val);
+        same((name + " k_pca_fill keys").c_str(), keys.get("keys"), p.keys);
         const std::vector<uint32_t> pm = perm.get("perm");
         for (uint64_t i = 0; i < nnz; i++)
             if (pm[i] != (uint32_t)i) die("%s: k_pca_fill perm[%llu] = %u", name.c_str(), (unsigned long long)i, pm[i]);
@@ -634,29 +533,29 @@ static void run_prepare(const Case &c, bool logged, uint32_t wg, Rng &rng) {
     if (nnz) {
         hipLaunchKernelGGL(k_pca_gather, dim3(2), dim3(WG), 0, st, d_keys_sorted.d, d_tpos.d, r_val.d, p.N, nnz, r_tval.d, r_tcell.d);
         g_gpu->launched("k_pca_gather");
-        same_bits((name + " k_pca_gather tval").c_str(), r_tval.get("tval"), p.tval);
-        same_ints((name + " k_pca_gather tcell").c_str(), r_tcell.get("tcell"), p.tcell);
+        same((name + " k_pca_gather tval").c_str(), r_tval.get("tval"), p.tval);
+        same((name + " k_pca_gather tcell").c_str(), r_tcell.get("tcell"), p.tcell);
     }
     {
         hipLaunchKernelGGL(k_pca_tptr, dim3(p.F / WG + 1u), dim3(WG), 0, st, d_keys_sorted.d, nnz, p.N, p.F, r_tptr.d);
         g_gpu->launched("k_pca_tptr");
-        same_ints((name + " k_pca_tptr").c_str(), r_tptr.get("tptr"), p.tptr);
+        same((name + " k_pca_tptr").c_str(), r_tptr.get("tptr"), p.tptr);
         GBuf<double> mean(p.F, FILL_F64), var(p.F, FILL_F64);
         hipLaunchKernelGGL(k_pca_meanvar, dim3(2), dim3(wg), 0, st, r_tptr.d, r_tval.d, p.N, p.F, mean.d, var.d);
         g_gpu->launched("k_pca_meanvar");
-        same_bits((name + " k_pca_meanvar mean").c_str(), mean.get("mean"), P.mean);
-        same_bits((name + " k_pca_meanvar var").c_str(), var.get("var"), P.var);
+        same((name + " k_pca_meanvar mean").c_str(), mean.get("mean"), P.mean);
+        same((name + " k_pca_meanvar var").c_str(), var.get("var"), P.var);
     }
     // pca_scale, and k_pca_scale by direct launch
     GOK(pca_scale(ctx, P, d_inv.d));
     scale_values(p, inv);
-    same_bits((name + " scaled val").c_str(), download<double>(P.val.p, nnz), p.val);
-    same_bits((name + " scaled tval").c_str(), download<double>(P.tval.p, nnz), p.tval);
-    same_ints((name + " tcell after the scaling").c_str(), download<uint32_t>(P.tcell.p, nnz), p.tcell);
+    same((name + " scaled val").c_str(), download<double>(P.val.p, nnz), p.val);
+    same((name + " scaled tval").c_str(), download<double>(P.tval.p, nnz), p.tval);
+    same((name + " tcell after the scaling").c_str(), download<uint32_t>(P.tcell.p, nnz), p.tcell);
     if (nnz) {
         hipLaunchKernelGGL(k_pca_scale, dim3(2), dim3(WG), 0, st, r_val.d, r_col.d, nnz, d_inv.d);
         g_gpu->launched("k_pca_scale");
-        same_bits((name + " k_pca_scale").c_str(), r_val.get("val"), p.val);
+        same((name + " k_pca_scale").c_str(), r_val.get("val"), p.val);
     }
     case_done("%s: N=%llu F=%u nnz=%llu median=%g", name.c_str(), (unsigned long long)p.N, p.F, (unsigned long long)p.nnz, p.median);
 }
@@ -684,7 +583,7 @@ static void run_feature_counts(const Case &c, uint32_t G) {
             counts.zero();
             hipLaunchKernelGGL(k_pca_feature_counts, dim3(grid), dim3(wg), 0, g_gpu->ctx->stream, indptr.d, indices.d, data.d, d_bcs.d, N, G, counts.d);
             g_gpu->launched("k_pca_feature_counts");
-            same_ints((name + " wg=" + std::to_string(wg) + " grid=" + std::to_string(grid)).c_str(), counts.get("counts"), want);
+            same((name + " wg=" + std::to_string(wg) + " grid=" + std::to_string(grid)).c_str(), counts.get("counts"), want);
         }
     unsigned long long top = 0;
     for (unsigned long long v : want) top = std::max(top, v);
@@ -858,8 +757,8 @@ static void run_operator(const Case &c, uint32_t wg, Rng &rng) {
         A.rowptr = download<uint64_t>(P.rowptr.p, p.N + 1), A.tptr = download<uint64_t>(P.tptr.p, (uint64_t)p.F + 1);
         A.col = download<uint32_t>(P.col.p, p.nnz), A.tcell = download<uint32_t>(P.tcell.p, p.nnz);
         A.val = download<double>(P.val.p, p.nnz), A.tval = download<double>(P.tval.p, p.nnz);
-        same_ints((c.name + " rowptr").c_str(), A.rowptr, p.rowptr), same_ints((c.name + " tptr").c_str(), A.tptr, p.tptr);
-        same_ints((c.name + " col").c_str(), A.col, p.col), same_ints((c.name + " tcell").c_str(), A.tcell, p.tcell);
+        same((c.name + " rowptr").c_str(), A.rowptr, p.rowptr), same((c.name + " tptr").c_str(), A.tptr, p.tptr);
+        same((c.name + " col").c_str(), A.col, p.col), same((c.name + " tcell").c_str(), A.tcell, p.tcell);
         L.ctx = ctx, L.A = &P, L.m = p.N, L.n = p.F, L.wg = wg, L.ppb = 1;
         GOK(L.init(2));
     }
@@ -915,7 +814,7 @@ static void run_operator(const Case &c, uint32_t wg, Rng &rng) {
             check_atw(name + " k_pca_atw grid " + std::to_string(grid), A, w, Scalar::exact(s1), center, uw, hf.data(), nullptr);
         }
     }
-    case_done("operator on %s: %llu x %u, nnz %llu%s", c.name.c_str(), (unsigned long long)p.N, p.F, (unsigned long long)p.nnz, g_host_only ? " (host only)" : "");
+    case_done("operator on %s: %llu x %u, nnz %llu", c.name.c_str(), (unsigned long long)p.N, p.F, (unsigned long long)p.nnz);
 }
 static void group_operator() {
     Rng rng(0x5eed0be7ull);
@@ -961,7 +860,7 @@ static void run_dots(uint64_t n, uint32_t ncols, VecKind kind, Rng &rng) {
         g_gpu->launched("k_pca_dots");
         hipLaunchKernelGGL(k_pca_dots_finish, dim3((ncols + WG - 1) / WG), dim3(WG), 0, g_gpu->ctx->stream, d_slab.d, n_parts, ncols, d_out.d);
         g_gpu->launched("k_pca_dots_finish");
-        same_bits((name + " ppb=" + std::to_string(ppb) + " slab").c_str(), d_slab.get("slab"), slab);
+        same((name + " ppb=" + std::to_string(ppb) + " slab").c_str(), d_slab.get("slab"), slab);
         const std::vector<double> h = d_out.get("dots");
         for (uint32_t c = 0; c < ncols; c++) judge((name + " ppb=" + std::to_string(ppb)).c_str(), c, out[c], &h[c], refs[c].s, refs[c].bound(ddot(n)));
     }
@@ -1010,9 +909,9 @@ static void run_vector_steps(uint64_t n, Rng &rng) {  // k_pca_axpy, k_pca_scal,
         g_gpu->launched("k_pca_fill_ones");
         std::vector<double> wa = y, ws = y, wo = y;
         for (uint64_t r = 0; r < n; r++) wa[r] = y[r] - alpha * x[r], ws[r] = alpha * y[r], wo[r] = 1.0;
-        same_bits(("axpy " + name).c_str(), a.get("axpy"), wa);  // the padding behind n included: still the NaN it held
-        same_bits(("scal " + name).c_str(), s.get("scal"), ws);
-        same_bits(("fill_ones " + name).c_str(), o.get("ones"), wo);
+        same(("axpy " + name).c_str(), a.get("axpy"), wa);  // the padding behind n included: still the NaN it held
+        same(("scal " + name).c_str(), s.get("scal"), ws);
+        same(("fill_ones " + name).c_str(), o.get("ones"), wo);
     }
 }
 // out[:, c] = X[:, 0:mb] M[:, c], t ascending: through PcaLanczos::small_product in place (the restart's use) and by a direct launch
@@ -1037,7 +936,7 @@ static void run_small_product(uint64_t n, uint32_t mb, uint32_t k, Rng &rng) {
             hipLaunchKernelGGL(k_pca_small_product, dim3(1), dim3(WG), 0, g_gpu->ctx->stream, d_X.d, ld, n, mb, d_M.d, k, d_out.d);
             g_gpu->launched("k_pca_small_product");
             got = d_out.get("out");
-            same_bits((name + " direct").c_str(), got, want);  // the padding rows still hold the NaN of the fill
+            same((name + " direct").c_str(), got, want);  // the padding rows still hold the NaN of the fill
         } else if (!g_host_only) {
             PcaLanczos L;
             L.ctx = g_gpu->ctx, L.A = nullptr, L.m = L.n = n, L.wg = WG, L.ppb = 1;
@@ -1061,17 +960,17 @@ static void group_dense() {
     for (uint64_t n : ns) {
         for (uint32_t nc : cols) run_dots(n, nc, nc % 2u ? VEC_DECADES : VEC_NORMAL, rng), run_update(n, nc, rng);
         run_vector_steps(n, rng);
-        case_done("dense n=%llu: dots and update at %zu column counts, axpy, scal, fill_ones%s", (unsigned long long)n, sizeof(cols) / sizeof(cols[0]), g_host_only ? " (host only)" : "");
+        case_done("dense n=%llu: dots and update at %zu column counts, axpy, scal, fill_ones", (unsigned long long)n, sizeof(cols) / sizeof(cols[0]));
     }
     // n * k off and on a multiple of the workgroup, n = 1, more elements than one workgroup has threads
     const uint64_t sp_n[5] = {1, WV + 1, WG / 2, PR + 1, 3 * PR + 1};
     for (uint64_t n : sp_n) {
         run_small_product(n, 5, 2, rng);
         run_small_product(n, 2 * WPW + 1, 2 * WPW - 2, rng);
-        case_done("small_product n=%llu%s", (unsigned long long)n, g_host_only ? " (host only)" : "");
+        case_done("small_product n=%llu", (unsigned long long)n);
     }
     run_small_product(WV + 1, PCA_MAX_MB, PCA_MAX_MB - 3, rng);
-    case_done("small_product mb=%u%s", PCA_MAX_MB, g_host_only ? " (host only)" : "");
+    case_done("small_product mb=%u", PCA_MAX_MB);
 }
 
 // ---- the projection -------------------------------------------------------------------------------------------------------
@@ -1146,7 +1045,7 @@ static void group_project() {
                     all("project nu=" + std::to_string(nu) + " wg=" + std::to_string(wg) + " grid=" + std::to_string(grid), h.data());
                 }
         }
-        case_done("project nu=%u: %llu rows, %u of %u features mapped%s", nu, (unsigned long long)N, n_used, G, g_host_only ? " (host only)" : "");
+        case_done("project nu=%u: %llu rows, %u of %u features mapped", nu, (unsigned long long)N, n_used, G);
     }
 }
 

@@ -22,14 +22,14 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#include "stage_common.h"
+#include "graph_common.h"
+#include "kernel_test.h"
 
 namespace tsne_under_test {
 #include "tsne.hip"
@@ -37,56 +37,13 @@ namespace tsne_under_test {
 using namespace tsne_under_test;
 
 typedef long double ld_t;
-static const uint32_t CH = CRGPU_TSNE_CAND_CHUNK, PR = TSNE_PART_ROWS;
-static const uint64_t GUARD = 64;
-static const double U = 0x1.0p-53;
-
-[[noreturn]] static void die(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    std::fprintf(stdout, "FAIL ");
-    std::vfprintf(stdout, fmt, ap);
-    std::fprintf(stdout, "\n");
-    va_end(ap);
-    std::fflush(stdout);
-    std::exit(1);
-}
-static bool g_host_only = false;
-static int g_cases = 0;
+static const uint32_t CH = CRGPU_TSNE_CAND_CHUNK, PR = GRAPH_PART_ROWS;
 static double g_worst = 0.0, g_worst_exp = 0.0, g_worst_log = 0.0;
-static void case_done(const char *fmt, ...) {
-    char b[400];
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(b, sizeof(b), fmt, ap);
-    va_end(ap);
-    std::printf("ok   %s%s\n", b, g_host_only ? " (host only)" : "");
-    g_cases++;
-}
-static double gamma_k(double k) { return k * U / (1.0 - k * U); }
 static void within(const char *what, uint64_t at, double got, ld_t ref, double bound) {
     const double dev = (double)fabsl((ld_t)got - ref);
     if (!(dev <= bound)) die("%s[%llu]: %.17g against %.21Lg, off by %.3g, bound %.3g", what, (unsigned long long)at, got, ref, dev, bound);
     if (bound > 0.0) g_worst = std::max(g_worst, dev / bound);
 }
-static void same_bits(const char *what, const std::vector<double> &got, const std::vector<double> &want) {
-    if (got.size() != want.size()) die("%s: %zu values against %zu", what, got.size(), want.size());
-    for (size_t i = 0; i < got.size(); i++)
-        if (std::memcmp(&got[i], &want[i], 8) != 0) die("%s[%zu]: %.17g on the device, %.17g in the order model", what, i, got[i], want[i]);
-}
-
-struct Rng {  // splitmix64
-    uint64_t s;
-    explicit Rng(uint64_t seed) : s(seed) {}
-    uint64_t next() {
-        uint64_t z = (s += 0x9E3779B97F4A7C15ull);
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        return z ^ (z >> 31);
-    }
-    double unit() { return ((double)(next() >> 11) + 0.5) * 0x1.0p-53; }
-    double normal() { return std::sqrt(-2.0 * std::log(unit())) * std::cos(6.283185307179586 * unit()); }
-};
 enum YKind { Y_NORMAL = 0, Y_DECADES = 1, Y_COINCIDENT = 2 };
 static const char *Y_NAMES[3] = {"normal", "twelve decades", "coincident rows"};
 static std::vector<double> make_y(uint32_t n, uint32_t D, YKind kind, uint64_t seed) {
@@ -101,53 +58,6 @@ static std::vector<double> make_y(uint32_t n, uint32_t D, YKind kind, uint64_t s
             for (uint32_t t = 0; t < D; t++) y[(size_t)i * D + t] = y[(size_t)(i - 1) * D + t];  // q = 1 for the pair
     return y;
 }
-
-// ---- the device ----------------------------------------------------------------------------------------------------------------------
-struct Gpu {
-    crgpu_ctx *ctx = nullptr;
-    Gpu() {
-        const int rc = crgpu_create(&ctx, 0, 1, 0, nullptr);
-        if (rc != CRGPU_OK) die("crgpu_create -> %d: %s", rc, crgpu_last_error(nullptr));
-    }
-    ~Gpu() { crgpu_destroy(ctx); }
-    void ok(int rc, const char *what) const {
-        if (rc != CRGPU_OK) die("%s -> %d: %s", what, rc, crgpu_last_error(ctx));
-    }
-    void launched(const char *what) const {
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) die("launch of %s: %s", what, hipGetErrorString(e));
-    }
-};
-static Gpu *g_gpu = nullptr;
-#define GOK(call) g_gpu->ok((call), #call)
-// n elements and GUARD more behind them, filled with one byte before anything is launched (0xFF: every f64 a NaN); get() asserts that
-// the guard came back untouched
-template <typename T>
-struct GBuf {
-    T *d = nullptr;
-    uint64_t n;
-    GBuf(uint64_t n_) : n(n_) {
-        void *p = nullptr;
-        GOK(crgpu_malloc(g_gpu->ctx, &p, (n + GUARD) * sizeof(T)));
-        d = (T *)p;
-        GOK(crgpu_memset(g_gpu->ctx, d, 0xFF, (n + GUARD) * sizeof(T)));
-    }
-    GBuf(const std::vector<T> &h) : GBuf(h.size()) {
-        if (n) GOK(crgpu_memcpy_h2d(g_gpu->ctx, d, h.data(), n * sizeof(T)));
-    }
-    GBuf(const GBuf &) = delete;
-    GBuf &operator=(const GBuf &) = delete;
-    ~GBuf() { (void)crgpu_free(g_gpu->ctx, d); }
-    std::vector<T> get(const char *what) const {
-        std::vector<T> h(n + GUARD);
-        GOK(crgpu_memcpy_d2h(g_gpu->ctx, h.data(), d, (n + GUARD) * sizeof(T)));
-        const unsigned char *g = (const unsigned char *)(h.data() + n);
-        for (uint64_t i = 0; i < GUARD * sizeof(T); i++)
-            if (g[i] != 0xFFu) die("%s: byte %llu behind the %llu elements of the buffer was written", what, (unsigned long long)i, (unsigned long long)n);
-        h.resize(n);
-        return h;
-    }
-};
 
 // ---- the order model -----------------------------------------------------------------------------------------------------------------
 static double model_colsum(const std::vector<double> &a, uint64_t n, uint32_t ld, uint32_t c) {
@@ -287,11 +197,11 @@ static void repulse_case(uint32_t n, YKind kind, bool reference) {
                 hipLaunchKernelGGL(k_tsne_finish, dim3(cr_grid((uint64_t)rows * (D + 1u), TSNE_WG)), dim3(TSNE_WG), 0, g_gpu->ctx->stream, d_slab.d, row0, rows,
                                    n_chunks, D + 1u, d_rep.d);
             }
-            tsne_colsums(g_gpu->ctx, d_rep.d, n, D + 1u, 1u, d_parts.d, d_z.d);
+            cr_colsums(g_gpu->ctx, d_rep.d, n, D + 1u, 1u, d_parts.d, d_z.d);
             g_gpu->launched("k_tsne_repulse");
             (void)d_slab.get("slab");  // only the guard: slots of a last, shorter group keep their fill
-            same_bits("rep", d_rep.get("rep"), rep);
-            same_bits("Z", d_z.get("Z"), std::vector<double>(1, Z));
+            same("rep", d_rep.get("rep"), rep);
+            same("Z", d_z.get("Z"), std::vector<double>(1, Z));
             (void)d_parts.get("parts");
         }
     }
@@ -347,21 +257,21 @@ static void attract_case(uint32_t n, uint32_t K, uint32_t thr, YKind kind) {
                 hipLaunchKernelGGL((k_tsne_attract<D, true>), dim3(cr_grid((uint64_t)n * 64u, TSNE_WG)), dim3(TSNE_WG), 0, g_gpu->ctx->stream, d_ptr.d, d_ind.d, d_val.d,
                                    d_y.d, d_rep.d, d_z.d, st, d_uY.d, d_gains.d, d_ynew.d, d_grad.d);
             }
-            tsne_colsums(g_gpu->ctx, d_ynew.d, n, D, D, d_parts.d, d_sums.d);
+            cr_colsums(g_gpu->ctx, d_ynew.d, n, D, D, d_parts.d, d_sums.d);
             hipLaunchKernelGGL(k_tsne_centre, dim3(cr_grid((uint64_t)n * D, TSNE_WG)), dim3(TSNE_WG), 0, g_gpu->ctx->stream, d_ynew.d, (uint64_t)n, D, d_sums.d, d_yc.d);
             g_gpu->launched("k_tsne_attract");
-            same_bits("grad", d_grad.get("grad"), grad);
-            same_bits("gains", d_gains.get("gains"), gains2);
-            same_bits("uY", d_uY.get("uY"), uY2);
-            same_bits("Ynew", d_ynew.get("Ynew"), ynew);
-            same_bits("Y centred", d_yc.get("Y"), yc);
+            same("grad", d_grad.get("grad"), grad);
+            same("gains", d_gains.get("gains"), gains2);
+            same("uY", d_uY.get("uY"), uY2);
+            same("Ynew", d_ynew.get("Ynew"), ynew);
+            same("Y centred", d_yc.get("Y"), yc);
         }
         // the cost at the device's own P, Y and Z against long double.  r = (p + m) / (q / Z + m) carries 2 D + 6 roundings; log(r) is
         // off by that relative error of r absolutely, plus OCML's 1 ulp = 2^-52 of itself, plus the product's rounding; the row's sum
         // and the 256-row partials add gamma(entries + 256 + partials) of the sum of |terms|
         GBuf<double> d_rowkl(n), d_parts((n + PR - 1u) / PR), d_kl(1);
         hipLaunchKernelGGL(k_tsne_kl<D>, dim3(cr_grid(n, TSNE_WG)), dim3(TSNE_WG), 0, g_gpu->ctx->stream, d_ptr.d, d_ind.d, d_val.d, d_y.d, d_z.d, n, d_rowkl.d);
-        tsne_colsums(g_gpu->ctx, d_rowkl.d, n, 1u, 1u, d_parts.d, d_kl.d);
+        cr_colsums(g_gpu->ctx, d_rowkl.d, n, 1u, 1u, d_parts.d, d_kl.d);
         g_gpu->launched("k_tsne_kl");
         const double kl = d_kl.get("kl")[0];
         ld_t ref = 0.0L;
@@ -445,17 +355,17 @@ static void affinities_case(uint32_t n, uint32_t k, double perplexity, uint64_t 
     GBuf<double> d_val(n2);
     GBuf<int32_t> d_ind(n2);
     GBuf<long long> d_ptr(n + 1u);
-    hipLaunchKernelGGL(k_tsne_keys, dim3(cr_grid(nk, TSNE_WG)), dim3(TSNE_WG), 0, g_gpu->ctx->stream, d_nn.d, n, k, d_keys.d, d_perm.d);
+    hipLaunchKernelGGL(k_pair_keys<uint32_t>, dim3(cr_grid(nk, GRAPH_WG)), dim3(GRAPH_WG), 0, g_gpu->ctx->stream, d_nn.d, n, k, d_keys.d, d_perm.d);
     bool in_tmp = false;
     GOK(cr_radix_sort_u64(g_gpu->ctx, d_keys.d, d_keyt.d, d_perm.d, d_permt.d, n2, 0, std::max(1u, cr_ceil_log2((uint64_t)n * n)), &in_tmp));
     const uint64_t *sk = in_tmp ? d_keyt.d : d_keys.d;
     const uint32_t *sp = in_tmp ? d_permt.d : d_perm.d;
-    GOK(compact(g_gpu->ctx, TsneHeadFlag{sk}, TsneEmitMerged{sk, sp, d_cond.d, n2, d_ckeys.d, d_val.d}, n2, d_block.d, d_block.d + 4096));
+    GOK(compact(g_gpu->ctx, KeyHeadFlag{sk}, TsneEmitMerged{sk, sp, d_cond.d, n2, d_ckeys.d, d_val.d}, n2, d_block.d, d_block.d + 4096));
     uint32_t nnz = 0;
     GOK(read_u32(g_gpu->ctx, d_block.d + 4096, &nnz));
-    hipLaunchKernelGGL(k_tsne_indptr, dim3(cr_grid(std::max<uint64_t>(nnz, n + 1u), TSNE_WG)), dim3(TSNE_WG), 0, g_gpu->ctx->stream, d_ckeys.d, (uint64_t)nnz, n, d_ptr.d,
-                       d_ind.d);
-    g_gpu->launched("k_tsne_indptr");
+    hipLaunchKernelGGL(k_keys_to_csr<uint32_t>, dim3(cr_grid(std::max<uint64_t>(nnz, n + 1u), GRAPH_WG)), dim3(GRAPH_WG), 0, g_gpu->ctx->stream, d_ckeys.d, (uint64_t)nnz, n, d_ptr.d,
+                       d_ind.d, (uint32_t *)nullptr);
+    g_gpu->launched("k_keys_to_csr");
     std::vector<std::pair<uint64_t, double>> pairs;
     for (uint64_t e = 0; e < nk; e++) {
         const uint64_t i = e / k, j = (uint64_t)nn[e];
@@ -479,18 +389,18 @@ static void affinities_case(uint32_t n, uint32_t k, double perplexity, uint64_t 
     std::vector<double> got_val = d_val.get("values");
     got_ind.resize(nnz), got_val.resize(nnz);
     if (got_ind != ind || d_ptr.get("indptr") != ptr) die("the CSR structure differs");
-    same_bits("merged values", got_val, val);
+    same("merged values", got_val, val);
     // the normalisation: the total in the stated order, then the division
     GBuf<double> d_parts((nnz + PR - 1u) / PR), d_total(1);
-    tsne_colsums(g_gpu->ctx, d_val.d, nnz, 1u, 1u, d_parts.d, d_total.d);
+    cr_colsums(g_gpu->ctx, d_val.d, nnz, 1u, 1u, d_parts.d, d_total.d);
     hipLaunchKernelGGL(k_tsne_divide, dim3(cr_grid(nnz, TSNE_WG)), dim3(TSNE_WG), 0, g_gpu->ctx->stream, d_val.d, (uint64_t)nnz, d_total.d);
     g_gpu->launched("k_tsne_divide");
     const double total = model_colsum(val, nnz, 1u, 0u);
-    same_bits("total", d_total.get("total"), std::vector<double>(1, total));
+    same("total", d_total.get("total"), std::vector<double>(1, total));
     for (double &v : val) v = v / total;
     got_val = d_val.get("values");
     got_val.resize(nnz);
-    same_bits("values", got_val, val);
+    same("values", got_val, val);
     case_done("affinities n = %u, K = %u, perplexity %g: %u entries, a row of zeros", n, k, perplexity, nnz);
 }
 static void group_affinities() {

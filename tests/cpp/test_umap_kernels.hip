@@ -28,7 +28,6 @@
 // One line per case, "all tests passed" at the end; the first mismatch or HIP error ends the program with status 1.
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -36,8 +35,9 @@
 #include <string>
 #include <vector>
 
+#include "graph_common.h"
+#include "kernel_test.h"
 #include "philox.h"
-#include "stage_common.h"
 
 namespace umap_under_test {
 #include "umap.hip"
@@ -45,105 +45,14 @@ namespace umap_under_test {
 using namespace umap_under_test;
 
 typedef long double ld_t;
-static const uint64_t GUARD = 64;
-static const double U = 0x1.0p-53;
-
-[[noreturn]] static void die(const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    std::fprintf(stdout, "FAIL ");
-    std::vfprintf(stdout, fmt, ap);
-    std::fprintf(stdout, "\n");
-    va_end(ap);
-    std::fflush(stdout);
-    std::exit(1);
-}
-static bool g_host_only = false;
-static int g_cases = 0;
 static double g_worst_delta = 0.0, g_worst_y = 0.0, g_worst_exp = 0.0, g_worst_psum = 0.0;  // the device's, or with --host-only the order model's
 static double g_model[4] = {0.0, 0.0, 0.0, 0.0};                                        // the order model's beside a device
 static uint64_t g_zero_d2 = 0, g_self = 0, g_clipped = 0, g_neg0 = 0, g_neg15 = 0, g_neg16 = 0;
-static void case_done(const char *fmt, ...) {
-    char b[400];
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(b, sizeof(b), fmt, ap);
-    va_end(ap);
-    std::printf("ok   %s%s\n", b, g_host_only ? " (host only)" : "");
-    g_cases++;
-}
-static double gamma_k(double k) { return k * U / (1.0 - k * U); }
 static void within(double *worst, const char *what, uint64_t at, double got, ld_t ref, double bound) {
     const double dev = (double)fabsl((ld_t)got - ref);
     if (!(dev <= bound)) die("%s[%llu]: %.17g against %.21Lg, off by %.3g, bound %.3g", what, (unsigned long long)at, got, ref, dev, bound);
     if (bound > 0.0) *worst = std::max(*worst, dev / bound);
 }
-template <typename T>
-static void same(const char *what, const std::vector<T> &got, const std::vector<T> &want) {
-    if (got.size() != want.size()) die("%s: %zu values against %zu", what, got.size(), want.size());
-    for (size_t i = 0; i < got.size(); i++)
-        if (std::memcmp(&got[i], &want[i], sizeof(T)) != 0) die("%s[%zu]: %.17g on the device, %.17g in the order model", what, i, (double)got[i], (double)want[i]);
-}
-
-struct Rng {  // splitmix64
-    uint64_t s;
-    explicit Rng(uint64_t seed) : s(seed) {}
-    uint64_t next() {
-        uint64_t z = (s += 0x9E3779B97F4A7C15ull);
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        return z ^ (z >> 31);
-    }
-    double unit() { return ((double)(next() >> 11) + 0.5) * 0x1.0p-53; }
-};
-
-// ---- the device ----------------------------------------------------------------------------------------------------------------------
-struct Gpu {
-    crgpu_ctx *ctx = nullptr;
-    Gpu() {
-        const int rc = crgpu_create(&ctx, 0, 1, 0, nullptr);
-        if (rc != CRGPU_OK) die("crgpu_create -> %d: %s", rc, crgpu_last_error(nullptr));
-    }
-    ~Gpu() { crgpu_destroy(ctx); }
-    void ok(int rc, const char *what) const {
-        if (rc != CRGPU_OK) die("%s -> %d: %s", what, rc, crgpu_last_error(ctx));
-    }
-    void launched(const char *what) const {
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) die("launch of %s: %s", what, hipGetErrorString(e));
-    }
-};
-static Gpu *g_gpu = nullptr;
-#define GOK(call) g_gpu->ok((call), #call)
-// n elements and GUARD more behind them, filled with one byte before anything is launched (0xFF: every f64 a NaN); get() asserts that
-// the guard came back untouched
-template <typename T>
-struct GBuf {
-    T *d = nullptr;
-    uint64_t n;
-    GBuf(uint64_t n_) : n(n_) {
-        void *p = nullptr;
-        GOK(crgpu_malloc(g_gpu->ctx, &p, (n + GUARD) * sizeof(T)));
-        d = (T *)p;
-        GOK(crgpu_memset(g_gpu->ctx, d, 0xFF, (n + GUARD) * sizeof(T)));
-    }
-    GBuf(const std::vector<T> &h) : GBuf(h.size()) {
-        if (n) GOK(crgpu_memcpy_h2d(g_gpu->ctx, d, h.data(), n * sizeof(T)));
-    }
-    GBuf(const GBuf &) = delete;
-    GBuf &operator=(const GBuf &) = delete;
-    ~GBuf() { (void)crgpu_free(g_gpu->ctx, d); }
-    std::vector<T> get(const char *what) const {
-        std::vector<T> h(n + GUARD);
-        GOK(crgpu_memcpy_d2h(g_gpu->ctx, h.data(), d, (n + GUARD) * sizeof(T)));
-        const unsigned char *g = (const unsigned char *)(h.data() + n);
-        for (uint64_t i = 0; i < GUARD * sizeof(T); i++)
-            if (g[i] != 0xFFu) die("%s: byte %llu behind the %llu elements of the buffer was written", what, (unsigned long long)i, (unsigned long long)n);
-        h.resize(n);
-        return h;
-    }
-};
-
 // ---- the order model: the stream -----------------------------------------------------------------------------------------------------
 static void host_philox(uint64_t c0, uint64_t c1, uint64_t k0, uint64_t w[4]) {
     uint64_t c2 = 0, c3 = 0, k1 = 0;
@@ -399,9 +308,9 @@ static void graph_case(uint32_t n, uint32_t k, uint32_t n_epochs, uint64_t seed)
         rho[i] = r, rowsum[i] = s;
     }
     double total = 0.0;
-    for (uint32_t r0 = 0; r0 < n; r0 += UMAP_PART_ROWS) {
+    for (uint32_t r0 = 0; r0 < n; r0 += GRAPH_PART_ROWS) {
         double s = 0.0;
-        for (uint32_t r = r0; r < std::min(n, r0 + UMAP_PART_ROWS); r++) s += rowsum[r];
+        for (uint32_t r = r0; r < std::min(n, r0 + GRAPH_PART_ROWS); r++) s += rowsum[r];
         total += s;
     }
     const double target = std::log2((double)(k + 1u)), den_row = (double)(k + 1u), den_all = (double)n * (double)(k + 1u);
@@ -445,10 +354,10 @@ static void graph_case(uint32_t n, uint32_t k, uint32_t n_epochs, uint64_t seed)
         GBuf<double> d_dist(dist), d_rho((uint64_t)n), d_rowsum((uint64_t)n), d_sigma((uint64_t)n), d_memb(nk), d_parts((uint64_t)1024), d_scal((uint64_t)4);
         GBuf<uint32_t> d_steps((uint64_t)n);
         const uint32_t row_grid = (n + UMAP_WG - 1u) / UMAP_WG;
-        const uint64_t n_parts = (n + UMAP_PART_ROWS - 1u) / UMAP_PART_ROWS;
+        const uint64_t n_parts = (n + GRAPH_PART_ROWS - 1u) / GRAPH_PART_ROWS;
         hipLaunchKernelGGL(k_umap_rows, dim3(row_grid), dim3(UMAP_WG), 0, ctx->stream, (const double *)d_dist.d, n, k, d_rho.d, d_rowsum.d);
-        hipLaunchKernelGGL(k_umap_parts, dim3(1), dim3(UMAP_WG), 0, ctx->stream, (const double *)d_rowsum.d, (uint64_t)n, n_parts, d_parts.d);
-        hipLaunchKernelGGL(k_umap_final, dim3(1), dim3(64), 0, ctx->stream, (const double *)d_parts.d, n_parts, d_scal.d);
+        hipLaunchKernelGGL(k_colparts<double>, dim3(1), dim3(GRAPH_WG), 0, ctx->stream, (const double *)d_rowsum.d, (uint64_t)n, 1u, 1u, n_parts, d_parts.d);
+        hipLaunchKernelGGL(k_colfinal<double>, dim3(1), dim3(64), 0, ctx->stream, (const double *)d_parts.d, n_parts, 1u, d_scal.d);
         hipLaunchKernelGGL(k_umap_search, dim3(row_grid), dim3(UMAP_WG), 0, ctx->stream, (const double *)d_dist.d, (const double *)d_rho.d,
                            (const double *)d_rowsum.d, (const double *)d_scal.d, n, k, target, den_row, den_all, d_sigma.d, d_steps.d, d_memb.d);
         g_gpu->launched("k_umap_search");
@@ -465,8 +374,8 @@ static void graph_case(uint32_t n, uint32_t k, uint32_t n_epochs, uint64_t seed)
         GBuf<double> d_val(n2), d_kept(n2);
         GBuf<int32_t> d_ind(n2);
         GBuf<long long> d_ptr((uint64_t)n + 1);
-        hipLaunchKernelGGL(k_umap_keys, dim3(cr_grid(nk, UMAP_WG)), dim3(UMAP_WG), 0, ctx->stream, (const int32_t *)d_nn.d, n, k, d_keys.d, d_perm.d);
-        g_gpu->launched("k_umap_keys");
+        hipLaunchKernelGGL(k_pair_keys<uint32_t>, dim3(cr_grid(nk, GRAPH_WG)), dim3(GRAPH_WG), 0, ctx->stream, (const int32_t *)d_nn.d, n, k, d_keys.d, d_perm.d);
+        g_gpu->launched("k_pair_keys");
         std::vector<uint64_t> keys(n2);
         for (uint64_t e = 0; e < nk; e++) keys[2 * e] = (e / k) * n + (uint32_t)nn[e], keys[2 * e + 1] = (uint64_t)(uint32_t)nn[e] * n + e / k;
         same("keys", d_keys.get("keys"), keys);
@@ -476,7 +385,7 @@ static void graph_case(uint32_t n, uint32_t k, uint32_t n_epochs, uint64_t seed)
         uint64_t *spare = in_tmp ? d_keys.d : d_keyt.d;
         const uint32_t *sp = in_tmp ? d_permt.d : d_perm.d;
         uint32_t *d_count = d_block.d + 4096;
-        GOK(compact(ctx, UmapHeadFlag{sk}, UmapEmitUnion{sk, sp, d_memb.d, n2, d_ckeys.d, d_val.d}, n2, d_block.d, d_count));
+        GOK(compact(ctx, KeyHeadFlag{sk}, UmapEmitUnion{sk, sp, d_memb.d, n2, d_ckeys.d, d_val.d}, n2, d_block.d, d_count));
         uint32_t merged = 0;
         GOK(read_u32(ctx, d_count, &merged));
         std::map<uint64_t, std::pair<double, double>> runs;
@@ -507,9 +416,9 @@ static void graph_case(uint32_t n, uint32_t k, uint32_t n_epochs, uint64_t seed)
         for (size_t e = 0; e < ukeys.size(); e++)
             if (uval[e] >= wmax / (double)n_epochs) kkeys.push_back(ukeys[e]), kval.push_back(uval[e]);
         if (nnz != kkeys.size() || nnz == merged) die("%u kept entries of %u against %zu (the case is meant to prune)", nnz, merged, kkeys.size());
-        hipLaunchKernelGGL(k_umap_indptr, dim3(cr_grid(std::max<uint64_t>(nnz, n + 1), UMAP_WG)), dim3(UMAP_WG), 0, ctx->stream, (const uint64_t *)spare,
-                           (uint64_t)nnz, n, d_ptr.d, d_ind.d);
-        g_gpu->launched("k_umap_indptr");
+        hipLaunchKernelGGL(k_keys_to_csr<uint32_t>, dim3(cr_grid(std::max<uint64_t>(nnz, n + 1), GRAPH_WG)), dim3(GRAPH_WG), 0, ctx->stream, (const uint64_t *)spare,
+                           (uint64_t)nnz, n, d_ptr.d, d_ind.d, (uint32_t *)nullptr);
+        g_gpu->launched("k_keys_to_csr");
         std::vector<double> got_kept = d_kept.get("kept values");
         std::vector<int32_t> got_ind = d_ind.get("indices"), want_ind;
         got_kept.resize(nnz), got_ind.resize(nnz);

@@ -85,8 +85,18 @@ def test_louvain_kernels_round(exe):
 
 @pytest.mark.gpu
 def test_louvain_kernels_levels(exe):
-    """k_lv_keys, the library's sort, the run heads and k_lv_csr (the union, with rows that name themselves) at n = 63 / 64 / 65 / 255 /
+    """k_lv_keys, the library's sort, the run heads and k_keys_to_csr (the union, with rows that name themselves) at n = 63 / 64 / 65 / 255 /
     257 / 300 / 1100; k_lv_check on the union and on a swapped pair, a weight of 0, an unequal twin; k_lv_degrees; k_lv_identity and
     k_lv_begin; the dense renumbering with unused ids, k_lv_compose; k_lv_agg_keys, the sort with its payload, k_lv_run_sums and the
     CSR of the aggregated graph, down to two communities (runs of tens of thousands of keys)."""
     _run(exe, ["--group", "levels"])
+
+
+@pytest.mark.gpu
+def test_louvain_kernels_csr(exe):
+    """k_keys_to_csr of graph_common.h, the kernel tsne.hip, umap.hip and louvain.hip share, through its launch helper on hand-made sorted
+    distinct keys against a host loop, exact integers, guarded buffers, each with and without the weights pointer: n = 5 with entries in
+    rows 1 and 3 only (empty rows at the start, in the middle and at the end; 3 entries, so the grid is sized by n + 1); n = 2 with
+    every cell; n = 300 with one row of 257 entries and one entry in every other row (more entries than n + 1 and than a workgroup has
+    threads)."""
+    _run(exe, ["--group", "csr"])

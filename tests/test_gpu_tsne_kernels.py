@@ -87,5 +87,5 @@ def test_tsne_kernels_attract(exe):
 @pytest.mark.gpu
 def test_tsne_kernels_affinities(exe):
     """k_tsne_search at K = 3, 90 and 1024 with a row of zeros (200 steps, uniform): the entropy and every p in long double at the
-    device's own beta; k_tsne_keys, the library's sort, the merge, k_tsne_indptr, the total and k_tsne_divide against a host merge."""
+    device's own beta; k_pair_keys, the library's sort, the merge, k_keys_to_csr, the total and k_tsne_divide against a host merge."""
     _run(exe, ["--group", "affinities"])

@@ -67,7 +67,7 @@ def test_umap_kernels_compile_and_the_order_model_is_within_its_bound(exe):
 
 @pytest.mark.gpu
 def test_umap_kernels_graph(exe):
-    """k_umap_rows, the 256-row partials, k_umap_search, k_umap_keys, the library's sort, the union, wmax, the prune and k_umap_indptr at
+    """k_umap_rows, the 256-row partials, k_umap_search, k_pair_keys, the library's sort, the union, wmax, the prune and k_keys_to_csr at
     N = 63 / 64 / 65 / 255 / 257 with K = 3, at K = 29 and at K = 1024: a row of zeros (rho 0, 64 steps, the all-distances floor), a row
     with leading zeros, a row that is named by none it names; psum and every membership in long double at the device's own sigma."""
     _run(exe, ["--group", "graph"])
