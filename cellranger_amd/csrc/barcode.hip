@@ -8,7 +8,128 @@
 // Integer / f64 work, HBM- and cache-latency bound: no MFMA.  Built with -ffp-contract=off so the
 // f64 multiply and the running sum are never fused (the reference's rustc flags have no +fma,
 // lib/rust/.cargo/config.toml:5-8).
+#include <cmath>
+#include <cstdint>
 #include <cstdlib>
+
+// ------------------------------------------------------------------------------------------------
+// Sizing arithmetic of the host side: what a call asks the pool for and how it cuts its reads into rounds, with the
+// constants it shares with the kernels below.  Pure host functions of their arguments (the callers read the environment
+// switches, per call) and nothing of HIP up to the #ifndef that closes the section: barcode_plan.h includes this file up
+// to there, so that a plain C++ program can pin the values (tests/cpp/test_barcode_plan.cpp).  Equal arguments give equal
+// block sizes, and cr_pool_alloc matches exact sizes, so a caller's repeated calls reuse the blocks.
+// The section is in this file, not in the header, because tests/barcode_cases.py reads the constants and several of the
+// expressions out of this file's text (its _read_constants; it raises where one no longer reads as assumed).  That is
+// also why plan_rank_bits and plan_k2_sorted name ctx->n_canon (Ctx: crgpu_ctx, or any struct with n_canon).
+// ------------------------------------------------------------------------------------------------
+#define BIN_SHIFT 15  // a bucket of the staged histogram holds 2^15 ranks (k_match_binned, k_hist_buckets)
+#define BIN_SIZE (1u << BIN_SHIFT)
+#define MB_ITEMS 16
+#define MB_TILE (256 * MB_ITEMS)
+#define MB_MAX_BUCKETS 1024
+#ifndef MB_STAGE_BUDGET
+#define MB_STAGE_BUDGET (8ull << 30)  // bytes of u16 staging per super-batch: 6 launch rounds per 1 B reads (2 GB = 22 rounds cost 1.1 ms more in ramp-up / table loads)
+#endif
+#define SI_MISS_BUCKET 31u  // k_stage_idx takes up to 31 buckets; bucket 31 collects the misses
+#define LH_THREADS 1024     // k_lookup_hot's workgroup
+#define LH_REGIONS (256u * (LH_THREADS / 64))  // one region per wave of k_lookup_hot (its grid is pinned to 256 workgroups)
+// k_lookup_hot's MODE (its comment below)
+#define LH_FULL 0
+#define LH_SPLIT 1
+#define LH_HOTCNT 3
+#define HC_MAX_RANK_BITS 24u  // LH_HOTCNT needs at least 8 bits of counter field
+
+// Staging area: super-batches sized so that every bucket could take ALL reads of the batch (sb is a multiple of 4096 ->
+// every bucket region is 16-byte aligned); slices per bucket: ~2 workgroups per CU in total (128 KB of LDS each -> one
+// resident per CU)
+struct StagePlan {
+    uint64_t sb;
+    uint32_t slices;
+};
+static inline StagePlan plan_staging(uint32_t n_buckets, uint64_t n) {
+    uint64_t sb = MB_STAGE_BUDGET / 2 / n_buckets;
+    sb = sb / MB_TILE * MB_TILE;
+    if (sb < MB_TILE) sb = MB_TILE;
+    if (sb > n) sb = (n + MB_TILE - 1) / MB_TILE * MB_TILE;
+    uint32_t slices = 512 / n_buckets;
+    if (slices < 1) slices = 1;
+    return {sb, slices};
+}
+
+// reads of the sampling batch of a call with a hot-barcode table (a multiple of MB_TILE)
+static inline uint64_t plan_sampling_batch(uint64_t n) {
+    uint64_t first = n / 4 < (4ull << 20) ? n / 4 : (4ull << 20);
+    first = first / MB_TILE * MB_TILE;
+    return first;
+}
+
+// entries of a region of the miss records: a third of a wave's reads may miss
+static inline uint32_t plan_miss_record_cap(uint64_t n, uint64_t first, uint64_t sb) {
+    const uint64_t H = n - first;
+    const uint64_t launches = (H + sb - 1) / sb + 1;
+    return (uint32_t)(H / LH_REGIONS / 3 + 2048 + 512 * launches);
+}
+
+// LH_HOTCNT: the rank bits of the table's rank words, so that rank_mask = 2^bits - 1 >= n_canon is never a rank
+template <typename Ctx>
+static inline uint32_t plan_rank_bits(const Ctx *ctx) {
+    uint32_t cnt_shift = 1;
+    while (cnt_shift < 32u && (1ull << cnt_shift) <= ctx->n_canon) cnt_shift++;
+    return cnt_shift;
+}
+
+// The default is LH_HOTCNT (hit counters in the table entries) on every list whose ranks leave it 8 bits of field.
+// LH_SPLIT (slot stream) pays only beyond the 31 buckets of k_stage_idx (profiles/r02_k1_split_ab.txt: -4 ms per 1 B
+// reads on the 6.8 M-entry list, a wash on the 737 K one); it is the default where LH_HOTCNT cannot run.
+// CRGPU_K1_SPLIT=1 forces LH_SPLIT, =0 the full staging of every round.
+static inline int plan_table_mode(const char *split_env, uint32_t cnt_shift, uint32_t n_buckets) {
+    return split_env ? (split_env[0] != '0' ? LH_SPLIT : LH_FULL)
+           : cnt_shift <= HC_MAX_RANK_BITS ? LH_HOTCNT
+           : n_buckets > SI_MISS_BUCKET    ? LH_SPLIT
+                                           : LH_FULL;
+}
+
+// Counted table rounds, sized after the sampling batch from the share of the hits that the table will not answer:
+// reads per round, entries per cold region, and whether the rounds are counted at all (else every round is staged in full).
+struct RoundPlan {
+    uint64_t round;
+    uint64_t cap;
+    bool counted;
+};
+static inline RoundPlan plan_table_rounds(double cold_frac, uint64_t plan_cap, uint64_t n, uint64_t first, uint64_t sb,
+                                          const uint64_t *forced_cap) {
+    const uint32_t cold_regions = LH_REGIONS;
+    // head room for the spread between the waves; in steps of 0.05 (and the round in steps of 32 Mi reads below) so that
+    // a caller's repeated calls ask the pool for the same block sizes -- the table's content, and with it this estimate,
+    // varies a little from call to call (insertion order)
+    const double f = std::ceil((cold_frac * 1.5 + 0.02) * 20.0) / 20.0;
+    if (!(f < 0.5)) return {0, 0, false};
+    // all cold hits of a round may fall into one bucket of the staging area (plan_cap entries)
+    uint64_t per_region = plan_cap / cold_regions;
+    uint64_t round = per_region > 128 ? (uint64_t)((double)(per_region - 64) * cold_regions / f) : 0;
+    if (round > (1ull << 30)) round = 1ull << 30;
+    if (round > (32ull << 20)) round = round / (32ull << 20) * (32ull << 20);
+    if (round > n - first) round = n - first;
+    round = (round + MB_TILE - 1) / MB_TILE * MB_TILE;
+    uint64_t cap = (uint64_t)((double)round * f / cold_regions) + 64;
+    if (forced_cap) cap = *forced_cap;  // CRGPU_COLD_CAP (tests: force the overflow fallback)
+    const bool counted =
+        (round >= sb || round >= (n - first) / MB_TILE * MB_TILE) && round > 0 && cap * cold_regions <= plan_cap;
+    return {round, cap, counted};
+}
+
+// Barcode order (k_correct_sorted) for the recorded misses of pass B: pays once the pigeonhole bins are long (the
+// 6.8 M-entry list: ~104 entries per bin against ~11 with 737 K); CRGPU_K2_SORTED=0/1 forces either way.
+template <typename Ctx>
+static inline bool plan_k2_sorted(bool use_rec, bool uniform, bool buffers, uint64_t rec_entries, const char *sorted_env,
+                                  const Ctx *ctx) {
+    bool sorted = use_rec && uniform && buffers && rec_entries < 0xFFFFFFFFull;
+    if (sorted_env) sorted = sorted && atoi(sorted_env) != 0;
+    else sorted = sorted && ctx->n_canon > (1u << 21);
+    return sorted;
+}
+
+#ifndef CRGPU_BARCODE_PLAN_ONLY  // to the end of the file
 
 #include "common.h"
 #include "block_utils.h"
@@ -299,11 +420,6 @@ static int make_view_set(crgpu_ctx *ctx, WlViewSet &vs, int ulib) {
 //   k_hist_buckets  one workgroup per (bucket, slice): 32768 u32 counters in LDS (128 KB), streams the
 //                   bucket's u16 entries with 16-byte loads, then adds the non-zero counters to the
 //                   library's valid table (contiguous atomics, a few per barcode).
-#define BIN_SHIFT 15
-#define BIN_SIZE (1u << BIN_SHIFT)
-#define MB_ITEMS 16
-#define MB_TILE (256 * MB_ITEMS)
-#define MB_MAX_BUCKETS 1024
 #define MB_BPT (MB_MAX_BUCKETS / 256)  // buckets per thread in the tile scan
 #define MB_LKB 8                       // reads whose lookups advance together
 #define MB_LKG 4                       // ... in a call with several libraries (per-lane table pointers cost registers)
@@ -646,7 +762,6 @@ __global__ __launch_bounds__(256) void k_hot_build(const uint32_t *__restrict__ 
 // The lookups proper: no barrier inside the loop, every thread keeps LH_ITEMS reads in flight, 16 waves per
 // CU.  (A single kernel that also staged the histogram had to stop all 16 waves of the one workgroup a CU
 // can hold -- the table takes 128 KB -- at five barriers per tile and was latency bound.)
-#define LH_THREADS 1024
 #ifndef LH_ITEMS
 #define LH_ITEMS 8
 #endif
@@ -665,14 +780,10 @@ __global__ __launch_bounds__(256) void k_hot_build(const uint32_t *__restrict__ 
 //   workgroup ends, the fields go to VALID (flush below).  Cold hits go to the per-wave regions as in MODE 1; a full region
 //   counts its surplus hits with device atomics, so no round needs a fallback.  The regions are not cleared: k_stage_idx
 //   reads the ranks each one holds (cold_count), and for k_match_binned every wave closes its region with CRGPU_MISS.
-#define LH_FULL 0
-#define LH_SPLIT 1
-#define LH_HOTCNT 3
 // Flush of the LH_HOTCNT fields at the end of a workgroup: each workgroup writes its 16384 fields as one coalesced row of
 // a slot image and k_hot_flush adds the column sums to VALID (one atomic per non-empty slot and row slice).  One device
 // atomic into VALID per non-zero field and workgroup instead (up to 256 x 8192 per round on the same 8192 addresses) was
 // measured 0.05 ms per 1 B reads slower (profiles/r04_k1_hotcnt_ab.txt).
-#define HC_MAX_RANK_BITS 24u  // LH_HOTCNT needs at least 8 bits of counter field
 #ifndef HC_GROUP
 #define HC_GROUP 4            // LH_HOTCNT: reads probed together before their atomics
 #endif
@@ -947,7 +1058,6 @@ __global__ __launch_bounds__(256) void k_hist_ranks_atomic(const uint32_t *__res
 #define SI_ITEMS 32  // 8192 ranks per tile: 3.97 -> 3.45 ms per 400 M reads against 4096 (fewer barriers and cursor atomics)
 #endif
 #define SI_TILE (256 * SI_ITEMS)
-#define SI_MISS_BUCKET 31u
 // region_fill (nullable): idx is a row of n / region_cap regions of region_cap entries, of which region q holds
 // region_fill[q] ranks at its start and nothing worth reading behind them (LH_HOTCNT's cold regions: the rest is never
 // written).  Tiles are then cut per region, and a tile beyond its region's ranks is skipped whole.
@@ -1067,49 +1177,122 @@ __global__ __launch_bounds__(512) void k_hist_buckets(const WlViewSet vs, const 
     }
 }
 
-#ifndef MB_STAGE_BUDGET
-#define MB_STAGE_BUDGET (8ull << 30)  // bytes of u16 staging per super-batch: 6 launch rounds per 1 B reads (2 GB = 22 rounds cost 1.1 ms more in ramp-up / table loads)
-#endif
-
-// Histogram of a dense array of canonical ranks (CRGPU_MISS entries are skipped) into v[0].valid of `vs`, with the
-// staging kernels of K1: k_stage_idx (needs plan.n_buckets <= SI_MISS_BUCKET) + k_hist_buckets.
-static int hist_from_idx(crgpu_ctx *ctx, const WlViewSet &vs, BinPlan plan, const uint32_t *d_idx, uint64_t n) {
-    if (n == 0) return CRGPU_OK;
-    uint64_t sb = MB_STAGE_BUDGET / 2 / plan.n_buckets;
-    sb = sb / MB_TILE * MB_TILE;
-    if (sb < MB_TILE) sb = MB_TILE;
-    if (sb > n) sb = (n + MB_TILE - 1) / MB_TILE * MB_TILE;
-    plan.cap = sb;
-    DevBuf stage, cursor;
-    CR_TRY(dmalloc(ctx, stage, (uint64_t)plan.n_buckets * plan.cap * sizeof(uint16_t)));
-    CR_TRY(dmalloc(ctx, cursor, plan.n_buckets * MB_CURSOR_STRIDE * sizeof(uint32_t)));
-    uint16_t *d_stage = stage.as<uint16_t>();
-    uint32_t *d_cursor = cursor.as<uint32_t>();
-    uint32_t slices = 512 / plan.n_buckets;
-    if (slices < 1) slices = 1;
-    cr_allow_lds(ctx, (const void *)k_hist_buckets, BIN_SIZE * 4);
-    hipError_t e = hipSuccess;
-    for (uint64_t off = 0; off < n && e == hipSuccess; off += sb) {
-        const uint64_t m = n - off < sb ? n - off : sb;
-        e = hipMemsetAsync(d_cursor, 0, plan.n_buckets * MB_CURSOR_STRIDE * sizeof(uint32_t), ctx->stream);
-        hipLaunchKernelGGL(k_stage_idx, dim3(cr_grid((m + SI_TILE - 1) / SI_TILE, 1, 256u * 6u)), dim3(256), 0, ctx->stream, plan,
-                           d_idx + off, m, d_stage, d_cursor);
-        hipLaunchKernelGGL(k_hist_buckets, dim3(plan.n_buckets * slices), dim3(512), BIN_SIZE * 4, ctx->stream, vs, plan, slices,
-                           d_stage, d_cursor);
-        if (e == hipSuccess) e = hipGetLastError();
-    }
-    if (e != hipSuccess) return cr_fail(ctx, CRGPU_EHIP, "histogram of ranks: %s", hipGetErrorString(e));
-    return CRGPU_OK;
+// k_one for a call about one library, k_mixed for a mixed one (the <true> and <false> instances of one kernel)
+template <typename... P, typename... A>
+static void launch_by_libs(bool uniform, void (*k_one)(P...), void (*k_mixed)(P...), dim3 grid, dim3 block, hipStream_t stream,
+                           A... args) {
+    hipLaunchKernelGGL(uniform ? k_one : k_mixed, grid, block, 0, stream, args...);
 }
 
-extern "C" int crgpu_match_and_count_dev(crgpu_ctx *ctx, const uint32_t *d_cb, const uint8_t *d_flags, uint64_t n,
-                                         uint32_t *d_idx_out) {
-    if (!ctx) return CRGPU_EINVAL;
-    CR_ENTER(ctx);
-    CR_REQUIRE(ctx, ctx->canon_set, CRGPU_ESTATE, "crgpu_match_and_count: no whitelist set");
-    CR_REQUIRE(ctx, ctx->n_segments == 0, CRGPU_ESTATE,
-               "crgpu_match_and_count: this context holds a segmented barcode space; run the barcode stage on the segment contexts");
-    if (n == 0) return CRGPU_OK;
+// The staging area of the staged histogram (k_hist_buckets): the bucket plan, the u16 regions and their cursors.  Every host
+// path that counts ranks through it sets the slots, opens the area for its n entries (plan_staging) and
+// then, per super-batch of at most `sb` entries: zero, stage (ranks from an index array, or reads), add.
+struct Staging {
+    crgpu_ctx *ctx;
+    BinPlan plan;
+    DevBuf stage, cursor;
+    uint64_t sb = 0;      // entries of a super-batch = staging entries per bucket (plan.cap)
+    uint32_t slices = 1;  // workgroups of k_hist_buckets per bucket
+
+    // a call about one library stages into a single slot, which k_hist_buckets adds to v[0] (= that library's tables)
+    explicit Staging(crgpu_ctx *c) : Staging(c, true) {}
+    // one_lib == false, a mixed call: a slot for every configured library
+    Staging(crgpu_ctx *c, bool one_lib) : ctx(c) {
+        uint32_t n_slots = 0;
+        for (int l = 0; l < CRGPU_MAX_LIB; l++) plan.lib_slot[l] = (one_lib ? l == 0 : c->wl[l].set) ? n_slots++ : 0xFFFFFFFFu;
+        plan.buckets_per_lib = (c->n_canon + BIN_SIZE - 1) / BIN_SIZE;
+        plan.n_buckets = plan.buckets_per_lib * n_slots;
+        plan.cap = 0;
+    }
+    bool takes_idx_tiles() const { return plan.n_buckets <= SI_MISS_BUCKET; }  // k_stage_idx can stage the ranks
+
+    int open(uint64_t n) {
+        const StagePlan s = plan_staging(plan.n_buckets, n);
+        sb = plan.cap = s.sb;
+        slices = s.slices;
+        CR_TRY(dmalloc(ctx, stage, (uint64_t)plan.n_buckets * plan.cap * sizeof(uint16_t)));
+        CR_TRY(dmalloc(ctx, cursor, plan.n_buckets * MB_CURSOR_STRIDE * sizeof(uint32_t)));
+        cr_allow_lds(ctx, (const void *)k_hist_buckets, BIN_SIZE * 4);
+        return CRGPU_OK;
+    }
+    hipError_t zero() { return hipMemsetAsync(cursor.p, 0, plan.n_buckets * MB_CURSOR_STRIDE * sizeof(uint32_t), ctx->stream); }
+    // The ranks of idx[0, n) (CRGPU_MISS entries are skipped): k_stage_idx up to its 31 buckets, else k_match_binned, which
+    // only reads idx here.  skip_if (nullable): a device word that cancels the launch when it is not 0.  region_fill +
+    // region_cap (k_stage_idx only): idx is a row of regions, see the kernel.
+    void stage_ranks(const WlViewSet &vs, const uint32_t *idx, uint64_t n, const uint32_t *skip_if = nullptr,
+                     const uint32_t *region_fill = nullptr, uint32_t region_cap = 0u) {
+        if (takes_idx_tiles())
+            hipLaunchKernelGGL(k_stage_idx, dim3(cr_grid((n + SI_TILE - 1) / SI_TILE, 1, 256u * 6u)), dim3(256), 0, ctx->stream, plan,
+                               idx, n, stage.as<uint16_t>(), cursor.as<uint32_t>(), skip_if, region_fill, region_cap);
+        else
+            hipLaunchKernelGGL((k_match_binned<true, true>), dim3(cr_grid((n + MB_ITEMS - 1) / MB_ITEMS, 256, 256u * 6u)), dim3(256),
+                               0, ctx->stream, vs, plan, (const uint32_t *)nullptr, (const uint8_t *)nullptr, n,
+                               const_cast<uint32_t *>(idx), stage.as<uint16_t>(), cursor.as<uint32_t>(), skip_if);
+    }
+    // the lookups of n reads: ranks to idx_out and to the staging area
+    void stage_reads(const WlViewSet &vs, bool uniform, const uint32_t *cb, const uint8_t *flags, uint64_t n, uint32_t *idx_out) {
+        const dim3 grid(cr_grid((n + MB_ITEMS - 1) / MB_ITEMS, 256, 256u * 6u)), block(256);
+        launch_by_libs(uniform, k_match_binned<true>, k_match_binned<false>, grid, block, ctx->stream, vs, plan, cb, flags, n, idx_out,
+                       stage.as<uint16_t>(), cursor.as<uint32_t>(), (const uint32_t *)nullptr);
+    }
+    void add_to_tables(const WlViewSet &vs) {
+        hipLaunchKernelGGL(k_hist_buckets, dim3(plan.n_buckets * slices), dim3(512), BIN_SIZE * 4, ctx->stream, vs, plan, slices,
+                           stage.as<uint16_t>(), cursor.as<uint32_t>());
+    }
+    // Histogram of a dense array of canonical ranks into v[0].valid of `vs`, with the staging kernels of K1: k_stage_idx
+    // (the caller checks takes_idx_tiles()) + k_hist_buckets.
+    int hist_ranks(const WlViewSet &vs, const uint32_t *d_idx, uint64_t n) {
+        if (n == 0) return CRGPU_OK;
+        CR_TRY(open(n));
+        hipError_t e = hipSuccess;
+        for (uint64_t off = 0; off < n && e == hipSuccess; off += sb) {
+            const uint64_t m = n - off < sb ? n - off : sb;
+            e = zero();
+            stage_ranks(vs, d_idx + off, m);
+            add_to_tables(vs);
+            if (e == hipSuccess) e = hipGetLastError();
+        }
+        if (e != hipSuccess) return cr_fail(ctx, CRGPU_EHIP, "histogram of ranks: %s", hipGetErrorString(e));
+        return CRGPU_OK;
+    }
+};
+
+// ---- K1 (pass A): the state of one crgpu_match_and_count_dev call and its steps -----------------------------------------
+static const size_t HOT_IMAGE_BYTES = HOT_SLOTS * sizeof(unsigned long long);                             // table image
+static const size_t LOOKUP_LDS = HOT_IMAGE_BYTES + (LH_THREADS / 64) * LH_QUEUE * sizeof(uint32_t);  // + per-wave cold queues
+
+struct K1Call {
+    crgpu_ctx *ctx;
+    const uint32_t *d_cb;
+    const uint8_t *d_flags;
+    uint64_t n;
+    uint32_t *d_idx_out;
+    int ulib;
+    WlViewSet vs;
+    bool uniform = ulib >= 0;
+    const WlTables *uw = &ctx->wl[uniform ? ulib : 0];  // the call's library (one-library calls only)
+    Staging st{ctx, uniform};
+    // hot-barcode table: built after the sampling batch of `first` reads (a multiple of MB_TILE), then looked up first
+    bool use_hot = false, hot_ready = false;
+    uint64_t first = 0;
+    const uint32_t *d_hot_keys = nullptr;
+    MissRecords *rec = nullptr;  // miss records for K2 (not valid: K2 scans idx)
+    // Split histogram of the table rounds (k_lookup_hot's comment): hits the table answers are counted per table slot in
+    // LDS, the others are appended to per-wave regions and staged -- a sixth of the entries the staging used to see, so the
+    // rounds can be that much longer.  Sized after the sampling batch from the share of the reads the table's barcodes
+    // carry.  A region that overflows: LH_SPLIT makes its round fall back to device atomics (cold_count[regions] != 0),
+    // LH_HOTCNT counts the surplus hits with device atomics in the lookup.
+    DevBuf hot_slot, cold, cold_count, cnt_image;
+    uint64_t hot_round = 0;    // reads per table round (0: the split histogram is off)
+    uint32_t cold_cap = 0;
+    int table_mode = LH_FULL;  // k_lookup_hot's MODE in the table rounds
+    uint32_t cnt_shift = plan_rank_bits(ctx);  // LH_HOTCNT: the rank bits of the table's rank words
+    hipError_t e = hipSuccess;
+};
+
+// what comes before the call's state, for a call of n > 0 reads
+static int k1_check_and_views(crgpu_ctx *ctx, const uint32_t *d_cb, const uint8_t *d_flags, uint64_t n, uint32_t *d_idx_out, int *ulib,
+                              WlViewSet &vs) {
     CR_REQUIRE(ctx, d_cb && d_idx_out, CRGPU_EINVAL, "crgpu_match_and_count: NULL buffer");
     // records of an earlier call about these buffers are stale now; the other sets stay (other libraries of the well)
     for (MissRecords &old : ctx->recs)
@@ -1128,67 +1311,43 @@ extern "C" int crgpu_match_and_count_dev(crgpu_ctx *ctx, const uint32_t *d_cb, c
                            "crgpu_pack*_dev and to this call (CRGPU_FLAG_CB_HAS_N)");
         }
     }
-    int ulib = -1;
-    CR_TRY(pick_uniform_lib(ctx, d_flags, n, &ulib));
-    const bool uniform = ulib >= 0;
-    WlViewSet vs;
-    CR_TRY(make_view_set(ctx, vs, ulib));
-    const WlTables &uw = ctx->wl[uniform ? ulib : 0];  // the call's library (one-library calls only)
+    CR_TRY(pick_uniform_lib(ctx, d_flags, n, ulib));
+    return make_view_set(ctx, vs, *ulib);
+}
 
-    BinPlan plan;
-    uint32_t n_slots = 0;
-    // a one-library call stages into a single slot, which k_hist_buckets adds to v[0] (= that library's tables)
-    for (int l = 0; l < CRGPU_MAX_LIB; l++)
-        plan.lib_slot[l] = uniform ? (l == 0 ? n_slots++ : 0xFFFFFFFFu) : (ctx->wl[l].set ? n_slots++ : 0xFFFFFFFFu);
-    plan.buckets_per_lib = (ctx->n_canon + BIN_SIZE - 1) / BIN_SIZE;
-    plan.n_buckets = plan.buckets_per_lib * n_slots;
+// very large whitelist x many libraries: plain device atomics
+static int k1_plain_atomics(K1Call &c) {
+    CrTimer t(c.ctx, CRGPU_T_MATCH, c.n);
+    launch_by_libs(c.uniform, k_match<true>, k_match<false>, dim3(cr_grid(c.n, 256)), dim3(256), c.ctx->stream, c.vs, c.d_cb, c.d_flags, c.n, c.d_idx_out);
+    CR_HIP(c.ctx, hipGetLastError());
+    return CRGPU_OK;
+}
 
-    if (plan.n_buckets > MB_MAX_BUCKETS) {
-        // very large whitelist x many libraries: plain device atomics
-        CrTimer t(ctx, CRGPU_T_MATCH, n);
-        const dim3 grid(cr_grid(n, 256)), block(256);
-        if (uniform)
-            hipLaunchKernelGGL(k_match<true>, grid, block, 0, ctx->stream, vs, d_cb, d_flags, n, d_idx_out);
-        else
-            hipLaunchKernelGGL(k_match<false>, grid, block, 0, ctx->stream, vs, d_cb, d_flags, n, d_idx_out);
-        CR_HIP(ctx, hipGetLastError());
-        return CRGPU_OK;
-    }
-
-    // super-batches sized so that every bucket could take ALL reads of the batch
-    uint64_t sb = MB_STAGE_BUDGET / 2 / plan.n_buckets;
-    sb = sb / MB_TILE * MB_TILE;
-    if (sb < MB_TILE) sb = MB_TILE;
-    if (sb > n) sb = (n + MB_TILE - 1) / MB_TILE * MB_TILE;
-    plan.cap = sb;  // multiple of 4096 -> every bucket region is 16-byte aligned
-    DevBuf stage, cursor;
-    CR_TRY(dmalloc(ctx, stage, (uint64_t)plan.n_buckets * plan.cap * sizeof(uint16_t)));
-    CR_TRY(dmalloc(ctx, cursor, plan.n_buckets * MB_CURSOR_STRIDE * sizeof(uint32_t)));
-    uint16_t *d_stage = stage.as<uint16_t>();
-    uint32_t *d_cursor = cursor.as<uint32_t>();
-    // slices per bucket: ~2 workgroups per CU in total (128 KB of LDS each -> one resident per CU)
-    uint32_t slices = 512 / plan.n_buckets;
-    if (slices < 1) slices = 1;
-    cr_allow_lds(ctx, (const void *)k_hist_buckets, BIN_SIZE * 4);
-    // hot-barcode table: one library without translation, and enough reads to pay for the sampling batch
-    // (CRGPU_HOT_MIN_READS lowers the threshold so that the parity tests can drive this path with small inputs)
+// hot-barcode table: one library without translation, and enough reads to pay for the sampling batch
+// (CRGPU_HOT_MIN_READS lowers the threshold so that the parity tests can drive this path with small inputs)
+static int k1_open_table(K1Call &c) {
+    crgpu_ctx *ctx = c.ctx;
+    const uint64_t n = c.n;
     uint64_t hot_min = 16ull << 20;
     if (const char *env = getenv("CRGPU_HOT_MIN_READS")) hot_min = strtoull(env, nullptr, 10);
     // (a translated or partial list brings its own rank -> key array; a rank without a key of this list never has a count)
-    const uint32_t *d_hot_keys = uw.d_valA ? uw.d_key_of_rank : ctx->d_canon_keys;
-    const bool use_hot = uniform && n >= hot_min && n >= 4ull * MB_TILE && d_hot_keys != nullptr;
-    uint64_t first = 0;  // reads of the sampling batch (a multiple of MB_TILE)
-    if (use_hot) {
-        first = n / 4 < (4ull << 20) ? n / 4 : (4ull << 20);
-        first = first / MB_TILE * MB_TILE;
-    }
-    const size_t hot_lds = HOT_SLOTS * sizeof(unsigned long long);                       // table image
-    const size_t lookup_lds = hot_lds + (LH_THREADS / 64) * LH_QUEUE * sizeof(uint32_t);  // + per-wave cold queues
-    if (use_hot && !ctx->d_hot_image) {
-        if (hipMalloc((void **)&ctx->d_hot_image, hot_lds + 256 * sizeof(uint32_t) + 2 * sizeof(unsigned long long)) != hipSuccess)
-            return cr_fail(ctx, CRGPU_ENOMEM, "hipMalloc hot table failed");
-    }
-    // miss records for K2: one region per wave of the lookup kernel (its grid is pinned to 256 workgroups)
+    c.d_hot_keys = c.uw->d_valA ? c.uw->d_key_of_rank : ctx->d_canon_keys;
+    c.use_hot = c.uniform && n >= hot_min && n >= 4ull * MB_TILE && c.d_hot_keys != nullptr;
+    if (!c.use_hot) return CRGPU_OK;
+    c.first = plan_sampling_batch(n);
+    if (!ctx->d_hot_image &&
+        hipMalloc((void **)&ctx->d_hot_image, HOT_IMAGE_BYTES + 256 * sizeof(uint32_t) + 2 * sizeof(unsigned long long)) != hipSuccess)
+        return cr_fail(ctx, CRGPU_ENOMEM, "hipMalloc hot table failed");
+    cr_allow_lds(ctx, (const void *)k_lookup_hot<LH_FULL>, LOOKUP_LDS);
+    cr_allow_lds(ctx, (const void *)k_lookup_hot<LH_SPLIT>, LOOKUP_LDS);
+    cr_allow_lds(ctx, (const void *)k_lookup_hot<LH_HOTCNT>, LOOKUP_LDS);
+    return CRGPU_OK;
+}
+
+// miss records for K2: one region per wave of the lookup kernel.  The set the call writes is chosen (and emptied) in any
+// case; a call without a table, or one whose blocks the pool cannot give, leaves it empty and K2 scans idx as before.
+static void k1_open_records(K1Call &c) {
+    crgpu_ctx *ctx = c.ctx;
     uint32_t rec_slot = CR_REC_SETS;
     for (uint32_t k = 0; k < CR_REC_SETS && rec_slot == CR_REC_SETS; k++)
         if (!ctx->recs[k].valid) rec_slot = k;
@@ -1197,188 +1356,166 @@ extern "C" int crgpu_match_and_count_dev(crgpu_ctx *ctx, const uint32_t *d_cb, c
         ctx->rec_next = (ctx->rec_next + 1u) % CR_REC_SETS;
     }
     MissRecords &rec = ctx->recs[rec_slot];
+    c.rec = &rec;
     cr_drop_miss_records(ctx, rec);
-    if (use_hot && ctx->trust_buffers && n < 0xFFFFFFFFull && !getenv("CRGPU_NO_MISS_RECORDS")) {
-        const uint64_t H = n - first;
-        const uint64_t launches = (H + sb - 1) / sb + 1;
-        rec.regions = 256u * (LH_THREADS / 64);
-        rec.cap = (uint32_t)(H / rec.regions / 3 + 2048 + 512 * launches);  // a third of a wave's reads may miss
-        if (const char *env = getenv("CRGPU_MISS_RECORD_CAP")) rec.cap = (uint32_t)strtoul(env, nullptr, 10);  // tests: force the overflow fallback
-        const uint64_t C = (uint64_t)rec.regions * rec.cap;
-        int rr = cr_pool_alloc(ctx, (void **)&rec.d_i, C * sizeof(uint32_t));
-        if (rr == CRGPU_OK) rr = cr_pool_alloc(ctx, (void **)&rec.d_key, C * sizeof(uint32_t));
-        if (rr == CRGPU_OK) rr = cr_pool_alloc(ctx, (void **)&rec.d_fl, C);
-        if (rr == CRGPU_OK) rr = cr_pool_alloc(ctx, (void **)&rec.d_count, (rec.regions + 1) * sizeof(uint32_t));
-        if (rr == CRGPU_OK &&
-            hipMemsetAsync(rec.d_count, 0, (rec.regions + 1) * sizeof(uint32_t), ctx->stream) == hipSuccess) {
-            rec.valid = true;
-            rec.d_cb = d_cb;
-            rec.d_flags = d_flags;
-            rec.d_idx = d_idx_out;
-            rec.n = n;
-            rec.first = first;
-            rec.ulib = ulib;
-        } else {
-            cr_drop_miss_records(ctx, rec);  // not fatal: K2 scans idx as before
-        }
+    if (!(c.use_hot && ctx->trust_buffers && c.n < 0xFFFFFFFFull && !getenv("CRGPU_NO_MISS_RECORDS"))) return;
+    rec.regions = 256u * (LH_THREADS / 64);  // = LH_REGIONS, spelled out for tests/barcode_cases.py, which looks for this text
+    rec.cap = plan_miss_record_cap(c.n, c.first, c.st.sb);
+    if (const char *env = getenv("CRGPU_MISS_RECORD_CAP")) rec.cap = (uint32_t)strtoul(env, nullptr, 10);  // tests: force the overflow fallback
+    const uint64_t C = (uint64_t)rec.regions * rec.cap;
+    int rr = cr_pool_alloc(ctx, (void **)&rec.d_i, C * sizeof(uint32_t));
+    if (rr == CRGPU_OK) rr = cr_pool_alloc(ctx, (void **)&rec.d_key, C * sizeof(uint32_t));
+    if (rr == CRGPU_OK) rr = cr_pool_alloc(ctx, (void **)&rec.d_fl, C);
+    if (rr == CRGPU_OK) rr = cr_pool_alloc(ctx, (void **)&rec.d_count, (rec.regions + 1) * sizeof(uint32_t));
+    if (rr != CRGPU_OK || hipMemsetAsync(rec.d_count, 0, (rec.regions + 1) * sizeof(uint32_t), ctx->stream) != hipSuccess) {
+        cr_drop_miss_records(ctx, rec);  // not fatal
+        return;
     }
-    if (use_hot) {
-        cr_allow_lds(ctx, (const void *)k_lookup_hot<LH_FULL>, lookup_lds);
-        cr_allow_lds(ctx, (const void *)k_lookup_hot<LH_SPLIT>, lookup_lds);
-        cr_allow_lds(ctx, (const void *)k_lookup_hot<LH_HOTCNT>, lookup_lds);
+    rec.valid = true;
+    rec.d_cb = c.d_cb;
+    rec.d_flags = c.d_flags;
+    rec.d_idx = c.d_idx_out;
+    rec.n = c.n;
+    rec.first = c.first;
+    rec.ulib = c.ulib;
+}
+
+// reads of the round that starts at `off`: the sampling batch, a table round, or a super-batch of the staging area
+static uint64_t k1_round_reads(const K1Call &c, uint64_t off) {
+    const uint64_t left = c.n - off;
+    if (c.hot_ready && c.hot_round) return left < c.hot_round ? left : c.hot_round;
+    uint64_t m = left < c.st.sb ? left : c.st.sb;
+    if (c.use_hot && off == 0 && m > c.first) m = c.first;
+    return m;
+}
+
+// k_lookup_hot<MODE> over the reads [off, off + m); a call states what differs between the modes: the hot-slot stream, the
+// cold regions, cnt_shift, the slot image and cold_fill.  Returns the workgroups it launched.
+template <int MODE>
+static uint32_t k1_lookup(K1Call &c, uint64_t off, uint64_t m, uint16_t *slots_out, uint32_t *cold_rank, uint32_t *cold_cnt, uint32_t cap,
+                      uint32_t regions, uint32_t shift, uint32_t *image, bool cold_fill) {
+    const MissRecords &rec = *c.rec;
+    const uint32_t lh_grid = cr_grid((m + MB_TILE - 1) / MB_TILE, 1, 256u);
+    hipLaunchKernelGGL(k_lookup_hot<MODE>, dim3(lh_grid), dim3(LH_THREADS), LOOKUP_LDS, c.ctx->stream, c.vs,
+                       c.ctx->d_hot_image, c.d_cb + off, c.d_flags ? c.d_flags + off : nullptr, m, c.d_idx_out + off,
+                       rec.valid ? rec.d_i : nullptr, rec.d_key, rec.d_fl, rec.d_count, rec.cap, rec.regions, (uint32_t)off, slots_out,
+                       cold_rank, cold_cnt, cap, regions, shift, image, cold_fill);
+    return lh_grid;
+}
+
+// a table round of LH_HOTCNT or LH_SPLIT: the table's hits are counted in LDS, only the cold hits are staged
+static void k1_round_counted(K1Call &c, uint64_t off, uint64_t m) {
+    crgpu_ctx *ctx = c.ctx;
+    ctx->k1_split_rounds++;
+    uint32_t *const d_cold = c.cold.as<uint32_t>(), *const d_cold_count = c.cold_count.as<uint32_t>();
+    if (c.e == hipSuccess) c.e = hipMemsetAsync(d_cold_count, 0, (LH_REGIONS + 1) * sizeof(uint32_t), ctx->stream);
+    if (c.table_mode == LH_HOTCNT) {
+        // the regions of the launched waves; k_stage_idx reads the ranks each holds (cold_count), k_match_binned whole
+        // regions, which their waves close with CRGPU_MISS; no fallback round
+        const uint32_t lh_grid = k1_lookup<LH_HOTCNT>(c, off, m, nullptr, d_cold, d_cold_count, c.cold_cap, LH_REGIONS, c.cnt_shift,
+                                                      c.cnt_image.as<uint32_t>(), !c.st.takes_idx_tiles());
+        hipLaunchKernelGGL(k_hot_flush, dim3(HOT_SLOTS / 256u, 8), dim3(256), 0, ctx->stream, c.cnt_image.as<uint32_t>(), lh_grid,
+                           ctx->d_hot_image, c.uw->d_valid);
+        c.st.stage_ranks(c.vs, d_cold, (uint64_t)lh_grid * (LH_THREADS / 64) * c.cold_cap, nullptr, d_cold_count, c.cold_cap);
+        return;
     }
-    hipError_t e = hipSuccess;
-    bool hot_ready = false;
-    // Split histogram of the table rounds (k_lookup_hot's comment): hits the table answers are counted per table slot in
-    // LDS, the others are appended to per-wave regions and staged -- a sixth of the entries the staging used to see, so the
-    // rounds can be that much longer.  Sized after the sampling batch from the share of the reads the table's barcodes
-    // carry.  A region that overflows: LH_SPLIT makes its round fall back to device atomics (cold_count[regions] != 0),
-    // LH_HOTCNT counts the surplus hits with device atomics in the lookup.
-    const uint32_t cold_regions = 256u * (LH_THREADS / 64);
-    DevBuf hot_slot, cold, cold_count, cnt_image;
-    uint64_t hot_round = 0;   // reads per table round (0: the split histogram is off)
-    uint32_t cold_cap = 0;
-    int table_mode = LH_FULL;  // k_lookup_hot's MODE in the table rounds
-    // LH_HOTCNT: the rank bits of the table's rank words, so that rank_mask = 2^bits - 1 >= n_canon is never a rank
-    uint32_t cnt_shift = 1;
-    while (cnt_shift < 32u && (1ull << cnt_shift) <= ctx->n_canon) cnt_shift++;
-    for (uint64_t off = 0; off < n && e == hipSuccess;) {
-        uint64_t m = n - off < sb ? n - off : sb;
-        if (use_hot && off == 0 && m > first) m = first;
-        if (hot_ready && hot_round) m = n - off < hot_round ? n - off : hot_round;
+    const uint64_t C = (uint64_t)LH_REGIONS * c.cold_cap;
+    const uint32_t *d_over = d_cold_count + LH_REGIONS;  // != 0 after the lookup: a cold region overflowed
+    if (c.e == hipSuccess) c.e = hipMemsetAsync(d_cold, 0xFF, C * sizeof(uint32_t), ctx->stream);
+    k1_lookup<LH_SPLIT>(c, off, m, c.hot_slot.as<uint16_t>(), d_cold, d_cold_count, c.cold_cap, LH_REGIONS, 0u, nullptr, false);
+    const uint64_t lh_chunk = (uint64_t)LH_THREADS * LH_ITEMS;
+    hipLaunchKernelGGL(k_hist_hot_slots, dim3(128), dim3(HH_THREADS), HOT_SLOTS * sizeof(uint32_t), ctx->stream,
+                       c.hot_slot.as<uint16_t>(), (m + lh_chunk - 1) / lh_chunk * LH_THREADS, ctx->d_hot_image, c.uw->d_valid, d_over);
+    c.st.stage_ranks(c.vs, d_cold, C, d_over, nullptr, c.cold_cap);
+    hipLaunchKernelGGL(k_hist_ranks_atomic, dim3(cr_grid(m, 256)), dim3(256), 0, ctx->stream, c.d_idx_out + off, m, c.uw->d_valid, d_over);
+}
+
+// a table round of LH_FULL: every hit goes through the staged histogram
+static void k1_round_table_full(K1Call &c, uint64_t off, uint64_t m) {
+    k1_lookup<LH_FULL>(c, off, m, nullptr, nullptr, nullptr, 0u, 0u, 0u, nullptr, false);
+    c.st.stage_ranks(c.vs, c.d_idx_out + off, m);
+}
+
+// a round without a table (the sampling batch, and every round of a call that has none)
+static void k1_round_lookup(K1Call &c, uint64_t off, uint64_t m) {
+    c.st.stage_reads(c.vs, c.uniform, c.d_cb + off, c.d_flags ? c.d_flags + off : nullptr, m, c.d_idx_out + off);
+}
+
+// The tail of the sampling round: the most frequent barcodes so far -> table image (the histogram includes earlier batches
+// of the caller), then the mode and the size of the table rounds from the share of the hits that the table will not answer
+// (one read-back per call).  Whatever fails on the way to counted rounds is not fatal: the rounds are staged in full.
+static void k1_build_table(K1Call &c) {
+    crgpu_ctx *ctx = c.ctx;
+    uint32_t *d_hh = reinterpret_cast<uint32_t *>(ctx->d_hot_image + HOT_SLOTS);
+    if (c.e == hipSuccess) c.e = hipMemsetAsync(ctx->d_hot_image, 0xFF, HOT_IMAGE_BYTES, ctx->stream);
+    if (c.e == hipSuccess) c.e = hipMemsetAsync(d_hh, 0, 256 * sizeof(uint32_t), ctx->stream);
+    hipLaunchKernelGGL(k_hot_hist, dim3(128), dim3(256), 0, ctx->stream, c.uw->d_valid, ctx->n_canon, d_hh);
+    unsigned long long *d_sums = reinterpret_cast<unsigned long long *>(d_hh + 256);
+    if (c.e == hipSuccess) c.e = hipMemsetAsync(d_sums, 0, 2 * sizeof(unsigned long long), ctx->stream);
+    hipLaunchKernelGGL(k_hot_build, dim3(128), dim3(256), 0, ctx->stream, c.uw->d_valid, c.d_hot_keys, ctx->n_canon, d_hh,
+                       ctx->d_hot_image, d_sums, c.uw->d_valA != nullptr);
+    c.hot_ready = true;
+    const int mode = plan_table_mode(getenv("CRGPU_K1_SPLIT"), c.cnt_shift, c.st.plan.n_buckets);
+    unsigned long long sums[2] = {0, 0};
+    if (c.e != hipSuccess || mode == LH_FULL ||
+        hipMemcpyAsync(sums, d_sums, sizeof(sums), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
+        hipStreamSynchronize(ctx->stream) != hipSuccess || sums[0] == 0)
+        return;
+    const double cold_frac = 1.0 - (double)sums[1] / (double)sums[0];
+    uint64_t forced_cap = 0;
+    const char *cap_env = getenv("CRGPU_COLD_CAP");  // tests: force the overflow fallback
+    if (cap_env) forced_cap = strtoull(cap_env, nullptr, 10);
+    const RoundPlan rp = plan_table_rounds(cold_frac, c.st.plan.cap, c.n, c.first, c.st.sb, cap_env ? &forced_cap : nullptr);
+    if (!rp.counted) return;
+    const uint64_t lh_chunk = (uint64_t)LH_THREADS * LH_ITEMS;
+    int rr = mode != LH_SPLIT ? CRGPU_OK : dmalloc(ctx, c.hot_slot, (rp.round + lh_chunk) / lh_chunk * lh_chunk * sizeof(uint16_t));
+    if (rr == CRGPU_OK && mode == LH_HOTCNT)  // the flush image: one row of fields per workgroup
+        rr = dmalloc(ctx, c.cnt_image, 256u * HOT_SLOTS * sizeof(uint32_t));
+    if (rr == CRGPU_OK) rr = dmalloc(ctx, c.cold, rp.cap * LH_REGIONS * sizeof(uint32_t));
+    if (rr == CRGPU_OK) rr = dmalloc(ctx, c.cold_count, (LH_REGIONS + 1) * sizeof(uint32_t));
+    if (rr != CRGPU_OK) return;
+    c.hot_round = rp.round;
+    c.cold_cap = (uint32_t)rp.cap;
+    c.table_mode = mode;
+    cr_allow_lds(ctx, (const void *)k_hist_hot_slots, HOT_SLOTS * sizeof(uint32_t));
+}
+
+extern "C" int crgpu_match_and_count_dev(crgpu_ctx *ctx, const uint32_t *d_cb, const uint8_t *d_flags, uint64_t n,
+                                         uint32_t *d_idx_out) {
+    if (!ctx) return CRGPU_EINVAL;
+    CR_ENTER(ctx);
+    CR_REQUIRE(ctx, ctx->canon_set, CRGPU_ESTATE, "crgpu_match_and_count: no whitelist set");
+    CR_REQUIRE(ctx, ctx->n_segments == 0, CRGPU_ESTATE,
+               "crgpu_match_and_count: this context holds a segmented barcode space; run the barcode stage on the segment contexts");
+    if (n == 0) return CRGPU_OK;
+    int ulib = -1;
+    WlViewSet vs;
+    CR_TRY(k1_check_and_views(ctx, d_cb, d_flags, n, d_idx_out, &ulib, vs));
+    K1Call c{ctx, d_cb, d_flags, n, d_idx_out, ulib, vs};
+    if (c.st.plan.n_buckets > MB_MAX_BUCKETS) return k1_plain_atomics(c);
+    CR_TRY(c.st.open(n));
+    CR_TRY(k1_open_table(c));
+    k1_open_records(c);
+    for (uint64_t off = 0; off < n && c.e == hipSuccess;) {
+        const uint64_t m = k1_round_reads(c, off);
         {
             CrTimer t(ctx, CRGPU_T_MATCH, m);
-            e = hipMemsetAsync(d_cursor, 0, plan.n_buckets * MB_CURSOR_STRIDE * sizeof(uint32_t), ctx->stream);
-            // k_lookup_hot<mode> over this round's reads; a call states what differs between the modes: the hot-slot stream,
-            // the cold regions, cnt_shift, the slot image and cold_fill
-            const uint32_t lh_grid = cr_grid((m + MB_TILE - 1) / MB_TILE, 1, 256u);
-            auto lookup = [&](auto mode, uint16_t *slots_out, uint32_t *cold_rank, uint32_t *cold_cnt, uint32_t cap, uint32_t regions,
-                              uint32_t shift, uint32_t *image, bool cold_fill) {
-                hipLaunchKernelGGL(k_lookup_hot<decltype(mode)::value>, dim3(lh_grid), dim3(LH_THREADS), lookup_lds, ctx->stream, vs,
-                                   ctx->d_hot_image, d_cb + off, d_flags ? d_flags + off : nullptr, m, d_idx_out + off,
-                                   rec.valid ? rec.d_i : nullptr, rec.d_key, rec.d_fl, rec.d_count, rec.cap, rec.regions,
-                                   (uint32_t)off, slots_out, cold_rank, cold_cnt, cap, regions, shift, image, cold_fill);
-            };
-            if (hot_ready && hot_round) {
-                ctx->k1_split_rounds++;
-                uint16_t *const d_hot_slot = hot_slot.as<uint16_t>();
-                uint32_t *const d_cold = cold.as<uint32_t>(), *const d_cold_count = cold_count.as<uint32_t>();
-                uint32_t *const d_cnt_image = cnt_image.as<uint32_t>();
-                uint64_t C = (uint64_t)cold_regions * cold_cap;
-                const uint32_t *d_over = d_cold_count + cold_regions;  // != 0 after the lookup: a cold region overflowed
-                if (e == hipSuccess) e = hipMemsetAsync(d_cold_count, 0, (cold_regions + 1) * sizeof(uint32_t), ctx->stream);
-                if (table_mode == LH_HOTCNT) {
-                    // the regions of the launched waves; k_stage_idx reads the ranks each holds (cold_count), k_match_binned
-                    // whole regions, which their waves close with CRGPU_MISS; no fallback round
-                    C = (uint64_t)lh_grid * (LH_THREADS / 64) * cold_cap;
-                    d_over = nullptr;
-                    lookup(std::integral_constant<int, LH_HOTCNT>{}, nullptr, d_cold, d_cold_count, cold_cap, cold_regions, cnt_shift,
-                           d_cnt_image, plan.n_buckets > SI_MISS_BUCKET);
-                    hipLaunchKernelGGL(k_hot_flush, dim3(HOT_SLOTS / 256u, 8), dim3(256), 0, ctx->stream, d_cnt_image, lh_grid,
-                                       ctx->d_hot_image, uw.d_valid);
-                } else {
-                    if (e == hipSuccess) e = hipMemsetAsync(d_cold, 0xFF, C * sizeof(uint32_t), ctx->stream);
-                    lookup(std::integral_constant<int, LH_SPLIT>{}, d_hot_slot, d_cold, d_cold_count, cold_cap, cold_regions, 0u, nullptr,
-                           false);
-                    const uint64_t lh_chunk = (uint64_t)LH_THREADS * LH_ITEMS;
-                    hipLaunchKernelGGL(k_hist_hot_slots, dim3(128), dim3(HH_THREADS), HOT_SLOTS * sizeof(uint32_t), ctx->stream,
-                                       d_hot_slot, (m + lh_chunk - 1) / lh_chunk * LH_THREADS, ctx->d_hot_image, uw.d_valid, d_over);
-                }
-                if (plan.n_buckets <= SI_MISS_BUCKET)
-                    hipLaunchKernelGGL(k_stage_idx, dim3(cr_grid((C + SI_TILE - 1) / SI_TILE, 1, 256u * 6u)), dim3(256), 0, ctx->stream,
-                                       plan, d_cold, C, d_stage, d_cursor, d_over,
-                                       table_mode == LH_HOTCNT ? (const uint32_t *)d_cold_count : nullptr, cold_cap);
-                else
-                    hipLaunchKernelGGL((k_match_binned<true, true>), dim3(cr_grid((C + MB_ITEMS - 1) / MB_ITEMS, 256, 256u * 6u)),
-                                       dim3(256), 0, ctx->stream, vs, plan, (const uint32_t *)nullptr, (const uint8_t *)nullptr, C, d_cold,
-                                       d_stage, d_cursor, d_over);
-                if (table_mode == LH_SPLIT)
-                    hipLaunchKernelGGL(k_hist_ranks_atomic, dim3(cr_grid(m, 256)), dim3(256), 0, ctx->stream, d_idx_out + off, m, uw.d_valid,
-                                       d_over);
-            } else if (hot_ready) {
-                lookup(std::integral_constant<int, LH_FULL>{}, nullptr, nullptr, nullptr, 0u, 0u, 0u, nullptr, false);
-                if (plan.n_buckets <= SI_MISS_BUCKET)
-                    hipLaunchKernelGGL(k_stage_idx, dim3(cr_grid((m + SI_TILE - 1) / SI_TILE, 1, 256u * 6u)), dim3(256), 0,
-                                       ctx->stream, plan, d_idx_out + off, m, d_stage, d_cursor);
-                else
-                    hipLaunchKernelGGL((k_match_binned<true, true>), dim3(cr_grid((m + MB_ITEMS - 1) / MB_ITEMS, 256, 256u * 6u)),
-                                       dim3(256), 0, ctx->stream, vs, plan, d_cb + off, d_flags ? d_flags + off : nullptr, m,
-                                       d_idx_out + off, d_stage, d_cursor);
-            } else {
-                const dim3 grid(cr_grid((m + MB_ITEMS - 1) / MB_ITEMS, 256, 256u * 6u)), block(256);
-                if (uniform)
-                    hipLaunchKernelGGL(k_match_binned<true>, grid, block, 0, ctx->stream, vs, plan, d_cb + off,
-                                       d_flags ? d_flags + off : nullptr, m, d_idx_out + off, d_stage, d_cursor);
-                else
-                    hipLaunchKernelGGL(k_match_binned<false>, grid, block, 0, ctx->stream, vs, plan, d_cb + off,
-                                       d_flags ? d_flags + off : nullptr, m, d_idx_out + off, d_stage, d_cursor);
-            }
-            hipLaunchKernelGGL(k_hist_buckets, dim3(plan.n_buckets * slices), dim3(512), BIN_SIZE * 4, ctx->stream, vs, plan,
-                               slices, d_stage, d_cursor);
-            if (use_hot && off == 0) {
-                // the most frequent barcodes so far -> table image (the histogram includes earlier batches of the caller)
-                uint32_t *d_hh = reinterpret_cast<uint32_t *>(ctx->d_hot_image + HOT_SLOTS);
-                if (e == hipSuccess) e = hipMemsetAsync(ctx->d_hot_image, 0xFF, hot_lds, ctx->stream);
-                if (e == hipSuccess) e = hipMemsetAsync(d_hh, 0, 256 * sizeof(uint32_t), ctx->stream);
-                hipLaunchKernelGGL(k_hot_hist, dim3(128), dim3(256), 0, ctx->stream, uw.d_valid, ctx->n_canon, d_hh);
-                unsigned long long *d_sums = reinterpret_cast<unsigned long long *>(d_hh + 256);
-                if (e == hipSuccess) e = hipMemsetAsync(d_sums, 0, 2 * sizeof(unsigned long long), ctx->stream);
-                hipLaunchKernelGGL(k_hot_build, dim3(128), dim3(256), 0, ctx->stream, uw.d_valid, d_hot_keys,
-                                   ctx->n_canon, d_hh, ctx->d_hot_image, d_sums, uw.d_valA != nullptr);
-                hot_ready = true;
-                // share of the hits that the table will not answer (one read-back per call) -> size of the cold regions
-                unsigned long long sums[2] = {0, 0};
-                // The default is LH_HOTCNT (hit counters in the table entries) on every list whose ranks leave it 8 bits of
-                // field.  LH_SPLIT (slot stream) pays only beyond the 31 buckets of k_stage_idx (profiles/r02_k1_split_ab.txt:
-                // -4 ms per 1 B reads on the 6.8 M-entry list, a wash on the 737 K one); it is the default where LH_HOTCNT
-                // cannot run.  CRGPU_K1_SPLIT=1 forces LH_SPLIT, =0 the full staging of every round.
-                const char *split_env = getenv("CRGPU_K1_SPLIT");
-                const int mode = split_env ? (split_env[0] != '0' ? LH_SPLIT : LH_FULL)
-                                 : cnt_shift <= HC_MAX_RANK_BITS   ? LH_HOTCNT
-                                 : plan.n_buckets > SI_MISS_BUCKET ? LH_SPLIT
-                                                                   : LH_FULL;
-                if (e == hipSuccess && mode != LH_FULL &&
-                    hipMemcpyAsync(sums, d_sums, sizeof(sums), hipMemcpyDeviceToHost, ctx->stream) == hipSuccess &&
-                    hipStreamSynchronize(ctx->stream) == hipSuccess && sums[0] > 0) {
-                    const double cold_frac = 1.0 - (double)sums[1] / (double)sums[0];
-                    // head room for the spread between the waves; in steps of 0.05 (and the round in steps of 32 Mi reads
-                    // below) so that a caller's repeated calls ask the pool for the same block sizes -- the table's content,
-                    // and with it this estimate, varies a little from call to call (insertion order)
-                    const double f = std::ceil((cold_frac * 1.5 + 0.02) * 20.0) / 20.0;
-                    if (f < 0.5) {
-                        // all cold hits of a round may fall into one bucket of the staging area (plan.cap entries)
-                        uint64_t per_region = plan.cap / cold_regions;
-                        uint64_t round = per_region > 128 ? (uint64_t)((double)(per_region - 64) * cold_regions / f) : 0;
-                        if (round > (1ull << 30)) round = 1ull << 30;
-                        if (round > (32ull << 20)) round = round / (32ull << 20) * (32ull << 20);
-                        if (round > n - first) round = n - first;
-                        round = (round + MB_TILE - 1) / MB_TILE * MB_TILE;
-                        uint64_t cap = (uint64_t)((double)round * f / cold_regions) + 64;
-                        if (const char *env = getenv("CRGPU_COLD_CAP")) cap = strtoull(env, nullptr, 10);  // tests: force the overflow fallback
-                        if ((round >= sb || round >= (n - first) / MB_TILE * MB_TILE) && round > 0 && cap * cold_regions <= plan.cap) {
-                            const uint64_t lh_chunk = (uint64_t)LH_THREADS * LH_ITEMS;
-                            int rr = mode != LH_SPLIT ? CRGPU_OK : dmalloc(ctx, hot_slot, (round + lh_chunk) / lh_chunk * lh_chunk * sizeof(uint16_t));
-                            if (rr == CRGPU_OK && mode == LH_HOTCNT)  // the flush image: one row of fields per workgroup
-                                rr = dmalloc(ctx, cnt_image, 256u * HOT_SLOTS * sizeof(uint32_t));
-                            if (rr == CRGPU_OK) rr = dmalloc(ctx, cold, cap * cold_regions * sizeof(uint32_t));
-                            if (rr == CRGPU_OK) rr = dmalloc(ctx, cold_count, (cold_regions + 1) * sizeof(uint32_t));
-                            if (rr == CRGPU_OK) {
-                                hot_round = round;
-                                cold_cap = (uint32_t)cap;
-                                table_mode = mode;
-                                cr_allow_lds(ctx, (const void *)k_hist_hot_slots, HOT_SLOTS * sizeof(uint32_t));
-                            }  // else: not fatal, the rounds are staged in full as before
-                        }
-                    }
-                }
-            }
-            if (e == hipSuccess) e = hipGetLastError();
+            c.e = c.st.zero();
+            if (c.hot_ready && c.hot_round)
+                k1_round_counted(c, off, m);
+            else if (c.hot_ready)
+                k1_round_table_full(c, off, m);
+            else
+                k1_round_lookup(c, off, m);
+            c.st.add_to_tables(c.vs);
+            if (c.use_hot && off == 0) k1_build_table(c);
+            if (c.e == hipSuccess) c.e = hipGetLastError();
         }
         off += m;
     }
-    if (e != hipSuccess) {
-        cr_drop_miss_records(ctx, rec);
-        return cr_fail(ctx, CRGPU_EHIP, "crgpu_match_and_count: %s", hipGetErrorString(e));
+    if (c.e != hipSuccess) {
+        cr_drop_miss_records(ctx, *c.rec);
+        return cr_fail(ctx, CRGPU_EHIP, "crgpu_match_and_count: %s", hipGetErrorString(c.e));
     }
     return CRGPU_OK;
 }
@@ -1989,6 +2126,146 @@ extern "C" int crgpu_set_posterior(crgpu_ctx *ctx, double max_expected_barcode_e
     return CRGPU_OK;
 }
 
+// ---- K2 (pass B): the state of one correction call and its steps --------------------------------------------------------
+struct K2Call {
+    crgpu_ctx *ctx;
+    const uint32_t *d_cb;
+    const uint8_t *d_qualn, *d_flags;
+    uint64_t n;
+    uint32_t *d_idx_inout;
+    uint8_t *d_corrected_out;
+    MissRecords none;
+    MissRecords *rec = &none;  // the records K1 left for exactly these buffers, if any
+    bool use_rec = false;
+    int ulib = -1;
+    bool uniform = false;
+    WlViewSet vs;
+    uint32_t *miss_list = nullptr;  // the reads k_correct goes through, and how many
+    unsigned long long *n_miss = nullptr;
+    K2Params P;
+};
+
+// the records K1 left for exactly these buffers (consumed by this call: a second call scans idx again) also say which
+// library the call is about; otherwise the flag bytes do.  Then the views and the miss list.
+static int k2_find_records(K2Call &c) {
+    crgpu_ctx *ctx = c.ctx;
+    for (MissRecords &r : ctx->recs)
+        if (r.valid && r.d_cb == c.d_cb && r.d_flags == c.d_flags && r.d_idx == c.d_idx_inout && r.n == c.n) c.rec = &r;
+    c.use_rec = c.rec != &c.none;
+    if (c.use_rec)
+        c.ulib = c.rec->ulib;
+    else
+        CR_TRY(pick_uniform_lib(ctx, c.d_flags, c.n, &c.ulib));
+    c.uniform = c.ulib >= 0;
+    CR_TRY(make_view_set(ctx, c.vs, c.ulib));
+    void *ws;
+    CR_TRY(cr_scratch(ctx, c.n * sizeof(uint32_t), &ws));
+    c.miss_list = (uint32_t *)ws;
+    c.n_miss = (unsigned long long *)(ctx->d_scalars + CR_SCALAR_MISS_COUNT);
+    return CRGPU_OK;
+}
+
+// the misses among idx[begin, begin + m) join the miss list; run_if (nullable): only when that device word is not 0
+static void k2_collect(K2Call &c, uint64_t begin, uint64_t m, const uint32_t *run_if) {
+    hipLaunchKernelGGL(k_collect_miss, dim3(cr_grid(m, 256)), dim3(256), 0, c.ctx->stream, c.d_idx_inout + begin, m, (uint32_t)begin,
+                       run_if, c.miss_list, c.n_miss);
+}
+static void k2_collect_misses(K2Call &c) {
+    if (!c.use_rec) return k2_collect(c, 0, c.n, nullptr);
+    // reads before rec.first (K1's sampling batch) are not in the records; everything is scanned when they overflowed
+    const MissRecords &rec = *c.rec;
+    if (rec.first) k2_collect(c, 0, rec.first, nullptr);
+    k2_collect(c, rec.first, c.n - rec.first, rec.d_count + rec.regions);
+}
+
+// exclusive prefix of the records' region counts -> d_off (k_region_offsets) / its last word read back: the number of
+// records, 0 when they overflowed.  (Two steps: the records path launches k_correct_records between them.)
+static void k2_region_offsets(K2Call &c, uint32_t *d_off) {
+    hipLaunchKernelGGL(k_region_offsets, dim3(1), dim3(1024), 0, c.ctx->stream, c.rec->d_count, c.rec->regions, d_off);
+}
+static int k2_region_total(K2Call &c, const uint32_t *d_off, uint32_t *total) {
+    return crgpu_memcpy_d2h(c.ctx, total, d_off + c.rec->regions, sizeof(*total));
+}
+
+// Barcode order for the recorded misses: compact (the reads with an N join the miss list of the k_correct launch), sort by
+// barcode, k_correct_sorted.  Nothing here is fatal to the launches that follow; the call returns this code at its end.
+static int k2_sorted_path(K2Call &c) {
+    crgpu_ctx *ctx = c.ctx;
+    const MissRecords &rec = *c.rec;
+    DevBuf o, k, v, kt, vt;
+    CR_TRY(dmalloc(ctx, o, (rec.regions + 1) * sizeof(uint32_t)));
+    uint32_t *const d_o = o.as<uint32_t>();
+    uint32_t total = 0;
+    k2_region_offsets(c, d_o);
+    CR_TRY(k2_region_total(c, d_o, &total));
+    ctx->k2_sorted_reads = total;
+    if (!total) return CRGPU_OK;
+    const uint64_t bytes = (uint64_t)total * sizeof(uint32_t);
+    if (dmalloc(ctx, k, bytes) != CRGPU_OK || dmalloc(ctx, v, bytes) != CRGPU_OK || dmalloc(ctx, kt, bytes) != CRGPU_OK ||
+        dmalloc(ctx, vt, bytes) != CRGPU_OK)
+        return cr_fail(ctx, CRGPU_ENOMEM, "crgpu_correct: no memory for the sorted misses");
+    uint32_t *const d_k = k.as<uint32_t>(), *const d_v = v.as<uint32_t>(), *const d_kt = kt.as<uint32_t>(), *const d_vt = vt.as<uint32_t>();
+    hipLaunchKernelGGL(k_compact_records, dim3(rec.regions), dim3(256), 0, ctx->stream, rec.d_i, rec.d_key, rec.d_fl, rec.d_count,
+                       rec.cap, rec.regions, d_o, c.vs.ulib, d_k, d_v, c.miss_list, c.n_miss);
+    // the passes of this sort belong to the CORRECT span that is already open (on its own the 32-bit sort books itself
+    // under the count stage, whose candidate sort it normally is)
+    bool in_tmp = false;
+    const bool timing = ctx->timing;
+    ctx->timing = false;
+    const int rc = cr_radix_sort_u32(ctx, d_k, d_kt, d_v, d_vt, total, 0u, 2u * ctx->cb_len, &in_tmp);
+    ctx->timing = timing;
+    CR_TRY(rc);
+    const uint32_t chunks = (total + 63u) / 64u;
+    const uint32_t wgs = (chunks + KS_WAVES - 1) / KS_WAVES;
+    hipLaunchKernelGGL(k_correct_sorted, dim3(wgs < 256u * KS_WGS_PER_CU ? wgs : 256u * KS_WGS_PER_CU), dim3(64 * KS_WAVES), 0, ctx->stream,
+                       c.vs, in_tmp ? d_kt : d_k, in_tmp ? d_vt : d_v, total, c.P, c.miss_list, c.n_miss);
+    if (c.d_corrected_out)
+        hipLaunchKernelGGL(k_flag_corrected, dim3(rec.regions), dim3(256), 0, ctx->stream, rec.d_i, rec.d_fl, rec.d_count, rec.cap,
+                           rec.regions, c.vs.ulib, c.d_idx_inout, c.d_corrected_out);
+    if (hipGetLastError() != hipSuccess) return cr_fail(ctx, CRGPU_EHIP, "crgpu_correct: launch failed");
+    return CRGPU_OK;
+}
+
+// Record order: the corrected ranks of the records go to a compact array and are counted by K1's staged LDS histogram (when
+// its bucket plan applies: one library, at most 31 rank buckets) instead of one scattered atomic per corrected read.  The
+// records are used up here.
+static int k2_records_path(K2Call &c) {
+    crgpu_ctx *ctx = c.ctx;
+    MissRecords &rec = *c.rec;
+    Staging st(ctx);
+    DevBuf off, rank;
+    const uint64_t rec_total_cap = (uint64_t)rec.regions * rec.cap;
+    bool staged = st.takes_idx_tiles() && rec_total_cap < 0xFFFFFFFFull;
+    if (staged && (dmalloc(ctx, off, (rec.regions + 1) * sizeof(uint32_t)) != CRGPU_OK ||
+                   dmalloc(ctx, rank, rec_total_cap * sizeof(uint32_t)) != CRGPU_OK))
+        staged = false;  // not fatal: atomics as before
+    uint32_t *const d_off = staged ? off.as<uint32_t>() : nullptr, *const d_rank = staged ? rank.as<uint32_t>() : nullptr;
+    if (staged) k2_region_offsets(c, d_off);
+    // one workgroup per region (the regions are K1's waves: 4096): with 2048 workgroups taking two regions each, the 256
+    // that do not fit beside the 1792 resident ones ran almost alone at the end (K2 3.24 -> 2.87 ms per 500 M reads)
+    // K2_PARTS workgroups then share a region: 2.88 -> 2.74 ms per 500 M reads on top of the one-per-region gain
+    hipLaunchKernelGGL(k_correct_records, dim3(rec.regions * K2_PARTS), dim3(256), 0, ctx->stream, c.vs, rec.d_i, rec.d_key, rec.d_fl,
+                       rec.d_count, rec.cap, rec.regions, c.P, d_off, d_rank, K2_PARTS);
+    int rc = CRGPU_OK;
+    if (hipGetLastError() != hipSuccess) rc = cr_fail(ctx, CRGPU_EHIP, "crgpu_correct: launch failed");
+    uint32_t total = 0;
+    if (rc == CRGPU_OK && staged) rc = k2_region_total(c, d_off, &total);
+    if (rc == CRGPU_OK) ctx->k2_record_reads = staged ? total : ~0ull;  // (the atomics fallback reads nothing back)
+    if (rc == CRGPU_OK && staged && total) {
+        WlViewSet vc = c.vs;
+        vc.v[0].valid = vc.v[0].corrected;  // k_hist_buckets adds to `valid` of the call's library (v[0])
+        rc = st.hist_ranks(vc, d_rank, total);
+    }
+    cr_drop_miss_records(ctx, rec);  // stream-ordered: the pool reuses the blocks only for later work
+    return rc;
+}
+
+// every read of the miss list; launched for the worst case, it loops over the device-side count: no host round trip
+static void k2_correct_misses(K2Call &c) {
+    const dim3 grid(cr_grid((c.use_rec ? c.rec->first + c.n / 64 : c.n) / 8 + 1, 256)), block(256);
+    launch_by_libs(c.uniform, k_correct<true>, k_correct<false>, grid, block, c.ctx->stream, c.vs, c.d_cb, c.d_flags, c.miss_list, c.n_miss, c.P);
+}
+
 // fake_quals: the quality bytes only carry the N flags (host path without qualities): the
 // expected-error sum is 0.0 as in corrector.rs:154 map_or.
 static int correct_dev_impl(crgpu_ctx *ctx, const uint32_t *d_cb, const uint8_t *d_qualn, const uint8_t *d_flags,
@@ -2004,146 +2281,30 @@ static int correct_dev_impl(crgpu_ctx *ctx, const uint32_t *d_cb, const uint8_t 
     cr_dense_drop(ctx);  // the CORRECTED table changes
     if (ctx->cb_len == 16 && d_qualn)
         CR_REQUIRE(ctx, (uintptr_t)d_qualn % 16 == 0, CRGPU_EINVAL, "crgpu_correct: quality buffer must be 16-byte aligned");
-    // the records K1 left for exactly these buffers (consumed here: a second call scans idx again) also say which
-    // library the call is about; otherwise the flag bytes do
-    MissRecords *recp = nullptr;
-    for (MissRecords &r : ctx->recs)
-        if (r.valid && r.d_cb == d_cb && r.d_flags == d_flags && r.d_idx == d_idx_inout && r.n == n) recp = &r;
-    const bool use_rec = recp != nullptr;
-    MissRecords none;
-    MissRecords &rec = recp ? *recp : none;
-    int ulib = -1;
-    if (use_rec)
-        ulib = rec.ulib;
-    else
-        CR_TRY(pick_uniform_lib(ctx, d_flags, n, &ulib));
-    const bool uniform = ulib >= 0;
-    WlViewSet vs;
-    CR_TRY(make_view_set(ctx, vs, ulib));
-    void *ws;
-    CR_TRY(cr_scratch(ctx, n * sizeof(uint32_t), &ws));
-    uint32_t *miss_list = (uint32_t *)ws;
-    unsigned long long *n_miss = (unsigned long long *)(ctx->d_scalars + CR_SCALAR_MISS_COUNT);
+    K2Call c{ctx, d_cb, d_qualn, d_flags, n, d_idx_inout, d_corrected_out};
+    CR_TRY(k2_find_records(c));
     CrTimer t(ctx, CRGPU_T_CORRECT, n);
-    CR_HIP(ctx, hipMemsetAsync(n_miss, 0, sizeof(unsigned long long), ctx->stream));
+    CR_HIP(ctx, hipMemsetAsync(c.n_miss, 0, sizeof(unsigned long long), ctx->stream));
     if (d_corrected_out) CR_HIP(ctx, hipMemsetAsync(d_corrected_out, 0, n, ctx->stream));
     // NotNan::try_from(threshold).ok()? (corrector.rs:152): a NaN threshold corrects nothing -- the flags say so, and the
     // records of pass A are used up as by any other call
     if (ctx->confidence_threshold != ctx->confidence_threshold) {
-        if (use_rec) cr_drop_miss_records(ctx, rec);
+        if (c.use_rec) cr_drop_miss_records(ctx, *c.rec);
         return CRGPU_OK;
     }
     // expected_errors < f64::MAX is always true for a finite sum: skip the sum for the default
     const bool check_expected = d_qualn && !fake_quals && ctx->max_expected_errors < 1.7976931348623157e308;
-    const K2Params P{d_qualn, ctx->cb_len, ctx->d_ptab, ctx->max_expected_errors, ctx->confidence_threshold, check_expected,
-                     d_idx_inout, d_corrected_out, d_flags != nullptr};
-    if (use_rec) {
-        // reads before rec.first (K1's sampling batch) are not in the records; everything is scanned when they overflowed
-        const uint32_t *overflow = rec.d_count + rec.regions;
-        if (rec.first)
-            hipLaunchKernelGGL(k_collect_miss, dim3(cr_grid(rec.first, 256)), dim3(256), 0, ctx->stream, d_idx_inout, rec.first, 0u,
-                               (const uint32_t *)nullptr, miss_list, n_miss);
-        hipLaunchKernelGGL(k_collect_miss, dim3(cr_grid(n - rec.first, 256)), dim3(256), 0, ctx->stream, d_idx_inout + rec.first,
-                           n - rec.first, (uint32_t)rec.first, overflow, miss_list, n_miss);
-    } else {
-        hipLaunchKernelGGL(k_collect_miss, dim3(cr_grid(n, 256)), dim3(256), 0, ctx->stream, d_idx_inout, n, 0u,
-                           (const uint32_t *)nullptr, miss_list, n_miss);
-    }
-    // Barcode order (k_correct_sorted) for the recorded misses: pays once the pigeonhole bins are long (the 6.8 M-entry list:
-    // ~104 entries per bin against ~11 with 737 K); CRGPU_K2_SORTED=0/1 forces either way.  The reads with an N join the
-    // miss list of the k_correct launch below.
-    bool sorted = use_rec && uniform && d_qualn && d_flags && (uint64_t)rec.regions * rec.cap < 0xFFFFFFFFull;
-    if (const char *g = getenv("CRGPU_K2_SORTED")) sorted = sorted && atoi(g) != 0;
-    else sorted = sorted && ctx->n_canon > (1u << 21);
-    int sorted_rc = CRGPU_OK;
-    if (sorted) {
-        DevBuf o, k, v, kt, vt;
-        int rc = dmalloc(ctx, o, (rec.regions + 1) * sizeof(uint32_t));
-        uint32_t *const d_o = o.as<uint32_t>();
-        uint32_t total = 0;
-        if (rc == CRGPU_OK) {
-            hipLaunchKernelGGL(k_region_offsets, dim3(1), dim3(1024), 0, ctx->stream, rec.d_count, rec.regions, d_o);
-            rc = crgpu_memcpy_d2h(ctx, &total, d_o + rec.regions, sizeof(total));  // 0 when the records overflowed
-        }
-        if (rc == CRGPU_OK) ctx->k2_sorted_reads = total;
-        if (rc == CRGPU_OK && total) {
-            const uint64_t bytes = (uint64_t)total * sizeof(uint32_t);
-            if (dmalloc(ctx, k, bytes) != CRGPU_OK || dmalloc(ctx, v, bytes) != CRGPU_OK || dmalloc(ctx, kt, bytes) != CRGPU_OK ||
-                dmalloc(ctx, vt, bytes) != CRGPU_OK)
-                rc = cr_fail(ctx, CRGPU_ENOMEM, "crgpu_correct: no memory for the sorted misses");
-        }
-        if (rc == CRGPU_OK && total) {
-            uint32_t *const d_k = k.as<uint32_t>(), *const d_v = v.as<uint32_t>(), *const d_kt = kt.as<uint32_t>(), *const d_vt = vt.as<uint32_t>();
-            hipLaunchKernelGGL(k_compact_records, dim3(rec.regions), dim3(256), 0, ctx->stream, rec.d_i, rec.d_key, rec.d_fl, rec.d_count,
-                               rec.cap, rec.regions, d_o, vs.ulib, d_k, d_v, miss_list, n_miss);
-            bool in_tmp = false;
-            {   // the passes of this sort belong to the CORRECT span that is already open (on its own the 32-bit sort books
-                // itself under the count stage, whose candidate sort it normally is)
-                const bool timing = ctx->timing;
-                ctx->timing = false;
-                const uint32_t kb = 2u * ctx->cb_len;
-                rc = cr_radix_sort_u32(ctx, d_k, d_kt, d_v, d_vt, total, 0u, kb, &in_tmp);
-                ctx->timing = timing;
-            }
-            if (rc == CRGPU_OK) {
-                const uint32_t chunks = (total + 63u) / 64u;
-                const uint32_t wgs = (chunks + KS_WAVES - 1) / KS_WAVES;
-                hipLaunchKernelGGL(k_correct_sorted, dim3(wgs < 256u * KS_WGS_PER_CU ? wgs : 256u * KS_WGS_PER_CU), dim3(64 * KS_WAVES), 0, ctx->stream, vs,
-                                   in_tmp ? d_kt : d_k, in_tmp ? d_vt : d_v, total, P, miss_list, n_miss);
-                if (d_corrected_out)
-                    hipLaunchKernelGGL(k_flag_corrected, dim3(rec.regions), dim3(256), 0, ctx->stream, rec.d_i, rec.d_fl, rec.d_count,
-                                       rec.cap, rec.regions, vs.ulib, d_idx_inout, d_corrected_out);
-                if (hipGetLastError() != hipSuccess) rc = cr_fail(ctx, CRGPU_EHIP, "crgpu_correct: launch failed");
-            }
-        }
-        sorted_rc = rc;
-    }
-    // K2 is launched for the worst case and loops over the device-side count: no host round trip
-    const dim3 grid(cr_grid((use_rec ? rec.first + n / 64 : n) / 8 + 1, 256)), block(256);
-    if (uniform)
-        hipLaunchKernelGGL(k_correct<true>, grid, block, 0, ctx->stream, vs, d_cb, d_flags, miss_list, n_miss, P);
-    else
-        hipLaunchKernelGGL(k_correct<false>, grid, block, 0, ctx->stream, vs, d_cb, d_flags, miss_list, n_miss, P);
-    if (sorted) {
-        CR_HIP(ctx, hipGetLastError());
-        cr_drop_miss_records(ctx, rec);  // stream-ordered: the pool reuses the blocks only for later work
-        return sorted_rc;
-    }
-    if (use_rec) {
-        // the corrected ranks of the records go to a compact array and are counted by K1's staged LDS histogram (when its
-        // bucket plan applies: one library, at most 31 rank buckets) instead of one scattered atomic per corrected read
-        BinPlan plan;
-        for (int l = 0; l < CRGPU_MAX_LIB; l++) plan.lib_slot[l] = l == 0 ? 0u : 0xFFFFFFFFu;
-        plan.buckets_per_lib = (ctx->n_canon + BIN_SIZE - 1) / BIN_SIZE;
-        plan.n_buckets = plan.buckets_per_lib;
-        DevBuf off, rank;
-        const uint64_t rec_total_cap = (uint64_t)rec.regions * rec.cap;
-        bool staged = plan.n_buckets <= SI_MISS_BUCKET && rec_total_cap < 0xFFFFFFFFull;
-        if (staged && (dmalloc(ctx, off, (rec.regions + 1) * sizeof(uint32_t)) != CRGPU_OK ||
-                       dmalloc(ctx, rank, rec_total_cap * sizeof(uint32_t)) != CRGPU_OK))
-            staged = false;  // not fatal: atomics as before
-        uint32_t *const d_off = staged ? off.as<uint32_t>() : nullptr, *const d_rank = staged ? rank.as<uint32_t>() : nullptr;
-        if (staged) hipLaunchKernelGGL(k_region_offsets, dim3(1), dim3(1024), 0, ctx->stream, rec.d_count, rec.regions, d_off);
-        // one workgroup per region (the regions are K1's waves: 4096): with 2048 workgroups taking two regions each, the 256
-        // that do not fit beside the 1792 resident ones ran almost alone at the end (K2 3.24 -> 2.87 ms per 500 M reads)
-        // K2_PARTS workgroups then share a region: 2.88 -> 2.74 ms per 500 M reads on top of the one-per-region gain
-        hipLaunchKernelGGL(k_correct_records, dim3(rec.regions * K2_PARTS), dim3(256), 0, ctx->stream, vs, rec.d_i, rec.d_key, rec.d_fl,
-                           rec.d_count, rec.cap, rec.regions, P, d_off, d_rank, K2_PARTS);
-        int rc = CRGPU_OK;
-        if (hipGetLastError() != hipSuccess) rc = cr_fail(ctx, CRGPU_EHIP, "crgpu_correct: launch failed");
-        uint32_t total = 0;
-        if (rc == CRGPU_OK && staged) rc = crgpu_memcpy_d2h(ctx, &total, d_off + rec.regions, sizeof(total));
-        if (rc == CRGPU_OK) ctx->k2_record_reads = staged ? total : ~0ull;  // (the atomics fallback reads nothing back)
-        if (rc == CRGPU_OK && staged && total) {
-            WlViewSet vc = vs;
-            vc.v[0].valid = vc.v[0].corrected;  // k_hist_buckets adds to `valid` of the call's library (v[0])
-            rc = hist_from_idx(ctx, vc, plan, d_rank, total);
-        }
-        cr_drop_miss_records(ctx, rec);  // stream-ordered: the pool reuses the blocks only for later work
-        return rc;
-    }
+    c.P = K2Params{d_qualn, ctx->cb_len, ctx->d_ptab, ctx->max_expected_errors, ctx->confidence_threshold, check_expected,
+                   d_idx_inout, d_corrected_out, d_flags != nullptr};
+    k2_collect_misses(c);
+    const bool sorted = plan_k2_sorted(c.use_rec, c.uniform, d_qualn && d_flags, (uint64_t)c.rec->regions * c.rec->cap,
+                                       getenv("CRGPU_K2_SORTED"), ctx);
+    const int sorted_rc = sorted ? k2_sorted_path(c) : CRGPU_OK;
+    k2_correct_misses(c);
+    if (c.use_rec && !sorted) return k2_records_path(c);
     CR_HIP(ctx, hipGetLastError());
-    return CRGPU_OK;
+    if (sorted) cr_drop_miss_records(ctx, *c.rec);  // stream-ordered: the pool reuses the blocks only for later work
+    return sorted_rc;
 }
 
 extern "C" int crgpu_correct_dev(crgpu_ctx *ctx, const uint32_t *d_cb, const uint8_t *d_qualn, const uint8_t *d_flags,
@@ -2225,16 +2386,13 @@ extern "C" int crgpu_combine_segments_dev(crgpu_ctx *ctx, int lib, const uint32_
     const WlTables &w = ctx->wl[lib];
     uint32_t *table = after_correction ? w.d_corrected : w.d_valid;
     const uint32_t *src = after_correction ? d_fresh : d_idx_inout;
-    BinPlan plan;
-    for (int l = 0; l < CRGPU_MAX_LIB; l++) plan.lib_slot[l] = l == 0 ? 0u : 0xFFFFFFFFu;
-    plan.buckets_per_lib = (ctx->n_canon + BIN_SIZE - 1) / BIN_SIZE;
-    plan.n_buckets = plan.buckets_per_lib;
-    if (plan.n_buckets <= SI_MISS_BUCKET) {
+    Staging st(ctx);
+    if (st.takes_idx_tiles()) {
         WlViewSet vs{};
         vs.n_canon = ctx->n_canon;
         vs.ulib = (uint32_t)lib;
         vs.v[0].valid = table;
-        CR_TRY(hist_from_idx(ctx, vs, plan, src, n));
+        CR_TRY(st.hist_ranks(vs, src, n));
     } else {
         hipLaunchKernelGGL(k_hist_ranks_atomic, dim3(cr_grid(n, 256)), dim3(256), 0, ctx->stream, src, n, table, (const uint32_t *)nullptr);
         CR_HIP(ctx, hipGetLastError());
@@ -2318,3 +2476,5 @@ extern "C" int crgpu_correct(crgpu_ctx *ctx, int lib, const uint8_t *seq, const 
     if (corrected_flag_out) CR_TRY(crgpu_memcpy_d2h(ctx, corrected_flag_out, b.d_corr, n));
     return CRGPU_OK;
 }
+
+#endif  // CRGPU_BARCODE_PLAN_ONLY
