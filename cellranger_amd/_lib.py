@@ -353,6 +353,21 @@ class SseqResult(C.Structure):
         (n, C.c_double) for n in ("ms_sums", "ms_exact", "ms_asymptotic", "ms_bh")]
 
 
+class SseqPairArgs(C.Structure):
+    """crgpu_sseq_pair_args"""
+    _fields_ = [(n, C.c_uint32) for n in ("n_features", "wave_min", "wg_min", "reserved")] + [("de_threshold", C.c_double)]
+
+
+class SseqPairResult(C.Structure):
+    """crgpu_sseq_pair_result"""
+    _fields_ = [(n, C.c_void_p) for n in ("use_out", "mean_out", "phi_mm_out", "phi_out", "sums_a_out", "sums_b_out", "norm_mean_a_out", "norm_mean_b_out",
+                                           "log2_fold_change_out", "p_values_out", "adjusted_p_values_out", "below_median_out")] + [
+        (n, C.c_double) for n in ("zeta_hat", "delta", "s_a", "s_b")] + [
+        (n, C.c_uint64) for n in ("n_cells_a", "n_cells_b", "n_exact", "n_asymptotic", "n_terms", "n_de")] + [
+        (n, C.c_uint32) for n in ("n_used", "n_runs")] + [
+        (n, C.c_double) for n in ("ms_median", "ms_sums", "ms_exact", "ms_asymptotic", "ms_bh")]
+
+
 class KnnArgs(C.Structure):
     """crgpu_knn_args"""
     _fields_ = [("query_start", C.c_uint64), ("n_queries", C.c_uint64)] + [
@@ -632,6 +647,11 @@ SYMBOLS = {
     "crgpu_sseq_params_get": (_i, [_vp, _vp, C.POINTER(SseqParamsInfo)]),
     "crgpu_sseq_diffexp_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _vp, _u32, C.POINTER(SseqArgs), C.POINTER(SseqResult)]),
     "crgpu_sseq_adjust_bh": (_i, [_vp, _u64, _vp]),
+    "crgpu_sseq_pairs_create_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, C.POINTER(SseqPairArgs), C.POINTER(_vp)]),
+    "crgpu_sseq_pairs_free": (None, [_vp, _vp]),
+    "crgpu_sseq_pair_dev": (_i, [_vp, _vp, _vp, _u32, _vp, _u32, C.POINTER(SseqPairArgs), C.POINTER(SseqPairResult)]),
+    "crgpu_cluster_medians_dev": (_i, [_vp, _vp, _u64, _u32, _u64, _vp, _u32, _vp, _vp]),
+    "crgpu_linkage_complete": (_i, [_vp, _u32, _u32, _vp]),
     "crgpu_knn_dev": (_i, [_vp, _vp, _u64, _u32, _u64, _u32, C.POINTER(KnnArgs), C.POINTER(KnnResult)]),
     "crgpu_graphclust_num_neighbors": (_i, [_u64, _u32, _dbl, _dbl, C.POINTER(_u32)]),
     "crgpu_knn_cross_dev": (_i, [_vp, _vp, _u64, _u32, _u64, _u32, C.POINTER(KnnCrossArgs), C.POINTER(KnnResult)]),

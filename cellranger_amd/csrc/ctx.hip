@@ -382,6 +382,40 @@ const std::vector<AbiStruct> &abi_table() {
               ABI_F(crgpu_sseq_result, ms_exact),
               ABI_F(crgpu_sseq_result, ms_asymptotic),
               ABI_F(crgpu_sseq_result, ms_bh)),
+        ABI_S(crgpu_sseq_pair_args, ABI_F(crgpu_sseq_pair_args, n_features),
+              ABI_F(crgpu_sseq_pair_args, wave_min),
+              ABI_F(crgpu_sseq_pair_args, wg_min),
+              ABI_F(crgpu_sseq_pair_args, reserved),
+              ABI_F(crgpu_sseq_pair_args, de_threshold)),
+        ABI_S(crgpu_sseq_pair_result, ABI_F(crgpu_sseq_pair_result, use_out),
+              ABI_F(crgpu_sseq_pair_result, mean_out),
+              ABI_F(crgpu_sseq_pair_result, phi_mm_out),
+              ABI_F(crgpu_sseq_pair_result, phi_out),
+              ABI_F(crgpu_sseq_pair_result, sums_a_out),
+              ABI_F(crgpu_sseq_pair_result, sums_b_out),
+              ABI_F(crgpu_sseq_pair_result, norm_mean_a_out),
+              ABI_F(crgpu_sseq_pair_result, norm_mean_b_out),
+              ABI_F(crgpu_sseq_pair_result, log2_fold_change_out),
+              ABI_F(crgpu_sseq_pair_result, p_values_out),
+              ABI_F(crgpu_sseq_pair_result, adjusted_p_values_out),
+              ABI_F(crgpu_sseq_pair_result, below_median_out),
+              ABI_F(crgpu_sseq_pair_result, zeta_hat),
+              ABI_F(crgpu_sseq_pair_result, delta),
+              ABI_F(crgpu_sseq_pair_result, s_a),
+              ABI_F(crgpu_sseq_pair_result, s_b),
+              ABI_F(crgpu_sseq_pair_result, n_cells_a),
+              ABI_F(crgpu_sseq_pair_result, n_cells_b),
+              ABI_F(crgpu_sseq_pair_result, n_exact),
+              ABI_F(crgpu_sseq_pair_result, n_asymptotic),
+              ABI_F(crgpu_sseq_pair_result, n_terms),
+              ABI_F(crgpu_sseq_pair_result, n_de),
+              ABI_F(crgpu_sseq_pair_result, n_used),
+              ABI_F(crgpu_sseq_pair_result, n_runs),
+              ABI_F(crgpu_sseq_pair_result, ms_median),
+              ABI_F(crgpu_sseq_pair_result, ms_sums),
+              ABI_F(crgpu_sseq_pair_result, ms_exact),
+              ABI_F(crgpu_sseq_pair_result, ms_asymptotic),
+              ABI_F(crgpu_sseq_pair_result, ms_bh)),
         ABI_S(crgpu_knn_args, ABI_F(crgpu_knn_args, query_start),
               ABI_F(crgpu_knn_args, n_queries),
               ABI_F(crgpu_knn_args, capacity),

@@ -11,3 +11,4 @@
 #include "multigenome.h"
 #include "rtl_tags.h"
 #include "sseq.h"
+#include "sseq_pair.h"

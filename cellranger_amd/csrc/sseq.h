@@ -345,6 +345,57 @@ __global__ __launch_bounds__(SQ_WG) void k_sq_bh_close(const uint64_t *__restric
     }
 }
 
+// ---- the host arithmetic of the parameters: crgpu_sseq_params_dev and crgpu_sseq_pair_dev (sseq_pair.h) share it, so that a pair of
+// groups gets the bits the sub-matrix of its cells gets ----
+// sf[c] = cnt[c] / median; returns S = sum 1 / sf in the order of cnt
+static double sq_size_factors(const uint32_t *cnt, uint64_t N, double median, std::vector<double> &sf) {
+    sf.resize(N);
+    double S = 0.0;
+    for (uint64_t c = 0; c < N; c++) {
+        sf[c] = (double)cnt[c] / median;
+        S += 1.0 / sf[c];
+    }
+    return S;
+}
+// the G-vectors (mean, var, use, phi_mm, the quantile, delta, phi) from the per-gene sums s1 = sum x / sf, s2 = sum (x / sf)^2;
+// P.n_cells and P.n_features are set
+static int sq_gene_params(crgpu_ctx *ctx, const char *who, crgpu_sseq_params &P, const std::vector<double> &s1, const std::vector<double> &s2, double S) {
+    const uint32_t G = P.n_features;
+    P.mean.resize(G), P.var.resize(G), P.phi_mm.assign(G, 0.0), P.phi.assign(G, std::nan("")), P.use.assign(G, 0);
+    std::vector<double> pm;
+    const double n = (double)P.n_cells;
+    bool any_pos = false;
+    for (uint32_t g = 0; g < G; g++) {
+        const double mean = s1[g] / n, mean_sq = s2[g] / n, var = mean_sq - mean * mean;
+        P.mean[g] = mean, P.var[g] = var;
+        if (!(var > 0.0)) continue;
+        P.use[g] = 1;
+        const double v = (n * var - mean * S) / (mean * mean * S);
+        P.phi_mm[g] = v > 0.0 ? v : 0.0;
+        any_pos = any_pos || P.phi_mm[g] > 0.0;
+        pm.push_back(P.phi_mm[g]);
+    }
+    P.n_used = (uint32_t)pm.size();
+    CR_REQUIRE(ctx, !pm.empty(), CRGPU_EINVAL, "%s: no gene varies over the cells", who);
+    std::vector<double> srt(pm);
+    std::sort(srt.begin(), srt.end());
+    P.zeta_hat = cr_quantile_sorted(srt, SQ_ZETA_QUANTILE);
+    const double pm_mean = cr_pairwise_sum(pm.data(), pm.size()) / (double)pm.size();
+    std::vector<double> q1(pm.size()), q2(pm.size());
+    for (size_t i = 0; i < pm.size(); i++) q1[i] = (pm[i] - pm_mean) * (pm[i] - pm_mean), q2[i] = (pm[i] - P.zeta_hat) * (pm[i] - P.zeta_hat);
+    const double num = cr_pairwise_sum(q1.data(), q1.size()) / (double)(G - 1u), den = cr_pairwise_sum(q2.data(), q2.size()) / (double)(G - 2u);
+    // every phi_mm 0: the Python leaves delta 0 / 0 and sets phi to 0 (the Poisson limit); otherwise a zero denominator is refused
+    CR_REQUIRE(ctx, !any_pos || den > 0.0, CRGPU_EINVAL, "%s: every moment dispersion equals the shrinkage target, delta is x / 0", who);
+    P.delta = any_pos ? num / den : std::nan("");
+    for (uint32_t g = 0; g < G; g++)
+        if (P.use[g]) {
+            P.phi[g] = any_pos ? (1.0 - P.delta) * P.phi_mm[g] + P.delta * P.zeta_hat : 0.0;
+            // delta above 1 can push a gene below 0, where the negative binomial has no meaning (the Python goes on to NaN)
+            CR_REQUIRE(ctx, P.phi[g] >= 0.0, CRGPU_EINVAL, "%s: the shrunken dispersion of gene %u is %g (delta = %g)", who, g, P.phi[g], P.delta);
+        }
+    return CRGPU_OK;
+}
+
 // ---- the entry points ----------------------------------------------------------------------------------------------------------------------
 extern "C" void crgpu_sseq_params_free(crgpu_ctx *ctx, crgpu_sseq_params *p) {
     if (!p) return;
@@ -381,12 +432,7 @@ extern "C" int crgpu_sseq_params_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, 
     const double median = cr_median_sorted(sorted);
     std::unique_ptr<crgpu_sseq_params> P(new crgpu_sseq_params);
     P->n_cells = N, P->n_features = G;
-    P->sf.resize(N);
-    double S = 0.0;
-    for (uint64_t c = 0; c < N; c++) {
-        P->sf[c] = (double)cnt[c] / median;
-        S += 1.0 / P->sf[c];
-    }
+    const double S = sq_size_factors(cnt.data(), N, median, P->sf);
 
     // the transpose by one sort, then a wave per gene
     DevBuf sf_b, k_b, kt_b, v_b, vt_b, s1_b, s2_b;
@@ -420,39 +466,7 @@ extern "C" int crgpu_sseq_params_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, 
     CR_TRY(crgpu_memcpy_d2h(ctx, s1.data(), s1_b.p, G * sizeof(double)));
     CR_TRY(crgpu_memcpy_d2h(ctx, s2.data(), s2_b.p, G * sizeof(double)));
 
-    // the G-vectors on the host
-    P->mean.resize(G), P->var.resize(G), P->phi_mm.assign(G, 0.0), P->phi.assign(G, std::nan("")), P->use.assign(G, 0);
-    std::vector<double> pm;
-    const double n = (double)N;
-    bool any_pos = false;
-    for (uint32_t g = 0; g < G; g++) {
-        const double mean = s1[g] / n, mean_sq = s2[g] / n, var = mean_sq - mean * mean;
-        P->mean[g] = mean, P->var[g] = var;
-        if (!(var > 0.0)) continue;
-        P->use[g] = 1;
-        const double v = (n * var - mean * S) / (mean * mean * S);
-        P->phi_mm[g] = v > 0.0 ? v : 0.0;
-        any_pos = any_pos || P->phi_mm[g] > 0.0;
-        pm.push_back(P->phi_mm[g]);
-    }
-    P->n_used = (uint32_t)pm.size();
-    CR_REQUIRE(ctx, !pm.empty(), CRGPU_EINVAL, "crgpu_sseq_params_dev: no gene varies over the cells");
-    std::vector<double> srt(pm);
-    std::sort(srt.begin(), srt.end());
-    P->zeta_hat = cr_quantile_sorted(srt, SQ_ZETA_QUANTILE);
-    const double pm_mean = cr_pairwise_sum(pm.data(), pm.size()) / (double)pm.size();
-    std::vector<double> q1(pm.size()), q2(pm.size());
-    for (size_t i = 0; i < pm.size(); i++) q1[i] = (pm[i] - pm_mean) * (pm[i] - pm_mean), q2[i] = (pm[i] - P->zeta_hat) * (pm[i] - P->zeta_hat);
-    const double num = cr_pairwise_sum(q1.data(), q1.size()) / (double)(G - 1u), den = cr_pairwise_sum(q2.data(), q2.size()) / (double)(G - 2u);
-    // every phi_mm 0: the Python leaves delta 0 / 0 and sets phi to 0 (the Poisson limit); otherwise a zero denominator is refused
-    CR_REQUIRE(ctx, !any_pos || den > 0.0, CRGPU_EINVAL, "crgpu_sseq_params_dev: every moment dispersion equals the shrinkage target, delta is x / 0");
-    P->delta = any_pos ? num / den : std::nan("");
-    for (uint32_t g = 0; g < G; g++)
-        if (P->use[g]) {
-            P->phi[g] = any_pos ? (1.0 - P->delta) * P->phi_mm[g] + P->delta * P->zeta_hat : 0.0;
-            // delta above 1 can push a gene below 0, where the negative binomial has no meaning (the Python goes on to NaN)
-            CR_REQUIRE(ctx, P->phi[g] >= 0.0, CRGPU_EINVAL, "crgpu_sseq_params_dev: the shrunken dispersion of gene %u is %g (delta = %g)", g, P->phi[g], P->delta);
-        }
+    CR_TRY(sq_gene_params(ctx, "crgpu_sseq_params_dev", *P, s1, s2, S));
 
     CR_TRY(cr_pool_alloc(ctx, (void **)&P->d_sf, N * sizeof(double)));
     crgpu_sseq_params *raw = P.release();
@@ -486,67 +500,35 @@ extern "C" int crgpu_sseq_params_get(crgpu_ctx *ctx, const crgpu_sseq_params *p,
     return CRGPU_OK;
 }
 
-extern "C" int crgpu_sseq_diffexp_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const crgpu_sseq_params *P, const int32_t *labels, uint32_t K,
-                                      const crgpu_sseq_args *a, crgpu_sseq_result *res) {
-    if (!ctx || !m || !P || !labels || !a || !res) return CRGPU_EINVAL;
-    CR_ENTER(ctx);
-    const uint64_t N = m->n_barcodes;
-    const uint32_t G = P->n_features;
-    CR_REQUIRE(ctx, G >= 3 && N >= 2, CRGPU_EINVAL, "crgpu_sseq_diffexp_dev: %u features and %llu cells, at least 3 and 2", G, (unsigned long long)N);
-    CR_REQUIRE(ctx, K >= 2 && K <= CRGPU_SSEQ_MAX_K, CRGPU_EINVAL, "crgpu_sseq_diffexp_dev: %u clusters, 2 to %u", K, CRGPU_SSEQ_MAX_K);
-    CR_REQUIRE(ctx, P->n_cells == N && (a->n_features == 0 || a->n_features == G), CRGPU_EINVAL,
-               "crgpu_sseq_diffexp_dev: the parameters are those of a %u x %llu matrix, this one is %u x %llu", G, (unsigned long long)P->n_cells,
-               a->n_features ? a->n_features : G, (unsigned long long)N);
-    std::vector<uint64_t> size(K, 0);
-    for (uint64_t c = 0; c < N; c++) {
-        CR_REQUIRE(ctx, labels[c] >= 1 && (uint32_t)labels[c] <= K, CRGPU_EINVAL, "crgpu_sseq_diffexp_dev: label %d of cell %llu, 1 to %u", labels[c],
-                   (unsigned long long)c, K);
-        size[labels[c] - 1]++;
-    }
-    for (uint32_t c = 0; c < K; c++) CR_REQUIRE(ctx, size[c] > 0, CRGPU_EINVAL, "crgpu_sseq_diffexp_dev: cluster %u is empty", c + 1u);
+// the results of sq_run_tests that stay on the device: [K][G] each
+struct SqTested {
+    DevBuf p_b, adj_b, side_b;
+    std::vector<uint64_t> n_exact, n_big;
+};
+// The exact and asymptotic tests of K clusters and Benjamini-Hochberg over the used genes of each: xin [K][G] = x_a, total [G] = x_a + x_b,
+// s_a / s_b [K].  Fills res->ms_exact, ms_asymptotic, ms_bh, n_terms and the kernel classes.  crgpu_sseq_diffexp_dev and
+// crgpu_sseq_pair_dev (sseq_pair.h, K = 1) share it.
+static int sq_run_tests(crgpu_ctx *ctx, const char *who, const crgpu_sseq_params &P, uint32_t K, const std::vector<uint64_t> &xin,
+                        const std::vector<uint64_t> &total, const std::vector<double> &s_a, const std::vector<double> &s_b, const crgpu_sseq_args *a,
+                        crgpu_sseq_result *res, SqTested &T) {
+    const uint32_t G = P.n_features;
     const uint32_t short_max = a->wave_min == 0u ? SQ_SHORT : std::min(a->wave_min - 1u, SQ_SHORT);  // terms of the short class at the most
     const uint64_t wg_min = a->wg_min ? a->wg_min : SQ_WG_MIN_DEFAULT;
     const size_t KG = (size_t)K * G;
-
-    // the group sums
-    auto t0 = std::chrono::steady_clock::now();
-    DevBuf lab_b, sums_b;
-    CR_TRY(dmalloc(ctx, lab_b, N * sizeof(int32_t)));
-    CR_TRY(dmalloc(ctx, sums_b, KG * sizeof(uint64_t)));
-    CR_TRY(crgpu_memcpy_h2d(ctx, lab_b.p, labels, N * sizeof(int32_t)));
-    CR_HIP(ctx, hipMemsetAsync(sums_b.p, 0, KG * sizeof(uint64_t), ctx->stream));
-    {
-        CrTimer t(ctx, CRGPU_T_MATRIX, m->nnz);
-        hipLaunchKernelGGL(k_sq_group_sums, dim3(cr_grid(N * 64, SQ_WG)), dim3(SQ_WG), 0, ctx->stream, (const long long *)m->d_indptr, m->d_indices, m->d_data, N,
-                           G, lab_b.as<int32_t>(), sums_b.as<unsigned long long>());
-        CR_HIP(ctx, hipGetLastError());
-    }
-    std::vector<uint64_t> xin(KG);
-    CR_TRY(crgpu_memcpy_d2h(ctx, xin.data(), sums_b.p, KG * sizeof(uint64_t)));
-    res->ms_sums = cr_ms_since(t0);
-
-    // per cluster the sums of the size factors, in cell order; per gene the total
-    std::vector<double> s_a(K, 0.0), s_b(K, 0.0);
-    for (uint32_t c = 0; c < K; c++)
-        for (uint64_t i = 0; i < N; i++) {
-            if ((uint32_t)labels[i] == c + 1u) s_a[c] += P->sf[i]; else s_b[c] += P->sf[i];
-        }
-    std::vector<uint64_t> total(G, 0);
-    for (uint32_t c = 0; c < K; c++)
-        for (uint32_t g = 0; g < G; g++) total[g] += xin[(size_t)c * G + g];
 
     // the work lists
     std::vector<SqTest> t_short, t_wave, t_wg;
     std::vector<SqBig> t_big;
     std::vector<uint32_t> used;
-    std::vector<uint64_t> n_exact(K, 0), n_big(K, 0);
+    std::vector<uint64_t> &n_exact = T.n_exact, &n_big = T.n_big;
+    n_exact.assign(K, 0), n_big.assign(K, 0);
     uint64_t n_terms = 0;
     for (uint32_t g = 0; g < G; g++)
-        if (P->use[g]) used.push_back(g);
+        if (P.use[g]) used.push_back(g);
     for (uint32_t c = 0; c < K; c++)
         for (uint32_t g : used) {
             const uint64_t xa = xin[(size_t)c * G + g], xb = total[g] - xa;
-            const double mu = P->mean[g], phi = P->phi[g];
+            const double mu = P.mean[g], phi = P.phi[g];
             const uint32_t out = (uint32_t)((size_t)c * G + g);
             if (xa > SQ_BIG_COUNT && xb > SQ_BIG_COUNT) {
                 SqBig b;
@@ -555,7 +537,7 @@ extern "C" int crgpu_sseq_diffexp_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m,
                 t_big.push_back(b), n_big[c]++;
                 continue;
             }
-            CR_REQUIRE(ctx, total[g] < 0xFFFFFFFFull, CRGPU_ERANGE, "crgpu_sseq_diffexp_dev: an exact test of %llu terms (gene %u)", (unsigned long long)total[g] + 1ull, g);
+            CR_REQUIRE(ctx, total[g] < 0xFFFFFFFFull, CRGPU_ERANGE, "%s: an exact test of %llu terms (gene %u)", who, (unsigned long long)total[g] + 1ull, g);
             SqTest t;
             t.poisson = phi == 0.0 ? 1u : 0u;
             t.ra = t.poisson ? std::log(s_a[c]) : s_a[c] / phi, t.rb = t.poisson ? std::log(s_b[c]) : s_b[c] / phi;
@@ -564,9 +546,10 @@ extern "C" int crgpu_sseq_diffexp_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m,
             (terms <= short_max ? t_short : terms >= wg_min ? t_wg : t_wave).push_back(t);
             n_exact[c]++, n_terms += terms;
         }
-    CR_REQUIRE(ctx, KG < 0xFFFFFFFFull, CRGPU_ERANGE, "crgpu_sseq_diffexp_dev: %u clusters x %u genes", K, G);
+    CR_REQUIRE(ctx, KG < 0xFFFFFFFFull, CRGPU_ERANGE, "%s: %u clusters x %u genes", who, K, G);
 
-    DevBuf p_b, adj_b, side_b, ts_b, tw_b, tg_b, tb_b;
+    DevBuf &p_b = T.p_b, &adj_b = T.adj_b, &side_b = T.side_b;
+    DevBuf ts_b, tw_b, tg_b, tb_b;
     std::vector<double> ones(KG, 1.0);
     CR_TRY(dmalloc(ctx, p_b, KG * sizeof(double)));
     CR_TRY(dmalloc(ctx, adj_b, KG * sizeof(double)));
@@ -585,7 +568,7 @@ extern "C" int crgpu_sseq_diffexp_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m,
     CR_TRY(upload(tb_b, t_big.data(), t_big.size() * sizeof(SqBig)));
     CR_HIP(ctx, hipStreamSynchronize(ctx->stream));
 
-    t0 = std::chrono::steady_clock::now();
+    auto t0 = std::chrono::steady_clock::now();
     {
         CrTimer t(ctx, CRGPU_T_MATRIX, n_terms);
         const uint32_t ns = (uint32_t)t_short.size(), nw = (uint32_t)t_wave.size(), ng = (uint32_t)t_wg.size();
@@ -636,8 +619,17 @@ extern "C" int crgpu_sseq_diffexp_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m,
         CR_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     res->ms_bh = cr_ms_since(t0);
+    res->n_terms = n_terms;
+    res->n_short = t_short.size(), res->n_wave = t_wave.size(), res->n_workgroup = t_wg.size();
+    return CRGPU_OK;
+}
 
-    // what the caller asked for
+// what the caller set a pointer for, [K][G] and [K]
+static int sq_write_results(crgpu_ctx *ctx, uint32_t G, uint32_t K, const std::vector<uint64_t> &xin, const std::vector<uint64_t> &total,
+                            const std::vector<double> &s_a, const std::vector<double> &s_b, SqTested &T, crgpu_sseq_result *res) {
+    const size_t KG = (size_t)K * G;
+    const std::vector<uint64_t> &n_exact = T.n_exact, &n_big = T.n_big;
+    DevBuf &p_b = T.p_b, &adj_b = T.adj_b, &side_b = T.side_b;
     if (res->p_values_out) CR_TRY(crgpu_memcpy_d2h(ctx, res->p_values_out, p_b.p, KG * sizeof(double)));
     if (res->adjusted_p_values_out) CR_TRY(crgpu_memcpy_d2h(ctx, res->adjusted_p_values_out, adj_b.p, KG * sizeof(double)));
     if (res->below_median_out) CR_TRY(crgpu_memcpy_d2h(ctx, res->below_median_out, side_b.p, KG));
@@ -657,7 +649,58 @@ extern "C" int crgpu_sseq_diffexp_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m,
         if (res->n_exact_out) res->n_exact_out[c] = n_exact[c];
         if (res->n_asymptotic_out) res->n_asymptotic_out[c] = n_big[c];
     }
-    res->n_terms = n_terms;
-    res->n_short = t_short.size(), res->n_wave = t_wave.size(), res->n_workgroup = t_wg.size();
+    return CRGPU_OK;
+}
+
+extern "C" int crgpu_sseq_diffexp_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const crgpu_sseq_params *P, const int32_t *labels, uint32_t K,
+                                      const crgpu_sseq_args *a, crgpu_sseq_result *res) {
+    if (!ctx || !m || !P || !labels || !a || !res) return CRGPU_EINVAL;
+    CR_ENTER(ctx);
+    const uint64_t N = m->n_barcodes;
+    const uint32_t G = P->n_features;
+    CR_REQUIRE(ctx, G >= 3 && N >= 2, CRGPU_EINVAL, "crgpu_sseq_diffexp_dev: %u features and %llu cells, at least 3 and 2", G, (unsigned long long)N);
+    CR_REQUIRE(ctx, K >= 2 && K <= CRGPU_SSEQ_MAX_K, CRGPU_EINVAL, "crgpu_sseq_diffexp_dev: %u clusters, 2 to %u", K, CRGPU_SSEQ_MAX_K);
+    CR_REQUIRE(ctx, P->n_cells == N && (a->n_features == 0 || a->n_features == G), CRGPU_EINVAL,
+               "crgpu_sseq_diffexp_dev: the parameters are those of a %u x %llu matrix, this one is %u x %llu", G, (unsigned long long)P->n_cells,
+               a->n_features ? a->n_features : G, (unsigned long long)N);
+    std::vector<uint64_t> size(K, 0);
+    for (uint64_t c = 0; c < N; c++) {
+        CR_REQUIRE(ctx, labels[c] >= 1 && (uint32_t)labels[c] <= K, CRGPU_EINVAL, "crgpu_sseq_diffexp_dev: label %d of cell %llu, 1 to %u", labels[c],
+                   (unsigned long long)c, K);
+        size[labels[c] - 1]++;
+    }
+    for (uint32_t c = 0; c < K; c++) CR_REQUIRE(ctx, size[c] > 0, CRGPU_EINVAL, "crgpu_sseq_diffexp_dev: cluster %u is empty", c + 1u);
+    const size_t KG = (size_t)K * G;
+
+    // the group sums
+    auto t0 = std::chrono::steady_clock::now();
+    DevBuf lab_b, sums_b;
+    CR_TRY(dmalloc(ctx, lab_b, N * sizeof(int32_t)));
+    CR_TRY(dmalloc(ctx, sums_b, KG * sizeof(uint64_t)));
+    CR_TRY(crgpu_memcpy_h2d(ctx, lab_b.p, labels, N * sizeof(int32_t)));
+    CR_HIP(ctx, hipMemsetAsync(sums_b.p, 0, KG * sizeof(uint64_t), ctx->stream));
+    {
+        CrTimer t(ctx, CRGPU_T_MATRIX, m->nnz);
+        hipLaunchKernelGGL(k_sq_group_sums, dim3(cr_grid(N * 64, SQ_WG)), dim3(SQ_WG), 0, ctx->stream, (const long long *)m->d_indptr, m->d_indices, m->d_data, N,
+                           G, lab_b.as<int32_t>(), sums_b.as<unsigned long long>());
+        CR_HIP(ctx, hipGetLastError());
+    }
+    std::vector<uint64_t> xin(KG);
+    CR_TRY(crgpu_memcpy_d2h(ctx, xin.data(), sums_b.p, KG * sizeof(uint64_t)));
+    res->ms_sums = cr_ms_since(t0);
+
+    // per cluster the sums of the size factors, in cell order; per gene the total
+    std::vector<double> s_a(K, 0.0), s_b(K, 0.0);
+    for (uint32_t c = 0; c < K; c++)
+        for (uint64_t i = 0; i < N; i++) {
+            if ((uint32_t)labels[i] == c + 1u) s_a[c] += P->sf[i]; else s_b[c] += P->sf[i];
+        }
+    std::vector<uint64_t> total(G, 0);
+    for (uint32_t c = 0; c < K; c++)
+        for (uint32_t g = 0; g < G; g++) total[g] += xin[(size_t)c * G + g];
+
+    SqTested T;
+    CR_TRY(sq_run_tests(ctx, "crgpu_sseq_diffexp_dev", *P, K, xin, total, s_a, s_b, a, res, T));
+    CR_TRY(sq_write_results(ctx, G, K, xin, total, s_a, s_b, T, res));
     return CRGPU_OK;
 }

@@ -255,6 +255,46 @@ class SseqParams:
             pass
 
 
+class SseqPairs:
+    """crgpu_sseq_pairs: one matrix and one grouping of its cells, transposed once for every local sSeq test of two sets of groups
+    (Context.sseq_pairs; csrc/sseq_pair.h)"""
+
+    VECTORS = (("use", np.uint8), ("mean", np.float64), ("phi_mm", np.float64), ("phi", np.float64), ("sums_a", np.uint64), ("sums_b", np.uint64),
+               ("norm_mean_a", np.float64), ("norm_mean_b", np.float64), ("log2_fold_change", np.float64), ("p_values", np.float64),
+               ("adjusted_p_values", np.float64), ("below_median", np.uint8))
+
+    def __init__(self, ctx, h, n_groups, n_features):
+        self.ctx, self._h, self.n_groups, self.n_features = ctx, h, n_groups, n_features
+
+    def compare(self, groups_a, groups_b, de_threshold=0.0, wave_min=0, wg_min=0, vectors=True):
+        """crgpu_sseq_pair_dev: the cells of groups_a against those of groups_b (ascending, distinct, disjoint lists of group ids), the
+        sSeq parameters computed on these cells alone -> dict(zeta_hat, delta, n_used, s_a, s_b, n_cells_a, n_cells_b, n_exact,
+        n_asymptotic, n_terms, n_de = genes with adjusted p < de_threshold (0 = 0.05), ms_*) and, with vectors, per gene use, mean, phi_mm,
+        phi, sums_a, sums_b, norm_mean_a, norm_mean_b, log2_fold_change, p_values, adjusted_p_values, below_median.  Every value equals
+        bit for bit cluster 1 of Context.sseq_params + Context.sseq_diffexp on the sub-matrix of the pair's cells in (group, cell) order"""
+        ga, gb = np.ascontiguousarray(groups_a, dtype=np.uint32).reshape(-1), np.ascontiguousarray(groups_b, dtype=np.uint32).reshape(-1)
+        G = self.n_features
+        o = {k: np.zeros(G, t) for k, t in self.VECTORS} if vectors else {}
+        r = _lib.SseqPairResult(**{k + "_out": ptr(v) for k, v in o.items()})
+        a = _lib.SseqPairArgs(n_features=G, wave_min=int(wave_min), wg_min=int(wg_min), de_threshold=float(de_threshold))
+        self.ctx._check(self.ctx.L.crgpu_sseq_pair_dev(self.ctx.h, self._h, ptr(ga), len(ga), ptr(gb), len(gb), C.byref(a), C.byref(r)))
+        o.update(zeta_hat=r.zeta_hat, delta=r.delta, s_a=r.s_a, s_b=r.s_b, n_cells_a=int(r.n_cells_a), n_cells_b=int(r.n_cells_b), n_exact=int(r.n_exact),
+                 n_asymptotic=int(r.n_asymptotic), n_terms=int(r.n_terms), n_de=int(r.n_de), n_used=int(r.n_used), n_runs=int(r.n_runs),
+                 ms_median=r.ms_median, ms_sums=r.ms_sums, ms_exact=r.ms_exact, ms_asymptotic=r.ms_asymptotic, ms_bh=r.ms_bh)
+        return o
+
+    def free(self):
+        if self._h is not None and self.ctx.h:
+            self.ctx.L.crgpu_sseq_pairs_free(self.ctx.h, self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 class CellCall:
     """Result of Context.call_cells_ordmag: `cols` = the called columns (DeviceArray of u64, ascending positions in the count
     vector / the matrix the counts came from), `n_cells`, `metrics` = crgpu_ordmag_result as a dict (BarcodeFilterResults of
@@ -1265,8 +1305,105 @@ def modularity(indptr, indices, labels, weights=None):
     return int(S.value), int(M.value), S.value / float(M.value) ** 2
 
 
+def linkage_complete(points):
+    """scipy.cluster.hierarchy.linkage(points, "complete") (crgpu_linkage_complete, host only): points f64[K, d], K >= 2 -> Z f64[K - 1, 4],
+    rows ascending by height, the smaller id first, the cluster of row s numbered K + s, column 3 its size.  Equal distances merge by the
+    smallest (height, id0, id1); scipy's order among ties is not reproduced"""
+    pts = np.ascontiguousarray(points, dtype=np.float64)
+    if pts.ndim != 2 or pts.shape[0] < 2 or pts.shape[1] < 1:
+        raise ValueError("linkage_complete: points is K x d with K >= 2")
+    z = np.zeros((pts.shape[0] - 1, 4))
+    rc = _lib.load().crgpu_linkage_complete(ptr(pts), pts.shape[0], pts.shape[1], ptr(z))
+    if rc != 0:
+        raise ValueError("linkage_complete: refused (%d)" % rc)
+    return z
+
+
+def merge_clusters(ctx, m, projection, labels, n_features=None, num_pcs=None, de_threshold=0.05):
+    """MERGE_CLUSTERS (stages/analyzer/merge_clusters join(), what graph_clustering.rs:156 calls after Louvain), statement by statement:
+    m = the filtered MatrixDev with all of its features, projection f64[barcodes x PCs], labels 1-based with 0 for a barcode that was
+    not used (run_graph_clustering's labels).  Loop: the per-cluster medians of the PCs (Context.cluster_medians), linkage_complete,
+    for every row whose two ids are leaves a local sSeq test (SseqPairs.compare on ONE plan made from the initial labels; a pair
+    already tested is skipped), a merge into the smaller label when no gene has adjusted p < de_threshold, then from the top; it ends
+    with one cluster or a walk without a merge.  -> dict(labels = the stage's final_labels (relabel_by_size, 0 = not used), steps = per
+    iteration and pair dict(iteration, leaf0, leaf1, groups0, groups1 (the initial 0-based groups), skipped, n_de, merged), n_tests,
+    n_skipped, n_merges, n_iterations, n_clusters_in, n_clusters_out, plan_ms, medians_ms, linkage_ms, pairs_ms, total_ms)"""
+    t_all = time.perf_counter()
+    labels = np.asarray(labels)
+    x = np.ascontiguousarray(projection, dtype=np.float64)
+    if labels.ndim != 1 or len(labels) != m.n_barcodes or x.ndim != 2 or x.shape[0] != len(labels):
+        raise ValueError("merge_clusters: one label and one projection row per barcode of the matrix")
+    d = x.shape[1] if num_pcs is None else min(x.shape[1], int(num_pcs))
+    total_bcs = len(labels)
+    use_bcs = np.flatnonzero(labels > 0)
+    if len(use_bcs) == 0:
+        raise ValueError("merge_clusters: no barcode has a cluster")
+    lab = labels[use_bcs].astype(np.int64) - 1
+    n_in = int(lab.max()) + 1
+    pca = np.ascontiguousarray(x[use_bcs, :d])
+    groups = np.full(total_bcs, -1, np.int32)
+    groups[use_bcs] = lab
+    members = [[g] for g in range(n_in)]      # the initial groups of every current cluster, ascending
+    times = dict(plan_ms=0.0, medians_ms=0.0, linkage_ms=0.0, pairs_ms=0.0)
+    steps, checked = [], set()
+    n_tests = n_skipped = n_merges = n_iterations = 0
+    pairs = None
+    try:
+        while len(members) > 1:
+            n_iterations += 1
+            if pairs is None:
+                t0 = time.perf_counter()
+                pairs = ctx.sseq_pairs(m, groups, n_features=n_features)
+                times["plan_ms"] += (time.perf_counter() - t0) * 1e3
+            t0 = time.perf_counter()
+            medoids = ctx.cluster_medians(pca, lab, len(members))["medians"]
+            t1 = time.perf_counter()
+            hc = linkage_complete(medoids)
+            times["medians_ms"] += (t1 - t0) * 1e3
+            times["linkage_ms"] += (time.perf_counter() - t1) * 1e3
+            max_label = len(members) - 1
+            any_merged = False
+            for step in range(hc.shape[0]):
+                if not (hc[step, 0] <= max_label and hc[step, 1] <= max_label):
+                    continue
+                leaf0, leaf1 = int(hc[step, 0]), int(hc[step, 1])
+                rec = dict(iteration=n_iterations, leaf0=leaf0, leaf1=leaf1, groups0=list(members[leaf0]), groups1=list(members[leaf1]), skipped=False,
+                           n_de=None, merged=False)
+                steps.append(rec)
+                key = frozenset((frozenset(members[leaf0]), frozenset(members[leaf1])))
+                if key in checked:
+                    rec["skipped"] = True
+                    n_skipped += 1
+                    continue
+                checked.add(key)
+                t0 = time.perf_counter()
+                r = pairs.compare(members[leaf0], members[leaf1], de_threshold=de_threshold, vectors=False)
+                times["pairs_ms"] += (time.perf_counter() - t0) * 1e3
+                n_tests += 1
+                rec["n_de"] = r["n_de"]
+                if r["n_de"] == 0:
+                    lab[lab == leaf1] = leaf0
+                    lab[lab > leaf1] -= 1
+                    members[leaf0] = sorted(members[leaf0] + members[leaf1])
+                    del members[leaf1]
+                    rec["merged"] = any_merged = True
+                    n_merges += 1
+                    break
+            if not any_merged:
+                break
+    finally:
+        if pairs is not None:
+            pairs.free()
+    final = np.zeros(total_bcs, dtype=np.int64)
+    final[use_bcs] = relabel_by_size(lab + 1)
+    out = dict(labels=final, steps=steps, n_tests=n_tests, n_skipped=n_skipped, n_merges=n_merges, n_iterations=n_iterations, n_clusters_in=n_in,
+               n_clusters_out=len(members))
+    out.update(times, total_ms=(time.perf_counter() - t_all) * 1e3)
+    return out
+
+
 def run_graph_clustering(ctx, projection, num_neighbors=None, neighbor_a=None, neighbor_b=None, input_pcs=None, louvain=None,
-                         num_barcodes=None, use_bcs=None, queries_per_call=_lib.NN_QUERIES_PER_CHUNK):
+                         num_barcodes=None, use_bcs=None, queries_per_call=_lib.NN_QUERIES_PER_CHUNK, merge_matrix=None):
     """RUN_GRAPH_CLUSTERING up to the Louvain binary: k by split()'s rule, the exact k nearest neighbours of every row of the cells x PCs
     projection (Context.knn, in calls of queries_per_call rows as the reference's chunks), the neighbour matrix of join()
     -> dict(num_neighbors, indices i32[n, k] by rank, distances f64[n, k], nn_indptr i64[n + 1], nn_indices i32[n k] (row-wise
@@ -1276,7 +1413,10 @@ def run_graph_clustering(ctx, projection, num_neighbors=None, neighbor_a=None, n
     louvain="device": Context.louvain on the neighbour matrix (the published algorithm in synchronous integer rounds, no parity with
     bin/louvain); labels = level 0 plus 1 (0 for a barcode that was not used) = louvain_labels(.., louvain_pairs(result)), clusters =
     relabel_by_size(labels), final_clusters = the same of the last level, levels = the partition of every level, modularity = Q per
-    level, louvain = Context.louvain's dict"""
+    level, louvain = Context.louvain's dict.
+    merge_matrix: with a louvain, the filtered MatrixDev (all features, one column per barcode of labels, the projection one row per
+    barcode): adds merge = merge_clusters(ctx, merge_matrix, projection, labels, num_pcs=input_pcs), merged_labels = its labels and
+    merged_clusters = relabel_by_size(merged_labels), what RUN_GRAPH_CLUSTERING_NG reports; None (the default) changes nothing"""
     if isinstance(louvain, str) and louvain != "device":
         raise ValueError("run_graph_clustering: louvain is None, a callable or \"device\"")
     x = np.asarray(projection)
@@ -1310,6 +1450,10 @@ def run_graph_clustering(ctx, projection, num_neighbors=None, neighbor_a=None, n
         pairs = louvain(row, out["nn_indices"].astype(np.int64))
         out["labels"] = louvain_labels(n if num_barcodes is None else num_barcodes, np.arange(n) if use_bcs is None else use_bcs, pairs)
         out["clusters"] = relabel_by_size(out["labels"])
+    if merge_matrix is not None and louvain is not None:
+        out["merge"] = merge_clusters(ctx, merge_matrix, projection, out["labels"], num_pcs=input_pcs)
+        out["merged_labels"] = out["merge"]["labels"]
+        out["merged_clusters"] = relabel_by_size(out["merged_labels"])
     return out
 
 
@@ -3255,6 +3399,40 @@ class Context:
         data[:, 0::3], data[:, 1::3], data[:, 2::3] = o["norm_mean_in"].T, o["log2_fold_change"].T, o["adjusted_p_values"].T
         o["data"] = data
         return o
+
+    def sseq_pairs(self, m, groups, n_groups=None, n_features=None):
+        """The plan of the local sSeq tests of one MatrixDev and one grouping of its cells (crgpu_sseq_pairs_create_dev, csrc/sseq_pair.h):
+        groups i32[cells], -1 = a cell in no group, else 0 .. n_groups - 1 (default: the largest + 1), every group with a cell.  The
+        entries of the grouped cells are sorted into (gene, group, cell) order once -> SseqPairs; n_features as Context.sseq_params"""
+        if n_features is None:
+            n_features = getattr(m, "n_features", None) or getattr(self, "n_features", None)
+            if n_features is None:
+                raise ValueError("sseq_pairs: pass n_features")
+        g = np.ascontiguousarray(groups, dtype=np.int32)
+        if g.ndim != 1 or len(g) != m.n_barcodes:
+            raise ValueError("sseq_pairs: one group per cell")
+        K = (int(g.max()) + 1 if len(g) else 0) if n_groups is None else int(n_groups)
+        a = _lib.SseqPairArgs(n_features=int(n_features))
+        h = C.c_void_p()
+        self._check(self.L.crgpu_sseq_pairs_create_dev(self.h, m._mv, ptr(g), max(K, 0), C.byref(a), C.byref(h)))
+        return SseqPairs(self, h, K, int(n_features))
+
+    def cluster_medians(self, projection, labels, n_clusters=None, num_pcs=None):
+        """np.median of every column of the f64 projection [rows x PCs] over the rows of every cluster (labels 0 .. n_clusters - 1, every
+        cluster with a row) by an exact radix select on the device (crgpu_cluster_medians_dev, csrc/merge_clusters.hip): the medoids of
+        MERGE_CLUSTERS -> dict(medians f64[K, d], sizes u64[K])"""
+        x = np.ascontiguousarray(projection, dtype=np.float64)
+        lab = np.ascontiguousarray(labels, dtype=np.int32)
+        if x.ndim != 2 or lab.ndim != 1 or len(lab) != x.shape[0]:
+            raise ValueError("cluster_medians: the projection is rows x PCs, one label per row")
+        n, ld = x.shape
+        d = ld if num_pcs is None else int(num_pcs)
+        K = (int(lab.max()) + 1 if n else 0) if n_clusters is None else int(n_clusters)
+        if not 1 <= K <= _lib.SSEQ_MAX_K or not 1 <= d <= ld:      # the output needs a shape; the library refuses the rest
+            raise ValueError("cluster_medians: %d clusters (1 to %d), %d of %d columns" % (K, _lib.SSEQ_MAX_K, d, ld))
+        med, sizes = np.zeros((K, d)), np.zeros(K, np.uint64)
+        self._check(self.L.crgpu_cluster_medians_dev(self.h, ptr(x), n, d, ld, ptr(lab), K, ptr(med), ptr(sizes)))
+        return dict(medians=med, sizes=sizes)
 
     def tag_moments(self, m, tag_rows, n_features=None):
         """the exact sums over the cells of x, x^2 and x y for the listed tag rows (at most 16) -> (u64[n], u64[n], u64[n, n])"""

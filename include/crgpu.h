@@ -1824,7 +1824,8 @@ int crgpu_kmeans_seed_draws(uint32_t seed, uint64_t n, uint32_t k, double *u_out
  *   refused with CRGPU_EINVAL before any device work: a NULL argument, G < 3, N < 2, n_clusters < 2 or > CRGPU_SSEQ_MAX_K, a label
  *   outside 1 .. n_clusters, an empty cluster, parameters of a matrix of another shape
  * NOT covered: get_local_sseq_params and the pairwise comparisons of MEASURE_PERTURBATIONS, the H5 and CSV writers, PCA, parity with
- * the diff_exp crate. */
+ * the diff_exp crate.  (That holds for THESE entry points; the parameters of two groups of cells alone and the test of one group
+ * against the other are crgpu_sseq_pair_dev of the MERGE_CLUSTERS section below.) */
 #define CRGPU_SSEQ_MAX_K 4096
 struct crgpu_sseq_args {
     uint32_t n_features;   /* G: the rows of the matrix (crgpu_sseq_diffexp_dev: 0 or the G of the parameters) */
@@ -1870,6 +1871,104 @@ int crgpu_sseq_params_get(crgpu_ctx *ctx, const crgpu_sseq_params *params, crgpu
 int crgpu_sseq_diffexp_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const crgpu_sseq_params *params, const int32_t *labels,
                            uint32_t n_clusters, const crgpu_sseq_args *args, crgpu_sseq_result *result);
 int crgpu_sseq_adjust_bh(const double *p, uint64_t n, double *q_out);
+
+/* ---- MERGE_CLUSTERS: medoids, complete linkage, local sSeq tests of sibling leaves ---------------------------------------------------
+ * RUN_GRAPH_CLUSTERING_NG never hands the Louvain labels on as they are: lib/rust/cr_ana/src/stages/graph_clustering.rs:156 calls
+ * merge_clusters(&matrix, &proj, labels) first.  Its source is in the crate; the Python stage
+ * mro/rna/stages/analyzer/merge_clusters/__init__.py spells the procedure out, and this section follows join() of that file: (1) the
+ * per-cluster median of every principal component (the "medoids"), (2) scipy's linkage(medoids, "complete"), (3) for every row of the dendrogram whose two ids are both
+ * leaves, a LOCAL sSeq test -- compute_sseq_params on the cells of the two clusters alone, then cluster against cluster, as
+ * get_local_sseq_params does (lib/python/cellranger/analysis/diffexp.py:69-85) -- (4) a merge when no gene has an adjusted p below
+ * MERGE_CLUSTERS_DE_ADJ_P_THRESHOLD = 0.05, and back to (1) until a whole walk merges nothing.  The loop itself is host code
+ * (cellranger_amd.engine.merge_clusters); the three primitives are below.
+ *   crgpu_sseq_pairs_create_dev  the plan of one matrix and one grouping of its cells.  group_of_cell: host i32[N], -1 = a cell in no
+ *                                group (an unused barcode), else 0 .. n_groups - 1; every group holds a cell; 2 <= n_groups <=
+ *                                CRGPU_SSEQ_MAX_K.  pos = the grouped cells ordered by (group, cell index).  Every entry of a grouped
+ *                                cell is keyed row * Npos + pos(cell) and radix-sorted ONCE: the transpose crgpu_sseq_params_dev builds
+ *                                and throws away, with pos in place of the column.  The plan keeps the sorted keys, the values, the
+ *                                counts per cell in pos order (device and host) and, on the host, the start of every group in pos.  Library-owned,
+ *                                release with crgpu_sseq_pairs_free.  Limits as crgpu_sseq_params_dev: G >= 3, 2 <= N < 2^31, a
+ *                                matrix with an entry; a row >= n_features is CRGPU_EINVAL.
+ *   crgpu_sseq_pair_dev          groups_a / groups_b: ascending, distinct, disjoint lists of group ids.  THE CONTRACT: every output
+ *                                equals bit for bit what crgpu_sseq_params_dev and crgpu_sseq_diffexp_dev give for cluster 1 of the
+ *                                sub-matrix crgpu_select_barcodes_dev(m, cols), cols = the cells of groups_a ascending by pos, then
+ *                                those of groups_b, with the labels 1 .. 1, 2 .. 2.  So the result is a pure function of the plan and
+ *                                the two sets, whatever way the caller arrived at them.  n_terms counts the terms of THESE tests (the
+ *                                composed path counts the mirrored tests of cluster 2 as well: twice as many).  n_de = the genes
+ *                                with adjusted p < de_threshold.
+ *                                ORDER OF THE CELLS: the reference orders a side's cells by cell index (np.flatnonzero(labels ==
+ *                                leaf)), this call by (initial group, cell index).  For a cluster made of several initial groups that
+ *                                permutes the cells within a side, which moves the last bits of the floating-point sums (S, s_a, s_b,
+ *                                the per-gene sums) and nothing else; integers and the median are the same.  The order the crate
+ *                                itself adds in is not known, and the statement of the sSeq section stands: no parity with the
+ *                                diff_exp crate is claimed.
+ *                                Work per pair: a gene's entries of a listed group are one contiguous run of the gene's sorted keys;
+ *                                no sort and no compaction, G x (groups listed) x 2 binary searches plus the pair's entries.  The
+ *                                entry of concatenated index r belongs to lane r % 64, a lane adds in ascending r, the lanes are
+ *                                joined by the fixed tree: the order of crgpu_sseq_params_dev on the sub-matrix.  x_a and x_b come
+ *                                from the same walk as u64 sums: no atomics.  The median of the pair's counts goes through the u32
+ *                                radix sort; size factors, S, s_a, s_b and the G-vectors are the host arithmetic of
+ *                                crgpu_sseq_params_dev (one function for both); the exact tests, the asymptotic tests and
+ *                                Benjamini-Hochberg are those of crgpu_sseq_diffexp_dev with one cluster.
+ *                                Refused with CRGPU_EINVAL before any device work: a NULL argument, n_features that is neither 0 nor
+ *                                the plan's, an empty list, a list that is not strictly ascending, a group id >= n_groups, a group
+ *                                on both sides, a cell of the pair without counts; after the sums: no gene varies over the pair.
+ *   crgpu_cluster_medians_dev    x: host f64, n x d with row stride ld (as crgpu_knn_dev), finite; labels: host i32[n], 0 ..
+ *                                n_clusters - 1, every cluster with a row; 1 <= d <= 128, 1 <= n_clusters <= CRGPU_SSEQ_MAX_K.
+ *                                medians_out[c][t] = np.median(x[labels == c, t]) as a number: the middle element, or (lo + hi) / 2
+ *                                of the two middle ones (a median of -0 and +0 may come with either sign).  An exact selection: no
+ *                                tolerance, no order of summation.  The rows go up counting-sorted by label; a workgroup per
+ *                                (cluster, dimension) runs a most-significant-byte-first radix select over the order-preserving u64
+ *                                image of the doubles (eight passes, a 256-bin histogram in LDS), twice for an even size.
+ *                                sizes_out[c] (u64, NULL = not wanted) = the rows of cluster c.
+ *   crgpu_linkage_complete       host only, no context: scipy.cluster.hierarchy.linkage(points, "complete") for K >= 2 points of d
+ *                                dimensions.  Distances are sqrt of the f64 sum of squared differences in dimension order; the
+ *                                Lance-Williams update of complete linkage is a max, so every height is one of the input distances.
+ *                                Z_out[K - 1][4]: rows ascend by height, the smaller id first, the cluster made by row s is K + s,
+ *                                column 3 is its size.  On a tie-free set of distances the dendrogram is unique and equals scipy's.
+ *                                With equal distances the pair with the smallest (height, id0, id1) is merged first; scipy's
+ *                                nearest-neighbour-chain order is NOT reproduced there.  O(K^2) memory; a cached nearest neighbour per
+ *                                cluster keeps the usual case at O(K^2) time.
+ * NOT covered: the MEASURE_PERTURBATIONS stage itself (crgpu_sseq_pair_dev is its primitive), several pairs in one pass, the H5 and
+ * CSV writers, float32, parity with scan_rs or the diff_exp crate, whose sources are not in the reference tree. */
+struct crgpu_sseq_pair_args {
+    uint32_t n_features;   /* G: the rows of the matrix (crgpu_sseq_pair_dev: 0 or the G of the plan) */
+    uint32_t wave_min;     /* the class thresholds of the exact tests, as crgpu_sseq_args; they change no bit */
+    uint32_t wg_min;
+    uint32_t reserved;
+    double de_threshold;   /* a gene is differentially expressed below this adjusted p; 0 = 0.05 */
+};
+typedef struct crgpu_sseq_pair_args crgpu_sseq_pair_args;
+struct crgpu_sseq_pair_result {
+    uint8_t *use_out;                   /* u8[G]; every pointer: caller-owned, NULL = not wanted */
+    double *mean_out;                   /* f64[G] each */
+    double *phi_mm_out;
+    double *phi_out;
+    uint64_t *sums_a_out;               /* u64[G] each */
+    uint64_t *sums_b_out;
+    double *norm_mean_a_out;            /* f64[G] each */
+    double *norm_mean_b_out;
+    double *log2_fold_change_out;
+    double *p_values_out;
+    double *adjusted_p_values_out;
+    uint8_t *below_median_out;          /* u8[G]: 1 / 0 = the side of the median an asymptotic test took, 255 = none */
+    double zeta_hat, delta, s_a, s_b;
+    uint64_t n_cells_a, n_cells_b;
+    uint64_t n_exact, n_asymptotic, n_terms; /* the tests of side a against side b */
+    uint64_t n_de;                      /* genes with adjusted p < de_threshold */
+    uint32_t n_used, n_runs;            /* genes that vary over the pair; groups listed */
+    double ms_median, ms_sums, ms_exact, ms_asymptotic, ms_bh; /* host time of the five phases */
+};
+typedef struct crgpu_sseq_pair_result crgpu_sseq_pair_result;
+typedef struct crgpu_sseq_pairs crgpu_sseq_pairs;
+int crgpu_sseq_pairs_create_dev(crgpu_ctx *ctx, const crgpu_matrix_dev *m, const int32_t *group_of_cell, uint32_t n_groups,
+                                const crgpu_sseq_pair_args *args, crgpu_sseq_pairs **pairs_out);
+void crgpu_sseq_pairs_free(crgpu_ctx *ctx, crgpu_sseq_pairs *pairs);
+int crgpu_sseq_pair_dev(crgpu_ctx *ctx, const crgpu_sseq_pairs *pairs, const uint32_t *groups_a, uint32_t n_a, const uint32_t *groups_b,
+                        uint32_t n_b, const crgpu_sseq_pair_args *args, crgpu_sseq_pair_result *result);
+int crgpu_cluster_medians_dev(crgpu_ctx *ctx, const double *x, uint64_t n, uint32_t d, uint64_t ld, const int32_t *labels,
+                              uint32_t n_clusters, double *medians_out, uint64_t *sizes_out);
+int crgpu_linkage_complete(const double *points, uint32_t k, uint32_t d, double *z_out);
 
 /* ---- exact k-nearest-neighbour graph of a dense projection: the query of RUN_GRAPH_CLUSTERING ---------------------------------------
  * stages/analyzer/run_graph_clustering/__init__.py: split() fixes the number of neighbours and cuts the rows into chunks of 15 000,

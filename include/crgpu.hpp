@@ -1396,6 +1396,71 @@ inline SseqDiffexp sseq_diffexp(Context &ctx, const crgpu_matrix_dev *m, const S
     return o;
 }
 
+// ---- MERGE_CLUSTERS: medoids, complete linkage, local sSeq tests of sibling leaves ------------------------------------------------------
+static_assert(sizeof(crgpu_sseq_pair_args) == 24, "crgpu_sseq_pair_args changed: bump CRGPU_ABI_VERSION and every binding");
+static_assert(sizeof(crgpu_sseq_pair_result) == 224, "crgpu_sseq_pair_result changed: bump CRGPU_ABI_VERSION and every binding");
+struct SseqPair {
+    std::vector<uint8_t> use, below_median;   // [G]
+    std::vector<double> mean, phi_mm, phi, norm_mean_a, norm_mean_b, log2_fold_change, p_values, adjusted_p_values;  // [G]
+    std::vector<uint64_t> sums_a, sums_b;     // [G]
+    double zeta_hat = 0.0, delta = 0.0, s_a = 0.0, s_b = 0.0;
+    uint64_t n_cells_a = 0, n_cells_b = 0, n_exact = 0, n_asymptotic = 0, n_terms = 0, n_de = 0;
+    uint32_t n_used = 0;
+};
+/// crgpu_sseq_pairs: one matrix and one grouping of its cells (group_of_cell: -1 = in no group), transposed once for every pair test
+class SseqPairs {
+public:
+    SseqPairs(Context &ctx, const crgpu_matrix_dev *m, const std::vector<int32_t> &group_of_cell, uint32_t n_groups, uint32_t n_features)
+        : ctx_(ctx), n_features_(n_features) {
+        if (!m || group_of_cell.size() != m->n_barcodes) throw Error(CRGPU_EINVAL, "SseqPairs: one group per cell");
+        crgpu_sseq_pair_args a = {n_features, 0, 0, 0, 0.0};
+        ctx.check(crgpu_sseq_pairs_create_dev(ctx.get(), m, group_of_cell.data(), n_groups, &a, &p_));
+    }
+    ~SseqPairs() { crgpu_sseq_pairs_free(ctx_.get(), p_); }
+    SseqPairs(const SseqPairs &) = delete;
+    SseqPairs &operator=(const SseqPairs &) = delete;
+    /// crgpu_sseq_pair_dev: the groups of side a against those of side b (ascending, distinct, disjoint); de_threshold 0 = 0.05
+    SseqPair compare(const std::vector<uint32_t> &groups_a, const std::vector<uint32_t> &groups_b, double de_threshold = 0.0, uint32_t wave_min = 0,
+                     uint32_t wg_min = 0) const {
+        SseqPair o;
+        const size_t G = n_features_;
+        o.use.assign(G, 0), o.below_median.assign(G, 0), o.mean.assign(G, 0.0), o.phi_mm.assign(G, 0.0), o.phi.assign(G, 0.0);
+        o.norm_mean_a.assign(G, 0.0), o.norm_mean_b.assign(G, 0.0), o.log2_fold_change.assign(G, 0.0), o.p_values.assign(G, 0.0);
+        o.adjusted_p_values.assign(G, 0.0), o.sums_a.assign(G, 0), o.sums_b.assign(G, 0);
+        crgpu_sseq_pair_result r = {};
+        r.use_out = o.use.data(), r.mean_out = o.mean.data(), r.phi_mm_out = o.phi_mm.data(), r.phi_out = o.phi.data();
+        r.sums_a_out = o.sums_a.data(), r.sums_b_out = o.sums_b.data(), r.norm_mean_a_out = o.norm_mean_a.data(), r.norm_mean_b_out = o.norm_mean_b.data();
+        r.log2_fold_change_out = o.log2_fold_change.data(), r.p_values_out = o.p_values.data(), r.adjusted_p_values_out = o.adjusted_p_values.data();
+        r.below_median_out = o.below_median.data();
+        crgpu_sseq_pair_args a = {n_features_, wave_min, wg_min, 0, de_threshold};
+        ctx_.check(crgpu_sseq_pair_dev(ctx_.get(), p_, groups_a.data(), (uint32_t)groups_a.size(), groups_b.data(), (uint32_t)groups_b.size(), &a, &r));
+        o.zeta_hat = r.zeta_hat, o.delta = r.delta, o.s_a = r.s_a, o.s_b = r.s_b, o.n_cells_a = r.n_cells_a, o.n_cells_b = r.n_cells_b;
+        o.n_exact = r.n_exact, o.n_asymptotic = r.n_asymptotic, o.n_terms = r.n_terms, o.n_de = r.n_de, o.n_used = r.n_used;
+        return o;
+    }
+
+private:
+    Context &ctx_;
+    crgpu_sseq_pairs *p_ = nullptr;
+    uint32_t n_features_;
+};
+/// crgpu_cluster_medians_dev: np.median of every dimension over the rows of every cluster (labels 0 .. n_clusters - 1) -> [n_clusters][d]
+inline std::vector<double> cluster_medians(Context &ctx, const std::vector<double> &x, uint64_t n, uint32_t d, const std::vector<int32_t> &labels,
+                                           uint32_t n_clusters) {
+    if (x.size() != n * d || labels.size() != n) throw Error(CRGPU_EINVAL, "cluster_medians: x is n x d, one label per row");
+    std::vector<double> med((size_t)n_clusters * d);
+    ctx.check(crgpu_cluster_medians_dev(ctx.get(), x.data(), n, d, d, labels.data(), n_clusters, med.data(), nullptr));
+    return med;
+}
+/// crgpu_linkage_complete (host only): scipy's linkage(points, "complete") -> Z [k - 1][4]
+inline std::vector<double> linkage_complete(const std::vector<double> &points, uint32_t k, uint32_t d) {
+    if (points.size() != (size_t)k * d || k < 2) throw Error(CRGPU_EINVAL, "linkage_complete: points is k x d, k >= 2");
+    std::vector<double> z((size_t)(k - 1) * 4);
+    const int rc = crgpu_linkage_complete(points.data(), k, d, z.data());
+    if (rc != CRGPU_OK) throw Error(rc, "linkage_complete");
+    return z;
+}
+
 // ---- exact k-nearest-neighbour graph of a dense projection: the query of RUN_GRAPH_CLUSTERING -----------------------------------------
 static_assert(sizeof(crgpu_knn_args) == 32, "crgpu_knn_args changed: bump CRGPU_ABI_VERSION and every binding");
 static_assert(sizeof(crgpu_knn_result) == 96, "crgpu_knn_result changed: bump CRGPU_ABI_VERSION and every binding");

@@ -27,15 +27,16 @@ KS = list(range(2, 11))
 GROUP_SHARE = np.array([22, 18, 14, 11, 9, 8, 7, 5, 3, 3], float) / 100.0
 
 
-def synth(n_cells, n_genes, entries, seed=11):
-    """-> (indptr i64[N + 1], indices u32, data u32, groups i32[N]); the rows of a column ascend"""
+def synth(n_cells, n_genes, entries, seed=11, share=GROUP_SHARE):
+    """-> (indptr i64[N + 1], indices u32, data u32, groups i32[N]); the rows of a column ascend; share: the sizes of the latent groups"""
+    n_groups = len(share)
     rs = np.random.RandomState(seed)
     w = np.exp(rs.normal(0.0, 1.6, n_genes))
-    effect = np.ones((10, n_genes))
-    for j in range(10):
+    effect = np.ones((n_groups, n_genes))
+    for j in range(n_groups):
         sel = rs.choice(n_genes, n_genes // 20, replace=False)
         effect[j, sel] = np.exp(rs.normal(0.0, 1.2, len(sel)))
-    cdfs = [np.cumsum(w * effect[j]) for j in range(10)]
+    cdfs = [np.cumsum(w * effect[j]) for j in range(n_groups)]
     cdfs = [c / c[-1] for c in cdfs]
 
     def block(j, n, draws):
@@ -52,11 +53,11 @@ def synth(n_cells, n_genes, entries, seed=11):
         else:
             hi = mid
     draws = hi
-    groups = np.repeat(np.arange(10), np.maximum(1, np.round(GROUP_SHARE * n_cells).astype(int)))[:n_cells]
+    groups = np.repeat(np.arange(n_groups), np.maximum(1, np.round(np.asarray(share) * n_cells).astype(int)))[:n_cells]
     groups = np.concatenate([groups, np.zeros(n_cells - len(groups), int)])
     rs.shuffle(groups)
     per_cell, idx, dat = np.zeros(n_cells, np.int64), [None] * n_cells, [None] * n_cells
-    for j in range(10):
+    for j in range(n_groups):
         cells = np.flatnonzero(groups == j)
         for s in range(0, len(cells), 512):
             part = cells[s:s + 512]
