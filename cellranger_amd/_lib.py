@@ -368,6 +368,16 @@ class SseqPairResult(C.Structure):
         (n, C.c_double) for n in ("ms_median", "ms_sums", "ms_exact", "ms_asymptotic", "ms_bh")]
 
 
+class PbItem(C.Structure):
+    """crgpu_pb_item"""
+    _fields_ = [(n, C.c_uint32) for n in ("gene", "group_a", "group_b", "stream")]
+
+
+class PbArgs(C.Structure):
+    """crgpu_pb_args"""
+    _fields_ = [(n, C.c_uint32) for n in ("n_bootstraps", "lds_cells", "draws_per_wg", "reserved")] + [("seed", C.c_uint64)]
+
+
 class KnnArgs(C.Structure):
     """crgpu_knn_args"""
     _fields_ = [("query_start", C.c_uint64), ("n_queries", C.c_uint64)] + [
@@ -650,6 +660,8 @@ SYMBOLS = {
     "crgpu_sseq_pairs_create_dev": (_i, [_vp, C.POINTER(MatrixDevView), _vp, _u32, C.POINTER(SseqPairArgs), C.POINTER(_vp)]),
     "crgpu_sseq_pairs_free": (None, [_vp, _vp]),
     "crgpu_sseq_pair_dev": (_i, [_vp, _vp, _vp, _u32, _vp, _u32, C.POINTER(SseqPairArgs), C.POINTER(SseqPairResult)]),
+    "crgpu_sseq_pair_bootstrap_dev": (_i, [_vp, _vp, _vp, _u32, C.POINTER(PbArgs), _vp, _vp]),
+    "crgpu_perturbation_ci": (_i, [_vp, _vp, _u32, C.c_double, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp]),
     "crgpu_cluster_medians_dev": (_i, [_vp, _vp, _u64, _u32, _u64, _vp, _u32, _vp, _vp]),
     "crgpu_linkage_complete": (_i, [_vp, _u32, _u32, _vp]),
     "crgpu_knn_dev": (_i, [_vp, _vp, _u64, _u32, _u64, _u32, C.POINTER(KnnArgs), C.POINTER(KnnResult)]),

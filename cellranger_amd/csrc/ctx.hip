@@ -416,6 +416,15 @@ const std::vector<AbiStruct> &abi_table() {
               ABI_F(crgpu_sseq_pair_result, ms_exact),
               ABI_F(crgpu_sseq_pair_result, ms_asymptotic),
               ABI_F(crgpu_sseq_pair_result, ms_bh)),
+        ABI_S(crgpu_pb_item, ABI_F(crgpu_pb_item, gene),
+              ABI_F(crgpu_pb_item, group_a),
+              ABI_F(crgpu_pb_item, group_b),
+              ABI_F(crgpu_pb_item, stream)),
+        ABI_S(crgpu_pb_args, ABI_F(crgpu_pb_args, n_bootstraps),
+              ABI_F(crgpu_pb_args, lds_cells),
+              ABI_F(crgpu_pb_args, draws_per_wg),
+              ABI_F(crgpu_pb_args, reserved),
+              ABI_F(crgpu_pb_args, seed)),
         ABI_S(crgpu_knn_args, ABI_F(crgpu_knn_args, query_start),
               ABI_F(crgpu_knn_args, n_queries),
               ABI_F(crgpu_knn_args, capacity),

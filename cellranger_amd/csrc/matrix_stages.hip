@@ -9,6 +9,7 @@
 #include "marginal_calls.h"
 #include "matrix_summary.h"
 #include "multigenome.h"
+#include "perturbations.h"
 #include "rtl_tags.h"
 #include "sseq.h"
 #include "sseq_pair.h"

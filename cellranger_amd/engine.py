@@ -283,6 +283,18 @@ class SseqPairs:
                  ms_median=r.ms_median, ms_sums=r.ms_sums, ms_exact=r.ms_exact, ms_asymptotic=r.ms_asymptotic, ms_bh=r.ms_bh)
         return o
 
+    def bootstrap(self, items, n_bootstraps=500, seed=0, lds_cells=0, draws_per_wg=0):
+        """crgpu_sseq_pair_bootstrap_dev: items = rows of (gene, group_a, group_b, stream) -> (sums_a, sums_b) u64[n_items, B]: the sum of the
+        gene over draw b's resample (with replacement) of the cells of group_a / of group_b, each side one group of the plan.  The
+        stream is Philox keyed (seed, 0), numbered by the item's `stream`, the side and the draw (include/crgpu.h); the reference's
+        unseeded np.random stream is not reproduced.  lds_cells and draws_per_wg change no value"""
+        it = np.ascontiguousarray(items, dtype=np.uint32).reshape(-1, 4)
+        B = int(n_bootstraps) if n_bootstraps else 500
+        sa, sb = np.zeros((len(it), B), np.uint64), np.zeros((len(it), B), np.uint64)
+        a = _lib.PbArgs(n_bootstraps=int(n_bootstraps), lds_cells=int(lds_cells), draws_per_wg=int(draws_per_wg), seed=int(seed))
+        self.ctx._check(self.ctx.L.crgpu_sseq_pair_bootstrap_dev(self.ctx.h, self._h, ptr(it), len(it), C.byref(a), ptr(sa), ptr(sb)))
+        return sa, sb
+
     def free(self):
         if self._h is not None and self.ctx.h:
             self.ctx.L.crgpu_sseq_pairs_free(self.ctx.h, self._h)
@@ -1856,6 +1868,261 @@ def call_protospacers(ctx, filtered, guide_rows, n_features=None, report_prefix=
                "1 protospacer assigned": (md["num_singlets"], 100 * md["frac_singlets"]),
                "More than 1 protospacer assigned": (md["num_multiplets"], 100 * md["frac_multiplets"])}
     return dict(calls=mc, metadata=md, metrics=metrics, summary=summary, umi_thresholds=mc.umi_thresholds())
+
+
+# ---- MEASURE_PERTURBATIONS (stages/feature/measure_perturbations, cellranger/feature/crispr/measure_perturbations.py) ----------------
+PERTURBATION_FILTER_LIST = ("None", "Non-Targeting", "Ignore")      # cellranger.constants.FILTER_LIST
+PERTURBATION_CONTROL_LIST = ("Non-Targeting",)
+MIN_NUMBER_CELLS_PER_PERTURBATION = 10
+MIN_COUNTS_PERTURBATION = MIN_COUNTS_CONTROL = 5
+NUM_TOP_GENES = 10
+PERTURBATION_EFFICIENCY_SUMMARY_COLUMNS = ("Perturbation", "target_string", "Log2 Fold Change", "p Value", "Log2 Fold Change Lower Bound",
+                                           "Log2 Fold Change Upper Bound", "Cells with Perturbation", "Mean UMI Count Among Cells with Perturbation",
+                                           "Cells with Non-Targeting Guides", "Mean UMI Count Among Cells with Non-Targeting Guides")
+TOP_GENES_SUMMARY_COLUMNS = ("Gene Name", "Gene ID", "Log2 Fold Change", "Adjusted p-value")
+
+
+def _str(x):
+    return x.decode() if isinstance(x, bytes) else str(x)
+
+
+def perturbation_target_info(feature_ref):
+    """_get_target_info: feature_ref = the rows of the feature reference as dicts (id, target_gene_id, optional target_gene_name)
+    -> {feature id: dict(target_id, target_name)}; a row without a name takes its target id"""
+    info = {}
+    for row in feature_ref:
+        tid = row["target_gene_id"]
+        info[row["id"]] = dict(target_id=tid, target_name=row.get("target_gene_name", tid))
+    return info
+
+
+def protospacer_calls(marginal_calls, guide_ids, barcodes):
+    """The `calls` of perturbation_clusters from a MarginalCalls (call_protospacers' `calls`): {barcode: (the ids of the guides assigned
+    to the cell joined by "|" in row order, their number)} for the cells with a guide, as protospacer_calls_per_cell.csv lists them"""
+    indptr, cols = marginal_calls.assignments()
+    per_cell = collections.defaultdict(list)
+    for p in range(marginal_calls.n_rows):
+        for c in cols[indptr[p]:indptr[p + 1]]:
+            per_cell[int(c)].append(_str(guide_ids[p]))
+    return {_str(barcodes[c]): ("|".join(f), len(f)) for c, f in sorted(per_cell.items())}
+
+
+def perturbation_clusters(feature_ref, calls, barcodes, by_feature=False, ignore_multiples=False):
+    """_get_ps_clusters, statement by statement (_get_bc_targets_dict, _add_bcs_without_ps_calls, _get_ps_clusters_by_target /
+    _by_feature, _get_feature_from_bc): calls = {barcode: (feature_call "A|B", num_features)} for the cells with a call
+    -> (cluster_per_bc i64[barcodes], 1-based; {cluster: perturbation name}).  The names are sorted to number the clusters; a
+    multi-guide cell whose targets are all Non-Targeting is a control cell; "None", "Non-Targeting" and "Ignore" are taken out of a
+    multi-guide cell's targets; "Ignore" holds the ignored multiples and, by feature, the cells without a call as well.
+    DEVIATION: the reference joins list(set(targets)), whose order depends on the process's hash seed; here the targets are joined
+    in sorted order"""
+    info = perturbation_target_info(feature_ref)
+    bc_targets = {}
+    for bc, (feature_call, num_features) in calls.items():
+        if feature_call in info:
+            tid, tname = info[feature_call]["target_id"], info[feature_call]["target_name"]
+        else:
+            tid = tname = feature_call
+        if num_features > 1:
+            if ignore_multiples:
+                tid = tname = "Ignore"
+            else:
+                feats = feature_call.split("|")
+                tids, tnames = [info[x]["target_id"] for x in feats], [info[x]["target_name"] for x in feats]
+                if set(tids) == set(PERTURBATION_CONTROL_LIST):
+                    tid = tname = "Non-Targeting"
+                else:
+                    tids = sorted(set(tids).difference(PERTURBATION_FILTER_LIST))
+                    tnames = sorted(set(tnames).difference(PERTURBATION_FILTER_LIST))
+                    if tids:
+                        tid, tname = "|".join(tids), "|".join(tnames)
+                    else:
+                        tid = tname = "Ignore"
+        bc_targets[_str(bc)] = dict(num_features=num_features, feature_call=feature_call, target_id=tid, target_name=tname)
+    bcs = [_str(bc) for bc in barcodes]
+    for bc in bcs:
+        if bc not in bc_targets:
+            bc_targets[bc] = dict(target_name="None", num_features=-1, target_id="None", feature_call="None")
+    if not by_feature:
+        id_name = {v["target_id"]: v["target_name"] for v in info.values()}
+        per_bc = [bc_targets[bc]["target_id"] for bc in bcs]
+        number = {el: i + 1 for i, el in enumerate(sorted(set(per_bc)))}
+        names = {b: "|".join(id_name.get(x, x) for x in a.split("|")) for a, b in number.items()}
+    else:
+        def feature_of(t):
+            if t["target_id"] not in PERTURBATION_FILTER_LIST:
+                return t["feature_call"]
+            return "Ignore" if t["target_id"] == "None" else t["target_id"]
+
+        per_bc = [feature_of(bc_targets[bc]) for bc in bcs]
+        number = {el: i + 1 for i, el in enumerate(sorted(set(per_bc)))}
+        names = {b: a for a, b in number.items()}
+    return np.asarray([number[x] for x in per_bc], dtype=np.int64), names
+
+
+def perturbation_ci(sums_a, sums_b, s_a, s_b, ci_lower=5.0, ci_upper=95.0):
+    """crgpu_perturbation_ci (host only): per draw log2((1 + A) / (1 + s_a)) - log2((1 + B) / (1 + s_b)), then np.percentile at the two
+    bounds -> (lower, upper, log2fc f64[B]).  s_a, s_b: the sums of the size factors of the ORIGINAL cells (SseqPairs.compare's), as
+    _get_fold_change_cis takes them, not of the resampled cells"""
+    A, B = np.ascontiguousarray(sums_a, dtype=np.uint64).reshape(-1), np.ascontiguousarray(sums_b, dtype=np.uint64).reshape(-1)
+    if len(A) != len(B):
+        raise ValueError("perturbation_ci: one sum per draw and side")
+    fc = np.zeros(len(A))
+    lo, hi = C.c_double(0.0), C.c_double(0.0)
+    rc = _lib.load().crgpu_perturbation_ci(ptr(A), ptr(B), len(A), float(s_a), float(s_b), float(ci_lower), float(ci_upper), ptr(fc), C.byref(lo), C.byref(hi))
+    if rc != 0:
+        raise _lib.CrgpuError(rc, "crgpu_perturbation_ci")
+    return lo.value, hi.value, fc
+
+
+def top_perturbed_genes(result, gene_ids, gene_names, num_genes=NUM_TOP_GENES):
+    """sanitize_perturbation_results on one pair's vectors: keep sum_b > 0, keep sum_a >= 5 or sum_b >= 5, order by (|log2 fold change|
+    descending, adjusted p, gene name) -> the first num_genes rows as (gene name, gene id, log2 fold change, adjusted p).  (The
+    reference's save_top_perturbed_genes slices the COLUMN list with its num_genes_to_keep, so its CSV keeps every row.)"""
+    sa, sb = np.asarray(result["sums_a"]), np.asarray(result["sums_b"])
+    keep = np.flatnonzero((sb > 0) & ((sa >= MIN_COUNTS_PERTURBATION) | (sb >= MIN_COUNTS_CONTROL)))
+    names = np.array([_str(gene_names[g]) for g in keep], dtype=object)
+    name_rank = np.unique(names, return_inverse=True)[1] if len(keep) else np.zeros(0, np.int64)
+    fc, adj = result["log2_fold_change"][keep], result["adjusted_p_values"][keep]
+    order = np.lexsort((name_rank, adj, -np.abs(fc)))[:num_genes]
+    return [(_str(gene_names[keep[i]]), _str(gene_ids[keep[i]]), float(fc[i]), float(adj[i])) for i in order]
+
+
+def measure_perturbations(ctx, m, gene_ids, gene_names, feature_ref, calls, barcodes, by_feature=False, ignore_multiples=False, num_bootstraps=500,
+                          seed=0, ci=(5.0, 95.0)):
+    """MEASURE_PERTURBATIONS (join() of the stage, get_perturbation_efficiency, _analyze_transcriptome, _get_log2_fold_change): m = the
+    filtered MatrixDev restricted to the Gene Expression rows (Context.select_features_dev), gene_ids / gene_names = its rows,
+    feature_ref / calls / barcodes as perturbation_clusters.  None where the reference writes nothing: a feature reference without
+    target_gene_id or without a Non-Targeting target, no Non-Targeting cell.  A perturbation is tested when its name is not in the
+    filter list, not all of its targets are, and it has at least 10 cells.  ONE plan (Context.sseq_pairs): the tested perturbations
+    and the control are its groups, every other cell is in none; SseqPairs.compare([p], [control]) per perturbation; ONE
+    SseqPairs.bootstrap for all (perturbation, target) items, stream = the item's ordinal; perturbation_ci per item.
+    -> dict(log2_fold_change {name: {target: (log2 fc, p, sum_a, sum_b)}}, log2_fold_change_ci {name: {target: (lower, upper)}},
+    num_cells_per_perturbation, results_per_perturbation {name: the pair's dict}, results_all_perturbations f64[G, 3 k] (sum_a /
+    cells -- raw, not normalised, as the reference --, log2 fold change, adjusted p), cluster_names, summary (the rows of
+    construct_perturbation_efficiency_summary, ascending by log2 fold change, the UNADJUSTED p), summary_columns,
+    top_perturbed_genes {name: rows}, items, cluster_per_bc, perturbation_keys, plan_ms, pairs_ms, bootstrap_ms, ci_ms, total_ms)"""
+    t_all = time.perf_counter()
+    feature_ref = list(feature_ref)
+    if any("target_gene_id" not in row for row in feature_ref) or "Non-Targeting" not in [row["target_gene_id"] for row in feature_ref]:
+        return None
+    gene_ids, gene_names = [_str(g) for g in gene_ids], [_str(g) for g in gene_names]
+    G = len(gene_ids)
+    info = perturbation_target_info(feature_ref)
+    if by_feature:
+        id_of_name = {x: info[x]["target_id"] for x in info}
+    else:
+        id_of_name = {info[x]["target_name"]: info[x]["target_id"] for x in info}
+    cluster_per_bc, keys = perturbation_clusters(feature_ref, calls, barcodes, by_feature, ignore_multiples)
+    if len(cluster_per_bc) != m.n_barcodes:
+        raise ValueError("measure_perturbations: one barcode per column of the matrix")
+    num_cells = {name: int(np.sum(cluster_per_bc == cluster)) for cluster, name in keys.items()}
+    nt = [c for c in keys if keys[c] == "Non-Targeting"]
+    if not nt:
+        return None
+    tested = []     # (cluster, name, target names, target ids)
+    for cluster, name in keys.items():
+        if name in PERTURBATION_FILTER_LIST:
+            continue
+        t_names = name.split("|")
+        t_ids = [id_of_name[p] for p in t_names]
+        if all(x in PERTURBATION_FILTER_LIST for x in t_ids) or int(np.sum(cluster_per_bc == cluster)) < MIN_NUMBER_CELLS_PER_PERTURBATION:
+            continue
+        tested.append((cluster, name, t_names, t_ids))
+    T = len(tested)
+    if T > _lib.SSEQ_MAX_K - 1:
+        raise ValueError("measure_perturbations: %d tested perturbations, one plan holds at most %d and the control" % (T, _lib.SSEQ_MAX_K - 1))
+    times = dict(plan_ms=0.0, pairs_ms=0.0, bootstrap_ms=0.0, ci_ms=0.0)
+    fold_change, fold_change_ci, per_perturbation = {}, {}, collections.OrderedDict()
+    all_de = np.zeros((G, 3 * T))
+    items, item_keys = [], []
+    if T:
+        groups = np.full(len(cluster_per_bc), -1, np.int32)
+        for j, (cluster, _, _, _) in enumerate(tested):
+            groups[cluster_per_bc == cluster] = j
+        groups[cluster_per_bc == nt[0]] = T
+        t0 = time.perf_counter()
+        pairs = ctx.sseq_pairs(m, groups, n_groups=T + 1, n_features=G)
+        times["plan_ms"] = (time.perf_counter() - t0) * 1e3
+        try:
+            t0 = time.perf_counter()
+            for j, (cluster, name, t_names, t_ids) in enumerate(tested):
+                r = pairs.compare([j], [T])
+                per_perturbation[name] = r
+                all_de[:, 3 * j] = r["sums_a"] / float(r["n_cells_a"])
+                all_de[:, 3 * j + 1], all_de[:, 3 * j + 2] = r["log2_fold_change"], r["adjusted_p_values"]
+                fold_change[name], fold_change_ci[name] = {}, {}
+                for t_name, target in zip(t_names, t_ids):
+                    if target in PERTURBATION_FILTER_LIST or target not in gene_ids:      # _get_ko_per_target: no such gene
+                        continue
+                    g = gene_ids.index(target)
+                    fold_change[name][t_name] = (float(r["log2_fold_change"][g]), float(r["p_values"][g]), int(r["sums_a"][g]), int(r["sums_b"][g]))
+                    items.append((g, j, T, len(items)))
+                    item_keys.append((name, t_name))
+            times["pairs_ms"] = (time.perf_counter() - t0) * 1e3
+            if items:
+                t0 = time.perf_counter()
+                sums_a, sums_b = pairs.bootstrap(items, n_bootstraps=num_bootstraps, seed=seed)
+                times["bootstrap_ms"] = (time.perf_counter() - t0) * 1e3
+                t0 = time.perf_counter()
+                for i, (name, t_name) in enumerate(item_keys):
+                    r = per_perturbation[name]
+                    lo, hi, _ = perturbation_ci(sums_a[i], sums_b[i], r["s_a"], r["s_b"], ci[0], ci[1])
+                    fold_change_ci[name][t_name] = (lo, hi)
+                times["ci_ms"] = (time.perf_counter() - t0) * 1e3
+        finally:
+            pairs.free()
+    columns = list(PERTURBATION_EFFICIENCY_SUMMARY_COLUMNS)
+    columns[1] = "Target Guide" if by_feature else "Target Gene"
+    control_cells = num_cells["Non-Targeting"]
+    rows = []
+    for key in sorted(fold_change):
+        n = num_cells[key]
+        for ps, res in fold_change[key].items():
+            lo, hi = fold_change_ci[key][ps]
+            rows.append((key, ps, res[0], res[1], lo, hi, n, _robust_divide(res[2], n), control_cells, _robust_divide(res[3], control_cells)))
+    rows.sort(key=lambda row: row[2])      # a stable sort; pandas' default breaks ties in no stated order
+    top = {name: top_perturbed_genes(r, gene_ids, gene_names) for name, r in per_perturbation.items()}
+    out = dict(log2_fold_change=fold_change, log2_fold_change_ci=fold_change_ci, num_cells_per_perturbation=num_cells,
+               results_per_perturbation=per_perturbation, results_all_perturbations=all_de, cluster_names=[t[1] for t in tested], summary=rows,
+               summary_columns=columns, top_perturbed_genes=top, items=items, cluster_per_bc=cluster_per_bc, perturbation_keys=keys)
+    out.update(times, total_ms=(time.perf_counter() - t_all) * 1e3)
+    return out
+
+
+def write_perturbation_efficiencies_csv(path, result):
+    """perturbation_efficiencies.csv as the stage's join() writes it: the summary rows under their columns"""
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f, lineterminator="\n")
+        w.writerow(result["summary_columns"])
+        for row in result["summary"]:
+            w.writerow(list(row))
+
+
+def write_transcriptome_analysis_csv(path, result, gene_ids, gene_names):
+    """transcriptome_analysis.csv (save_differential_expression_csv with cluster_names): per gene its id, its name and per tested
+    perturbation the mean counts, the log2 fold change and the adjusted p value"""
+    header = differential_expression_header(len(result["cluster_names"]), result["cluster_names"])
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f, lineterminator="\n")
+        w.writerow(header)
+        for g, row in enumerate(result["results_all_perturbations"].tolist()):
+            w.writerow([_str(gene_ids[g]), _str(gene_names[g])] + row)
+
+
+def write_top_perturbed_genes_csv(path, result):
+    """top_perturbed_genes.csv: per tested perturbation four columns "Perturbation: <name>, <column>", the rows of top_perturbed_genes"""
+    names = [n for n, rows in result["top_perturbed_genes"].items() if rows]
+    header = ["Perturbation: %s, %s" % (n, c) for n in names for c in TOP_GENES_SUMMARY_COLUMNS]
+    depth = max([len(result["top_perturbed_genes"][n]) for n in names] or [0])
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f, lineterminator="\n")
+        w.writerow(header)
+        for i in range(depth):
+            row = []
+            for n in names:
+                rows = result["top_perturbed_genes"][n]
+                row += list(rows[i]) if i < len(rows) else [""] * 4
+            w.writerow(row)
 
 
 def call_antibodies(ctx, filtered, rows, ids, n_features=None, feature_bc_name="antibody", report_prefix="ANTIBODY_"):

@@ -1663,7 +1663,8 @@ int crgpu_jibes_fit_dev(crgpu_ctx *ctx, const double *y, uint64_t n, uint32_t k,
  *   crgpu_marginal_seed_draws    test hook, not a stable interface: u_out f64[30] = per init the double of choice() and the two of the
  *                                trial candidates under RandomState(0); first_cell_out u64[10] = the cells choice(V, p = uniform) gives
  * NOT covered: the CSV / JSON writers; the Poisson and "measurable" columns of the n-let frequency table and the efficiency metrics
- * built on them; MEASURE_PERTURBATIONS; median and standard deviation of the UMIs per call group. */
+ * built on them; median and standard deviation of the UMIs per call group.  (MEASURE_PERTURBATIONS, the stage that uses the guide calls,
+ * is the section of that name below.) */
 #define CRGPU_MC_INITS 10
 #define CRGPU_MC_SKIPPED 0u
 #define CRGPU_MC_FITTED 1u
@@ -1825,7 +1826,8 @@ int crgpu_kmeans_seed_draws(uint32_t seed, uint64_t n, uint32_t k, double *u_out
  *   outside 1 .. n_clusters, an empty cluster, parameters of a matrix of another shape
  * NOT covered: get_local_sseq_params and the pairwise comparisons of MEASURE_PERTURBATIONS, the H5 and CSV writers, PCA, parity with
  * the diff_exp crate.  (That holds for THESE entry points; the parameters of two groups of cells alone and the test of one group
- * against the other are crgpu_sseq_pair_dev of the MERGE_CLUSTERS section below.) */
+ * against the other are crgpu_sseq_pair_dev of the MERGE_CLUSTERS section below, and the MEASURE_PERTURBATIONS section behind it
+ * runs that test per perturbation.) */
 #define CRGPU_SSEQ_MAX_K 4096
 struct crgpu_sseq_args {
     uint32_t n_features;   /* G: the rows of the matrix (crgpu_sseq_diffexp_dev: 0 or the G of the parameters) */
@@ -1929,8 +1931,8 @@ int crgpu_sseq_adjust_bh(const double *p, uint64_t n, double *q_out);
  *                                With equal distances the pair with the smallest (height, id0, id1) is merged first; scipy's
  *                                nearest-neighbour-chain order is NOT reproduced there.  O(K^2) memory; a cached nearest neighbour per
  *                                cluster keeps the usual case at O(K^2) time.
- * NOT covered: the MEASURE_PERTURBATIONS stage itself (crgpu_sseq_pair_dev is its primitive), several pairs in one pass, the H5 and
- * CSV writers, float32, parity with scan_rs or the diff_exp crate, whose sources are not in the reference tree. */
+ * NOT covered: several pairs in one pass, the H5 and CSV writers, float32, parity with scan_rs or the diff_exp crate, whose sources
+ * are not in the reference tree.  (The MEASURE_PERTURBATIONS stage, whose primitive crgpu_sseq_pair_dev is, has the next section.) */
 struct crgpu_sseq_pair_args {
     uint32_t n_features;   /* G: the rows of the matrix (crgpu_sseq_pair_dev: 0 or the G of the plan) */
     uint32_t wave_min;     /* the class thresholds of the exact tests, as crgpu_sseq_args; they change no bit */
@@ -1969,6 +1971,68 @@ int crgpu_sseq_pair_dev(crgpu_ctx *ctx, const crgpu_sseq_pairs *pairs, const uin
 int crgpu_cluster_medians_dev(crgpu_ctx *ctx, const double *x, uint64_t n, uint32_t d, uint64_t ld, const int32_t *labels,
                               uint32_t n_clusters, double *medians_out, uint64_t *sizes_out);
 int crgpu_linkage_complete(const double *points, uint32_t k, uint32_t d, double *z_out);
+
+/* ---- MEASURE_PERTURBATIONS: every perturbation against the Non-Targeting cells, bootstrap confidence intervals ----------------------
+ * mro/rna/stages/feature/measure_perturbations/__init__.py with lib/python/cellranger/feature/crispr/measure_perturbations.py: the
+ * cells are grouped by the target (or the guide) of their protospacer calls, every group of at least 10 cells is tested against the
+ * Non-Targeting cells with local sSeq parameters (_analyze_transcriptome, :342-459 -- crgpu_sseq_pair_dev of one plan whose groups are
+ * the tested perturbations and the control), and for every (perturbation, target gene) _get_fold_change_cis (:504-540) draws 500
+ * bootstrap samples: both sides' cells resampled with replacement, the target gene summed over each resample, the 5th and 95th
+ * percentile of the log2 fold changes.  The grouping, the loop over the perturbations, the summary and the top genes are host code
+ * (cellranger_amd.engine.perturbation_clusters / measure_perturbations); the two primitives are below.
+ *   crgpu_sseq_pair_bootstrap_dev  items[i] = (gene, group_a, group_b, stream); sums_a_out[i * B + b] = the sum of the gene over draw
+ *                                b's resample of the cells of group_a, sums_b_out the same for group_b; host u64[n_items x B] each, B =
+ *                                n_bootstraps (0 = 500).  EACH SIDE IS ONE GROUP OF THE PLAN: all the stage needs (a perturbation
+ *                                and the control are a group each); a side of several groups, as crgpu_sseq_pair_dev takes, is not
+ *                                offered.
+ *                                THE STREAM: the reference calls the unseeded global np.random.choice, so its stream is NOT
+ *                                reproduced (there is none to reproduce).  A side's n cells take the positions 0 .. n - 1 in the
+ *                                plan's (group, cell) order.  Position q of draw b of side z (0 = a, 1 = b) takes the cell at index
+ *                                __umul64hi(w, n), w = word q & 3 of Philox4x64-10(counter = (1 + (q >> 2), s, 0, 0), key = (seed,
+ *                                0)), s = ((uint64)stream << 33) | ((uint64)z << 32) | b: element q of np.random.Philox(counter=[0, s,
+ *                                0, 0], key=[seed, 0]).random_raw(), the convention of EmptyDrops and the subsampling.  The
+ *                                multiply-high is biased by less than n / 2^64.  The result is a pure function of (plan, item,
+ *                                seed, B): it does not depend on what else is in the batch, on lds_cells or on draws_per_wg, and,
+ *                                the sums being integers, not on the order of addition.
+ *                                Work: a wave per DISTINCT (gene, group) writes the gene's run inside the group (two searches, as
+ *                                crgpu_sseq_pair_dev) as a dense u32 column, every word once -- a control column is gathered once per
+ *                                target gene, not once per item.  A 256-thread workgroup per (item, side, draws_per_wg draws; 0 =
+ *                                8) stages the column into LDS when the side has at most lds_cells cells (0 = 16384 = 64 KiB, at most
+ *                                40960 = 160 KiB; 1 forces the global path for every side of two cells or more: a seam for tests)
+ *                                and reads it from global memory otherwise; a wave takes whole draws, a lane whole Philox blocks; u64
+ *                                sums, no atomics.
+ *                                Refused with CRGPU_EINVAL before any device work: a NULL argument, n_items == 0, a gene >= the
+ *                                plan's G, a group >= n_groups, group_a == group_b, n_bootstraps > 65536, lds_cells > 40960.
+ *   crgpu_perturbation_ci        host only, no context: log2fc[b] = log2((1 + A_b) / (1 + s_a)) - log2((1 + B_b) / (1 + s_b)), then
+ *                                np.percentile(log2fc, ci_lower) and (..., ci_upper) with the linear rule (the reference: 5 and 95).
+ *                                QUIRK kept (measure_perturbations.py:527-528): s_a and s_b are the sums of the size factors of
+ *                                the ORIGINAL cells of each side -- s_a and s_b of crgpu_sseq_pair_result -- not of the resampled
+ *                                cells.  log2fc_out f64[B] (NULL = not wanted) is in draw order.  Refused: a NULL array or bound,
+ *                                n_bootstraps outside 1 .. 65536, a size factor sum that is negative or not finite, a percentile
+ *                                outside 0 .. 100.
+ * Deviations of the host stage: the stream (above); a multi-guide cell's targets are joined in SORTED order where the reference joins
+ * list(set(...)), whose order depends on the hash seed of the process.
+ * NOT covered: the reference's random stream, a bootstrap side of several groups, the H5 writer of the tables (the CSV tables are
+ * written by cellranger_amd.engine), more than CRGPU_SSEQ_MAX_K - 1 tested perturbations in one call, float32. */
+struct crgpu_pb_item {
+    uint32_t gene;         /* the row whose counts are summed */
+    uint32_t group_a;      /* the resampled group of side a */
+    uint32_t group_b;      /* that of side b, another group */
+    uint32_t stream;       /* the item's random stream: the caller numbers its items below 2^31 (bit 31 is shifted out of s) */
+};
+typedef struct crgpu_pb_item crgpu_pb_item;
+struct crgpu_pb_args {
+    uint32_t n_bootstraps; /* B; 0 = 500, at most 65536 */
+    uint32_t lds_cells;    /* a side of at most this many cells is staged in LDS; 0 = 16384, at most 40960; changes no bit */
+    uint32_t draws_per_wg; /* draws of one workgroup; 0 = 8; changes no bit */
+    uint32_t reserved;
+    uint64_t seed;
+};
+typedef struct crgpu_pb_args crgpu_pb_args;
+int crgpu_sseq_pair_bootstrap_dev(crgpu_ctx *ctx, const crgpu_sseq_pairs *pairs, const crgpu_pb_item *items, uint32_t n_items,
+                                  const crgpu_pb_args *args, uint64_t *sums_a_out, uint64_t *sums_b_out);
+int crgpu_perturbation_ci(const uint64_t *sums_a, const uint64_t *sums_b, uint32_t n_bootstraps, double s_a, double s_b, double ci_lower,
+                          double ci_upper, double *log2fc_out, double *lower_out, double *upper_out);
 
 /* ---- exact k-nearest-neighbour graph of a dense projection: the query of RUN_GRAPH_CLUSTERING ---------------------------------------
  * stages/analyzer/run_graph_clustering/__init__.py: split() fixes the number of neighbours and cuts the rows into chunks of 15 000,

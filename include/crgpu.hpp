@@ -1438,12 +1438,34 @@ public:
         o.n_exact = r.n_exact, o.n_asymptotic = r.n_asymptotic, o.n_terms = r.n_terms, o.n_de = r.n_de, o.n_used = r.n_used;
         return o;
     }
+    /// crgpu_sseq_pair_bootstrap_dev: per item and draw the sum of the item's gene over a resample of group_a / of group_b
+    /// -> (sums_a, sums_b), u64[items x B] each (B = n_bootstraps, 0 = 500); the stream is Philox, not the reference's np.random
+    std::pair<std::vector<uint64_t>, std::vector<uint64_t>> bootstrap(const std::vector<crgpu_pb_item> &items, uint32_t n_bootstraps = 0, uint64_t seed = 0,
+                                                                      uint32_t lds_cells = 0, uint32_t draws_per_wg = 0) const {
+        const size_t B = n_bootstraps ? n_bootstraps : 500;
+        std::vector<uint64_t> sa(items.size() * B), sb(items.size() * B);
+        crgpu_pb_args a = {n_bootstraps, lds_cells, draws_per_wg, 0, seed};
+        ctx_.check(crgpu_sseq_pair_bootstrap_dev(ctx_.get(), p_, items.data(), (uint32_t)items.size(), &a, sa.data(), sb.data()));
+        return {std::move(sa), std::move(sb)};
+    }
 
 private:
     Context &ctx_;
     crgpu_sseq_pairs *p_ = nullptr;
     uint32_t n_features_;
 };
+// ---- MEASURE_PERTURBATIONS: the bootstrap sums (SseqPairs::bootstrap above) and the confidence interval --------------------------------
+static_assert(sizeof(crgpu_pb_item) == 16, "crgpu_pb_item changed: bump CRGPU_ABI_VERSION and every binding");
+static_assert(sizeof(crgpu_pb_args) == 24, "crgpu_pb_args changed: bump CRGPU_ABI_VERSION and every binding");
+/// crgpu_perturbation_ci (host only): the percentiles ci_lower / ci_upper of the draws' log2 fold changes; s_a, s_b = those of the pair
+inline std::pair<double, double> perturbation_ci(const uint64_t *sums_a, const uint64_t *sums_b, uint32_t n_bootstraps, double s_a, double s_b,
+                                                 double ci_lower = 5.0, double ci_upper = 95.0, std::vector<double> *log2fc = nullptr) {
+    if (log2fc) log2fc->assign(n_bootstraps, 0.0);
+    double lo = 0.0, hi = 0.0;
+    const int rc = crgpu_perturbation_ci(sums_a, sums_b, n_bootstraps, s_a, s_b, ci_lower, ci_upper, log2fc ? log2fc->data() : nullptr, &lo, &hi);
+    if (rc != CRGPU_OK) throw Error(rc, "crgpu_perturbation_ci");
+    return {lo, hi};
+}
 /// crgpu_cluster_medians_dev: np.median of every dimension over the rows of every cluster (labels 0 .. n_clusters - 1) -> [n_clusters][d]
 inline std::vector<double> cluster_medians(Context &ctx, const std::vector<double> &x, uint64_t n, uint32_t d, const std::vector<int32_t> &labels,
                                            uint32_t n_clusters) {
